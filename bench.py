@@ -5,7 +5,7 @@ One "step" = one fused forward (encoder -> 3 S5 layers -> decoder, int32 in -> i
 batch of synthetic NDNS-shaped sequences that is already resident in HBM.  Workload = BASELINE.json
 configs[1]: B=32 sequences x L=4096 frames per GPU, dense (un-pruned) w8a16.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config 1|2|3|4]
+  python bench.py [--gpus N --steps K --warmup W] [--config 1|2|3|4] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (what the driver does)
 
 With --gpus N > 1 and no launcher (WORLD_SIZE unset) the script starts the N ranks itself: fresh child processes,
@@ -31,6 +31,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BYTES = 48 << 20  # --dump-outputs: at most this much of float64 output (below the 64 MB cap with room for the header)
 
 
 def pmc_traffic(B, L, P, kernel, groups, slots):
@@ -114,7 +115,13 @@ def main() -> None:
                     help="skip the extra pass of plain one-batch forwards (profiling runs that want only the grouped launches)")
     ap.add_argument("--self-contained", action="store_true",
                     help="enqueue the gated exact re-run kernels with every forward (no status check needed)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output of the last timed step as DIR/y.npy (float64, the values "
+                         "y * 2^-out_exp a caller of the forward receives; rank 0's batch; a fixed, seeded sample of frames "
+                         "when the whole output exceeds 48 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     preset = {1: (0.5, 0.0, "w8a16", 32), 2: (0.5, 0.9, "w8a16", 32), 3: (1.0, 0.9, "w8a16", 512), 4: (1.0, 0.0, "w4a8", 32)}[args.config]
     args.dim_scale = preset[0] if args.dim_scale is None else args.dim_scale
     args.sparsity = preset[1] if args.sparsity is None else args.sparsity
@@ -319,6 +326,20 @@ def main() -> None:
     sync_all()
     dt = time.perf_counter() - t0
     st0 = check_all(depth)
+
+    # ---- --dump-outputs: the output of the last timed step (batch K - 1: the last group of the last launch set, on lane
+    # (sets - 1) % depth), taken now, before the passes below reuse the output buffers.  Its input is the same in every run
+    # with the same arguments (seeded synthetic model and batches), so two builds can be compared output for output.
+    if args.dump_outputs and rank == 0:
+        sets = n_sets(args.steps, G)
+        gk = args.steps - (sets - 1) * G
+        y_last = ys[0 if depth == 1 else (sets - 1) % depth][(gk - 1) * B:gk * B].reshape(B * L, -1)
+        rows, row_bytes = B * L, y_last.shape[1] * 8
+        if rows * row_bytes > DUMP_BYTES:  # a fixed, seeded sample of frames, in order
+            keep = np.sort(np.random.default_rng(0).choice(rows, DUMP_BYTES // row_bytes, replace=False))
+            y_last = y_last[torch.from_numpy(keep).to(dev)]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "y.npy"), y_last.cpu().numpy().astype(np.float64) / 2.0 ** eng.out_exp)
 
     # ---- the same K steps one launch set at a time (no overlap between sets), for reference; not the headline
     single, ev1, evg = None, None, None

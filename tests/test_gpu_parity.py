@@ -930,6 +930,48 @@ def test_bench_starts_its_own_ranks(tmp_path):
     assert bad.returncode != 0 and "WORLD_SIZE=3" in (bad.stdout + bad.stderr)
 
 
+def test_bench_dump_outputs_is_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the output of the last timed step, as floats, equal to the C oracle's run of
+    that step's batch: step K - 1 is group (K - 1) % G of the last launch set, on lane (sets - 1) % inflight, whose
+    batches are pool[(lane + g) % max(G, inflight)] of the seeded inputs.  The small case dumps the whole output; the
+    larger one exceeds the size cap and dumps a fixed, seeded sample of frames."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from sparsernns_amd.fxparray import RoundingMode, fxp_from_fp
+    from sparsernns_amd.fxpmodel import build_regression_model
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    md, qc, dims = _make(dict(dim_scale=0.5, quantization="w8a16", sparsity=0.0, calib_L=1024, state_headroom_bits=1,
+                              input_scale=1.0))   # bench.py's configs[1] model
+    cm = cref.CModel(build_regression_model(md, qc, dims["n_layers"]).export())
+    for B, L, steps, G, depth in ((2, 256, 5, 2, 3), (32, 1024, 11, 8, 3)):
+        out = tmp_path / f"dump_{B}x{L}"
+        args = ["--batch", str(B), "--seq-len", str(L), "--steps", str(steps), "--warmup", "1", "--groups", str(G),
+                "--inflight", str(depth), "--no-cpu-baseline", "--no-scan-sweep", "--dump-outputs", str(out)]
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args, cwd=root, capture_output=True, text=True,
+                           timeout=900)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        sets = (steps + G - 1) // G
+        lane, g = (sets - 1) % depth, (steps - 1) % G
+        x = synth.make_input(B, L, dims["d_in"], seed=1000 + 4096 * ((lane + g) % max(G, depth)), scale=1.0)
+        fx = fxp_from_fp(x, bits=qc["encoder"]["inp_bits"], exp=qc["encoder"]["inp_exp"], signed=True, round_mode=RoundingMode.FLOOR)
+        ref, _, re_, _ = cm.forward(fx.numpy(), fx.bits, fx.exp)
+        want = ref.reshape(B * L, -1).astype(np.float64) / 2.0 ** re_
+        files = os.listdir(out)
+        assert files == ["y.npy"] and os.path.getsize(out / "y.npy") <= 64 << 20
+        got = np.load(out / "y.npy")
+        assert got.dtype == np.float64
+        if want.nbytes > 48 << 20:
+            keep = np.sort(np.random.default_rng(0).choice(B * L, (48 << 20) // want[0].nbytes, replace=False))
+            want = want[keep]
+        assert got.shape == want.shape and np.array_equal(got, want)
+
+
 def test_pair_recurrence_kernel_is_selected_and_guarded():
     """The optimistic forward of the NDNS models runs the pair kernel (two lanes per state, Bu folded into the multiply's
     addend: csrc/scan_quad.hpp).  Its exactness bound on |state| is tighter than the quad kernel's; inputs scaled so that
