@@ -323,7 +323,7 @@ struct ModelCfg {
     bool no_dec_resid = false; // S5FXP_NO_DEC_RESID: the last layer's residual pass as its own launch (proj_p.hpp k_dec_p<.., RESID>)
     int pairl_blocks = 32;    // S5FXP_PAIRL_BLOCKS=16: 16 time blocks per LDS buffer of the LDS-fed pair kernel
     size_t plane_skew = 0;    // S5FXP_PLANE_SKEW=<bytes, multiple of 256>: extra distance between the workspace's planes (experiments)
-    int64_t cap_enc = 512, cap_dec = 512, cap_cgate = 512, cap_bproj = 1024, cap_resid = 512; // S5FXP_WGS_*: workgroups per launch
+    int64_t cap_enc = 512, cap_dec = 512, cap_cgate = 512, cap_bproj = 1024, cap_resid = 512; // S5FXP_WGS_ENC|DEC|CGATE|BPROJ|RESID: workgroups per launch
     static ModelCfg from_env()
     {
         ModelCfg c;

@@ -554,7 +554,7 @@ int forward_fast(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, 
 #endif
             {
                 a.t_lo = 0; a.t_len = L;
-                const int64_t tl = (int64_t)B * ((a.t_len + 63) / 64), cap = big ? cap_bproj / 2 : cap_bproj, per = (tl + cap - 1) / cap;
+                const int64_t tl = (int64_t)B * ((a.t_len + 63) / 64), cap = big ? std::max<int64_t>(cap_bproj / 2, 1) : cap_bproj, per = (tl + cap - 1) / cap;
                 const unsigned bthr = big ? 512 : 256; // one wave per 32-column tile of [B_re | B_im]
                 const unsigned pgrid = (unsigned)((tl + per - 1) / per);
                 // SM: the stream the recurrence rung wants (proj_p.hpp); a compacted layer has half the column tiles

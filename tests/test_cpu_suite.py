@@ -596,3 +596,92 @@ def test_hand_written_wait_counts_match_the_compiled_store_counts():
     import sys
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_vmwait.py")], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
+
+
+def _switch_names(text: str) -> set:
+    """S5FXP_* names in `text`, with the header's 'S5FXP_WGS_ENC|DEC|...' shorthand expanded."""
+    out = set()
+    for m in re.finditer(r"S5FXP_([A-Z0-9_]*[A-Z0-9])((?:\|[A-Z0-9]+)*)", text):
+        out.add("S5FXP_" + m.group(1))
+        if m.group(2):
+            stem = "S5FXP_" + m.group(1).rsplit("_", 1)[0] + "_"
+            out.update(stem + s for s in m.group(2).split("|")[1:])
+    return out
+
+
+def test_switch_names_agree_between_library_header_and_scripts():
+    """The S5FXP_* environment switches the library reads (getenv in csrc/), the ones include/s5fxp.h lists under
+    "Environment" and the ones ModelCfg documents must be the same set; every S5FXP_* name a script or test under tools/ or
+    tests/ mentions must be one the library or the Python side reads, or a C-ABI identifier of the header.  A stale name
+    (a switch that was renamed or removed) silently tests nothing."""
+    import glob
+    csrc = os.path.join(ROOT, "sparsernns_amd", "csrc")
+    src = "".join(open(f).read() for f in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.hpp"))))
+    read = set(re.findall(r'getenv\("(S5FXP_[A-Z0-9_]+)"\)', src)) | set(re.findall(r'(?:on|cap)\("(S5FXP_[A-Z0-9_]+)"', src))
+    header = open(os.path.join(ROOT, "include", "s5fxp.h")).read()
+    env = re.search(r"/\* Environment .*?\*/", header, re.S).group(0)
+    cfg = re.search(r"struct ModelCfg \{.*?static ModelCfg from_env", src, re.S).group(0)
+    assert read and read == _switch_names(env), (sorted(read - _switch_names(env)), sorted(_switch_names(env) - read))
+    assert read == _switch_names(cfg), (sorted(read - _switch_names(cfg)), sorted(_switch_names(cfg) - read))
+    py_files = [os.path.join(ROOT, "bench.py")] + glob.glob(os.path.join(ROOT, "sparsernns_amd", "*.py")) + \
+        glob.glob(os.path.join(ROOT, "tools", "*.py"))
+    py_read = set()
+    for f in py_files:
+        py_read |= set(re.findall(r'(?:environ\.get\(|environ\[|getenv\()\s*"(S5FXP_[A-Z0-9_]+)"', open(f).read()))
+    assert {"S5FXP_LIB", "S5FXP_BENCH_BACKEND"} <= py_read, py_read
+    c_api = set(re.findall(r"\b(S5FXP_[A-Z0-9_]+)\b", re.sub(r"/\*.*?\*/", "", header, flags=re.S)))
+    known = read | py_read | c_api
+    stale = {}
+    for f in sorted(glob.glob(os.path.join(ROOT, "tools", "*.sh")) + glob.glob(os.path.join(ROOT, "tools", "*.py")) +
+                    glob.glob(os.path.join(ROOT, "tests", "*.py"))):
+        if os.path.abspath(f) == os.path.abspath(__file__):
+            continue
+        text = open(f).read()
+        names = set(re.findall(r"\bS5FXP_[A-Z0-9_]*[A-Z0-9]\b", text))
+        prefixes = set(re.findall(r"\b(S5FXP_[A-Z0-9_]*_)\$", text))   # S5FXP_WGS_$k in a loop
+        bad = sorted(n for n in names if n not in known) + sorted(p for p in prefixes if not any(k.startswith(p) for k in read))
+        if bad:
+            stale[os.path.relpath(f, ROOT)] = bad
+    assert not stale, stale
+    # the switch settings of the variant matrix are built from parts (S5FXP_WGS_{k}): check the names they come to
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("variant_matrix", os.path.join(ROOT, "tests", "test_variant_matrix.py"))
+    vm = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(vm)
+    used = {k for sw in vm.SWITCHES.values() for k in sw}
+    assert used and used <= read, sorted(used - read)
+    assert read <= used, sorted(read - used)   # and every switch the library reads has a row
+
+
+_HIDDEN_FRAGMENT = """\
+_ZN2s56k_testEv:
+\ts_load_dwordx2 s[2:3], s[0:1], 0x0
+.LBB0_1:
+\t;;#ASMSTART
+\tglobal_load_dwordx4 v[4:7], v1, s[2:3]
+\t;;#ASMEND
+\tglobal_store_dword v2, v3, s[2:3]
+{early}\ts_cbranch_scc1 .LBB0_3
+.LBB0_2:
+\t;;#ASMSTART
+\ts_waitcnt vmcnt(1)
+\t;;#ASMEND
+\tv_add_u32_e32 v9, v5, v9
+\ts_branch .LBB0_1
+.LBB0_3:
+\ts_endpgm
+.Lfunc_end0:
+"""
+
+
+@pytest.mark.parametrize("early,ok", [("", True), ("\tv_mov_b32_e32 v10, v5\n", False), ("\tv_mov_b32_e32 v6, 0\n", False)])
+def test_register_audit_rejects_a_prefetch_register_touched_before_its_wait(tmp_path, early, ok):
+    """tools/check_vmwait.py's register audit on a hand-made fragment: a hidden load (inline assembly the compiler cannot see)
+    whose destination is read or overwritten by compiler code before the hand-written wait must be rejected; the same
+    fragment with the first use behind the wait passes."""
+    s = tmp_path / "k.s"
+    s.write_text(_HIDDEN_FRAGMENT.format(early=early))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_vmwait.py"), "--asm", str(s)], capture_output=True,
+                       text=True, timeout=60)
+    assert (r.returncode == 0) == ok, r.stdout + r.stderr
+    assert ("REGISTER TOUCHED BEFORE ITS WAIT" in r.stdout) != ok, r.stdout

@@ -4,7 +4,18 @@ by hand, scan_quad.hpp vm_wait) are only right while the compiler issues exactly
 taken from: N stores per wave on a full tile, the same number again on the guarded path of a partial tile.  If a later
 compiler merged or split those stores, vm_wait<N> would return before the prefetch has landed.  This compiles the device
 code to assembly (no GPU needed) and checks, per kernel, that the hand-written wait is there and that the kernel holds
-2 x N tile stores (+ the few prologue stores).  Exit code 0 = consistent."""
+2 x N tile stores (+ the few prologue stores).
+
+The same loads break in a second way: the compiler does not know their destination registers are being written, so it may
+copy, spill or reuse them before the data has landed.  The register audit follows every hidden load (a global_load inside
+;;#ASMSTART / ;;#ASMEND) through the control-flow graph -- the loop's back edge included, since the prefetch at the end of a
+tile is waited for at the top of the next -- to the wait that guards it (the hand-written s_waitcnt vmcnt(N), or a compiler wait
+that leaves no more memory operations outstanding than were issued after the load), and fails if an instruction outside the inline-assembly blocks reads or writes one of its destination VGPRs on the
+way.  It also reports .private_segment_fixed_size and .vgpr_spill_count of every kernel with hidden loads.  It audits
+every kernel of the default build that has hidden loads (today k_enc_p, k_dec_p and the pair recurrence kernels); the gate
+kernel's gload8_hidden prefetches exist only in the -DS5_CGATE_HID=1 experiment build, which this script does not compile.
+  python tools/check_vmwait.py [--asm FILE.s]    (--asm: audit a given assembly file instead of compiling the library)
+Exit code 0 = consistent."""
 import os
 import re
 import subprocess
@@ -21,7 +32,106 @@ EXPECT = {
 }
 
 
-def main() -> int:
+_VMEM = re.compile(r"^(global|buffer|flat|scratch)_(load|store|atomic)")
+_WAIT = re.compile(r"s_waitcnt\b.*\bvmcnt\((\d+)\)")
+
+
+def _vregs(operands: str) -> set:
+    """VGPR numbers named in an operand string: v7, v[4:7]."""
+    out = set()
+    for a, b in re.findall(r"\bv\[(\d+):(\d+)\]", operands):
+        out.update(range(int(a), int(b) + 1))
+    out.update(int(v) for v in re.findall(r"(?<![\w\[:])v(\d+)\b", operands))
+    return out
+
+
+def _parse(body: str):
+    """[(kind, text)] of a kernel body: kind 'asm' (inside ;;#ASMSTART/END), 'ins', 'label'; plus label -> index."""
+    items, labels, in_asm = [], {}, False
+    for line in body.split("\n"):
+        t = line.split(";")[0].strip() if not line.strip().startswith(";;#ASM") else line.strip()
+        if t == ";;#ASMSTART":
+            in_asm = True
+        elif t == ";;#ASMEND":
+            in_asm = False
+        elif re.match(r"^[.\w$]+:$", t):
+            labels[t[:-1]] = len(items)
+            items.append(("label", t[:-1]))
+        elif t and not t.startswith("."):
+            items.append(("asm" if in_asm else "ins", t))
+    return items, labels
+
+
+def audit_kernel(body: str):
+    """Violations [(load, offending instruction)] of the hidden loads in one kernel body, and how many hidden loads it has."""
+    items, labels = _parse(body)
+    loads = [i for i, (k, t) in enumerate(items) if k == "asm" and re.match(r"^global_load_dword", t)]
+    bad = []
+    for i in loads:
+        op, rest = (items[i][1].split(None, 1) + [""])[:2]
+        dest = _vregs(rest.split(",")[0])
+        seen, stack = set(), [(i + 1, 0)]
+        while stack:
+            j, n = stack.pop()
+            while j < len(items):
+                key = (j, min(n, 64))
+                if key in seen:
+                    break
+                seen.add(key)
+                kind, t = items[j]
+                w = _WAIT.search(t)
+                if w and (kind == "asm" or n >= int(w.group(1))):
+                    break   # the hand-written wait (its count is checked above), or one that leaves <= n newer operations
+                if kind != "label":
+                    mn = t.split(None, 1)[0]
+                    if kind == "ins" and not mn.startswith("s_") and _vregs(t.split(None, 1)[1] if " " in t else "") & dest:
+                        bad.append((items[i][1], t))
+                    if _VMEM.match(mn):
+                        n += 1
+                    if mn == "s_endpgm":
+                        break
+                    if mn.startswith("s_cbranch") or mn == "s_branch":
+                        tgt = t.split()[-1]
+                        if tgt in labels:
+                            if mn == "s_branch":
+                                j = labels[tgt]
+                                continue
+                            stack.append((labels[tgt], n))
+                j += 1
+    return bad, len(loads)
+
+
+def kernel_meta(text: str) -> dict:
+    """name -> {'.private_segment_fixed_size': .., '.vgpr_spill_count': ..} from the code object metadata."""
+    meta = {}
+    for entry in re.split(r"\n  - ", text[text.find("amdhsa.kernels:"):]):
+        name = re.search(r"^\s*\.name:\s+(\S+)", entry, re.M)
+        if name:
+            meta[name.group(1)] = {k: int(v) for k, v in re.findall(r"^\s*(\.private_segment_fixed_size|\.vgpr_spill_count):\s+(\d+)",
+                                                                   entry, re.M)}
+    return meta
+
+
+def audit(text: str) -> int:
+    """Register audit of every kernel of an assembly file that issues hidden loads; returns the number of violations."""
+    meta = kernel_meta(text)
+    bad = 0
+    for m in re.finditer(r"^(\w+):[^\n]*\n(.*?)^\.Lfunc_end", text, re.S | re.M):
+        viol, n = audit_kernel(m.group(2))
+        if not n:
+            continue
+        km = meta.get(m.group(1), {})
+        print(f"{m.group(1)}: {n} hidden loads, private_segment_fixed_size {km.get('.private_segment_fixed_size', '?')}, "
+              f"vgpr_spill_count {km.get('.vgpr_spill_count', '?')}: {'ok' if not viol else 'REGISTER TOUCHED BEFORE ITS WAIT'}")
+        for load, ins in viol[:8]:
+            print(f"    {load}  <-  {ins}")
+        bad += len(viol)
+    return bad
+
+
+def main(argv) -> int:
+    if len(argv) > 2 and argv[1] == "--asm":
+        return 1 if audit(open(argv[2]).read()) else 0
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "k.s")
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-S",
@@ -40,8 +150,9 @@ def main() -> int:
         ok = waits >= 1 and stores == 2 * n + extra
         print(f"{key}: {stores} stores (expected {2 * n + extra}), {waits} x vmcnt({n}): {'ok' if ok else 'MISMATCH'}")
         bad += 0 if ok else 1
+    bad += audit(text)
     return 1 if bad else 0
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(main(sys.argv))

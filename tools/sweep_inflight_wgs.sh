@@ -15,5 +15,4 @@ run S5FXP_WGS_BPROJ=512
 run S5FXP_WGS_RESID=256
 run S5FXP_WGS_ENC=384 S5FXP_WGS_DEC=384 S5FXP_WGS_CGATE=384 S5FXP_WGS_BPROJ=768 S5FXP_WGS_RESID=384
 run S5FXP_WGS_ENC=768 S5FXP_WGS_DEC=768 S5FXP_WGS_CGATE=768 S5FXP_WGS_BPROJ=2048 S5FXP_WGS_RESID=1024
-run S5FXP_NO_CGATE_DMA=1
 run A=1
