@@ -64,29 +64,6 @@ struct EncArgs {
 };
 
 // ---------------------------------------------------------------------------------------------
-// out2 dense + LUT sigmoid + mult_gate + maxima of the residual compute_best add.
-// fxpmodel.py:1133-1137, 97-144, 1075-1093, 1147-1152.   LDS: [weights][cs128][bias_eff][lut 8]
-// ---------------------------------------------------------------------------------------------
-struct GateMArgs {
-    const int16_t *x1;   // (N,H)
-    const int16_t *skip; // (N,H) layer input
-    int16_t *z;          // (N,H)
-    MfmaW w;
-    const int32_t *bias_eff;
-    int32_t *tr_out2, *tr_sig, *tr_z; // optional int32 traces
-    int64_t N;
-    int32_t H;
-    int32_t y_bits, y_exp, conv, inp_bits, inp_exp, rs, out_bits, out_exp;
-    int32_t sig_x, sig_y;
-    int32_t lut[8];
-    int32_t l_bits, l_exp, r_bits, r_exp, res_bits, res_exp, rs_gate;
-    DynExp skip_e;
-    LayerDyn *dynw;
-    const int32_t *run_if; // exact re-run: do the work only when *run_if != 0 (nullptr: always)
-    int32_t mx_slot;       // first of the three LayerDyn::mx slots that receive the maxima
-};
-
-// ---------------------------------------------------------------------------------------------
 // Decoder: int16 (N,H) with a device-chosen exponent -> int32 (N,M).  fxpmodel.py:1437, 331-366.
 // CG column groups of NT tiles are processed one after the other from the same activation fragments.
 // LDS: [weights][cs128][bias_eff]

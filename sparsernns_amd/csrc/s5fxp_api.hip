@@ -10,6 +10,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -500,6 +501,47 @@ int validate(const s5fxp_model_desc *d)
 constexpr int SCAN_DEPTH = S5_SCANP_ASM_DEPTH;
 static_assert(S5_SCANP_ASM_DEPTH % S5_SCAN_ASM_DEPTH == 0, "one padding rule for all recurrence kernels");
 
+// the recurrence kernels address one (sequence, state group) run of a stream through a 32-bit buffer extent
+inline bool stream_extent_ok(const s5fxp_model *m, int L)
+{
+    return (((int64_t)L + 3) / 4 + 2 * SCAN_DEPTH) * (m->P ? m->P : 1) * 32 < 0xffffffffll;
+}
+
+// BatchNorm arguments of layer l, whose input has hb_in bits and the (device) exponent he_in
+BnArgs make_bn(const LayerDev &l, int hb_in, DynExp he_in, LayerDyn *d)
+{
+    const s5fxp_ssm_desc &s = l.sd;
+    auto mx = [](int a, int b) { return a > b ? a : b; };
+    BnArgs bn{};
+    bn.mm = l.mm; bn.isv = l.isv; bn.scale = l.scale; bn.bias = l.nbias;
+    bn.xb = hb_in; bn.xe = he_in;
+    bn.mb = l.nd.mean_bits; bn.me = l.nd.mean_exp; bn.b1 = mx(hb_in, bn.mb);
+    bn.ib = l.nd.invsq_var_bits; bn.ie = l.nd.invsq_var_exp; bn.b2 = mx(bn.b1, bn.ib);
+    bn.sb = l.nd.scale_bits; bn.se = l.nd.scale_exp; bn.b3 = l.scale ? mx(bn.b2, bn.sb) : bn.b2;
+    bn.bb = l.nd.bias_bits; bn.be = l.nd.bias_exp; bn.b4 = l.nbias ? mx(bn.b3, bn.bb) : bn.b3;
+    bn.ub = s.u_bits; bn.ue = s.u_exp; bn.out_bits = bn.b4; bn.dyn = d;
+    return bn;
+}
+
+// BatchNorm exponents by full reductions, one compute_best op after the other: reduce -> (cross-rank max) -> finalize.
+// reduce(std::integral_constant<int, OP>) launches the reduce kernel of op 1..4 over the layer input (k_bn_reduce on the
+// generic path's int32 planes, k_bn_reduce16 on the fused path's int16 ones).
+template <class Reduce>
+int bn_exponent_ops(Reduce reduce, const BnArgs &bn, LayerDyn *d, int32_t *status, int32_t *st_exps, const s5fxp_forward_opts *opts,
+                    hipStream_t st)
+{
+    const s5fxp_allreduce_max_fn allreduce = opts ? opts->allreduce : nullptr;
+    auto op = [&](auto k, int slot, int n) {
+        reduce(k);
+        if (allreduce && allreduce(opts->allreduce_ctx, reinterpret_cast<float *>(d->mx + slot), n, (void *)st)) return false;
+        hipLaunchKernelGGL(k_bn_finalize<decltype(k)::value>, dim3(1), dim3(64), 0, st, bn, d, status, st_exps);
+        return true;
+    };
+    const bool ok = op(std::integral_constant<int, 1>{}, 0, 3) && op(std::integral_constant<int, 2>{}, 3, 1) &&
+                    (!bn.scale || op(std::integral_constant<int, 3>{}, 4, 1)) && (!bn.bias || op(std::integral_constant<int, 4>{}, 5, 3));
+    return ok ? S5FXP_OK : S5FXP_EHIP;
+}
+
 } // namespace
 
 #include "s5fxp_fast.hpp"
@@ -586,13 +628,11 @@ extern "C" int s5fxp_model_recurrence_xmax(const s5fxp_model *m, int layer)
     const int k = s5fxp_model_recurrence_kernel(m, layer);
     if (k < 0) return -1;
     const LayerDev &l = m->layers[layer];
-    // a plain forward (no traces, no carry) of a compactable layer runs on its live states: their bounds apply
-    const bool compact = m->fast && m->fast->layers[layer].compact_ok && !m->cfg.no_compact;
-    const int32_t pair_xmax = compact ? m->fast->layers[layer].c_bounds.pair_xmax : l.pair_xmax;
-    const int32_t quad_xmax = compact ? m->fast->layers[layer].c_bounds.quad_xmax : l.quad_xmax;
-    if (k >= 3) return pair_xmax;
-    if (k == 2) return quad_xmax < 32766 ? quad_xmax : 32766;
-    return l.quad_ok ? quad_xmax : 0;
+    // the fused path: a plain forward of a compactable layer runs on its live states, and their bounds apply
+    const int32_t bound = m->fast ? plain_plan(m, layer).bound : l.quad_xmax;
+    if (k >= 3) return bound;
+    if (k == 2) return bound < 32766 ? bound : 32766;
+    return l.quad_ok ? bound : 0;
 }
 
 extern "C" int s5fxp_model_recurrence_kernel(const s5fxp_model *m, int layer)
@@ -600,8 +640,8 @@ extern "C" int s5fxp_model_recurrence_kernel(const s5fxp_model *m, int layer)
     if (!m || layer < 0 || layer >= m->n_layers) return -1;
     const LayerDev &l = m->layers[layer];
     if (!m->fast) return l.quad_ok && !(m->flags & S5FXP_MODEL_FORCE_GENERIC) ? 1 : 0;
-    // the fused path: the same decision forward_fast takes (and reports in status word [8 + 8*layer + 5])
-    const int code = select_rung(m, layer, S5FXP_FWD_DEFER_REDO, false, m->fast->layers[layer].compact_ok && !m->cfg.no_compact).code;
+    // the fused path: the plan of a plain forward (reported in status word [8 + 8*layer + 5])
+    const int code = plain_plan(m, layer).rung.code;
     return code == RK_EXACT ? 1 : code; // no fast rung applies: a quad kernel all the same, the 32-bit chain
 }
 
@@ -689,38 +729,14 @@ int generic_layers(const GenericRun &g, int first, int last, int32_t *&h, int32_
         LayerDyn *d = dyn + li;
         int32_t *st_exps = status + 8 + 8 * li;
         const s5fxp_ssm_desc &s = l.sd;
-        auto mx = [](int a, int b) { return a > b ? a : b; };
-
-        BnArgs bn{};
-        bn.mm = l.mm; bn.isv = l.isv; bn.scale = l.scale; bn.bias = l.nbias;
-        bn.xb = hb; bn.xe = he;
-        bn.mb = l.nd.mean_bits; bn.me = l.nd.mean_exp; bn.b1 = mx(hb, bn.mb);
-        bn.ib = l.nd.invsq_var_bits; bn.ie = l.nd.invsq_var_exp; bn.b2 = mx(bn.b1, bn.ib);
-        bn.sb = l.nd.scale_bits; bn.se = l.nd.scale_exp; bn.b3 = l.scale ? mx(bn.b2, bn.sb) : bn.b2;
-        bn.bb = l.nd.bias_bits; bn.be = l.nd.bias_exp; bn.b4 = l.nbias ? mx(bn.b3, bn.bb) : bn.b3;
-        bn.ub = s.u_bits; bn.ue = s.u_exp; bn.out_bits = bn.b4; bn.dyn = d;
+        const BnArgs bn = make_bn(l, hb, he, d);
 
         // ---- BatchNorm exponents: reduce -> (cross-rank max) -> finalize, per compute_best op
         const unsigned rg = ew_grid(NH) > 2048 ? 2048 : ew_grid(NH);
-        auto hook = [&](int slot, int n) -> int {
-            return allreduce ? allreduce(allreduce_ctx, reinterpret_cast<float *>(d->mx + slot), n, stream) : 0;
-        };
-        hipLaunchKernelGGL(k_bn_reduce<1>, dim3(rg), dim3(256), 0, st, bn, h, NH, H, d);
-        if (hook(0, 3)) return S5FXP_EHIP;
-        hipLaunchKernelGGL(k_bn_finalize<1>, dim3(1), dim3(64), 0, st, bn, d, status, st_exps);
-        hipLaunchKernelGGL(k_bn_reduce<2>, dim3(rg), dim3(256), 0, st, bn, h, NH, H, d);
-        if (hook(3, 1)) return S5FXP_EHIP;
-        hipLaunchKernelGGL(k_bn_finalize<2>, dim3(1), dim3(64), 0, st, bn, d, status, st_exps);
-        if (l.scale) {
-            hipLaunchKernelGGL(k_bn_reduce<3>, dim3(rg), dim3(256), 0, st, bn, h, NH, H, d);
-            if (hook(4, 1)) return S5FXP_EHIP;
-            hipLaunchKernelGGL(k_bn_finalize<3>, dim3(1), dim3(64), 0, st, bn, d, status, st_exps);
-        }
-        if (l.nbias) {
-            hipLaunchKernelGGL(k_bn_reduce<4>, dim3(rg), dim3(256), 0, st, bn, h, NH, H, d);
-            if (hook(5, 3)) return S5FXP_EHIP;
-            hipLaunchKernelGGL(k_bn_finalize<4>, dim3(1), dim3(64), 0, st, bn, d, status, st_exps);
-        }
+        if ((rc = bn_exponent_ops([&](auto op) {
+                 hipLaunchKernelGGL(k_bn_reduce<decltype(op)::value>, dim3(rg), dim3(256), 0, st, bn, h, NH, H, d);
+             }, bn, d, status, st_exps, g.opts, st)))
+            return rc;
 
         // ---- B projection (fused BatchNorm apply + change_cfg), writes the scan-native stream
         const int sh_re = s.Bu_re_exp - s.x_re_exp, sh_im = s.Bu_im_exp - s.x_im_exp;
@@ -802,7 +818,7 @@ int generic_layers(const GenericRun &g, int first, int last, int32_t *&h, int32_
             else S5_DISPATCH_MW(a.mw, false, k_out2gate, tiles, st, a);
             if (tr && tr->post_GLU) hipMemcpyAsync(tr->post_GLU, a.z, (size_t)NH * 4, hipMemcpyDeviceToDevice, st);
         }
-        if (hook(8, 3)) return S5FXP_EHIP;
+        if (allreduce && allreduce(allreduce_ctx, reinterpret_cast<float *>(d->mx + 8), 3, stream)) return S5FXP_EHIP;
         hipLaunchKernelGGL(k_res_finalize, dim3(1), dim3(64), 0, st, d, l.res_exp, he, l.res_bits, status, st_exps, 8);
         hipLaunchKernelGGL(k_resid, dim3(ew_grid(NH)), dim3(256), 0, st, (const int32_t *)I(w.z), (const int32_t *)h, hn,
                            tr ? tr->residadd : nullptr, NH, l.res_bits, hb, (const LayerDyn *)d);
@@ -811,8 +827,21 @@ int generic_layers(const GenericRun &g, int first, int last, int32_t *&h, int32_
         he = DynExp{0, &d->res.eo};
     }
 
-    (void)rc;
     return S5FXP_OK;
+}
+
+// the status words of a generic forward over layers [first, last) start from zero except the path and, per layer, the
+// recurrence kernel, the state slots and the slots the streams hold
+void clear_status_generic(const s5fxp_model *m, int first, int last, int32_t *status, hipStream_t st)
+{
+    StatusInit si{};
+    si.path = S5FXP_PATH_GENERIC;
+    for (int li = first; li < last; ++li) {
+        si.rk[li] = m->layers[li].quad_ok && !(m->flags & S5FXP_MODEL_FORCE_GENERIC) ? 1 : 0;
+        si.slots[li] = m->P;
+        si.stream[li] = m->P;
+    }
+    hipLaunchKernelGGL(k_clear2, dim3(1), dim3(256), 0, st, status, (int)S5FXP_STATUS_WORDS, (int32_t *)nullptr, 0, si, m->n_layers, GroupOff{});
 }
 
 } // namespace
@@ -828,8 +857,7 @@ extern "C" int s5fxp_model_forward(const s5fxp_model *m, const int32_t *x, int x
     if (G > 1) {
         // Grouped call: G independent reference batches of B sequences each.  The fused kernels take them in ONE set of
         // launches (gridDim.y = G) when nothing couples the groups on the host; otherwise one forward per group.
-        if (m->fast && !traces && !opts->allreduce && fast_bn_ext(m) &&
-            (((int64_t)L + 3) / 4 + 2 * SCAN_DEPTH) * (m->P ? m->P : 1) * 32 < 0xffffffffll)
+        if (m->fast && !traces && !opts->allreduce && fast_bn_ext(m) && stream_extent_ok(m, L))
             return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), G, ws_one);
         const size_t plane = (size_t)m->n_layers * 2 * B * (m->P ? m->P : 1);
         for (int g = 0; g < G; ++g) {
@@ -844,14 +872,8 @@ extern "C" int s5fxp_model_forward(const s5fxp_model *m, const int32_t *x, int x
         }
         return S5FXP_OK;
     }
-    // the recurrence kernels address one (sequence, state group) run of a stream through a 32-bit buffer extent
-    if ((((int64_t)L + 3) / 4 + 2 * SCAN_DEPTH) * (m->P ? m->P : 1) * 32 >= 0xffffffffll) return S5FXP_EBADARG;
+    if (!stream_extent_ok(m, L)) return S5FXP_EBADARG;
     if (m->fast) return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream));
-    s5fxp_allreduce_max_fn allreduce = opts ? opts->allreduce : nullptr;
-    void *allreduce_ctx = opts ? opts->allreduce_ctx : nullptr;
-    void **scan_events = opts ? opts->scan_events : nullptr;
-    const int32_t *state_in = opts ? opts->state_in : nullptr;
-    int32_t *state_out = opts ? opts->state_out : nullptr;
     const WsLayout w = ws_layout(m, B, L);
     if (workspace_bytes < w.total) return S5FXP_EWORKSPACE;
     hipStream_t st = S(stream);
@@ -859,20 +881,9 @@ extern "C" int s5fxp_model_forward(const s5fxp_model *m, const int32_t *x, int x
     auto I = [&](size_t off) { return reinterpret_cast<int32_t *>(ws + off); };
     LayerDyn *dyn = reinterpret_cast<LayerDyn *>(ws + w.dyn);
     const int64_t N = (int64_t)B * L;
-    const int H = m->H, P = m->P;
-    const int64_t NH = N * H;
     const unsigned tiles = (unsigned)((N + TN - 1) / TN);
     int rc;
-    {
-        StatusInit si{};
-        si.path = S5FXP_PATH_GENERIC;
-        for (int li = 0; li < m->n_layers; ++li) {
-            si.rk[li] = m->layers[li].quad_ok && !(m->flags & S5FXP_MODEL_FORCE_GENERIC) ? 1 : 0;
-            si.slots[li] = m->P;
-            si.stream[li] = m->P;
-        }
-        hipLaunchKernelGGL(k_clear2, dim3(1), dim3(256), 0, st, status, (int)S5FXP_STATUS_WORDS, (int32_t *)nullptr, 0, si, m->n_layers, GroupOff{});
-    }
+    clear_status_generic(m, 0, m->n_layers, status, st);
     if ((rc = hip_rc(hipMemsetAsync(dyn, 0, sizeof(LayerDyn) * (size_t)(m->n_layers ? m->n_layers : 1), st)))) return rc;
 
     // ---- encoder + ReLU (fxpmodel.py:1263-1266)
@@ -921,21 +932,14 @@ extern "C" int s5fxp_layer_forward(const s5fxp_model *m, int layer, const int32_
     if (!m || !x || !y || !workspace || !status || layer < 0 || layer >= m->n_layers || B < 1 || L < 1 || x_bits < 1 || x_bits > 32)
         return S5FXP_EBADARG;
     if (opts && opts->groups > 1) return S5FXP_EUNSUPPORTED;
-    if ((((int64_t)L + 3) / 4 + 2 * SCAN_DEPTH) * (m->P ? m->P : 1) * 32 >= 0xffffffffll) return S5FXP_EBADARG;
+    if (!stream_extent_ok(m, L)) return S5FXP_EBADARG;
     const WsLayout w = ws_layout(m, B, L);
     if (workspace_bytes < w.total) return S5FXP_EWORKSPACE;
     hipStream_t st = S(stream);
     char *ws = reinterpret_cast<char *>(workspace);
     LayerDyn *dyn = reinterpret_cast<LayerDyn *>(ws + w.dyn);
     int rc;
-    {
-        StatusInit si{};
-        si.path = S5FXP_PATH_GENERIC;
-        si.rk[layer] = m->layers[layer].quad_ok && !(m->flags & S5FXP_MODEL_FORCE_GENERIC) ? 1 : 0;
-        si.slots[layer] = m->P;
-        si.stream[layer] = m->P;
-        hipLaunchKernelGGL(k_clear2, dim3(1), dim3(256), 0, st, status, (int)S5FXP_STATUS_WORDS, (int32_t *)nullptr, 0, si, m->n_layers, GroupOff{});
-    }
+    clear_status_generic(m, layer, layer + 1, status, st);
     if ((rc = hip_rc(hipMemsetAsync(dyn, 0, sizeof(LayerDyn) * (size_t)m->n_layers, st)))) return rc;
     // streaming carry of a single layer: the arrays are [1][2][B][P] here
     s5fxp_forward_opts o{};

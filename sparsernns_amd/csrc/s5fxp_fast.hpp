@@ -216,6 +216,7 @@ void pack_fast(Packer &p, const s5fxp_model_desc *d, FastModel *f)
 }
 
 struct FastWs {
+    // x1: no fused kernel uses it; it stays until a change of the workspace size (s5fxp_workspace_bytes) is wanted
     size_t hA, hB, x1, z, u, bq, xs, dyn, ext, dyn_bytes, total;
     int TB;
 };
@@ -244,24 +245,9 @@ FastWs fast_ws(const s5fxp_model *m, int B, int L)
     return w;
 }
 
-template <class K, class A>
-inline void launch_smem(K kernel, unsigned grid, size_t smem, hipStream_t st, const A &args, unsigned threads, int G, const GroupOff &go)
-{
-    if (smem > 65536) // the dim_scale 1.0 tiles need more than the default dynamic-LDS limit
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(kernel, dim3(grid, G), dim3(threads), smem, st, args, go);
-}
-
-// one workgroup = 4 waves x 32 frames; cap the grid at 4 workgroups per CU and let waves loop
-inline unsigned mfma_grid(int64_t N)
-{
-    const int64_t blocks = ((N + 31) / 32 + 3) / 4;
-    return (unsigned)(blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks));
-}
-
 // Which recurrence kernel a fused forward with these S5FXP_FWD_* flags runs for layer li.  Codes 1..4 as
-// s5fxp_model_recurrence_kernel (include/s5fxp.h); RK_EXACT = the exact 32-bit chain (k_scan_quad32_asm).  The one place
-// that decides: forward_fast launches by it, the status words report it, the query answers from it.
+// s5fxp_model_recurrence_kernel (include/s5fxp.h); RK_EXACT = the exact 32-bit chain (k_scan_quad32_asm).  Only plan_layer
+// calls it: forward_fast launches by the plan, the status words report it, the queries answer from it.
 enum { RK_LANE = 0, RK_QUAD32 = 1, RK_QUAD16 = 2, RK_PAIR = 3, RK_PAIRL = 4, RK_EXACT = 5 };
 struct Rung {
     bool exact, defer, quad, s16, pair, pairl;
@@ -304,9 +290,6 @@ int stream_live_slots(const s5fxp_model *m, int li, const Rung &rung, bool compa
     return n >= fl.c_slots ? 0 : n;
 }
 
-// G > 1: a grouped launch (include/s5fxp.h s5fxp_forward_opts::groups): x, y, workspace, status and the carry arrays hold G
-// consecutive copies of what one forward uses; every kernel runs with gridDim.y = G (scan_quad.hpp GroupOff).  The caller
-// (s5fxp_model_forward) sends only hook-free, trace-free forwards here with G > 1.
 bool fast_bn_ext(const s5fxp_model *m)
 {
     // BatchNorm exponents from per-channel extremes need every BN operand to be <= 16 bit with exponents in
@@ -323,122 +306,244 @@ bool fast_bn_ext(const s5fxp_model *m)
     return bn_ext;
 }
 
-int forward_fast(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int B, int L, int32_t *y, void *workspace,
-                 int32_t *status, const s5fxp_layer_trace *traces, const s5fxp_forward_opts *opts, hipStream_t st, int G = 1,
-                 size_t ws_stride = 0)
+// The form of a layer's gate kernel (mfma_fused.hpp k_cgate_p): traced; 64-frame tiles; the packed-epilogue kernel on
+// 32-frame tiles with three-wave workgroups; the packed-epilogue kernel that recomputes u (GBN).
+enum GateForm { GATE_TRACED, GATE_FT64, GATE_FT32, GATE_GBN };
+
+// Everything a fused forward decides about layer li before it enqueues anything.
+struct LayerPlan {
+    bool compact;     // live-state compaction (FastLayer): the layer's kernels run on c_slots state slots
+    Rung rung;
+    int P;            // state slots the layer's kernels run on: m->P, or c_slots when compacted
+    int ks;           // P / 32: the KS of k_cgate_p and half the NC of k_bproj_p
+    int live_slots;   // state slots the recurrence streams hold, 0 = every one (stream_live_slots)
+    int stream_slots; // status word [8 + 8l + 7]
+    int32_t bound;    // the recurrence kernel's exactness bound on |state| (pair or quad, over the slots it runs on)
+    int32_t xmax;     // the bound the gate kernel checks on every state: <= 32767 (the C projection's 16-bit planes)
+    bool direct;      // the sigmoid input has a direct table (FastLayer::sigdir)
+    bool pk16;        // packed int16 epilogues of the gate kernel (mfma_fused.hpp PK16)
+    bool gate_bn;     // the gate kernel recomputes u (S5FXP_GATE_BN)
+    GateForm gate;
+    const MfmaW *w_bproj, *w_cre, *w_cim; // full or compacted; w_bproj: the pair-ordered packing on the pair rungs
+    const int32_t *a_re, *a_im;           // Lambda_bar of the slots
+};
+
+LayerPlan plan_layer(const s5fxp_model *m, int li, int fwd_flags, bool traced, bool carry, bool fold)
 {
+    const LayerDev &l = m->layers[li];
+    const FastLayer &fl = m->fast->layers[li];
+    const s5fxp_ssm_desc &s = l.sd;
+    const bool big = m->H == 192;
+    LayerPlan p{};
+    p.compact = fl.compact_ok && !m->cfg.no_compact && !traced && !carry;
+    p.rung = select_rung(m, li, fwd_flags, traced, p.compact);
+    const Rung &r = p.rung;
+    p.P = p.compact ? fl.c_slots : m->P;
+    p.ks = p.P / 32;
+    // on the int16 rungs a compacted layer keeps only its live slots in the two recurrence streams (whole lane quads = state
+    // pairs; scan_quad.hpp ScanPairLArgs::live_slots)
+    p.live_slots = stream_live_slots(m, li, r, p.compact);
+    p.stream_slots = p.live_slots ? p.live_slots : p.P;
+    const ScanBounds &cb = fl.c_bounds;
+    p.bound = r.pair ? (p.compact ? cb.pair_xmax : l.pair_xmax) : (p.compact ? cb.quad_xmax : l.quad_xmax);
+    p.xmax = 32767;
+    if (r.quad) p.xmax = std::min(p.bound, p.xmax); // the pair bound is <= 32766: a saturated int16 state fails the check
+    if (r.quad && r.s16 && !r.pair) p.xmax = std::min(p.xmax, 32766); // a saturated int16 state must fail the check
+    // packed int16 epilogues of the gate kernel (mfma_fused.hpp PK16): every width they touch is 16, no out2 input conversion
+    const bool out2_conv = s.y_bits > l.out2.inp_bits || s.y_exp > l.out2.inp_exp;
+    p.direct = r.s16 && fl.sigdir_bits > 0;
+    p.pk16 = p.direct && !traced && !m->cfg.no_pk16 && fl.bias16 && s.y_bits == 16 && l.out2.out_bits == 16 && l.res_bits == 16 &&
+             l.l_bits == 16 && !out2_conv && l.l_exp - s.y_exp <= 14;
+    // ... and on that kernel the SSM input u CAN be recomputed from the layer input instead of travelling through memory
+    // (k_cgate_p<.., GBN>, S5FXP_GATE_BN=1; the exponents are the ones this layer's B projection publishes in its prologue).
+    // Off by default: -50 MB per layer and batch, but the twelve VALU operations per element land in the kernel that is
+    // VALU-co-limited already -- gate kernel 207 -> 250 us per 8-batch launch, B projection 104 -> 90: 3 % slower overall
+    p.gate_bn = p.pk16 && fold && !big && m->cfg.gate_bn;
+    // 32-frame tiles, three-wave workgroups: with the sigmoid table sized exactly FIVE of them fit a CU's LDS and registers --
+    // 15 waves instead of the 12 of two six-wave workgroups, for a kernel whose waves wait two thirds of their cycles.  The
+    // grid is exactly what is resident at once (5 x 256 CUs): 170 us per 8-batch launch against 190 (tools/ab_cgate_ft32.sh;
+    // 1024 or 1536 workgroups: 189 / 209).  (Without PK16 they were tried as well: 39 vs 36 us.)
+    p.gate = traced ? GATE_TRACED : p.gate_bn ? GATE_GBN : (!big && p.pk16 && !m->cfg.cgate_ft64) ? GATE_FT32 : GATE_FT64;
+    p.w_bproj = r.pair ? &(p.compact ? fl.c_bproj_pair : fl.bproj_pair).w : &(p.compact ? fl.c_bproj : fl.bproj).w;
+    p.w_cre = &(p.compact ? fl.c_cre : fl.cre).w;
+    p.w_cim = &(p.compact ? fl.c_cim : fl.cim).w;
+    p.a_re = p.compact ? fl.c_a_re : l.a_re;
+    p.a_im = p.compact ? fl.c_a_im : l.a_im;
+    return p;
+}
+
+// What s5fxp_model_recurrence_kernel / _xmax report: a plain forward (no traces, no carry) under S5FXP_FWD_DEFER_REDO
+LayerPlan plain_plan(const s5fxp_model *m, int li) { return plan_layer(m, li, S5FXP_FWD_DEFER_REDO, false, false, fast_bn_ext(m)); }
+
+// kernel(std::integral_constant<int, KS>) for a layer's KS = state slots / 32: 2 (H = 96) or 4 (H = 192, NT = 6), halved or
+// quartered for a compacted layer.  The one KS helper of the fused path: it instantiates no KS that cannot run.
+template <int NT, class Kernel> auto ks_kernel(int ks, Kernel kernel)
+{
+    if constexpr (NT == 6)
+        if (ks == 4) return kernel(std::integral_constant<int, 4>{});
+    return ks == 1 ? kernel(std::integral_constant<int, 1>{}) : kernel(std::integral_constant<int, 2>{});
+}
+
+// k_bproj_p of an untraced layer: SM = the stream its recurrence rung wants (proj_p.hpp), NC = 2 KS column tiles
+template <int SM> auto bproj_kernel(bool big, int ks)
+{
+    return big ? ks_kernel<6>(ks, [](auto k) { return k_bproj_p<6, 8, false, SM, 2 * decltype(k)::value>; })
+               : ks_kernel<3>(ks, [](auto k) { return k_bproj_p<3, 4, false, SM, 2 * decltype(k)::value>; });
+}
+
+// k_cgate_p<KS, NT, false, S16, DIRECT, FTP, false, PAIR, PK16, GBN> of an untraced, inexact layer in its gate form: the
+// 32-frame and GBN forms exist for the packed epilogues (PK16) at H = 96 only
+template <bool S16, bool DIR, bool PAIR, bool PK16> auto cgate_kernel(const LayerPlan &p, bool big)
+{
+    if (big) return ks_kernel<6>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 6, false, S16, DIR, 64, false, PAIR, PK16>; });
+    if constexpr (PK16) {
+        if (p.gate == GATE_FT32)
+            return ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 32, false, PAIR, true>; });
+        if (p.gate == GATE_GBN)
+            return ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 64, false, PAIR, true, true>; });
+    }
+    return ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 64, false, PAIR, PK16>; });
+}
+// ... for the seven (S16, DIRECT, PAIR, PK16) a plan can hold (PK16 needs DIRECT; DIRECT and PAIR need S16)
+auto gate_kernel(const LayerPlan &p, bool big)
+{
+    const bool pair = p.rung.pair;
+    return p.pk16 && pair   ? cgate_kernel<true, true, true, true>(p, big)
+           : p.pk16         ? cgate_kernel<true, true, false, true>(p, big)
+           : p.direct && pair ? cgate_kernel<true, true, true, false>(p, big)
+           : pair           ? cgate_kernel<true, false, true, false>(p, big)
+           : p.direct       ? cgate_kernel<true, true, false, false>(p, big)
+           : p.rung.s16     ? cgate_kernel<true, false, false, false>(p, big)
+                            : cgate_kernel<false, false, false, false>(p, big);
+}
+
+// Workgroups of a launch over `tiles` tiles, at most `cap` of them (persistent loops over the tiles)
+inline unsigned grid_for(int64_t tiles, int64_t cap)
+{
+    const int64_t per = (tiles + cap - 1) / cap;
+    return (unsigned)((tiles + per - 1) / per);
+}
+
+// One fused forward: the plan and the stages that enqueue it.
+// G > 1: a grouped launch (include/s5fxp.h s5fxp_forward_opts::groups): x, y, workspace, status and the carry arrays hold G
+// consecutive copies of what one forward uses; every kernel runs with gridDim.y = G (scan_quad.hpp GroupOff).  The caller
+// (s5fxp_model_forward) sends only hook-free, trace-free forwards here with G > 1.
+struct FusedForward {
+    const s5fxp_model *m;
+    const s5fxp_forward_opts *opts;
+    const s5fxp_layer_trace *traces;
+    int32_t *status;
+    hipStream_t st;
+    int G, B, L;
+    char *ws;
+    size_t ws_stride; // bytes between the groups' workspaces (0: this forward's size)
+
     const FastModel &F = *m->fast;
     const ModelCfg &cfg = m->cfg;
-    const int fwd_flags = opts ? opts->flags : 0;
-    s5fxp_allreduce_max_fn allreduce = opts ? opts->allreduce : nullptr;
-    void *allreduce_ctx = opts ? opts->allreduce_ctx : nullptr;
-    void **scan_events = opts ? opts->scan_events : nullptr;
-    void **gate_events = opts ? opts->gate_events : nullptr;
+    const int H = m->H, fwd_flags = opts ? opts->flags : 0;
+    const int64_t N = (int64_t)B * L, NH = N * H;
+    const bool big = H == 192;
+    const bool exact = (fwd_flags & S5FXP_FWD_EXACT) != 0, defer = (fwd_flags & S5FXP_FWD_DEFER_REDO) && !exact;
+    const s5fxp_allreduce_max_fn allreduce = opts ? opts->allreduce : nullptr;
     const int32_t *state_in = opts ? opts->state_in : nullptr;
     int32_t *state_out = opts ? opts->state_out : nullptr;
-    const bool exact = (fwd_flags & S5FXP_FWD_EXACT) != 0;
-    const bool defer = (fwd_flags & S5FXP_FWD_DEFER_REDO) && !exact;
     const FastWs w = fast_ws(m, B, L);
-    GroupOff go{};
-    go.x = (int64_t)B * L * m->d_in * 4; go.y = (int64_t)B * L * m->d_out * 4; go.ws = (int64_t)(ws_stride ? ws_stride : w.total); go.status = 4 * S5FXP_STATUS_WORDS;
-    go.state_in = go.state_out = (int64_t)m->n_layers * 2 * B * (m->P ? m->P : 1) * 4;
-    // ModelCfg::debug_sync: synchronise and check for launch / execution errors after every stage (names the stage that
-    // failed); off by default -- a forward has no host synchronisation, and launch errors are collected once at the end
-    const bool debug_sync = cfg.debug_sync;
-    auto stage_ok = [&](const char *what, int layer) -> bool {
-        if (!debug_sync) return true;
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) std::fprintf(stderr, "[s5fxp] %s (layer %d): %s\n", what, layer, hipGetErrorString(e));
-        return e == hipSuccess;
-    };
-    char *ws = reinterpret_cast<char *>(workspace);
-    auto I16 = [&](size_t off) { return reinterpret_cast<int16_t *>(ws + off); };
-    auto I32 = [&](size_t off) { return reinterpret_cast<int32_t *>(ws + off); };
     LayerDyn *dyn = reinterpret_cast<LayerDyn *>(ws + w.dyn);
-    const int64_t N = (int64_t)B * L;
-    const int H = m->H, P = m->P;
-    const int64_t NH = N * H;
-    const bool big = (H == 192);
-    const unsigned grid = mfma_grid(N);
-    int rc;
-    // the status words start from zero except what the host already knows: which path runs ([2]) and which recurrence
-    // kernel each layer gets ([8 + 8l + 5])
-    StatusInit si{};
-    si.path = S5FXP_PATH_FUSED;
-    for (int li = 0; li < m->n_layers; ++li) {
-        const bool compact = F.layers[li].compact_ok && !cfg.no_compact && !traces && !state_in && !state_out;
-        si.rk[li] = select_rung(m, li, fwd_flags, traces != nullptr, compact).code;
-        si.slots[li] = compact ? F.layers[li].c_slots : m->P;
-        const int ls = stream_live_slots(m, li, select_rung(m, li, fwd_flags, traces != nullptr, compact), compact);
-        si.stream[li] = ls ? ls : si.slots[li];
-    }
-    hipLaunchKernelGGL(k_clear2, dim3(8, G), dim3(256), 0, st, status, (int)S5FXP_STATUS_WORDS, reinterpret_cast<int32_t *>(dyn),
-                       (int)(w.dyn_bytes / 4), si, m->n_layers, go);
-    const bool bn_ext = fast_bn_ext(m);
+    const int64_t carry_stride = (int64_t)m->n_layers * 2 * B * (m->P ? m->P : 1) * 4;
+    const GroupOff go{N * m->d_in * 4, N * m->d_out * 4, (int64_t)(ws_stride ? ws_stride : w.total), 4 * S5FXP_STATUS_WORDS,
+                      carry_stride, carry_stride};
 
+    // ---- the plan
+    const bool bn_ext = fast_bn_ext(m);
+    // single-rank mode folds the two one-workgroup "finalize" kernels of every layer into the residual pass
+    // (mfma_bn.hpp k_resid_minmax16); with a multi-rank hook the maxima are exchanged in between, so they stay
+    const bool fold = bn_ext && !allreduce;
+    const std::array<LayerPlan, 15> layer = plan_layers(); // validate: 8 + 8 * n_layers <= S5FXP_STATUS_WORDS
+    // the layer whose residual pass rides on the decoder (proj_p.hpp k_dec_p<.., RESID>), or -1
+    const int dec_resid = bn_ext && fold && !traces && !cfg.no_dec_resid ? m->n_layers - 1 : -1;
     // workgroups per launch (persistent loops over tiles): tuned per kernel on MI355X (256 CUs); ModelCfg (S5FXP_WGS_* at
     // model creation) overrides them
     // A grouped launch shares the caps between its groups (every workgroup pays its prologue once -- weights into registers,
     // tables into LDS, the exponent derivation -- and G x 512 workgroups of 4 tiles each pay it 4 times as often as 512
     // workgroups of 16 tiles: tools/sweep_groups.sh, +4 % at G = 4), down to a floor that still fills the chip with G groups
-    auto per_group = [&](int64_t cap, int64_t floor_) { return G > 1 ? std::max<int64_t>(cap / G, floor_) : cap; };
-    const int64_t cap_enc = per_group(cfg.cap_enc, 64), cap_dec = per_group(cfg.cap_dec, 64), cap_cgate = per_group(cfg.cap_cgate, 64),
-                  cap_bproj = per_group(cfg.cap_bproj, 128), cap_resid = per_group(cfg.cap_resid, 64);
-    // six-wave phase-split kernels (proj_p.hpp, mfma_fused.hpp): 64-frame tiles
-    const int64_t tiles64 = (N + 63) / 64;
-    auto grid_for = [&](int64_t tiles, int64_t cap) {
-        const int64_t per = (tiles + cap - 1) / cap;
-        return (unsigned)((tiles + per - 1) / per);
-    };
-    const unsigned grid_enc = grid_for(tiles64, cap_enc), grid_dec = grid_for(tiles64, cap_dec);
-    auto launch6g = [&](auto kernel, unsigned g6, size_t smem, const auto &args, unsigned threads = 384) {
-        if (smem > 65536)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(kernel, dim3(g6, G), dim3(threads), smem, st, args, go);
-    };
-    auto launch6 = [&](auto kernel, size_t smem, const auto &args) { launch6g(kernel, grid_dec, smem, args); };
-    // the gate kernel's launch can carry a pair of HIP events (s5fxp_forward_opts::gate_events: measurement only)
-    hipEvent_t gev0 = nullptr, gev1 = nullptr;
-    auto launch_gate = [&](auto kernel, unsigned g6, size_t smem, const auto &args, unsigned threads = 384) {
-        if (smem > 65536)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (gev0 && gev1) hipExtLaunchKernelGGL(kernel, dim3(g6, G), dim3(threads), smem, st, gev0, gev1, 0, args, go);
-        else hipLaunchKernelGGL(kernel, dim3(g6, G), dim3(threads), smem, st, args, go);
-    };
-    auto launch6x = [&](auto kernel, size_t smem, const auto &args, float *ext, int ext_reps) {
-        if (smem > 65536)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(kernel, dim3(grid_enc, G), dim3(384), smem, st, args, ext, ext_reps, go);
-    };
-
+    int64_t per_group(int64_t cap, int64_t floor_) const { return G > 1 ? std::max<int64_t>(cap / G, floor_) : cap; }
+    // six-wave phase-split kernels (proj_p.hpp, mfma_fused.hpp): 64-frame tiles; the per-layer ones tile each sequence
+    const int64_t tiles64 = (N + 63) / 64, seq_tiles64 = (int64_t)B * ((L + 63) / 64);
+    const unsigned grid_enc = grid_for(tiles64, per_group(cfg.cap_enc, 64)), grid_dec = grid_for(tiles64, per_group(cfg.cap_dec, 64));
+    // the B projection: up to 4 (H=96) / 2 (H=192) workgroups per CU
+    const int64_t cap_bproj = per_group(cfg.cap_bproj, 128);
+    const unsigned grid_bproj = grid_for(seq_tiles64, big ? std::max<int64_t>(cap_bproj / 2, 1) : cap_bproj);
+    const unsigned grid_gate = grid_for(seq_tiles64, per_group(cfg.cap_cgate, 64)), grid_gate_exact = grid_for(seq_tiles64, 512);
+    const unsigned grid_gate32 = grid_for((int64_t)B * ((L + 31) / 32), std::max<int64_t>(cfg.cap_cgate32 / G, 1));
     // residual / extremes pass: a workgroup owns rm_span consecutive frames, a multiple of its 4 x R frame step
     const int64_t rm_step = 4 * (RESID_THREADS / (H / 8)), rm_iters = (N + rm_step - 1) / rm_step;
     // (the kernel addresses a workgroup's span with 32-bit byte offsets: at most 2^31 bytes of one (N,H) int16 tensor per workgroup)
-    const int64_t rm_per_max = std::max<int64_t>(1, ((int64_t(1) << 31) / (2 * H)) / rm_step);
-    const int64_t rm_per = std::min(rm_per_max, (rm_iters + cap_resid - 1) / cap_resid), rm_span = rm_per * rm_step;
+    const int64_t rm_per = std::min(std::max<int64_t>(1, ((int64_t(1) << 31) / (2 * H)) / rm_step),
+                                    (rm_iters + per_group(cfg.cap_resid, 64) - 1) / per_group(cfg.cap_resid, 64));
+    const int64_t rm_span = rm_per * rm_step;
     const unsigned rm_grid = (unsigned)((rm_iters + rm_per - 1) / rm_per);
 
+    // the current layer input: its plane, the other one of the ping-pong pair, its bits and (device) exponent
     int16_t *h = I16(w.hA), *hn = I16(w.hB);
     int hb = m->enc.out_bits;
     DynExp he{m->enc.out_exp, nullptr};
-    // BatchNorm arguments of layer li, whose input has hb_in bits and the (device) exponent he_in
-    auto make_bn = [&](int li, int hb_in, DynExp he_in) {
-        const LayerDev &l = m->layers[li];
-        const s5fxp_ssm_desc &s = l.sd;
-        auto mx = [](int a, int b) { return a > b ? a : b; };
-        BnArgs bn{};
-        bn.mm = l.mm; bn.isv = l.isv; bn.scale = l.scale; bn.bias = l.nbias;
-        bn.xb = hb_in; bn.xe = he_in;
-        bn.mb = l.nd.mean_bits; bn.me = l.nd.mean_exp; bn.b1 = mx(hb_in, bn.mb);
-        bn.ib = l.nd.invsq_var_bits; bn.ie = l.nd.invsq_var_exp; bn.b2 = mx(bn.b1, bn.ib);
-        bn.sb = l.nd.scale_bits; bn.se = l.nd.scale_exp; bn.b3 = l.scale ? mx(bn.b2, bn.sb) : bn.b2;
-        bn.bb = l.nd.bias_bits; bn.be = l.nd.bias_exp; bn.b4 = l.nbias ? mx(bn.b3, bn.bb) : bn.b3;
-        bn.ub = s.u_bits; bn.ue = s.u_exp; bn.out_bits = bn.b4; bn.dyn = dyn + li;
-        return bn;
-    };
+
+    std::array<LayerPlan, 15> plan_layers() const
+    {
+        std::array<LayerPlan, 15> p{};
+        for (int li = 0; li < m->n_layers; ++li) p[li] = plan_layer(m, li, fwd_flags, traces != nullptr, state_in || state_out, fold);
+        return p;
+    }
+    int16_t *I16(size_t off) const { return reinterpret_cast<int16_t *>(ws + off); }
+    int32_t *I32(size_t off) const { return reinterpret_cast<int32_t *>(ws + off); }
+    const s5fxp_layer_trace *trace(int li) const { return traces ? &traces[li] : nullptr; }
+    float *ext(int li) const { return reinterpret_cast<float *>(ws + w.ext) + (size_t)li * 2 * H * EXT_REPS; }
+    int32_t *status_exps(int li) const { return status + 8 + 8 * li; }
+    // one event of the pair s5fxp_forward_opts::scan_events / gate_events attaches to layer li's launch (measurement only)
+    static hipEvent_t event(void **evs, int li, int k) { return evs ? (hipEvent_t)evs[2 * li + k] : nullptr; }
+
+    // Every launch with gridDim.y = G: the dynamic-LDS attribute where a kernel needs more than the default 64 KB (the
+    // dim_scale 1.0 tiles; a host-side table update), and the kernel's own start / stop time stamps when a pair of events is
+    // attached (what rocprofv3's kernel trace reports), not events recorded around it
+    template <class K, class... A>
+    void launch(K kernel, unsigned grid, unsigned block, size_t smem, hipEvent_t ev0, hipEvent_t ev1, const A &...args) const
+    {
+        if (smem > 65536)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (ev0 && ev1) hipExtLaunchKernelGGL(kernel, dim3(grid, G), dim3(block), smem, st, ev0, ev1, 0, args..., go);
+        else hipLaunchKernelGGL(kernel, dim3(grid, G), dim3(block), smem, st, args..., go);
+    }
+
+    // ModelCfg::debug_sync: synchronise and check for launch / execution errors after every stage (names the stage that
+    // failed); off by default -- a forward has no host synchronisation, and launch errors are collected once at the end
+    bool stage_ok(const char *what, int li) const
+    {
+        if (!cfg.debug_sync) return true;
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) std::fprintf(stderr, "[s5fxp] %s (layer %d): %s\n", what, li, hipGetErrorString(e));
+        return e == hipSuccess;
+    }
+
+    // the status words start from zero except what the host already knows: which path runs ([2]) and, per layer, the
+    // recurrence kernel ([8 + 8l + 5]), the state slots ([6]) and the slots the streams hold ([7]); the per-layer device state
+    // and extremes are zeroed by the same launch
+    void clear_status() const
+    {
+        StatusInit si{};
+        si.path = S5FXP_PATH_FUSED;
+        for (int li = 0; li < m->n_layers; ++li) {
+            si.rk[li] = layer[li].rung.code;
+            si.slots[li] = layer[li].P;
+            si.stream[li] = layer[li].stream_slots;
+        }
+        launch(k_clear2, 8, 256, 0, nullptr, nullptr, status, (int)S5FXP_STATUS_WORDS, reinterpret_cast<int32_t *>(dyn),
+               (int)(w.dyn_bytes / 4), si, m->n_layers);
+    }
+
     // ---- encoder + ReLU
+    int encoder(const int32_t *x, int x_bits, int x_exp) const
     {
         const DenseDev &e = m->enc;
         EncArgs a{};
@@ -451,382 +556,277 @@ int forward_fast(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, 
         const size_t smem = 4 * (size_t)H * 4 + 2 * 64 * 304; // cs128 + bias_eff + byte planes + extremes
         // the extremes of the output (layer 0's BatchNorm operand) are gathered on the way; single-rank mode also
         // lets the last workgroup derive layer 0's BatchNorm exponents (mfma_bn.hpp ResidTail)
-        float *ext0 = bn_ext && m->n_layers > 0 ? reinterpret_cast<float *>(ws + w.ext) : nullptr;
+        float *ext0 = bn_ext ? ext(0) : nullptr;
         const int ext_reps = (ext0 && !allreduce) ? EXT_REPS : 1; // the consumer (k_bproj_p's prologue) folds the replicas
-        if (big) launch6x(k_enc_p<6>, smem, a, ext0, ext_reps);
-        else launch6x(k_enc_p<3>, smem, a, ext0, ext_reps);
-        if (!stage_ok("encoder", -1)) return S5FXP_EHIP;
+        launch(big ? k_enc_p<6> : k_enc_p<3>, grid_enc, 384, smem, nullptr, nullptr, a, ext0, ext_reps);
+        return S5FXP_OK;
     }
-    // single-rank mode folds the two one-workgroup "finalize" kernels of every layer into the residual pass
-    // (mfma_bn.hpp k_resid_minmax16); with a multi-rank hook the maxima are exchanged in between, so they stay
-    const bool fold = bn_ext && !allreduce;
 
-    bool dec_resid = false; // the decoder does the last layer's residual pass itself
-    DecResid dz{};
-    int dec_bits = 0;
-    for (int li = 0; li < m->n_layers; ++li) {
-        const LayerDev &l = m->layers[li];
-        const FastLayer &fl = F.layers[li];
-        const s5fxp_layer_trace *tr = traces ? &traces[li] : nullptr;
+    // ---- BatchNorm exponents of layer li: from the extremes the previous stage left (layer 0: the encoder; later layers:
+    // the previous layer's residual pass), or the four full reductions
+    int bn_exponents(int li, const BnArgs &bn) const
+    {
         LayerDyn *d = dyn + li;
-        int32_t *st_exps = status + 8 + 8 * li;
-        const s5fxp_ssm_desc &s = l.sd;
-        auto mx = [](int a, int b) { return a > b ? a : b; };
-
-        const BnArgs bn = make_bn(li, hb, he);
-
-        const unsigned rg = ew_grid(NH / 4) > 2048 ? 2048 : ew_grid(NH / 4);
-        auto hook = [&](int slot, int n) -> int {
-            return allreduce ? allreduce(allreduce_ctx, reinterpret_cast<float *>(d->mx + slot), n, (void *)st) : 0;
-        };
-        if (bn_ext) {
-            float *ext = reinterpret_cast<float *>(ws + w.ext) + (size_t)li * 2 * H * EXT_REPS;
-            // layer 0: extremes of the encoder output; later layers: the previous layer's residual pass left them
-            // layer 0: the encoder left the extremes; later layers: the previous layer's residual pass
-            if (!fold) {
-                // mode A: the extremes (positive floats) are what the ranks exchange -- one MAX over 2H values
-                if (allreduce && allreduce(allreduce_ctx, ext, 2 * H, (void *)st)) return S5FXP_EHIP;
-                hipLaunchKernelGGL(k_bn_finalize_mm, dim3(1), dim3(256), 0, st, bn, (const float *)ext, H, d, status, st_exps);
-            }
-        } else {
-        hipLaunchKernelGGL(k_bn_reduce16<1>, dim3(rg), dim3(256), 0, st, bn, (const int16_t *)h, NH, H, d);
-        if (hook(0, 3)) return S5FXP_EHIP;
-        hipLaunchKernelGGL(k_bn_finalize<1>, dim3(1), dim3(64), 0, st, bn, d, status, st_exps);
-        hipLaunchKernelGGL(k_bn_reduce16<2>, dim3(rg), dim3(256), 0, st, bn, (const int16_t *)h, NH, H, d);
-        if (hook(3, 1)) return S5FXP_EHIP;
-        hipLaunchKernelGGL(k_bn_finalize<2>, dim3(1), dim3(64), 0, st, bn, d, status, st_exps);
-        if (l.scale) {
-            hipLaunchKernelGGL(k_bn_reduce16<3>, dim3(rg), dim3(256), 0, st, bn, (const int16_t *)h, NH, H, d);
-            if (hook(4, 1)) return S5FXP_EHIP;
-            hipLaunchKernelGGL(k_bn_finalize<3>, dim3(1), dim3(64), 0, st, bn, d, status, st_exps);
+        if (!bn_ext) {
+            const unsigned rg = std::min(ew_grid(NH / 4), 2048u);
+            return bn_exponent_ops([&](auto op) {
+                hipLaunchKernelGGL(k_bn_reduce16<decltype(op)::value>, dim3(rg), dim3(256), 0, st, bn, (const int16_t *)h, NH, H, d);
+            }, bn, d, status, status_exps(li), opts, st);
         }
-        if (l.nbias) {
-            hipLaunchKernelGGL(k_bn_reduce16<4>, dim3(rg), dim3(256), 0, st, bn, (const int16_t *)h, NH, H, d);
-            if (hook(5, 3)) return S5FXP_EHIP;
-            hipLaunchKernelGGL(k_bn_finalize<4>, dim3(1), dim3(64), 0, st, bn, d, status, st_exps);
+        if (!fold) { // (fold: the B projection's prologue derives them)
+            // mode A: the extremes (positive floats) are what the ranks exchange -- one MAX over 2H values
+            if (allreduce && allreduce(opts->allreduce_ctx, ext(li), 2 * H, (void *)st)) return S5FXP_EHIP;
+            hipLaunchKernelGGL(k_bn_finalize_mm, dim3(1), dim3(256), 0, st, bn, (const float *)ext(li), H, d, status, status_exps(li));
         }
-        }
+        return S5FXP_OK;
+    }
 
-        // ---- B projection -> scan-native stream (+ u for the C projection)
-        const int sh_re = s.Bu_re_exp - s.x_re_exp, sh_im = s.Bu_im_exp - s.x_im_exp;
-        // live-state compaction (FastLayer): this layer's kernels run on c_slots state slots
-        const bool compact = fl.compact_ok && !cfg.no_compact && !tr && !state_in && !state_out;
-        const Rung rung = select_rung(m, li, fwd_flags, tr != nullptr, compact);
-        const bool quad = rung.quad, s16 = rung.s16, pair = rung.pair, pairl = rung.pairl;
-        const int32_t l_pair_xmax = compact ? fl.c_bounds.pair_xmax : l.pair_xmax, l_quad_xmax = compact ? fl.c_bounds.quad_xmax : l.quad_xmax;
-        const int P = compact ? fl.c_slots : m->P;
-        // on the LDS-fed pair rung a compacted layer with ONE group of 32 slots keeps only its live slots in the two recurrence
-        // streams (whole lane quads = state pairs; scan_quad.hpp ScanPairLArgs::live_lanes): 0 = every slot
-        const int live_slots = stream_live_slots(m, li, rung, compact);
-        const int32_t *la_re = compact ? fl.c_a_re : l.a_re, *la_im = compact ? fl.c_a_im : l.a_im;
-        const MfmaW &w_bproj = compact ? fl.c_bproj.w : fl.bproj.w, &w_bproj_pair = compact ? fl.c_bproj_pair.w : fl.bproj_pair.w;
-        const MfmaW &w_cre = compact ? fl.c_cre.w : fl.cre.w, &w_cim = compact ? fl.c_cim.w : fl.cim.w;
-        // packed int16 epilogues of the gate kernel (mfma_fused.hpp PK16): every width they touch is 16, no out2 input conversion
-        const bool out2_conv = s.y_bits > l.out2.inp_bits || s.y_exp > l.out2.inp_exp;
-        const bool direct = s16 && fl.sigdir_bits > 0;
-        const bool pk16 = direct && !tr && !cfg.no_pk16 && fl.bias16 && s.y_bits == 16 && l.out2.out_bits == 16 && l.res_bits == 16 &&
-                          l.l_bits == 16 && !out2_conv && l.l_exp - s.y_exp <= 14;
-        // ... and on that kernel the SSM input u CAN be recomputed from the layer input instead of travelling through memory
-        // (k_cgate_p<.., GBN>, S5FXP_GATE_BN=1; the exponents are the ones this layer's B projection publishes in its prologue).
-        // Off by default: -50 MB per layer and batch, but the twelve VALU operations per element land in the kernel that is
-        // VALU-co-limited already -- gate kernel 207 -> 250 us per 8-batch launch, B projection 104 -> 90: 3 % slower overall
-        const bool gate_bn = pk16 && fold && !big && cfg.gate_bn;
-        {
-            BprojM2Args a{};
-            a.bn = bn; a.x = h; a.w = w_bproj; a.bq = I32(w.bq); a.u = I16(w.u);
-            a.tr_bu_re = tr ? tr->Bu_re : nullptr; a.tr_bu_im = tr ? tr->Bu_im : nullptr;
-            a.tr_pre_s5 = tr ? tr->pre_s5 : nullptr; a.tr_u = tr ? tr->u : nullptr;
-            a.N = N; a.L = L; a.TB = w.TB; a.H = H; a.P = P;
-            a.rs_re = s.u_exp + s.B_re_exp - s.Bu_re_exp; a.rs_im = s.u_exp + s.B_im_exp - s.Bu_im_exp;
-            a.bre_bits = s.Bu_re_bits; a.bim_bits = s.Bu_im_bits; a.sh_re = sh_re; a.sh_im = sh_im;
-            a.k_re = 65536 - (1 << (16 - s.A_re_exp));
-            a.live_slots = live_slots;
-            a.no_u = gate_bn ? 1 : 0;
-            if (fold) {
-                a.ext = reinterpret_cast<const float *>(ws + w.ext) + (size_t)li * 2 * H * EXT_REPS;
-                a.ext_reps = EXT_REPS; a.status = status; a.status_exps = st_exps;
-            }
-            // phase-split kernel (proj_p.hpp): 64-step tiles, up to 4 (H=96) / 2 (H=192) workgroups per CU
+    // ---- B projection -> scan-native stream (+ u for the gate kernel)
+    void bproj(int li, const BnArgs &bn) const
+    {
+        const LayerPlan &p = layer[li];
+        const s5fxp_ssm_desc &s = m->layers[li].sd;
+        const s5fxp_layer_trace *tr = trace(li);
+        BprojM2Args a{};
+        a.bn = bn; a.x = h; a.w = *p.w_bproj; a.bq = I32(w.bq); a.u = I16(w.u);
+        a.tr_bu_re = tr ? tr->Bu_re : nullptr; a.tr_bu_im = tr ? tr->Bu_im : nullptr;
+        a.tr_pre_s5 = tr ? tr->pre_s5 : nullptr; a.tr_u = tr ? tr->u : nullptr;
+        a.N = N; a.L = L; a.TB = w.TB; a.H = H; a.P = p.P;
+        a.rs_re = s.u_exp + s.B_re_exp - s.Bu_re_exp; a.rs_im = s.u_exp + s.B_im_exp - s.Bu_im_exp;
+        a.bre_bits = s.Bu_re_bits; a.bim_bits = s.Bu_im_bits; a.sh_re = s.Bu_re_exp - s.x_re_exp; a.sh_im = s.Bu_im_exp - s.x_im_exp;
+        a.k_re = 65536 - (1 << (16 - s.A_re_exp));
+        a.live_slots = p.live_slots;
+        a.no_u = p.gate_bn ? 1 : 0;
+        if (fold) {
+            a.ext = ext(li);
+            a.ext_reps = EXT_REPS; a.status = status; a.status_exps = status_exps(li);
+        }
+        a.t_lo = 0; a.t_len = L;
 #ifdef S5_BPROJ_CSR
-            const size_t smem = 16 * (size_t)H + 4 * 64 * (size_t)(H + 16) + 2 * (size_t)(2 * m->P) * S5_BPROJ_CSR + 64; // + compressed columns
+        const size_t smem = 16 * (size_t)H + 4 * 64 * (size_t)(H + 16) + 2 * (size_t)(2 * m->P) * S5_BPROJ_CSR + 64; // + compressed columns
 #else
-            const size_t smem = 16 * (size_t)H + 4 * 64 * (size_t)(H + 16); // BN operands + double-buffered byte planes
+        const size_t smem = 16 * (size_t)H + 4 * 64 * (size_t)(H + 16); // BN operands + double-buffered byte planes
 #endif
-            {
-                a.t_lo = 0; a.t_len = L;
-                const int64_t tl = (int64_t)B * ((a.t_len + 63) / 64), cap = big ? std::max<int64_t>(cap_bproj / 2, 1) : cap_bproj, per = (tl + cap - 1) / cap;
-                const unsigned bthr = big ? 512 : 256; // one wave per 32-column tile of [B_re | B_im]
-                const unsigned pgrid = (unsigned)((tl + per - 1) / per);
-                // SM: the stream the recurrence rung wants (proj_p.hpp); a compacted layer has half the column tiles
-                auto bproj = [&](auto sm) {
-                    constexpr int SM = decltype(sm)::value;
-                    if (big) {
-                        if (compact && P == 32) launch_smem(k_bproj_p<6, 8, false, SM, 2>, pgrid, smem, st, a, bthr, G, go);
-                        else if (compact) launch_smem(k_bproj_p<6, 8, false, SM, 4>, pgrid, smem, st, a, bthr, G, go);
-                        else launch_smem(k_bproj_p<6, 8, false, SM, 8>, pgrid, smem, st, a, bthr, G, go);
-                    } else {
-                        if (compact) launch_smem(k_bproj_p<3, 4, false, SM, 2>, pgrid, smem, st, a, bthr, G, go);
-                        else launch_smem(k_bproj_p<3, 4, false, SM, 4>, pgrid, smem, st, a, bthr, G, go);
-                    }
-                };
-                if (tr) {
-                    if (big) launch_smem(k_bproj_p<6, 8, true>, pgrid, smem, st, a, bthr, G, go);
-                    else launch_smem(k_bproj_p<3, 4, true>, pgrid, smem, st, a, bthr, G, go);
-                } else if (pairl) {
-                    a.w = w_bproj_pair;
-                    bproj(std::integral_constant<int, 3>{});
-                } else if (pair) {
-                    a.w = w_bproj_pair;
-                    bproj(std::integral_constant<int, 2>{});
-                } else if (s16) {
-                    bproj(std::integral_constant<int, 1>{});
-                } else {
-                    bproj(std::integral_constant<int, 0>{});
-                }
-            }
-        }
-        if (!stage_ok("B projection", li)) return S5FXP_EHIP;
-        // ---- recurrence
-        const size_t plane = (size_t)B * P;
-        const int32_t *x0_re = state_in ? state_in + (size_t)li * 2 * plane : nullptr, *x0_im = state_in ? x0_re + plane : nullptr;
-        int32_t xmax = 32767; // the C projection's 16-bit planes
-        hipStream_t sst = st; // the stream the recurrence runs on
-        // measurement: the two events are attached to the launch itself (start / stop time stamps of this dispatch,
-        // what rocprofv3's kernel trace reports), not recorded around it
-        hipEvent_t ev0 = scan_events ? (hipEvent_t)scan_events[2 * li] : nullptr, ev1 = scan_events ? (hipEvent_t)scan_events[2 * li + 1] : nullptr;
-        auto launch_scan = [&](auto kernel, dim3 grid, dim3 block, auto args) {
-            grid.y = G;
-            if (ev0 && ev1) hipExtLaunchKernelGGL(kernel, grid, block, 0, sst, ev0, ev1, 0, args, go);
-            else hipLaunchKernelGGL(kernel, grid, block, 0, sst, args, go);
-        };
-        if (pairl) {
+        // phase-split kernel (proj_p.hpp), one wave per 32-column tile of [B_re | B_im]; SM: the stream the recurrence rung
+        // wants; a compacted layer has fewer column tiles (NC)
+        const Rung &r = p.rung;
+        auto kernel = tr ? (big ? k_bproj_p<6, 8, true> : k_bproj_p<3, 4, true>)
+                         : r.pairl ? bproj_kernel<3>(big, p.ks) : r.pair ? bproj_kernel<2>(big, p.ks) : r.s16 ? bproj_kernel<1>(big, p.ks) : bproj_kernel<0>(big, p.ks);
+        launch(kernel, grid_bproj, big ? 512 : 256, smem, nullptr, nullptr, a);
+    }
+    // the recurrence's arguments on the quad layout (the fast quad kernels, the exact chain and its gated re-run)
+    ScanQuadArgs quad_args(int li, const int32_t *run_if) const
+    {
+        const LayerPlan &p = layer[li];
+        const s5fxp_ssm_desc &s = m->layers[li].sd;
+        ScanQuadArgs q{};
+        q.bq = I32(w.bq); q.xs = I32(w.xs); q.a_re = p.a_re; q.a_im = p.a_im; q.B = B; q.TB = w.TB; q.P = p.P;
+        q.ea_re = s.A_re_exp; q.ea_im = s.A_im_exp; q.run_if = run_if; q.x0_re = x0(li, 0); q.x0_im = x0(li, 1);
+        q.live_slots = p.live_slots;
+        return q;
+    }
+    // the carry in of layer li, part c (0 = re, 1 = im), or nullptr
+    const int32_t *x0(int li, int c) const
+    {
+        const size_t plane = (size_t)B * layer[li].P;
+        return state_in ? state_in + (size_t)li * 2 * plane + c * plane : nullptr;
+    }
+
+    // ---- recurrence: the first launch of the layer carries the scan events on every rung
+    void recurrence(int li) const
+    {
+        const LayerPlan &p = layer[li];
+        const Rung &r = p.rung;
+        const s5fxp_ssm_desc &s = m->layers[li].sd;
+        void **evs = opts ? opts->scan_events : nullptr;
+        const hipEvent_t ev0 = event(evs, li, 0), ev1 = event(evs, li, 1);
+        const unsigned pair_grid = (unsigned)((int64_t)B * (p.P / 32)), quad_grid = (unsigned)((int64_t)B * p.P / 16);
+        if (r.pairl) {
             ScanPairLArgs q{};
-            q.b16 = I16(w.bq); q.xs = I16(w.xs); q.a_re = la_re; q.a_im = la_im; q.B = B; q.TB = w.TB; q.P = P;
-            q.ea_re = s.A_re_exp; q.ea_im = s.A_im_exp; q.x0_re = x0_re; q.x0_im = x0_im; q.live_slots = live_slots;
+            q.b16 = I16(w.bq); q.xs = I16(w.xs); q.a_re = p.a_re; q.a_im = p.a_im; q.B = B; q.TB = w.TB; q.P = p.P;
+            q.ea_re = s.A_re_exp; q.ea_im = s.A_im_exp; q.x0_re = x0(li, 0); q.x0_im = x0(li, 1); q.live_slots = p.live_slots;
             // one helper wave (a second one lands on the computing wave's side of the LDS path and costs more than it
             // helps: profiles/r02_ubench_pair.log).  Blocks per LDS buffer = steps per s_barrier / 4: S5FXP_PAIRL_BLOCKS
             const int blocks = cfg.pairl_blocks;
-            const dim3 sgrid((unsigned)((int64_t)B * (P / 32)), G);
-            auto launch_pairl = [&](auto kernel, int smem_bytes) {
-                if (smem_bytes > 65536) // > 64 KB of dynamic LDS needs the attribute (idempotent, a host-side table update)
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-                if (ev0 && ev1) hipExtLaunchKernelGGL(kernel, sgrid, dim3(128), smem_bytes, sst, ev0, ev1, 0, q, go);
-                else hipLaunchKernelGGL(kernel, sgrid, dim3(128), smem_bytes, sst, q, go);
-            };
-            if (blocks == 16) launch_pairl(k_scan_pairl_asm<16>, 3 * 16 * 1024);
-            else launch_pairl(k_scan_pairl_asm<32>, 3 * 32 * 1024);
-            xmax = l_pair_xmax < xmax ? l_pair_xmax : xmax;
-        } else if (pair) {
+            launch(blocks == 16 ? k_scan_pairl_asm<16> : k_scan_pairl_asm<32>, pair_grid, 128, 3 * (size_t)blocks * 1024, ev0, ev1, q);
+        } else if (r.pair) {
             ScanPairArgs q{};
-            q.k = I32(w.bq); q.xs = I16(w.xs); q.a_re = la_re; q.a_im = la_im; q.B = B; q.TB = w.TB; q.P = P;
-            q.ea_re = s.A_re_exp; q.ea_im = s.A_im_exp; q.x0_re = x0_re; q.x0_im = x0_im;
-            launch_scan(k_scan_pair_asm, dim3((unsigned)((int64_t)B * (P / 32))), dim3(64), q);
-            xmax = l_pair_xmax < xmax ? l_pair_xmax : xmax; // <= 32766: a saturated int16 state fails the check
-        } else if (quad) {
-            ScanQuadArgs q{};
-            q.bq = I32(w.bq); q.xs = I32(w.xs); q.a_re = la_re; q.a_im = la_im; q.B = B; q.TB = w.TB; q.P = P;
-            q.ea_re = s.A_re_exp; q.ea_im = s.A_im_exp; q.x0_re = x0_re; q.x0_im = x0_im; q.live_slots = live_slots;
-            {
-                if (s16) launch_scan(k_scan_quad_asm16, dim3((unsigned)((int64_t)B * P / 16)), dim3(64), q);
-                else launch_scan(k_scan_quad_asm, dim3((unsigned)((int64_t)B * P / 16)), dim3(64), q);
-            }
-            xmax = l_quad_xmax < xmax ? l_quad_xmax : xmax;
-            if (s16 && xmax > 32766) xmax = 32766; // a saturated int16 state must fail the check
+            q.k = I32(w.bq); q.xs = I16(w.xs); q.a_re = p.a_re; q.a_im = p.a_im; q.B = B; q.TB = w.TB; q.P = p.P;
+            q.ea_re = s.A_re_exp; q.ea_im = s.A_im_exp; q.x0_re = x0(li, 0); q.x0_im = x0(li, 1);
+            launch(k_scan_pair_asm, pair_grid, 64, 0, ev0, ev1, q);
         } else {
-            // states of any width: the exact 32-bit chain in the same quad layout
-            ScanQuadArgs q{};
-            q.bq = I32(w.bq); q.xs = I32(w.xs); q.a_re = la_re; q.a_im = la_im; q.B = B; q.TB = w.TB; q.P = P;
-            q.ea_re = s.A_re_exp; q.ea_im = s.A_im_exp; q.run_if = nullptr; q.x0_re = x0_re; q.x0_im = x0_im;
-            launch_scan(k_scan_quad32_asm, dim3((unsigned)((int64_t)B * P / 16)), dim3(64), q);
+            // not quad: states of any width, the exact 32-bit chain in the same quad layout
+            auto kernel = !r.quad ? k_scan_quad32_asm : r.s16 ? k_scan_quad_asm16 : k_scan_quad_asm;
+            launch(kernel, quad_grid, 64, 0, ev0, ev1, quad_args(li, nullptr));
         }
-        if (!stage_ok("recurrence", li)) return S5FXP_EHIP;
-        // ---- fused C projection + D*u + ReLU + out2 + sigmoid + gate (+ range check, + residual maxima)
-        GateMArgs ga{};
-        bool fused = false;
-        {
-            const DenseDev &o = l.out2;
-            ga.x1 = I16(w.x1); ga.skip = h; ga.z = I16(w.z); ga.w = fl.out2.w; ga.bias_eff = fl.out2.bias_eff;
-            ga.tr_out2 = tr ? tr->out2 : nullptr; ga.tr_sig = tr ? tr->out2_sigmoid : nullptr;
-            ga.tr_z = tr ? tr->post_GLU : nullptr;
-            ga.N = N; ga.H = H; ga.y_bits = s.y_bits; ga.y_exp = s.y_exp;
-            ga.conv = (s.y_bits > o.inp_bits || s.y_exp > o.inp_exp) ? 1 : 0;
-            ga.inp_bits = o.inp_bits; ga.inp_exp = o.inp_exp;
-            ga.rs = (ga.conv ? o.inp_exp : s.y_exp) + o.w_exp - o.out_exp;
-            if (!shift_ok(ga.rs)) return S5FXP_ENEGSHIFT;
-            ga.out_bits = o.out_bits; ga.out_exp = o.out_exp; ga.sig_x = l.sig_x; ga.sig_y = l.sig_y;
-            std::memcpy(ga.lut, l.lut, sizeof(ga.lut));
-            ga.l_bits = l.l_bits; ga.l_exp = l.l_exp; ga.r_bits = l.r_bits; ga.r_exp = l.r_exp; ga.res_bits = l.res_bits;
-            ga.res_exp = l.res_exp; ga.rs_gate = l.l_exp + l.r_exp - l.res_exp; ga.skip_e = he; ga.dynw = d;
-        }
-        {
-            CGateArgs a{};
-            a.u = I16(w.u); a.skip = h; a.xs = I32(w.xs); a.w_re = w_cre; a.w_im = w_cim; a.w_o2 = fl.out2.w;
-            a.D = fl.Dpad; a.bias_eff = fl.out2.bias_eff; a.z = I16(w.z); a.sigtab = fl.sigtab; a.sigdir = fl.sigdir; a.sigdir_bits = fl.sigdir_bits; a.mx_slot = 8;
-            a.tr_ys = tr ? tr->ys : nullptr; a.tr_out2 = ga.tr_out2; a.tr_sig = ga.tr_sig; a.tr_z = ga.tr_z;
-            a.N = N; a.L = L; a.TB = w.TB; a.H = H;
-            a.rs_re = s.x_re_exp + s.C_re_exp - s.y_exp; a.rs_im = s.x_im_exp + s.C_im_exp - s.y_exp;
-            a.rs_d = s.D_exp + s.u_exp - s.y_exp; a.y_bits = s.y_bits; a.y_exp = s.y_exp; a.xmax = xmax;
-            a.conv = ga.conv; a.inp_bits = ga.inp_bits; a.inp_exp = ga.inp_exp; a.rs_o2 = ga.rs; a.out_bits = ga.out_bits;
-            a.out_exp = ga.out_exp; a.sig_x = l.sig_x; a.sig_y = l.sig_y;
-            std::memcpy(a.lut, l.lut, sizeof(a.lut));
-            a.l_bits = l.l_bits; a.l_exp = l.l_exp; a.r_bits = l.r_bits; a.r_exp = l.r_exp; a.res_bits = l.res_bits;
-            a.res_exp = l.res_exp; a.rs_gate = ga.rs_gate; a.skip_e = he; a.dynw = d; a.status = status;
-            a.live_slots = live_slots;
+    }
+
+    // ---- fused C projection + D*u + ReLU + out2 + sigmoid + gate (+ range check, + residual maxima); the exact re-run, the
+    // carry out and the state trace
+    int gate(int li, const BnArgs &bn) const
+    {
+        const LayerPlan &p = layer[li];
+        const Rung &r = p.rung;
+        const LayerDev &l = m->layers[li];
+        const FastLayer &fl = F.layers[li];
+        const s5fxp_ssm_desc &s = l.sd;
+        const DenseDev &o = l.out2;
+        const s5fxp_layer_trace *tr = trace(li);
+        LayerDyn *d = dyn + li;
+        CGateArgs a{};
+        a.u = I16(w.u); a.skip = h; a.xs = I32(w.xs); a.w_re = *p.w_cre; a.w_im = *p.w_cim; a.w_o2 = fl.out2.w;
+        a.D = fl.Dpad; a.bias_eff = fl.out2.bias_eff; a.z = I16(w.z); a.sigtab = fl.sigtab; a.sigdir = fl.sigdir; a.sigdir_bits = fl.sigdir_bits; a.mx_slot = 8;
+        a.tr_ys = tr ? tr->ys : nullptr; a.tr_out2 = tr ? tr->out2 : nullptr; a.tr_sig = tr ? tr->out2_sigmoid : nullptr;
+        a.tr_z = tr ? tr->post_GLU : nullptr;
+        a.N = N; a.L = L; a.TB = w.TB; a.H = H;
+        a.rs_re = s.x_re_exp + s.C_re_exp - s.y_exp; a.rs_im = s.x_im_exp + s.C_im_exp - s.y_exp;
+        a.rs_d = s.D_exp + s.u_exp - s.y_exp; a.y_bits = s.y_bits; a.y_exp = s.y_exp; a.xmax = p.xmax;
+        a.conv = (s.y_bits > o.inp_bits || s.y_exp > o.inp_exp) ? 1 : 0; a.inp_bits = o.inp_bits; a.inp_exp = o.inp_exp;
+        a.rs_o2 = (a.conv ? o.inp_exp : s.y_exp) + o.w_exp - o.out_exp;
+        if (!shift_ok(a.rs_o2)) return S5FXP_ENEGSHIFT;
+        a.out_bits = o.out_bits; a.out_exp = o.out_exp; a.sig_x = l.sig_x; a.sig_y = l.sig_y;
+        std::memcpy(a.lut, l.lut, sizeof(a.lut));
+        a.l_bits = l.l_bits; a.l_exp = l.l_exp; a.r_bits = l.r_bits; a.r_exp = l.r_exp; a.res_bits = l.res_bits;
+        a.res_exp = l.res_exp; a.rs_gate = l.l_exp + l.r_exp - l.res_exp; a.skip_e = he; a.dynw = d; a.status = status;
+        a.live_slots = p.live_slots;
+        a.bad_bits = ST_WIDE_STATE | (defer ? ST_REDO : 0);
+        a.bn = bn;
+        a.t_lo = 0; a.t_len = L;
+        const unsigned threads = big ? 768 : 384;
+        // the untraced, inexact gate launch carries the gate events
+        void **evs = opts ? opts->gate_events : nullptr;
+        const hipEvent_t gev0 = event(evs, li, 0), gev1 = event(evs, li, 1);
+        const size_t sig_lds = p.direct ? (size_t)sigdir_lds_bytes(fl.sigdir_bits) : 4 * (size_t)SIGTAB_WORDS;
+        if (exact) {
+            // S5FXP_FWD_EXACT: the exact kernels below are the only ones; raise their gate
+            for (int g = 0; g < G; ++g)
+                if (int rc = hip_rc(hipMemsetAsync(reinterpret_cast<char *>(&d->redo) + (size_t)g * go.ws, 0xff, 4, st))) return rc;
+        } else if (p.gate == GATE_FT32) {
+            const size_t smem32 = 5 * (size_t)H * 4 + 32 + sig_lds + 2 * 32 * (size_t)(2 * p.P + 16) + 2 * 32 * (size_t)(H + 16) + 192 +
+                                  2 * 32 * (size_t)(2 * H + 8);
+            launch(gate_kernel(p, big), grid_gate32, 192, smem32, gev0, gev1, a);
+        } else {
             // phase-split fused kernel (mfma_fused.hpp): six waves per workgroup, 64-frame tiles, no weights in LDS
-            fused = true;
-            a.bad_bits = ST_WIDE_STATE | (defer ? ST_REDO : 0);
-            a.bn = bn;
-            const size_t smem = 5 * (size_t)H * 4 + 32 + (direct ? (size_t)sigdir_lds_bytes(fl.sigdir_bits) : 4 * (size_t)SIGTAB_WORDS) +
-                                2 * 64 * (size_t)(2 * P + 16) + 2 * 64 * (size_t)(H + 16) + 192 + (gate_bn ? 16 * (size_t)H : 0) +
-                                (pk16 && !gate_bn ? 2 * 64 * (size_t)(2 * H + 8) : 0); // + the u / skip / z tiles (mfma_fused.hpp COAL)
-            if (exact) {
-                // S5FXP_FWD_EXACT: the exact kernels below are the only ones; raise their gate
-                for (int g = 0; g < G; ++g)
-                    if ((rc = hip_rc(hipMemsetAsync(reinterpret_cast<char *>(&d->redo) + (size_t)g * go.ws, 0xff, 4, st)))) return rc;
-            } else {
-                {
-                    a.t_lo = 0; a.t_len = L;
-                    const int64_t tl = (int64_t)B * ((a.t_len + 63) / 64), per = (tl + cap_cgate - 1) / cap_cgate;
-                    const unsigned cg = (unsigned)((tl + per - 1) / per);
-                    // <S16, DIRECT, PAIR, PK16> of mfma_fused.hpp; KS = state slots / 32 (halved for a compacted layer)
-                    gev0 = gate_events ? (hipEvent_t)gate_events[2 * li] : nullptr; gev1 = gate_events ? (hipEvent_t)gate_events[2 * li + 1] : nullptr;
-                    auto cgate = [&](auto s16_t, auto direct_t, auto pair_t, auto pk16_t) {
-                        constexpr bool S16_ = decltype(s16_t)::value, DIR_ = decltype(direct_t)::value, PAIR_ = decltype(pair_t)::value,
-                                       PK_ = decltype(pk16_t)::value;
-                        if (big) {
-                            if (compact && P == 32) launch_gate(k_cgate_p<1, 6, false, S16_, DIR_, 64, false, PAIR_, PK_>, cg, smem, a, 768);
-                            else if (compact) launch_gate(k_cgate_p<2, 6, false, S16_, DIR_, 64, false, PAIR_, PK_>, cg, smem, a, 768);
-                            else launch_gate(k_cgate_p<4, 6, false, S16_, DIR_, 64, false, PAIR_, PK_>, cg, smem, a, 768);
-                        } else if (PK_ && !cfg.cgate_ft64 && !gate_bn) {
-                            // 32-frame tiles, three-wave workgroups: with the sigmoid table sized exactly FIVE of them fit a CU's LDS and
-                            // registers -- 15 waves instead of the 12 of two six-wave workgroups, for a kernel whose waves wait two thirds
-                            // of their cycles.  The grid is exactly what is resident at once (5 x 256 CUs): 170 us per 8-batch launch
-                            // against 190 (tools/ab_cgate_ft32.sh; 1024 or 1536 workgroups: 189 / 209).
-                            const size_t smem32 = 5 * (size_t)H * 4 + 32 + (direct ? (size_t)sigdir_lds_bytes(fl.sigdir_bits) : 4 * (size_t)SIGTAB_WORDS) +
-                                                  2 * 32 * (size_t)(2 * P + 16) + 2 * 32 * (size_t)(H + 16) + 192 + 2 * 32 * (size_t)(2 * H + 8);
-                            const int64_t tl32 = (int64_t)B * ((L + 31) / 32), cap32 = std::max<int64_t>(cfg.cap_cgate32 / G, 1), per32 = (tl32 + cap32 - 1) / cap32;
-                            const unsigned g32 = (unsigned)((tl32 + per32 - 1) / per32);
-                            if (compact) launch_gate(k_cgate_p<1, 3, false, S16_, DIR_, 32, false, PAIR_, PK_>, g32, smem32, a, 192);
-                            else launch_gate(k_cgate_p<2, 3, false, S16_, DIR_, 32, false, PAIR_, PK_>, g32, smem32, a, 192);
-                        } else if (PK_ && gate_bn) {
-                            if (compact) launch_gate(k_cgate_p<1, 3, false, S16_, DIR_, 64, false, PAIR_, PK_, PK_>, cg, smem, a);
-                            else launch_gate(k_cgate_p<2, 3, false, S16_, DIR_, 64, false, PAIR_, PK_, PK_>, cg, smem, a);
-                        } else {
-                            if (compact) launch_gate(k_cgate_p<1, 3, false, S16_, DIR_, 64, false, PAIR_, PK_>, cg, smem, a);
-                            else launch_gate(k_cgate_p<2, 3, false, S16_, DIR_, 64, false, PAIR_, PK_>, cg, smem, a);
-                        }
-                    };
-                    using T_ = std::true_type;
-                    using F_ = std::false_type;
-                    if (tr) {
-                        if (big) launch6g(k_cgate_p<4, 6, true>, cg, smem, a, 768);
-                        else launch6g(k_cgate_p<2, 3, true>, cg, smem, a);
-                    } else if (pk16 && pair) cgate(T_{}, T_{}, T_{}, T_{});
-                    else if (pk16) cgate(T_{}, T_{}, F_{}, T_{});
-                    else if (direct && pair) cgate(T_{}, T_{}, T_{}, F_{});
-                    else if (pair) cgate(T_{}, F_{}, T_{}, F_{});
-                    else if (direct) cgate(T_{}, T_{}, F_{}, F_{}); // (32-frame tiles with three-wave workgroups were tried: 39 vs 36 us)
-                    else if (s16) cgate(T_{}, F_{}, F_{}, F_{});
-                    else cgate(F_{}, F_{}, F_{}, F_{});
-                }
-            }
-            // ---- exact re-run, only if a state left the fast kernels' range (LayerDyn::redo); with
-            // S5FXP_FWD_DEFER_REDO the caller repeats the forward instead (S5FXP_ST_REDO)
-            if (!defer) {
-                if (quad) {
-                    ScanQuadArgs q{};
-                    q.bq = I32(w.bq); q.xs = I32(w.xs); q.a_re = la_re; q.a_im = la_im; q.B = B; q.TB = w.TB; q.P = P;
-                    q.ea_re = s.A_re_exp; q.ea_im = s.A_im_exp; q.run_if = &d->redo; q.x0_re = x0_re; q.x0_im = x0_im;
-                    hipLaunchKernelGGL(k_scan_quad32_asm, dim3((unsigned)((int64_t)B * P / 16), G), dim3(64), 0, st, q, go);
-                }
-                // the exact gate kernel: four byte planes of the int32 states, no range assumption; its maxima go to
-                // slots 11..13, which the residual pass picks when `redo` is set
-                CGateArgs e = a;
-                e.run_if = &d->redo; e.mx_slot = 11; e.t_lo = 0; e.t_len = L; e.bad_bits = 0;
-                const size_t smem_w = 5 * (size_t)H * 4 + 32 + 4 * (size_t)SIGTAB_WORDS + 4 * 64 * (size_t)(2 * P + 16) +
-                                      2 * 64 * (size_t)(H + 16) + 192;
-                const int64_t tlw = (int64_t)B * ((L + 63) / 64), perw = (tlw + 511) / 512;
-                const unsigned cgw = (unsigned)((tlw + perw - 1) / perw);
-                if (tr) {
-                    if (big) launch6g(k_cgate_p<4, 6, true, false, false, 64, true>, cgw, smem_w, e, 768);
-                    else launch6g(k_cgate_p<2, 3, true, false, false, 64, true>, cgw, smem_w, e);
-                } else if (big) {
-                    if (compact && P == 32) launch6g(k_cgate_p<1, 6, false, false, false, 64, true>, cgw, smem_w, e, 768);
-                    else if (compact) launch6g(k_cgate_p<2, 6, false, false, false, 64, true>, cgw, smem_w, e, 768);
-                    else launch6g(k_cgate_p<4, 6, false, false, false, 64, true>, cgw, smem_w, e, 768);
-                } else {
-                    if (compact) launch6g(k_cgate_p<1, 3, false, false, false, 64, true>, cgw, smem_w, e);
-                    else launch6g(k_cgate_p<2, 3, false, false, false, 64, true>, cgw, smem_w, e);
-                }
-            }
-            if (state_out) // carry out: the state after frame L-1, from whichever kernel wrote the stream last
-                hipLaunchKernelGGL(k_state_out, dim3((unsigned)((plane + 255) / 256), G), dim3(256), 0, st, (const void *)I32(w.xs),
-                                   pair ? 2 : (s16 ? 1 : 0), defer ? (const int32_t *)nullptr : (const int32_t *)&d->redo, B, L, P,
-                                   w.TB, state_out + (size_t)li * 2 * plane, state_out + (size_t)li * 2 * plane + plane, go);
-            if (tr && (tr->xs_re || tr->xs_im))
-                hipLaunchKernelGGL(k_unpack_native, dim3(ew_grid(N * P)), dim3(256), 0, st, (const int32_t *)I32(w.xs),
-                                   tr->xs_re, tr->xs_im, B, L, P, w.TB);
+            const size_t smem = 5 * (size_t)H * 4 + 32 + sig_lds + 2 * 64 * (size_t)(2 * p.P + 16) + 2 * 64 * (size_t)(H + 16) + 192 +
+                                (p.gate_bn ? 16 * (size_t)H : 0) +
+                                (p.pk16 && !p.gate_bn ? 2 * 64 * (size_t)(2 * H + 8) : 0); // + the u / skip / z tiles (mfma_fused.hpp COAL)
+            if (tr) launch(big ? k_cgate_p<4, 6, true> : k_cgate_p<2, 3, true>, grid_gate, threads, smem, nullptr, nullptr, a);
+            else launch(gate_kernel(p, big), grid_gate, threads, smem, gev0, gev1, a);
         }
-        if (!stage_ok("gate kernel", li)) return S5FXP_EHIP;
+        // ---- exact re-run, only if a state left the fast kernels' range (LayerDyn::redo); with
+        // S5FXP_FWD_DEFER_REDO the caller repeats the forward instead (S5FXP_ST_REDO)
+        if (!defer) {
+            if (r.quad) launch(k_scan_quad32_asm, (unsigned)((int64_t)B * p.P / 16), 64, 0, nullptr, nullptr, quad_args(li, &d->redo));
+            // the exact gate kernel: four byte planes of the int32 states, no range assumption; its maxima go to
+            // slots 11..13, which the residual pass picks when `redo` is set
+            CGateArgs e = a;
+            e.run_if = &d->redo; e.mx_slot = 11; e.bad_bits = 0;
+            const size_t smem_w = 5 * (size_t)H * 4 + 32 + 4 * (size_t)SIGTAB_WORDS + 4 * 64 * (size_t)(2 * p.P + 16) +
+                                  2 * 64 * (size_t)(H + 16) + 192;
+            auto kernel = tr ? (big ? k_cgate_p<4, 6, true, false, false, 64, true> : k_cgate_p<2, 3, true, false, false, 64, true>)
+                        : big ? ks_kernel<6>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 6, false, false, false, 64, true>; })
+                              : ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, false, false, 64, true>; });
+            launch(kernel, grid_gate_exact, threads, smem_w, nullptr, nullptr, e);
+        }
+        const size_t plane = (size_t)B * p.P;
+        if (state_out) // carry out: the state after frame L-1, from whichever kernel wrote the stream last
+            launch(k_state_out, (unsigned)((plane + 255) / 256), 256, 0, nullptr, nullptr, (const void *)I32(w.xs),
+                   r.pair ? 2 : (r.s16 ? 1 : 0), defer ? (const int32_t *)nullptr : (const int32_t *)&d->redo, B, L, p.P, w.TB,
+                   state_out + (size_t)li * 2 * plane, state_out + (size_t)li * 2 * plane + plane);
+        if (tr && (tr->xs_re || tr->xs_im))
+            hipLaunchKernelGGL(k_unpack_native, dim3(ew_grid(N * p.P)), dim3(256), 0, st, (const int32_t *)I32(w.xs),
+                               tr->xs_re, tr->xs_im, B, L, p.P, w.TB);
+        return S5FXP_OK;
+    }
+    // ---- the residual add's exponent, after the cross-rank maxima
+    int res_exponent(int li) const
+    {
+        LayerDyn *d = dyn + li;
         if (allreduce) {
             // ranks may differ in `redo`: move the valid maxima to slots 8..10 before they are exchanged
-            if (fused) hipLaunchKernelGGL(k_select_maxima, dim3(1), dim3(64), 0, st, d);
-            if (hook(8, 3)) return S5FXP_EHIP;
+            hipLaunchKernelGGL(k_select_maxima, dim3(1), dim3(64), 0, st, d);
+            if (allreduce(opts->allreduce_ctx, reinterpret_cast<float *>(d->mx + 8), 3, (void *)st)) return S5FXP_EHIP;
         }
-        const int redo_slot = (allreduce || defer) ? 8 : 11; // mode A moved them; deferred: no re-run happened
         if (!fold)
-            hipLaunchKernelGGL(k_res_finalize, dim3(1), dim3(64), 0, st, d, l.res_exp, he, l.res_bits, status, st_exps, redo_slot);
-        const bool more_layers = li + 1 < m->n_layers;
-        if (bn_ext && fold && !tr && !more_layers && !cfg.no_dec_resid) {
-            // the last layer's residual pass rides on the decoder (proj_p.hpp k_dec_p<.., RESID>)
-            dec_resid = true;
-            dz.z = I16(w.z); dz.res_bits = l.res_bits; dz.skip_bits = hb;
-            dz.hd.d = d; dz.hd.res_exp = l.res_exp; dz.hd.skip_e = he; dz.hd.redo_slot = redo_slot; dz.hd.status_exps = st_exps;
-            dz.hd.enable = 1;
-            dec_bits = l.res_bits;
-            break;
-        }
+            hipLaunchKernelGGL(k_res_finalize, dim3(1), dim3(64), 0, st, d, m->layers[li].res_exp, he, m->layers[li].res_bits, status,
+                               status_exps(li), redo_slot());
+        return S5FXP_OK;
+    }
+    int redo_slot() const { return (allreduce || defer) ? 8 : 11; } // mode A moved them; deferred: no re-run happened
+    ResidHead resid_head(int li) const
+    {
+        ResidHead hd{};
+        hd.d = dyn + li; hd.res_exp = m->layers[li].res_exp; hd.skip_e = he; hd.redo_slot = redo_slot(); hd.status_exps = status_exps(li);
+        hd.enable = fold ? 1 : 0;
+        return hd;
+    }
+
+    // ---- residual pass (+ the extremes of its output, the next layer's BatchNorm operand); the output becomes the layer input
+    void residual(int li)
+    {
+        const LayerDev &l = m->layers[li];
+        const s5fxp_layer_trace *tr = trace(li);
         if (bn_ext) {
             const bool more = li + 1 < m->n_layers;
-            float *ext_next = more ? reinterpret_cast<float *>(ws + w.ext) + (size_t)(li + 1) * 2 * H * EXT_REPS : nullptr;
-            ResidHead hd{};
-            hd.d = d; hd.res_exp = l.res_exp; hd.skip_e = he; hd.redo_slot = redo_slot; hd.status_exps = st_exps;
-            hd.enable = fold ? 1 : 0;
             const int ext_reps = (more && fold) ? EXT_REPS : 1; // the next layer's B projection derives its exponents from the extremes
-            hipLaunchKernelGGL(k_resid_minmax16<true>, dim3(rm_grid, G), dim3(RESID_THREADS), 0, st, (const int16_t *)I16(w.z),
-                               (const int16_t *)h, hn, tr ? tr->residadd : nullptr, N, H, rm_span, l.res_bits, hb, hd, ext_next, ext_reps,
-                               status, go);
+            launch(k_resid_minmax16<true>, rm_grid, RESID_THREADS, 0, nullptr, nullptr, (const int16_t *)I16(w.z), (const int16_t *)h, hn,
+                   tr ? tr->residadd : nullptr, N, H, rm_span, l.res_bits, hb, resid_head(li), more ? ext(li + 1) : nullptr, ext_reps,
+                   status);
         } else {
             hipLaunchKernelGGL(k_resid16, dim3(ew_grid(NH / 4)), dim3(256), 0, st, (const int16_t *)I16(w.z),
-                               (const int16_t *)h, hn, tr ? tr->residadd : nullptr, NH, l.res_bits, hb, (const LayerDyn *)d);
+                               (const int16_t *)h, hn, tr ? tr->residadd : nullptr, NH, l.res_bits, hb, (const LayerDyn *)(dyn + li));
         }
-        if (!stage_ok("residual pass", li)) return S5FXP_EHIP;
-        int16_t *sw = h; h = hn; hn = sw;
+        std::swap(h, hn);
         hb = l.res_bits;
-        he = DynExp{0, &d->res.eo};
+        he = DynExp{0, &dyn[li].res.eo};
     }
-    // ---- decoder
+
+    // ---- decoder (with dec_resid: after the last layer's residual pass, which it does itself)
+    void decoder(int32_t *y) const
     {
         const DenseDev &e = m->dec;
+        DecResid dz{};
         DecArgs a{};
         a.x = h; a.y = y; a.w = F.dec.w; a.bias_eff = F.dec.bias_eff; a.N = N; a.H = H; a.M = e.M;
-        a.xb = dec_resid ? dec_bits : hb; a.xe = he; a.inp_bits = e.inp_bits; a.inp_exp = e.inp_exp; a.w_exp = e.w_exp;
+        a.xb = hb; a.xe = he; a.inp_bits = e.inp_bits; a.inp_exp = e.inp_exp; a.w_exp = e.w_exp;
         a.out_bits = e.out_bits; a.out_exp = e.out_exp; a.status = status;
-        const size_t smem = 2 * 64 * (size_t)(H + 16);
-        auto launch_dec = [&](auto kernel) {
-            if (smem > 65536)
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            hipLaunchKernelGGL(kernel, dim3(grid_dec, G), dim3(384), smem, st, a, dz, go);
-        };
-        if (dec_resid) {
-            if (big) launch_dec(k_dec_p<6, true>); // 192 channels: 2 x 4 vectors of prefetch, one workgroup per CU
-            else launch_dec(k_dec_p<3, true>);
-        } else {
-            if (big) launch_dec(k_dec_p<6, false>);
-            else launch_dec(k_dec_p<3, false>);
+        if (dec_resid >= 0) {
+            const LayerDev &l = m->layers[dec_resid];
+            dz.z = I16(w.z); dz.res_bits = l.res_bits; dz.skip_bits = hb; dz.hd = resid_head(dec_resid);
+            a.xb = l.res_bits;
         }
-        if (!stage_ok("decoder", -1)) return S5FXP_EHIP;
+        const size_t smem = 2 * 64 * (size_t)(H + 16);
+        // 192 channels: 2 x 4 vectors of prefetch, one workgroup per CU
+        auto kernel = dec_resid >= 0 ? (big ? k_dec_p<6, true> : k_dec_p<3, true>) : (big ? k_dec_p<6, false> : k_dec_p<3, false>);
+        launch(kernel, grid_dec, 384, smem, nullptr, nullptr, a, dz);
     }
+};
+
+int forward_fast(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int B, int L, int32_t *y, void *workspace,
+                 int32_t *status, const s5fxp_layer_trace *traces, const s5fxp_forward_opts *opts, hipStream_t st, int G = 1,
+                 size_t ws_stride = 0)
+{
+    FusedForward f{m, opts, traces, status, st, G, B, L, reinterpret_cast<char *>(workspace), ws_stride};
+    int rc;
+    f.clear_status();
+    if ((rc = f.encoder(x, x_bits, x_exp))) return rc;
+    if (!f.stage_ok("encoder", -1)) return S5FXP_EHIP;
+    for (int li = 0; li < m->n_layers; ++li) {
+        const BnArgs bn = make_bn(m->layers[li], f.hb, f.he, f.dyn + li);
+        if ((rc = f.bn_exponents(li, bn))) return rc;
+        f.bproj(li, bn);
+        if (!f.stage_ok("B projection", li)) return S5FXP_EHIP;
+        f.recurrence(li);
+        if (!f.stage_ok("recurrence", li)) return S5FXP_EHIP;
+        if ((rc = f.gate(li, bn))) return rc;
+        if (!f.stage_ok("gate kernel", li)) return S5FXP_EHIP;
+        if ((rc = f.res_exponent(li))) return rc;
+        if (li == f.dec_resid) break;
+        f.residual(li);
+        if (!f.stage_ok("residual pass", li)) return S5FXP_EHIP;
+    }
+    f.decoder(y);
+    if (!f.stage_ok("decoder", -1)) return S5FXP_EHIP;
     return launch_rc();
 }
 

@@ -21,12 +21,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "sparsernns_amd", "libs5fxp.so")
 LLVM = "/opt/rocm/llvm/bin"
 
-# Kernels no forward can launch, each with the host condition (s5fxp_fast.hpp forward_fast, s5fxp_api.hip) that rules it out.
-# Keys are regular expressions over the demangled name without its parameter list: instantiations that a dispatch (the `cgate`
-# lambda of forward_fast, S5_DISPATCH_MW) makes for every branch of a runtime `if` whose condition can never hold for them.
+# Kernels no forward can launch, each with the host condition (s5fxp_api.hip) that rules it out.
+# Keys are regular expressions over the demangled name without its parameter list: instantiations that a dispatch
+# (S5_DISPATCH_MW) makes for every branch of a runtime `if` whose condition can never hold for them.
 ALLOW = [
-    (r"k_cgate_p<\d, 3, false, (true|false), (true|false), 32, false, (true|false), false, false>",
-     "the 32-frame gate arm runs only `if (PK_ && !cfg.cgate_ft64 && !gate_bn)`: cgate<.., PK_ = false> instantiates it unused"),
     (r"k_out2gate<(64|68), (true|false)>",
      "k_out2gate's column budget is mw_for(H), and s5fxp_model_create refuses mw_for(H) > MW_LIMIT_C = 48 (s5fxp_api.hip)"),
 ]
