@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define S5FXP_VERSION 102
+#define S5FXP_VERSION 103
 
 enum {
     S5FXP_OK = 0,
@@ -278,6 +278,23 @@ typedef struct {
 int s5fxp_model_forward(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int B, int L, int32_t *y,
                         void *workspace, size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces,
                         const s5fxp_forward_opts *opts, void *stream);
+
+/* The same forward, float32 in and float32 out: the reference's N-DNS validation step (sparseRNNs/fxprun.py:63-88) builds
+ * fxp_x = fxp_from_fp(x, x_bits, x_exp, FLOOR), runs y = model(fxp_x) and uses y.to_float().  Bit for bit what
+ *   s5fxp_from_fp(x -> xi, B*L*d_in, x_bits, x_exp, S5FXP_FLOOR);
+ *   s5fxp_model_forward(m, xi, x_bits, x_exp, B, L, yi, ...);
+ *   s5fxp_to_float(yi -> y, B*L*d_out, s5fxp_model_out_exp(m));
+ * gives -- y, status words, traces and state_out -- for every opts setting the int entry takes.  x: (B,L,d_in) float32 device;
+ * y: (B,L,d_out) float32 device; x_bits 1..32 and x_exp 0..31 are the quantisation target of x (usually the encoder's input
+ * configuration).  On the fused path the conversions happen inside the encoder and decoder kernels (no extra launch or pass);
+ * elsewhere the int32 input and output are staged in the workspace.  workspace_bytes >= G * s5fxp_workspace_bytes_f32(m, B, L)
+ * (the group stride of a grouped call).  A model whose output exponent is outside 0..31 returns S5FXP_EUNSUPPORTED. */
+int s5fxp_model_forward_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int B, int L, float *y,
+                            void *workspace, size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces,
+                            const s5fxp_forward_opts *opts, void *stream);
+/* Device workspace for one s5fxp_model_forward_f32 of B sequences of L frames: s5fxp_workspace_bytes for a model on the fused
+ * path, plus the staged int32 input and output for a generic one.  0: bad argument. */
+size_t s5fxp_workspace_bytes_f32(const s5fxp_model *m, int B, int L);
 
 /* Environment (experiments and tests only; read ONCE by s5fxp_model_create and stored in the handle, never by a forward):
  *   S5FXP_NO_PAIR, S5FXP_PAIR_GLOBAL, S5FXP_PAIRL_BLOCKS=16   recurrence kernel choice (see s5fxp_model_recurrence_kernel)

@@ -75,15 +75,29 @@ def si_snr(target: torch.Tensor, estimate: torch.Tensor) -> torch.Tensor:
     return 10.0 * torch.log10(sdr + eps)
 
 
+def _takes(model, inp_bits: int, inp_exp: int) -> bool:
+    """forward_float quantises to the encoder's input configuration: the float route applies when that is what was asked."""
+    q = getattr(model, "fxp_qconfig", None)
+    try:
+        return (int(q["encoder"]["inp_bits"]), int(q["encoder"]["inp_exp"])) == (int(inp_bits), int(inp_exp))
+    except (TypeError, KeyError):
+        return False
+
+
 def denoise(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor):
     """fxprun.py:63-78: noisy audio (B, T) -> (cleaned audio, cleaned magnitude, noisy magnitude).
 
-    ``model`` is an ``FxpRegressionModel`` (or anything callable FxpArray -> FxpArray with ``to_float``)."""
+    ``model`` is an ``FxpRegressionModel`` (or anything callable FxpArray -> FxpArray with ``to_float``).  A model with
+    ``forward_float`` whose encoder takes (inp_bits, inp_exp) runs the quantisation, the forward and to_float in one engine
+    call (s5fxp_model_forward_f32, bit for bit the same mask), unless it stores intermediates (the op-by-op path)."""
     from .fxparray import RoundingMode, fxp_from_fp
 
     mag, phase = stft_splitter(noisy)
     x = (mag - STFT_MAG_MEAN).transpose(-1, -2).contiguous()  # (B, n_seg, 257)
-    fx = fxp_from_fp(x, bits=inp_bits, exp=inp_exp, signed=True, round_mode=RoundingMode.FLOOR)
-    mask = model(fx).to_float().transpose(-1, -2)
+    if hasattr(model, "forward_float") and not getattr(model, "store_intermediates", False) and _takes(model, inp_bits, inp_exp):
+        mask = model.forward_float(x).transpose(-1, -2)
+    else:
+        fx = fxp_from_fp(x, bits=inp_bits, exp=inp_exp, signed=True, round_mode=RoundingMode.FLOOR)
+        mask = model(fx).to_float().transpose(-1, -2)
     cleaned_mag = mag * (1.0 + mask)
     return stft_mixer(cleaned_mag, phase), cleaned_mag, mag

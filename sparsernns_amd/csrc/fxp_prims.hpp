@@ -84,6 +84,15 @@ __device__ __forceinline__ float tofloat(int32_t d, int e) { return ldexpf((floa
 // f32 -> s32 as XLA converts: truncate toward zero, saturate (v_cvt_i32_f32 does exactly that).
 __device__ __forceinline__ int32_t f2i(float f) { return (int32_t)f; }
 
+// fxp_from_fp, fxparray.py:287-307, one element: clip(round_mode(x * 2^exp)) at `bits`, sc = 2^exp.  mode 0 FLOOR, 1 CEIL,
+// 2 ROUND (include/s5fxp.h).  The op (k_from_fp) and the float-input encoder (proj_p.hpp k_enc_pf) both call this.
+__device__ __forceinline__ int32_t fromfp(float x, float sc, int bits, int mode = 0)
+{
+    const float v = __fmul_rn(x, sc);
+    const float r = mode == 2 ? rintf(v) : (mode == 1 ? ceilf(v) : floorf(v));
+    return sat(f2i(r), bits);
+}
+
 // Complex ReLU, fxpmodel.py:30-45: jax.nn.relu on complex64 == lexicographic maximum(z, 0);
 // both parts round-trip through float32.
 __device__ __forceinline__ void crelu(int32_t &re, int32_t &im)

@@ -34,6 +34,9 @@ __device__ long long g_phase_prof[2048 * 8];
 #define PHASE_MARK(i, reg)
 #define PHASE_DUMP
 #endif
+#define PHASE_DECL_F
+#define PHASE_MARK_F(i, reg)
+#define PHASE_DUMP_F
 #include "mfma_bn.hpp"
 
 namespace s5 {
@@ -614,6 +617,191 @@ __global__ __launch_bounds__(384, 3) void k_enc_p(EncArgs a, float *ext, int ext
     }
 }
 
+// k_enc_p for a float32 input (s5fxp_model_forward_f32): a.x holds float rows -- the same 4 bytes per element, so loads,
+// LDS and stores are k_enc_p's.  Each element is first quantised to (xb, xe) as fxp_from_fp with FLOOR does it
+// (fxprun.py:69-75, fxp_prims.hpp fromfp), then takes k_enc_p's change_cfg and int16 check.  A copy of k_enc_p rather than
+// a shared body: k_enc_p keeps its code as it is.
+template <int NT>
+__global__ __launch_bounds__(384, 3) void k_enc_pf(EncArgs a, float *ext, int ext_reps, GroupOff go)
+{
+    {
+        const int64_t g = blockIdx.y;
+        gshift(a.x, g * go.x); gshift(a.y, g * go.ws); gshift(a.status, g * go.status); gshift(ext, g * go.ws);
+    }
+    constexpr int KS = 9, FT = 64, KP = 32 * KS + 16, NW = 6, H = 32 * NT;
+    constexpr int NU = 2 * NT / NW, SUBSTEP = NW / NT;
+    constexpr int RPW = (FT + NW - 1) / NW; // rows per wave
+    extern __shared__ __attribute__((aligned(16))) int8_t smem[];
+    int32_t *cs = reinterpret_cast<int32_t *>(smem), *be = cs + H;
+    int8_t *Xh = reinterpret_cast<int8_t *>(be + H), *Xl = Xh + FT * KP;
+    uint32_t *ehi = reinterpret_cast<uint32_t *>(Xl + FT * KP), *elo = ehi + H;
+    const int l = threadIdx.x & 63, r = l & 31, h = l >> 5, wave = threadIdx.x >> 6;
+    const int ct = wave % NT, sub0 = wave / NT, ch0 = 32 * ct + 4 * h;
+    const int64_t tiles = (a.N + FT - 1) / FT;
+    const int K = a.K, rem = K - 256;
+    uint32_t pk[16]; // low half: max, high half: 65535 - min
+#pragma unroll
+    for (int i = 0; i < 16; ++i) pk[i] = 0;
+    v4i wreg[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+        wreg[ks] = *reinterpret_cast<const v4i *>(a.w.wt + (size_t)(32 * ct + r) * a.w.Kp + 32 * ks + 16 * h);
+    for (int i = threadIdx.x; i < H; i += 384) {
+        cs[i] = a.w.cs128[i];
+        be[i] = a.bias_eff[i];
+        ehi[i] = 0;
+        elo[i] = 0;
+    }
+    const CfgOp cv = make_cfg(a.conv != 0, a.xb, a.xe, a.inp_bits, a.inp_exp);
+    const SatB so = sat_bounds(a.out_bits);
+    const float sc = ldexpf(1.f, a.xe); // the float input's quantisation scale
+    // rows wave, wave+6, ... of the tile.  Two workgroups of six waves per CU are three waves per SIMD whatever the kernel
+    // does, so it may hold 168 registers: all of a tile's rows are requested a tile ahead (dim 0.5; the two-unit phase B
+    // of dim 1.0 has no room for that: there the first RA rows are prefetched and the rest requested at the top of phase A).
+    // The prefetch is issued behind the compiler's back (scan_quad.hpp vm_wait): its own wait at the first use -- a tile
+    // later, behind phase B's stores -- would be vmcnt(0), every tile opening with a wait for the previous tile's stores.
+    constexpr int RA = NT <= 3 ? RPW : 3, RB = RPW - RA;
+    v4i rawa[RA], rawb[RB > 0 ? RB : 1];
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    auto row_base = [&](int64_t tl, int i) { // wave-uniform
+        int64_t n = tl * FT + wave_u + NW * i;
+        n = n < a.N ? n : a.N - 1;
+        return reinterpret_cast<const char *>(a.x + n * K);
+    };
+    auto row_ptr = [&](int64_t tl, int i) {
+        return reinterpret_cast<const v4i *>(row_base(tl, i) + 16 * l); // 4-byte aligned 16-byte load
+    };
+    auto convert_row = [&](const v4i &q, int f, bool &wide) {
+        int32_t v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = fromfp(__int_as_float(q[e]), sc, a.xb);
+        if (a.conv) { // uniform: usually the input already has the encoder's configuration
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = cv(v[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) wide |= (v[e] != (int32_t)(int16_t)v[e]);
+        const unsigned p01 = perm((unsigned)v[1], (unsigned)v[0], 0x05010400u), p23 = perm((unsigned)v[3], (unsigned)v[2], 0x05010400u);
+        *reinterpret_cast<int32_t *>(Xl + f * KP + 4 * l) = (int32_t)(perm(p23, p01, 0x05040100u) ^ 0x80808080u);
+        *reinterpret_cast<int32_t *>(Xh + f * KP + 4 * l) = (int32_t)perm(p23, p01, 0x07060302u);
+    };
+    int64_t tile = blockIdx.x;
+    if (tile < tiles) {
+#pragma unroll
+        for (int i = 0; i < RA; ++i) rawa[i] = gload16_hidden(row_base(tile, i), 16u * (unsigned)l);
+    }
+    bool wide = false;
+    __syncthreads();
+    PHASE_DECL_F
+    prologue_loads_done();
+    const bool even = a.M == H; // no ragged column tile: full tiles store unconditionally
+    for (; tile < tiles; tile += gridDim.x) {
+        const int64_t n0 = tile * FT;
+        PHASE_MARK_F(0, l); // loop top (includes the previous tile's closing barrier)
+        // ---- phase A
+        // the prefetched rows are older than the previous tile's stores: NU x 4 per wave on the unconditional path (the
+        // conditional one ends with a full wait)
+        vm_wait<4 * NU>(rawa);
+        if constexpr (RB > 0) {
+#pragma unroll
+            for (int i = 0; i < RB; ++i) rawb[i] = *row_ptr(tile, RA + i);
+        }
+#pragma unroll
+        for (int i = 0; i < RA; ++i)
+            if (wave_u + NW * i < FT) convert_row(rawa[i], wave_u + NW * i, wide);
+        PHASE_MARK_F(1, rawa[RA - 1][0]); // prefetched rows converted
+        if constexpr (RB > 0) {
+#pragma unroll
+            for (int i = 0; i < RB; ++i)
+                if (wave_u + NW * (RA + i) < FT) convert_row(rawb[i], wave_u + NW * (RA + i), wide);
+        }
+        PHASE_MARK_F(2, rawb[0][0]); // rows requested at the top (their HBM latency included)
+        for (int e = threadIdx.x; e < FT * rem; e += 384) { // the K-256 tail of every row
+            const int f = e / rem, k = 256 + e % rem;
+            int64_t n = n0 + f;
+            n = n < a.N ? n : a.N - 1;
+            const int32_t v = cv(fromfp(__int_as_float(a.x[n * K + k]), sc, a.xb));
+            wide |= (v != (int32_t)(int16_t)v);
+            Xl[f * KP + k] = (int8_t)((v & 0xff) ^ 0x80);
+            Xh[f * KP + k] = (int8_t)(v >> 8);
+        }
+        if (tile + gridDim.x < tiles) {
+#pragma unroll
+            for (int i = 0; i < RA; ++i) rawa[i] = gload16_hidden(row_base(tile + gridDim.x, i), 16u * (unsigned)l); // in flight during phase B
+        }
+        PHASE_MARK_F(3, l); // tail column + prefetch issue
+        __syncthreads();
+        PHASE_MARK_F(4, l); // mid barrier
+        // ---- phase B
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int sub = sub0 + u * SUBSTEP;
+            const int64_t n = n0 + 32 * sub + r;
+            v16i acc;
+            mfma_planes<KS>(acc, wreg, Xh + (32 * sub + r) * KP + 16 * h, Xl + (32 * sub + r) * KP + 16 * h, cs + ch0);
+            PHASE_MARK_F(5, acc[15]); // operand reads + MFMA chain, complete
+            auto group = [&](int g) {
+                const int ch = ch0 + 8 * g;
+                const v4i bv = *reinterpret_cast<const v4i *>(be + ch);
+                int32_t o[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    int32_t v = sat(asr(acc[4 * g + e], a.rs), so);
+                    v = sat(wadd(v, bv[e]), so);
+                    o[e] = v < 0 ? 0 : v;
+                    // (v, 65535 - v) as a u16 pair; one packed max keeps both running extremes
+                    const uint32_t t = (uint32_t)__umul24((unsigned)o[e], 0x10001u) ^ 0xffff0000u;
+                    pk[4 * g + e] = __builtin_bit_cast(
+                        uint32_t, __builtin_elementwise_max(__builtin_bit_cast(v2u16, pk[4 * g + e]), __builtin_bit_cast(v2u16, t)));
+                }
+                *reinterpret_cast<v2i *>(a.y + n * a.M + ch) = pack4_i16(o[0], o[1], o[2], o[3]);
+            };
+            if (even && n0 + FT <= a.N) { // no control flow around the stores (see vm_wait above)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) group(g);
+            } else {
+                if (n < a.N) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+                        if (ch0 + 8 * g < a.M) group(g);
+                }
+                prologue_loads_done(); // nothing in flight behind a conditional store
+            }
+        }
+        PHASE_MARK_F(6, pk[15]); // epilogue arithmetic done, stores issued
+        __syncthreads(); // planes are single-buffered
+    }
+    PHASE_DUMP_F;
+    if (__any(wide) && l == 0) atomicOr(a.status, ST_WIDE_INPUT);
+    if (!ext) return;
+    // ---- extremes: fold the 32 frame lanes of each half wave, then the waves of the workgroup (LDS), then one
+    // atomic per channel and bound
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        uint32_t v = pk[i];
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) {
+            const uint32_t w = (uint32_t)__shfl_xor((int)v, o, 64);
+            const uint32_t lo16 = (v & 0xffffu) > (w & 0xffffu) ? (v & 0xffffu) : (w & 0xffffu);
+            const uint32_t hi16 = (v >> 16) > (w >> 16) ? (v >> 16) : (w >> 16);
+            v = lo16 | (hi16 << 16);
+        }
+        const int ch = ch0 + 8 * (i >> 2) + (i & 3);
+        if (r == 0 && ch < a.M) {
+            atomicMax(&ehi[ch], v & 0xffffu);
+            atomicMax(&elo[ch], v >> 16);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < a.M) { // max = ehi, min = 65535 - elo; as the positive floats of mfma_bn.hpp
+        const int c = threadIdx.x;
+        uint32_t *dst = reinterpret_cast<uint32_t *>(ext) + (ext_reps > 1 ? (int)(blockIdx.x % ext_reps) : 0) * 2 * a.M;
+        atomicMax(dst + c, __float_as_uint(EXT_BIAS - (float)(65535 - (int)elo[c])));
+        atomicMax(dst + a.M + c, __float_as_uint(EXT_BIAS + (float)ehi[c]));
+    }
+}
+
+
 // ---------------------------------------------------------------------------------------------
 // where masked-off lanes of a store send their value instead (never read)
 __device__ int32_t g_store_sink[64];
@@ -788,5 +976,167 @@ __global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_p(DecArgs
         __syncthreads(); // planes are single-buffered
     }
 }
+
+// k_dec_p with a float32 output (s5fxp_model_forward_f32): every value is stored as to_float of k_dec_p's result
+// (fxparray.py:72-73, fxp_prims.hpp tofloat, rounded as k_to_float rounds), one 4-byte store per value on the same
+// addresses, so the store count per tile (vm_wait<48>) holds; ragged column tiles still go to g_store_sink.  A copy of
+// k_dec_p rather than a shared body: k_dec_p keeps its code as it is.
+template <int KS, bool RESID>
+__global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_pf(DecArgs a, DecResid rz, GroupOff go)
+{
+    {
+        const int64_t g = blockIdx.y;
+        gshift(a.x, g * go.ws); gshift(a.y, g * go.y); gshift(a.xe.dyn, g * go.ws); gshift(a.status, g * go.status);
+        if constexpr (RESID) {
+            gshift(rz.z, g * go.ws); gshift_nn(rz.hd.d, g * go.ws); gshift(rz.hd.skip_e.dyn, g * go.ws);
+            gshift_nn(rz.hd.status_exps, g * go.status);
+        }
+    }
+    constexpr int H = 32 * KS, FT = 64, KP = H + 16, NW = 6, CT = 9, CPW = 3;
+    constexpr int VPF = H / 8, NV = FT * VPF / 384;
+    static_assert(FT * VPF % 384 == 0, "tile shape");
+    extern __shared__ __attribute__((aligned(16))) int8_t smem[];
+    int8_t *Xh = smem, *Xl = Xh + FT * KP;
+    const int l = threadIdx.x & 63, r = l & 31, h = l >> 5, wave = threadIdx.x >> 6;
+    const int sub = wave / 3, c0 = wave % 3;
+    const int64_t tiles = (a.N + FT - 1) / FT;
+    AddCb rp{};
+    if constexpr (RESID) {
+        __shared__ AddCb sp;
+        if (rz.hd.enable) {
+            if (threadIdx.x == 0) {
+                sp = finalize_add_cb(rz.hd.d->mx + (rz.hd.d->redo ? rz.hd.redo_slot : 8), rz.hd.res_exp, rz.hd.skip_e.get(), rz.res_bits, a.status);
+                if (blockIdx.x == 0) {
+                    rz.hd.d->res = sp;
+                    rz.hd.status_exps[4] = sp.eo;
+                }
+            }
+            __syncthreads();
+            rp = sp;
+        } else {
+            rp = rz.hd.d->res;
+        }
+    }
+    const int xe0 = RESID ? rp.eo : a.xe.get();
+    const bool conv = a.xb > a.inp_bits || xe0 > a.inp_exp;
+    int rs = (conv ? a.inp_exp : xe0) + a.w_exp - a.out_exp;
+    if (rs < 0 || rs > 31) {
+        if (threadIdx.x == 0 && blockIdx.x == 0) atomicOr(a.status, ST_NEGSHIFT);
+        rs = rs < 0 ? 0 : 31;
+    }
+    const CfgOp cv = make_cfg(conv, a.xb, xe0, a.inp_bits, a.inp_exp);
+    const SatB so = sat_bounds(a.out_bits);
+    AddCbV rpv{};
+    if constexpr (RESID) rpv = make_add_cb_v(rp, rz.res_bits, rz.skip_bits, rz.res_bits);
+    v4i wreg[CPW][KS];
+    int32_t csv[CPW], bev[CPW];
+#pragma unroll
+    for (int c = 0; c < CPW; ++c) {
+        const int col = 32 * (c0 + 3 * c) + r;
+        csv[c] = a.w.cs128[col];
+        bev[c] = a.bias_eff[col];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+            wreg[c][ks] = *reinterpret_cast<const v4i *>(a.w.wt + (size_t)col * a.w.Kp + 32 * ks + 16 * h);
+    }
+    v4i raw[NV], rawz[RESID ? NV : 1];
+    auto fetch = [&](int64_t tl) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int v = threadIdx.x + 384 * i;
+            const int64_t left = a.N - tl * FT; // frames from the tile's first to the end of the tensor (wave-uniform)
+            int f = v / VPF;
+            f = f < left ? f : (int)left - 1;
+            if constexpr (RESID)
+                rawz[i] = gload16_hidden(reinterpret_cast<const char *>(rz.z + tl * FT * H), 2u * (unsigned)(f * H + 8 * (v % VPF)));
+            // issued behind the compiler's back (see vm_wait): its wait-count pass would otherwise guard the first use of
+            // these registers, a tile later, with vmcnt(0) -- behind the 48 stores of this tile's phase B
+            raw[i] = gload16_hidden(reinterpret_cast<const char *>(a.x + tl * FT * H), 2u * (unsigned)(f * H + 8 * (v % VPF)));
+        }
+    };
+    int64_t tile = blockIdx.x;
+    if (tile < tiles) fetch(tile);
+    prologue_loads_done();
+    for (; tile < tiles; tile += gridDim.x) {
+        const int64_t n0 = tile * FT;
+        // the prefetched rows are older than the previous tile's 3 x 16 stores per wave (every tile but the tensor's last is
+        // full and stores unconditionally; that last one has no successor)
+        vm_wait<3 * 16>(raw);
+        if constexpr (RESID) vm_wait<3 * 16>(rawz);
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int v = threadIdx.x + 384 * i, f = v / VPF, og = v % VPF;
+            int32_t x[8];
+            unpack8_i16(raw[i], x);
+            if constexpr (RESID) {
+                int32_t z[8];
+                unpack8_i16(rawz[i], z);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const int32_t rr = add_cb_apply(z[e], x[e], rpv);
+                    x[e] = rr < 0 ? 0 : rr;
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[e] = cv(x[e]);
+            v2i hi, lo;
+            planes8_from_i32(x, hi, lo);
+            *reinterpret_cast<v2i *>(Xh + f * KP + 8 * og) = hi;
+            *reinterpret_cast<v2i *>(Xl + f * KP + 8 * og) = lo;
+        }
+        if (tile + gridDim.x < tiles) fetch(tile + gridDim.x);
+        __syncthreads();
+        const int8_t *rowh = Xh + (32 * sub + r) * KP + 16 * h, *rowl = Xl + (32 * sub + r) * KP + 16 * h;
+        const int64_t nb = n0 + 32 * sub + 4 * h; // frame of accumulator register 0
+#pragma unroll
+        for (int c = 0; c < CPW; ++c) {
+            const int col = 32 * (c0 + 3 * c) + r;
+            v16i acc;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] = 0;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(*reinterpret_cast<const v4i *>(rowh + 32 * ks), wreg[c][ks], acc, 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] = wadd(wshl(acc[i], 8), csv[c]);
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(*reinterpret_cast<const v4i *>(rowl + 32 * ks), wreg[c][ks], acc, 0, 0, 0);
+            // Stores without control flow around them on full tiles (all but the tensor's last): lanes of the ragged last
+            // column tile (col >= M) write to a sink word instead of being masked off.  Every conditional store would make
+            // the number of memory operations in flight unknowable to the compiler's wait-count pass, and the wait it
+            // then puts at the top of the next tile -- for the rows prefetched BEFORE these stores -- degenerates to
+            // vmcnt(0): every tile would begin by waiting for the previous tile's stores to be acknowledged.
+            const bool okc = col < a.M;
+            char *yl = okc ? reinterpret_cast<char *>(a.y + n0 * a.M) + 4u * (unsigned)((32 * sub + 4 * h) * a.M + col)
+                           : reinterpret_cast<char *>(as_global(&g_store_sink[l]));
+            const unsigned ystep = okc ? 4u * (unsigned)a.M : 0u;
+            if (n0 + FT <= a.N) {
+                char *yp = yl; // a running pointer: sixteen hoisted offsets per column tile would cost the kernel its occupancy
+#pragma unroll
+                for (int i = 0; i < 16; ++i) { // frames (i & 3) + 8 * (i >> 2)
+                    const int32_t v = sat(asr(acc[i], rs), so);
+                    *reinterpret_cast<float *>(yp) = tofloat(sat(wadd(v, bev[c]), so), a.out_exp);
+                    yp += (i & 3) == 3 ? 5 * ystep : ystep;
+                }
+            } else {
+                char *yp = yl;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int fo = (i & 3) + 8 * (i >> 2);
+                    if (nb + fo < a.N) {
+                        const int32_t v = sat(asr(acc[i], rs), so);
+                        *reinterpret_cast<float *>(yp) = tofloat(sat(wadd(v, bev[c]), so), a.out_exp);
+                    }
+                    yp += (i & 3) == 3 ? 5 * ystep : ystep;
+                }
+                prologue_loads_done(); // the tensor's last tile: nothing is left in flight on this path
+            }
+            __builtin_amdgcn_sched_barrier(0); // one column tile at a time: interleaved, the three of a wave do not fit its registers
+        }
+        __syncthreads(); // planes are single-buffered
+    }
+}
+
 
 } // namespace s5

@@ -922,6 +922,62 @@ extern "C" int s5fxp_model_forward(const s5fxp_model *m, const int32_t *x, int x
     return launch_rc();
 }
 
+// The float-in, float-out forward of fxprun.py:63-88.  A fused model converts inside its encoder and decoder kernels (proj_p.hpp
+// k_enc_pf / k_dec_pf) and needs no more workspace than an int forward; a generic one stages the int32 input and output behind
+// the int forward's workspace and runs k_from_fp -> the int forward -> k_to_float.
+namespace {
+inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+}
+
+extern "C" size_t s5fxp_workspace_bytes_f32(const s5fxp_model *m, int B, int L)
+{
+    const size_t ws = s5fxp_workspace_bytes(m, B, L);
+    if (!ws || m->fast) return ws;
+    const size_t N = (size_t)B * L;
+    return ws + al256(N * m->d_in * 4) + al256(N * m->d_out * 4);
+}
+
+extern "C" int s5fxp_model_forward_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int B, int L, float *y,
+                                       void *workspace, size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces,
+                                       const s5fxp_forward_opts *opts, void *stream)
+{
+    if (!m || !x || !y || !workspace || !status || B < 1 || L < 1 || x_bits < 1 || x_bits > 32 || x_exp < 0 || x_exp > 31)
+        return S5FXP_EBADARG;
+    if (m->dec.out_exp < 0 || m->dec.out_exp > 31) return S5FXP_EUNSUPPORTED; // the range s5fxp_to_float takes
+    const int G = opts && opts->groups > 1 ? opts->groups : 1;
+    const size_t ws_one = s5fxp_workspace_bytes_f32(m, B, L);
+    if (workspace_bytes < (size_t)G * ws_one) return S5FXP_EWORKSPACE;
+    if (G > 1) {
+        // the same split as s5fxp_model_forward: one set of fused launches, or one (fused or generic) forward per group
+        if (m->fast && !traces && !opts->allreduce && fast_bn_ext(m) && stream_extent_ok(m, L))
+            return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), G, ws_one, true);
+        const size_t plane = (size_t)m->n_layers * 2 * B * (m->P ? m->P : 1);
+        for (int g = 0; g < G; ++g) {
+            s5fxp_forward_opts o = *opts;
+            o.groups = 1;
+            if (o.state_in) o.state_in += g * plane;
+            if (o.state_out) o.state_out += g * plane;
+            const int rc = s5fxp_model_forward_f32(m, x + (size_t)g * B * L * m->d_in, x_bits, x_exp, B, L, y + (size_t)g * B * L * m->d_out,
+                                                   reinterpret_cast<char *>(workspace) + g * ws_one, ws_one,
+                                                   status + (size_t)g * S5FXP_STATUS_WORDS, traces ? traces + (size_t)g * m->n_layers : nullptr,
+                                                   &o, stream);
+            if (rc) return rc;
+        }
+        return S5FXP_OK;
+    }
+    if (!stream_extent_ok(m, L)) return S5FXP_EBADARG;
+    if (m->fast) return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), 1, 0, true);
+    // generic: the three steps, on int32 copies staged behind the int forward's workspace
+    const size_t ws_int = s5fxp_workspace_bytes(m, B, L);
+    const int64_t N = (int64_t)B * L;
+    int32_t *xi = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(workspace) + ws_int);
+    int32_t *yi = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(xi) + al256((size_t)N * m->d_in * 4));
+    int rc;
+    if ((rc = s5fxp_from_fp(x, xi, N * m->d_in, x_bits, x_exp, S5FXP_FLOOR, stream))) return rc;
+    if ((rc = s5fxp_model_forward(m, xi, x_bits, x_exp, B, L, yi, workspace, ws_int, status, traces, opts, stream))) return rc;
+    return s5fxp_to_float(yi, y, N * m->d_out, m->dec.out_exp, stream);
+}
+
 // FxpSequenceLayer.forward for ONE layer of a created model (fxpmodel.py:1110-1161): BatchNorm -> SSM -> ReLU -> out2 ->
 // sigmoid -> gate -> residual compute_best add -> ReLU, on the generic int32 kernels (exact for any int32 operands; the
 // fused kernels exist for whole forwards, where the int16 inter-kernel planes pay off).

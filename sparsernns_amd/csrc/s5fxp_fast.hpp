@@ -437,6 +437,7 @@ struct FusedForward {
     int G, B, L;
     char *ws;
     size_t ws_stride; // bytes between the groups' workspaces (0: this forward's size)
+    bool f32 = false; // s5fxp_model_forward_f32: float32 input and output, converted inside the encoder and the decoder
 
     const FastModel &F = *m->fast;
     const ModelCfg &cfg = m->cfg;
@@ -543,11 +544,12 @@ struct FusedForward {
     }
 
     // ---- encoder + ReLU
-    int encoder(const int32_t *x, int x_bits, int x_exp) const
+    int encoder(const void *x, int x_bits, int x_exp) const
     {
         const DenseDev &e = m->enc;
         EncArgs a{};
-        a.x = x; a.y = h; a.w = F.enc.w; a.bias_eff = F.enc.bias_eff; a.N = N; a.K = e.K; a.M = e.M;
+        // f32: float rows, read as their bits by k_enc_pf
+        a.x = reinterpret_cast<const int32_t *>(x); a.y = h; a.w = F.enc.w; a.bias_eff = F.enc.bias_eff; a.N = N; a.K = e.K; a.M = e.M;
         a.xb = x_bits; a.xe = x_exp; a.inp_bits = e.inp_bits; a.inp_exp = e.inp_exp;
         a.conv = (x_bits > e.inp_bits || x_exp > e.inp_exp) ? 1 : 0;
         a.rs = (a.conv ? e.inp_exp : x_exp) + e.w_exp - e.out_exp;
@@ -558,7 +560,8 @@ struct FusedForward {
         // lets the last workgroup derive layer 0's BatchNorm exponents (mfma_bn.hpp ResidTail)
         float *ext0 = bn_ext ? ext(0) : nullptr;
         const int ext_reps = (ext0 && !allreduce) ? EXT_REPS : 1; // the consumer (k_bproj_p's prologue) folds the replicas
-        launch(big ? k_enc_p<6> : k_enc_p<3>, grid_enc, 384, smem, nullptr, nullptr, a, ext0, ext_reps);
+        auto kernel = f32 ? (big ? k_enc_pf<6> : k_enc_pf<3>) : (big ? k_enc_p<6> : k_enc_p<3>);
+        launch(kernel, grid_enc, 384, smem, nullptr, nullptr, a, ext0, ext_reps);
         return S5FXP_OK;
     }
 
@@ -782,12 +785,13 @@ struct FusedForward {
     }
 
     // ---- decoder (with dec_resid: after the last layer's residual pass, which it does itself)
-    void decoder(int32_t *y) const
+    void decoder(void *y) const
     {
         const DenseDev &e = m->dec;
         DecResid dz{};
         DecArgs a{};
-        a.x = h; a.y = y; a.w = F.dec.w; a.bias_eff = F.dec.bias_eff; a.N = N; a.H = H; a.M = e.M;
+        // f32: k_dec_pf stores float bits
+        a.x = h; a.y = reinterpret_cast<int32_t *>(y); a.w = F.dec.w; a.bias_eff = F.dec.bias_eff; a.N = N; a.H = H; a.M = e.M;
         a.xb = hb; a.xe = he; a.inp_bits = e.inp_bits; a.inp_exp = e.inp_exp; a.w_exp = e.w_exp;
         a.out_bits = e.out_bits; a.out_exp = e.out_exp; a.status = status;
         if (dec_resid >= 0) {
@@ -797,16 +801,18 @@ struct FusedForward {
         }
         const size_t smem = 2 * 64 * (size_t)(H + 16);
         // 192 channels: 2 x 4 vectors of prefetch, one workgroup per CU
-        auto kernel = dec_resid >= 0 ? (big ? k_dec_p<6, true> : k_dec_p<3, true>) : (big ? k_dec_p<6, false> : k_dec_p<3, false>);
+        auto kernel = f32 ? (dec_resid >= 0 ? (big ? k_dec_pf<6, true> : k_dec_pf<3, true>) : (big ? k_dec_pf<6, false> : k_dec_pf<3, false>))
+                          : (dec_resid >= 0 ? (big ? k_dec_p<6, true> : k_dec_p<3, true>) : (big ? k_dec_p<6, false> : k_dec_p<3, false>));
         launch(kernel, grid_dec, 384, smem, nullptr, nullptr, a, dz);
     }
 };
 
-int forward_fast(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int B, int L, int32_t *y, void *workspace,
+// x / y: int32 tensors, or float32 ones with f32 (s5fxp_model_forward_f32); the same 4 bytes per element either way
+int forward_fast(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int B, int L, void *y, void *workspace,
                  int32_t *status, const s5fxp_layer_trace *traces, const s5fxp_forward_opts *opts, hipStream_t st, int G = 1,
-                 size_t ws_stride = 0)
+                 size_t ws_stride = 0, bool f32 = false)
 {
-    FusedForward f{m, opts, traces, status, st, G, B, L, reinterpret_cast<char *>(workspace), ws_stride};
+    FusedForward f{m, opts, traces, status, st, G, B, L, reinterpret_cast<char *>(workspace), ws_stride, f32};
     int rc;
     f.clear_status();
     if ((rc = f.encoder(x, x_bits, x_exp))) return rc;

@@ -728,12 +728,7 @@ __global__ __launch_bounds__(256) void k_resid(const int32_t *__restrict__ z, co
 __global__ void k_from_fp(const float *__restrict__ x, int32_t *__restrict__ y, int64_t n, int bits, int exp, int mode)
 {
     const float sc = ldexpf(1.f, exp);
-    S5_GRID_STRIDE(i, n)
-    {
-        const float v = __fmul_rn(x[i], sc);
-        const float r = mode == 2 ? rintf(v) : (mode == 1 ? ceilf(v) : floorf(v));
-        y[i] = sat(f2i(r), bits);
-    }
+    S5_GRID_STRIDE(i, n) y[i] = fromfp(x[i], sc, bits, mode);
 }
 
 __global__ void k_to_float(const int32_t *__restrict__ x, float *__restrict__ y, int64_t n, int exp)

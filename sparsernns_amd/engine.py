@@ -1,4 +1,5 @@
-"""Fused forward of the fixed-point S5 model: Python driver of ``s5fxp_model_forward``.
+"""Fused forward of the fixed-point S5 model: Python driver of ``s5fxp_model_forward`` (int32 in and out) and
+``s5fxp_model_forward_f32`` (float32 in and out, the reference's validation step, sparseRNNs/fxprun.py:63-88).
 
 ``Engine`` takes the INTEGER model in the reference's ``export()`` layout
 (sparseRNNs/fxpmodel.py:1441-1458 and the nested exports it gathers), hands it to the C ABI,
@@ -161,12 +162,12 @@ class Engine:
             st = self._status[lane] = torch.zeros(groups * _lib.STATUS_WORDS, dtype=torch.int32, device=self.device)
         return st
 
-    def workspace(self, B: int, L: int, lane: int = 0, groups: int = 1) -> torch.Tensor:
+    def workspace(self, B: int, L: int, lane: int = 0, groups: int = 1, f32: bool = False) -> torch.Tensor:
         key, ws = self._wsl.get(lane, (None, None))
-        if key != (B, L, groups):
-            n = groups * lib.s5fxp_workspace_bytes(self._h, B, L)
-            ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-            self._wsl[lane] = ((B, L, groups), ws)
+        if key != (B, L, groups, f32):
+            per = lib.s5fxp_workspace_bytes_f32(self._h, B, L) if f32 else lib.s5fxp_workspace_bytes(self._h, B, L)
+            ws = torch.empty(groups * per, dtype=torch.uint8, device=self.device)
+            self._wsl[lane] = ((B, L, groups, f32), ws)
         return ws
 
     def enqueue(self, x: torch.Tensor, x_bits: int, x_exp: int, y: torch.Tensor, B: int, L: int,
@@ -181,10 +182,19 @@ class Engine:
         (include/s5fxp.h, s5fxp_forward_opts::groups).
 
         flags: _lib.FWD_DEFER_REDO drops the (normally idle) gated exact re-run launches -- the caller must then
-        read the status words and repeat with _lib.FWD_EXACT when ST_REDO is set (``forward`` does)."""
+        read the status words and repeat with _lib.FWD_EXACT when ST_REDO is set (``forward`` does).
+
+        x and y are both int32 (``s5fxp_model_forward``) or both float32 (``s5fxp_model_forward_f32``: x_bits / x_exp are then
+        the quantisation target of the float input, and y receives to_float of the output)."""
+        if x.dtype == torch.int32 and y.dtype == torch.int32:
+            f32 = False
+        elif x.dtype == torch.float32 and y.dtype == torch.float32:
+            f32 = True
+        else:
+            raise ValueError(f"x and y must both be int32 or both float32, got {x.dtype} and {y.dtype}")
         if groups > 1 and (traces is not None or allreduce is not None):
             raise ValueError("a grouped forward takes neither traces nor a cross-rank hook: run the groups one by one")
-        ws = self.workspace(B, L, lane, groups)
+        ws = self.workspace(B, L, lane, groups, f32)
         self._groups[lane] = groups
         tr = None
         if traces is not None:
@@ -227,10 +237,10 @@ class Engine:
                     raise ValueError(f"{name} must be a contiguous int32 device tensor of shape {want}")
                 setattr(opts, name, t.data_ptr())
         self._cb_keep = opts
-        check(lib.s5fxp_model_forward(self._h, x.data_ptr(), x_bits, x_exp, B, L, y.data_ptr(), ws.data_ptr(),
-                                      ws.numel(), self.lane_status(lane, groups).data_ptr(),
-                                      C.cast(tr, C.POINTER(LayerTrace)) if tr is not None else None, C.byref(opts),
-                                      torch.cuda.current_stream().cuda_stream), "s5fxp_model_forward")
+        entry, name = (lib.s5fxp_model_forward_f32, "s5fxp_model_forward_f32") if f32 else (lib.s5fxp_model_forward, "s5fxp_model_forward")
+        check(entry(self._h, x.data_ptr(), x_bits, x_exp, B, L, y.data_ptr(), ws.data_ptr(), ws.numel(),
+                    self.lane_status(lane, groups).data_ptr(), C.cast(tr, C.POINTER(LayerTrace)) if tr is not None else None,
+                    C.byref(opts), torch.cuda.current_stream().cuda_stream), name)
 
     def check_status(self, lane: int = 0) -> np.ndarray:
         """Reads the status words back (one sync) and raises what the reference would have raised.  After a grouped
@@ -285,6 +295,59 @@ class Engine:
         out = FxpArray(y, self.out_bits, self.out_exp, True)
         return (out, tr) if traces else out
 
+
+    def _float_input(self, x: torch.Tensor, x_bits: Optional[int], x_exp: Optional[int]):
+        data = torch.as_tensor(x)
+        if data.dtype != torch.float32:
+            raise ValueError(f"expected a float32 tensor, got {data.dtype}")
+        data = data.to(self.device).contiguous()
+        if data.shape[-1] != self.d_in:
+            raise ValueError(f"expected last dim {self.d_in}, got {tuple(data.shape)}")
+        return (data, self.inp_bits if x_bits is None else int(x_bits), self.inp_exp if x_exp is None else int(x_exp))
+
+    def forward_float(self, x: torch.Tensor, x_bits: Optional[int] = None, x_exp: Optional[int] = None,
+                      check_status: bool = True, allreduce: Optional[Callable] = None) -> torch.Tensor:
+        """The reference's validation step (sparseRNNs/fxprun.py:63-88) in one call: x float32 (B,L,d_in) or (L,d_in) ->
+        float32 (.., d_out), bit for bit ``forward(fxp_from_fp(x, x_bits, x_exp, FLOOR)).to_float()``.  x_bits / x_exp default
+        to the encoder's input configuration.  The conversions run inside the encoder and decoder kernels on the fused path.
+        check_status / allreduce as in ``forward``."""
+        data, xb, xe = self._float_input(x, x_bits, x_exp)
+        B, L = (1, data.shape[0]) if data.ndim == 2 else (data.shape[0], data.shape[1])
+        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=torch.float32, device=data.device)
+        if B * L == 0:
+            return y
+        if not check_status or allreduce:
+            self.enqueue(data, xb, xe, y, B, L, allreduce=allreduce)  # self-contained: exact re-run enqueued, gated
+            if check_status:
+                self.check_status()
+        else:
+            self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, B, L, flags=fl), self.check_status)
+        return y
+
+    def forward_batches_float(self, x: torch.Tensor, batch: int, x_bits: Optional[int] = None,
+                              x_exp: Optional[int] = None) -> torch.Tensor:
+        """``forward_batches`` float32 in and out: x (G * batch, L, d_in) -> (G * batch, L, d_out), one set of launches."""
+        data, xb, xe = self._float_input(x, x_bits, x_exp)
+        if data.ndim != 3 or data.shape[0] % batch:
+            raise ValueError(f"expected (G * {batch}, L, {self.d_in}), got {tuple(data.shape)}")
+        G, L = data.shape[0] // batch, data.shape[1]
+        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=torch.float32, device=data.device)
+        if G * batch * L:
+            self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, batch, L, flags=fl, groups=G), self.check_status)
+        return y
+
+    def forward_chunk_float(self, x: torch.Tensor, state: Optional[torch.Tensor] = None, x_bits: Optional[int] = None,
+                            x_exp: Optional[int] = None):
+        """``forward_chunk`` float32 in and out: returns (y float32, new_state); `state` is not modified."""
+        data, xb, xe = self._float_input(x, x_bits, x_exp)
+        B, L = (1, data.shape[0]) if data.ndim == 2 else (data.shape[0], data.shape[1])
+        if B * L == 0:
+            raise ValueError("empty chunk")
+        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=torch.float32, device=data.device)
+        new_state = torch.empty((self.n_layers, 2, B, self.P), dtype=torch.int32, device=data.device)
+        self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, B, L, flags=fl, state_in=state, state_out=new_state),
+                        self.check_status)
+        return y, new_state
 
     def layer_forward(self, layer: int, x: FxpArray, traces: bool = False):
         """One ``FxpSequenceLayer.forward`` (sparseRNNs/fxpmodel.py:1110-1161) through ``s5fxp_layer_forward``: x is the

@@ -612,6 +612,18 @@ class FxpRegressionModel(FxpModule):  # :1380-1458
                 self._generic_engine = Engine(self.export(), flags=self.engine_flags | MODEL_FORCE_GENERIC)
             return self._generic_engine.forward(x, allreduce=self.exponent_allreduce)
 
+    def forward_float(self, x):
+        """float32 (B,L,d_in) -> float32 (B,L,d_out): ``forward(fxp_from_fp(x, inp_bits, inp_exp, FLOOR)).to_float()`` in one
+        engine call (fxprun.py:63-88), with the same fallback to the 32-bit kernels as ``forward``."""
+        try:
+            return self.engine().forward_float(x, allreduce=self.exponent_allreduce)
+        except OverflowError:
+            from ._lib import MODEL_FORCE_GENERIC
+            from .engine import Engine
+            if self._generic_engine is None:
+                self._generic_engine = Engine(self.export(), flags=self.engine_flags | MODEL_FORCE_GENERIC)
+            return self._generic_engine.forward_float(x, allreduce=self.exponent_allreduce)
+
     def export(self):
         encoder_data, decoder_data = self.encoder.export(), self.decoder.export()
         return dict(

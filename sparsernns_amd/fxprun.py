@@ -1,7 +1,7 @@
 """fxprun-style command line for the MI355X fixed-point S5 path.
 
 Mirrors what the reference's ``sparseRNNs/fxprun.py`` does around the model (``run_validation`` :63-88: float input
--> ``fxp_from_fp`` -> ``model(fxp_x)`` -> ``to_float``; ``run_verification`` :476-731: the same forward with
+-> ``fxp_from_fp`` -> ``model(fxp_x)`` -> ``to_float``, here one float-in, float-out engine call for --outputs and --steps; ``run_verification`` :476-731: the same forward with
 ``store_intermediates`` and a per-layer report), with the pieces that need JAX pickles or the NDNS dataset
 replaced by interchange files this repo can read:
 
@@ -162,14 +162,18 @@ def main(argv=None) -> int:
     B, L = x.shape[0], x.shape[1]
     # fxprun.py:69-75: signed, FLOOR, the encoder's input configuration
     fx = fxp_from_fp(x, bits=inp_bits, exp=inp_exp, signed=True, round_mode=RoundingMode.FLOOR)
+    # the validation step itself (fxprun.py:63-88) is float in, float out: one engine call does quantisation, forward and
+    # to_float (s5fxp_model_forward_f32); the int forward stays for --verify
+    xf = torch.from_numpy(x).to(eng.device)
 
     y = eng.forward(fx)
+    yf = eng.forward_float(xf, inp_bits, inp_exp)
     st = eng.check_status()
     print(f"[fxprun] output {tuple(y.data.shape)} bits={y.bits} exp={y.exp}  status=0x{int(st[0]):x}")
     for i, e in enumerate(eng.layer_exponents()):
         print(f"[fxprun] layer {i} compute_best exponents: " + ", ".join(f"{k}={v}" for k, v in e.items()))
     if args.outputs:
-        np.save(args.outputs, y.to_float().cpu().numpy())
+        np.save(args.outputs, yf.cpu().numpy())
 
     if args.verify:
         if model is None:
@@ -180,6 +184,9 @@ def main(argv=None) -> int:
         ye = eager(fx)
         same = bool(torch.equal(ye.data, y.data)) and (ye.bits, ye.exp) == (y.bits, y.exp)
         print(f"[fxprun] verification: op-by-op forward == fused forward: {same}")
+        fsame = bool(torch.equal(yf, y.to_float()))
+        print(f"[fxprun] verification: float entry == to_float(int forward): {fsame}")
+        same = same and fsame
         for i, layer in enumerate(eager.encoder.seq_layers):
             names = sorted(layer.intermediates.keys()) + sorted(f"mixer.{k}" for k in layer.mixer.intermediates.keys())
             print(f"[fxprun]   layer {i} intermediates: {', '.join(names)}")
@@ -212,18 +219,18 @@ def main(argv=None) -> int:
         print(f"[fxprun] wrote {args.export}.npz / .json")
 
     if args.steps > 0:
-        yo = [torch.empty_like(y.data) for _ in range(max(1, args.inflight))]
+        yo = [torch.empty_like(yf) for _ in range(max(1, args.inflight))]
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if args.inflight > 1:
             runner = InflightRunner(eng, args.inflight)
             for k in range(args.steps):
                 # the same input every time: the status check at drain() speaks for every step
-                runner.submit(fx.data, fx.bits, fx.exp, yo[k % args.inflight], B, L, check=False)
+                runner.submit(xf, inp_bits, inp_exp, yo[k % args.inflight], B, L, check=False)
             runner.drain()
         else:
             for _ in range(args.steps):
-                eng.enqueue(fx.data, fx.bits, fx.exp, yo[0], B, L)
+                eng.enqueue(xf, inp_bits, inp_exp, yo[0], B, L)
             torch.cuda.synchronize()
             eng.check_status()
         dt = time.perf_counter() - t0

@@ -29,6 +29,10 @@ EXPECT = {
     "_ZN2s57k_dec_pILi3ELb0EE": (48, 0), "_ZN2s57k_dec_pILi6ELb0EE": (48, 0),
     "_ZN2s57k_dec_pILi3ELb1EE": (48, 2), "_ZN2s57k_dec_pILi6ELb1EE": (48, 2),
     "_ZN2s57k_enc_pILi3EE": (4, 0), "_ZN2s57k_enc_pILi6EE": (8, 0),
+    # the float-in / float-out copies of those kernels (proj_p.hpp k_enc_pf / k_dec_pf): the same stores
+    "_ZN2s58k_dec_pfILi3ELb0EE": (48, 0), "_ZN2s58k_dec_pfILi6ELb0EE": (48, 0),
+    "_ZN2s58k_dec_pfILi3ELb1EE": (48, 2), "_ZN2s58k_dec_pfILi6ELb1EE": (48, 2),
+    "_ZN2s58k_enc_pfILi3EE": (4, 0), "_ZN2s58k_enc_pfILi6EE": (8, 0),
 }
 
 
