@@ -435,6 +435,210 @@ __device__ __forceinline__ void bn16_x4(const Bn16 &p, const int32_t (&x)[4], in
     for (int e = 0; e < 4; ++e) u[e] = sat(asr(wshl(t[e], p.cl), p.cr), p.scb);
 }
 
+// ---- packed 16-bit helpers of the PK16 epilogues (semantics probed on MI355X: tools/probe_pk16.hip -- the clamped forms
+// saturate the EXACT result, v_cvt_pk_i16_i32 saturates each half, the SDWA forms sign-extend the selected half)
+__device__ __forceinline__ uint32_t pk_cvt(int32_t lo, int32_t hi) // (sat16(lo), sat16(hi))
+{
+    uint32_t r;
+    asm("v_cvt_pk_i16_i32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+    return r;
+}
+__device__ __forceinline__ uint32_t pk_sub_sat(uint32_t a, uint32_t b)
+{
+    uint32_t r;
+    asm("v_pk_sub_i16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ uint32_t pk_add_sat(uint32_t a, uint32_t b)
+{
+    uint32_t r;
+    asm("v_pk_add_i16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ uint32_t pk_mad_sat(uint32_t a, uint32_t m, uint32_t c) // sat16(a * m + c) per half
+{
+    uint32_t r;
+    asm("v_pk_mad_i16 %0, %1, %2, %3 clamp" : "=v"(r) : "v"(a), "v"(m), "v"(c));
+    return r;
+}
+__device__ __forceinline__ uint32_t pk_max(uint32_t a, uint32_t b)
+{
+    uint32_t r;
+    asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ uint32_t pk_ashr(uint32_t a, uint32_t s) // s = shift in both halves
+{
+    uint32_t r;
+    asm("v_pk_ashrrev_i16 %0, %1, %2" : "=v"(r) : "v"(s), "v"(a));
+    return r;
+}
+// the same with a wave-uniform second operand taken from an SGPR (no v_mov per use)
+__device__ __forceinline__ uint32_t pk_mul_sat_u(uint32_t a, uint32_t m_uniform) // sat16(a * m) per half
+{
+    uint32_t r;
+    asm("v_pk_mad_i16 %0, %1, %2, 0 clamp" : "=v"(r) : "v"(a), "s"(m_uniform));
+    return r;
+}
+__device__ __forceinline__ uint32_t pk_ashr_u(uint32_t a, uint32_t s_uniform)
+{
+    uint32_t r;
+    asm("v_pk_ashrrev_i16 %0, %1, %2" : "=v"(r) : "s"(s_uniform), "v"(a));
+    return r;
+}
+template <int HALF>
+__device__ __forceinline__ int32_t mul24_h(int32_t a, uint32_t pk) // a * sext(half HALF of pk)
+{
+    int32_t r;
+    if (HALF == 0)
+        asm("v_mul_i32_i24_sdwa %0, %1, sext(%2) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0" : "=v"(r) : "v"(a), "v"(pk));
+    else
+        asm("v_mul_i32_i24_sdwa %0, %1, sext(%2) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "=v"(r) : "v"(a), "v"(pk));
+    return r;
+}
+template <int HALF>
+__device__ __forceinline__ float cvtf_h(uint32_t pk) // float(sext(half))
+{
+    float r;
+    if (HALF == 0) asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0" : "=v"(r) : "v"(pk));
+    else asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1" : "=v"(r) : "v"(pk));
+    return r;
+}
+template <int HALF>
+__device__ __forceinline__ int32_t ashr_h(int32_t s, uint32_t pk) // sext(half) >> s, s wave-uniform (an SGPR operand)
+{
+    int32_t r;
+    if (HALF == 0)
+        asm("v_ashrrev_i32_sdwa %0, %1, sext(%2) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0" : "=v"(r) : "s"(s), "v"(pk));
+    else
+        asm("v_ashrrev_i32_sdwa %0, %1, sext(%2) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "=v"(r) : "s"(s), "v"(pk));
+    return r;
+}
+
+// both operands taken from the same half of two packed registers (sign-extended)
+template <int HALF>
+__device__ __forceinline__ int32_t mul24_hh(uint32_t apk, uint32_t bpk) // sext(half of apk) * sext(half of bpk)
+{
+    int32_t r;
+    if (HALF == 0)
+        asm("v_mul_i32_i24_sdwa %0, sext(%1), sext(%2) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_0" : "=v"(r) : "v"(apk), "v"(bpk));
+    else
+        asm("v_mul_i32_i24_sdwa %0, sext(%1), sext(%2) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1" : "=v"(r) : "v"(apk), "v"(bpk));
+    return r;
+}
+template <int HALF>
+__device__ __forceinline__ int32_t add_hh(uint32_t apk, uint32_t bpk) // sext(half of apk) + sext(half of bpk): the 17-bit sum
+{
+    int32_t r;
+    if (HALF == 0)
+        asm("v_add_u32_sdwa %0, sext(%1), sext(%2) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_0" : "=v"(r) : "v"(apk), "v"(bpk));
+    else
+        asm("v_add_u32_sdwa %0, sext(%1), sext(%2) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1" : "=v"(r) : "v"(apk), "v"(bpk));
+    return r;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same chain in ROW layout, for a kernel whose threads hold 16-byte row vectors (eight consecutive channels of one frame
+// as int16) and always the SAME eight channels: the gate kernel's tile staging (mfma_fused.hpp k_cgate_p<.., UREC>), which
+// rebuilds the SSM input u from the layer input instead of reading the plane the B projection would have stored.  The
+// per-channel operands sit in registers as packed int16 pairs (no LDS table); models with a BatchNorm scale or bias stage do
+// not come here (host-known: s5fxp_fast.hpp plan_layer).
+//
+// One of three arms, chosen ONCE per workgroup from the wave-uniform shifts the B projection published in LayerDyn and the
+// static widths.  What the models of the benchmark and of the test recipes produce (NumPy oracle, all three layers, configs[1]
+// and [2], input scales 0.25 .. 6): every width 16; shx1 = 0..7, the mean never shifted, l1 = 0 always, r1 = 0..4;
+// rs2 = 6..14; cl = 0..4 or cr = 1..6.  With W16 := xb == 16 (or shx1 == 0: the stored input is within its bits), b1 == 16,
+// b2 == 16, min(out_bits, ub) == 16, mean and isv within 16 bits, shx1 <= 14, l1 == 0, cl <= 14, cr <= 15:
+//   ROW_PACKED  W16 && r1 == 0.  sat(x << shx1, 16) is the clamped packed multiply by 2^shx1 (exact product, then the clip:
+//               tools/probe_pk16.hip); the sum's clip at b1 = 16 is the clamped packed add; the product's clip at b2 = 16 is
+//               the saturating pack; change_cfg is a clamped packed multiply by 2^cl and a packed arithmetic shift by cr, one
+//               of them the identity (the clip at 16 bits after a right shift never acts).  9 instructions per channel pair.
+//   ROW_SHIFTED W16 && r1 >= 1.  The 17-bit sum x + m is formed in 32 bits from the two sign-extended halves; shifted right
+//               by r1 >= 1 it is within 16 bits, so the clip at b1 = 16 never acts (b1 >= 17 - r1).  12 per pair.
+//   ROW_GENERIC everything else: bn16_x4's operations in bn16_x4's order (bounds as scalar operands: the fallback does not pin
+//               eight more registers in a kernel that has none to spare).
+// tests/test_gate_urec.py runs tools/probe_bn16_row8.hip: every arm against bn16_x4 on all 65 536 inputs, every shift
+// pattern the arm admits, the patterns it must reject, constants on both rails and at zero.
+// ---------------------------------------------------------------------------------------------
+enum { ROW_GENERIC = 0, ROW_PACKED = 1, ROW_SHIFTED = 2 };
+struct Bn16Row {
+    uint32_t m[4], iv[4];      // this thread's eight channels: pre-shifted -mean and isv as int16 pairs (channel 2k | 2k+1 << 16)
+    int32_t arm;
+    uint32_t mulx, mulc, crp;  // 2^shx1, 2^cl and cr in both halves (wave-uniform: SGPR operands)
+    int32_t shx1, l1, r1, rs2, cl, cr;
+    int32_t xb, b1, b2, cbits;
+};
+
+// arm of a chain with these widths and shifts (wave-uniform)
+__host__ __device__ __forceinline__ int bn16_row_arm(int xb, int mb, int ib, int b1, int b2, int cbits, int shx1, int l1, int r1, int cl, int cr)
+{
+    const bool w16 = (xb == 16 || (shx1 == 0 && xb < 16)) && mb <= 16 && ib <= 16 && b1 == 16 && b2 == 16 && cbits == 16 &&
+                     shx1 <= 14 && l1 == 0 && cl <= 14 && cr <= 15;
+    return !w16 ? ROW_GENERIC : r1 == 0 ? ROW_PACKED : ROW_SHIFTED;
+}
+
+// the uniform part: widths, shifts and the arm, from explicit values (the probe) ...
+__host__ __device__ __forceinline__ void bn16_row_shifts(Bn16Row &p, int xb, int mb, int ib, int b1, int b2, int cbits, int shx1, int post1, int rs2, int de)
+{
+    p.shx1 = shx1; p.l1 = post1 > 0 ? post1 : 0; p.r1 = post1 < 0 ? -post1 : 0;
+    p.rs2 = rs2;
+    p.cl = de > 0 ? de : 0; p.cr = de < 0 ? -de : 0;
+    p.xb = xb; p.b1 = b1; p.b2 = b2; p.cbits = cbits;
+    p.arm = bn16_row_arm(xb, mb, ib, b1, b2, cbits, p.shx1, p.l1, p.r1, p.cl, p.cr);
+    p.mulx = 0x10001u * (1u << (p.shx1 & 15)); p.mulc = 0x10001u * (1u << (p.cl & 15)); p.crp = 0x10001u * (uint32_t)(p.cr & 15);
+}
+
+// ... or from a layer's BatchNorm arguments and published exponents, with the operands of the thread's eight channels
+// h0 .. h0 + 7.  No scale / bias stage (the caller's plan guarantees it).
+__device__ __forceinline__ Bn16Row bn16_row_setup(const BnArgs &a, const LayerDyn &d, int h0)
+{
+    Bn16Row p;
+    bn16_row_shifts(p, a.xb, a.mb, a.ib, a.b1, a.b2, a.out_bits < a.ub ? a.out_bits : a.ub, d.bn1.shx, d.bn1.post, d.rs2, a.ue - d.bn_e);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int32_t m0 = sat(wshl(a.mm[h0 + 2 * k], d.bn1.shy), a.mb), m1 = sat(wshl(a.mm[h0 + 2 * k + 1], d.bn1.shy), a.mb);
+        p.m[k] = ((uint32_t)m0 & 0xffffu) | ((uint32_t)m1 << 16);
+        p.iv[k] = ((uint32_t)a.isv[h0 + 2 * k] & 0xffffu) | ((uint32_t)a.isv[h0 + 2 * k + 1] << 16);
+    }
+    return p;
+}
+
+// eight consecutive channels of one frame (int16, as loaded) -> their SSM input u (int16, as bn16_x4 + pack4_i16 give it)
+template <int ARM>
+__device__ __forceinline__ v4i bn16_row8(const Bn16Row &p, const v4i &x)
+{
+    v4i u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if constexpr (ARM == ROW_GENERIC) {
+            int32_t o[2];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int32_t xe = e ? x[k] >> 16 : (int32_t)(int16_t)(x[k] & 0xffff);
+                const int32_t me = e ? (int32_t)p.m[k] >> 16 : (int32_t)(int16_t)(p.m[k] & 0xffffu);
+                const int32_t ie = e ? (int32_t)p.iv[k] >> 16 : (int32_t)(int16_t)(p.iv[k] & 0xffffu);
+                const int32_t v = sat(asr(wshl(wadd(sat(wshl(xe, p.shx1), p.xb), me), p.l1), p.r1), p.b1);
+                const int32_t t = sat(asr(__mul24(v, ie), p.rs2), p.b2);
+                o[e] = sat(asr(wshl(t, p.cl), p.cr), p.cbits);
+            }
+            u[k] = (int32_t)(((uint32_t)o[0] & 0xffffu) | ((uint32_t)o[1] << 16));
+        } else {
+            const uint32_t xs = pk_mul_sat_u((uint32_t)x[k], p.mulx); // sat16(x << shx1)
+            int32_t t0, t1;
+            if constexpr (ARM == ROW_PACKED) {
+                const uint32_t v = pk_add_sat(xs, p.m[k]);
+                t0 = mul24_hh<0>(v, p.iv[k]); t1 = mul24_hh<1>(v, p.iv[k]);
+            } else {
+                const int32_t v0 = asr(add_hh<0>(xs, p.m[k]), p.r1), v1 = asr(add_hh<1>(xs, p.m[k]), p.r1);
+                t0 = mul24_h<0>(v0, p.iv[k]); t1 = mul24_h<1>(v1, p.iv[k]);
+            }
+            const uint32_t t = pk_cvt(asr(t0, p.rs2), asr(t1, p.rs2));
+            u[k] = (int32_t)pk_ashr_u(pk_mul_sat_u(t, p.mulc), p.crp);
+        }
+    }
+    return u;
+}
+
 // ---------------------------------------------------------------------------------------------
 // B projection arguments (kernel: proj_p.hpp k_bproj_p)
 // ---------------------------------------------------------------------------------------------
@@ -450,7 +654,7 @@ struct BprojM2Args {
     int32_t rs_re, rs_im, bre_bits, bim_bits, sh_re, sh_im;
     int32_t t_lo, t_len; // k_bproj_p: the step range this launch covers (StepRange)
     int32_t k_re;        // SM = 2 (pair-native K stream): 2^16 - 2^(16 - A_re_exp), the addend of the negated product
-    int32_t no_u;        // != 0: u is not stored -- the gate kernel recomputes it (mfma_fused.hpp k_cgate_p<.., GBN>)
+    int32_t no_u;        // != 0: u is not stored -- the gate kernel rebuilds it (mfma_fused.hpp k_cgate_p<.., UREC> or <.., GBN>)
     int32_t live_slots;  // SM = 3 / 1, > 0: only state slots below it are stored (scan_quad.hpp ScanPairLArgs::live_slots)
     // != nullptr: the per-channel extremes of the layer input (ext_reps replicas of 2H floats); every workgroup derives the
     // BatchNorm exponents from them in its prologue (bn_finalize_mm_body), workgroup 0 publishes them

@@ -99,85 +99,8 @@ __device__ __forceinline__ void quad_transpose(int32_t (&w)[4], int lane)
     }
 }
 
-// ---- packed 16-bit helpers of the PK16 epilogues (semantics probed on MI355X: tools/probe_pk16.hip -- the clamped forms
-// saturate the EXACT result, v_cvt_pk_i16_i32 saturates each half, the SDWA forms sign-extend the selected half)
-__device__ __forceinline__ uint32_t pk_cvt(int32_t lo, int32_t hi) // (sat16(lo), sat16(hi))
-{
-    uint32_t r;
-    asm("v_cvt_pk_i16_i32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-__device__ __forceinline__ uint32_t pk_sub_sat(uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("v_pk_sub_i16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ uint32_t pk_add_sat(uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("v_pk_add_i16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ uint32_t pk_mad_sat(uint32_t a, uint32_t m, uint32_t c) // sat16(a * m + c) per half
-{
-    uint32_t r;
-    asm("v_pk_mad_i16 %0, %1, %2, %3 clamp" : "=v"(r) : "v"(a), "v"(m), "v"(c));
-    return r;
-}
-__device__ __forceinline__ uint32_t pk_max(uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ uint32_t pk_ashr(uint32_t a, uint32_t s) // s = shift in both halves
-{
-    uint32_t r;
-    asm("v_pk_ashrrev_i16 %0, %1, %2" : "=v"(r) : "v"(s), "v"(a));
-    return r;
-}
-// the same with a wave-uniform second operand taken from an SGPR (no v_mov per use)
-__device__ __forceinline__ uint32_t pk_mul_sat_u(uint32_t a, uint32_t m_uniform) // sat16(a * m) per half
-{
-    uint32_t r;
-    asm("v_pk_mad_i16 %0, %1, %2, 0 clamp" : "=v"(r) : "v"(a), "s"(m_uniform));
-    return r;
-}
-__device__ __forceinline__ uint32_t pk_ashr_u(uint32_t a, uint32_t s_uniform)
-{
-    uint32_t r;
-    asm("v_pk_ashrrev_i16 %0, %1, %2" : "=v"(r) : "s"(s_uniform), "v"(a));
-    return r;
-}
-template <int HALF>
-__device__ __forceinline__ int32_t mul24_h(int32_t a, uint32_t pk) // a * sext(half HALF of pk)
-{
-    int32_t r;
-    if (HALF == 0)
-        asm("v_mul_i32_i24_sdwa %0, %1, sext(%2) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0" : "=v"(r) : "v"(a), "v"(pk));
-    else
-        asm("v_mul_i32_i24_sdwa %0, %1, sext(%2) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "=v"(r) : "v"(a), "v"(pk));
-    return r;
-}
-template <int HALF>
-__device__ __forceinline__ float cvtf_h(uint32_t pk) // float(sext(half))
-{
-    float r;
-    if (HALF == 0) asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0" : "=v"(r) : "v"(pk));
-    else asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1" : "=v"(r) : "v"(pk));
-    return r;
-}
-template <int HALF>
-__device__ __forceinline__ int32_t ashr_h(int32_t s, uint32_t pk) // sext(half) >> s, s wave-uniform (an SGPR operand)
-{
-    int32_t r;
-    if (HALF == 0)
-        asm("v_ashrrev_i32_sdwa %0, %1, sext(%2) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0" : "=v"(r) : "s"(s), "v"(pk));
-    else
-        asm("v_ashrrev_i32_sdwa %0, %1, sext(%2) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "=v"(r) : "s"(s), "v"(pk));
-    return r;
-}
+// (the packed 16-bit helpers of the PK16 epilogues -- pk_cvt, pk_add_sat, mul24_h, ... -- live in mfma_bn.hpp: the row-layout
+// BatchNorm chain bn16_row8 uses them as well)
 
 constexpr int SIGTAB_WORDS = 2 * 7 * 64; // sig_x <= 6 on this path (host-checked)
 constexpr int SIGDIR_MAX_BITS = 12, SIGDIR_BYTES = 2 << SIGDIR_MAX_BITS;
@@ -200,8 +123,13 @@ __host__ __device__ __forceinline__ int sigdir_lds_bytes(int bits) { return ((2 
 // GBN (with PK16): the SSM input u = BatchNorm(layer input) is recomputed here from `skip` -- the layer input this kernel reads
 // anyway for the residual maxima -- with the exponents the B projection left in LayerDyn, instead of being written by the B
 // projection and read back: -2 x N x H x 2 bytes of traffic per layer for ~12 more VALU operations per element (mfma_bn.hpp bn16_x4)
+// UREC (with COAL, see below: PK16 && !TRACE && !WIDE && !GBN): the same idea where it costs least.  The tile staging
+// (tiles_in_out) holds each thread's 16-byte row vectors of `skip` with no accumulator live, and a thread's eight channels are
+// the same for every vector and tile (NTHR is a multiple of the vectors per frame), so their BatchNorm operands stay in eight
+// registers for the whole kernel and the u tile is filled with bn16_row8(skip row) (mfma_bn.hpp) instead of a loaded row: no u
+// loads, no LDS table, epilogues and barriers unchanged.  The B projection then does not store u (BprojM2Args::no_u).
 template <int KS, int NT, bool TRACE, bool S16 = false, bool DIRECT = false, int FTP = 64, bool WIDE = false, bool PAIR = false, bool PK16 = false,
-          bool GBN = false>
+          bool GBN = false, bool UREC = false>
 // <= 128 registers: two six-wave workgroups per CU (at 136 only one was ever resident: measured)
 // -DS5_CGATE_HID=1: states, u and skip of the NEXT tile all requested a tile ahead behind the compiler's back and waited for
 // by exact count (scan_quad.hpp vm_wait).  Measured (profiles/r03_gate_prefetch_ab.txt): 226 us per 8-batch launch against
@@ -226,9 +154,11 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
         const int64_t g = blockIdx.y;
         gshift(a.u, g * go.ws); gshift(a.skip, g * go.ws); gshift(a.xs, g * go.ws); gshift(a.z, g * go.ws);
         gshift(a.skip_e.dyn, g * go.ws); gshift(a.dynw, g * go.ws); gshift(a.run_if, g * go.ws); gshift(a.status, g * go.status);
-        if constexpr (GBN) { gshift(a.bn.dyn, g * go.ws); gshift(a.bn.xe.dyn, g * go.ws); }
+        if constexpr (GBN || UREC) { gshift(a.bn.dyn, g * go.ws); gshift(a.bn.xe.dyn, g * go.ws); }
     }
     static_assert(!GBN || (PK16 && !TRACE && !WIDE), "the BatchNorm rides on the packed-epilogue kernel only");
+    static_assert(!UREC || (S5_CGATE_COAL && PK16 && !TRACE && !WIDE && !GBN && !(S5_CGATE_HID && S16 && PAIR && KS * NT < 24)),
+                  "u is rebuilt in the row tiles' staging: COAL only");
     constexpr int P = 32 * KS, H = 32 * NT, FT = FTP, NW = (FT / 32) * NT, NTHR = 64 * NW; // one wave per (half, column tile)
     constexpr int KPS = 2 * P + 16, KPX = H + 16;
     constexpr int NU = 1, SUBSTEP = 0;   // units per wave
@@ -253,6 +183,7 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
     constexpr bool COAL = S5_CGATE_COAL && PK16 && !TRACE && !WIDE && !GBN && !HID;
     constexpr int TROW = 2 * H + 8, VPF = H / 8, NVC = FT * VPF / NTHR; // bytes per tile row; 16-byte vectors per frame / per thread
     static_assert(!COAL || FT * VPF % NTHR == 0, "tile vectors per thread");
+    static_assert(!UREC || NTHR % VPF == 0, "a thread's channel group must be the same for every vector");
     int8_t *Ut = reinterpret_cast<int8_t *>(red + 48), *St = Ut + FT * TROW; // u (then z) and skip of the current tile
     const int l = threadIdx.x & 63, r = l & 31, h = l >> 5, wave = threadIdx.x >> 6;
     const int ct = wave % NT, sub0 = wave / NT;
@@ -288,6 +219,8 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
     }
     Bn16 bn{};
     if constexpr (GBN) bn = bn16_setup(a.bn, *a.bn.dyn, bntab, H); // the B projection of this layer has published the exponents
+    std::conditional_t<UREC, Bn16Row, int> brow{};
+    if constexpr (UREC) brow = bn16_row_setup(a.bn, *a.bn.dyn, 8 * (int)(threadIdx.x % VPF)); // ... and so here
     const int dsh = a.out_exp - a.sig_x, dbias = 1 << (a.sigdir_bits - 1);
     const int skip_e = a.skip_e.get();
     const float kz = ldexpf(1.f, skip_e - a.res_exp); // fz + fs = 2^-skip_e * (z * kz + s), exactly
@@ -308,7 +241,7 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
     // its arithmetic phases instead of one burst at the top of every tile (32 KB per tile and workgroup outstanding for a third
     // of the tile's time is all that two workgroups per CU had in flight: ~3 TB/s by Little's law, which is what it ran at)
     v2i uq[NU][4], sq[NU][4];
-    v4i urow[COAL ? NVC : 1], srow[COAL ? NVC : 1]; // COAL: this thread's vectors of the NEXT tile's u and skip rows
+    v4i urow[COAL && !UREC ? NVC : 1], srow[COAL ? NVC : 1]; // COAL: this thread's vectors of the NEXT tile's u and skip rows (UREC: skip only)
     auto load_tile = [&](v4i(&dst)[COAL ? NVC : 1], const int16_t *src, const TileWalk<FT> &tw) {
         const int64_t b = tw.b;
         const int t = tw.t(sr), nv = tw.nvalid(sr);
@@ -370,7 +303,7 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
     if ((int64_t)blockIdx.x < tiles) {
         if constexpr (XPRE) load_x(walk);
         if constexpr (COAL) {
-            load_tile(urow, a.u, walk);
+            if constexpr (!UREC) load_tile(urow, a.u, walk);
             load_tile(srow, a.skip, walk);
         } else {
             if constexpr (!GBN) load_rows(uq, a.u, walk);
@@ -391,11 +324,31 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
                 if (f < nvalid_prev) *reinterpret_cast<v4i *>(zb_prev + 2u * (unsigned)(f * H + 8 * og)) = v4i{z0[0], z0[1], z1[0], z1[1]};
             }
             if (incoming) {
-                *reinterpret_cast<v2i *>(cu) = v2i{urow[i][0], urow[i][1]};
-                *reinterpret_cast<v2i *>(cu + 8) = v2i{urow[i][2], urow[i][3]};
+                const v4i &uv = urow[UREC ? 0 : i]; // (UREC calls this for the last tile's z only)
+                *reinterpret_cast<v2i *>(cu) = v2i{uv[0], uv[1]};
+                *reinterpret_cast<v2i *>(cu + 8) = v2i{uv[2], uv[3]};
                 *reinterpret_cast<v2i *>(cs_) = v2i{srow[i][0], srow[i][1]};
                 *reinterpret_cast<v2i *>(cs_ + 8) = v2i{srow[i][2], srow[i][3]};
             }
+        }
+    };
+    // UREC: the same, with the u vectors made here: bn16_row8(skip vector).  ARM (mfma_bn.hpp ROW_*) is wave-uniform and chosen
+    // once per call.  Frames clamped past nvalid recompute a valid row, as the loads re-read one.
+    auto tiles_in_urec = [&](auto arm_c) {
+        constexpr int ARM = decltype(arm_c)::value;
+#pragma unroll
+        for (int i = 0; i < NVC; ++i) {
+            const int v = threadIdx.x + NTHR * i, f = v / VPF, og = v % VPF;
+            int8_t *cu = Ut + f * TROW + 16 * og, *cs_ = St + f * TROW + 16 * og;
+            if (zb_prev) {
+                const v2i z0 = *reinterpret_cast<const v2i *>(cu), z1 = *reinterpret_cast<const v2i *>(cu + 8);
+                if (f < nvalid_prev) *reinterpret_cast<v4i *>(zb_prev + 2u * (unsigned)(f * H + 8 * og)) = v4i{z0[0], z0[1], z1[0], z1[1]};
+            }
+            const v4i uv = bn16_row8<ARM>(brow, srow[i]);
+            *reinterpret_cast<v2i *>(cu) = v2i{uv[0], uv[1]};
+            *reinterpret_cast<v2i *>(cu + 8) = v2i{uv[2], uv[3]};
+            *reinterpret_cast<v2i *>(cs_) = v2i{srow[i][0], srow[i][1]};
+            *reinterpret_cast<v2i *>(cs_ + 8) = v2i{srow[i][2], srow[i][3]};
         }
     };
 
@@ -410,7 +363,11 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
         char *zb = reinterpret_cast<char *>(a.z + n0 * H);
         const int64_t tile_next = tile + gridDim.x;
         if constexpr (HID) vm_wait<12>(xq); // newer than this tile's states: u, the last tile's stores, skip
-        if constexpr (COAL) tiles_in_out(true); // z of the previous tile out, u and skip of this one in
+        if constexpr (UREC) { // z of the previous tile out, skip of this one in, and u made from it
+            if (brow.arm == ROW_PACKED) tiles_in_urec(std::integral_constant<int, ROW_PACKED>{});
+            else if (brow.arm == ROW_SHIFTED) tiles_in_urec(std::integral_constant<int, ROW_SHIFTED>{});
+            else tiles_in_urec(std::integral_constant<int, ROW_GENERIC>{});
+        } else if constexpr (COAL) tiles_in_out(true); // z of the previous tile out, u and skip of this one in
         // ---- phase A: stream items -> byte planes
 #pragma unroll
         for (int i = 0; i < ROUNDS; ++i) {
@@ -519,7 +476,7 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
         }
         if constexpr (COAL) {
             if (tile_next < tiles) { // the registers are free again: the next tile's rows, a whole tile ahead
-                load_tile(urow, a.u, walk_next);
+                if constexpr (!UREC) load_tile(urow, a.u, walk_next);
                 load_tile(srow, a.skip, walk_next);
             }
         }

@@ -323,6 +323,7 @@ struct LayerPlan {
     bool direct;      // the sigmoid input has a direct table (FastLayer::sigdir)
     bool pk16;        // packed int16 epilogues of the gate kernel (mfma_fused.hpp PK16)
     bool gate_bn;     // the gate kernel recomputes u (S5FXP_GATE_BN)
+    bool gate_urec;   // the 32-frame gate kernel rebuilds u in its tile staging (k_cgate_p<.., UREC>; off: S5FXP_GATE_BN=0)
     GateForm gate;
     const MfmaW *w_bproj, *w_cre, *w_cim; // full or compacted; w_bproj: the pair-ordered packing on the pair rungs
     const int32_t *a_re, *a_im;           // Lambda_bar of the slots
@@ -354,16 +355,22 @@ LayerPlan plan_layer(const s5fxp_model *m, int li, int fwd_flags, bool traced, b
     p.direct = r.s16 && fl.sigdir_bits > 0;
     p.pk16 = p.direct && !traced && !m->cfg.no_pk16 && fl.bias16 && s.y_bits == 16 && l.out2.out_bits == 16 && l.res_bits == 16 &&
              l.l_bits == 16 && !out2_conv && l.l_exp - s.y_exp <= 14;
-    // ... and on that kernel the SSM input u CAN be recomputed from the layer input instead of travelling through memory
-    // (k_cgate_p<.., GBN>, S5FXP_GATE_BN=1; the exponents are the ones this layer's B projection publishes in its prologue).
-    // Off by default: -50 MB per layer and batch, but the twelve VALU operations per element land in the kernel that is
-    // VALU-co-limited already -- gate kernel 207 -> 250 us per 8-batch launch, B projection 104 -> 90: 3 % slower overall
+    // ... and on that kernel the SSM input u CAN be recomputed from the layer input instead of travelling through memory (the
+    // exponents are the ones this layer's B projection publishes in its prologue).  The first form of it (k_cgate_p<.., GBN>,
+    // S5FXP_GATE_BN=1: 64-frame tiles, bn16_x4 in the first epilogue, operands from an LDS table) lost: gate kernel 207 -> 250 us
+    // per 8-batch launch, B projection 104 -> 90, 3 % slower overall.  Kept as the record; what ships is gate_urec below.
     p.gate_bn = p.pk16 && fold && !big && m->cfg.gate_bn;
     // 32-frame tiles, three-wave workgroups: with the sigmoid table sized exactly FIVE of them fit a CU's LDS and registers --
     // 15 waves instead of the 12 of two six-wave workgroups, for a kernel whose waves wait two thirds of their cycles.  The
     // grid is exactly what is resident at once (5 x 256 CUs): 170 us per 8-batch launch against 190 (tools/ab_cgate_ft32.sh;
     // 1024 or 1536 workgroups: 189 / 209).  (Without PK16 they were tried as well: 39 vs 36 us.)
     p.gate = traced ? GATE_TRACED : p.gate_bn ? GATE_GBN : (!big && p.pk16 && !m->cfg.cgate_ft64) ? GATE_FT32 : GATE_FT64;
+    // The 32-frame form rebuilds u in its tile staging, where a thread holds whole 16-byte rows of the layer input and no
+    // accumulator is live, from operands in eight registers and in 4.5-6 instructions per element chosen by the layer's shifts
+    // (mfma_fused.hpp UREC, mfma_bn.hpp bn16_row8): by default wherever the B projection publishes the exponents (fold) and the
+    // BatchNorm has no scale / bias stage (those models keep reading u).  -50 MB per layer and batch, +5 % frames/s against the
+    // kernels that move u through memory, which S5FXP_GATE_BN=0 restores (profiles/r05_gate_urec_*).
+    p.gate_urec = p.gate == GATE_FT32 && fold && !l.scale && !l.nbias && !m->cfg.no_gate_urec;
     p.w_bproj = r.pair ? &(p.compact ? fl.c_bproj_pair : fl.bproj_pair).w : &(p.compact ? fl.c_bproj : fl.bproj).w;
     p.w_cre = &(p.compact ? fl.c_cre : fl.cre).w;
     p.w_cim = &(p.compact ? fl.c_cim : fl.cim).w;
@@ -391,12 +398,14 @@ template <int SM> auto bproj_kernel(bool big, int ks)
                : ks_kernel<3>(ks, [](auto k) { return k_bproj_p<3, 4, false, SM, 2 * decltype(k)::value>; });
 }
 
-// k_cgate_p<KS, NT, false, S16, DIRECT, FTP, false, PAIR, PK16, GBN> of an untraced, inexact layer in its gate form: the
-// 32-frame and GBN forms exist for the packed epilogues (PK16) at H = 96 only
+// k_cgate_p<KS, NT, false, S16, DIRECT, FTP, false, PAIR, PK16, GBN, UREC> of an untraced, inexact layer in its gate form: the
+// 32-frame (with or without UREC) and GBN forms exist for the packed epilogues (PK16) at H = 96 only
 template <bool S16, bool DIR, bool PAIR, bool PK16> auto cgate_kernel(const LayerPlan &p, bool big)
 {
     if (big) return ks_kernel<6>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 6, false, S16, DIR, 64, false, PAIR, PK16>; });
     if constexpr (PK16) {
+        if (p.gate == GATE_FT32 && p.gate_urec)
+            return ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 32, false, PAIR, true, false, true>; });
         if (p.gate == GATE_FT32)
             return ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 32, false, PAIR, true>; });
         if (p.gate == GATE_GBN)
@@ -599,7 +608,10 @@ struct FusedForward {
         a.bre_bits = s.Bu_re_bits; a.bim_bits = s.Bu_im_bits; a.sh_re = s.Bu_re_exp - s.x_re_exp; a.sh_im = s.Bu_im_exp - s.x_im_exp;
         a.k_re = 65536 - (1 << (16 - s.A_re_exp));
         a.live_slots = p.live_slots;
-        a.no_u = p.gate_bn ? 1 : 0;
+        // u is not stored when the gate kernel rebuilds it -- and nothing else reads it: the in-forward exact re-run
+        // (k_cgate_p<.., WIDE>, enqueued when !defer) takes u from memory.  (Today pk16 implies the int16 rungs and those imply
+        // defer; the rule is stated here so that it does not rest on that.)
+        a.no_u = (p.gate_bn || p.gate_urec) && defer ? 1 : 0;
         if (fold) {
             a.ext = ext(li);
             a.ext_reps = EXT_REPS; a.status = status; a.status_exps = status_exps(li);
