@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define S5FXP_VERSION 104
+#define S5FXP_VERSION 105
 
 enum {
     S5FXP_OK = 0,
@@ -328,15 +328,17 @@ int s5fxp_model_layer_out_bits(const s5fxp_model *m, int layer);
 /* States of `layer` whose rows of B_bar are not all zero.  The others receive Bu = 0 at every step and stay (0, 0) from a
  * zero carry (fxpmodel.py:147-172), so their columns of C multiply zeros: when at most P / 2 states are live, forwards on
  * the fused path that neither trace the states nor carry them in or out run the layer's kernels on the fewest groups of 32
- * state slots that hold the live ones (32 or 64 of 128, 32 of 64)
+ * state slots that hold the live ones (32 or 64 of 128, 32 of 64; layers of 32 or 96 states -- the N-DNS recipe at
+ * dim_scale 0.25 and 0.75 -- always run on all of them: the rule needs P to be a multiple of 64)
  * (bit-identical; S5FXP_NO_COMPACT at model creation switches it off).  -1: bad argument. */
 int s5fxp_model_live_states(const s5fxp_model *m, int layer);
 
 /* Static facts about a created model (for INTEGRATION / debugging). */
 int s5fxp_model_out_exp(const s5fxp_model *m);
 int s5fxp_model_out_bits(const s5fxp_model *m);
-/* 1 if the int8-MFMA kernels were packed for this model (NDNS shapes, <= 8-bit weights, <= 16-bit
- * activations); every forward of such a model runs them, whatever B and L (a sequence's last 4-step block may be
+/* 1 if the int8-MFMA kernels were packed for this model (the N-DNS recipe's shapes at dim_scale 0.25, 0.5, 0.75 and 1.0:
+ * (H, P) = (48, 32), (96, 64), (144, 96), (192, 128); <= 8-bit weights, <= 16-bit activations, 257 <= d_in <= 288,
+ * d_out <= 288); every forward of such a model runs them, whatever B and L (a sequence's last 4-step block may be
  * partial: L = 3751, the N-DNS clips' native length, or single frames of a stream).  status[2] reports it per forward. */
 int s5fxp_model_is_fast(const s5fxp_model *m);
 /* Which recurrence kernel an optimistic forward (S5FXP_FWD_DEFER_REDO) runs for `layer`:

@@ -210,7 +210,7 @@ __global__ __launch_bounds__(256) void k_bn_finalize_mm(BnArgs a, const float *e
 
 // Residual add + ReLU of one layer and, in the same pass, the per-channel extremes of its result (the next
 // layer's BatchNorm operand).  RESID=false: extremes of z only (the encoder output ahead of layer 0).
-// block = 384 threads = G8 channel-groups (8 channels = 16 bytes each) x R frame lanes (32 at H=96, 16 at H=192);
+// block = 384 threads = G8 channel-groups (8 channels = 16 bytes each) x R frame lanes (64 / 32 / 21 / 16 at H = 48 / 96 / 144 / 192);
 // a workgroup owns `span` consecutive frames (a multiple of 4R) and keeps four frames per thread in flight.
 // ext == nullptr: no extremes wanted (last layer).
 // Two single-workgroup kernels are folded in (single-rank mode; with a multi-rank hook they stay separate
@@ -251,7 +251,8 @@ __global__ __launch_bounds__(RESID_THREADS, 5) void k_resid_minmax16(const int16
     // first frame) plus a 32-bit byte offset per thread: no 64-bit address arithmetic in the loop (the kernel sits at the
     // 96 registers that three workgroups per CU allow)
     const int64_t lo_n = (int64_t)blockIdx.x * span;
-    const int cnt = (int)((lo_n + span < N ? lo_n + span : N) - lo_n);
+    // (H = 144: 18 groups x 21 frame lanes = 378 threads; the six spare ones, rl == R, own no frame and fold neutral extremes)
+    const int cnt = rl < R ? (int)((lo_n + span < N ? lo_n + span : N) - lo_n) : 0;
     const char *zb = reinterpret_cast<const char *>(z + lo_n * H), *sb = reinterpret_cast<const char *>(skip + lo_n * H);
     char *ob = reinterpret_cast<char *>(out + lo_n * H);
     const unsigned rowb = 2u * (unsigned)H;                       // bytes per frame

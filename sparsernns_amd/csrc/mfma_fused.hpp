@@ -51,8 +51,8 @@ __global__ void k_select_maxima(LayerDyn *d)
 }
 
 // ---------------------------------------------------------------------------------------------
-// Phase-split version (see proj_p.hpp for the idea).  Workgroup = one wave per (32-frame half, 32-channel tile): six
-// waves at H=96, twelve at H=192; tile = 64 frames:
+// Phase-split version (see proj_p.hpp for the idea).  Workgroup = one wave per (32-frame half, 32-channel tile): four, six,
+// ten, twelve waves at H = 48, 96, 144, 192; tile = 64 frames:
 //   A   all threads: one 32-byte stream item (state p, 4 steps, re+im) per thread -> range check, complex
 //       ReLU, 4x4 transpose inside the lane quad (DPP) so that a lane holds 4 consecutive states of ONE
 //       frame -> byte planes S[frame][re P | im P] in LDS;
@@ -147,7 +147,8 @@ template <int KS, int NT, bool TRACE, bool S16 = false, bool DIRECT = false, int
 #ifndef S5_CGATE_LB
 #define S5_CGATE_LB 4
 #endif
-__global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGATE_LB : 3) void k_cgate_p(const CGateArgs a_k, GroupOff go)
+// (H = 48: three four-wave workgroups fill a CU's LDS, so the three-waves-per-SIMD register budget costs no occupancy there)
+__global__ __launch_bounds__(FTP * 2 * NT, NT == 3 && KS == 1 && !WIDE ? S5_CGATE_LB : 3) void k_cgate_p(const CGateArgs a_k, GroupOff go)
 {
     CGateArgs a = a_k; // (the LUT is indexed by thread below: that read stays on the kernel argument, so that this copy lives in registers)
     {
@@ -159,14 +160,19 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
     static_assert(!GBN || (PK16 && !TRACE && !WIDE), "the BatchNorm rides on the packed-epilogue kernel only");
     static_assert(!UREC || (S5_CGATE_COAL && PK16 && !TRACE && !WIDE && !GBN && !(S5_CGATE_HID && S16 && PAIR && KS * NT < 24)),
                   "u is rebuilt in the row tiles' staging: COAL only");
-    constexpr int P = 32 * KS, H = 32 * NT, FT = FTP, NW = (FT / 32) * NT, NTHR = 64 * NW; // one wave per (half, column tile)
-    constexpr int KPS = 2 * P + 16, KPX = H + 16;
+    // H: the real channels (row stride in memory, vectors per frame); HP: the padded extent of the LDS tables, the X1 planes
+    // and the row tiles (proj_p.hpp shape_channels).  RAGGED: channel groups of the last tile at or beyond H are pad lanes:
+    // their weights, D and bias are zero, so they compute x1 = 0 and z = 0; their u and skip are zero instead of loaded (a zero
+    // adds nothing to the residual maximum) and they store nothing.
+    constexpr int P = 32 * KS, H = shape_channels(NT), HP = 32 * NT, FT = FTP, NW = (FT / 32) * NT, NTHR = 64 * NW; // one wave per (half, column tile)
+    constexpr bool RAGGED = H != HP;
+    constexpr int KPS = 2 * P + 16, KPX = HP + 16;
     constexpr int NU = 1, SUBSTEP = 0;   // units per wave
     constexpr int ITEMS = (FT / 4) * P, ROUNDS = (ITEMS + NTHR - 1) / NTHR;
     // hidden prefetches, see below (the dim 1.0 kernel on all 128 state slots has no registers left for them)
     constexpr bool HID = S5_CGATE_HID && S16 && PAIR && PK16 && !WIDE && !TRACE && KS * NT < 24;
     extern __shared__ __attribute__((aligned(16))) int8_t smem[];
-    int32_t *csr = reinterpret_cast<int32_t *>(smem), *csi = csr + H, *Dl = csi + H, *cs2 = Dl + H, *be = cs2 + H, *lutp = be + H;
+    int32_t *csr = reinterpret_cast<int32_t *>(smem), *csi = csr + HP, *Dl = csi + HP, *cs2 = Dl + HP, *be = cs2 + HP, *lutp = be + HP;
     int32_t *sigt = lutp + 8; // SIGTAB_WORDS, or the direct table (int16, SIGDIR_BYTES)
     const int16_t *sigd = reinterpret_cast<const int16_t *>(sigt);
     constexpr int NPL = WIDE ? 4 : 2; // byte planes of the state operand; plane NPL-1 is the signed top byte
@@ -181,8 +187,10 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
     // layout every global load / store instruction touched 64 different rows with 8 bytes each: the bytes per batch are the
     // same, the memory pipeline sees an eighth of the requests.  TROW: 8-byte reads by 32 lanes 200 bytes apart hit 32 bank pairs.
     constexpr bool COAL = S5_CGATE_COAL && PK16 && !TRACE && !WIDE && !GBN && !HID;
-    constexpr int TROW = 2 * H + 8, VPF = H / 8, NVC = FT * VPF / NTHR; // bytes per tile row; 16-byte vectors per frame / per thread
-    static_assert(!COAL || FT * VPF % NTHR == 0, "tile vectors per thread");
+    // bytes per tile row; 16-byte vectors per frame / per thread (ragged shapes: the last round is predicated, NVC_FULL false)
+    constexpr int TROW = 2 * HP + 8, VPF = H / 8, NVC = (FT * VPF + NTHR - 1) / NTHR;
+    constexpr bool NVC_FULL = FT * VPF % NTHR == 0;
+    static_assert(!COAL || NVC_FULL || RAGGED, "tile vectors per thread");
     static_assert(!UREC || NTHR % VPF == 0, "a thread's channel group must be the same for every vector");
     int8_t *Ut = reinterpret_cast<int8_t *>(red + 48), *St = Ut + FT * TROW; // u (then z) and skip of the current tile
     const int l = threadIdx.x & 63, r = l & 31, h = l >> 5, wave = threadIdx.x >> 6;
@@ -203,12 +211,12 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
 #pragma unroll
         for (int ks = 0; ks < NT; ++ks) wo2[ks] = *reinterpret_cast<const v4i *>(a.w_o2.wt + row * a.w_o2.Kp + 32 * ks + 16 * h);
     }
-    for (int i = threadIdx.x; i < H; i += NTHR) {
+    for (int i = threadIdx.x; i < HP; i += NTHR) {
         csr[i] = a.w_re.cs128[i]; csi[i] = a.w_im.cs128[i]; Dl[i] = a.D[i]; cs2[i] = a.w_o2.cs128[i];
         if (!PK16) be[i] = a.bias_eff[i];
     }
     if (PK16) // packed pairs (every value fits 16 bits: host-checked)
-        for (int i = threadIdx.x; i < H / 2; i += NTHR)
+        for (int i = threadIdx.x; i < HP / 2; i += NTHR)
             be[i] = (int32_t)(((uint32_t)a.bias_eff[2 * i] & 0xffffu) | ((uint32_t)a.bias_eff[2 * i + 1] << 16));
     if (threadIdx.x < 8) lutp[threadIdx.x] = a_k.lut[threadIdx.x] | (a_k.lut[threadIdx.x < 7 ? threadIdx.x + 1 : 7] << 16);
     if (DIRECT) {
@@ -249,6 +257,7 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
 #pragma unroll
         for (int i = 0; i < NVC; ++i) {
             const int v = threadIdx.x + NTHR * i;
+            if (!NVC_FULL && v >= FT * VPF) break; // (the last round of a ragged shape)
             int f = v / VPF;
             f = f < nv ? f : nv - 1;
             dst[i] = *reinterpret_cast<const v4i *>(base + 2u * (unsigned)(f * H + 8 * (v % VPF)));
@@ -265,7 +274,8 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
             const unsigned fb = 2u * (unsigned)(fo * H + ch0);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                if constexpr (HID) dst[u][g] = gload8_hidden(base, fb + 16 * g);
+                if (RAGGED && ch0 + 8 * g >= H) dst[u][g] = v2i{0, 0}; // a pad lane
+                else if constexpr (HID) dst[u][g] = gload8_hidden(base, fb + 16 * g);
                 else dst[u][g] = *reinterpret_cast<const v2i *>(base + fb + 16 * g);
             }
         }
@@ -299,6 +309,13 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
             }
         }
     };
+    if constexpr (COAL && RAGGED) { // the pad lanes' u and skip: zero once, no row vector ever lands there
+        for (int i = threadIdx.x; i < 2 * FT; i += NTHR) {
+            int8_t *t = Ut + i * TROW + 2 * H; // (rows of Ut, then of St; 8-byte aligned like every access to the tiles)
+#pragma unroll
+            for (int j = 0; j < (HP - H) / 4; ++j) *reinterpret_cast<v2i *>(t + 8 * j) = v2i{0, 0};
+        }
+    }
     TileWalk<FT> walk((int64_t)blockIdx.x, sr, gridDim.x);
     if ((int64_t)blockIdx.x < tiles) {
         if constexpr (XPRE) load_x(walk);
@@ -318,6 +335,7 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
 #pragma unroll
         for (int i = 0; i < NVC; ++i) {
             const int v = threadIdx.x + NTHR * i, f = v / VPF, og = v % VPF;
+            if (!NVC_FULL && v >= FT * VPF) break;
             int8_t *cu = Ut + f * TROW + 16 * og, *cs_ = St + f * TROW + 16 * og;
             if (zb_prev) {
                 const v2i z0 = *reinterpret_cast<const v2i *>(cu), z1 = *reinterpret_cast<const v2i *>(cu + 8);
@@ -339,6 +357,7 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
 #pragma unroll
         for (int i = 0; i < NVC; ++i) {
             const int v = threadIdx.x + NTHR * i, f = v / VPF, og = v % VPF;
+            if (!NVC_FULL && v >= FT * VPF) break;
             int8_t *cu = Ut + f * TROW + 16 * og, *cs_ = St + f * TROW + 16 * og;
             if (zb_prev) {
                 const v2i z0 = *reinterpret_cast<const v2i *>(cu), z1 = *reinterpret_cast<const v2i *>(cu + 8);
@@ -535,7 +554,7 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
                     const int32_t du = sat(asr(__mul24(Dv[e], uv[e]), a.rs_d), a.y_bits);
                     const int32_t y = sat(2 * cx + du, a.y_bits); // 2*cx is not clipped, fxpmodel.py:765-767
                     if (TRACE) {
-                        if (a.tr_ys && 32 * sub + r < nvalid) a.tr_ys[n * H + ch0 + 8 * g + e] = y;
+                        if (a.tr_ys && 32 * sub + r < nvalid && (!RAGGED || ch0 + 8 * g < H)) a.tr_ys[n * H + ch0 + 8 * g + e] = y;
                     }
                     const int32_t x1 = y < 0 ? 0 : y;
                     x1v[u][4 * g + e] = x1;
@@ -601,7 +620,7 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
                         mx[0] = fmaxf(mx[0], fabsf(__fmaf_rn(cvtf_h<1>(zp), kz, cvtf_h<1>(sp))));
                     }
                     if constexpr (COAL) *reinterpret_cast<v2i *>(Ut + (32 * sub + r) * TROW + 2 * ch) = zo; // u is done with: B1 is behind a barrier
-                    else *reinterpret_cast<v2i *>(zb + 2u * (unsigned)((32 * sub + r) * H + ch)) = zo;
+                    else if (!RAGGED || ch < H) *reinterpret_cast<v2i *>(zb + 2u * (unsigned)((32 * sub + r) * H + ch)) = zo;
                 }
             };
             if constexpr (PK16) {
@@ -649,7 +668,7 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
                         }
                         const int32_t lq = chcfg(x1v[u][4 * g + e], a.y_bits, a.y_exp, a.l_bits, a.l_exp);
                         const int32_t z = sat(asr(__mul24(lq, rq), a.rs_gate), a.res_bits);
-                        if (TRACE) {
+                        if (TRACE && (!RAGGED || ch < H)) {
                             if (a.tr_out2) a.tr_out2[n * H + ch + e] = gq;
                             if (a.tr_sig) a.tr_sig[n * H + ch + e] = s;
                             if (a.tr_z) a.tr_z[n * H + ch + e] = z;
@@ -660,7 +679,7 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT <= 3 && KS == 1 && !WIDE ? S5_CGAT
                         // (slots 9, 10) merely size the reference's intermediate bit width and are not needed
                         mx[0] = fmaxf(mx[0], fabsf(__fmaf_rn(cz, kz, cs)));
                     }
-                    *reinterpret_cast<v2i *>(zb + 2u * (unsigned)((32 * sub + r) * H + ch)) = pack4_i16(o[0], o[1], o[2], o[3]);
+                    if (!RAGGED || ch < H) *reinterpret_cast<v2i *>(zb + 2u * (unsigned)((32 * sub + r) * H + ch)) = pack4_i16(o[0], o[1], o[2], o[3]);
                 }
             }
         }

@@ -41,6 +41,25 @@ __device__ long long g_phase_prof[2048 * 8];
 
 namespace s5 {
 
+// Channels of a model whose tile kernels run on NT 32-channel tiles.  The N-DNS recipe has H = 12 * blocks with blocks = 4, 8,
+// 12, 16 (dim_scale 0.25 .. 1.0): 48, 96, 144, 192 -- every H a multiple of 16, so a row of an (N,H) int16 plane is whole
+// 16-byte vectors, and the last tile of 48 and 144 is half empty.  Rows stay dense in memory: the row stride, the vectors per
+// frame and the per-channel loops come from this count; the LDS byte planes and tables keep the padded extent 32 * NT, where
+// the padded weights, D and biases are zero (pack_mfma), so a pad channel computes 0 and only its loads, stores and
+// extremes are masked.
+__host__ __device__ constexpr int shape_channels(int NT) { return (NT == 2 || NT == 5) ? 32 * NT - 16 : 32 * NT; }
+
+// the k tail [HC, HP) of the byte planes of ragged shapes: initialised once per workgroup (it multiplies zero weights, so any
+// constant is right; what LDS happens to hold is not relied on).  rows x KP bytes per plane, NPLANES planes from `base`.
+template <int HC, int HP, int KP>
+__device__ __forceinline__ void zero_plane_tail(int8_t *base, int rows)
+{
+    if constexpr (HC != HP) {
+        static_assert(HP - HC == 16, "half a tile");
+        for (int i = threadIdx.x; i < rows; i += blockDim.x) *reinterpret_cast<v4i *>(base + i * KP + HC) = v4i{0, 0, 0, 0};
+    }
+}
+
 // eight values in int32 registers -> byte planes (2 packed registers each), k order preserved
 __device__ __forceinline__ void planes8_from_i32(const int32_t (&v)[8], v2i &hi, v2i &lo)
 {
@@ -100,7 +119,10 @@ struct TileWalk {
 // half w / NC -- the workgroup keeps its size, so phase A (the bulk of the kernel) is unchanged; NC == NT / 4 (a 128-state
 // layer on 32 slots): the same, and the waves with w / NC >= 2 sit phase B out.
 template <int KS, int NT, bool TRACE, int SM = 0, int NC = NT>
-__global__ __launch_bounds__(64 * NT, 4) void k_bproj_p(BprojM2Args a, GroupOff go)
+// (waves per SIMD the registers are budgeted for: 4; 3 at H = 144, whose grid holds two workgroups per CU anyway
+// (s5fxp_fast.hpp FastShape::wide) and whose 5 k-steps of weights do not fit 128 registers next to the prefetch; 2 for the
+// traced kernels, which hold the trace pointers as well and are no hot path)
+__global__ __launch_bounds__(64 * NT, TRACE ? 2 : KS == 5 ? 3 : 4) void k_bproj_p(BprojM2Args a, GroupOff go)
 {
     {
         const int64_t g = blockIdx.y;
@@ -108,7 +130,8 @@ __global__ __launch_bounds__(64 * NT, 4) void k_bproj_p(BprojM2Args a, GroupOff 
         gshift(a.ext, g * go.ws); gshift(a.status, g * go.status); gshift(a.status_exps, g * go.status);
     }
     static_assert(NC == NT || 2 * NC == NT || 4 * NC == NT, "column tiles per workgroup");
-    constexpr int H = 32 * KS, FT = 64, KP = 32 * KS + 16, PC = 16 * NC, SUB0_STEP = NT / NC; // halves a wave takes: 2 / SUB0_STEP
+    // H: the real channels (row stride, vectors per frame, BatchNorm operands); HP: the k extent of the byte planes
+    constexpr int H = shape_channels(KS), HP = 32 * KS, FT = 64, KP = 32 * KS + 16, PC = 16 * NC, SUB0_STEP = NT / NC; // halves a wave takes: 2 / SUB0_STEP
     constexpr int VPF = H / 8;             // 16-byte vectors per frame
     constexpr int NTHR = 64 * NT;          // one wave per column tile: 256 threads at dim 0.5, 512 at dim 1.0
     constexpr int NV = FT * VPF / NTHR;    // vectors per thread and tile
@@ -117,7 +140,8 @@ __global__ __launch_bounds__(64 * NT, 4) void k_bproj_p(BprojM2Args a, GroupOff 
     static_assert(FT * VPF % NTHR == 0, "tile shape");
     extern __shared__ __attribute__((aligned(16))) int8_t smem[];
     int32_t *tab = reinterpret_cast<int32_t *>(smem);             // 4*H BatchNorm operands
-    int8_t *Xh = smem + 16 * H, *Xl = Xh + 2 * PLANE;             // [buf][frame][KP]
+    int8_t *Xh = smem + 16 * HP, *Xl = Xh + 2 * PLANE;            // [buf][frame][KP]
+    zero_plane_tail<H, HP, KP>(Xh, 4 * FT);                       // (visible behind the barrier below)
     const int l = threadIdx.x & 63, r = l & 31, h = l >> 5, wave = threadIdx.x >> 6;
     const int wct = wave % NC, wsub = wave / NC; // this wave's column tile and first 32-frame half
     const StepRange sr{a.t_lo, a.t_len};
@@ -156,7 +180,7 @@ __global__ __launch_bounds__(64 * NT, 4) void k_bproj_p(BprojM2Args a, GroupOff 
     // column of the wave -- and the contraction on the VALU, one multiply-add per (frame, nonzero) and byte plane,
     // instead of the dense zero-filled MFMA operand.  Same accumulators, same epilogue, same results.
     constexpr int ELLW = S5_BPROJ_CSR;
-    uint16_t *ell = reinterpret_cast<uint16_t *>(smem + 16 * H + 4 * PLANE); // [32 * NC columns][ELLW]: k | w << 8
+    uint16_t *ell = reinterpret_cast<uint16_t *>(smem + 16 * HP + 4 * PLANE); // [32 * NC columns][ELLW]: k | w << 8
     int *ellmax = reinterpret_cast<int *>(ell + 32 * NC * ELLW);            // [NC]: widest column of the tile
     if (threadIdx.x < NC) ellmax[threadIdx.x] = 0;
     __syncthreads();
@@ -448,7 +472,12 @@ __global__ __launch_bounds__(384, 3) void k_enc_p(EncArgs a, float *ext, int ext
         gshift(a.x, g * go.x); gshift(a.y, g * go.ws); gshift(a.status, g * go.status); gshift(ext, g * go.ws);
     }
     constexpr int KS = 9, FT = 64, KP = 32 * KS + 16, NW = 6, H = 32 * NT;
-    constexpr int NU = 2 * NT / NW, SUBSTEP = NW / NT;
+    // phase B units (32-frame half, column tile) per wave: NT <= 3: wave -> (half wave / NT, tile wave % NT), one unit;
+    // NT > 3: wave -> tile `wave`, both halves.  UW waves have units: all six at NT = 3 and 6; at NT = 2 and 5 the last
+    // two / the last one sit phase B out (its weights stay per wave: a second tile's would not fit the registers)
+    constexpr int NU = NT <= 3 ? 1 : 2, SUBSTEP = NT <= 3 ? 0 : 1, UW = NT <= 3 ? 2 * NT : NT;
+    static_assert(UW <= NW, "one wave per unit or per column tile");
+    constexpr bool RAGGED = shape_channels(NT) != 32 * NT; // the last column tile is half empty: its stores are conditional
     constexpr int RPW = (FT + NW - 1) / NW; // rows per wave
     extern __shared__ __attribute__((aligned(16))) int8_t smem[];
     int32_t *cs = reinterpret_cast<int32_t *>(smem), *be = cs + H;
@@ -517,7 +546,7 @@ __global__ __launch_bounds__(384, 3) void k_enc_p(EncArgs a, float *ext, int ext
         // ---- phase A
         // the prefetched rows are older than the previous tile's stores: NU x 4 per wave on the unconditional path (the
         // conditional one ends with a full wait)
-        vm_wait<4 * NU>(rawa);
+        vm_wait<RAGGED ? 0 : 4 * NU>(rawa);
         if constexpr (RB > 0) {
 #pragma unroll
             for (int i = 0; i < RB; ++i) rawb[i] = *row_ptr(tile, RA + i);
@@ -551,6 +580,7 @@ __global__ __launch_bounds__(384, 3) void k_enc_p(EncArgs a, float *ext, int ext
         // ---- phase B
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
+            if (UW < NW && wave_u >= UW) break;
             const int sub = sub0 + u * SUBSTEP;
             const int64_t n = n0 + 32 * sub + r;
             v16i acc;
@@ -629,7 +659,12 @@ __global__ __launch_bounds__(384, 3) void k_enc_pf(EncArgs a, float *ext, int ex
         gshift(a.x, g * go.x); gshift(a.y, g * go.ws); gshift(a.status, g * go.status); gshift(ext, g * go.ws);
     }
     constexpr int KS = 9, FT = 64, KP = 32 * KS + 16, NW = 6, H = 32 * NT;
-    constexpr int NU = 2 * NT / NW, SUBSTEP = NW / NT;
+    // phase B units (32-frame half, column tile) per wave: NT <= 3: wave -> (half wave / NT, tile wave % NT), one unit;
+    // NT > 3: wave -> tile `wave`, both halves.  UW waves have units: all six at NT = 3 and 6; at NT = 2 and 5 the last
+    // two / the last one sit phase B out (its weights stay per wave: a second tile's would not fit the registers)
+    constexpr int NU = NT <= 3 ? 1 : 2, SUBSTEP = NT <= 3 ? 0 : 1, UW = NT <= 3 ? 2 * NT : NT;
+    static_assert(UW <= NW, "one wave per unit or per column tile");
+    constexpr bool RAGGED = shape_channels(NT) != 32 * NT; // the last column tile is half empty: its stores are conditional
     constexpr int RPW = (FT + NW - 1) / NW; // rows per wave
     extern __shared__ __attribute__((aligned(16))) int8_t smem[];
     int32_t *cs = reinterpret_cast<int32_t *>(smem), *be = cs + H;
@@ -701,7 +736,7 @@ __global__ __launch_bounds__(384, 3) void k_enc_pf(EncArgs a, float *ext, int ex
         // ---- phase A
         // the prefetched rows are older than the previous tile's stores: NU x 4 per wave on the unconditional path (the
         // conditional one ends with a full wait)
-        vm_wait<4 * NU>(rawa);
+        vm_wait<RAGGED ? 0 : 4 * NU>(rawa);
         if constexpr (RB > 0) {
 #pragma unroll
             for (int i = 0; i < RB; ++i) rawb[i] = *row_ptr(tile, RA + i);
@@ -735,6 +770,7 @@ __global__ __launch_bounds__(384, 3) void k_enc_pf(EncArgs a, float *ext, int ex
         // ---- phase B
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
+            if (UW < NW && wave_u >= UW) break;
             const int sub = sub0 + u * SUBSTEP;
             const int64_t n = n0 + 32 * sub + r;
             v16i acc;
@@ -831,11 +867,13 @@ __global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_p(DecArgs
             gshift_nn(rz.hd.status_exps, g * go.status);
         }
     }
-    constexpr int H = 32 * KS, FT = 64, KP = H + 16, NW = 6, CT = 9, CPW = 3;
+    // H: the real channels (row stride, vectors per frame); HP: the k extent of the byte planes (shape_channels)
+    constexpr int H = shape_channels(KS), HP = 32 * KS, FT = 64, KP = HP + 16, NW = 6, CT = 9, CPW = 3;
     constexpr int VPF = H / 8, NV = FT * VPF / 384;
     static_assert(FT * VPF % 384 == 0, "tile shape");
     extern __shared__ __attribute__((aligned(16))) int8_t smem[];
     int8_t *Xh = smem, *Xl = Xh + FT * KP;
+    zero_plane_tail<H, HP, KP>(Xh, 2 * FT); // (visible behind the first tile's barrier)
     const int l = threadIdx.x & 63, r = l & 31, h = l >> 5, wave = threadIdx.x >> 6;
     const int sub = wave / 3, c0 = wave % 3;
     const int64_t tiles = (a.N + FT - 1) / FT;
@@ -992,11 +1030,13 @@ __global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_pf(DecArg
             gshift_nn(rz.hd.status_exps, g * go.status);
         }
     }
-    constexpr int H = 32 * KS, FT = 64, KP = H + 16, NW = 6, CT = 9, CPW = 3;
+    // H: the real channels (row stride, vectors per frame); HP: the k extent of the byte planes (shape_channels)
+    constexpr int H = shape_channels(KS), HP = 32 * KS, FT = 64, KP = HP + 16, NW = 6, CT = 9, CPW = 3;
     constexpr int VPF = H / 8, NV = FT * VPF / 384;
     static_assert(FT * VPF % 384 == 0, "tile shape");
     extern __shared__ __attribute__((aligned(16))) int8_t smem[];
     int8_t *Xh = smem, *Xl = Xh + FT * KP;
+    zero_plane_tail<H, HP, KP>(Xh, 2 * FT); // (visible behind the first tile's barrier)
     const int l = threadIdx.x & 63, r = l & 31, h = l >> 5, wave = threadIdx.x >> 6;
     const int sub = wave / 3, c0 = wave % 3;
     const int64_t tiles = (a.N + FT - 1) / FT;

@@ -56,13 +56,45 @@ inline bool fits_bits(const int32_t *v, size_t n, int bits)
     return true;
 }
 
-// The MFMA path is instantiated for the NDNS shapes (recipes/ndns.json at dim_scale 0.5 and 1.0) with
-// <= 8-bit weights and <= 16-bit activations; everything else runs the generic kernels.
+// The shape class of a fused forward: everything its stages derive from the model's (H, P).  The tile kernels are instantiated
+// for the four N-DNS shapes (recipes/ndns.json at dim_scale 0.25, 0.5, 0.75, 1.0): H = 48, 96, 144, 192 on nt = 2, 3, 5, 6
+// 32-channel tiles, P = 2 H / 3 states.  48 and 144 leave the last tile half empty: rows stay dense in memory and the kernels
+// mask the pad lanes (proj_p.hpp shape_channels).  This is the one place that knows the shapes: the stages take tile counts,
+// thread counts and LDS extents from here, and nt_kernel / ks_kernel below turn nt and a layer's ks into template arguments.
+struct FastShape {
+    int nt = 0;        // 32-channel tiles of H (0: not a fused shape)
+    int hp = 0;        // 32 * nt: the extent of the kernels' LDS tables and byte planes
+    int bproj_waves;   // waves of k_bproj_p: one per 32-column tile of [B_re | B_im] = 2 P / 32
+    int gate_threads;  // k_cgate_p on 64-frame tiles: one wave per (32-frame half, channel tile)
+    bool gate32;       // the 32-frame, GBN and UREC forms of the packed-epilogue gate kernel exist (tuned for H = 96 only)
+    bool wide;         // H >= 144: half the B projection's workgroups per CU
+};
+inline FastShape fast_shape(int H, int P)
+{
+    FastShape s{};
+    if (!(H == 48 || H == 96 || H == 144 || H == 192) || 3 * P != 2 * H) return s;
+    s.nt = (H + 31) / 32;
+    s.hp = 32 * s.nt;
+    s.bproj_waves = 2 * P / 32;
+    s.gate_threads = 128 * s.nt;
+    s.gate32 = s.nt == 3;
+    s.wide = s.nt >= 5;
+    return s;
+}
+// kernel(std::integral_constant<int, NT>) for the shape's tile count
+template <class Kernel> auto nt_kernel(int nt, Kernel kernel)
+{
+    return nt == 2 ? kernel(std::integral_constant<int, 2>{}) : nt == 3 ? kernel(std::integral_constant<int, 3>{})
+         : nt == 5 ? kernel(std::integral_constant<int, 5>{}) : kernel(std::integral_constant<int, 6>{});
+}
+
+// The MFMA path runs the N-DNS shapes (FastShape) with <= 8-bit weights and <= 16-bit activations; everything else runs
+// the generic kernels.
 bool fast_eligible(const s5fxp_model_desc *d)
 {
     if (d->n_layers < 1) return false;
     const int H = d->encoder.M, K = d->encoder.K, M = d->decoder.M, P = d->layers[0].ssm.P;
-    if (!((H == 96 && P == 64) || (H == 192 && P == 128))) return false;
+    if (!fast_shape(H, P).nt) return false;
     if (K <= 256 || K > 288 || M > 288 || M < 1) return false;
     auto dense16 = [](const s5fxp_dense_desc &e) { return e.inp_bits <= 16 && e.out_bits <= 16 && e.b_bits <= 32; };
     if (!dense16(d->encoder) || d->decoder.inp_bits > 16 || d->decoder.out_bits > 32) return false;
@@ -334,7 +366,7 @@ LayerPlan plan_layer(const s5fxp_model *m, int li, int fwd_flags, bool traced, b
     const LayerDev &l = m->layers[li];
     const FastLayer &fl = m->fast->layers[li];
     const s5fxp_ssm_desc &s = l.sd;
-    const bool big = m->H == 192;
+    const FastShape sh = fast_shape(m->H, m->P);
     LayerPlan p{};
     p.compact = fl.compact_ok && !m->cfg.no_compact && !traced && !carry;
     p.rung = select_rung(m, li, fwd_flags, traced, p.compact);
@@ -359,12 +391,12 @@ LayerPlan plan_layer(const s5fxp_model *m, int li, int fwd_flags, bool traced, b
     // exponents are the ones this layer's B projection publishes in its prologue).  The first form of it (k_cgate_p<.., GBN>,
     // S5FXP_GATE_BN=1: 64-frame tiles, bn16_x4 in the first epilogue, operands from an LDS table) lost: gate kernel 207 -> 250 us
     // per 8-batch launch, B projection 104 -> 90, 3 % slower overall.  Kept as the record; what ships is gate_urec below.
-    p.gate_bn = p.pk16 && fold && !big && m->cfg.gate_bn;
+    p.gate_bn = p.pk16 && fold && sh.gate32 && m->cfg.gate_bn;
     // 32-frame tiles, three-wave workgroups: with the sigmoid table sized exactly FIVE of them fit a CU's LDS and registers --
     // 15 waves instead of the 12 of two six-wave workgroups, for a kernel whose waves wait two thirds of their cycles.  The
     // grid is exactly what is resident at once (5 x 256 CUs): 170 us per 8-batch launch against 190 (tools/ab_cgate_ft32.sh;
     // 1024 or 1536 workgroups: 189 / 209).  (Without PK16 they were tried as well: 39 vs 36 us.)
-    p.gate = traced ? GATE_TRACED : p.gate_bn ? GATE_GBN : (!big && p.pk16 && !m->cfg.cgate_ft64) ? GATE_FT32 : GATE_FT64;
+    p.gate = traced ? GATE_TRACED : p.gate_bn ? GATE_GBN : (sh.gate32 && p.pk16 && !m->cfg.cgate_ft64) ? GATE_FT32 : GATE_FT64;
     // The 32-frame form rebuilds u in its tile staging, where a thread holds whole 16-byte rows of the layer input and no
     // accumulator is live, from operands in eight registers and in 4.5-6 instructions per element chosen by the layer's shifts
     // (mfma_fused.hpp UREC, mfma_bn.hpp bn16_row8): by default wherever the B projection publishes the exponents (fold) and the
@@ -382,48 +414,82 @@ LayerPlan plan_layer(const s5fxp_model *m, int li, int fwd_flags, bool traced, b
 // What s5fxp_model_recurrence_kernel / _xmax report: a plain forward (no traces, no carry) under S5FXP_FWD_DEFER_REDO
 LayerPlan plain_plan(const s5fxp_model *m, int li) { return plan_layer(m, li, S5FXP_FWD_DEFER_REDO, false, false, fast_bn_ext(m)); }
 
-// kernel(std::integral_constant<int, KS>) for a layer's KS = state slots / 32: 2 (H = 96) or 4 (H = 192, NT = 6), halved or
-// quartered for a compacted layer.  The one KS helper of the fused path: it instantiates no KS that cannot run.
+// kernel(std::integral_constant<int, KS>) for a layer's KS = state slots / 32: 1 (NT = 2), 2 (NT = 3), 3 (NT = 5) or 4 (NT = 6);
+// at NT = 3 and 6 halved or quartered for a compacted layer (the 32 and 96 states of NT = 2 and 5 are never compacted:
+// FastLayer::compact_ok).  The one KS helper of the fused path: it instantiates no KS that cannot run.
 template <int NT, class Kernel> auto ks_kernel(int ks, Kernel kernel)
 {
-    if constexpr (NT == 6)
-        if (ks == 4) return kernel(std::integral_constant<int, 4>{});
-    return ks == 1 ? kernel(std::integral_constant<int, 1>{}) : kernel(std::integral_constant<int, 2>{});
+    if constexpr (NT == 2) return kernel(std::integral_constant<int, 1>{});
+    else if constexpr (NT == 5) return kernel(std::integral_constant<int, 3>{});
+    else {
+        if constexpr (NT == 6)
+            if (ks == 4) return kernel(std::integral_constant<int, 4>{});
+        return ks == 1 ? kernel(std::integral_constant<int, 1>{}) : kernel(std::integral_constant<int, 2>{});
+    }
 }
+// waves of the B projection for NT channel tiles (FastShape::bproj_waves as a template argument)
+template <int NT> constexpr int bproj_waves_of() { return NT == 2 ? 2 : NT == 3 ? 4 : NT == 5 ? 6 : 8; }
 
 // k_bproj_p of an untraced layer: SM = the stream its recurrence rung wants (proj_p.hpp), NC = 2 KS column tiles
-template <int SM> auto bproj_kernel(bool big, int ks)
+template <int SM> auto bproj_kernel(const FastShape &sh, int ks)
 {
-    return big ? ks_kernel<6>(ks, [](auto k) { return k_bproj_p<6, 8, false, SM, 2 * decltype(k)::value>; })
-               : ks_kernel<3>(ks, [](auto k) { return k_bproj_p<3, 4, false, SM, 2 * decltype(k)::value>; });
+    return nt_kernel(sh.nt, [&](auto n) {
+        constexpr int NT = decltype(n)::value;
+        return ks_kernel<NT>(ks, [](auto k) { return k_bproj_p<NT, bproj_waves_of<NT>(), false, SM, 2 * decltype(k)::value>; });
+    });
+}
+// ... and of a traced one (every state slot, int32 stream)
+inline auto bproj_traced_kernel(const FastShape &sh)
+{
+    return nt_kernel(sh.nt, [](auto n) { constexpr int NT = decltype(n)::value; return k_bproj_p<NT, bproj_waves_of<NT>(), true>; });
 }
 
 // k_cgate_p<KS, NT, false, S16, DIRECT, FTP, false, PAIR, PK16, GBN, UREC> of an untraced, inexact layer in its gate form: the
-// 32-frame (with or without UREC) and GBN forms exist for the packed epilogues (PK16) at H = 96 only
-template <bool S16, bool DIR, bool PAIR, bool PK16> auto cgate_kernel(const LayerPlan &p, bool big)
+// 32-frame (with or without UREC) and GBN forms exist for the packed epilogues (PK16) at H = 96 only (FastShape::gate32)
+template <bool S16, bool DIR, bool PAIR, bool PK16> auto cgate_kernel(const LayerPlan &p, const FastShape &sh)
 {
-    if (big) return ks_kernel<6>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 6, false, S16, DIR, 64, false, PAIR, PK16>; });
-    if constexpr (PK16) {
-        if (p.gate == GATE_FT32 && p.gate_urec)
-            return ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 32, false, PAIR, true, false, true>; });
-        if (p.gate == GATE_FT32)
-            return ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 32, false, PAIR, true>; });
-        if (p.gate == GATE_GBN)
-            return ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 64, false, PAIR, true, true>; });
-    }
-    return ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 64, false, PAIR, PK16>; });
+    return nt_kernel(sh.nt, [&](auto n) {
+        constexpr int NT = decltype(n)::value;
+        if constexpr (PK16 && NT == 3) {
+            if (p.gate == GATE_FT32 && p.gate_urec)
+                return ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 32, false, PAIR, true, false, true>; });
+            if (p.gate == GATE_FT32)
+                return ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 32, false, PAIR, true>; });
+            if (p.gate == GATE_GBN)
+                return ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 64, false, PAIR, true, true>; });
+        }
+        return ks_kernel<NT>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, NT, false, S16, DIR, 64, false, PAIR, PK16>; });
+    });
 }
 // ... for the seven (S16, DIRECT, PAIR, PK16) a plan can hold (PK16 needs DIRECT; DIRECT and PAIR need S16)
-auto gate_kernel(const LayerPlan &p, bool big)
+auto gate_kernel(const LayerPlan &p, const FastShape &sh)
 {
     const bool pair = p.rung.pair;
-    return p.pk16 && pair   ? cgate_kernel<true, true, true, true>(p, big)
-           : p.pk16         ? cgate_kernel<true, true, false, true>(p, big)
-           : p.direct && pair ? cgate_kernel<true, true, true, false>(p, big)
-           : pair           ? cgate_kernel<true, false, true, false>(p, big)
-           : p.direct       ? cgate_kernel<true, true, false, false>(p, big)
-           : p.rung.s16     ? cgate_kernel<true, false, false, false>(p, big)
-                            : cgate_kernel<false, false, false, false>(p, big);
+    return p.pk16 && pair   ? cgate_kernel<true, true, true, true>(p, sh)
+           : p.pk16         ? cgate_kernel<true, true, false, true>(p, sh)
+           : p.direct && pair ? cgate_kernel<true, true, true, false>(p, sh)
+           : pair           ? cgate_kernel<true, false, true, false>(p, sh)
+           : p.direct       ? cgate_kernel<true, true, false, false>(p, sh)
+           : p.rung.s16     ? cgate_kernel<true, false, false, false>(p, sh)
+                            : cgate_kernel<false, false, false, false>(p, sh);
+}
+// the exact gate kernel (k_cgate_p<.., WIDE>): the in-forward re-run and S5FXP_FWD_EXACT; traced: every state slot
+inline auto gate_exact_kernel(const LayerPlan &p, const FastShape &sh, bool traced)
+{
+    return nt_kernel(sh.nt, [&](auto n) {
+        constexpr int NT = decltype(n)::value;
+        constexpr int KSF = NT == 2 ? 1 : NT == 3 ? 2 : NT == 5 ? 3 : 4; // all of the shape's states
+        if (traced) return k_cgate_p<KSF, NT, true, false, false, 64, true>;
+        return ks_kernel<NT>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, NT, false, false, false, 64, true>; });
+    });
+}
+inline auto gate_traced_kernel(const FastShape &sh)
+{
+    return nt_kernel(sh.nt, [](auto n) {
+        constexpr int NT = decltype(n)::value;
+        constexpr int KSF = NT == 2 ? 1 : NT == 3 ? 2 : NT == 5 ? 3 : 4;
+        return k_cgate_p<KSF, NT, true>;
+    });
 }
 
 // Workgroups of a launch over `tiles` tiles, at most `cap` of them (persistent loops over the tiles)
@@ -452,7 +518,7 @@ struct FusedForward {
     const ModelCfg &cfg = m->cfg;
     const int H = m->H, fwd_flags = opts ? opts->flags : 0;
     const int64_t N = (int64_t)B * L, NH = N * H;
-    const bool big = H == 192;
+    const FastShape sh = fast_shape(m->H, m->P);
     const bool exact = (fwd_flags & S5FXP_FWD_EXACT) != 0, defer = (fwd_flags & S5FXP_FWD_DEFER_REDO) && !exact;
     const s5fxp_allreduce_max_fn allreduce = opts ? opts->allreduce : nullptr;
     const int32_t *state_in = opts ? opts->state_in : nullptr;
@@ -480,9 +546,9 @@ struct FusedForward {
     // six-wave phase-split kernels (proj_p.hpp, mfma_fused.hpp): 64-frame tiles; the per-layer ones tile each sequence
     const int64_t tiles64 = (N + 63) / 64, seq_tiles64 = (int64_t)B * ((L + 63) / 64);
     const unsigned grid_enc = grid_for(tiles64, per_group(cfg.cap_enc, 64)), grid_dec = grid_for(tiles64, per_group(cfg.cap_dec, 64));
-    // the B projection: up to 4 (H=96) / 2 (H=192) workgroups per CU
+    // the B projection: up to 4 (H <= 96) / 2 (H >= 144) workgroups per CU
     const int64_t cap_bproj = per_group(cfg.cap_bproj, 128);
-    const unsigned grid_bproj = grid_for(seq_tiles64, big ? std::max<int64_t>(cap_bproj / 2, 1) : cap_bproj);
+    const unsigned grid_bproj = grid_for(seq_tiles64, sh.wide ? std::max<int64_t>(cap_bproj / 2, 1) : cap_bproj);
     const unsigned grid_gate = grid_for(seq_tiles64, per_group(cfg.cap_cgate, 64)), grid_gate_exact = grid_for(seq_tiles64, 512);
     const unsigned grid_gate32 = grid_for((int64_t)B * ((L + 31) / 32), std::max<int64_t>(cfg.cap_cgate32 / G, 1));
     // residual / extremes pass: a workgroup owns rm_span consecutive frames, a multiple of its 4 x R frame step
@@ -564,12 +630,12 @@ struct FusedForward {
         a.rs = (a.conv ? e.inp_exp : x_exp) + e.w_exp - e.out_exp;
         if (!shift_ok(a.rs)) return S5FXP_ENEGSHIFT;
         a.out_bits = e.out_bits; a.status = status;
-        const size_t smem = 4 * (size_t)H * 4 + 2 * 64 * 304; // cs128 + bias_eff + byte planes + extremes
+        const size_t smem = 4 * (size_t)sh.hp * 4 + 2 * 64 * 304; // cs128 + bias_eff + byte planes + extremes
         // the extremes of the output (layer 0's BatchNorm operand) are gathered on the way; single-rank mode also
         // lets the last workgroup derive layer 0's BatchNorm exponents (mfma_bn.hpp ResidTail)
         float *ext0 = bn_ext ? ext(0) : nullptr;
         const int ext_reps = (ext0 && !allreduce) ? EXT_REPS : 1; // the consumer (k_bproj_p's prologue) folds the replicas
-        auto kernel = f32 ? (big ? k_enc_pf<6> : k_enc_pf<3>) : (big ? k_enc_p<6> : k_enc_p<3>);
+        auto kernel = nt_kernel(sh.nt, [&](auto n) { return f32 ? k_enc_pf<decltype(n)::value> : k_enc_p<decltype(n)::value>; });
         launch(kernel, grid_enc, 384, smem, nullptr, nullptr, a, ext0, ext_reps);
         return S5FXP_OK;
     }
@@ -618,16 +684,16 @@ struct FusedForward {
         }
         a.t_lo = 0; a.t_len = L;
 #ifdef S5_BPROJ_CSR
-        const size_t smem = 16 * (size_t)H + 4 * 64 * (size_t)(H + 16) + 2 * (size_t)(2 * m->P) * S5_BPROJ_CSR + 64; // + compressed columns
+        const size_t smem = 16 * (size_t)sh.hp + 4 * 64 * (size_t)(sh.hp + 16) + 2 * (size_t)(2 * m->P) * S5_BPROJ_CSR + 64; // + compressed columns
 #else
-        const size_t smem = 16 * (size_t)H + 4 * 64 * (size_t)(H + 16); // BN operands + double-buffered byte planes
+        const size_t smem = 16 * (size_t)sh.hp + 4 * 64 * (size_t)(sh.hp + 16); // BN operands + double-buffered byte planes
 #endif
         // phase-split kernel (proj_p.hpp), one wave per 32-column tile of [B_re | B_im]; SM: the stream the recurrence rung
         // wants; a compacted layer has fewer column tiles (NC)
         const Rung &r = p.rung;
-        auto kernel = tr ? (big ? k_bproj_p<6, 8, true> : k_bproj_p<3, 4, true>)
-                         : r.pairl ? bproj_kernel<3>(big, p.ks) : r.pair ? bproj_kernel<2>(big, p.ks) : r.s16 ? bproj_kernel<1>(big, p.ks) : bproj_kernel<0>(big, p.ks);
-        launch(kernel, grid_bproj, big ? 512 : 256, smem, nullptr, nullptr, a);
+        auto kernel = tr ? bproj_traced_kernel(sh)
+                         : r.pairl ? bproj_kernel<3>(sh, p.ks) : r.pair ? bproj_kernel<2>(sh, p.ks) : r.s16 ? bproj_kernel<1>(sh, p.ks) : bproj_kernel<0>(sh, p.ks);
+        launch(kernel, grid_bproj, 64 * sh.bproj_waves, smem, nullptr, nullptr, a);
     }
     // the recurrence's arguments on the quad layout (the fast quad kernels, the exact chain and its gated re-run)
     ScanQuadArgs quad_args(int li, const int32_t *run_if) const
@@ -707,7 +773,8 @@ struct FusedForward {
         a.bad_bits = ST_WIDE_STATE | (defer ? ST_REDO : 0);
         a.bn = bn;
         a.t_lo = 0; a.t_len = L;
-        const unsigned threads = big ? 768 : 384;
+        const unsigned threads = sh.gate_threads;
+        const size_t HP = sh.hp; // the kernels' LDS extents
         // the untraced, inexact gate launch carries the gate events
         void **evs = opts ? opts->gate_events : nullptr;
         const hipEvent_t gev0 = event(evs, li, 0), gev1 = event(evs, li, 1);
@@ -717,16 +784,16 @@ struct FusedForward {
             for (int g = 0; g < G; ++g)
                 if (int rc = hip_rc(hipMemsetAsync(reinterpret_cast<char *>(&d->redo) + (size_t)g * go.ws, 0xff, 4, st))) return rc;
         } else if (p.gate == GATE_FT32) {
-            const size_t smem32 = 5 * (size_t)H * 4 + 32 + sig_lds + 2 * 32 * (size_t)(2 * p.P + 16) + 2 * 32 * (size_t)(H + 16) + 192 +
-                                  2 * 32 * (size_t)(2 * H + 8);
-            launch(gate_kernel(p, big), grid_gate32, 192, smem32, gev0, gev1, a);
+            const size_t smem32 = 5 * HP * 4 + 32 + sig_lds + 2 * 32 * (size_t)(2 * p.P + 16) + 2 * 32 * (HP + 16) + 192 +
+                                  2 * 32 * (2 * HP + 8);
+            launch(gate_kernel(p, sh), grid_gate32, 192, smem32, gev0, gev1, a);
         } else {
             // phase-split fused kernel (mfma_fused.hpp): six waves per workgroup, 64-frame tiles, no weights in LDS
-            const size_t smem = 5 * (size_t)H * 4 + 32 + sig_lds + 2 * 64 * (size_t)(2 * p.P + 16) + 2 * 64 * (size_t)(H + 16) + 192 +
-                                (p.gate_bn ? 16 * (size_t)H : 0) +
-                                (p.pk16 && !p.gate_bn ? 2 * 64 * (size_t)(2 * H + 8) : 0); // + the u / skip / z tiles (mfma_fused.hpp COAL)
-            if (tr) launch(big ? k_cgate_p<4, 6, true> : k_cgate_p<2, 3, true>, grid_gate, threads, smem, nullptr, nullptr, a);
-            else launch(gate_kernel(p, big), grid_gate, threads, smem, gev0, gev1, a);
+            const size_t smem = 5 * HP * 4 + 32 + sig_lds + 2 * 64 * (size_t)(2 * p.P + 16) + 2 * 64 * (HP + 16) + 192 +
+                                (p.gate_bn ? 16 * HP : 0) +
+                                (p.pk16 && !p.gate_bn ? 2 * 64 * (2 * HP + 8) : 0); // + the u / skip / z tiles (mfma_fused.hpp COAL)
+            if (tr) launch(gate_traced_kernel(sh), grid_gate, threads, smem, nullptr, nullptr, a);
+            else launch(gate_kernel(p, sh), grid_gate, threads, smem, gev0, gev1, a);
         }
         // ---- exact re-run, only if a state left the fast kernels' range (LayerDyn::redo); with
         // S5FXP_FWD_DEFER_REDO the caller repeats the forward instead (S5FXP_ST_REDO)
@@ -736,12 +803,8 @@ struct FusedForward {
             // slots 11..13, which the residual pass picks when `redo` is set
             CGateArgs e = a;
             e.run_if = &d->redo; e.mx_slot = 11; e.bad_bits = 0;
-            const size_t smem_w = 5 * (size_t)H * 4 + 32 + 4 * (size_t)SIGTAB_WORDS + 4 * 64 * (size_t)(2 * p.P + 16) +
-                                  2 * 64 * (size_t)(H + 16) + 192;
-            auto kernel = tr ? (big ? k_cgate_p<4, 6, true, false, false, 64, true> : k_cgate_p<2, 3, true, false, false, 64, true>)
-                        : big ? ks_kernel<6>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 6, false, false, false, 64, true>; })
-                              : ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, false, false, 64, true>; });
-            launch(kernel, grid_gate_exact, threads, smem_w, nullptr, nullptr, e);
+            const size_t smem_w = 5 * HP * 4 + 32 + 4 * (size_t)SIGTAB_WORDS + 4 * 64 * (size_t)(2 * p.P + 16) + 2 * 64 * (HP + 16) + 192;
+            launch(gate_exact_kernel(p, sh, tr != nullptr), grid_gate_exact, threads, smem_w, nullptr, nullptr, e);
         }
         const size_t plane = (size_t)B * p.P;
         if (state_out) // carry out: the state after frame L-1, from whichever kernel wrote the stream last
@@ -811,10 +874,12 @@ struct FusedForward {
             dz.z = I16(w.z); dz.res_bits = l.res_bits; dz.skip_bits = hb; dz.hd = resid_head(dec_resid);
             a.xb = l.res_bits;
         }
-        const size_t smem = 2 * 64 * (size_t)(H + 16);
+        const size_t smem = 2 * 64 * (size_t)(sh.hp + 16);
         // 192 channels: 2 x 4 vectors of prefetch, one workgroup per CU
-        auto kernel = f32 ? (dec_resid >= 0 ? (big ? k_dec_pf<6, true> : k_dec_pf<3, true>) : (big ? k_dec_pf<6, false> : k_dec_pf<3, false>))
-                          : (dec_resid >= 0 ? (big ? k_dec_p<6, true> : k_dec_p<3, true>) : (big ? k_dec_p<6, false> : k_dec_p<3, false>));
+        auto kernel = nt_kernel(sh.nt, [&](auto n) {
+            constexpr int NT = decltype(n)::value;
+            return f32 ? (dec_resid >= 0 ? k_dec_pf<NT, true> : k_dec_pf<NT, false>) : (dec_resid >= 0 ? k_dec_p<NT, true> : k_dec_p<NT, false>);
+        });
         launch(kernel, grid_dec, 384, smem, nullptr, nullptr, a, dz);
     }
 };

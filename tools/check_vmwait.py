@@ -33,6 +33,12 @@ EXPECT = {
     "_ZN2s58k_dec_pfILi3ELb0EE": (48, 0), "_ZN2s58k_dec_pfILi6ELb0EE": (48, 0),
     "_ZN2s58k_dec_pfILi3ELb1EE": (48, 2), "_ZN2s58k_dec_pfILi6ELb1EE": (48, 2),
     "_ZN2s58k_enc_pfILi3EE": (4, 0), "_ZN2s58k_enc_pfILi6EE": (8, 0),
+    # the decoders of the ragged shapes (H = 48, 144): the same 48 stores.  (Their encoders, k_enc_p<2> / <5>, store
+    # conditionally and wait for their prefetch with vmcnt(0); the register audit below covers them.)
+    "_ZN2s57k_dec_pILi2ELb0EE": (48, 0), "_ZN2s57k_dec_pILi5ELb0EE": (48, 0),
+    "_ZN2s57k_dec_pILi2ELb1EE": (48, 2), "_ZN2s57k_dec_pILi5ELb1EE": (48, 2),
+    "_ZN2s58k_dec_pfILi2ELb0EE": (48, 0), "_ZN2s58k_dec_pfILi5ELb0EE": (48, 0),
+    "_ZN2s58k_dec_pfILi2ELb1EE": (48, 2), "_ZN2s58k_dec_pfILi5ELb1EE": (48, 2),
 }
 
 
