@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define S5FXP_VERSION 105
+#define S5FXP_VERSION 106
 
 enum {
     S5FXP_OK = 0,
@@ -198,17 +198,19 @@ size_t s5fxp_workspace_bytes(const s5fxp_model *m, int B, int L);
 
 /* Number of int32 words in the device status buffer, and its layout:
  *   [0] error bits (S5FXP_ST_*), [1] decoder output exponent,
- *   [2] which kernels this forward ran: S5FXP_PATH_GENERIC (one-lane / VALU kernels, any int32 operands) or
- *       S5FXP_PATH_FUSED (the int8-MFMA tile kernels + the quad / pair recurrence kernels),
+ *   [2] which kernels this forward ran: S5FXP_PATH_GENERIC (one-lane / VALU kernels, any int32 operands),
+ *       S5FXP_PATH_FUSED (the int8-MFMA tile kernels + the quad / pair recurrence kernels) or S5FXP_PATH_STEP (the
+ *       one-launch kernel of s5fxp_model_step),
  *   [8 + 8*l + 0..4] layer l: exponents chosen by the 4 BatchNorm ops and the residual add,
  *   [8 + 8*l + 5]    layer l: the recurrence kernel that was enqueued first, coded as s5fxp_model_recurrence_kernel
- *                    (5 = the exact 32-bit quad chain of a S5FXP_FWD_EXACT forward),
+ *                    (5 = the exact 32-bit quad chain of a S5FXP_FWD_EXACT forward, 6 = the 32-bit recurrence inside
+ *                    s5fxp_model_step's kernel),
  *   [8 + 8*l + 6]    layer l: the state slots its kernels ran on: P, or the live states rounded up to a multiple of 32
  *                    when the layer was compacted (s5fxp_model_live_states).
  *   [8 + 8*l + 7]    layer l: the state slots its two recurrence streams hold: [8 + 8*l + 6], or fewer -- the live states
  *                    rounded up to an even number -- when the LDS-fed pair kernel runs a layer compacted to 32 slots. */
 #define S5FXP_STATUS_WORDS 128
-enum { S5FXP_PATH_GENERIC = 1, S5FXP_PATH_FUSED = 2 };
+enum { S5FXP_PATH_GENERIC = 1, S5FXP_PATH_FUSED = 2, S5FXP_PATH_STEP = 3 };
 enum {
     S5FXP_ST_NEGSHIFT = 1,   /* a data-dependent shift came out negative: the reference raises ValueError */
     S5FXP_ST_NEGEXP = 2,     /* a compute_best exponent came out negative (1 << exp fails in the reference) */
@@ -314,6 +316,33 @@ size_t s5fxp_workspace_bytes_f32(const s5fxp_model *m, int B, int L);
  *   S5FXP_DEBUG_SYNC                                           synchronise and check after every stage of a forward
  * Results do not depend on any of them. */
 
+/* ------------------------------------------------------------------------------------------
+ * Streaming step: one short chunk of G independent streams in ONE kernel launch (grid = G, one workgroup per group).
+ * A group is one reference batch of B sequences x L frames with B * L <= S5FXP_STEP_MAX_ROWS rows; group g gets, bit
+ * for bit, what s5fxp_model_forward computes for that (B, L) input with that carry -- its own compute_best exponents,
+ * status words and carry, the `groups` semantics of s5fxp_forward_opts.  Every tensor-wide maximum of such a batch is a
+ * workgroup reduction, so the whole forward (encoder, per layer BatchNorm exponents -> B projection -> the plain
+ * 32-bit recurrence of fxpmodel.py:147-172 from the carry -> C projection, exact for int32 states of any width -> out2
+ * -> sigmoid -> gate -> residual, decoder) runs between __syncthreads() instead of kernel boundaries.  No workspace, no
+ * traces, no cross-rank hook, no flags, no redo: callers who need those use s5fxp_model_forward.
+ *   x (G,B,L,d_in), y (G,B,L,d_out): int32, or float32 for _f32 (fxp_from_fp FLOOR in, to_float out, as
+ *   s5fxp_model_forward_f32; x_exp 0..31); carry [G][n_layers][2][B][P]: state_in NULL = zeros, state_out NULL = not
+ *   wanted, state_out == state_in is allowed (a workgroup reads its carry before it writes it).
+ *   status: G * S5FXP_STATUS_WORDS words, written completely by the kernel: [0] error bits (NEGSHIFT, NEGEXP and
+ *   WIDE_INPUT as the fused batch path raises them: an input value beyond 16 bits after the encoder's input conversion
+ *   makes the results invalid; WIDE_STATE is informational: the four-plane C projection ran), [1] the decoder's output
+ *   exponent, [2] S5FXP_PATH_STEP, [8+8l+0..4] the five exponents, [8+8l+5] = 6, [8+8l+6] = [8+8l+7] = P.
+ * Returns S5FXP_EBADARG for null x / y / status / model, G < 1, B < 1, L < 1 or B * L > S5FXP_STEP_MAX_ROWS, and
+ * S5FXP_EUNSUPPORTED for a model that s5fxp_model_is_fast() does not report -- all before the device is touched. */
+#define S5FXP_STEP_MAX_ROWS 32
+/* 1: s5fxp_model_step serves this model at (B, L); 0: it does not (generic model, B * L > S5FXP_STEP_MAX_ROWS);
+ * -1: bad argument */
+int s5fxp_model_step_ok(const s5fxp_model *m, int B, int L);
+int s5fxp_model_step(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int G, int B, int L, int32_t *y,
+                     const int32_t *state_in, int32_t *state_out, int32_t *status, void *stream);
+int s5fxp_model_step_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int G, int B, int L, float *y,
+                         const int32_t *state_in, int32_t *state_out, int32_t *status, void *stream);
+
 /* FxpSequenceLayer.forward, fxpmodel.py:1110-1161, for layer `layer` of a created model -- the unit the reference's
  * verification walks (fxprun.py:583-727).  x: (B,L,H) int32 device with configuration (x_bits, x_exp); y: (B,L,H) int32
  * device, s5fxp_model_layer_out_bits() bits at the exponent the residual compute_best add chose: written to
@@ -345,6 +374,8 @@ int s5fxp_model_is_fast(const s5fxp_model *m);
  * 0 one lane per state (generic), 1 quad kernel with int32 streams, 2 quad kernel with int16 streams,
  * 3 pair kernel (int32 K stream in, int16 states out; sparseRNNs/fxpmodel.py:147-172 in four instructions per step),
  * 4 the same pair kernel fed through LDS by a helper wave from an int16 Bu stream (the default where it applies).
+ * (Status word [8 + 8*l + 5] uses two more codes that this query never returns: 5 = the exact 32-bit quad chain of a
+ * S5FXP_FWD_EXACT forward, 6 = the plain 32-bit recurrence that runs inside s5fxp_model_step's one kernel.)
  * -1: bad argument.  The exact re-run (S5FXP_FWD_EXACT) always uses the 32-bit quad kernel on the MFMA path. */
 int s5fxp_model_recurrence_kernel(const s5fxp_model *m, int layer);
 /* The bound on |state| up to which that kernel is exact (the consumer of the states checks it on the data and raises

@@ -6,3 +6,12 @@ forward over the C ABI), ``synth`` (synthetic NDNS-shaped models), ``_lib`` (cty
 libs5fxp.so; importing it fails loudly when the HIP extension has not been built).
 """
 __version__ = "0.1.0"
+
+_ENGINE_NAMES = ("Engine", "StreamingSession", "SessionPool", "InflightRunner")
+
+
+def __getattr__(name):  # lazy: importing the package alone must not load the HIP library
+    if name in _ENGINE_NAMES:
+        from . import engine
+        return getattr(engine, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

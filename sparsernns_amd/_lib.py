@@ -25,7 +25,8 @@ S5FXP_OK, S5FXP_EBADARG, S5FXP_ENEGSHIFT, S5FXP_EUNSUPPORTED, S5FXP_EHIP, S5FXP_
 ST_NEGSHIFT, ST_NEGEXP, ST_WIDE_STATE, ST_WIDE_INPUT, ST_REDO = 1, 2, 4, 8, 16
 FWD_DEFER_REDO, FWD_EXACT, FWD_NO_PAIR = 1, 2, 4
 STATUS_WORDS = 128
-PATH_GENERIC, PATH_FUSED = 1, 2   # status[2]
+PATH_GENERIC, PATH_FUSED, PATH_STEP = 1, 2, 3   # status[2]
+STEP_MAX_ROWS = 32
 MODEL_DEFAULT, MODEL_FORCE_DENSE, MODEL_FORCE_CSR, MODEL_FORCE_GENERIC = 0, 1, 2, 4
 
 
@@ -120,6 +121,9 @@ def _load():
         "s5fxp_model_is_fast": (i, [p]),
         "s5fxp_model_recurrence_kernel": (i, [p, i]),
         "s5fxp_model_recurrence_xmax": (i, [p, i]),
+        "s5fxp_model_step_ok": (i, [p, i, i]),
+        "s5fxp_model_step": (i, [p, p, i, i, i, i, i, p, p, p, p, p]),
+        "s5fxp_model_step_f32": (i, [p, p, i, i, i, i, i, p, p, p, p, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale: rebuild
@@ -131,7 +135,8 @@ lib = _load()
 EXPORTED_SYMBOLS = ("s5fxp_version s5fxp_strerror s5fxp_from_fp s5fxp_to_float s5fxp_change_cfg s5fxp_dense s5fxp_dense_csr s5fxp_add "
                     "s5fxp_mul s5fxp_add_cb s5fxp_mul_cb s5fxp_relu s5fxp_sigmoid s5fxp_scan s5fxp_assoc_scan_c64 s5fxp_model_blob_bytes "
                     "s5fxp_model_create s5fxp_model_destroy s5fxp_workspace_bytes s5fxp_model_forward s5fxp_model_forward_f32 s5fxp_workspace_bytes_f32 s5fxp_layer_forward s5fxp_model_layer_out_bits s5fxp_model_live_states "
-                    "s5fxp_model_out_exp s5fxp_model_out_bits s5fxp_model_is_fast s5fxp_model_recurrence_kernel s5fxp_model_recurrence_xmax").split()
+                    "s5fxp_model_out_exp s5fxp_model_out_bits s5fxp_model_is_fast s5fxp_model_recurrence_kernel s5fxp_model_recurrence_xmax "
+                    "s5fxp_model_step_ok s5fxp_model_step s5fxp_model_step_f32").split()
 
 
 def check(rc: int, what: str = "") -> None:

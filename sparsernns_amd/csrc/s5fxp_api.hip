@@ -549,6 +549,7 @@ int bn_exponent_ops(Reduce reduce, const BnArgs &bn, LayerDyn *d, int32_t *statu
 } // namespace
 
 #include "s5fxp_fast.hpp"
+#include "s5fxp_step.hpp"
 
 namespace {
 
@@ -565,6 +566,11 @@ size_t pack_all(const s5fxp_model_desc *d, Packer &p, s5fxp_model *m, bool allow
     if ((allow24 || !m) && fast_eligible(d)) {
         if (m) m->fast = new FastModel();
         pack_fast(p, d, m ? m->fast : nullptr);
+        // appended last: the parameter block of s5fxp_model_step, built from the addresses handed out above
+        StepParams sp;
+        if (m) fill_step_params(m, sp);
+        const void *dev = put_raw(p, &sp, sizeof(sp));
+        if (m) m->fast->step = reinterpret_cast<const StepParams *>(dev);
     }
     return p.off;
 }

@@ -4,6 +4,10 @@
 // -> decoder, with int16 activations and int32 recurrence streams.
 #pragma once
 
+namespace s5 {
+struct StepParams; // s5fxp_step.hpp
+}
+
 struct MfmaWDev {
     MfmaW w{};
     const int32_t *bias_eff = nullptr; // [Np], bias moved to out_exp (dense layers only)
@@ -36,6 +40,7 @@ struct FastLayer {
 struct FastModel {
     MfmaWDev enc, dec;
     std::vector<FastLayer> layers;
+    const s5::StepParams *step = nullptr; // the one-launch step's parameter block, appended to the blob (s5fxp_step.hpp)
 };
 
 namespace {

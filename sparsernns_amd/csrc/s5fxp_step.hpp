@@ -1,0 +1,594 @@
+// s5fxp_step.hpp -- the one-launch streaming step (include/s5fxp.h s5fxp_model_step): a whole forward of the fixed-point
+// S5 model, encoder to decoder, for R = B * L <= 32 rows in ONE workgroup; G independent groups are G workgroups of one
+// launch.  Included by s5fxp_api.hip after s5fxp_fast.hpp (it reads FastModel's packed int8 weight rows).
+//
+// Why one workgroup can do it: every tensor-wide maximum the model needs (the four BatchNorm compute_best exponents,
+// the residual add's exponent, the width of the states) is over R x H <= 32 x 192 values -- a workgroup reduction.  The
+// batch path (s5fxp_fast.hpp) needs a kernel boundary for each of them; here they are __syncthreads().
+//
+// Arithmetic: exactly the generic kernels' (s5fxp_kernels.hpp), op for op -- bn_chain, finalize_add_cb / finalize_mul_cb,
+// scan_step, crelu, sigmoid_lut, add_cb_apply -- with the int32 contractions on the int8 matrix cores as mfma_proj.hpp
+// describes: a 16-bit activation is two signed byte planes, an int32 state four, one v_mfma_i32_32x32x32_i8 pass per
+// plane, the partial sums recombined modulo 2^32 (fxparray.py:662 sums in int32 with wrap, so any split is exact).
+//   * rows R..31 of the 32-row MFMA tile are padding: their A-operand lanes re-read row R-1 (defined memory) and their
+//     results are dropped by the epilogues' row < R test -- they reach no maximum, check, carry or store;
+//   * k columns beyond a projection's K meet zero weights (pack_mfma pads with zeros), so their plane bytes are free;
+//   * the recurrence is the plain 32-bit chain of fxpmodel.py:147-172 (scan_step), one thread per (sequence, state),
+//     L <= 32 steps: no pair / quad rung, no range bound, no redo;
+//   * the C projection is exact for int32 states of any width: when every state of the layer (after the complex ReLU)
+//     fits 16 bits -- a workgroup-uniform test -- two byte planes run, otherwise four.
+// LDS (dynamic, sized by R): [PLA: encoder-input / state planes][PLB: u / out2-input / decoder-input planes]
+//   [h int16 R x H][x1 int16 R x H][z int16 R x H][bq int32 2 x R x P].  R = 32 at H = 192: 120 KB; R = 1: 3.4 KB.
+#pragma once
+
+namespace s5 {
+
+constexpr int STEP_MAX_ROWS = 32;
+constexpr int STEP_CUS = 256;          // MI355X
+constexpr size_t STEP_STATIC_LDS = 2048; // the kernel's static LDS (status words, reduction slots, LayerDyn, LUT), rounded up
+constexpr int STEP_MAX_WAVES = 8; // workgroups of 512, 256 or 128 threads (step_entry chooses)
+
+struct StepDense {
+    MfmaW w;
+    const int32_t *bias_eff;
+    int32_t K, M, inp_bits, inp_exp, w_exp, out_bits, out_exp;
+};
+
+struct StepLayer {
+    BnArgs bn; // xe and dyn are filled in by the kernel (the layer input's exponent is chosen on the device)
+    MfmaW bproj, cre, cim, out2;
+    const int32_t *o2_bias_eff, *Dpad, *a_re, *a_im;
+    int32_t rs_bre, rs_bim, bre_bits, bim_bits, sh_re, sh_im, ea_re, ea_im;
+    int32_t rs_cre, rs_cim, rs_d, y_bits, y_exp;
+    int32_t o2_conv, o2_inp_bits, o2_inp_exp, rs_o2, o2_out_bits, o2_out_exp, sig_x, sig_y;
+    int32_t lut[8];
+    int32_t l_bits, l_exp, r_bits, r_exp, res_bits, res_exp, rs_gate;
+};
+
+// Appended to the model blob by s5fxp_model_create (device memory; every pointer inside is a device address)
+struct StepParams {
+    int32_t n_layers, H, P, hp, d_in, d_out;
+    StepDense enc, dec;
+    StepLayer layers[15]; // 8 + 8 * n_layers <= S5FXP_STATUS_WORDS
+};
+
+struct StepArgs {
+    const StepParams *sp;
+    const void *x;          // (G,B,L,d_in) int32, or float32 with f32
+    void *y;                // (G,B,L,d_out) int32 / float32
+    const int32_t *state_in; // [G][n_layers][2][B][P] or nullptr (zeros)
+    int32_t *state_out;      // the same layout or nullptr; may alias state_in
+    int32_t *status;         // G x S5FXP_STATUS_WORDS
+    int32_t B, L, x_bits, x_exp, f32;
+};
+
+// LDS extents of one group of R rows (bytes; every region 16-byte aligned)
+struct StepLds {
+    int kpa_enc, kpa_st, kpb; // row strides of the byte planes: encoder input, states, u / out2 input / decoder input
+    size_t pla, plb, hb, x1, z, bq, total;
+};
+__host__ __device__ inline StepLds step_lds(int R, int H, int P, int hp, int d_in)
+{
+    StepLds l{};
+    auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    l.kpa_enc = (d_in + 31) / 32 * 32 + 16;
+    l.kpa_st = P + 16;
+    l.kpb = hp + 16;
+    const size_t enc = 2 * (size_t)R * l.kpa_enc, st = 8 * (size_t)R * l.kpa_st;
+    size_t off = 0;
+    l.pla = off; off += al(enc > st ? enc : st);
+    l.plb = off; off += al(2 * (size_t)R * l.kpb);
+    l.hb = off; off += al(2 * (size_t)R * H);
+    l.x1 = off; off += al(2 * (size_t)R * H);
+    l.z = off; off += al(2 * (size_t)R * H);
+    l.bq = off; off += al(8 * (size_t)R * P);
+    l.total = off;
+    return l;
+}
+
+// 16-bit value -> two byte planes [lo ^ 0x80][hi]; int32 value -> four [b0 ^ 0x80][b1 ^ 0x80][b2 ^ 0x80][b3] (mfma_proj.hpp)
+__device__ __forceinline__ void step_put2(int8_t *pl, int pstride, int off, int32_t v)
+{
+    pl[off] = (int8_t)((v & 0xff) ^ 0x80);
+    pl[pstride + off] = (int8_t)(v >> 8);
+}
+__device__ __forceinline__ void step_put4(int8_t *pl, int pstride, int off, int32_t v)
+{
+    pl[off] = (int8_t)((v & 0xff) ^ 0x80);
+    pl[pstride + off] = (int8_t)(((v >> 8) & 0xff) ^ 0x80);
+    pl[2 * pstride + off] = (int8_t)(((v >> 16) & 0xff) ^ 0x80);
+    pl[3 * pstride + off] = (int8_t)(v >> 24);
+}
+
+// One 32 x 32 output tile: rows = the group's rows (A operand: NPL byte planes [plane][row][KP] in LDS), columns =
+// channels 32 * tile .. + 31 (B operand: the channel's int8 weight row, 16 bytes per k-step and lane half, from the blob).
+// Two planes accumulate side by side (independent MFMA chains); four planes are two such pairs.  Lane (r = lane & 31,
+// h = lane >> 5) receives column 32 * tile + r of rows (i & 3) + 8 * (i >> 2) + 4 * h, i = 0..15.
+template <int NPL>
+__device__ __forceinline__ v16i step_mm(const int8_t *pl, int pstride, int KP, int arow, int h, const MfmaW &w, int col, int nks)
+{
+    static_assert(NPL == 2 || NPL == 4, "byte planes of a 16- or 32-bit operand");
+    const int8_t *wrow = as_global(w.wt) + (size_t)col * w.Kp + 16 * h;
+    const int8_t *xrow = pl + arow * KP + 16 * h;
+    const int32_t cs128 = as_global(w.cs128)[col];
+    v16i total;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) total[i] = 0;
+#pragma unroll
+    for (int pp = NPL - 2; pp >= 0; pp -= 2) {
+        v16i a0, a1;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) a0[i] = a1[i] = 0;
+        for (int ks = 0; ks < nks; ++ks) {
+            const v4i b = *reinterpret_cast<const v4i *>(wrow + 32 * ks);
+            const v4i x1 = *reinterpret_cast<const v4i *>(xrow + (pp + 1) * pstride + 32 * ks);
+            const v4i x0 = *reinterpret_cast<const v4i *>(xrow + pp * pstride + 32 * ks);
+            a1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(x1, b, a1, 0, 0, 0);
+            a0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(x0, b, a0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) total[i] = wadd(wadd(wshl(total[i], 16), wshl(a1[i], 8)), a0[i]);
+    }
+    // the +128 offsets of the lower planes: 128 * sum(w) once per lower plane at that plane's weight
+    const int32_t cs = wmul(cs128, NPL == 2 ? 1 : 65793);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) total[i] = wadd(total[i], cs);
+    return total;
+}
+
+// maxima of NV non-negative floats over the workgroup; every thread receives them
+template <int NV, int STEP_WAVES>
+__device__ __forceinline__ void step_wg_max(float (&v)[NV], float (*red)[STEP_MAX_WAVES])
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        float x = v[i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
+        if (lane == 0) red[i][wave] = x;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        float x = red[i][0];
+#pragma unroll
+        for (int w = 1; w < STEP_WAVES; ++w) x = fmaxf(x, red[i][w]);
+        v[i] = x;
+    }
+    __syncthreads();
+}
+
+// STEP_THREADS: 512 when the groups are at most one per CU (eight waves shorten one group's chain of stages); 256 or 128
+// when there are more groups than CUs and several fit a CU (the kernel needs up to 256 registers per lane, so a CU holds
+// eight waves of it: one, two or four workgroups)
+template <int STEP_THREADS>
+__global__ __launch_bounds__(STEP_THREADS, 2) void k_model_step(StepArgs a)
+{
+    constexpr int STEP_WAVES = STEP_THREADS / 64;
+    extern __shared__ __attribute__((aligned(16))) int8_t step_smem[];
+    __shared__ int32_t s_status[128]; // S5FXP_STATUS_WORDS: built here, stored once at the end
+    __shared__ float s_red[3][STEP_MAX_WAVES];
+    // the layer's per-channel and per-state operands, fetched together at the head of the layer
+    __shared__ LayerDyn s_d;
+    __shared__ int32_t s_lut[8];
+    __shared__ int32_t s_wide;
+
+    const StepParams &sp = *a.sp;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    const int64_t g = blockIdx.x;
+    const int B = a.B, L = a.L, R = B * L, H = sp.H, P = sp.P, HP = sp.hp, nl = sp.n_layers;
+    const int arow = r < R ? r : R - 1; // padding rows of the MFMA tile re-read the last real row
+    const StepLds lds = step_lds(R, H, P, HP, sp.d_in);
+    int8_t *pla = step_smem + lds.pla, *plb = step_smem + lds.plb;
+    int16_t *hb = reinterpret_cast<int16_t *>(step_smem + lds.hb), *x1b = reinterpret_cast<int16_t *>(step_smem + lds.x1),
+            *zb = reinterpret_cast<int16_t *>(step_smem + lds.z);
+    int32_t *bq = reinterpret_cast<int32_t *>(step_smem + lds.bq); // [re | im][row][state]
+    const int KPB = lds.kpb, psb = R * KPB;
+
+    for (int i = tid; i < 128; i += STEP_THREADS) {
+        int32_t v = 0;
+        if (i == 1) v = sp.dec.out_exp;
+        else if (i == 2) v = 3; // S5FXP_PATH_STEP
+        else if (i >= 8 && (i - 8) / 8 < nl) v = (i & 7) == 5 ? 6 : ((i & 7) >= 6 ? P : 0);
+        s_status[i] = v;
+    }
+    __syncthreads();
+
+    // ---- input rows -> byte planes (float rows: fxp_from_fp FLOOR first), with the encoder's input conversion
+    // (fxpmodel.py:335-347) and the 16-bit check of the fused encoder (proj_p.hpp k_enc_p)
+    {
+        const StepDense &e = sp.enc;
+        const int K = e.K, KPA = lds.kpa_enc, psa = R * KPA;
+        const bool conv = a.x_bits > e.inp_bits || a.x_exp > e.inp_exp;
+        const float sc = ldexpf(1.f, a.x_exp);
+        const int32_t *xg = as_global(reinterpret_cast<const int32_t *>(a.x)) + g * R * K;
+        bool wide = false;
+        for (int i = tid; i < R * K; i += STEP_THREADS) {
+            const int row = i / K, k = i - row * K;
+            int32_t v = xg[i];
+            if (a.f32) v = fromfp(__int_as_float(v), sc, a.x_bits);
+            if (conv) v = chcfg(v, a.x_bits, a.x_exp, e.inp_bits, e.inp_exp);
+            wide |= v != (int32_t)(int16_t)v;
+            step_put2(pla, psa, row * KPA + k, v);
+        }
+        if (__any(wide) && lane == 0) atomicOr(&s_status[0], ST_WIDE_INPUT);
+        __syncthreads();
+        // ---- encoder + bias + ReLU (fxpmodel.py:331-366, 1263-1266)
+        const int rs = (conv ? e.inp_exp : a.x_exp) + e.w_exp - e.out_exp; // checked by the host
+        const int nks = (K + 31) / 32;
+        for (int tile = wave; tile < HP / 32; tile += STEP_WAVES) {
+            const int col = 32 * tile + r;
+            const v16i acc = step_mm<2>(pla, psa, KPA, arow, h, e.w, col, nks);
+            const int32_t be = as_global(e.bias_eff)[col];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+                if (row < R && col < H) { // (a wave whose lanes all hold padding rows skips the element)
+                    int32_t v = sat(asr(acc[i], rs), e.out_bits);
+                    v = sat(wadd(v, be), e.out_bits);
+                    hb[row * H + col] = (int16_t)(v < 0 ? 0 : v);
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    int hbits = sp.enc.out_bits, he = sp.enc.out_exp; // the layer input's configuration (he: chosen on the device from layer 1 on)
+    for (int li = 0; li < nl; ++li) {
+        const StepLayer &sl = sp.layers[li];
+        BnArgs bn = sl.bn;
+        bn.xe.stat = he; bn.xe.dyn = nullptr; bn.dyn = nullptr;
+        int32_t *st_exps = s_status + 8 + 8 * li;
+        if (tid < 8) s_lut[tid] = sl.lut[tid];
+        if (tid == 0) s_wide = 0;
+
+        // ---- the four BatchNorm compute_best exponents (fxpmodel.py:892-933): full reductions over the R x H values,
+        // the rule of k_bn_reduce / k_bn_finalize
+        {
+            float v[3] = {0.f, 0.f, 0.f};
+            for (int i = tid; i < R * H; i += STEP_THREADS) {
+                const int c = i % H;
+                const float fx = tofloat(hb[i], he), fm = tofloat(bn.mm[c], bn.me);
+                v[0] = fmaxf(v[0], fabsf(__fadd_rn(fx, fm)));
+                v[1] = fmaxf(v[1], fabsf(fx));
+                v[2] = fmaxf(v[2], fabsf(fm));
+            }
+            step_wg_max<3, STEP_WAVES>(v, s_red);
+            if (tid == 0) {
+                const uint32_t m3[3] = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2])};
+                s_d.bn1 = finalize_add_cb(m3, he, bn.me, bn.b1, s_status);
+                st_exps[0] = s_d.bn1.eo;
+                s_d.bn_e = s_d.bn1.eo;
+            }
+            __syncthreads();
+        }
+        {
+            LayerDyn d = s_d;
+            float v[1] = {0.f};
+            for (int i = tid; i < R * H; i += STEP_THREADS) {
+                const int c = i % H;
+                const int32_t t = bn_chain<1>(bn, d, hb[i], c);
+                v[0] = fmaxf(v[0], fabsf(__fmul_rn(tofloat(t, d.bn1.eo), tofloat(bn.isv[c], bn.ie))));
+            }
+            step_wg_max<1, STEP_WAVES>(v, s_red);
+            if (tid == 0) {
+                finalize_mul_cb(__float_as_uint(v[0]), s_d.bn1.eo, bn.ie, bn.b2, s_d.rs2, s_d.e2, s_status);
+                st_exps[1] = s_d.e2;
+                s_d.bn_e = s_d.e2;
+            }
+            __syncthreads();
+        }
+        if (bn.scale) {
+            LayerDyn d = s_d;
+            float v[1] = {0.f};
+            for (int i = tid; i < R * H; i += STEP_THREADS) {
+                const int c = i % H;
+                const int32_t t = bn_chain<2>(bn, d, hb[i], c);
+                v[0] = fmaxf(v[0], fabsf(__fmul_rn(tofloat(t, d.e2), tofloat(bn.scale[c], bn.se))));
+            }
+            step_wg_max<1, STEP_WAVES>(v, s_red);
+            if (tid == 0) {
+                finalize_mul_cb(__float_as_uint(v[0]), s_d.e2, bn.se, bn.b3, s_d.rs3, s_d.e3, s_status);
+                st_exps[2] = s_d.e3;
+                s_d.bn_e = s_d.e3;
+            }
+            __syncthreads();
+        }
+        if (bn.bias) {
+            LayerDyn d = s_d;
+            float v[3] = {0.f, 0.f, 0.f};
+            for (int i = tid; i < R * H; i += STEP_THREADS) {
+                const int c = i % H;
+                const int32_t t = bn_chain<3>(bn, d, hb[i], c);
+                const float ft = tofloat(t, bn.scale ? d.e3 : d.e2), fb = tofloat(bn.bias[c], bn.be);
+                v[0] = fmaxf(v[0], fabsf(__fadd_rn(ft, fb)));
+                v[1] = fmaxf(v[1], fabsf(ft));
+                v[2] = fmaxf(v[2], fabsf(fb));
+            }
+            step_wg_max<3, STEP_WAVES>(v, s_red);
+            if (tid == 0) {
+                const uint32_t m3[3] = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2])};
+                s_d.bn4 = finalize_add_cb(m3, bn.scale ? s_d.e3 : s_d.e2, bn.be, bn.b4, s_status);
+                st_exps[3] = s_d.bn4.eo;
+                s_d.bn_e = s_d.bn4.eo;
+            }
+            __syncthreads();
+        }
+        const LayerDyn d = s_d;
+
+        // ---- u = change_cfg(BatchNorm(x)) -> byte planes (fxpmodel.py:620-624)
+        for (int i = tid; i < R * H; i += STEP_THREADS) {
+            const int row = i / H, c = i - row * H;
+            step_put2(plb, psb, row * KPB + c, bn_chain<5>(bn, d, hb[i], c));
+        }
+        __syncthreads();
+
+        // ---- B projection, Bu saturate and the shift to the state exponent (fxpmodel.py:626-644, 158-167)
+        for (int tile = wave; tile < 2 * P / 32; tile += STEP_WAVES) {
+            const int col = 32 * tile + r, c = col >= P ? 1 : 0, p = col - c * P;
+            const v16i acc = step_mm<2>(plb, psb, KPB, arow, h, sl.bproj, col, HP / 32);
+            const int rs = c ? sl.rs_bim : sl.rs_bre, bits = c ? sl.bim_bits : sl.bre_bits, sh = c ? sl.sh_im : sl.sh_re;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+                if (row < R) {
+                    const int32_t bu = sat(asr(acc[i], rs), bits);
+                    bq[(c * R + row) * P + p] = sh > 0 ? asr(bu, sh) : wshl(bu, -sh);
+                }
+            }
+        }
+        __syncthreads();
+
+        // ---- the recurrence from the carry, 32-bit wrap arithmetic (fxpmodel.py:147-172); carry out; complex ReLU
+        // (fxpmodel.py:740-742).  A thread owns one (sequence, state): it reads its carry before it writes it, so
+        // state_out may be state_in.  The states replace Bu in place.
+        {
+            const size_t plane = (size_t)B * P;
+            const size_t cbase = ((size_t)g * nl + li) * 2 * plane;
+            bool wide = false;
+            for (int i = tid; i < B * P; i += STEP_THREADS) {
+                const int b = i / P, p = i - b * P;
+                const int32_t Ar = as_global(sl.a_re)[p], Ai = as_global(sl.a_im)[p];
+                int32_t xr = a.state_in ? as_global(a.state_in)[cbase + i] : 0;
+                int32_t xi = a.state_in ? as_global(a.state_in)[cbase + plane + i] : 0;
+                for (int t = 0; t < L; ++t) {
+                    const int o = (b * L + t) * P + p;
+                    scan_step(Ar, Ai, sl.ea_re, sl.ea_im, bq[o], bq[R * P + o], xr, xi);
+                    int32_t sr = xr, si = xi;
+                    crelu(sr, si);
+                    wide |= sr != (int32_t)(int16_t)sr || si != (int32_t)(int16_t)si;
+                    bq[o] = sr;
+                    bq[R * P + o] = si;
+                }
+                if (a.state_out) {
+                    as_global(a.state_out)[cbase + i] = xr;
+                    as_global(a.state_out)[cbase + plane + i] = xi;
+                }
+            }
+            if (__any(wide) && lane == 0) atomicOr(&s_wide, 1);
+        }
+        __syncthreads();
+        const bool wide_states = s_wide != 0; // workgroup-uniform
+        const int KPS = lds.kpa_st, pss = R * KPS, npl = wide_states ? 4 : 2;
+        for (int i = tid; i < 2 * R * P; i += STEP_THREADS) {
+            const int c = i / (R * P), rem = i - c * R * P, row = rem / P, p = rem - row * P;
+            int8_t *base = pla + c * npl * pss;
+            if (wide_states) step_put4(base, pss, row * KPS + p, bq[i]);
+            else step_put2(base, pss, row * KPS + p, bq[i]);
+        }
+        if (wide_states && tid == 0) atomicOr(&s_status[0], ST_WIDE_STATE);
+        __syncthreads();
+
+        // ---- C projection + D u + ReLU (fxpmodel.py:746-793, 1125) -> x1 and out2's input planes
+        for (int tile = wave; tile < HP / 32; tile += STEP_WAVES) {
+            const int col = 32 * tile + r;
+            v16i are, aim;
+            if (wide_states) {
+                are = step_mm<4>(pla, pss, KPS, arow, h, sl.cre, col, P / 32);
+                aim = step_mm<4>(pla + 4 * pss, pss, KPS, arow, h, sl.cim, col, P / 32);
+            } else {
+                are = step_mm<2>(pla, pss, KPS, arow, h, sl.cre, col, P / 32);
+                aim = step_mm<2>(pla + 2 * pss, pss, KPS, arow, h, sl.cim, col, P / 32);
+            }
+            const int32_t Dv = as_global(sl.Dpad)[col];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+                if (row < R && col < H) {
+                    const int32_t cr = sat(asr(are[i], sl.rs_cre), sl.y_bits);
+                    const int32_t ci = sat(asr(aim[i], sl.rs_cim), sl.y_bits);
+                    const int32_t cx = sat(wadd(cr, wmul(ci, -1)), sl.y_bits);
+                    const int32_t cx2 = wmul(cx, 2); // not clipped, fxpmodel.py:765-767
+                    const int32_t u = bn_chain<5>(bn, d, hb[row * H + col], col);
+                    const int32_t du = sat(asr(wmul(Dv, u), sl.rs_d), sl.y_bits);
+                    const int32_t yv = sat(wadd(cx2, du), sl.y_bits);
+                    const int32_t x1 = yv < 0 ? 0 : yv;
+                    x1b[row * H + col] = (int16_t)x1;
+                    step_put2(plb, psb, row * KPB + col,
+                              sl.o2_conv ? chcfg(x1, sl.y_bits, sl.y_exp, sl.o2_inp_bits, sl.o2_inp_exp) : x1);
+                }
+            }
+        }
+        __syncthreads();
+
+        // ---- out2 + LUT sigmoid + gate (fxpmodel.py:1133-1137, 97-144, 1075-1093) + the residual add's maxima
+        {
+            float v[3] = {0.f, 0.f, 0.f};
+            for (int tile = wave; tile < HP / 32; tile += STEP_WAVES) {
+                const int col = 32 * tile + r;
+                const v16i acc = step_mm<2>(plb, psb, KPB, arow, h, sl.out2, col, HP / 32);
+                const int32_t be = as_global(sl.o2_bias_eff)[col];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+                    if (row < R && col < H) {
+                        int32_t gq = sat(asr(acc[i], sl.rs_o2), sl.o2_out_bits);
+                        gq = sat(wadd(gq, be), sl.o2_out_bits);
+                        const int32_t s = sigmoid_lut(gq, sl.o2_out_bits, sl.o2_out_exp, sl.sig_x, sl.sig_y, s_lut);
+                        const int32_t lv = chcfg(x1b[row * H + col], sl.y_bits, sl.y_exp, sl.l_bits, sl.l_exp);
+                        const int32_t rv = chcfg(s, sl.o2_out_bits, sl.sig_y, sl.r_bits, sl.r_exp);
+                        const int32_t z = sat(asr(wmul(lv, rv), sl.rs_gate), sl.res_bits);
+                        zb[row * H + col] = (int16_t)z;
+                        const float fz = tofloat(z, sl.res_exp), fs = tofloat(hb[row * H + col], he);
+                        v[0] = fmaxf(v[0], fabsf(__fadd_rn(fz, fs)));
+                        v[1] = fmaxf(v[1], fabsf(fz));
+                        v[2] = fmaxf(v[2], fabsf(fs));
+                    }
+                }
+            }
+            step_wg_max<3, STEP_WAVES>(v, s_red);
+            if (tid == 0) {
+                const uint32_t m3[3] = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2])};
+                s_d.res = finalize_add_cb(m3, sl.res_exp, he, sl.res_bits, s_status);
+                st_exps[4] = s_d.res.eo;
+            }
+            __syncthreads();
+        }
+        // ---- residual compute_best add + ReLU (fxpmodel.py:1147-1159): the next layer's input, in place
+        {
+            const AddCb rp = s_d.res;
+            for (int i = tid; i < R * H; i += STEP_THREADS) {
+                const int32_t rr = add_cb_apply(zb[i], sl.res_bits, hb[i], hbits, rp, sl.res_bits);
+                hb[i] = (int16_t)(rr < 0 ? 0 : rr);
+            }
+            hbits = sl.res_bits;
+            he = rp.eo;
+        }
+        __syncthreads();
+    }
+
+    // ---- decoder (fxpmodel.py:1437, 331-366): its input exponent is the last residual's
+    {
+        const StepDense &e = sp.dec;
+        const bool conv = hbits > e.inp_bits || he > e.inp_exp;
+        int rs = (conv ? e.inp_exp : he) + e.w_exp - e.out_exp;
+        if (rs < 0 || rs > 31) {
+            if (tid == 0) atomicOr(&s_status[0], ST_NEGSHIFT);
+            rs = rs < 0 ? 0 : 31;
+        }
+        for (int i = tid; i < R * H; i += STEP_THREADS) {
+            const int row = i / H, c = i - row * H;
+            const int32_t v = hb[i];
+            step_put2(plb, psb, row * KPB + c, conv ? chcfg(v, hbits, he, e.inp_bits, e.inp_exp) : v);
+        }
+        __syncthreads();
+        const int M = e.M;
+        int32_t *yg = as_global(reinterpret_cast<int32_t *>(a.y)) + g * R * M;
+        for (int tile = wave; tile < (M + 31) / 32; tile += STEP_WAVES) {
+            const int col = 32 * tile + r;
+            const v16i acc = step_mm<2>(plb, psb, KPB, arow, h, e.w, col, HP / 32);
+            const int32_t be = as_global(e.bias_eff)[col];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+                if (row < R && col < M) {
+                    int32_t v = sat(asr(acc[i], rs), e.out_bits);
+                    v = sat(wadd(v, be), e.out_bits);
+                    yg[row * M + col] = a.f32 ? __float_as_int(tofloat(v, e.out_exp)) : v;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    int32_t *stg = as_global(a.status) + g * 128;
+    for (int i = tid; i < 128; i += STEP_THREADS) stg[i] = s_status[i];
+}
+
+} // namespace s5
+
+namespace {
+
+// The step's parameter block for a model on the fused path, with the device addresses pack_all handed out.
+void fill_step_params(const s5fxp_model *m, StepParams &sp)
+{
+    std::memset(&sp, 0, sizeof(sp));
+    const FastModel &F = *m->fast;
+    sp.n_layers = m->n_layers; sp.H = m->H; sp.P = m->P; sp.hp = fast_shape(m->H, m->P).hp; sp.d_in = m->d_in; sp.d_out = m->d_out;
+    auto dense = [](const DenseDev &e, const MfmaWDev &w) {
+        StepDense o{};
+        o.w = w.w; o.bias_eff = w.bias_eff; o.K = e.K; o.M = e.M; o.inp_bits = e.inp_bits; o.inp_exp = e.inp_exp; o.w_exp = e.w_exp;
+        o.out_bits = e.out_bits; o.out_exp = e.out_exp;
+        return o;
+    };
+    sp.enc = dense(m->enc, F.enc);
+    sp.dec = dense(m->dec, F.dec);
+    int hb = m->enc.out_bits;
+    for (int li = 0; li < m->n_layers; ++li) {
+        const LayerDev &l = m->layers[li];
+        const FastLayer &fl = F.layers[li];
+        const s5fxp_ssm_desc &s = l.sd;
+        const DenseDev &o = l.out2;
+        StepLayer &q = sp.layers[li];
+        q.bn = make_bn(l, hb, DynExp{0, nullptr}, nullptr);
+        q.bproj = fl.bproj.w; q.cre = fl.cre.w; q.cim = fl.cim.w; q.out2 = fl.out2.w;
+        q.o2_bias_eff = fl.out2.bias_eff; q.Dpad = fl.Dpad; q.a_re = l.a_re; q.a_im = l.a_im;
+        q.rs_bre = s.u_exp + s.B_re_exp - s.Bu_re_exp; q.rs_bim = s.u_exp + s.B_im_exp - s.Bu_im_exp;
+        q.bre_bits = s.Bu_re_bits; q.bim_bits = s.Bu_im_bits; q.sh_re = s.Bu_re_exp - s.x_re_exp; q.sh_im = s.Bu_im_exp - s.x_im_exp;
+        q.ea_re = s.A_re_exp; q.ea_im = s.A_im_exp;
+        q.rs_cre = s.x_re_exp + s.C_re_exp - s.y_exp; q.rs_cim = s.x_im_exp + s.C_im_exp - s.y_exp;
+        q.rs_d = s.D_exp + s.u_exp - s.y_exp; q.y_bits = s.y_bits; q.y_exp = s.y_exp;
+        q.o2_conv = (s.y_bits > o.inp_bits || s.y_exp > o.inp_exp) ? 1 : 0; q.o2_inp_bits = o.inp_bits; q.o2_inp_exp = o.inp_exp;
+        q.rs_o2 = (q.o2_conv ? o.inp_exp : s.y_exp) + o.w_exp - o.out_exp; // checked per call (step_entry)
+        q.o2_out_bits = o.out_bits; q.o2_out_exp = o.out_exp; q.sig_x = l.sig_x; q.sig_y = l.sig_y;
+        std::memcpy(q.lut, l.lut, sizeof(q.lut));
+        q.l_bits = l.l_bits; q.l_exp = l.l_exp; q.r_bits = l.r_bits; q.r_exp = l.r_exp; q.res_bits = l.res_bits; q.res_exp = l.res_exp;
+        q.rs_gate = l.l_exp + l.r_exp - l.res_exp;
+        hb = l.res_bits;
+    }
+}
+
+int step_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int G, int B, int L, void *y, const int32_t *state_in,
+               int32_t *state_out, int32_t *status, void *stream, bool f32)
+{
+    if (!m || !x || !y || !status || G < 1 || B < 1 || L < 1 || (int64_t)B * L > STEP_MAX_ROWS || x_bits < 1 || x_bits > 32)
+        return S5FXP_EBADARG;
+    if (f32 && (x_exp < 0 || x_exp > 31)) return S5FXP_EBADARG;
+    if (!m->fast || !m->fast->step) return S5FXP_EUNSUPPORTED;
+    if (f32 && (m->dec.out_exp < 0 || m->dec.out_exp > 31)) return S5FXP_EUNSUPPORTED; // the range s5fxp_to_float takes
+    // the static shifts a batch forward checks while it enqueues (encoder, out2)
+    const DenseDev &e = m->enc;
+    const bool conv = x_bits > e.inp_bits || x_exp > e.inp_exp;
+    if (!shift_ok((conv ? e.inp_exp : x_exp) + e.w_exp - e.out_exp)) return S5FXP_ENEGSHIFT;
+    for (int li = 0; li < m->n_layers; ++li) {
+        const s5fxp_ssm_desc &s = m->layers[li].sd;
+        const DenseDev &o = m->layers[li].out2;
+        const bool c2 = s.y_bits > o.inp_bits || s.y_exp > o.inp_exp;
+        if (!shift_ok((c2 ? o.inp_exp : s.y_exp) + o.w_exp - o.out_exp)) return S5FXP_ENEGSHIFT;
+    }
+    const size_t smem = step_lds(B * L, m->H, m->P, fast_shape(m->H, m->P).hp, m->d_in).total;
+    StepArgs a{};
+    a.sp = m->fast->step; a.x = x; a.y = y; a.state_in = state_in; a.state_out = state_out; a.status = status;
+    a.B = B; a.L = L; a.x_bits = x_bits; a.x_exp = x_exp; a.f32 = f32 ? 1 : 0;
+    auto launch = [&](auto kernel, unsigned threads) {
+        if (smem > 65536)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)G), dim3(threads), smem, S(stream), a);
+    };
+    // workgroups of one CU: eight waves by registers, 160 KB of LDS
+    const size_t fit = (160 * 1024) / (smem + STEP_STATIC_LDS);
+    if (G <= STEP_CUS || fit < 2) launch(k_model_step<512>, 512);
+    else if (G <= 2 * STEP_CUS || fit < 4) launch(k_model_step<256>, 256);
+    else launch(k_model_step<128>, 128);
+    return launch_rc();
+}
+
+} // namespace
+
+extern "C" int s5fxp_model_step_ok(const s5fxp_model *m, int B, int L)
+{
+    if (!m || B < 1 || L < 1) return -1;
+    return m->fast && m->fast->step && (int64_t)B * L <= STEP_MAX_ROWS ? 1 : 0;
+}
+
+extern "C" int s5fxp_model_step(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int G, int B, int L, int32_t *y,
+                                const int32_t *state_in, int32_t *state_out, int32_t *status, void *stream)
+{
+    return step_entry(m, x, x_bits, x_exp, G, B, L, y, state_in, state_out, status, stream, false);
+}
+
+extern "C" int s5fxp_model_step_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int G, int B, int L, float *y,
+                                    const int32_t *state_in, int32_t *state_out, int32_t *status, void *stream)
+{
+    return step_entry(m, x, x_bits, x_exp, G, B, L, y, state_in, state_out, status, stream, true);
+}

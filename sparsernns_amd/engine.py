@@ -28,6 +28,7 @@ class Engine:
             raise RuntimeError("sparsernns_amd.Engine needs a ROCm GPU (no CPU fallback)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         self._keep: list = []
+        self._export, self._flags, self._generic = export, flags, None
         P, Q = export["params"], export["qconfig"]
         self.n_layers = len([k for k in P["encoder"] if k.startswith("layers_")])
         self._layers = (LayerDesc * max(self.n_layers, 1))()
@@ -416,6 +417,61 @@ class Engine:
     def stream(self, B: int = 1) -> "StreamingSession":
         return StreamingSession(self, B)
 
+    # -- one-launch streaming step -------------------------------------------------------------
+    def step_ok(self, B: int, L: int) -> bool:
+        """True when ``step`` serves this model at (B, L): a model on the fused path and B * L <= 32 rows per group."""
+        return lib.s5fxp_model_step_ok(self._h, int(B), int(L)) == 1
+
+    def step(self, x, state: Optional[torch.Tensor], y: Optional[torch.Tensor] = None, B: int = 1, L: int = 1, groups: int = 1,
+             x_bits: Optional[int] = None, x_exp: Optional[int] = None, state_out: Optional[torch.Tensor] = None,
+             lane=0) -> torch.Tensor:
+        """One short chunk of `groups` independent streams as ONE kernel launch (``s5fxp_model_step``): enqueue only --
+        nothing is synchronised, and nothing is allocated when `y` is given.
+
+        x: (groups, B, L, d_in) int32 (or an FxpArray of that shape) or float32 (``s5fxp_model_step_f32``; x_bits / x_exp
+        default to the encoder's input configuration); y: (groups, B, L, d_out) of the same dtype.  state: the carry
+        (groups, n_layers, 2, B, P) int32, read and -- unless `state_out` names another tensor -- replaced in place; None
+        starts from zeros and keeps no carry.  Every group is its own compute_best batch, exactly ``enqueue(...,
+        groups=groups)``.  The status words (``lane_status(lane, groups)``, ``check_status(lane)``) are the caller's to
+        read: ST_WIDE_INPUT means the results are invalid (serve the chunk through ``enqueue`` on a generic engine)."""
+        if isinstance(x, FxpArray):
+            x_bits, x_exp, x = x.bits, x.exp, x.data
+        f32 = x.dtype == torch.float32
+        if not f32 and x.dtype != torch.int32:
+            raise ValueError(f"x must be int32 or float32, got {x.dtype}")
+        want_x = (groups, B, L, self.d_in)
+        if x.numel() != groups * B * L * self.d_in or not x.is_contiguous() or not x.is_cuda:
+            raise ValueError(f"x must be a contiguous device tensor of shape {want_x}, got {tuple(x.shape)}")
+        xb = (self.inp_bits if f32 else 32) if x_bits is None else int(x_bits)
+        xe = self.inp_exp if x_exp is None else int(x_exp)
+        if y is None:
+            y = torch.empty((groups, B, L, self.d_out), dtype=x.dtype, device=x.device)
+        elif y.dtype != x.dtype or y.numel() != groups * B * L * self.d_out or not y.is_contiguous():
+            raise ValueError(f"y must be a contiguous {x.dtype} tensor of {groups * B * L * self.d_out} elements")
+        want = (groups, self.n_layers, 2, B, self.P)
+        for name, t in (("state", state), ("state_out", state_out)):
+            if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != want or not t.is_contiguous() or not t.is_cuda):
+                raise ValueError(f"{name} must be a contiguous int32 device tensor of shape {want}")
+        so = state_out if state_out is not None else state
+        self._groups[lane] = groups
+        entry, name = (lib.s5fxp_model_step_f32, "s5fxp_model_step_f32") if f32 else (lib.s5fxp_model_step, "s5fxp_model_step")
+        check(entry(self._h, x.data_ptr(), xb, xe, groups, B, L, y.data_ptr(), state.data_ptr() if state is not None else None,
+                    so.data_ptr() if so is not None else None, self.lane_status(lane, groups).data_ptr(),
+                    torch.cuda.current_stream().cuda_stream), name)
+        return y
+
+    def generic_twin(self) -> "Engine":
+        """The same model on the generic int32 kernels (MODEL_FORCE_GENERIC), built on first use: what serves inputs the
+        fused kernels refuse (ST_WIDE_INPUT)."""
+        if self._flags & _lib.MODEL_FORCE_GENERIC:
+            return self
+        if self._generic is None:
+            self._generic = Engine(self._export, self._flags | _lib.MODEL_FORCE_GENERIC, self.device)
+        return self._generic
+
+    def pool(self, sessions: int, B: int = 1) -> "SessionPool":
+        return SessionPool(self, sessions, B)
+
 
 class StreamingSession:
     """Frame-chunk-at-a-time inference with the SSM states carried between calls (the paper's
@@ -435,6 +491,131 @@ class StreamingSession:
     def reset(self) -> None:
         self.state = self.engine.zero_state(self.B)
         self.frames = 0
+
+
+class SessionPool:
+    """`sessions` independent streams of B sequences each, served together: one group per session, every chunk of all
+    sessions in ONE kernel launch (``Engine.step``) where the model and the chunk allow it -- a model on the fused path and
+    B * L <= 32 rows per session -- and through the grouped batch path (``Engine.enqueue(..., groups=sessions)``) or the
+    generic engine otherwise, so every model and chunk length is served.  The pool owns the carry (updated by every push)
+    and reusable output buffers: what ``push`` returns is valid until the next push of the same chunk shape.
+
+    Each session's chunk is its own compute_best batch: session s of a pool computes what a ``StreamingSession`` fed the
+    same chunks computes."""
+
+    def __init__(self, engine: "Engine", sessions: int, B: int = 1):
+        if sessions < 1 or B < 1:
+            raise ValueError("sessions and B must be >= 1")
+        self.engine, self.sessions, self.B = engine, int(sessions), int(B)
+        shape = (self.sessions, engine.n_layers, 2, self.B, engine.P)
+        self._state = torch.zeros(shape, dtype=torch.int32, device=engine.device)
+        self._next = torch.zeros(shape, dtype=torch.int32, device=engine.device)
+        self.frames = np.zeros(self.sessions, dtype=np.int64)
+        self.last_path: Optional[int] = None
+        self._lane = ("pool", id(self))
+        self._y: Dict[tuple, torch.Tensor] = {}
+        self._err = torch.zeros(self.sessions, dtype=torch.int32, device=engine.device)  # error bits of unchecked pushes
+        self._unchecked = False
+
+    @property
+    def state(self) -> torch.Tensor:
+        """The carry, (sessions, n_layers, 2, B, P) int32."""
+        return self._state
+
+    def reset(self, ids=None) -> None:
+        """Zeroes the carry (and the frame count) of the sessions in `ids`; None: all of them."""
+        if ids is None:
+            self._state.zero_()
+            self.frames[:] = 0
+        else:
+            idx = torch.as_tensor(list(ids), dtype=torch.long, device=self._state.device)
+            self._state.index_fill_(0, idx, 0)
+            self.frames[list(ids)] = 0
+
+    def _raise(self, bits: int) -> None:
+        if bits & _lib.ST_NEGSHIFT:
+            raise ValueError("invalid result_exp: a data-dependent shift came out negative (fxparray.py:619-621)")
+        if bits & _lib.ST_NEGEXP:
+            raise ValueError("a compute_best exponent came out negative")
+        if bits & _lib.ST_WIDE_INPUT:
+            raise OverflowError("an unchecked push held input values beyond 16 bits: its outputs and the carry are invalid; "
+                                "reset the sessions and push with check=True")
+
+    def check(self) -> None:
+        """Synchronises and raises what an unchecked push since the last check would have raised."""
+        if self._unchecked:
+            bits = int(np.bitwise_or.reduce(self._err.cpu().numpy()))
+            self._err.zero_()
+            self._unchecked = False
+            self._raise(bits)
+
+    def _batch(self, eng: "Engine", x, xb, xe, y, L, check: bool) -> None:
+        S = self.sessions
+        sin, sout = (self._state, self._next) if S > 1 else (self._state[0], self._next[0])
+        launch = lambda fl: eng.enqueue(x, xb, xe, y, self.B, L, flags=fl, lane=self._lane, state_in=sin, state_out=sout, groups=S)
+        if check:
+            eng.run_ladder(launch, lambda: eng.check_status(self._lane))
+            self.last_path = int(eng.lane_status(self._lane, S)[2].item())
+        else:
+            launch(0)  # self-contained: the gated exact re-run is part of the one enqueue
+            self._err |= eng.lane_status(self._lane, S)[:S * _lib.STATUS_WORDS].view(S, _lib.STATUS_WORDS)[:, 0]
+            self._unchecked = True
+            self.last_path = _lib.PATH_FUSED if lib.s5fxp_model_is_fast(eng._h) else _lib.PATH_GENERIC
+        self._state, self._next = self._next, self._state
+
+    def push(self, x, check: bool = True):
+        """x: (sessions, L, d_in) (B == 1) or (sessions, B, L, d_in), an FxpArray or a float32 tensor.  Returns the outputs
+        of exactly those frames, an FxpArray or a float32 tensor of the same leading shape.  check=False enqueues only:
+        nothing is synchronised, the status words are folded into the pool on the device and raised by the next checked
+        push or ``check()``."""
+        eng = self.engine
+        fxp = isinstance(x, FxpArray)
+        if fxp:
+            data, xb, xe = x.data, x.bits, x.exp
+            if data.dtype != torch.int32:
+                raise ValueError(f"expected int32 FxpArray data, got {data.dtype}")
+        else:
+            data = torch.as_tensor(x)
+            if data.dtype != torch.float32:
+                raise ValueError(f"expected an FxpArray or a float32 tensor, got {data.dtype}")
+            xb, xe = eng.inp_bits, eng.inp_exp
+        data = data.to(eng.device).contiguous()
+        S, B = self.sessions, self.B
+        if data.ndim == 3 and B == 1:
+            L = data.shape[1]
+        elif data.ndim == 4 and data.shape[1] == B:
+            L = data.shape[2]
+        else:
+            raise ValueError(f"expected ({S}, L, {eng.d_in})" + (f" or ({S}, {B}, L, {eng.d_in})"), f"got {tuple(data.shape)}")
+        if data.shape[0] != S or data.shape[-1] != eng.d_in or L < 1:
+            raise ValueError(f"expected {S} sessions of {eng.d_in} inputs and at least one frame, got {tuple(data.shape)}")
+        if check:
+            self.check()
+        key = (tuple(data.shape[:-1]), data.dtype)
+        y = self._y.get(key)
+        if y is None:
+            y = self._y[key] = torch.empty(key[0] + (eng.d_out,), dtype=data.dtype, device=eng.device)
+        if eng.step_ok(B, L):
+            if check:
+                eng.step(data, self._state, y, B, L, S, xb, xe, state_out=self._next, lane=self._lane)
+                st = eng.lane_status(self._lane, S).cpu().numpy()[:S * _lib.STATUS_WORDS].reshape(S, _lib.STATUS_WORDS)
+                bits = int(np.bitwise_or.reduce(st[:, 0]))
+                if bits & _lib.ST_WIDE_INPUT:
+                    # the fused kernels take 16-bit inputs: this chunk goes through the generic engine, from the same carry
+                    self._batch(eng.generic_twin(), data, xb, xe, y, L, True)
+                else:
+                    self._raise(bits)
+                    self._state, self._next = self._next, self._state
+                    self.last_path = int(st[0, 2])
+            else:
+                eng.step(data, self._state, y, B, L, S, xb, xe, lane=self._lane)
+                self._err |= eng.lane_status(self._lane, S)[:S * _lib.STATUS_WORDS].view(S, _lib.STATUS_WORDS)[:, 0]
+                self._unchecked = True
+                self.last_path = _lib.PATH_STEP
+        else:
+            self._batch(eng, data, xb, xe, y, L, check)
+        self.frames += L
+        return FxpArray(y, eng.out_bits, eng.out_exp, True) if fxp else y
 
 
 class InflightRunner:
