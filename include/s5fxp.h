@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define S5FXP_VERSION 106
+#define S5FXP_VERSION 107
 
 enum {
     S5FXP_OK = 0,
@@ -117,6 +117,27 @@ int s5fxp_scan(const int32_t *bu_re, const int32_t *bu_im, const int32_t *a_re, 
  * reverse != 0 scans from t = L-1 down to 0. */
 int s5fxp_assoc_scan_c64(const float *lambda, const float *bu, float *xs, const float *x0, float *x_last, int B, int L,
                          int P, int reverse, void *stream);
+
+/* The audio steps either side of the model in the N-DNS validation loop, sparseRNNs/fxprun.py:63-78, with the framing of
+ * train_helpers.py:1382-1412 (scipy.signal.stft / istft: nperseg = nfft = 512, hop 128, boxcar window, one-sided,
+ * boundary="zeros", padded=True, scaling="spectrum").  No model handle, no workspace.  Tensors are frame-major:
+ * (B, n_seg, 257), the rows s5fxp_model_forward_f32 takes and returns; the reference's (B, 257, n_seg) is their transpose.
+ * Both return S5FXP_EBADARG for a null required pointer or B < 1 and S5FXP_EUNSUPPORTED for T < 512 (where scipy changes
+ * nperseg), before the device is touched.
+ *
+ * Frames of a T-sample signal: ceil(T / 128) + 1, or -1 for T < 512.  The inverse returns (frames - 1) * 128 samples. */
+int64_t s5fxp_stft_frames(int64_t T);
+/* stft_splitter + the offset of fxprun.py:64-65: x = |Z| - sub (0.0007 for the model's input, 0 for a plain magnitude).
+ * audio: (B,T) float32; x: (B,n_seg,257) float32; spec: NULL or (B,n_seg,257) complex64 (re, im interleaved), the
+ * spectrum Z itself. */
+int s5fxp_stft_mag(const float *audio, int B, int64_t T, float sub, float *x, float *spec, void *stream);
+/* fxprun.py:76-78 + stft_mixer (train_helpers.py:1399-1412): the spectrum is rebuilt from the noisy audio (bit for bit
+ * s5fxp_stft_mag's), multiplied by 1 + mask -- polar(|Z| * (1 + mask), angle(Z)), negative factors included -- and
+ * transformed back, overlap-added, divided by the window cover and trimmed.  mask: (B,n_seg,257) float32 or NULL (zeros:
+ * the round trip); out: (B,(n_seg-1)*128) float32; cleaned_mag: NULL or (B,n_seg,257) float32 = |Z| * (1 + mask).
+ * No atomics: two calls give identical bits. */
+int s5fxp_mask_istft(const float *audio, const float *mask, int B, int64_t T, float *out, float *cleaned_mag,
+                     void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Model level: FxpRegressionModel.forward, fxpmodel.py:1431-1439 (-> 1261-1271 -> 1110-1161).

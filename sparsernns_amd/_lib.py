@@ -106,6 +106,9 @@ def _load():
         "s5fxp_sigmoid": (i, [p, p, i64, i, i, i, i, I32P, p]),
         "s5fxp_scan": (i, [p, p, p, p, p, p, i, i, i, i, i, i, i, i, i, i, p]),
         "s5fxp_assoc_scan_c64": (i, [p, p, p, p, p, i, i, i, i, p]),
+        "s5fxp_stft_frames": (i64, [i64]),
+        "s5fxp_stft_mag": (i, [p, i, i64, C.c_float, p, p, p]),
+        "s5fxp_mask_istft": (i, [p, p, i, i64, p, p, p]),
         "s5fxp_model_blob_bytes": (C.c_size_t, [C.POINTER(ModelDesc)]),
         "s5fxp_model_create": (i, [C.POINTER(ModelDesc), p, C.c_size_t, i, p, C.POINTER(p)]),
         "s5fxp_model_destroy": (None, [p]),
@@ -136,7 +139,8 @@ EXPORTED_SYMBOLS = ("s5fxp_version s5fxp_strerror s5fxp_from_fp s5fxp_to_float s
                     "s5fxp_mul s5fxp_add_cb s5fxp_mul_cb s5fxp_relu s5fxp_sigmoid s5fxp_scan s5fxp_assoc_scan_c64 s5fxp_model_blob_bytes "
                     "s5fxp_model_create s5fxp_model_destroy s5fxp_workspace_bytes s5fxp_model_forward s5fxp_model_forward_f32 s5fxp_workspace_bytes_f32 s5fxp_layer_forward s5fxp_model_layer_out_bits s5fxp_model_live_states "
                     "s5fxp_model_out_exp s5fxp_model_out_bits s5fxp_model_is_fast s5fxp_model_recurrence_kernel s5fxp_model_recurrence_xmax "
-                    "s5fxp_model_step_ok s5fxp_model_step s5fxp_model_step_f32").split()
+                    "s5fxp_model_step_ok s5fxp_model_step s5fxp_model_step_f32 "
+                    "s5fxp_stft_frames s5fxp_stft_mag s5fxp_mask_istft").split()
 
 
 def check(rc: int, what: str = "") -> None:

@@ -101,3 +101,98 @@ def denoise(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor):
         mask = model(fx).to_float().transpose(-1, -2)
     cleaned_mag = mag * (1.0 + mask)
     return stft_mixer(cleaned_mag, phase), cleaned_mag, mag
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The same loop on the HIP kernels of csrc/audio_stft.hpp (s5fxp_stft_mag / s5fxp_mask_istft).  Everything below is
+# frame-major, (B, n_seg, 257): the rows the model's encoder streams, so no transpose pass exists; the reference's
+# (B, 257, n_seg) is ``.transpose(-1, -2)`` of it.  CUDA tensors go to the kernels on the current stream; CPU tensors take
+# the torch functions above, arranged frame-major.
+# ---------------------------------------------------------------------------------------------------------------------
+def stft_frames(T: int) -> int:
+    """Frames of a T-sample signal, ceil(T / 128) + 1.  Below 512 samples scipy changes nperseg: not supported."""
+    if T < NFFT:
+        raise NotImplementedError(f"stft needs at least {NFFT} samples, got {T}")
+    return -(-T // HOP) + 1
+
+
+def _audio2d(audio: torch.Tensor) -> torch.Tensor:
+    if audio.dim() != 2:
+        raise ValueError(f"audio must be (B, T), got {tuple(audio.shape)}")
+    return audio.to(torch.float32).contiguous()
+
+
+def stft_mag(audio: torch.Tensor, sub: float = STFT_MAG_MEAN, spectrum: bool = False):
+    """audio (B, T) -> x = |Z| - sub, (B, n_seg, 257) float32 (fxprun.py:64-65: the model's input rows); with ``spectrum``
+    also the complex64 spectrum Z, same shape."""
+    audio = _audio2d(audio)
+    B, T = audio.shape
+    n_seg = stft_frames(T)
+    if not audio.is_cuda:
+        z = stft(audio).transpose(-1, -2).contiguous()
+        x = z.abs() - sub
+        return (x, z) if spectrum else x
+    from . import _lib
+    x = torch.empty(B, n_seg, NFFT // 2 + 1, dtype=torch.float32, device=audio.device)
+    spec = torch.empty(B, n_seg, NFFT // 2 + 1, dtype=torch.complex64, device=audio.device) if spectrum else None
+    with torch.cuda.device(audio.device):
+        _lib.check(_lib.lib.s5fxp_stft_mag(audio.data_ptr(), B, T, float(sub), x.data_ptr(),
+                                           spec.data_ptr() if spectrum else None,
+                                           torch.cuda.current_stream().cuda_stream), "s5fxp_stft_mag")
+    return (x, spec) if spectrum else x
+
+
+def mask_istft(audio: torch.Tensor, mask, cleaned_mag: bool = False):
+    """fxprun.py:76-78: the spectrum of ``audio`` (B, T) times 1 + mask (B, n_seg, 257), back to audio
+    (B, (n_seg - 1) * 128); with ``cleaned_mag`` also |Z| * (1 + mask).  ``mask=None`` is the plain round trip.  The complex
+    value is scaled, which is polar(|Z| * (1 + mask), angle(Z)) for either sign of 1 + mask."""
+    audio = _audio2d(audio)
+    B, T = audio.shape
+    n_seg = stft_frames(T)
+    shape = (B, n_seg, NFFT // 2 + 1)
+    if mask is not None:
+        if tuple(mask.shape) != shape or mask.device != audio.device:
+            raise ValueError(f"mask must be {shape} on {audio.device}, got {tuple(mask.shape)} on {mask.device}")
+        mask = mask.to(torch.float32).contiguous()
+    if not audio.is_cuda:
+        z = stft(audio).transpose(-1, -2)
+        f = 1.0 + mask if mask is not None else torch.ones(shape, dtype=torch.float32)
+        out = istft((z * f).transpose(-1, -2))
+        return (out, z.abs() * f) if cleaned_mag else out
+    from . import _lib
+    out = torch.empty(B, (n_seg - 1) * HOP, dtype=torch.float32, device=audio.device)
+    cm = torch.empty(shape, dtype=torch.float32, device=audio.device) if cleaned_mag else None
+    with torch.cuda.device(audio.device):
+        _lib.check(_lib.lib.s5fxp_mask_istft(audio.data_ptr(), mask.data_ptr() if mask is not None else None, B, T,
+                                             out.data_ptr(), cm.data_ptr() if cleaned_mag else None,
+                                             torch.cuda.current_stream().cuda_stream), "s5fxp_mask_istft")
+    return (out, cm) if cleaned_mag else out
+
+
+def denoise_fused(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor):
+    """fxprun.py:63-78 as stft_mag -> model -> mask_istft: noisy audio (B, T) -> (cleaned audio, cleaned magnitude, x, mask),
+    the last three (B, n_seg, 257).  On a GPU that is two launches plus the forward.
+
+    NOT bit-identical to ``denoise``: two FFT implementations differ in the last bits of |Z|, and the FLOOR quantiser turns a
+    few of those differences into one LSB of the model's input.  The model itself stays exact on the ``x`` returned here."""
+    from .fxparray import RoundingMode, fxp_from_fp
+
+    x = stft_mag(noisy)
+    if hasattr(model, "forward_float") and not getattr(model, "store_intermediates", False) and _takes(model, inp_bits, inp_exp):
+        mask = model.forward_float(x)
+    else:
+        fx = fxp_from_fp(x, bits=inp_bits, exp=inp_exp, signed=True, round_mode=RoundingMode.FLOOR)
+        mask = model(fx).to_float()
+    cleaned, cleaned_mag = mask_istft(noisy, mask, cleaned_mag=True)
+    return cleaned, cleaned_mag, x, mask
+
+
+def validate_batch(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, clean: torch.Tensor, lam: float = 0.001):
+    """fxprun.py:79-88: (loss, si_snr), one value per sequence: si_snr = si_snr(cleaned, clean) -- the cleaned audio is the
+    reference's ``target`` argument -- over the clean audio's length, loss = lam * mean((cleaned_mag - clean_mag)^2) +
+    (100 - si_snr), with clean_mag = stft_mag(clean, sub=0)."""
+    cleaned, cleaned_mag, _, _ = denoise_fused(model, inp_bits, inp_exp, noisy)
+    clean_mag = stft_mag(clean, sub=0.0)
+    score = si_snr(cleaned[..., : clean.shape[-1]], clean.to(torch.float32))
+    loss = lam * torch.mean((cleaned_mag - clean_mag) ** 2, dim=(1, 2)) + (100.0 - score)
+    return loss, score

@@ -6,6 +6,7 @@
 #include "s5fxp_kernels.hpp"
 #include "mfma_fused.hpp"
 #include "scan_assoc.hpp"
+#include "audio_stft.hpp"
 
 #include <hip/hip_ext.h>
 
@@ -273,6 +274,32 @@ extern "C" int s5fxp_assoc_scan_c64(const float *lambda, const float *bu, float 
     a.xs = reinterpret_cast<float2 *>(xs); a.x0 = reinterpret_cast<const float2 *>(x0);
     a.x_last = reinterpret_cast<float2 *>(x_last); a.B = B; a.L = L; a.P = P; a.reverse = reverse ? 1 : 0;
     hipLaunchKernelGGL(k_scan_assoc_c64, dim3((unsigned)grid), dim3(64 * ASSOC_WAVES), 0, S(stream), a);
+    return launch_rc();
+}
+
+// The audio steps either side of the model (audio_stft.hpp).  n_seg = ceil(T / 128) + 1 frames for T >= 512.
+extern "C" int64_t s5fxp_stft_frames(int64_t T) { return T < stft::NFFT ? -1 : (T + stft::HOP - 1) / stft::HOP + 1; }
+
+extern "C" int s5fxp_stft_mag(const float *audio, int B, int64_t T, float sub, float *x, float *spec, void *stream)
+{
+    if (!audio || !x || B < 1) return S5FXP_EBADARG;
+    if (T < stft::NFFT) return S5FXP_EUNSUPPORTED;
+    const int64_t n_seg = s5fxp_stft_frames(T), tiles = (n_seg + stft::FR - 1) / stft::FR;
+    if (tiles * B > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
+    hipLaunchKernelGGL(stft::k_stft_mag, dim3((unsigned)(tiles * B)), dim3(256), 0, S(stream), audio, T, n_seg, (int)tiles, sub, x,
+                       reinterpret_cast<float2 *>(spec));
+    return launch_rc();
+}
+
+extern "C" int s5fxp_mask_istft(const float *audio, const float *mask, int B, int64_t T, float *out, float *cleaned_mag,
+                                void *stream)
+{
+    if (!audio || !out || B < 1) return S5FXP_EBADARG;
+    if (T < stft::NFFT) return S5FXP_EUNSUPPORTED;
+    const int64_t n_seg = s5fxp_stft_frames(T), tiles = (n_seg - 1 + stft::OH - 1) / stft::OH;
+    if (tiles * B > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
+    hipLaunchKernelGGL(stft::k_mask_istft, dim3((unsigned)(tiles * B)), dim3(256), 0, S(stream), audio, mask, T, n_seg, (int)tiles,
+                       out, cleaned_mag);
     return launch_rc();
 }
 
