@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define S5FXP_VERSION 107
+#define S5FXP_VERSION 108
 
 enum {
     S5FXP_OK = 0,
@@ -138,6 +138,30 @@ int s5fxp_stft_mag(const float *audio, int B, int64_t T, float sub, float *x, fl
  * No atomics: two calls give identical bits. */
 int s5fxp_mask_istft(const float *audio, const float *mask, int B, int64_t T, float *out, float *cleaned_mag,
                      void *stream);
+
+/* The same framing for a live signal: whole hops of 128 samples in, cleaned hops out (a caller zero-fills its last hop, as
+ * scipy's padded=True does).  S streams advance in lock step.  With h = hops_before hops received and a push of c hops
+ * (1 .. S5FXP_STREAM_MAX_HOPS): the push completes frames h-1 .. h+c-2 of the batch framing, F = c - (h == 0 ? 1 : 0) of them,
+ * and yields output hops max(0, h-3) .. h+c-4, O = min(c, max(0, h+c-3)) of them, plus hop h+c-3 when `final`: a latency of
+ * 3 hops.  A stream of m hops ends with a push of two hops of zeros (audio = NULL) with final set -- scipy's trailing
+ * boundary: m + 1 frames and m hops in all.  Streamed this way x, cleaned_mag and out are bit for bit s5fxp_stft_mag's and
+ * s5fxp_mask_istft's for the whole signal and the concatenated masks.
+ *
+ * state: S * s5fxp_stream_audio_state_bytes() bytes of device memory owned by the caller, per-stream contiguous, updated in
+ * place; all-zero bytes are a fresh stream.  A push is s5fxp_stream_stft, the model on the F rows (s5fxp_model_step_f32),
+ * then s5fxp_stream_mask_istft with the same c and hops_before; the host tracks hops_before, nothing on the device counts.
+ * Both return S5FXP_EBADARG for a null state, S < 1, c outside 1..32, a negative hops_before or a null required tensor, and
+ * s5fxp_stream_mask_istft returns S5FXP_EUNSUPPORTED for final with hops_before < 4 (a signal below 512 samples), before the
+ * device is touched.  No atomics: two runs give identical bits. */
+#define S5FXP_STREAM_MAX_HOPS 32
+size_t s5fxp_stream_audio_state_bytes(void);                          /* per stream, a multiple of 16 */
+int64_t s5fxp_stream_frames(int64_t hops_before, int c);              /* F, or -1 for bad arguments */
+int64_t s5fxp_stream_out_hops(int64_t hops_before, int c, int final); /* O, or -1 for bad arguments */
+/* audio: (S,c*128) float32 or NULL (zeros); x: (S,F,257) float32 = |Z| - sub, may be NULL when F == 0. */
+int s5fxp_stream_stft(const float *audio, int S, int c, int64_t hops_before, float sub, void *state, float *x, void *stream);
+/* mask: (S,F,257) float32 or NULL (zeros); out: (S,O*128) float32, may be NULL when O == 0; cleaned_mag: NULL or (S,F,257). */
+int s5fxp_stream_mask_istft(const float *mask, int S, int c, int64_t hops_before, int final, void *state, float *out,
+                            float *cleaned_mag, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Model level: FxpRegressionModel.forward, fxpmodel.py:1431-1439 (-> 1261-1271 -> 1110-1161).

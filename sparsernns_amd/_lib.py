@@ -27,6 +27,7 @@ FWD_DEFER_REDO, FWD_EXACT, FWD_NO_PAIR = 1, 2, 4
 STATUS_WORDS = 128
 PATH_GENERIC, PATH_FUSED, PATH_STEP = 1, 2, 3   # status[2]
 STEP_MAX_ROWS = 32
+STREAM_MAX_HOPS = 32
 MODEL_DEFAULT, MODEL_FORCE_DENSE, MODEL_FORCE_CSR, MODEL_FORCE_GENERIC = 0, 1, 2, 4
 
 
@@ -109,6 +110,11 @@ def _load():
         "s5fxp_stft_frames": (i64, [i64]),
         "s5fxp_stft_mag": (i, [p, i, i64, C.c_float, p, p, p]),
         "s5fxp_mask_istft": (i, [p, p, i, i64, p, p, p]),
+        "s5fxp_stream_audio_state_bytes": (C.c_size_t, []),
+        "s5fxp_stream_frames": (i64, [i64, i]),
+        "s5fxp_stream_out_hops": (i64, [i64, i, i]),
+        "s5fxp_stream_stft": (i, [p, i, i, i64, C.c_float, p, p, p]),
+        "s5fxp_stream_mask_istft": (i, [p, i, i, i64, i, p, p, p, p]),
         "s5fxp_model_blob_bytes": (C.c_size_t, [C.POINTER(ModelDesc)]),
         "s5fxp_model_create": (i, [C.POINTER(ModelDesc), p, C.c_size_t, i, p, C.POINTER(p)]),
         "s5fxp_model_destroy": (None, [p]),
@@ -140,7 +146,8 @@ EXPORTED_SYMBOLS = ("s5fxp_version s5fxp_strerror s5fxp_from_fp s5fxp_to_float s
                     "s5fxp_model_create s5fxp_model_destroy s5fxp_workspace_bytes s5fxp_model_forward s5fxp_model_forward_f32 s5fxp_workspace_bytes_f32 s5fxp_layer_forward s5fxp_model_layer_out_bits s5fxp_model_live_states "
                     "s5fxp_model_out_exp s5fxp_model_out_bits s5fxp_model_is_fast s5fxp_model_recurrence_kernel s5fxp_model_recurrence_xmax "
                     "s5fxp_model_step_ok s5fxp_model_step s5fxp_model_step_f32 "
-                    "s5fxp_stft_frames s5fxp_stft_mag s5fxp_mask_istft").split()
+                    "s5fxp_stft_frames s5fxp_stft_mag s5fxp_mask_istft s5fxp_stream_audio_state_bytes s5fxp_stream_frames "
+                    "s5fxp_stream_out_hops s5fxp_stream_stft s5fxp_stream_mask_istft").split()
 
 
 def check(rc: int, what: str = "") -> None:

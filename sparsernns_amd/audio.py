@@ -196,3 +196,166 @@ def validate_batch(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, clea
     score = si_snr(cleaned[..., : clean.shape[-1]], clean.to(torch.float32))
     loss = lam * torch.mean((cleaned_mag - clean_mag) ** 2, dim=(1, 2)) + (100.0 - score)
     return loss, score
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The loop for a live signal: csrc/audio_stream.hpp (s5fxp_stream_stft / s5fxp_stream_mask_istft) either side of
+# SessionPool.push.
+# ---------------------------------------------------------------------------------------------------------------------
+STREAM_MAX_HOPS = 32
+
+
+def stream_frames(hops_before: int, c: int) -> int:
+    """Frames a push of c hops completes after hops_before hops: frame k covers audio hops k-2 .. k+1."""
+    return c - (1 if hops_before == 0 else 0)
+
+
+def stream_out_hops(hops_before: int, c: int, final: bool = False) -> int:
+    """Output hops of that push: hop o needs frames o-1 .. o+2, the last hop of a stream (``final``) has only three."""
+    return min(c, max(0, hops_before + c - 3)) + (1 if final else 0)
+
+
+class StreamDenoiser:
+    """``denoise_fused`` for ``sessions`` live signals in lock step: whole hops of 128 samples in, cleaned audio out, three
+    hops (24 ms at 16 kHz) behind the input.  A caller zero-fills its last hop.
+
+        d = StreamDenoiser(model, sessions)
+        for hops in source:                 # (sessions, c * 128) float32, c = 1 .. 32
+            sink(d.push(hops))              # (sessions, O * 128); O = 0 while the first three hops arrive
+        sink(d.finish())                    # the last 3 * 128 samples; reset() before the next signal
+
+    With h hops received, a push of c completes frames h-1 .. h+c-2 of the batch framing and yields output hops
+    max(0, h-3) .. h+c-4; ``finish`` pushes scipy's two trailing hops of zeros.  On a GPU a push is three launches: the x rows
+    and the audio of all pushes, concatenated, are bit for bit ``stft_mag`` / ``mask_istft`` of the whole signal with the
+    concatenated masks, and the masks are what a fresh ``SessionPool`` returns for the same rows in the same chunks.  They
+    are NOT the masks of one forward over the whole clip: every chunk is its own compute_best batch and chooses its own
+    exponents, so low bits differ (as for ``s5fxp_forward_opts.state_in``).
+
+    CPU tensors, and models without an engine (anything with a stateless ``forward_float``), take torch ops with the same
+    bookkeeping.  What ``push`` returns is valid until the next push of the same shape."""
+
+    latency_hops = 3
+
+    def __init__(self, model, sessions: int, sub: float = STFT_MAG_MEAN):
+        if sessions < 1:
+            raise ValueError("sessions must be >= 1")
+        self.model, self.sessions, self.sub = model, int(sessions), float(sub)
+        self.hops = 0
+        self._done = False
+        self._pool = None     # the model's SessionPool (kernel route)
+        self._state = None    # kernel route: (S, state floats); torch route: (audio history, segment carry)
+        self._buf = {}
+
+    # -- bookkeeping ----------------------------------------------------------------------------
+    def reset(self) -> None:
+        """All sessions start a new signal."""
+        self.hops, self._done = 0, False
+        if self._pool is not None:
+            self._pool.reset()
+        if torch.is_tensor(self._state):
+            self._state.zero_()
+        else:
+            self._state = None
+
+    def _kernels(self, dev: torch.device) -> bool:
+        return dev.type == "cuda" and hasattr(self.model, "engine")
+
+    def push(self, hops: torch.Tensor, check: bool = True, details: bool = False):
+        """hops: (sessions, c * 128) float32, c = 1 .. 32.  Returns the cleaned audio (sessions, O * 128); with ``details``
+        (cleaned, x, mask, cleaned_mag), the last three (sessions, F, 257).  ``check`` is SessionPool.push's."""
+        if hops.dim() != 2 or hops.shape[0] != self.sessions or hops.shape[1] % HOP or hops.dtype != torch.float32:
+            raise ValueError(f"hops must be ({self.sessions}, c * {HOP}) float32, got {tuple(hops.shape)} {hops.dtype}")
+        c = hops.shape[1] // HOP
+        if not 1 <= c <= STREAM_MAX_HOPS:
+            raise ValueError(f"a push takes 1 .. {STREAM_MAX_HOPS} hops, got {c}")
+        return self._push(hops.contiguous(), c, hops.device, False, check, details)
+
+    def finish(self, check: bool = True, details: bool = False, device=None):
+        """The end of the signal: scipy's trailing boundary, two hops of zeros.  Returns the last 3 * 128 samples per session
+        (and with ``details`` the last two frames' rows) and leaves the object needing a ``reset()``."""
+        if self.hops < 4:
+            raise NotImplementedError(f"stft needs at least {NFFT} samples, got {self.hops * HOP}")
+        if device is None:
+            device = self._state.device if torch.is_tensor(self._state) else self._state[0].device
+        return self._push(None, 2, torch.device(device), True, check, details)
+
+    def _push(self, hops, c, dev, final, check, details):
+        if self._done:
+            raise RuntimeError("the signal has ended: reset() first")
+        h, S = self.hops, self.sessions
+        F, n_out = stream_frames(h, c), stream_out_hops(h, c, final)
+        run = self._push_kernels if self._kernels(dev) else self._push_torch
+        res = run(hops, c, dev, final, check, details, h, S, F, n_out)
+        self.hops += c
+        self._done = final
+        return res
+
+    # -- HIP kernels + SessionPool ----------------------------------------------------------------
+    def _buffers(self, dev, F, n_out, details):
+        key = (F, n_out)
+        b = self._buf.get(key)
+        if b is None:
+            b = self._buf[key] = [torch.empty(self.sessions, F, NFFT // 2 + 1, dtype=torch.float32, device=dev),
+                                  torch.empty(self.sessions, n_out * HOP, dtype=torch.float32, device=dev), None]
+        if details and b[2] is None:
+            b[2] = torch.empty(self.sessions, F, NFFT // 2 + 1, dtype=torch.float32, device=dev)
+        return b
+
+    def _push_kernels(self, hops, c, dev, final, check, details, h, S, F, n_out):
+        from . import _lib
+        if self._pool is None:
+            self._pool = self.model.engine().pool(S)
+        if self._state is None:
+            self._state = torch.zeros(S, _lib.lib.s5fxp_stream_audio_state_bytes() // 4, dtype=torch.float32, device=dev)
+        x, out, cm = self._buffers(dev, F, n_out, details)
+        ptr = lambda t, n: t.data_ptr() if t is not None and n else None
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            _lib.check(_lib.lib.s5fxp_stream_stft(ptr(hops, 1), S, c, h, self.sub, self._state.data_ptr(), ptr(x, F), stream),
+                       "s5fxp_stream_stft")
+            mask = self._pool.push(x, check=check) if F else x
+            _lib.check(_lib.lib.s5fxp_stream_mask_istft(ptr(mask, F), S, c, h, int(final), self._state.data_ptr(),
+                                                        ptr(out, n_out), ptr(cm, F) if details else None, stream),
+                       "s5fxp_stream_mask_istft")
+        return (out, x, mask, cm) if details else out
+
+    # -- torch ops --------------------------------------------------------------------------------
+    def _mask(self, x, check):
+        if hasattr(self.model, "engine"):
+            if self._pool is None:
+                self._pool = self.model.engine().pool(self.sessions)
+            return self._pool.push(x.to(self._pool.engine.device), check=check).to(x.device)
+        return self.model.forward_float(x)
+
+    def _push_torch(self, hops, c, dev, final, check, details, h, S, F, n_out):
+        if self._state is None:
+            self._state = (torch.zeros(S, 3 * HOP, device=dev), torch.zeros(S, 3, NFFT, device=dev))
+        hist, carry = self._state
+        if hops is None:
+            hops = torch.zeros(S, c * HOP, device=dev)
+        window = torch.cat([hist, hops], dim=1)
+        fr = window.unfold(-1, NFFT, HOP)[:, c - F:]           # frames h-1 .. h+c-2 without frame -1
+        if F:
+            z = torch.fft.rfft(fr, n=NFFT, dim=-1) / NFFT
+            x = (z.abs() - self.sub).contiguous()
+            mask = self._mask(x, check)
+            f = 1.0 + mask
+            seg, cm = torch.fft.irfft(z * f, n=NFFT, dim=-1) * NFFT, z.abs() * f
+        else:  # the first hop of a signal completes no frame
+            x = mask = cm = torch.zeros(S, 0, NFFT // 2 + 1, device=dev)
+            seg = torch.zeros(S, 0, NFFT, device=dev)
+        # the segment list of the push: carried, (frame -1,) new, (the frame beyond the end); row r sums entries r .. r+3
+        zero = torch.zeros(S, 1, NFFT, device=dev)
+        v = torch.cat([carry] + [zero] * (c - F) + [seg] + [zero] * int(final), dim=1)
+        rows = c + int(final)
+        acc = torch.zeros(S, rows, HOP, device=dev)
+        for q in range(4):
+            acc = acc + v[:, q:q + rows, HOP * (3 - q):HOP * (4 - q)]
+        cover = torch.full((rows,), 4.0, device=dev)
+        if 0 <= 3 - h < rows:
+            cover[3 - h] = 3.0          # output hop 0: frame -1 does not exist
+        if final:
+            cover[-1] = 3.0
+        out = (acc / cover[None, :, None])[:, rows - n_out:].reshape(S, n_out * HOP)
+        self._state = (window[:, -3 * HOP:].contiguous(), v[:, c:c + 3].contiguous())
+        return (out, x, mask, cm) if details else out

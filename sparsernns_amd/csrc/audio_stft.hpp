@@ -112,21 +112,13 @@ __device__ __forceinline__ void make_twiddles(Smem &sm)
     }
 }
 
-// Stages hops h0 .. h0+18 of the padded signal of one sequence and leaves, for the 16 frames that start at those hops,
-// Y = the 256-point transform of z[n] = x[2n] + i x[2n+1] in plane B (natural order, frame stride FSTR).  Ends with a barrier.
-__device__ __forceinline__ void forward_tile(Smem &sm, const float *__restrict__ audio, int64_t T, int64_t h0)
+// With 19 hops staged in plane B (hop stride HSTR) and a barrier behind them: leaves, for the 16 frames that start at those
+// hops, Y = the 256-point transform of z[n] = x[2n] + i x[2n+1] in plane B (natural order, frame stride FSTR).  Ends with a
+// barrier.
+__device__ __forceinline__ void forward_transform(Smem &sm)
 {
 #pragma clang fp contract(off)
-    float *stage = reinterpret_cast<float *>(sm.b);
-    // unrolled: the loads of all ten rounds are in flight together
-#pragma unroll
-    for (int j = 0; j < (NHOP * HOP + 255) / 256; ++j) {
-        const int i = threadIdx.x + 256 * j;
-        const int64_t t = (h0 + (i >> 7)) * HOP + (i & 127) - NFFT / 2;
-        const float a = (i < NHOP * HOP && t >= 0 && t < T) ? audio[t] : 0.0f;
-        if (i < NHOP * HOP) stage[(i >> 7) * HSTR + (i & 127)] = a;
-    }
-    __syncthreads();
+    const float *stage = reinterpret_cast<const float *>(sm.b);
     const int fr = threadIdx.x >> 4, l = threadIdx.x & 15;
     float2 v[16];
 #pragma unroll
@@ -138,6 +130,22 @@ __device__ __forceinline__ void forward_tile(Smem &sm, const float *__restrict__
 #pragma unroll
     for (int d = 0; d < 16; ++d) sm.b[fr * FSTR + l + 16 * d] = v[pos16(d)];
     __syncthreads();
+}
+
+// Stages hops h0 .. h0+18 of the padded signal of one sequence and runs forward_transform on them.
+__device__ __forceinline__ void forward_tile(Smem &sm, const float *__restrict__ audio, int64_t T, int64_t h0)
+{
+    float *stage = reinterpret_cast<float *>(sm.b);
+    // unrolled: the loads of all ten rounds are in flight together
+#pragma unroll
+    for (int j = 0; j < (NHOP * HOP + 255) / 256; ++j) {
+        const int i = threadIdx.x + 256 * j;
+        const int64_t t = (h0 + (i >> 7)) * HOP + (i & 127) - NFFT / 2;
+        const float a = (i < NHOP * HOP && t >= 0 && t < T) ? audio[t] : 0.0f;
+        if (i < NHOP * HOP) stage[(i >> 7) * HSTR + (i & 127)] = a;
+    }
+    __syncthreads();
+    forward_transform(sm);
 }
 
 // Bin k (0..256) of the 512-point real transform, scaled by 1/512, from the 256-point Y of the packed signal.
@@ -155,6 +163,34 @@ __device__ __forceinline__ float cabs(float2 z)
 {
 #pragma clang fp contract(off)
     return __builtin_sqrtf(z.x * z.x + z.y * z.y);
+}
+
+// With the one-sided spectra Z' of the tile's 16 frames in plane A (bins 0..256, frame stride FSTR) and a barrier behind them:
+// leaves their 512 real samples in plane A (floats, frame stride 2 * FSTR).  Uses plane B.  Ends with a barrier.
+__device__ __forceinline__ void inverse_tile(Smem &sm)
+{
+#pragma clang fp contract(off)
+    const int fr = threadIdx.x >> 4, l = threadIdx.x & 15;
+    float2 v[16];
+    {
+        const float2 *Z = sm.a + fr * FSTR;
+#pragma unroll
+        for (int a = 0; a < 16; ++a) {
+            // Y'[k] = Xe + i Xo, Xe = (p + conj q) / 2, Xo = (p - conj q) / 2 * conj(w^k); the halves and the 512 of
+            // irfft(512 Z') cancel against the 1/256 of the packed inverse
+            const int k = 16 * a + l;
+            const float2 p = Z[k], q = Z[256 - k], w = sm.tw[k];
+            const float ex = p.x - q.x, ey = p.y + q.y;
+            const float gx = __builtin_fmaf(ex, w.x, ey * w.y), gy = __builtin_fmaf(ey, w.x, -(ex * w.y));
+            v[a] = make_float2((p.x + q.x) - gy, (p.y - q.y) + gx);
+        }
+    }
+    fft16<true>(v);
+    fft256_finish<true>(v, sm.b + fr * FSTR, sm.tw, l);
+    // lane l holds z'[l + 16 d] = (x'[2l + 32d], x'[2l + 32d + 1]); plane A was last read before the exchange's barrier
+#pragma unroll
+    for (int d = 0; d < 16; ++d) sm.a[fr * FSTR + l + 16 * d] = v[pos16(d)];
+    __syncthreads();
 }
 
 // grid = B * tiles, tiles = ceil(n_seg / 16)
@@ -216,27 +252,7 @@ __global__ __launch_bounds__(256) void k_mask_istft(const float *__restrict__ au
         sm.a[fr * FSTR + k] = z;
     }
     __syncthreads();
-    const int fr = threadIdx.x >> 4, l = threadIdx.x & 15;
-    float2 v[16];
-    {
-        const float2 *Z = sm.a + fr * FSTR;
-#pragma unroll
-        for (int a = 0; a < 16; ++a) {
-            // Y'[k] = Xe + i Xo, Xe = (p + conj q) / 2, Xo = (p - conj q) / 2 * conj(w^k); the halves and the 512 of
-            // irfft(512 Z') cancel against the 1/256 of the packed inverse
-            const int k = 16 * a + l;
-            const float2 p = Z[k], q = Z[256 - k], w = sm.tw[k];
-            const float ex = p.x - q.x, ey = p.y + q.y;
-            const float gx = __builtin_fmaf(ex, w.x, ey * w.y), gy = __builtin_fmaf(ey, w.x, -(ex * w.y));
-            v[a] = make_float2((p.x + q.x) - gy, (p.y - q.y) + gx);
-        }
-    }
-    fft16<true>(v);
-    fft256_finish<true>(v, sm.b + fr * FSTR, sm.tw, l);
-    // lane l holds z'[l + 16 d] = (x'[2l + 32d], x'[2l + 32d + 1]); plane A was last read before the exchange's barrier
-#pragma unroll
-    for (int d = 0; d < 16; ++d) sm.a[fr * FSTR + l + 16 * d] = v[pos16(d)];
-    __syncthreads();
+    inverse_tile(sm);
     const int64_t n_out = n_seg - 1;
     const int noh = (int)(n_out - o0 < OH ? n_out - o0 : OH);
     const float *seg = reinterpret_cast<const float *>(sm.a);

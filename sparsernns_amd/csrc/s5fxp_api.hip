@@ -7,6 +7,7 @@
 #include "mfma_fused.hpp"
 #include "scan_assoc.hpp"
 #include "audio_stft.hpp"
+#include "audio_stream.hpp"
 
 #include <hip/hip_ext.h>
 
@@ -300,6 +301,43 @@ extern "C" int s5fxp_mask_istft(const float *audio, const float *mask, int B, in
     if (tiles * B > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
     hipLaunchKernelGGL(stft::k_mask_istft, dim3((unsigned)(tiles * B)), dim3(256), 0, S(stream), audio, mask, T, n_seg, (int)tiles,
                        out, cleaned_mag);
+    return launch_rc();
+}
+
+// The same framing for a live signal (audio_stream.hpp): whole hops in, cleaned hops out, the caller's state between calls.
+extern "C" size_t s5fxp_stream_audio_state_bytes(void) { return stft::STATE_FLOATS * sizeof(float); }
+
+extern "C" int64_t s5fxp_stream_frames(int64_t hops_before, int c)
+{
+    if (hops_before < 0 || c < 1 || c > stft::STREAM_MAX_HOPS) return -1;
+    return c - (hops_before == 0 ? 1 : 0);
+}
+
+extern "C" int64_t s5fxp_stream_out_hops(int64_t hops_before, int c, int final)
+{
+    if (hops_before < 0 || c < 1 || c > stft::STREAM_MAX_HOPS) return -1;
+    const int64_t ready = hops_before + c - 3;
+    return (ready < 0 ? 0 : ready < c ? ready : c) + (final ? 1 : 0);
+}
+
+extern "C" int s5fxp_stream_stft(const float *audio, int n, int c, int64_t hops_before, float sub, void *state, float *x,
+                                 void *stream)
+{
+    if (!state || n < 1 || s5fxp_stream_frames(hops_before, c) < 0) return S5FXP_EBADARG;
+    if (!x && s5fxp_stream_frames(hops_before, c) > 0) return S5FXP_EBADARG;
+    hipLaunchKernelGGL(stft::k_stream_stft, dim3((unsigned)n), dim3(256), 0, S(stream), audio, c, hops_before == 0 ? 1 : 0, sub,
+                       static_cast<float *>(state), x);
+    return launch_rc();
+}
+
+extern "C" int s5fxp_stream_mask_istft(const float *mask, int n, int c, int64_t hops_before, int final, void *state, float *out,
+                                       float *cleaned_mag, void *stream)
+{
+    if (!state || n < 1 || s5fxp_stream_frames(hops_before, c) < 0) return S5FXP_EBADARG;
+    if (!out && s5fxp_stream_out_hops(hops_before, c, final) > 0) return S5FXP_EBADARG;
+    if (final && hops_before < 4) return S5FXP_EUNSUPPORTED;
+    hipLaunchKernelGGL(stft::k_stream_mask_istft, dim3((unsigned)n), dim3(256), 0, S(stream), mask, c,
+                       (int)(hops_before < 4 ? hops_before : 4), final ? 1 : 0, static_cast<float *>(state), out, cleaned_mag);
     return launch_rc();
 }
 
