@@ -262,9 +262,9 @@ enum {
     S5FXP_ST_WIDE_STATE = 4, /* informational: an SSM state exceeded 24 bits, the 32-bit C projection ran */
     S5FXP_ST_WIDE_INPUT = 8, /* the input tensor holds values beyond 24 bits: results invalid, re-run with a
                                 model created with S5FXP_MODEL_FORCE_GENERIC */
-    S5FXP_ST_REDO = 16       /* only with S5FXP_FWD_DEFER_REDO: a state left the fast recurrence's exact range and
-                                the exact re-run was NOT enqueued: results invalid, call again with
-                                S5FXP_FWD_EXACT */
+    S5FXP_ST_REDO = 16       /* only with S5FXP_FWD_DEFER_REDO: a state left the fast recurrence's exact range -- a
+                                stored state, or a state_in value the recurrence started from -- and the exact
+                                re-run was NOT enqueued: results invalid, call again with S5FXP_FWD_EXACT */
 };
 
 /* s5fxp_forward_opts.flags.  By default a forward is self-contained: next to the fast recurrence it enqueues
@@ -302,8 +302,12 @@ typedef struct {
      * states after the last frame are left (NULL: not wanted).  Feeding a sequence chunk by chunk with the carry gives,
      * per chunk, what the reference computes for that chunk started from that carry -- every chunk is its own
      * compute_best batch, so the exponents (and with them the low bits) can differ from one pass over the whole
-     * sequence.  With S5FXP_FWD_DEFER_REDO keep state_in and state_out apart: a forward that comes back with
-     * S5FXP_ST_REDO has left an unusable state_out, and its repeat needs the old state_in. */
+     * sequence.  state_in may hold int32 values of any width (the exact kernels, s5fxp_model_step and a caller leave
+     * such carries): the fast recurrence kernels range-check the values they start from against the bound the states
+     * are checked with, and a carry beyond it takes the same route as a state beyond it -- the gated exact kernels of
+     * a default forward, S5FXP_ST_REDO under S5FXP_FWD_DEFER_REDO.  state_in is only ever read.  With
+     * S5FXP_FWD_DEFER_REDO keep state_in and state_out apart: a forward that comes back with S5FXP_ST_REDO has left
+     * an unusable state_out, and its repeat needs the old state_in. */
     const int32_t *state_in;
     int32_t *state_out;
     /* Grouped call (0 or 1: a plain forward).  groups = G > 1: x and y hold G * B sequences -- G independent reference
@@ -423,10 +427,13 @@ int s5fxp_model_is_fast(const s5fxp_model *m);
  * S5FXP_FWD_EXACT forward, 6 = the plain 32-bit recurrence that runs inside s5fxp_model_step's one kernel.)
  * -1: bad argument.  The exact re-run (S5FXP_FWD_EXACT) always uses the 32-bit quad kernel on the MFMA path. */
 int s5fxp_model_recurrence_kernel(const s5fxp_model *m, int layer);
-/* The bound on |state| up to which that kernel is exact (the consumer of the states checks it on the data and raises
- * S5FXP_ST_REDO / runs the exact kernels beyond it): 32766 at most for the int16-stream kernels, less for the pair
- * kernel when the layer's coefficients and Bu width leave less room.  0: no bound (generic 32-bit recurrence), -1: bad
- * argument. */
+/* The bound on |state| up to which that kernel is exact, as the forward checks it: on every stored state by the consumer
+ * of the states, on the carry in (state_in) by the recurrence kernel itself; beyond it S5FXP_ST_REDO is raised / the exact
+ * kernels run.  Pair kernels (3, 4): the value checked, 32766 at most, less when the layer's coefficients and Bu width leave
+ * less room.  Quad kernel with int16 streams (2): min(the quad kernel's bound, 32766), the value checked.  Quad kernel with
+ * int32 streams (1): the quad kernel's bound (2^31 - 1 - 2^16) / max|A * 2^(16 - exp)|; a generic model checks exactly that,
+ * a default (not DEFER_REDO) forward on the fused path checks min(that, 32767), the reach of its 16-bit state planes.
+ * 0: no bound (generic 32-bit recurrence), -1: bad argument. */
 int s5fxp_model_recurrence_xmax(const s5fxp_model *m, int layer);
 
 #ifdef __cplusplus

@@ -827,7 +827,8 @@ int generic_layers(const GenericRun &g, int first, int last, int32_t *&h, int32_
             else S5_DISPATCH_MW(a.mw, false, k_bproj, tiles, st, a);
         }
         // ---- recurrence.  Fast: quad kernel (3 dependent VALU ops / step), exact while |x| <= xmax; the C
-        //      projection checks that bound on every state and, if it fails, the exact 32-bit kernels re-run.
+        //      projection checks that bound on every state, the quad kernel on the carry it starts from, and if
+        //      either fails, the exact 32-bit kernels re-run.
         ScanArgs sl{};
         sl.bu_re = I(w.bq); sl.a_re = l.a_re; sl.a_im = l.a_im; sl.out_re = I(w.xs);
         sl.B = B; sl.L = L; sl.P = P; sl.TB = w.TB; sl.ea_re = s.A_re_exp; sl.ea_im = s.A_im_exp;
@@ -842,6 +843,8 @@ int generic_layers(const GenericRun &g, int first, int last, int32_t *&h, int32_
             ScanQuadArgs q{};
             q.bq = I(w.bq); q.xs = I(w.xs); q.a_re = l.a_re; q.a_im = l.a_im; q.B = B; q.TB = w.TB; q.P = P;
             q.ea_re = s.A_re_exp; q.ea_im = s.A_im_exp; q.x0_re = sl.x0_re; q.x0_im = sl.x0_im;
+            // the carry is no stored state: the quad kernel checks it against its bound itself (scan_quad.hpp CarryCheck)
+            if (state_in) q.cc = CarryCheck{l.quad_xmax, ST_WIDE_STATE, &d->redo, status};
             hipLaunchKernelGGL(k_scan_quad_asm, dim3((unsigned)((int64_t)B * P / 16)), dim3(64), 0, st, q, GroupOff{});
             xmax = l.quad_xmax;
         } else {

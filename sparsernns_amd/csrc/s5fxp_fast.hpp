@@ -709,7 +709,18 @@ struct FusedForward {
         q.bq = I32(w.bq); q.xs = I32(w.xs); q.a_re = p.a_re; q.a_im = p.a_im; q.B = B; q.TB = w.TB; q.P = p.P;
         q.ea_re = s.A_re_exp; q.ea_im = s.A_im_exp; q.run_if = run_if; q.x0_re = x0(li, 0); q.x0_im = x0(li, 1);
         q.live_slots = p.live_slots;
+        if (!run_if) q.cc = carry_check(li); // the fast kernels; the gated exact chain takes a carry of any width
         return q;
+    }
+    // the fast recurrence kernels' range check of the carry in (scan_quad.hpp CarryCheck): the bound and the bits the gate
+    // kernel uses for the stored states.  Without state_in, and on the exact rung, there is nothing to check.
+    CarryCheck carry_check(int li) const
+    {
+        const LayerPlan &p = layer[li];
+        CarryCheck c{};
+        if (!state_in || !p.rung.quad) return c;
+        c.xmax = p.xmax; c.bad_bits = ST_WIDE_STATE | (defer ? ST_REDO : 0); c.redo = &dyn[li].redo; c.status = status;
+        return c;
     }
     // the carry in of layer li, part c (0 = re, 1 = im), or nullptr
     const int32_t *x0(int li, int c) const
@@ -731,6 +742,7 @@ struct FusedForward {
             ScanPairLArgs q{};
             q.b16 = I16(w.bq); q.xs = I16(w.xs); q.a_re = p.a_re; q.a_im = p.a_im; q.B = B; q.TB = w.TB; q.P = p.P;
             q.ea_re = s.A_re_exp; q.ea_im = s.A_im_exp; q.x0_re = x0(li, 0); q.x0_im = x0(li, 1); q.live_slots = p.live_slots;
+            q.cc = carry_check(li);
             // one helper wave (a second one lands on the computing wave's side of the LDS path and costs more than it
             // helps: profiles/r02_ubench_pair.log).  Blocks per LDS buffer = steps per s_barrier / 4: S5FXP_PAIRL_BLOCKS
             const int blocks = cfg.pairl_blocks;
@@ -739,6 +751,7 @@ struct FusedForward {
             ScanPairArgs q{};
             q.k = I32(w.bq); q.xs = I16(w.xs); q.a_re = p.a_re; q.a_im = p.a_im; q.B = B; q.TB = w.TB; q.P = p.P;
             q.ea_re = s.A_re_exp; q.ea_im = s.A_im_exp; q.x0_re = x0(li, 0); q.x0_im = x0(li, 1);
+            q.cc = carry_check(li);
             launch(k_scan_pair_asm, pair_grid, 64, 0, ev0, ev1, q);
         } else {
             // not quad: states of any width, the exact 32-bit chain in the same quad layout

@@ -20,9 +20,12 @@
 // Exactness: with |c*x| + k < 2^31 the 24-bit multiply-add is the true integer, its ">>16" equals
 // asr(A*x, e) (or its exact negation), and all additions wrap like int32.  The bound is
 // |x| <= xmax = (2^31 - 1 - 2^16) / max|c|  (32767 for 16-bit Lambda at exponent 15, i.e. the state's
-// nominal width).  The consumer of the states checks |x| <= xmax on every stored state; by
-// induction over t that proves every product was exact.  If the check fails the forward re-runs the
-// layer with the 32-bit one-lane-per-state kernel (k_scan_lane), so results are exact either way.
+// nominal width).  The consumer of the states checks |x| <= xmax on every stored state, and the recurrence
+// kernel itself checks it on the state it starts from -- the streaming carry, which is no stored state and
+// which the exact kernels, the step kernel and a caller may leave at any width (CarryCheck below): base case
+// and step of an induction over t that proves every product was exact.  If a check fails the forward re-runs
+// the layer with the exact 32-bit kernels (k_scan_quad32_asm; k_scan_lane_native on the generic path) or, under
+// S5FXP_FWD_DEFER_REDO, reports S5FXP_ST_REDO, so results are exact either way.
 //
 // Streams use the "scan-native" layout, written by the B projection and read by the C projection:
 //     word(b, tb, p, c, j) = ((((b*TB + tb)*P + p)*2 + c)*4 + j),   t = 4*tb + j,  c: 0 = re, 1 = im
@@ -117,6 +120,28 @@ __device__ __forceinline__ int64_t native_word(int64_t b, int t, int p, int c, i
     return ((((b * TB + (t >> 2)) * P + p) * 2 + c) << 2) + (t & 3);
 }
 
+// The base case of the exactness argument: a fast recurrence kernel that starts from a carry compares the value every lane
+// loaded -- whatever the rung's lane layout -- with the bound the consumer checks on the stored states (LayerPlan::xmax; the
+// generic path's quad bound).  |lambda| < 1, so a carry beyond the bound can produce wrapped products and a first stored state
+// back inside it, which the consumer's check alone would pass.  On a violation: LayerDyn::redo (a default forward then runs
+// its exact kernels) and bad_bits in this group's status words (S5FXP_ST_REDO under S5FXP_FWD_DEFER_REDO).  The carry is
+// only read.  xmax == 0: nothing to check -- a forward without state_in (one scalar compare), or an exact kernel.
+struct CarryCheck {
+    int32_t xmax, bad_bits;
+    int32_t *redo;   // LayerDyn::redo of the layer (workspace)
+    int32_t *status; // the forward's status words
+};
+__device__ __forceinline__ void carry_check(CarryCheck c, const GroupOff &go, int32_t x0)
+{
+    if (c.xmax <= 0) return;
+    if (__any(x0 > c.xmax || x0 < -c.xmax) && (threadIdx.x & 63) == 0) {
+        const int64_t g = blockIdx.y;
+        gshift_nn(c.redo, g * go.ws); gshift_nn(c.status, g * go.status);
+        atomicExch(c.redo, 1);
+        atomicOr(c.status, c.bad_bits);
+    }
+}
+
 struct ScanQuadArgs {
     const int32_t *bq;          // native stream: Bu already shifted to the state exponent
     int32_t *xs;                // native stream: raw states
@@ -127,6 +152,7 @@ struct ScanQuadArgs {
     const int32_t *run_if;      // k_scan_quad32_asm: do the work only when *run_if != 0 (nullptr: always)
     const int32_t *x0_re, *x0_im; // (B,P) state before the first step (streaming carry), nullptr = zeros
     int32_t live_slots;         // k_scan_quad_asm16, > 0: state slots at or above it are not in the streams (ScanPairLArgs)
+    CarryCheck cc;              // k_scan_quad_asm, k_scan_quad_asm16: the range check of x0 (xmax == 0: none)
 };
 
 // the state a quad lane holds before an even step: lanes 0,3 the real part, lanes 1,2 the imaginary part
@@ -243,6 +269,7 @@ __global__ __launch_bounds__(64) void k_scan_quad_asm(ScanQuadArgs a, GroupOff g
     // 0,3 of a quad hold the real part and lanes 1,2 the imaginary part.
     const int tb0 = a.tb0, ntb = a.ntb > 0 ? a.ntb : a.TB - a.tb0;
     int32_t x0 = quad_x0(a, b, p, r);
+    carry_check(a.cc, go, x0);
     if (tb0 > 0) x0 = a.xs[native_word(b, 4 * tb0 - 1, p, (r == 0 || r == 3) ? 0 : 1, a.TB, a.P)];
     const size_t wave_off = (((size_t)b * a.TB + tb0) * a.P + p0) * 8; // words
     const unsigned blk_stride = (unsigned)a.P * 32u;
@@ -283,6 +310,7 @@ __global__ __launch_bounds__(64) void k_scan_quad_asm16(ScanQuadArgs a, GroupOff
     else if (r == 2) { cA = -(Ai << sre); kA = kre; cB = Ai << sim; }
     else { cA = Ai << sim; cB = -(Ai << sre); kB = kre; }
     const int32_t x0 = quad_x0(a, b, p, r);
+    carry_check(a.cc, go, x0);
     const size_t wave_off = (((size_t)b * a.TB) * a.P + p0) * 8; // halfwords
     const unsigned blk_stride = (unsigned)a.P * 16u;
     const unsigned extent = (unsigned)a.TB * blk_stride;
@@ -355,8 +383,8 @@ __global__ __launch_bounds__(64) void k_scan_quad32_asm(ScanQuadArgs a, GroupOff
 //
 // Exactness: z2 < 2^31 needs |Ar| * 2^(16-e) * |x| < 2^31; z1 needs |Ai| * 2^(16-e) * |x| + 2^16 * (|Bu| + 1) < 2^31.
 // With |Bu| <= bmax known statically (its bits minus the shift to the state exponent) that is a bound |x| <= xmax
-// (pack_layer: LayerDev::pair_xmax), checked by the consumer on every stored state exactly like the quad kernels'
-// bound; states are stored as saturated int16, so a state beyond 16 bits fails the check as well.
+// (pack_layer: LayerDev::pair_xmax), checked by the consumer on every stored state and by this kernel on its carry exactly
+// like the quad kernels' bound; states are stored as saturated int16, so a state beyond 16 bits fails the check as well.
 //
 // Streams ("pair-native", a wave's blocks are contiguous so that immediate offsets reach eight of them):
 //   K   int32  word(b, tb, p, lane, slot) = ((((b*PG + p/32)*TB + tb)*32 + p%32)*2 + lane)*4 + slot,  PG = P/32,
@@ -411,6 +439,7 @@ struct ScanPairArgs {
     int32_t B, TB, P;           // TB % S5_SCANP_ASM_DEPTH == 0
     int32_t ea_re, ea_im;
     const int32_t *x0_re, *x0_im; // (B,P) state before the first step (streaming carry), nullptr = zeros
+    CarryCheck cc;                // the range check of x0 (xmax == 0: none)
 };
 
 __global__ __launch_bounds__(64) void k_scan_pair_asm(ScanPairArgs a, GroupOff go)
@@ -436,6 +465,7 @@ __global__ __launch_bounds__(64) void k_scan_pair_asm(ScanPairArgs a, GroupOff g
     // lane A holds re before an even step, lane B im
     const size_t sp = (size_t)(wave / (a.P >> 5)) * a.P + p;
     const int32_t x0 = a.x0_re ? (laneB ? a.x0_im[sp] : a.x0_re[sp]) : 0;
+    carry_check(a.cc, go, x0);
     unsigned cnt = (unsigned)a.TB / S5_SCANP_ASM_DEPTH;
     asm volatile(S5_SCANP_ASM_BODY
                  : [cnt] "+s"(cnt)
@@ -470,6 +500,7 @@ struct ScanPairLArgs {
     // once in BOTH waves, so the padding slots' share of the two streams is neither read nor written (their producer and
     // consumer skip the same slots: k_bproj_p<.., SM = 3> and k_cgate_p<.., PAIR>)
     int32_t live_slots;
+    CarryCheck cc; // the range check of x0, by the computing wave (xmax == 0: none)
 };
 
 template <int... J, class F>
@@ -635,6 +666,7 @@ __global__ __launch_bounds__(128) void k_scan_pairl_asm(ScanPairLArgs a, GroupOf
     const unsigned vlds = (unsigned)(size_t)kbuf + lane * 16, vout = lane * 16 + 4096;
     const size_t sp = (size_t)(wave / (a.P >> 5)) * a.P + p;
     const int32_t x0 = a.x0_re ? (laneB ? a.x0_im[sp] : a.x0_re[sp]) : 0; // lane A holds re before an even step
+    carry_check(a.cc, go, x0);
 
     unsigned cnt = (unsigned)n_it;
     if constexpr (BLOCKS == 16)
