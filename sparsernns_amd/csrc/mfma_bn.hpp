@@ -62,6 +62,23 @@ __device__ __forceinline__ void unpack8_i16(const v4i &w, int32_t (&v)[8])
     }
 }
 
+// eight uint16 values of a row vector (the residual add's aligned sum U, see SumU16 below)
+__device__ __forceinline__ void unpack8_u16(const v4i &w, int32_t (&v)[8])
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        v[2 * i] = (int32_t)((uint32_t)w[i] & 0xffffu);
+        v[2 * i + 1] = (int32_t)((uint32_t)w[i] >> 16);
+    }
+}
+// U -> h = relu(add_cb_apply(z, skip)) for the result shift post = lsh - rsh (one of them zero) and the result's clip bounds:
+// what add_cb_apply and the ReLU do with a sum that is already formed (the ReLU acts only where a left shift beyond 15 wraps)
+__device__ __forceinline__ int32_t resolve_u16(int32_t u, int lsh, int rsh, const SatB &so)
+{
+    const int32_t v = sat(asr(wshl(u, lsh), rsh), so);
+    return v < 0 ? 0 : v;
+}
+
 // block reduce of NV float maxima over blockDim.x threads (every thread gets the result)
 template <int NV>
 __device__ __forceinline__ void block_allmax(float (&v)[NV], float (*red)[8])
@@ -228,8 +245,10 @@ struct ResidHead {
     int32_t enable; // 0: d->res was written by k_res_finalize
 };
 
+// USUM (with RESID): z_ holds the gate kernel's aligned sum U (uint16, SumU16 below) instead of z: the pass reads that one
+// plane, not z and skip, and h = resolve_u16(U) (s5fxp_fast.hpp LayerPlan::resid_fold)
 constexpr int RESID_THREADS = 384;
-template <bool RESID>
+template <bool RESID, bool USUM = false>
 __global__ __launch_bounds__(RESID_THREADS, 5) void k_resid_minmax16(const int16_t *z_, const int16_t *skip_, int16_t *out_, int32_t *tr_resid,
                                                                   int64_t N, int H, int64_t span, int res_bits, int skip_bits, ResidHead hd,
                                                                   float *ext, int ext_reps, int32_t *status, GroupOff go)
@@ -264,7 +283,7 @@ __global__ __launch_bounds__(RESID_THREADS, 5) void k_resid_minmax16(const int16
             if (i0 + k * R + rl < cnt) {
                 const unsigned o = toff + (unsigned)(i0 / R) * kstep + (unsigned)k * kstep;
                 zq[k] = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(zb + o));
-                if constexpr (RESID) sq[k] = *reinterpret_cast<const v4i *>(sb + o);
+                if constexpr (RESID && !USUM) sq[k] = *reinterpret_cast<const v4i *>(sb + o);
             }
         }
     };
@@ -300,8 +319,15 @@ __global__ __launch_bounds__(RESID_THREADS, 5) void k_resid_minmax16(const int16
         for (int k = 0; k < 4; ++k) {
             if (i0 + k * R + rl < cnt) {
                 int32_t v[8], s[8];
-                unpack8_i16(zq[k], v);
-                if constexpr (RESID) {
+                if constexpr (USUM) unpack8_u16(zq[k], v);
+                else unpack8_i16(zq[k], v);
+                if constexpr (RESID && USUM) {
+                    const unsigned o = toff + (unsigned)(i0 / R) * kstep + (unsigned)k * kstep;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[e] = resolve_u16(v[e], pv.lsh, pv.rsh, pv.so);
+                    const v2i a = pack4_i16(v[0], v[1], v[2], v[3]), b = pack4_i16(v[4], v[5], v[6], v[7]);
+                    *reinterpret_cast<v4i *>(ob + o) = v4i{a[0], a[1], b[0], b[1]};
+                } else if constexpr (RESID) {
                     unpack8_i16(sq[k], s);
                     const unsigned o = toff + (unsigned)(i0 / R) * kstep + (unsigned)k * kstep;
 #pragma unroll
@@ -535,6 +561,57 @@ __device__ __forceinline__ int32_t add_hh(uint32_t apk, uint32_t bpk) // sext(ha
         asm("v_add_u32_sdwa %0, sext(%1), sext(%2) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_0" : "=v"(r) : "v"(apk), "v"(bpk));
     else
         asm("v_add_u32_sdwa %0, sext(%1), sext(%2) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1" : "=v"(r) : "v"(apk), "v"(bpk));
+    return r;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The residual add's aligned sum as an unsigned 16-bit word (resid_fold).  Of the compute_best add
+// h = relu(add_cb_apply(z, skip)) (fxp_prims.hpp) only the result shift `post` depends on the batch-wide maximum; the operand
+// shifts shx, shy depend on the two operand exponents alone (s5fxp_kernels.hpp finalize_add_cb), and those the gate kernel
+// knows.  With 16-bit operands and skip >= 0 (a ReLU output)
+//     U = max(sat16(z << shx) + sat16(skip << shy), 0)   lies in [0, 65534]: a uint16, nothing lost, and
+//     h = min(shift(U, post), 32767)                     for every post in [-31, 15]
+// (the ReLU commutes with the floor shift and the clip; a negative sum shifted LEFT by more than 15 could wrap to a positive
+// int32, which is why the plan asks for res_exp >= 0: then post <= 15, s5fxp_fast.hpp plan_layers).  The gate kernel stores U
+// where z went; the residual pass and the decoder's fused residual read that one plane instead of z and skip.
+// tests/test_resid_fold.py runs tools/probe_resid_u16.hip: both helpers against add_cb_apply + ReLU on every operand pair.
+// ---------------------------------------------------------------------------------------------
+struct SumU16 {
+    // sat16(v << sh) as two clamped packed multiplies, by 2^min(sh, 14) and by 2^(sh > 14): a 16-bit value shifted left by 15 or
+    // more is already on its rail (or zero), so sh = 16 gives what sh = 15 gives; beyond 16 the reference's int32 shift wraps,
+    // which the plan excludes for every valid batch: 0 <= res_exp <= 16 is checked on the host, and the layer input's exponent
+    // is in [0, 15] unless a compute_best op chose a negative one -- that batch carries ST_NEGEXP, the caller raises on it
+    // (include/s5fxp.h) and its output, here as in the two-plane kernels, means nothing.  Both halves of a word
+    // hold the same multiplier; the gate kernel keeps the four words in LDS (it has no scalar register to spare)
+    uint32_t mz, mz2, ms, ms2;
+};
+__host__ __device__ __forceinline__ SumU16 sum_u16_setup(int shx, int shy)
+{
+    SumU16 p;
+    p.mz = 0x10001u << (shx < 14 ? shx : 14); p.mz2 = shx > 14 ? 0x20002u : 0x10001u;
+    p.ms = 0x10001u << (shy < 14 ? shy : 14); p.ms2 = shy > 14 ? 0x20002u : 0x10001u;
+    return p;
+}
+// the shifts finalize_add_cb will derive for x = z at res_exp and y = skip at skip_e
+__host__ __device__ __forceinline__ SumU16 sum_u16_setup_exps(int res_exp, int skip_e)
+{
+    const int ea = res_exp > skip_e ? res_exp : skip_e;
+    return sum_u16_setup(ea - res_exp, ea - skip_e);
+}
+__device__ __forceinline__ uint32_t pk_mul_sat(uint32_t a, uint32_t m) // sat16(a * m) per half
+{
+    uint32_t r;
+    asm("v_pk_mad_i16 %0, %1, %2, 0 clamp" : "=v"(r) : "v"(a), "v"(m));
+    return r;
+}
+// one int16 pair of z and of skip (skip >= 0) -> their U pair
+__device__ __forceinline__ uint32_t sum_u16_pair(const SumU16 &p, uint32_t z, uint32_t s)
+{
+    const uint32_t a = pk_mul_sat(pk_mul_sat(z, p.mz), p.mz2), b = pk_mul_sat(pk_mul_sat(s, p.ms), p.ms2);
+    // a + b >= 0 fits 16 unsigned bits, and max(a, -b) + b is max(a + b, 0) without the 17-bit intermediate
+    const uint32_t m = pk_max(a, pk_sub_sat(0u, b)); // (-b >= -32767: the clamp never acts)
+    uint32_t r;
+    asm("v_pk_add_u16 %0, %1, %2" : "=v"(r) : "v"(m), "v"(b));
     return r;
 }
 

@@ -851,10 +851,13 @@ __device__ int32_t g_store_sink[64];
 // h = relu(z + skip) (fxpmodel.py:1147-1159) is formed in registers -- the h plane is neither written nor read back
 // (-75 + 25 MB per batch at configs[1]) and the forward is one launch shorter.  The residual exponents come from the
 // maxima the gate kernel left, derived by every workgroup for itself as in the B projection.
+// usum (s5fxp_fast.hpp LayerPlan::resid_fold): the gate kernel stored the add's aligned sum U (mfma_bn.hpp SumU16) in z's place;
+// a.x is that plane, the only one read (25 MB per batch instead of 50), and h = resolve_u16(U).
 struct DecResid {
     const int16_t *z;
     ResidHead hd;
     int32_t res_bits, skip_bits;
+    int32_t usum;
 };
 template <int KS, bool RESID = false>
 __global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_p(DecArgs a, DecResid rz, GroupOff go)
@@ -870,6 +873,7 @@ __global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_p(DecArgs
     // H: the real channels (row stride, vectors per frame); HP: the k extent of the byte planes (shape_channels)
     constexpr int H = shape_channels(KS), HP = 32 * KS, FT = 64, KP = HP + 16, NW = 6, CT = 9, CPW = 3;
     constexpr int VPF = H / 8, NV = FT * VPF / 384;
+    constexpr bool USUM = RESID && KS == 3; // the one-plane route exists where the 32-frame gate kernel does: H = 96 (DecResid::usum)
     static_assert(FT * VPF % 384 == 0, "tile shape");
     extern __shared__ __attribute__((aligned(16))) int8_t smem[];
     int8_t *Xh = smem, *Xl = Xh + FT * KP;
@@ -924,7 +928,7 @@ __global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_p(DecArgs
             const int64_t left = a.N - tl * FT; // frames from the tile's first to the end of the tensor (wave-uniform)
             int f = v / VPF;
             f = f < left ? f : (int)left - 1;
-            if constexpr (RESID)
+            if (RESID && !(USUM && rz.usum))
                 rawz[i] = gload16_hidden(reinterpret_cast<const char *>(rz.z + tl * FT * H), 2u * (unsigned)(f * H + 8 * (v % VPF)));
             // issued behind the compiler's back (see vm_wait): its wait-count pass would otherwise guard the first use of
             // these registers, a tile later, with vmcnt(0) -- behind the 48 stores of this tile's phase B
@@ -939,13 +943,19 @@ __global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_p(DecArgs
         // the prefetched rows are older than the previous tile's 3 x 16 stores per wave (every tile but the tensor's last is
         // full and stores unconditionally; that last one has no successor)
         vm_wait<3 * 16>(raw);
-        if constexpr (RESID) vm_wait<3 * 16>(rawz);
+        if (RESID && !(USUM && rz.usum)) vm_wait<3 * 16>(rawz);
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int v = threadIdx.x + 384 * i, f = v / VPF, og = v % VPF;
             int32_t x[8];
-            unpack8_i16(raw[i], x);
-            if constexpr (RESID) {
+            if (USUM && rz.usum) {
+                unpack8_u16(raw[i], x);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) x[e] = resolve_u16(x[e], rpv.lsh, rpv.rsh, rpv.so);
+            } else if constexpr (!RESID) {
+                unpack8_i16(raw[i], x);
+            } else {
+                unpack8_i16(raw[i], x);
                 int32_t z[8];
                 unpack8_i16(rawz[i], z);
 #pragma unroll
@@ -1033,6 +1043,7 @@ __global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_pf(DecArg
     // H: the real channels (row stride, vectors per frame); HP: the k extent of the byte planes (shape_channels)
     constexpr int H = shape_channels(KS), HP = 32 * KS, FT = 64, KP = HP + 16, NW = 6, CT = 9, CPW = 3;
     constexpr int VPF = H / 8, NV = FT * VPF / 384;
+    constexpr bool USUM = RESID && KS == 3; // the one-plane route exists where the 32-frame gate kernel does: H = 96 (DecResid::usum)
     static_assert(FT * VPF % 384 == 0, "tile shape");
     extern __shared__ __attribute__((aligned(16))) int8_t smem[];
     int8_t *Xh = smem, *Xl = Xh + FT * KP;
@@ -1087,7 +1098,7 @@ __global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_pf(DecArg
             const int64_t left = a.N - tl * FT; // frames from the tile's first to the end of the tensor (wave-uniform)
             int f = v / VPF;
             f = f < left ? f : (int)left - 1;
-            if constexpr (RESID)
+            if (RESID && !(USUM && rz.usum))
                 rawz[i] = gload16_hidden(reinterpret_cast<const char *>(rz.z + tl * FT * H), 2u * (unsigned)(f * H + 8 * (v % VPF)));
             // issued behind the compiler's back (see vm_wait): its wait-count pass would otherwise guard the first use of
             // these registers, a tile later, with vmcnt(0) -- behind the 48 stores of this tile's phase B
@@ -1102,13 +1113,19 @@ __global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_pf(DecArg
         // the prefetched rows are older than the previous tile's 3 x 16 stores per wave (every tile but the tensor's last is
         // full and stores unconditionally; that last one has no successor)
         vm_wait<3 * 16>(raw);
-        if constexpr (RESID) vm_wait<3 * 16>(rawz);
+        if (RESID && !(USUM && rz.usum)) vm_wait<3 * 16>(rawz);
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int v = threadIdx.x + 384 * i, f = v / VPF, og = v % VPF;
             int32_t x[8];
-            unpack8_i16(raw[i], x);
-            if constexpr (RESID) {
+            if (USUM && rz.usum) {
+                unpack8_u16(raw[i], x);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) x[e] = resolve_u16(x[e], rpv.lsh, rpv.rsh, rpv.so);
+            } else if constexpr (!RESID) {
+                unpack8_i16(raw[i], x);
+            } else {
+                unpack8_i16(raw[i], x);
                 int32_t z[8];
                 unpack8_i16(rawz[i], z);
 #pragma unroll

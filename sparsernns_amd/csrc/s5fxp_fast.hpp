@@ -361,6 +361,7 @@ struct LayerPlan {
     bool pk16;        // packed int16 epilogues of the gate kernel (mfma_fused.hpp PK16)
     bool gate_bn;     // the gate kernel recomputes u (S5FXP_GATE_BN)
     bool gate_urec;   // the 32-frame gate kernel rebuilds u in its tile staging (k_cgate_p<.., UREC>; off: S5FXP_GATE_BN=0)
+    bool resid_fold;  // the gate kernel stores the residual add's aligned sum U, its consumer reads that one plane (FusedForward::plan_layers)
     GateForm gate;
     const MfmaW *w_bproj, *w_cre, *w_cim; // full or compacted; w_bproj: the pair-ordered packing on the pair rungs
     const int32_t *a_re, *a_im;           // Lambda_bar of the slots
@@ -451,23 +452,33 @@ inline auto bproj_traced_kernel(const FastShape &sh)
 
 // k_cgate_p<KS, NT, false, S16, DIRECT, FTP, false, PAIR, PK16, GBN, UREC> of an untraced, inexact layer in its gate form: the
 // 32-frame (with or without UREC) and GBN forms exist for the packed epilogues (PK16) at H = 96 only (FastShape::gate32)
-template <bool S16, bool DIR, bool PAIR, bool PK16> auto cgate_kernel(const LayerPlan &p, const FastShape &sh)
+// (k_cgate_p has two overloads, told apart by the argument block: the pointer type names the one that is meant)
+using GateKernel = void (*)(const CGateArgs, GroupOff);
+using GateFoldKernel = void (*)(const CGateFoldArgs, GroupOff);
+template <bool S16, bool DIR, bool PAIR, bool PK16> GateKernel cgate_kernel(const LayerPlan &p, const FastShape &sh)
 {
-    return nt_kernel(sh.nt, [&](auto n) {
+    return nt_kernel(sh.nt, [&](auto n) -> GateKernel {
         constexpr int NT = decltype(n)::value;
         if constexpr (PK16 && NT == 3) {
             if (p.gate == GATE_FT32 && p.gate_urec)
-                return ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 32, false, PAIR, true, false, true>; });
+                return ks_kernel<3>(p.ks, [](auto k) -> GateKernel { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 32, false, PAIR, true, false, true>; });
             if (p.gate == GATE_FT32)
-                return ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 32, false, PAIR, true>; });
+                return ks_kernel<3>(p.ks, [](auto k) -> GateKernel { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 32, false, PAIR, true>; });
             if (p.gate == GATE_GBN)
-                return ks_kernel<3>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 64, false, PAIR, true, true>; });
+                return ks_kernel<3>(p.ks, [](auto k) -> GateKernel { return k_cgate_p<decltype(k)::value, 3, false, S16, DIR, 64, false, PAIR, true, true>; });
         }
-        return ks_kernel<NT>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, NT, false, S16, DIR, 64, false, PAIR, PK16>; });
+        return ks_kernel<NT>(p.ks, [](auto k) -> GateKernel { return k_cgate_p<decltype(k)::value, NT, false, S16, DIR, 64, false, PAIR, PK16>; });
     });
 }
+// the UREC kernel that stores the aligned sum (mfma_fused.hpp FOLD): gate_urec implies H = 96, PK16 and with it S16 and DIRECT
+inline GateFoldKernel gate_fold_kernel(const LayerPlan &p)
+{
+    if (p.rung.pair)
+        return ks_kernel<3>(p.ks, [](auto k) -> GateFoldKernel { return k_cgate_p<decltype(k)::value, 3, false, true, true, 32, false, true, true, false, true>; });
+    return ks_kernel<3>(p.ks, [](auto k) -> GateFoldKernel { return k_cgate_p<decltype(k)::value, 3, false, true, true, 32, false, false, true, false, true>; });
+}
 // ... for the seven (S16, DIRECT, PAIR, PK16) a plan can hold (PK16 needs DIRECT; DIRECT and PAIR need S16)
-auto gate_kernel(const LayerPlan &p, const FastShape &sh)
+GateKernel gate_kernel(const LayerPlan &p, const FastShape &sh)
 {
     const bool pair = p.rung.pair;
     return p.pk16 && pair   ? cgate_kernel<true, true, true, true>(p, sh)
@@ -479,18 +490,18 @@ auto gate_kernel(const LayerPlan &p, const FastShape &sh)
                             : cgate_kernel<false, false, false, false>(p, sh);
 }
 // the exact gate kernel (k_cgate_p<.., WIDE>): the in-forward re-run and S5FXP_FWD_EXACT; traced: every state slot
-inline auto gate_exact_kernel(const LayerPlan &p, const FastShape &sh, bool traced)
+inline GateKernel gate_exact_kernel(const LayerPlan &p, const FastShape &sh, bool traced)
 {
-    return nt_kernel(sh.nt, [&](auto n) {
+    return nt_kernel(sh.nt, [&](auto n) -> GateKernel {
         constexpr int NT = decltype(n)::value;
         constexpr int KSF = NT == 2 ? 1 : NT == 3 ? 2 : NT == 5 ? 3 : 4; // all of the shape's states
         if (traced) return k_cgate_p<KSF, NT, true, false, false, 64, true>;
-        return ks_kernel<NT>(p.ks, [](auto k) { return k_cgate_p<decltype(k)::value, NT, false, false, false, 64, true>; });
+        return ks_kernel<NT>(p.ks, [](auto k) -> GateKernel { return k_cgate_p<decltype(k)::value, NT, false, false, false, 64, true>; });
     });
 }
-inline auto gate_traced_kernel(const FastShape &sh)
+inline GateKernel gate_traced_kernel(const FastShape &sh)
 {
-    return nt_kernel(sh.nt, [](auto n) {
+    return nt_kernel(sh.nt, [](auto n) -> GateKernel {
         constexpr int NT = decltype(n)::value;
         constexpr int KSF = NT == 2 ? 1 : NT == 3 ? 2 : NT == 5 ? 3 : 4;
         return k_cgate_p<KSF, NT, true>;
@@ -572,7 +583,23 @@ struct FusedForward {
     std::array<LayerPlan, 15> plan_layers() const
     {
         std::array<LayerPlan, 15> p{};
-        for (int li = 0; li < m->n_layers; ++li) p[li] = plan_layer(m, li, fwd_flags, traces != nullptr, state_in || state_out, fold);
+        for (int li = 0; li < m->n_layers; ++li) {
+            p[li] = plan_layer(m, li, fwd_flags, traces != nullptr, state_in || state_out, fold);
+            // resid_fold: of the residual add h = relu(z + skip), a compute_best op, only the result shift waits
+            // for the batch-wide maximum; the operand shifts follow from res_exp and the layer input's exponent, which the gate
+            // kernel reads anyway.  Where it rebuilds u in its staging (gate_urec) it holds z(t) and skip(t) side by side when z
+            // leaves the tile, and stores U = max(sat16(z << shx) + sat16(skip << shy), 0) in z's place (mfma_bn.hpp SumU16): a
+            // uint16 that loses nothing when both operands are 16 bit and skip >= 0 (the layer input is a ReLU output).  The
+            // residual pass (k_resid_minmax16<true, true>) or the decoder's fused residual then read ONE plane and shift it.
+            // Conditions: a deferred forward (the in-forward exact re-run would store a plain z), no traces and no multi-rank
+            // hook (both implied by gate_urec: pk16 needs !traced, fold needs !allreduce), 0 <= res_exp <= 16 (then post <= 15,
+            // so a negative sum cannot wrap to a positive value in the result shift, and the operand shifts are <= 16, so
+            // the reference's int32 shift of a 16-bit operand does not wrap either).  A model created with S5FXP_MODEL_NO_RESID_FOLD keeps the
+            // two-plane kernels (the A/B partner).
+            const int in_bits = li ? m->layers[li - 1].res_bits : m->enc.out_bits;
+            p[li].resid_fold = p[li].gate_urec && defer && !traces && fold && m->layers[li].res_bits == 16 && in_bits == 16 &&
+                               m->layers[li].res_exp >= 0 && m->layers[li].res_exp <= 16 && !(m->flags & S5FXP_MODEL_NO_RESID_FOLD);
+        }
         return p;
     }
     int16_t *I16(size_t off) const { return reinterpret_cast<int16_t *>(ws + off); }
@@ -804,7 +831,11 @@ struct FusedForward {
         } else if (p.gate == GATE_FT32) {
             const size_t smem32 = 5 * HP * 4 + 32 + sig_lds + 2 * 32 * (size_t)(2 * p.P + 16) + 2 * 32 * (HP + 16) + 192 +
                                   2 * 32 * (2 * HP + 8);
-            launch(gate_kernel(p, sh), grid_gate32, 192, smem32, gev0, gev1, a);
+            if (p.resid_fold) {
+                CGateFoldArgs fa{};
+                static_cast<CGateArgs &>(fa) = a;
+                launch(gate_fold_kernel(p), grid_gate32, 192, smem32, gev0, gev1, fa);
+            } else launch(gate_kernel(p, sh), grid_gate32, 192, smem32, gev0, gev1, a);
         } else {
             // phase-split fused kernel (mfma_fused.hpp): six waves per workgroup, 64-frame tiles, no weights in LDS
             const size_t smem = 5 * HP * 4 + 32 + sig_lds + 2 * 64 * (size_t)(2 * p.P + 16) + 2 * 64 * (HP + 16) + 192 +
@@ -865,7 +896,9 @@ struct FusedForward {
         if (bn_ext) {
             const bool more = li + 1 < m->n_layers;
             const int ext_reps = (more && fold) ? EXT_REPS : 1; // the next layer's B projection derives its exponents from the extremes
-            launch(k_resid_minmax16<true>, rm_grid, RESID_THREADS, 0, nullptr, nullptr, (const int16_t *)I16(w.z), (const int16_t *)h, hn,
+            // (resid_fold: the z plane holds U and the pass reads nothing else)
+            launch(layer[li].resid_fold ? k_resid_minmax16<true, true> : k_resid_minmax16<true, false>, rm_grid, RESID_THREADS, 0,
+                   nullptr, nullptr, (const int16_t *)I16(w.z), (const int16_t *)h, hn,
                    tr ? tr->residadd : nullptr, N, H, rm_span, l.res_bits, hb, resid_head(li), more ? ext(li + 1) : nullptr, ext_reps,
                    status);
         } else {
@@ -891,6 +924,10 @@ struct FusedForward {
             const LayerDev &l = m->layers[dec_resid];
             dz.z = I16(w.z); dz.res_bits = l.res_bits; dz.skip_bits = hb; dz.hd = resid_head(dec_resid);
             a.xb = l.res_bits;
+            if (layer[dec_resid].resid_fold) { // the z plane holds U: the one plane the decoder reads
+                dz.usum = 1;
+                a.x = I16(w.z);
+            }
         }
         const size_t smem = 2 * 64 * (size_t)(sh.hp + 16);
         // 192 channels: 2 x 4 vectors of prefetch, one workgroup per CU
