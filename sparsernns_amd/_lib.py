@@ -28,7 +28,7 @@ STATUS_WORDS = 128
 PATH_GENERIC, PATH_FUSED, PATH_STEP = 1, 2, 3   # status[2]
 STEP_MAX_ROWS = 32
 STREAM_MAX_HOPS = 32
-MODEL_DEFAULT, MODEL_FORCE_DENSE, MODEL_FORCE_CSR, MODEL_FORCE_GENERIC, MODEL_NO_RESID_FOLD = 0, 1, 2, 4, 8
+MODEL_DEFAULT, MODEL_FORCE_DENSE, MODEL_FORCE_CSR, MODEL_FORCE_GENERIC, MODEL_NO_RESID_FOLD, MODEL_NO_RESID_LAZY = 0, 1, 2, 4, 8, 16
 
 
 class DenseDesc(C.Structure):

@@ -616,6 +616,166 @@ __device__ __forceinline__ uint32_t sum_u16_pair(const SumU16 &p, uint32_t z, ui
 }
 
 // ---------------------------------------------------------------------------------------------
+// resid_lazy: between two layers the U plane IS the layer input.  The residual pass stores nothing; the next
+// layer's B projection and gate kernel load U and shift it themselves, with the result shift the pass published in the
+// producer layer's LayerDyn::res.  U -> h is resolve_u16 above: min(shift(U, post), 32767) for post in [-31, 15], monotone
+// non-decreasing in U, so the per-channel extremes of h are resolve_u16 of the per-channel extremes of U.
+// On a uint16 pair: a logical right shift by -post (a shift of 16 or more leaves zero: the multiplier m1 is 0 then, the
+// packed shift takes its count modulo 16), the clip min(., 32767) as an unsigned minimum -- after it both halves are
+// non-negative int16 -- and a left shift as two clamped multiplies, by 2^min(post, 14) and by 2^(post > 14), which saturate
+// at 32767 as the clip does.  RES_RIGHT (-15 <= post <= 0): the shift and the minimum are all there is.
+// tests/test_resid_lazy.py runs tools/probe_resolve_u16.hip: every U x every post against resolve_u16, both halves.
+// ---------------------------------------------------------------------------------------------
+enum { RES_GENERIC = 0, RES_RIGHT = 1 };
+struct ResolveU16 {
+    uint32_t shr, m1, m2; // -post mod 16, 2^min(post, 14) or 0, 2^(post > 14): the same in both halves
+    int32_t arm;
+};
+__host__ __device__ __forceinline__ ResolveU16 resolve_u16_setup(int post)
+{
+    const int lsh = post > 0 ? post : 0, rsh = post < 0 ? -post : 0;
+    ResolveU16 p;
+    p.shr = 0x10001u * (uint32_t)(rsh & 15);
+    p.m1 = rsh > 15 ? 0u : 0x10001u << (lsh < 14 ? lsh : 14);
+    p.m2 = lsh > 14 ? 0x20002u : 0x10001u;
+    p.arm = lsh == 0 && rsh <= 15 ? RES_RIGHT : RES_GENERIC;
+    return p;
+}
+__device__ __forceinline__ uint32_t pk_lshr(uint32_t a, uint32_t s) // logical, s = shift in both halves
+{
+    uint32_t r;
+    asm("v_pk_lshrrev_b16 %0, %1, %2" : "=v"(r) : "v"(s), "v"(a));
+    return r;
+}
+__device__ __forceinline__ uint32_t pk_min_u(uint32_t a, uint32_t b)
+{
+    uint32_t r;
+    asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ uint32_t pk_max_u(uint32_t a, uint32_t b)
+{
+    uint32_t r;
+    asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// one uint16 pair of U -> its h pair (int16, >= 0)
+template <int ARM = RES_GENERIC>
+__device__ __forceinline__ uint32_t resolve_u16_pair(const ResolveU16 &p, uint32_t u)
+{
+    const uint32_t t = pk_min_u(pk_lshr(u, p.shr), 0x7fff7fffu);
+    if constexpr (ARM == RES_RIGHT) return t;
+    else return pk_mul_sat(pk_mul_sat(t, p.m1), p.m2);
+}
+
+// The residual pass of a lazy layer: a read-only reduction over the U plane.  Head as in k_resid_minmax16 above (the residual
+// add's exponent; workgroup 0 publishes it, and with it the shift the consumers of the plane use); body: packed unsigned
+// running extremes of the thread's eight channels, nothing stored; tail: the folded extremes of U go through resolve_u16 and
+// into the replicas as the extremes of h.  Same threads, spans and grid as the storing form.  It is an overload on the
+// argument block, not a third template argument (the launch list of a forward names k_resid_minmax16<true, true>).
+struct ResidLazyArgs {
+    const int16_t *u; // (N,H) uint16: the gate kernel's aligned sum
+    int64_t N, span;
+    int32_t H, res_bits;
+    ResidHead hd;
+    float *ext;
+    int32_t ext_reps;
+    int32_t *status;
+};
+template <bool RESID, bool USUM>
+__global__ __launch_bounds__(RESID_THREADS, 5) void k_resid_minmax16(ResidLazyArgs a, GroupOff go)
+{
+    static_assert(RESID && USUM, "the read-only pass exists for the one-plane residual add");
+    const int64_t gws = (int64_t)blockIdx.y * go.ws, gst = (int64_t)blockIdx.y * go.status;
+    const int16_t *__restrict__ u = reinterpret_cast<const int16_t *>(reinterpret_cast<const char *>(a.u) + gws);
+    ResidHead hd = a.hd;
+    float *ext = a.ext;
+    int32_t *status = a.status;
+    gshift(ext, gws); gshift_nn(hd.d, gws); gshift(hd.skip_e.dyn, gws); gshift_nn(hd.status_exps, gst); gshift_nn(status, gst);
+    __shared__ uint32_t smin[RESID_THREADS * 4], smax[RESID_THREADS * 4]; // packed pairs: [thread][pair]
+    __shared__ AddCb sp;
+    const int H = a.H, G = H >> 3, R = RESID_THREADS / G;
+    const int g = threadIdx.x % G, rl = threadIdx.x / G;
+    const int64_t lo_n = (int64_t)blockIdx.x * a.span;
+    const int cnt = rl < R ? (int)((lo_n + a.span < a.N ? lo_n + a.span : a.N) - lo_n) : 0;
+    const char *ub = reinterpret_cast<const char *>(u + lo_n * H);
+    const unsigned rowb = 2u * (unsigned)H, toff = (unsigned)rl * rowb + 16u * (unsigned)g, kstep = (unsigned)R * rowb;
+    auto fetch = [&](v4i(&q)[4], int i0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i0 + k * R + rl < cnt)
+                q[k] = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(ub + toff + (unsigned)(i0 / R) * kstep + (unsigned)k * kstep));
+    };
+    v4i qa[4];
+    const int step = 4 * R;
+    if (rl < cnt) fetch(qa, 0);
+    AddCb p{};
+    if (hd.enable) {
+        if (threadIdx.x == 0) {
+            sp = finalize_add_cb(hd.d->mx + (hd.d->redo ? hd.redo_slot : 8), hd.res_exp, hd.skip_e.get(), a.res_bits, status);
+            if (blockIdx.x == 0) {
+                hd.d->res = sp;
+                hd.status_exps[4] = sp.eo;
+            }
+        }
+        __syncthreads();
+        p = sp;
+    } else {
+        p = hd.d->res;
+    }
+    uint32_t lo[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[4] = {0u, 0u, 0u, 0u};
+    for (int i0 = 0; i0 + rl < cnt; i0 += step) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (i0 + k * R + rl < cnt) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    lo[e] = pk_min_u(lo[e], (uint32_t)qa[k][e]);
+                    hi[e] = pk_max_u(hi[e], (uint32_t)qa[k][e]);
+                }
+            }
+        }
+        if (i0 + step + rl < cnt) fetch(qa, i0 + step);
+    }
+    if (!ext) return;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        smin[threadIdx.x * 4 + e] = lo[e];
+        smax[threadIdx.x * 4 + e] = hi[e];
+    }
+    __syncthreads();
+    {
+        // fold the R frame lanes: one thread per (bound, channel) -- two per item at H = 96, each folding half the lanes
+        const int items = 2 * H, parts = RESID_THREADS / items > 1 ? 2 : 1, per = R / parts;
+        const int item = threadIdx.x % items, part = threadIdx.x / items;
+        const bool is_max = item >= H;
+        const int c = is_max ? item - H : item;
+        int32_t v = is_max ? 0 : 65535;
+        if (part < parts) {
+            const uint16_t *src = reinterpret_cast<const uint16_t *>(is_max ? smax : smin);
+            for (int r = part * per; r < (part + 1) * per; ++r) {
+                const int32_t t = src[r * G * 8 + c];
+                v = is_max ? max(v, t) : min(v, t);
+            }
+        }
+        __syncthreads();
+        if (parts == 2 && part == 1) smin[item] = (uint32_t)v; // the arrays are free now
+        __syncthreads();
+        if (part == 0) {
+            if (parts == 2) {
+                const int32_t t = (int32_t)smin[item];
+                v = is_max ? max(v, t) : min(v, t);
+            }
+            // the extremes of h: the shift and the clip are monotone in U
+            v = resolve_u16(v, p.post > 0 ? p.post : 0, p.post < 0 ? -p.post : 0, sat_bounds(a.res_bits));
+            const int rep = a.ext_reps > 1 ? (int)(blockIdx.x % a.ext_reps) : 0;
+            atomicMax(reinterpret_cast<uint32_t *>(ext) + rep * 2 * H + item,
+                      __float_as_uint(is_max ? EXT_BIAS + (float)v : EXT_BIAS - (float)v));
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // The same chain in ROW layout, for a kernel whose threads hold 16-byte row vectors (eight consecutive channels of one frame
 // as int16) and always the SAME eight channels: the gate kernel's tile staging (mfma_fused.hpp k_cgate_p<.., UREC>), which
 // rebuilds the SSM input u from the layer input instead of reading the plane the B projection would have stored.  The
@@ -739,6 +899,9 @@ struct BprojM2Args {
     const float *ext;
     int32_t ext_reps;
     int32_t *status, *status_exps;
+    // != nullptr (resid_lazy): x is the previous layer's U plane (uint16) and this is that layer's LayerDyn, whose res.post
+    // shifts it: the row vectors go through resolve_u16_pair before the BatchNorm chain
+    const LayerDyn *lazy;
 };
 
 } // namespace s5

@@ -106,6 +106,16 @@ constexpr int SIGTAB_WORDS = 2 * 7 * 64; // sig_x <= 6 on this path (host-checke
 constexpr int SIGDIR_MAX_BITS = 12, SIGDIR_BYTES = 2 << SIGDIR_MAX_BITS;
 __host__ __device__ __forceinline__ int sigdir_lds_bytes(int bits) { return ((2 << bits) + 15) & ~15; }
 
+// The argument block of the k_cgate_p overload that stores the aligned sum (FOLD below).
+// skip_dyn != nullptr (resid_lazy): `skip` is the previous layer's U plane, not its shifted copy, and this is
+// that layer's LayerDyn: every skip row vector goes through resolve_u16_pair (mfma_bn.hpp) with its res.post before it feeds
+// bn16_row8 and the skip tile, so that everything downstream sees the layer input as before.
+struct CGateFoldArgs : CGateArgs {
+    const LayerDyn *skip_dyn;
+};
+__device__ __forceinline__ const LayerDyn *skip_dyn_of(const CGateArgs &) { return nullptr; }
+__device__ __forceinline__ const LayerDyn *skip_dyn_of(const CGateFoldArgs &a) { return a.skip_dyn; }
+
 // S16: the state stream holds int16, written with saturation by k_scan_quad_asm16 (a.xmax <= 32766 then: a saturated
 // state fails the range check like any other state beyond the bound)
 // DIRECT: the sigmoid input xx = gq >> (out_exp - sig_x) has only out_bits - (out_exp - sig_x) <= 12 bits, so r is read
@@ -162,7 +172,6 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT == 3 && KS == 1 && !WIDE ? S5_CGAT
 // The same kernel storing the aligned sum U in z's place (FOLD above).  It is told apart by its argument block, not by a
 // template argument: the template arguments stay the eleven every k_cgate_p has.  One body, compiled into both (the kernels
 // that do not fold keep their code as it was).
-struct CGateFoldArgs : CGateArgs {};
 template <int KS, int NT, bool TRACE, bool S16, bool DIRECT, int FTP, bool WIDE, bool PAIR, bool PK16, bool GBN, bool UREC>
 __global__ __launch_bounds__(FTP * 2 * NT, NT == 3 && KS == 1 && !WIDE ? S5_CGATE_LB : 3) void k_cgate_p(const CGateFoldArgs a_k, GroupOff go)
 {

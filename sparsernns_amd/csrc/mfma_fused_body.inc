@@ -89,8 +89,23 @@
         if (threadIdx.x == 0) {
             const SumU16 us = sum_u16_setup_exps(a.res_exp, skip_e);
             *reinterpret_cast<v4i *>(red + 8) = v4i{(int)us.mz, (int)us.mz2, (int)us.ms, (int)us.ms2};
+            // resid_lazy: `skip` is the previous layer's U plane; the words that shift it into the layer input (mfma_bn.hpp
+            // ResolveU16) sit beside the four above, [3] != 0 says that there is something to shift
+            const LayerDyn *sd = skip_dyn_of(a_k);
+            gshift(sd, (int64_t)blockIdx.y * go.ws);
+            const ResolveU16 rz = resolve_u16_setup(sd ? sd->res.post : 0);
+            *reinterpret_cast<v4i *>(red + 12) = v4i{(int)rz.shr, (int)rz.m1, (int)rz.m2, sd ? 1 : 0};
         }
     }
+    // FOLD: a row vector of `skip` as the layer input h (a plain row unless the layer input is lazy)
+    auto resolve_skip = [&](v4i &sv) {
+        const v4i rw = *reinterpret_cast<const v4i *>(red + 12);
+        if (__builtin_amdgcn_readfirstlane(rw[3])) {
+            const ResolveU16 rz{(uint32_t)rw[0], (uint32_t)rw[1], (uint32_t)rw[2], RES_GENERIC};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) sv[q] = (int)resolve_u16_pair<RES_GENERIC>(rz, (uint32_t)sv[q]);
+        }
+    };
     const int sx = a.sig_x, S = 1 << sx;
     // out2 input conversion (fxpmodel.py:335-347) as uniform shift/clip operands; identity when not needed
     const int cv_l = a.conv && a.inp_exp > a.y_exp ? a.inp_exp - a.y_exp : 0, cv_r = a.conv && a.y_exp > a.inp_exp ? a.y_exp - a.inp_exp : 0;
@@ -235,6 +250,7 @@
                 if constexpr (FOLD) fold_z(z0, z1, cs_);
                 if (f < nvalid_prev) *reinterpret_cast<v4i *>(zb_prev + 2u * (unsigned)(f * H + 8 * og)) = v4i{z0[0], z0[1], z1[0], z1[1]};
             }
+            if constexpr (FOLD) resolve_skip(srow[i]);
             const v4i uv = bn16_row8<ARM>(brow, srow[i]);
             *reinterpret_cast<v2i *>(cu) = v2i{uv[0], uv[1]};
             *reinterpret_cast<v2i *>(cu + 8) = v2i{uv[2], uv[3]};

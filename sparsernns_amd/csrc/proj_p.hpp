@@ -203,6 +203,19 @@ __global__ __launch_bounds__(64 * NT, TRACE ? 2 : KS == 5 ? 3 : 4) void k_bproj_
                                                    blockIdx.x == 0)
                              : *a.bn.dyn;
     const Bn16 bn = bn16_setup(a.bn, d, tab, H);
+    // resid_lazy (mfma_bn.hpp ResolveU16): the rows are the previous layer's aligned sum U; that layer's residual pass has
+    // published the shift that makes them the layer input.  0: plain rows; otherwise 1 + the arm, chosen once per workgroup
+    // (the route exists where the gate kernel that stores U does: H = 96; the other shapes keep their code)
+    constexpr bool LAZY = KS == 3 && !TRACE;
+    ResolveU16 rz{};
+    int lazy_arm = 0;
+    if constexpr (LAZY) {
+        if (a.lazy) {
+            gshift_nn(a.lazy, (int64_t)blockIdx.y * go.ws);
+            rz = resolve_u16_setup(a.lazy->res.post);
+            lazy_arm = 1 + rz.arm;
+        }
+    }
     __syncthreads();
 
     prologue_loads_done();
@@ -218,6 +231,15 @@ __global__ __launch_bounds__(64 * NT, TRACE ? 2 : KS == 5 ? 3 : 4) void k_bproj_
             const int v = threadIdx.x + NTHR * i, f = v / VPF, og = v % VPF;
             const int64_t n = n0 + f;
             int32_t xin[8], t[8], u[8];
+            if constexpr (LAZY) {
+                if (lazy_arm == 1 + RES_RIGHT) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) raw[i][e] = (int)resolve_u16_pair<RES_RIGHT>(rz, (uint32_t)raw[i][e]);
+                } else if (lazy_arm) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) raw[i][e] = (int)resolve_u16_pair<RES_GENERIC>(rz, (uint32_t)raw[i][e]);
+                }
+            }
             unpack8_i16(raw[i], xin);
             bn16_x4(bn, reinterpret_cast<const int32_t(&)[4]>(xin[0]), 8 * og, reinterpret_cast<int32_t(&)[4]>(t[0]),
                     reinterpret_cast<int32_t(&)[4]>(u[0]));

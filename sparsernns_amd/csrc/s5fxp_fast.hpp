@@ -362,6 +362,7 @@ struct LayerPlan {
     bool gate_bn;     // the gate kernel recomputes u (S5FXP_GATE_BN)
     bool gate_urec;   // the 32-frame gate kernel rebuilds u in its tile staging (k_cgate_p<.., UREC>; off: S5FXP_GATE_BN=0)
     bool resid_fold;  // the gate kernel stores the residual add's aligned sum U, its consumer reads that one plane (FusedForward::plan_layers)
+    bool resid_lazy;  // ... and between this layer and the next nobody stores the shifted sum: the U plane is the next layer's input
     GateForm gate;
     const MfmaW *w_bproj, *w_cre, *w_cim; // full or compacted; w_bproj: the pair-ordered packing on the pair rungs
     const int32_t *a_re, *a_im;           // Lambda_bar of the slots
@@ -455,6 +456,10 @@ inline auto bproj_traced_kernel(const FastShape &sh)
 // (k_cgate_p has two overloads, told apart by the argument block: the pointer type names the one that is meant)
 using GateKernel = void (*)(const CGateArgs, GroupOff);
 using GateFoldKernel = void (*)(const CGateFoldArgs, GroupOff);
+// (k_resid_minmax16 likewise: the storing pass and the read-only one of a lazy layer, mfma_bn.hpp ResidLazyArgs)
+using ResidKernel = void (*)(const int16_t *, const int16_t *, int16_t *, int32_t *, int64_t, int, int64_t, int, int, ResidHead, float *, int,
+                             int32_t *, GroupOff);
+using ResidLazyKernel = void (*)(ResidLazyArgs, GroupOff);
 template <bool S16, bool DIR, bool PAIR, bool PK16> GateKernel cgate_kernel(const LayerPlan &p, const FastShape &sh)
 {
     return nt_kernel(sh.nt, [&](auto n) -> GateKernel {
@@ -577,6 +582,11 @@ struct FusedForward {
 
     // the current layer input: its plane, the other one of the ping-pong pair, its bits and (device) exponent
     int16_t *h = I16(w.hA), *hn = I16(w.hB);
+    // the plane the gate kernel writes (z, or the aligned sum U).  Behind a lazy layer (LayerPlan::resid_lazy) that plane IS the
+    // next layer input -- uint16, shifted on load with *h_lazy, the LayerDyn of the layer that produced it -- and the plane
+    // that held the layer input until then, dead once the gate kernel has run, takes the next gate kernel's output
+    int16_t *zp = I16(w.z);
+    const LayerDyn *h_lazy = nullptr;
     int hb = m->enc.out_bits;
     DynExp he{m->enc.out_exp, nullptr};
 
@@ -600,6 +610,15 @@ struct FusedForward {
             p[li].resid_fold = p[li].gate_urec && defer && !traces && fold && m->layers[li].res_bits == 16 && in_bits == 16 &&
                                m->layers[li].res_exp >= 0 && m->layers[li].res_exp <= 16 && !(m->flags & S5FXP_MODEL_NO_RESID_FOLD);
         }
+        // resid_lazy: U -> h is one shift and one clip (mfma_bn.hpp resolve_u16), and only the shift is late --
+        // the residual pass publishes it in LayerDyn::res before either reader of h starts.  So between two layers that both
+        // fold, the pass stores nothing (it still gathers the extremes: the map is monotone, the extremes of h are the resolved
+        // extremes of U) and the next layer's B projection and gate kernel shift U as they load it.  The next layer must be one
+        // whose kernels can: the MFMA B projection that derives its exponents from the extremes and the gate kernel that
+        // rebuilds u -- what gives it its own resid_fold.  The last layer's U goes to the decoder as before.  A model created
+        // with S5FXP_MODEL_NO_RESID_LAZY keeps the storing pass (the A/B partner).
+        for (int li = 0; li + 1 < m->n_layers; ++li)
+            p[li].resid_lazy = p[li].resid_fold && p[li + 1].resid_fold && !(m->flags & S5FXP_MODEL_NO_RESID_LAZY);
         return p;
     }
     int16_t *I16(size_t off) const { return reinterpret_cast<int16_t *>(ws + off); }
@@ -714,6 +733,7 @@ struct FusedForward {
             a.ext = ext(li);
             a.ext_reps = EXT_REPS; a.status = status; a.status_exps = status_exps(li);
         }
+        a.lazy = h_lazy;
         a.t_lo = 0; a.t_len = L;
 #ifdef S5_BPROJ_CSR
         const size_t smem = 16 * (size_t)sh.hp + 4 * 64 * (size_t)(sh.hp + 16) + 2 * (size_t)(2 * m->P) * S5_BPROJ_CSR + 64; // + compressed columns
@@ -801,7 +821,7 @@ struct FusedForward {
         LayerDyn *d = dyn + li;
         CGateArgs a{};
         a.u = I16(w.u); a.skip = h; a.xs = I32(w.xs); a.w_re = *p.w_cre; a.w_im = *p.w_cim; a.w_o2 = fl.out2.w;
-        a.D = fl.Dpad; a.bias_eff = fl.out2.bias_eff; a.z = I16(w.z); a.sigtab = fl.sigtab; a.sigdir = fl.sigdir; a.sigdir_bits = fl.sigdir_bits; a.mx_slot = 8;
+        a.D = fl.Dpad; a.bias_eff = fl.out2.bias_eff; a.z = zp; a.sigtab = fl.sigtab; a.sigdir = fl.sigdir; a.sigdir_bits = fl.sigdir_bits; a.mx_slot = 8;
         a.tr_ys = tr ? tr->ys : nullptr; a.tr_out2 = tr ? tr->out2 : nullptr; a.tr_sig = tr ? tr->out2_sigmoid : nullptr;
         a.tr_z = tr ? tr->post_GLU : nullptr;
         a.N = N; a.L = L; a.TB = w.TB; a.H = H;
@@ -834,6 +854,7 @@ struct FusedForward {
             if (p.resid_fold) {
                 CGateFoldArgs fa{};
                 static_cast<CGateArgs &>(fa) = a;
+                fa.skip_dyn = h_lazy;
                 launch(gate_fold_kernel(p), grid_gate32, 192, smem32, gev0, gev1, fa);
             } else launch(gate_kernel(p, sh), grid_gate32, 192, smem32, gev0, gev1, a);
         } else {
@@ -896,16 +917,31 @@ struct FusedForward {
         if (bn_ext) {
             const bool more = li + 1 < m->n_layers;
             const int ext_reps = (more && fold) ? EXT_REPS : 1; // the next layer's B projection derives its exponents from the extremes
+            if (layer[li].resid_lazy) {
+                // the pass reads U for its extremes and stores nothing; the U plane becomes the layer input, and the plane of
+                // the old one the next gate kernel's output
+                ResidLazyArgs a{};
+                a.u = zp; a.N = N; a.span = rm_span; a.H = H; a.res_bits = l.res_bits; a.hd = resid_head(li);
+                a.ext = ext(li + 1); a.ext_reps = ext_reps; a.status = status;
+                launch(static_cast<ResidLazyKernel>(k_resid_minmax16<true, true>), rm_grid, RESID_THREADS, 0, nullptr, nullptr, a);
+                std::swap(h, zp);
+                h_lazy = dyn + li;
+                hb = l.res_bits;
+                he = DynExp{0, &dyn[li].res.eo};
+                return;
+            }
             // (resid_fold: the z plane holds U and the pass reads nothing else)
-            launch(layer[li].resid_fold ? k_resid_minmax16<true, true> : k_resid_minmax16<true, false>, rm_grid, RESID_THREADS, 0,
-                   nullptr, nullptr, (const int16_t *)I16(w.z), (const int16_t *)h, hn,
+            launch(layer[li].resid_fold ? static_cast<ResidKernel>(k_resid_minmax16<true, true>) : static_cast<ResidKernel>(k_resid_minmax16<true, false>),
+                   rm_grid, RESID_THREADS, 0,
+                   nullptr, nullptr, (const int16_t *)zp, (const int16_t *)h, hn,
                    tr ? tr->residadd : nullptr, N, H, rm_span, l.res_bits, hb, resid_head(li), more ? ext(li + 1) : nullptr, ext_reps,
                    status);
         } else {
-            hipLaunchKernelGGL(k_resid16, dim3(ew_grid(NH / 4)), dim3(256), 0, st, (const int16_t *)I16(w.z),
+            hipLaunchKernelGGL(k_resid16, dim3(ew_grid(NH / 4)), dim3(256), 0, st, (const int16_t *)zp,
                                (const int16_t *)h, hn, tr ? tr->residadd : nullptr, NH, l.res_bits, hb, (const LayerDyn *)(dyn + li));
         }
         std::swap(h, hn);
+        h_lazy = nullptr;
         hb = l.res_bits;
         he = DynExp{0, &dyn[li].res.eo};
     }
@@ -922,11 +958,11 @@ struct FusedForward {
         a.out_bits = e.out_bits; a.out_exp = e.out_exp; a.status = status;
         if (dec_resid >= 0) {
             const LayerDev &l = m->layers[dec_resid];
-            dz.z = I16(w.z); dz.res_bits = l.res_bits; dz.skip_bits = hb; dz.hd = resid_head(dec_resid);
+            dz.z = zp; dz.res_bits = l.res_bits; dz.skip_bits = hb; dz.hd = resid_head(dec_resid);
             a.xb = l.res_bits;
             if (layer[dec_resid].resid_fold) { // the z plane holds U: the one plane the decoder reads
                 dz.usum = 1;
-                a.x = I16(w.z);
+                a.x = zp;
             }
         }
         const size_t smem = 2 * 64 * (size_t)(sh.hp + 16);
@@ -952,6 +988,9 @@ int forward_fast(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int
     for (int li = 0; li < m->n_layers; ++li) {
         const BnArgs bn = make_bn(m->layers[li], f.hb, f.he, f.dyn + li);
         if ((rc = f.bn_exponents(li, bn))) return rc;
+        // a lazy layer input is shifted on load by the untraced H = 96 B projection and the fold gate kernel alone (proj_p.hpp LAZY,
+        // mfma_fused.hpp CGateFoldArgs::skip_dyn); the plan gives it to no other kernel, and this says so where they are chosen
+        if (f.h_lazy && (f.sh.nt != 3 || traces || !f.layer[li].resid_fold)) return S5FXP_EUNSUPPORTED;
         f.bproj(li, bn);
         if (!f.stage_ok("B projection", li)) return S5FXP_EHIP;
         f.recurrence(li);

@@ -35,6 +35,8 @@ def main() -> None:
         short = re.sub(r"\(.*", "", name).replace("void s5::", "")
         if "CGateFoldArgs" in name:   # the k_cgate_p overload that stores the aligned sum (same template arguments)
             short += " [fold]"
+        if "ResidLazyArgs" in name:   # the k_resid_minmax16 overload that stores nothing (same template arguments)
+            short += " [lazy]"
         if pats and not any(p in short for p in pats):
             continue
         print(f"{short:70s} vgpr {r.get('vgpr', -1):3d} agpr {r.get('agpr', 0):3d} sgpr {r.get('sgpr', -1):3d} "
