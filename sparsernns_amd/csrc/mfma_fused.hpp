@@ -68,11 +68,7 @@ __global__ void k_select_maxima(LayerDyn *d)
 // a tile ahead would be drained at the next barrier.  This one waits for the wave's LDS operations and nothing else.
 __device__ __forceinline__ void lds_barrier()
 {
-#ifdef S5_BARRIER_VM0
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#else
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
@@ -147,24 +143,10 @@ __device__ __forceinline__ const LayerDyn *skip_dyn_of(const CGateFoldArgs &a) {
 template <int KS, int NT, bool TRACE, bool S16 = false, bool DIRECT = false, int FTP = 64, bool WIDE = false, bool PAIR = false, bool PK16 = false,
           bool GBN = false, bool UREC = false>
 // <= 128 registers: two six-wave workgroups per CU (at 136 only one was ever resident: measured)
-// -DS5_CGATE_HID=1: states, u and skip of the NEXT tile all requested a tile ahead behind the compiler's back and waited for
-// by exact count (scan_quad.hpp vm_wait).  Measured (profiles/r03_gate_prefetch_ab.txt): 226 us per 8-batch launch against
-// 210 us for the default below, which requests the states at the top of the tile that uses them and lets the compiler's
-// vmcnt(0) there drain the skip prefetch as well -- MORE bytes in flight make this kernel slower, not faster (the same
-// build with every barrier draining all loads: 245 us).  Kept as the experiment's record.
-#ifndef S5_CGATE_HID
-#define S5_CGATE_HID 0
-#endif
-// -DS5_CGATE_COAL=0: u, skip and z move between registers and memory in the MFMA accumulator's layout (lane = frame: every
-// load / store instruction touches 64 rows with 8 bytes each) instead of through the LDS tiles described at COAL below
-#ifndef S5_CGATE_COAL
-#define S5_CGATE_COAL 1
-#endif
-#ifndef S5_CGATE_LB
-#define S5_CGATE_LB 4
-#endif
+// (measured and lost, DESIGN.md 4a: states, u and skip all requested a tile ahead and waited for by exact count)
+// (measured and lost, DESIGN.md 4a: u, skip and z moved in the accumulator's layout instead of through the LDS tiles, COAL)
 // (H = 48: three four-wave workgroups fill a CU's LDS, so the three-waves-per-SIMD register budget costs no occupancy there)
-__global__ __launch_bounds__(FTP * 2 * NT, NT == 3 && KS == 1 && !WIDE ? S5_CGATE_LB : 3) void k_cgate_p(const CGateArgs a_k, GroupOff go)
+__global__ __launch_bounds__(FTP * 2 * NT, NT == 3 && KS == 1 && !WIDE ? 4 : 3) void k_cgate_p(const CGateArgs a_k, GroupOff go)
 {
     constexpr bool FOLD = false;
 #include "mfma_fused_body.inc"
@@ -173,7 +155,7 @@ __global__ __launch_bounds__(FTP * 2 * NT, NT == 3 && KS == 1 && !WIDE ? S5_CGAT
 // template argument: the template arguments stay the eleven every k_cgate_p has.  One body, compiled into both (the kernels
 // that do not fold keep their code as it was).
 template <int KS, int NT, bool TRACE, bool S16, bool DIRECT, int FTP, bool WIDE, bool PAIR, bool PK16, bool GBN, bool UREC>
-__global__ __launch_bounds__(FTP * 2 * NT, NT == 3 && KS == 1 && !WIDE ? S5_CGATE_LB : 3) void k_cgate_p(const CGateFoldArgs a_k, GroupOff go)
+__global__ __launch_bounds__(FTP * 2 * NT, NT == 3 && KS == 1 && !WIDE ? 4 : 3) void k_cgate_p(const CGateFoldArgs a_k, GroupOff go)
 {
     constexpr bool FOLD = true;
 #include "mfma_fused_body.inc"

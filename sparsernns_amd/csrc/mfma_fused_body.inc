@@ -7,8 +7,7 @@
         if constexpr (GBN || UREC) { gshift(a.bn.dyn, g * go.ws); gshift(a.bn.xe.dyn, g * go.ws); }
     }
     static_assert(!GBN || (PK16 && !TRACE && !WIDE), "the BatchNorm rides on the packed-epilogue kernel only");
-    static_assert(!UREC || (S5_CGATE_COAL && PK16 && !TRACE && !WIDE && !GBN && !(S5_CGATE_HID && S16 && PAIR && KS * NT < 24)),
-                  "u is rebuilt in the row tiles' staging: COAL only");
+    static_assert(!UREC || (PK16 && !TRACE && !WIDE && !GBN), "u is rebuilt in the row tiles' staging: COAL only");
     // H: the real channels (row stride in memory, vectors per frame); HP: the padded extent of the LDS tables, the X1 planes
     // and the row tiles (proj_p.hpp shape_channels).  RAGGED: channel groups of the last tile at or beyond H are pad lanes:
     // their weights, D and bias are zero, so they compute x1 = 0 and z = 0; their u and skip are zero instead of loaded (a zero
@@ -18,8 +17,6 @@
     constexpr int KPS = 2 * P + 16, KPX = HP + 16;
     constexpr int NU = 1, SUBSTEP = 0;   // units per wave
     constexpr int ITEMS = (FT / 4) * P, ROUNDS = (ITEMS + NTHR - 1) / NTHR;
-    // hidden prefetches, see below (the dim 1.0 kernel on all 128 state slots has no registers left for them)
-    constexpr bool HID = S5_CGATE_HID && S16 && PAIR && PK16 && !WIDE && !TRACE && KS * NT < 24;
     extern __shared__ __attribute__((aligned(16))) int8_t smem[];
     int32_t *csr = reinterpret_cast<int32_t *>(smem), *csi = csr + HP, *Dl = csi + HP, *cs2 = Dl + HP, *be = cs2 + HP, *lutp = be + HP;
     int32_t *sigt = lutp + 8; // SIGTAB_WORDS, or the direct table (int16, SIGDIR_BYTES)
@@ -35,7 +32,7 @@
     // layout of the channel-major MFMA), pick their 8-byte (frame, four channels) pieces out of LDS.  In the accumulator's own
     // layout every global load / store instruction touched 64 different rows with 8 bytes each: the bytes per batch are the
     // same, the memory pipeline sees an eighth of the requests.  TROW: 8-byte reads by 32 lanes 200 bytes apart hit 32 bank pairs.
-    constexpr bool COAL = S5_CGATE_COAL && PK16 && !TRACE && !WIDE && !GBN && !HID;
+    constexpr bool COAL = PK16 && !TRACE && !WIDE && !GBN;
     // bytes per tile row; 16-byte vectors per frame / per thread (ragged shapes: the last round is predicated, NVC_FULL false)
     constexpr int TROW = 2 * HP + 8, VPF = H / 8, NVC = (FT * VPF + NTHR - 1) / NTHR;
     constexpr bool NVC_FULL = FT * VPF % NTHR == 0;
@@ -149,40 +146,12 @@
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 if (RAGGED && ch0 + 8 * g >= H) dst[u][g] = v2i{0, 0}; // a pad lane
-                else if constexpr (HID) dst[u][g] = gload8_hidden(base, fb + 16 * g);
                 else dst[u][g] = *reinterpret_cast<const v2i *>(base + fb + 16 * g);
             }
         }
     };
-    // ... and so are the recurrence's states on the pair rung (the shipped path): phase A's two 8-byte loads per item used to
-    // be issued and consumed on the spot, every tile opening with one exposed round trip to memory
-    // On that path the three prefetches are issued behind the compiler's back and waited for by count (scan_quad.hpp
-    // vm_wait): the wait its own pass puts in front of their first use, a tile later and behind conditional stores, is
-    // vmcnt(0) -- which also drains whatever was requested since.  Memory operations of a wave on a full tile, in order:
-    //   phase A: [x(next): NX]   B1: [u(next): 4]   B2: [z stores: 4] [skip(next): 4]
-    constexpr bool XPRE = HID;
-    constexpr int NX_MIN = 2 * (ITEMS / NTHR); // x loads every wave issues per tile (waves of the last round: two more)
-    v2i xq[XPRE ? ROUNDS : 1][2];
-    auto load_x = [&](const TileWalk<FT> &tw) {
-        const int64_t b = tw.b;
-        const int t = tw.t(sr), nv = tw.nvalid(sr);
-        const char *xb = reinterpret_cast<const char *>(reinterpret_cast<const int16_t *>(a.xs) + (pair_word(b, t >> 3, 0, a.TB >> 1, P) << 1));
-#pragma unroll
-        for (int i = 0; i < ROUNDS; ++i) {
-            const int q = threadIdx.x + NTHR * i;
-            if (ROUNDS * NTHR == ITEMS || q < ITEMS) {
-                const int grp = q / P, p = q % P;
-                int o = 4 * grp;
-                if (o >= nv) o = (nv - 1) & ~3;
-                const unsigned xo = 2u * (unsigned)((((((p >> 5) * (a.TB >> 1) + (o >> 3)) << 5) + (p & 31)) << 4) + (o & 4));
-                xq[i][0] = xq[i][1] = v2i{0, 0};
-                if (a.live_slots <= 0 || p < a.live_slots) {
-                    xq[i][0] = gload8_hidden(xb, xo);
-                    xq[i][1] = gload8_hidden(xb, xo + 16);
-                }
-            }
-        }
-    };
+    // (the recurrence's states are requested at the top of the tile that uses them: requesting them a tile ahead as well
+    // made the kernel slower, DESIGN.md 4a)
     if constexpr (COAL && RAGGED) { // the pad lanes' u and skip: zero once, no row vector ever lands there
         for (int i = threadIdx.x; i < 2 * FT; i += NTHR) {
             int8_t *t = Ut + i * TROW + 2 * H; // (rows of Ut, then of St; 8-byte aligned like every access to the tiles)
@@ -192,7 +161,6 @@
     }
     TileWalk<FT> walk((int64_t)blockIdx.x, sr, gridDim.x);
     if ((int64_t)blockIdx.x < tiles) {
-        if constexpr (XPRE) load_x(walk);
         if constexpr (COAL) {
             if constexpr (!UREC) load_tile(urow, a.u, walk);
             load_tile(srow, a.skip, walk);
@@ -269,7 +237,6 @@
         // thread: the kernel sits at its register cap)
         char *zb = reinterpret_cast<char *>(a.z + n0 * H);
         const int64_t tile_next = tile + gridDim.x;
-        if constexpr (HID) vm_wait<12>(xq); // newer than this tile's states: u, the last tile's stores, skip
         if constexpr (UREC) { // z of the previous tile out, skip of this one in, and u made from it
             if (brow.arm == ROW_PACKED) tiles_in_urec(std::integral_constant<int, ROW_PACKED>{});
             else if (brow.arm == ROW_SHIFTED) tiles_in_urec(std::integral_constant<int, ROW_SHIFTED>{});
@@ -315,16 +282,11 @@
                         // one 8-step item per lane of the pair: this thread takes the half with its 4 steps from both.
                         // lane A: [im0 im2 | re1 re3], lane B: [re0 re2 | im1 im3] (per half)
                         // the tile's items of state group p >> 5 start at pair_word(b0, t0 >> 3, 32 (p >> 5), ...): uniform base + 32-bit offset
-                        v2i qa, qb;
-                        if constexpr (XPRE) {
-                            qa = xq[i][0]; qb = xq[i][1]; // load_x: requested a tile ago
-                        } else {
-                            const char *xb = reinterpret_cast<const char *>(reinterpret_cast<const int16_t *>(a.xs) + (pair_word(b0, t0 >> 3, 0, a.TB >> 1, P) << 1));
-                            const unsigned xo = 2u * (unsigned)((((((p >> 5) * (a.TB >> 1) + (o >> 3)) << 5) + (p & 31)) << 4) + (o & 4));
-                            qa = qb = v2i{0, 0};
-                            if (a.live_slots <= 0 || p < a.live_slots) {
-                                qa = *reinterpret_cast<const v2i *>(xb + xo); qb = *reinterpret_cast<const v2i *>(xb + xo + 16);
-                            }
+                        const char *xb = reinterpret_cast<const char *>(reinterpret_cast<const int16_t *>(a.xs) + (pair_word(b0, t0 >> 3, 0, a.TB >> 1, P) << 1));
+                        const unsigned xo = 2u * (unsigned)((((((p >> 5) * (a.TB >> 1) + (o >> 3)) << 5) + (p & 31)) << 4) + (o & 4));
+                        v2i qa = {0, 0}, qb = {0, 0};
+                        if (a.live_slots <= 0 || p < a.live_slots) {
+                            qa = *reinterpret_cast<const v2i *>(xb + xo); qb = *reinterpret_cast<const v2i *>(xb + xo + 16);
                         }
                         w[0] = (int32_t)perm((unsigned)qa[0], (unsigned)qb[0], 0x05040100u);
                         w[1] = (int32_t)perm((unsigned)qb[1], (unsigned)qa[1], 0x05040100u);
@@ -378,9 +340,6 @@
                 *reinterpret_cast<int32_t *>(Sh + row + P) = (int32_t)perm(u23, u01, 0x07060302u);
             }
         }
-        if constexpr (XPRE) {
-            if (tile_next < tiles) load_x(walk_next);
-        }
         if constexpr (COAL) {
             if (tile_next < tiles) { // the registers are free again: the next tile's rows, a whole tile ahead
                 if constexpr (!UREC) load_tile(urow, a.u, walk_next);
@@ -388,7 +347,6 @@
             }
         }
         lds_barrier();
-        if constexpr (HID) vm_wait<8>(uq); // newer: the last tile's stores, skip (and x(next), if there is a next tile)
         // ---- phase B1: C projection + first epilogue
         int32_t x1v[NU][16];
         uint32_t x1p[NU][8]; // PK16: the same values as int16 pairs (channels 2q, 2q+1 of group g at [2g + q])
@@ -462,25 +420,12 @@
             if (!COAL && tile_next < tiles) load_rows(uq, a.u, walk_next); // the first epilogue is done with u
         }
         lds_barrier();
-        if constexpr (HID) { // newer: x(next) and u(next), if there is a next tile
-            if (tile_next < tiles) vm_wait<NX_MIN + 4>(sq);
-            else vm_wait<0>(sq);
-        }
         // ---- phase B2: out2 + second epilogue
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
             const int sub = sub0 + u * SUBSTEP;
             const int64_t n = n0 + 32 * sub + r;
             v16i acc;
-#ifdef S5_GATE_CHECK
-            bool live2 = false; // out2's operand: one decision for the whole row of fragments (mfma_planes takes them all)
-#pragma unroll
-            for (int ks = 0; ks < NT; ++ks) live2 |= gate_check<2>(Xl + (32 * sub + r) * KPX + 16 * h + 32 * ks, -(FT * KPX), 2);
-            if (!live2) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[i] = 0;
-            } else
-#endif
             mfma_planes<NT>(acc, wo2, Xh + (32 * sub + r) * KPX + 16 * h, Xl + (32 * sub + r) * KPX + 16 * h, cs2 + ch0);
             auto b2_pk16 = [&]() {
                 // out2 bias, table sigmoid, gate (fxpmodel.py:1133-1137, :97-144, :1075-1093) on int16 pairs
@@ -512,14 +457,7 @@
                 }
             };
             if constexpr (PK16) {
-                if (!HID) {
-                    if (32 * sub + r < nvalid) b2_pk16();
-                } else if (nvalid == FT) {
-                    b2_pk16(); // a full tile: no control flow around its stores, their number is known
-                } else {
-                    if (32 * sub + r < nvalid) b2_pk16();
-                    prologue_loads_done(); // behind conditional stores nothing is left in flight
-                }
+                if (32 * sub + r < nvalid) b2_pk16();
             }
             if (!PK16 && 32 * sub + r < nvalid) {
 #pragma unroll

@@ -16,7 +16,7 @@
 // waves.  ~30 KB LDS and < 128 registers: four workgroups (16 waves) per CU.
 #pragma once
 // -DS5_PHASE_PROF (tools/prof_phases.py, never in the shipped library): every thread 0 accumulates the shader clock between
-// phase marks of k_enc_p.  A mark first touches a register the preceding work produced (a v_cmp into vcc: the hardware interlock makes
+// phase marks of k_enc_p (and of k_enc_pf, which shares its body: proj_enc_body.inc).  A mark first touches a register the preceding work produced (a v_cmp into vcc: the hardware interlock makes
 // it wait for an MFMA or a load that is still in flight -- a bare s_memtime is hoisted over pure arithmetic by the compiler
 // and overtakes pending MFMAs in the hardware), then reads the clock.
 #ifdef S5_PHASE_PROF
@@ -34,9 +34,6 @@ __device__ long long g_phase_prof[2048 * 8];
 #define PHASE_MARK(i, reg)
 #define PHASE_DUMP
 #endif
-#define PHASE_DECL_F
-#define PHASE_MARK_F(i, reg)
-#define PHASE_DUMP_F
 #include "mfma_bn.hpp"
 
 namespace s5 {
@@ -174,27 +171,6 @@ __global__ __launch_bounds__(64 * NT, TRACE ? 2 : KS == 5 ? 3 : 4) void k_bproj_
         for (int ks = 0; ks < KS; ++ks)
             wreg[c][ks] = *reinterpret_cast<const v4i *>(a.w.wt + (size_t)col * a.w.Kp + 32 * ks + 16 * h);
     }
-#ifdef S5_BPROJ_CSR
-    // EXPERIMENT build only (-DS5_BPROJ_CSR=<max nonzeros per column>; tools/variant.py): the
-    // weight operand as compressed columns -- per output column the (k, w) pairs of its nonzeros, padded to the widest
-    // column of the wave -- and the contraction on the VALU, one multiply-add per (frame, nonzero) and byte plane,
-    // instead of the dense zero-filled MFMA operand.  Same accumulators, same epilogue, same results.
-    constexpr int ELLW = S5_BPROJ_CSR;
-    uint16_t *ell = reinterpret_cast<uint16_t *>(smem + 16 * HP + 4 * PLANE); // [32 * NC columns][ELLW]: k | w << 8
-    int *ellmax = reinterpret_cast<int *>(ell + 32 * NC * ELLW);            // [NC]: widest column of the tile
-    if (threadIdx.x < NC) ellmax[threadIdx.x] = 0;
-    __syncthreads();
-    if (wsub == 0 && h == 0) {
-        const int col = 32 * wct + r;
-        int n = 0;
-        for (int k = 0; k < H; ++k) {
-            const int8_t wv = a.w.wt[(size_t)col * a.w.Kp + k];
-            if (wv != 0 && n < ELLW) ell[col * ELLW + n++] = (uint16_t)(k | ((unsigned)(uint8_t)wv << 8));
-        }
-        for (int j = n; j < ELLW; ++j) ell[col * ELLW + j] = 0;
-        atomicMax(ellmax + wct, n);
-    }
-#endif
     // The BatchNorm exponents of this layer: read from *dyn, or -- single-rank forwards -- derived here, by every
     // workgroup for itself, from the per-channel extremes the producer of the layer input left behind (the first tile's
     // loads are in flight meanwhile).  A single workgroup doing this at the tail of the producer kernel cost 4-7 us of
@@ -281,28 +257,6 @@ __global__ __launch_bounds__(64 * NT, TRACE ? 2 : KS == 5 ? 3 : 4) void k_bproj_
                 if (SUB0_STEP > 2 && sub >= 2) break; // a quarter of the column tiles: half of the waves have no unit in phase B
                 const int8_t *rowh = xh + (32 * sub + r) * KP + 16 * h, *rowl = xl + (32 * sub + r) * KP + 16 * h;
                 v16i acc;
-#ifdef S5_BPROJ_CSR
-                {
-                    (void)rowh; (void)rowl;
-                    int32_t ah[16], al[16];
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) ah[i] = al[i] = 0;
-                    const uint16_t *mine = ell + (32 * (wct + NC * c) + r) * ELLW;
-                    const int nz = ellmax[wct + NC * c];
-                    for (int j = 0; j < nz; ++j) {
-                        const unsigned e = mine[j];
-                        const int k = e & 0xff, wv = (int8_t)(e >> 8);
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            const int f = 32 * sub + 8 * (i >> 2) + 4 * h + (i & 3);
-                            ah[i] += wv * xh[f * KP + k];
-                            al[i] += wv * xl[f * KP + k];
-                        }
-                    }
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) acc[i] = wadd(wadd(wshl(ah[i], 8), csv[c]), al[i]);
-                }
-#else
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc[i] = 0;
 #pragma unroll
@@ -313,7 +267,6 @@ __global__ __launch_bounds__(64 * NT, TRACE ? 2 : KS == 5 ? 3 : 4) void k_bproj_
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks)
                     acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(*reinterpret_cast<const v4i *>(rowl + 32 * ks), wreg[c][ks], acc, 0, 0, 0);
-#endif
                 // rows (frames) (i&3) + 8*(i>>2) + 4*h of this half: registers 4g..4g+3 are one 4-step block
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
@@ -414,47 +367,10 @@ __device__ __forceinline__ void mfma_planes(v16i &acc, const v4i (&w)[KSTEPS], c
 // the same for NPL byte planes [plane][frame][k] (plane NPL-1 = signed top byte), Horner from the top: the constant
 // 128*sum(w) enters at every shift, so after NPL-1 shifts it has the weight 2^(8(NPL-2)) + ... + 2^8 + 1 that the
 // +128 offsets of the lower planes need
-#ifdef S5_GATE_CHECK
-// EXPERIMENT builds only (tools/variant.py): the test an activation-gating kernel makes before each
-// MFMA of the gate kernel's two projections -- is this wave's operand fragment (32 frames x 32 k, every byte plane) all zero?
-//   -DS5_GATE_CHECK=1 (gate_count): counts them; the MFMA still runs.  [0]/[1]: fragments / all-zero fragments of the C
-//     projection's operand (the states after the complex ReLU, fxpmodel.py:740-742), [2]/[3]: the same for out2's operand (the
-//     SSM output after the ReLU, :1125).  Not for timing: every wave hits the same two counters.
-//   -DS5_GATE_CHECK=2 (gate_skip): branches around the MFMAs of an all-zero fragment, no counters: what a gating kernel
-//     costs.  (Skipping drops the fragment's share of the lower planes' +128 correction: exact only when nothing is skipped
-//     or the skipped k carry zero weights, as the padding slots of a compacted layer do.)
-__device__ unsigned long long g_gate_frag[4];
-template <int NPL>
-__device__ __forceinline__ bool gate_check(const int8_t *frag0, int plane_stride, int slot)
-{
-    unsigned nz = 0;
-#pragma unroll
-    for (int pl = 0; pl < NPL; ++pl) {
-        const v4i b = *reinterpret_cast<const v4i *>(frag0 + pl * plane_stride);
-        const unsigned pat = pl == NPL - 1 ? 0u : 0x80808080u; // the lower planes hold (byte ^ 0x80)
-        nz |= ((unsigned)b[0] ^ pat) | ((unsigned)b[1] ^ pat) | ((unsigned)b[2] ^ pat) | ((unsigned)b[3] ^ pat);
-    }
-    const bool any = __any(nz != 0);
-#if S5_GATE_CHECK == 1
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd(&g_gate_frag[slot], 1ull);
-        if (!any) atomicAdd(&g_gate_frag[slot + 1], 1ull);
-    }
-    return true;
-#else
-    return any;
-#endif
-}
-#endif
 template <int KSTEPS, int NPL>
 __device__ __forceinline__ void mfma_nplanes(v16i &acc, const v4i (&w)[KSTEPS], const int8_t *row0, int plane_stride,
                                              const int32_t *cs)
 {
-#ifdef S5_GATE_CHECK
-    bool live[KSTEPS];
-#pragma unroll
-    for (int ks = 0; ks < KSTEPS; ++ks) live[ks] = gate_check<NPL>(row0 + 32 * ks, plane_stride, 0);
-#endif
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0;
 #pragma unroll
@@ -469,9 +385,6 @@ __device__ __forceinline__ void mfma_nplanes(v16i &acc, const v4i (&w)[KSTEPS], 
         }
 #pragma unroll
         for (int ks = 0; ks < KSTEPS; ++ks) {
-#ifdef S5_GATE_CHECK
-            if (!live[ks]) continue;
-#endif
             acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(w[ks], *reinterpret_cast<const v4i *>(row0 + pl * plane_stride + 32 * ks), acc, 0, 0, 0);
         }
     }
@@ -489,376 +402,23 @@ __device__ __forceinline__ void mfma_nplanes(v16i &acc, const v4i (&w)[KSTEPS], 
 template <int NT>
 __global__ __launch_bounds__(384, 3) void k_enc_p(EncArgs a, float *ext, int ext_reps, GroupOff go)
 {
-    {
-        const int64_t g = blockIdx.y;
-        gshift(a.x, g * go.x); gshift(a.y, g * go.ws); gshift(a.status, g * go.status); gshift(ext, g * go.ws);
-    }
-    constexpr int KS = 9, FT = 64, KP = 32 * KS + 16, NW = 6, H = 32 * NT;
-    // phase B units (32-frame half, column tile) per wave: NT <= 3: wave -> (half wave / NT, tile wave % NT), one unit;
-    // NT > 3: wave -> tile `wave`, both halves.  UW waves have units: all six at NT = 3 and 6; at NT = 2 and 5 the last
-    // two / the last one sit phase B out (its weights stay per wave: a second tile's would not fit the registers)
-    constexpr int NU = NT <= 3 ? 1 : 2, SUBSTEP = NT <= 3 ? 0 : 1, UW = NT <= 3 ? 2 * NT : NT;
-    static_assert(UW <= NW, "one wave per unit or per column tile");
-    constexpr bool RAGGED = shape_channels(NT) != 32 * NT; // the last column tile is half empty: its stores are conditional
-    constexpr int RPW = (FT + NW - 1) / NW; // rows per wave
-    extern __shared__ __attribute__((aligned(16))) int8_t smem[];
-    int32_t *cs = reinterpret_cast<int32_t *>(smem), *be = cs + H;
-    int8_t *Xh = reinterpret_cast<int8_t *>(be + H), *Xl = Xh + FT * KP;
-    uint32_t *ehi = reinterpret_cast<uint32_t *>(Xl + FT * KP), *elo = ehi + H;
-    const int l = threadIdx.x & 63, r = l & 31, h = l >> 5, wave = threadIdx.x >> 6;
-    const int ct = wave % NT, sub0 = wave / NT, ch0 = 32 * ct + 4 * h;
-    const int64_t tiles = (a.N + FT - 1) / FT;
-    const int K = a.K, rem = K - 256;
-    uint32_t pk[16]; // low half: max, high half: 65535 - min
-#pragma unroll
-    for (int i = 0; i < 16; ++i) pk[i] = 0;
-    v4i wreg[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-        wreg[ks] = *reinterpret_cast<const v4i *>(a.w.wt + (size_t)(32 * ct + r) * a.w.Kp + 32 * ks + 16 * h);
-    for (int i = threadIdx.x; i < H; i += 384) {
-        cs[i] = a.w.cs128[i];
-        be[i] = a.bias_eff[i];
-        ehi[i] = 0;
-        elo[i] = 0;
-    }
-    const CfgOp cv = make_cfg(a.conv != 0, a.xb, a.xe, a.inp_bits, a.inp_exp);
-    const SatB so = sat_bounds(a.out_bits);
-    // rows wave, wave+6, ... of the tile.  Two workgroups of six waves per CU are three waves per SIMD whatever the kernel
-    // does, so it may hold 168 registers: all of a tile's rows are requested a tile ahead (dim 0.5; the two-unit phase B
-    // of dim 1.0 has no room for that: there the first RA rows are prefetched and the rest requested at the top of phase A).
-    // The prefetch is issued behind the compiler's back (scan_quad.hpp vm_wait): its own wait at the first use -- a tile
-    // later, behind phase B's stores -- would be vmcnt(0), every tile opening with a wait for the previous tile's stores.
-    constexpr int RA = NT <= 3 ? RPW : 3, RB = RPW - RA;
-    v4i rawa[RA], rawb[RB > 0 ? RB : 1];
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    auto row_base = [&](int64_t tl, int i) { // wave-uniform
-        int64_t n = tl * FT + wave_u + NW * i;
-        n = n < a.N ? n : a.N - 1;
-        return reinterpret_cast<const char *>(a.x + n * K);
-    };
-    auto row_ptr = [&](int64_t tl, int i) {
-        return reinterpret_cast<const v4i *>(row_base(tl, i) + 16 * l); // 4-byte aligned 16-byte load
-    };
-    auto convert_row = [&](const v4i &q, int f, bool &wide) {
-        int32_t v[4] = {q[0], q[1], q[2], q[3]};
-        if (a.conv) { // uniform: usually the input already has the encoder's configuration
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = cv(v[e]);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) wide |= (v[e] != (int32_t)(int16_t)v[e]);
-        const unsigned p01 = perm((unsigned)v[1], (unsigned)v[0], 0x05010400u), p23 = perm((unsigned)v[3], (unsigned)v[2], 0x05010400u);
-        *reinterpret_cast<int32_t *>(Xl + f * KP + 4 * l) = (int32_t)(perm(p23, p01, 0x05040100u) ^ 0x80808080u);
-        *reinterpret_cast<int32_t *>(Xh + f * KP + 4 * l) = (int32_t)perm(p23, p01, 0x07060302u);
-    };
-    int64_t tile = blockIdx.x;
-    if (tile < tiles) {
-#pragma unroll
-        for (int i = 0; i < RA; ++i) rawa[i] = gload16_hidden(row_base(tile, i), 16u * (unsigned)l);
-    }
-    bool wide = false;
-    __syncthreads();
-    PHASE_DECL
-    prologue_loads_done();
-    const bool even = a.M == H; // no ragged column tile: full tiles store unconditionally
-    for (; tile < tiles; tile += gridDim.x) {
-        const int64_t n0 = tile * FT;
-        PHASE_MARK(0, l); // loop top (includes the previous tile's closing barrier)
-        // ---- phase A
-        // the prefetched rows are older than the previous tile's stores: NU x 4 per wave on the unconditional path (the
-        // conditional one ends with a full wait)
-        vm_wait<RAGGED ? 0 : 4 * NU>(rawa);
-        if constexpr (RB > 0) {
-#pragma unroll
-            for (int i = 0; i < RB; ++i) rawb[i] = *row_ptr(tile, RA + i);
-        }
-#pragma unroll
-        for (int i = 0; i < RA; ++i)
-            if (wave_u + NW * i < FT) convert_row(rawa[i], wave_u + NW * i, wide);
-        PHASE_MARK(1, rawa[RA - 1][0]); // prefetched rows converted
-        if constexpr (RB > 0) {
-#pragma unroll
-            for (int i = 0; i < RB; ++i)
-                if (wave_u + NW * (RA + i) < FT) convert_row(rawb[i], wave_u + NW * (RA + i), wide);
-        }
-        PHASE_MARK(2, rawb[0][0]); // rows requested at the top (their HBM latency included)
-        for (int e = threadIdx.x; e < FT * rem; e += 384) { // the K-256 tail of every row
-            const int f = e / rem, k = 256 + e % rem;
-            int64_t n = n0 + f;
-            n = n < a.N ? n : a.N - 1;
-            const int32_t v = cv(a.x[n * K + k]);
-            wide |= (v != (int32_t)(int16_t)v);
-            Xl[f * KP + k] = (int8_t)((v & 0xff) ^ 0x80);
-            Xh[f * KP + k] = (int8_t)(v >> 8);
-        }
-        if (tile + gridDim.x < tiles) {
-#pragma unroll
-            for (int i = 0; i < RA; ++i) rawa[i] = gload16_hidden(row_base(tile + gridDim.x, i), 16u * (unsigned)l); // in flight during phase B
-        }
-        PHASE_MARK(3, l); // tail column + prefetch issue
-        __syncthreads();
-        PHASE_MARK(4, l); // mid barrier
-        // ---- phase B
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            if (UW < NW && wave_u >= UW) break;
-            const int sub = sub0 + u * SUBSTEP;
-            const int64_t n = n0 + 32 * sub + r;
-            v16i acc;
-            mfma_planes<KS>(acc, wreg, Xh + (32 * sub + r) * KP + 16 * h, Xl + (32 * sub + r) * KP + 16 * h, cs + ch0);
-            PHASE_MARK(5, acc[15]); // operand reads + MFMA chain, complete
-            auto group = [&](int g) {
-                const int ch = ch0 + 8 * g;
-                const v4i bv = *reinterpret_cast<const v4i *>(be + ch);
-                int32_t o[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    int32_t v = sat(asr(acc[4 * g + e], a.rs), so);
-                    v = sat(wadd(v, bv[e]), so);
-                    o[e] = v < 0 ? 0 : v;
-                    // (v, 65535 - v) as a u16 pair; one packed max keeps both running extremes
-                    const uint32_t t = (uint32_t)__umul24((unsigned)o[e], 0x10001u) ^ 0xffff0000u;
-                    pk[4 * g + e] = __builtin_bit_cast(
-                        uint32_t, __builtin_elementwise_max(__builtin_bit_cast(v2u16, pk[4 * g + e]), __builtin_bit_cast(v2u16, t)));
-                }
-                *reinterpret_cast<v2i *>(a.y + n * a.M + ch) = pack4_i16(o[0], o[1], o[2], o[3]);
-            };
-            if (even && n0 + FT <= a.N) { // no control flow around the stores (see vm_wait above)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) group(g);
-            } else {
-                if (n < a.N) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g)
-                        if (ch0 + 8 * g < a.M) group(g);
-                }
-                prologue_loads_done(); // nothing in flight behind a conditional store
-            }
-        }
-        PHASE_MARK(6, pk[15]); // epilogue arithmetic done, stores issued
-        __syncthreads(); // planes are single-buffered
-    }
-    PHASE_DUMP;
-    if (__any(wide) && l == 0) atomicOr(a.status, ST_WIDE_INPUT);
-    if (!ext) return;
-    // ---- extremes: fold the 32 frame lanes of each half wave, then the waves of the workgroup (LDS), then one
-    // atomic per channel and bound
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        uint32_t v = pk[i];
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) {
-            const uint32_t w = (uint32_t)__shfl_xor((int)v, o, 64);
-            const uint32_t lo16 = (v & 0xffffu) > (w & 0xffffu) ? (v & 0xffffu) : (w & 0xffffu);
-            const uint32_t hi16 = (v >> 16) > (w >> 16) ? (v >> 16) : (w >> 16);
-            v = lo16 | (hi16 << 16);
-        }
-        const int ch = ch0 + 8 * (i >> 2) + (i & 3);
-        if (r == 0 && ch < a.M) {
-            atomicMax(&ehi[ch], v & 0xffffu);
-            atomicMax(&elo[ch], v >> 16);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < a.M) { // max = ehi, min = 65535 - elo; as the positive floats of mfma_bn.hpp
-        const int c = threadIdx.x;
-        uint32_t *dst = reinterpret_cast<uint32_t *>(ext) + (ext_reps > 1 ? (int)(blockIdx.x % ext_reps) : 0) * 2 * a.M;
-        atomicMax(dst + c, __float_as_uint(EXT_BIAS - (float)(65535 - (int)elo[c])));
-        atomicMax(dst + a.M + c, __float_as_uint(EXT_BIAS + (float)ehi[c]));
-    }
+    constexpr bool F32 = false;
+#include "proj_enc_body.inc"
 }
 
 // k_enc_p for a float32 input (s5fxp_model_forward_f32): a.x holds float rows -- the same 4 bytes per element, so loads,
 // LDS and stores are k_enc_p's.  Each element is first quantised to (xb, xe) as fxp_from_fp with FLOOR does it
-// (fxprun.py:69-75, fxp_prims.hpp fromfp), then takes k_enc_p's change_cfg and int16 check.  A copy of k_enc_p rather than
-// a shared body: k_enc_p keeps its code as it is.
+// (fxprun.py:69-75, fxp_prims.hpp fromfp), then takes k_enc_p's change_cfg and int16 check.  The body is shared as text,
+// not as a function: with it in a forceinline function template called from thin kernels all 24 encoder / decoder kernels
+// compiled to other code (4 to 238 instructions each, the int ones included), with the include every kernel of the library
+// keeps its instruction stream (tools/disasm_compare.py) -- these kernels sit at their register caps and wait by
+// hand-counted vmcnt.
 template <int NT>
 __global__ __launch_bounds__(384, 3) void k_enc_pf(EncArgs a, float *ext, int ext_reps, GroupOff go)
 {
-    {
-        const int64_t g = blockIdx.y;
-        gshift(a.x, g * go.x); gshift(a.y, g * go.ws); gshift(a.status, g * go.status); gshift(ext, g * go.ws);
-    }
-    constexpr int KS = 9, FT = 64, KP = 32 * KS + 16, NW = 6, H = 32 * NT;
-    // phase B units (32-frame half, column tile) per wave: NT <= 3: wave -> (half wave / NT, tile wave % NT), one unit;
-    // NT > 3: wave -> tile `wave`, both halves.  UW waves have units: all six at NT = 3 and 6; at NT = 2 and 5 the last
-    // two / the last one sit phase B out (its weights stay per wave: a second tile's would not fit the registers)
-    constexpr int NU = NT <= 3 ? 1 : 2, SUBSTEP = NT <= 3 ? 0 : 1, UW = NT <= 3 ? 2 * NT : NT;
-    static_assert(UW <= NW, "one wave per unit or per column tile");
-    constexpr bool RAGGED = shape_channels(NT) != 32 * NT; // the last column tile is half empty: its stores are conditional
-    constexpr int RPW = (FT + NW - 1) / NW; // rows per wave
-    extern __shared__ __attribute__((aligned(16))) int8_t smem[];
-    int32_t *cs = reinterpret_cast<int32_t *>(smem), *be = cs + H;
-    int8_t *Xh = reinterpret_cast<int8_t *>(be + H), *Xl = Xh + FT * KP;
-    uint32_t *ehi = reinterpret_cast<uint32_t *>(Xl + FT * KP), *elo = ehi + H;
-    const int l = threadIdx.x & 63, r = l & 31, h = l >> 5, wave = threadIdx.x >> 6;
-    const int ct = wave % NT, sub0 = wave / NT, ch0 = 32 * ct + 4 * h;
-    const int64_t tiles = (a.N + FT - 1) / FT;
-    const int K = a.K, rem = K - 256;
-    uint32_t pk[16]; // low half: max, high half: 65535 - min
-#pragma unroll
-    for (int i = 0; i < 16; ++i) pk[i] = 0;
-    v4i wreg[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-        wreg[ks] = *reinterpret_cast<const v4i *>(a.w.wt + (size_t)(32 * ct + r) * a.w.Kp + 32 * ks + 16 * h);
-    for (int i = threadIdx.x; i < H; i += 384) {
-        cs[i] = a.w.cs128[i];
-        be[i] = a.bias_eff[i];
-        ehi[i] = 0;
-        elo[i] = 0;
-    }
-    const CfgOp cv = make_cfg(a.conv != 0, a.xb, a.xe, a.inp_bits, a.inp_exp);
-    const SatB so = sat_bounds(a.out_bits);
-    const float sc = ldexpf(1.f, a.xe); // the float input's quantisation scale
-    // rows wave, wave+6, ... of the tile.  Two workgroups of six waves per CU are three waves per SIMD whatever the kernel
-    // does, so it may hold 168 registers: all of a tile's rows are requested a tile ahead (dim 0.5; the two-unit phase B
-    // of dim 1.0 has no room for that: there the first RA rows are prefetched and the rest requested at the top of phase A).
-    // The prefetch is issued behind the compiler's back (scan_quad.hpp vm_wait): its own wait at the first use -- a tile
-    // later, behind phase B's stores -- would be vmcnt(0), every tile opening with a wait for the previous tile's stores.
-    constexpr int RA = NT <= 3 ? RPW : 3, RB = RPW - RA;
-    v4i rawa[RA], rawb[RB > 0 ? RB : 1];
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    auto row_base = [&](int64_t tl, int i) { // wave-uniform
-        int64_t n = tl * FT + wave_u + NW * i;
-        n = n < a.N ? n : a.N - 1;
-        return reinterpret_cast<const char *>(a.x + n * K);
-    };
-    auto row_ptr = [&](int64_t tl, int i) {
-        return reinterpret_cast<const v4i *>(row_base(tl, i) + 16 * l); // 4-byte aligned 16-byte load
-    };
-    auto convert_row = [&](const v4i &q, int f, bool &wide) {
-        int32_t v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fromfp(__int_as_float(q[e]), sc, a.xb);
-        if (a.conv) { // uniform: usually the input already has the encoder's configuration
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = cv(v[e]);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) wide |= (v[e] != (int32_t)(int16_t)v[e]);
-        const unsigned p01 = perm((unsigned)v[1], (unsigned)v[0], 0x05010400u), p23 = perm((unsigned)v[3], (unsigned)v[2], 0x05010400u);
-        *reinterpret_cast<int32_t *>(Xl + f * KP + 4 * l) = (int32_t)(perm(p23, p01, 0x05040100u) ^ 0x80808080u);
-        *reinterpret_cast<int32_t *>(Xh + f * KP + 4 * l) = (int32_t)perm(p23, p01, 0x07060302u);
-    };
-    int64_t tile = blockIdx.x;
-    if (tile < tiles) {
-#pragma unroll
-        for (int i = 0; i < RA; ++i) rawa[i] = gload16_hidden(row_base(tile, i), 16u * (unsigned)l);
-    }
-    bool wide = false;
-    __syncthreads();
-    PHASE_DECL_F
-    prologue_loads_done();
-    const bool even = a.M == H; // no ragged column tile: full tiles store unconditionally
-    for (; tile < tiles; tile += gridDim.x) {
-        const int64_t n0 = tile * FT;
-        PHASE_MARK_F(0, l); // loop top (includes the previous tile's closing barrier)
-        // ---- phase A
-        // the prefetched rows are older than the previous tile's stores: NU x 4 per wave on the unconditional path (the
-        // conditional one ends with a full wait)
-        vm_wait<RAGGED ? 0 : 4 * NU>(rawa);
-        if constexpr (RB > 0) {
-#pragma unroll
-            for (int i = 0; i < RB; ++i) rawb[i] = *row_ptr(tile, RA + i);
-        }
-#pragma unroll
-        for (int i = 0; i < RA; ++i)
-            if (wave_u + NW * i < FT) convert_row(rawa[i], wave_u + NW * i, wide);
-        PHASE_MARK_F(1, rawa[RA - 1][0]); // prefetched rows converted
-        if constexpr (RB > 0) {
-#pragma unroll
-            for (int i = 0; i < RB; ++i)
-                if (wave_u + NW * (RA + i) < FT) convert_row(rawb[i], wave_u + NW * (RA + i), wide);
-        }
-        PHASE_MARK_F(2, rawb[0][0]); // rows requested at the top (their HBM latency included)
-        for (int e = threadIdx.x; e < FT * rem; e += 384) { // the K-256 tail of every row
-            const int f = e / rem, k = 256 + e % rem;
-            int64_t n = n0 + f;
-            n = n < a.N ? n : a.N - 1;
-            const int32_t v = cv(fromfp(__int_as_float(a.x[n * K + k]), sc, a.xb));
-            wide |= (v != (int32_t)(int16_t)v);
-            Xl[f * KP + k] = (int8_t)((v & 0xff) ^ 0x80);
-            Xh[f * KP + k] = (int8_t)(v >> 8);
-        }
-        if (tile + gridDim.x < tiles) {
-#pragma unroll
-            for (int i = 0; i < RA; ++i) rawa[i] = gload16_hidden(row_base(tile + gridDim.x, i), 16u * (unsigned)l); // in flight during phase B
-        }
-        PHASE_MARK_F(3, l); // tail column + prefetch issue
-        __syncthreads();
-        PHASE_MARK_F(4, l); // mid barrier
-        // ---- phase B
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            if (UW < NW && wave_u >= UW) break;
-            const int sub = sub0 + u * SUBSTEP;
-            const int64_t n = n0 + 32 * sub + r;
-            v16i acc;
-            mfma_planes<KS>(acc, wreg, Xh + (32 * sub + r) * KP + 16 * h, Xl + (32 * sub + r) * KP + 16 * h, cs + ch0);
-            PHASE_MARK_F(5, acc[15]); // operand reads + MFMA chain, complete
-            auto group = [&](int g) {
-                const int ch = ch0 + 8 * g;
-                const v4i bv = *reinterpret_cast<const v4i *>(be + ch);
-                int32_t o[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    int32_t v = sat(asr(acc[4 * g + e], a.rs), so);
-                    v = sat(wadd(v, bv[e]), so);
-                    o[e] = v < 0 ? 0 : v;
-                    // (v, 65535 - v) as a u16 pair; one packed max keeps both running extremes
-                    const uint32_t t = (uint32_t)__umul24((unsigned)o[e], 0x10001u) ^ 0xffff0000u;
-                    pk[4 * g + e] = __builtin_bit_cast(
-                        uint32_t, __builtin_elementwise_max(__builtin_bit_cast(v2u16, pk[4 * g + e]), __builtin_bit_cast(v2u16, t)));
-                }
-                *reinterpret_cast<v2i *>(a.y + n * a.M + ch) = pack4_i16(o[0], o[1], o[2], o[3]);
-            };
-            if (even && n0 + FT <= a.N) { // no control flow around the stores (see vm_wait above)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) group(g);
-            } else {
-                if (n < a.N) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g)
-                        if (ch0 + 8 * g < a.M) group(g);
-                }
-                prologue_loads_done(); // nothing in flight behind a conditional store
-            }
-        }
-        PHASE_MARK_F(6, pk[15]); // epilogue arithmetic done, stores issued
-        __syncthreads(); // planes are single-buffered
-    }
-    PHASE_DUMP_F;
-    if (__any(wide) && l == 0) atomicOr(a.status, ST_WIDE_INPUT);
-    if (!ext) return;
-    // ---- extremes: fold the 32 frame lanes of each half wave, then the waves of the workgroup (LDS), then one
-    // atomic per channel and bound
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        uint32_t v = pk[i];
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) {
-            const uint32_t w = (uint32_t)__shfl_xor((int)v, o, 64);
-            const uint32_t lo16 = (v & 0xffffu) > (w & 0xffffu) ? (v & 0xffffu) : (w & 0xffffu);
-            const uint32_t hi16 = (v >> 16) > (w >> 16) ? (v >> 16) : (w >> 16);
-            v = lo16 | (hi16 << 16);
-        }
-        const int ch = ch0 + 8 * (i >> 2) + (i & 3);
-        if (r == 0 && ch < a.M) {
-            atomicMax(&ehi[ch], v & 0xffffu);
-            atomicMax(&elo[ch], v >> 16);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < a.M) { // max = ehi, min = 65535 - elo; as the positive floats of mfma_bn.hpp
-        const int c = threadIdx.x;
-        uint32_t *dst = reinterpret_cast<uint32_t *>(ext) + (ext_reps > 1 ? (int)(blockIdx.x % ext_reps) : 0) * 2 * a.M;
-        atomicMax(dst + c, __float_as_uint(EXT_BIAS - (float)(65535 - (int)elo[c])));
-        atomicMax(dst + a.M + c, __float_as_uint(EXT_BIAS + (float)ehi[c]));
-    }
+    constexpr bool F32 = true;
+#include "proj_enc_body.inc"
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // where masked-off lanes of a store send their value instead (never read)
@@ -884,337 +444,19 @@ struct DecResid {
 template <int KS, bool RESID = false>
 __global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_p(DecArgs a, DecResid rz, GroupOff go)
 {
-    {
-        const int64_t g = blockIdx.y;
-        gshift(a.x, g * go.ws); gshift(a.y, g * go.y); gshift(a.xe.dyn, g * go.ws); gshift(a.status, g * go.status);
-        if constexpr (RESID) {
-            gshift(rz.z, g * go.ws); gshift_nn(rz.hd.d, g * go.ws); gshift(rz.hd.skip_e.dyn, g * go.ws);
-            gshift_nn(rz.hd.status_exps, g * go.status);
-        }
-    }
-    // H: the real channels (row stride, vectors per frame); HP: the k extent of the byte planes (shape_channels)
-    constexpr int H = shape_channels(KS), HP = 32 * KS, FT = 64, KP = HP + 16, NW = 6, CT = 9, CPW = 3;
-    constexpr int VPF = H / 8, NV = FT * VPF / 384;
-    constexpr bool USUM = RESID && KS == 3; // the one-plane route exists where the 32-frame gate kernel does: H = 96 (DecResid::usum)
-    static_assert(FT * VPF % 384 == 0, "tile shape");
-    extern __shared__ __attribute__((aligned(16))) int8_t smem[];
-    int8_t *Xh = smem, *Xl = Xh + FT * KP;
-    zero_plane_tail<H, HP, KP>(Xh, 2 * FT); // (visible behind the first tile's barrier)
-    const int l = threadIdx.x & 63, r = l & 31, h = l >> 5, wave = threadIdx.x >> 6;
-    const int sub = wave / 3, c0 = wave % 3;
-    const int64_t tiles = (a.N + FT - 1) / FT;
-    AddCb rp{};
-    if constexpr (RESID) {
-        __shared__ AddCb sp;
-        if (rz.hd.enable) {
-            if (threadIdx.x == 0) {
-                sp = finalize_add_cb(rz.hd.d->mx + (rz.hd.d->redo ? rz.hd.redo_slot : 8), rz.hd.res_exp, rz.hd.skip_e.get(), rz.res_bits, a.status);
-                if (blockIdx.x == 0) {
-                    rz.hd.d->res = sp;
-                    rz.hd.status_exps[4] = sp.eo;
-                }
-            }
-            __syncthreads();
-            rp = sp;
-        } else {
-            rp = rz.hd.d->res;
-        }
-    }
-    const int xe0 = RESID ? rp.eo : a.xe.get();
-    const bool conv = a.xb > a.inp_bits || xe0 > a.inp_exp;
-    int rs = (conv ? a.inp_exp : xe0) + a.w_exp - a.out_exp;
-    if (rs < 0 || rs > 31) {
-        if (threadIdx.x == 0 && blockIdx.x == 0) atomicOr(a.status, ST_NEGSHIFT);
-        rs = rs < 0 ? 0 : 31;
-    }
-    const CfgOp cv = make_cfg(conv, a.xb, xe0, a.inp_bits, a.inp_exp);
-    const SatB so = sat_bounds(a.out_bits);
-    AddCbV rpv{};
-    if constexpr (RESID) rpv = make_add_cb_v(rp, rz.res_bits, rz.skip_bits, rz.res_bits);
-    v4i wreg[CPW][KS];
-    int32_t csv[CPW], bev[CPW];
-#pragma unroll
-    for (int c = 0; c < CPW; ++c) {
-        const int col = 32 * (c0 + 3 * c) + r;
-        csv[c] = a.w.cs128[col];
-        bev[c] = a.bias_eff[col];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-            wreg[c][ks] = *reinterpret_cast<const v4i *>(a.w.wt + (size_t)col * a.w.Kp + 32 * ks + 16 * h);
-    }
-    v4i raw[NV], rawz[RESID ? NV : 1];
-    auto fetch = [&](int64_t tl) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int v = threadIdx.x + 384 * i;
-            const int64_t left = a.N - tl * FT; // frames from the tile's first to the end of the tensor (wave-uniform)
-            int f = v / VPF;
-            f = f < left ? f : (int)left - 1;
-            if (RESID && !(USUM && rz.usum))
-                rawz[i] = gload16_hidden(reinterpret_cast<const char *>(rz.z + tl * FT * H), 2u * (unsigned)(f * H + 8 * (v % VPF)));
-            // issued behind the compiler's back (see vm_wait): its wait-count pass would otherwise guard the first use of
-            // these registers, a tile later, with vmcnt(0) -- behind the 48 stores of this tile's phase B
-            raw[i] = gload16_hidden(reinterpret_cast<const char *>(a.x + tl * FT * H), 2u * (unsigned)(f * H + 8 * (v % VPF)));
-        }
-    };
-    int64_t tile = blockIdx.x;
-    if (tile < tiles) fetch(tile);
-    prologue_loads_done();
-    for (; tile < tiles; tile += gridDim.x) {
-        const int64_t n0 = tile * FT;
-        // the prefetched rows are older than the previous tile's 3 x 16 stores per wave (every tile but the tensor's last is
-        // full and stores unconditionally; that last one has no successor)
-        vm_wait<3 * 16>(raw);
-        if (RESID && !(USUM && rz.usum)) vm_wait<3 * 16>(rawz);
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int v = threadIdx.x + 384 * i, f = v / VPF, og = v % VPF;
-            int32_t x[8];
-            if (USUM && rz.usum) {
-                unpack8_u16(raw[i], x);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) x[e] = resolve_u16(x[e], rpv.lsh, rpv.rsh, rpv.so);
-            } else if constexpr (!RESID) {
-                unpack8_i16(raw[i], x);
-            } else {
-                unpack8_i16(raw[i], x);
-                int32_t z[8];
-                unpack8_i16(rawz[i], z);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int32_t rr = add_cb_apply(z[e], x[e], rpv);
-                    x[e] = rr < 0 ? 0 : rr;
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = cv(x[e]);
-            v2i hi, lo;
-            planes8_from_i32(x, hi, lo);
-            *reinterpret_cast<v2i *>(Xh + f * KP + 8 * og) = hi;
-            *reinterpret_cast<v2i *>(Xl + f * KP + 8 * og) = lo;
-        }
-        if (tile + gridDim.x < tiles) fetch(tile + gridDim.x);
-        __syncthreads();
-        const int8_t *rowh = Xh + (32 * sub + r) * KP + 16 * h, *rowl = Xl + (32 * sub + r) * KP + 16 * h;
-        const int64_t nb = n0 + 32 * sub + 4 * h; // frame of accumulator register 0
-#pragma unroll
-        for (int c = 0; c < CPW; ++c) {
-            const int col = 32 * (c0 + 3 * c) + r;
-            v16i acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(*reinterpret_cast<const v4i *>(rowh + 32 * ks), wreg[c][ks], acc, 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = wadd(wshl(acc[i], 8), csv[c]);
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(*reinterpret_cast<const v4i *>(rowl + 32 * ks), wreg[c][ks], acc, 0, 0, 0);
-            // Stores without control flow around them on full tiles (all but the tensor's last): lanes of the ragged last
-            // column tile (col >= M) write to a sink word instead of being masked off.  Every conditional store would make
-            // the number of memory operations in flight unknowable to the compiler's wait-count pass, and the wait it
-            // then puts at the top of the next tile -- for the rows prefetched BEFORE these stores -- degenerates to
-            // vmcnt(0): every tile would begin by waiting for the previous tile's stores to be acknowledged.
-            const bool okc = col < a.M;
-            char *yl = okc ? reinterpret_cast<char *>(a.y + n0 * a.M) + 4u * (unsigned)((32 * sub + 4 * h) * a.M + col)
-                           : reinterpret_cast<char *>(as_global(&g_store_sink[l]));
-            const unsigned ystep = okc ? 4u * (unsigned)a.M : 0u;
-            if (n0 + FT <= a.N) {
-                char *yp = yl; // a running pointer: sixteen hoisted offsets per column tile would cost the kernel its occupancy
-#pragma unroll
-                for (int i = 0; i < 16; ++i) { // frames (i & 3) + 8 * (i >> 2)
-                    const int32_t v = sat(asr(acc[i], rs), so);
-                    *reinterpret_cast<int32_t *>(yp) = sat(wadd(v, bev[c]), so);
-                    yp += (i & 3) == 3 ? 5 * ystep : ystep;
-                }
-            } else {
-                char *yp = yl;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int fo = (i & 3) + 8 * (i >> 2);
-                    if (nb + fo < a.N) {
-                        const int32_t v = sat(asr(acc[i], rs), so);
-                        *reinterpret_cast<int32_t *>(yp) = sat(wadd(v, bev[c]), so);
-                    }
-                    yp += (i & 3) == 3 ? 5 * ystep : ystep;
-                }
-                prologue_loads_done(); // the tensor's last tile: nothing is left in flight on this path
-            }
-            __builtin_amdgcn_sched_barrier(0); // one column tile at a time: interleaved, the three of a wave do not fit its registers
-        }
-        __syncthreads(); // planes are single-buffered
-    }
+    constexpr bool F32 = false;
+#include "proj_dec_body.inc"
 }
 
 // k_dec_p with a float32 output (s5fxp_model_forward_f32): every value is stored as to_float of k_dec_p's result
 // (fxparray.py:72-73, fxp_prims.hpp tofloat, rounded as k_to_float rounds), one 4-byte store per value on the same
-// addresses, so the store count per tile (vm_wait<48>) holds; ragged column tiles still go to g_store_sink.  A copy of
-// k_dec_p rather than a shared body: k_dec_p keeps its code as it is.
+// addresses, so the store count per tile (vm_wait<48>) holds; ragged column tiles still go to g_store_sink.  One body,
+// shared as text for the reason given at k_enc_pf.
 template <int KS, bool RESID>
 __global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_pf(DecArgs a, DecResid rz, GroupOff go)
 {
-    {
-        const int64_t g = blockIdx.y;
-        gshift(a.x, g * go.ws); gshift(a.y, g * go.y); gshift(a.xe.dyn, g * go.ws); gshift(a.status, g * go.status);
-        if constexpr (RESID) {
-            gshift(rz.z, g * go.ws); gshift_nn(rz.hd.d, g * go.ws); gshift(rz.hd.skip_e.dyn, g * go.ws);
-            gshift_nn(rz.hd.status_exps, g * go.status);
-        }
-    }
-    // H: the real channels (row stride, vectors per frame); HP: the k extent of the byte planes (shape_channels)
-    constexpr int H = shape_channels(KS), HP = 32 * KS, FT = 64, KP = HP + 16, NW = 6, CT = 9, CPW = 3;
-    constexpr int VPF = H / 8, NV = FT * VPF / 384;
-    constexpr bool USUM = RESID && KS == 3; // the one-plane route exists where the 32-frame gate kernel does: H = 96 (DecResid::usum)
-    static_assert(FT * VPF % 384 == 0, "tile shape");
-    extern __shared__ __attribute__((aligned(16))) int8_t smem[];
-    int8_t *Xh = smem, *Xl = Xh + FT * KP;
-    zero_plane_tail<H, HP, KP>(Xh, 2 * FT); // (visible behind the first tile's barrier)
-    const int l = threadIdx.x & 63, r = l & 31, h = l >> 5, wave = threadIdx.x >> 6;
-    const int sub = wave / 3, c0 = wave % 3;
-    const int64_t tiles = (a.N + FT - 1) / FT;
-    AddCb rp{};
-    if constexpr (RESID) {
-        __shared__ AddCb sp;
-        if (rz.hd.enable) {
-            if (threadIdx.x == 0) {
-                sp = finalize_add_cb(rz.hd.d->mx + (rz.hd.d->redo ? rz.hd.redo_slot : 8), rz.hd.res_exp, rz.hd.skip_e.get(), rz.res_bits, a.status);
-                if (blockIdx.x == 0) {
-                    rz.hd.d->res = sp;
-                    rz.hd.status_exps[4] = sp.eo;
-                }
-            }
-            __syncthreads();
-            rp = sp;
-        } else {
-            rp = rz.hd.d->res;
-        }
-    }
-    const int xe0 = RESID ? rp.eo : a.xe.get();
-    const bool conv = a.xb > a.inp_bits || xe0 > a.inp_exp;
-    int rs = (conv ? a.inp_exp : xe0) + a.w_exp - a.out_exp;
-    if (rs < 0 || rs > 31) {
-        if (threadIdx.x == 0 && blockIdx.x == 0) atomicOr(a.status, ST_NEGSHIFT);
-        rs = rs < 0 ? 0 : 31;
-    }
-    const CfgOp cv = make_cfg(conv, a.xb, xe0, a.inp_bits, a.inp_exp);
-    const SatB so = sat_bounds(a.out_bits);
-    AddCbV rpv{};
-    if constexpr (RESID) rpv = make_add_cb_v(rp, rz.res_bits, rz.skip_bits, rz.res_bits);
-    v4i wreg[CPW][KS];
-    int32_t csv[CPW], bev[CPW];
-#pragma unroll
-    for (int c = 0; c < CPW; ++c) {
-        const int col = 32 * (c0 + 3 * c) + r;
-        csv[c] = a.w.cs128[col];
-        bev[c] = a.bias_eff[col];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-            wreg[c][ks] = *reinterpret_cast<const v4i *>(a.w.wt + (size_t)col * a.w.Kp + 32 * ks + 16 * h);
-    }
-    v4i raw[NV], rawz[RESID ? NV : 1];
-    auto fetch = [&](int64_t tl) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int v = threadIdx.x + 384 * i;
-            const int64_t left = a.N - tl * FT; // frames from the tile's first to the end of the tensor (wave-uniform)
-            int f = v / VPF;
-            f = f < left ? f : (int)left - 1;
-            if (RESID && !(USUM && rz.usum))
-                rawz[i] = gload16_hidden(reinterpret_cast<const char *>(rz.z + tl * FT * H), 2u * (unsigned)(f * H + 8 * (v % VPF)));
-            // issued behind the compiler's back (see vm_wait): its wait-count pass would otherwise guard the first use of
-            // these registers, a tile later, with vmcnt(0) -- behind the 48 stores of this tile's phase B
-            raw[i] = gload16_hidden(reinterpret_cast<const char *>(a.x + tl * FT * H), 2u * (unsigned)(f * H + 8 * (v % VPF)));
-        }
-    };
-    int64_t tile = blockIdx.x;
-    if (tile < tiles) fetch(tile);
-    prologue_loads_done();
-    for (; tile < tiles; tile += gridDim.x) {
-        const int64_t n0 = tile * FT;
-        // the prefetched rows are older than the previous tile's 3 x 16 stores per wave (every tile but the tensor's last is
-        // full and stores unconditionally; that last one has no successor)
-        vm_wait<3 * 16>(raw);
-        if (RESID && !(USUM && rz.usum)) vm_wait<3 * 16>(rawz);
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int v = threadIdx.x + 384 * i, f = v / VPF, og = v % VPF;
-            int32_t x[8];
-            if (USUM && rz.usum) {
-                unpack8_u16(raw[i], x);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) x[e] = resolve_u16(x[e], rpv.lsh, rpv.rsh, rpv.so);
-            } else if constexpr (!RESID) {
-                unpack8_i16(raw[i], x);
-            } else {
-                unpack8_i16(raw[i], x);
-                int32_t z[8];
-                unpack8_i16(rawz[i], z);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int32_t rr = add_cb_apply(z[e], x[e], rpv);
-                    x[e] = rr < 0 ? 0 : rr;
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = cv(x[e]);
-            v2i hi, lo;
-            planes8_from_i32(x, hi, lo);
-            *reinterpret_cast<v2i *>(Xh + f * KP + 8 * og) = hi;
-            *reinterpret_cast<v2i *>(Xl + f * KP + 8 * og) = lo;
-        }
-        if (tile + gridDim.x < tiles) fetch(tile + gridDim.x);
-        __syncthreads();
-        const int8_t *rowh = Xh + (32 * sub + r) * KP + 16 * h, *rowl = Xl + (32 * sub + r) * KP + 16 * h;
-        const int64_t nb = n0 + 32 * sub + 4 * h; // frame of accumulator register 0
-#pragma unroll
-        for (int c = 0; c < CPW; ++c) {
-            const int col = 32 * (c0 + 3 * c) + r;
-            v16i acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(*reinterpret_cast<const v4i *>(rowh + 32 * ks), wreg[c][ks], acc, 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = wadd(wshl(acc[i], 8), csv[c]);
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(*reinterpret_cast<const v4i *>(rowl + 32 * ks), wreg[c][ks], acc, 0, 0, 0);
-            // Stores without control flow around them on full tiles (all but the tensor's last): lanes of the ragged last
-            // column tile (col >= M) write to a sink word instead of being masked off.  Every conditional store would make
-            // the number of memory operations in flight unknowable to the compiler's wait-count pass, and the wait it
-            // then puts at the top of the next tile -- for the rows prefetched BEFORE these stores -- degenerates to
-            // vmcnt(0): every tile would begin by waiting for the previous tile's stores to be acknowledged.
-            const bool okc = col < a.M;
-            char *yl = okc ? reinterpret_cast<char *>(a.y + n0 * a.M) + 4u * (unsigned)((32 * sub + 4 * h) * a.M + col)
-                           : reinterpret_cast<char *>(as_global(&g_store_sink[l]));
-            const unsigned ystep = okc ? 4u * (unsigned)a.M : 0u;
-            if (n0 + FT <= a.N) {
-                char *yp = yl; // a running pointer: sixteen hoisted offsets per column tile would cost the kernel its occupancy
-#pragma unroll
-                for (int i = 0; i < 16; ++i) { // frames (i & 3) + 8 * (i >> 2)
-                    const int32_t v = sat(asr(acc[i], rs), so);
-                    *reinterpret_cast<float *>(yp) = tofloat(sat(wadd(v, bev[c]), so), a.out_exp);
-                    yp += (i & 3) == 3 ? 5 * ystep : ystep;
-                }
-            } else {
-                char *yp = yl;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int fo = (i & 3) + 8 * (i >> 2);
-                    if (nb + fo < a.N) {
-                        const int32_t v = sat(asr(acc[i], rs), so);
-                        *reinterpret_cast<float *>(yp) = tofloat(sat(wadd(v, bev[c]), so), a.out_exp);
-                    }
-                    yp += (i & 3) == 3 ? 5 * ystep : ystep;
-                }
-                prologue_loads_done(); // the tensor's last tile: nothing is left in flight on this path
-            }
-            __builtin_amdgcn_sched_barrier(0); // one column tile at a time: interleaved, the three of a wave do not fit its registers
-        }
-        __syncthreads(); // planes are single-buffered
-    }
+    constexpr bool F32 = true;
+#include "proj_dec_body.inc"
 }
 
 

@@ -735,11 +735,7 @@ struct FusedForward {
         }
         a.lazy = h_lazy;
         a.t_lo = 0; a.t_len = L;
-#ifdef S5_BPROJ_CSR
-        const size_t smem = 16 * (size_t)sh.hp + 4 * 64 * (size_t)(sh.hp + 16) + 2 * (size_t)(2 * m->P) * S5_BPROJ_CSR + 64; // + compressed columns
-#else
         const size_t smem = 16 * (size_t)sh.hp + 4 * 64 * (size_t)(sh.hp + 16); // BN operands + double-buffered byte planes
-#endif
         // phase-split kernel (proj_p.hpp), one wave per 32-column tile of [B_re | B_im]; SM: the stream the recurrence rung
         // wants; a compacted layer has fewer column tiles (NC)
         const Rung &r = p.rung;

@@ -88,12 +88,6 @@ __device__ __forceinline__ v4i_ gload16_hidden(const char *base, unsigned off)
     asm volatile("global_load_dwordx4 %0, %1, %2" : "=&v"(r) : "v"(off), "s"(base) : "memory");
     return r;
 }
-__device__ __forceinline__ __attribute__((ext_vector_type(2))) int gload8_hidden(const char *base, unsigned off)
-{
-    __attribute__((ext_vector_type(2))) int r;
-    asm volatile("global_load_dwordx2 %0, %1, %2" : "=&v"(r) : "v"(off), "s"(base) : "memory");
-    return r;
-}
 template <int NEWER, class T, int N>
 __device__ __forceinline__ void vm_wait(T (&regs)[N])
 {
@@ -102,16 +96,6 @@ __device__ __forceinline__ void vm_wait(T (&regs)[N])
     // volatile statements keep their order: every later reader of a register depends on its pass through here
 #pragma unroll
     for (int i = 0; i < N; ++i) asm volatile("" : "+v"(regs[i]));
-}
-template <int NEWER, class T, int N, int M>
-__device__ __forceinline__ void vm_wait(T (&regs)[N][M])
-{
-    static_assert(NEWER >= 0 && NEWER < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" : : "n"(NEWER) : "memory");
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int j = 0; j < M; ++j) asm volatile("" : "+v"(regs[i][j]));
 }
 
 // word index of (sequence b, step t, state p, component c) in a scan-native stream with TB blocks/sequence

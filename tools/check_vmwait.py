@@ -12,8 +12,7 @@ copy, spill or reuse them before the data has landed.  The register audit follow
 tile is waited for at the top of the next -- to the wait that guards it (the hand-written s_waitcnt vmcnt(N), or a compiler wait
 that leaves no more memory operations outstanding than were issued after the load), and fails if an instruction outside the inline-assembly blocks reads or writes one of its destination VGPRs on the
 way.  It also reports .private_segment_fixed_size and .vgpr_spill_count of every kernel with hidden loads.  It audits
-every kernel of the default build that has hidden loads (today k_enc_p, k_dec_p and the pair recurrence kernels); the gate
-kernel's gload8_hidden prefetches exist only in the -DS5_CGATE_HID=1 experiment build, which this script does not compile.
+every kernel of the library that has hidden loads (today k_enc_p, k_dec_p, their float twins and the pair recurrence kernels).
   python tools/check_vmwait.py [--asm FILE.s]    (--asm: audit a given assembly file instead of compiling the library)
 Exit code 0 = consistent."""
 import os
@@ -29,7 +28,7 @@ EXPECT = {
     "_ZN2s57k_dec_pILi3ELb0EE": (48, 0), "_ZN2s57k_dec_pILi6ELb0EE": (48, 0),
     "_ZN2s57k_dec_pILi3ELb1EE": (48, 2), "_ZN2s57k_dec_pILi6ELb1EE": (48, 2),
     "_ZN2s57k_enc_pILi3EE": (4, 0), "_ZN2s57k_enc_pILi6EE": (8, 0),
-    # the float-in / float-out copies of those kernels (proj_p.hpp k_enc_pf / k_dec_pf): the same stores
+    # float in / float out (proj_p.hpp k_enc_pf / k_dec_pf: the same bodies, proj_enc_body.inc / proj_dec_body.inc): the same stores
     "_ZN2s58k_dec_pfILi3ELb0EE": (48, 0), "_ZN2s58k_dec_pfILi6ELb0EE": (48, 0),
     "_ZN2s58k_dec_pfILi3ELb1EE": (48, 2), "_ZN2s58k_dec_pfILi6ELb1EE": (48, 2),
     "_ZN2s58k_enc_pfILi3EE": (4, 0), "_ZN2s58k_enc_pfILi6EE": (8, 0),

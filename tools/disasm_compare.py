@@ -2,9 +2,10 @@
 """Per-kernel comparison of two device assemblies of the library's translation unit.
 
 usage: hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S -o A.s sparsernns_amd/csrc/s5fxp_api.hip   (each tree)
-       tools/disasm_compare.py PARENT.s NEW.s
+       tools/disasm_compare.py [--strict] PARENT.s NEW.s
 Per kernel the instruction text (labels renumbered, comments and directives dropped) is compared; prints the kernels whose
-streams differ, with the number of differing instructions, and those only one side has.  No GPU needed."""
+streams differ, with the number of differing instructions, and those only one side has.  --strict: exit status 1 when any
+kernel's stream differs or exists on one side only (the gate of a refactor that must not change device code).  No GPU needed."""
 import difflib
 import re
 import subprocess
@@ -47,7 +48,8 @@ def short(n):
 
 
 def main():
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    args = [x for x in sys.argv[1:] if x != "--strict"]
+    a, b = kernels(args[0]), kernels(args[1])
     both = [k for k in a if k in b]
     same = [k for k in both if a[k] == b[k]]
     print(f"kernels: parent {len(a)}, this commit {len(b)}; identical instruction streams: {len(same)}")
@@ -63,7 +65,8 @@ def main():
             print(f"\n{title}:")
             for k in only:
                 print(f"  {k}: {len(x[k])} instructions")
+    return 1 if "--strict" in sys.argv[1:] and not len(same) == len(a) == len(b) else 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
