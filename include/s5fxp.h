@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define S5FXP_VERSION 108
+#define S5FXP_VERSION 109
 
 enum {
     S5FXP_OK = 0,
@@ -138,6 +138,15 @@ int s5fxp_stft_mag(const float *audio, int B, int64_t T, float sub, float *x, fl
  * No atomics: two calls give identical bits. */
 int s5fxp_mask_istft(const float *audio, const float *mask, int B, int64_t T, float *out, float *cleaned_mag,
                      void *stream);
+
+/* The two steps with the model's int16 boundary (s5fxp_model_forward_i16) on the model's side: 2 bytes per value instead of 4.
+ * x: (B,n_seg,257) int16 = fxp_from_fp(|Z| - sub, FLOOR) at (x_bits 1..16, x_exp 0..31) of the very float s5fxp_stft_mag
+ * stores; mask: (B,n_seg,257) int16 at mask_exp 0..31 (the model's output exponent) or NULL, used as 1 + to_float(mask).  Both
+ * conversions restate 16-bit integers, so out and cleaned_mag are bit for bit what s5fxp_stft_mag -> s5fxp_model_forward_f32 ->
+ * s5fxp_mask_istft give.  Widths or exponents outside those ranges: S5FXP_EBADARG, before the device is touched. */
+int s5fxp_stft_mag_i16(const float *audio, int B, int64_t T, float sub, int x_bits, int x_exp, int16_t *x, float *spec, void *stream);
+int s5fxp_mask_istft_i16(const float *audio, const int16_t *mask, int mask_exp, int B, int64_t T, float *out, float *cleaned_mag,
+                         void *stream);
 
 /* The same framing for a live signal: whole hops of 128 samples in, cleaned hops out (a caller zero-fills its last hop, as
  * scipy's padded=True does).  S streams advance in lock step.  With h = hops_before hops received and a push of c hops
@@ -351,6 +360,21 @@ int s5fxp_model_forward_f32(const s5fxp_model *m, const float *x, int x_bits, in
 /* Device workspace for one s5fxp_model_forward_f32 of B sequences of L frames: s5fxp_workspace_bytes for a model on the fused
  * path, plus the staged int32 input and output for a generic one.  0: bad argument. */
 size_t s5fxp_workspace_bytes_f32(const s5fxp_model *m, int B, int L);
+
+/* The same forward with an int16 model boundary: x (B,L,d_in) int16 device at (x_bits 1..16, x_exp), y (B,L,d_out) int16 device.
+ * Bit for bit what s5fxp_model_forward gives for the sign-extended x -- y narrowed to int16, status words, traces and state_out
+ * -- for every opts setting the int entry takes.  The narrowing loses nothing: a model whose decoder has out_bits > 16 returns
+ * S5FXP_EUNSUPPORTED, and whatever the int entry rejects returns S5FXP_EBADARG, both before the device is touched.
+ * x and y need 2-byte alignment only: rows are 2 * d_in / 2 * d_out bytes (514 at 257 columns) and the groups of a grouped
+ * call follow each other densely, so a group's base may be an odd number of int16.  On the fused path the encoder reads and the
+ * decoder writes int16 directly (no extra launch or pass; the int forward's grids and workspace); elsewhere int32 copies are
+ * staged in the workspace.  workspace_bytes >= G * s5fxp_workspace_bytes_i16(m, B, L). */
+int s5fxp_model_forward_i16(const s5fxp_model *m, const int16_t *x, int x_bits, int x_exp, int B, int L, int16_t *y,
+                            void *workspace, size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces,
+                            const s5fxp_forward_opts *opts, void *stream);
+/* Device workspace for one s5fxp_model_forward_i16: s5fxp_workspace_bytes for a model on the fused path, plus the staged int32
+ * input and output for a generic one.  0: bad argument. */
+size_t s5fxp_workspace_bytes_i16(const s5fxp_model *m, int B, int L);
 
 /* Environment (experiments and tests only; read ONCE by s5fxp_model_create and stored in the handle, never by a forward):
  *   S5FXP_NO_PAIR, S5FXP_PAIR_GLOBAL, S5FXP_PAIRL_BLOCKS=16   recurrence kernel choice (see s5fxp_model_recurrence_kernel)

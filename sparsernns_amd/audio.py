@@ -169,14 +169,84 @@ def mask_istft(audio: torch.Tensor, mask, cleaned_mag: bool = False):
     return (out, cm) if cleaned_mag else out
 
 
-def denoise_fused(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor):
+def _int16_range(bits: int, exp: int, what: str) -> None:
+    if not 1 <= int(bits) <= 16 or not 0 <= int(exp) <= 31:
+        raise ValueError(f"{what}: bits must be 1..16 and the exponent 0..31, got ({bits}, {exp})")
+
+
+def stft_mag_i16(audio: torch.Tensor, x_bits: int, x_exp: int, sub: float = STFT_MAG_MEAN, spectrum: bool = False):
+    """``stft_mag`` with the model's int16 boundary: x = fxp_from_fp(|Z| - sub, FLOOR) at (x_bits <= 16, x_exp) as an int16
+    tensor (B, n_seg, 257) -- exactly ``fxp_from_fp(stft_mag(audio, sub), bits=x_bits, exp=x_exp, FLOOR).data`` in half the
+    bytes of the float rows, which are never written."""
+    _int16_range(x_bits, x_exp, "stft_mag_i16")
+    audio = _audio2d(audio)
+    B, T = audio.shape
+    n_seg = stft_frames(T)
+    if not audio.is_cuda:
+        r = stft_mag(audio, sub, spectrum)
+        xf, z = r if spectrum else (r, None)
+        # fxp_from_fp with FLOOR (fxparray.py:287-307) in torch: the scale is a power of two, so the float32 product is exact
+        hi = float((1 << (int(x_bits) - 1)) - 1)
+        q = torch.floor(xf * float(2.0 ** int(x_exp)))
+        x = torch.nan_to_num(q, nan=0.0, posinf=hi, neginf=-hi - 1.0).clamp(-hi - 1.0, hi).to(torch.int16)
+        return (x, z) if spectrum else x
+    from . import _lib
+    x = torch.empty(B, n_seg, NFFT // 2 + 1, dtype=torch.int16, device=audio.device)
+    spec = torch.empty(B, n_seg, NFFT // 2 + 1, dtype=torch.complex64, device=audio.device) if spectrum else None
+    with torch.cuda.device(audio.device):
+        _lib.check(_lib.lib.s5fxp_stft_mag_i16(audio.data_ptr(), B, T, float(sub), int(x_bits), int(x_exp), x.data_ptr(),
+                                               spec.data_ptr() if spectrum else None,
+                                               torch.cuda.current_stream().cuda_stream), "s5fxp_stft_mag_i16")
+    return (x, spec) if spectrum else x
+
+
+def mask_istft_i16(audio: torch.Tensor, mask: torch.Tensor, mask_exp: int, cleaned_mag: bool = False):
+    """``mask_istft`` for a mask as the model's decoder leaves it: int16 (B, n_seg, 257) at ``mask_exp``.  The factor is
+    1 + to_float(mask), so the results are bit for bit ``mask_istft(audio, FxpArray(mask, 16, mask_exp).to_float())``."""
+    _int16_range(16, mask_exp, "mask_istft_i16")
+    audio = _audio2d(audio)
+    B, T = audio.shape
+    n_seg = stft_frames(T)
+    shape = (B, n_seg, NFFT // 2 + 1)
+    if mask.dtype != torch.int16 or tuple(mask.shape) != shape or mask.device != audio.device:
+        raise ValueError(f"mask must be int16 {shape} on {audio.device}, got {mask.dtype} {tuple(mask.shape)} on {mask.device}")
+    mask = mask.contiguous()
+    if not audio.is_cuda:
+        return mask_istft(audio, torch.ldexp(mask.to(torch.float32), torch.tensor(-int(mask_exp))), cleaned_mag)
+    from . import _lib
+    out = torch.empty(B, (n_seg - 1) * HOP, dtype=torch.float32, device=audio.device)
+    cm = torch.empty(shape, dtype=torch.float32, device=audio.device) if cleaned_mag else None
+    with torch.cuda.device(audio.device):
+        _lib.check(_lib.lib.s5fxp_mask_istft_i16(audio.data_ptr(), mask.data_ptr(), int(mask_exp), B, T, out.data_ptr(),
+                                                 cm.data_ptr() if cleaned_mag else None,
+                                                 torch.cuda.current_stream().cuda_stream), "s5fxp_mask_istft_i16")
+    return (out, cm) if cleaned_mag else out
+
+
+def denoise_fused(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, boundary: str = "float32"):
     """fxprun.py:63-78 as stft_mag -> model -> mask_istft: noisy audio (B, T) -> (cleaned audio, cleaned magnitude, x, mask),
     the last three (B, n_seg, 257).  On a GPU that is two launches plus the forward.
+
+    boundary="int16": the rows cross the model's boundary as int16 (stft_mag_i16 -> model.forward_int16 -> mask_istft_i16), 2
+    bytes per value instead of 4, and ``x`` / ``mask`` come back as int16 tensors at (inp_bits, inp_exp) / the model's output
+    exponent.  The cleaned audio and magnitude are bit for bit the default route's: float32 restates the same 16-bit integers.
+    It needs a model with ``forward_int16`` (and ``engine()`` or an ``out_exp`` attribute) and an output of at most 16 bits;
+    a model that stores intermediates (the op-by-op path, which the default route takes for it) is refused with ValueError.
 
     NOT bit-identical to ``denoise``: two FFT implementations differ in the last bits of |Z|, and the FLOOR quantiser turns a
     few of those differences into one LSB of the model's input.  The model itself stays exact on the ``x`` returned here."""
     from .fxparray import RoundingMode, fxp_from_fp
 
+    if boundary not in ("float32", "int16"):
+        raise ValueError(f'boundary must be "float32" or "int16", got {boundary!r}')
+    if boundary == "int16":
+        if getattr(model, "store_intermediates", False):
+            raise ValueError("a model that stores intermediates runs op by op on FxpArrays: use the float32 boundary")
+        x = stft_mag_i16(noisy, inp_bits, inp_exp)
+        mask = model.forward_int16(x, inp_bits, inp_exp)
+        out_exp = model.out_exp if hasattr(model, "out_exp") else model.engine().out_exp
+        cleaned, cleaned_mag = mask_istft_i16(noisy, mask, out_exp, cleaned_mag=True)
+        return cleaned, cleaned_mag, x, mask
     x = stft_mag(noisy)
     if hasattr(model, "forward_float") and not getattr(model, "store_intermediates", False) and _takes(model, inp_bits, inp_exp):
         mask = model.forward_float(x)
@@ -187,11 +257,12 @@ def denoise_fused(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor):
     return cleaned, cleaned_mag, x, mask
 
 
-def validate_batch(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, clean: torch.Tensor, lam: float = 0.001):
+def validate_batch(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, clean: torch.Tensor, lam: float = 0.001,
+                   boundary: str = "float32"):
     """fxprun.py:79-88: (loss, si_snr), one value per sequence: si_snr = si_snr(cleaned, clean) -- the cleaned audio is the
     reference's ``target`` argument -- over the clean audio's length, loss = lam * mean((cleaned_mag - clean_mag)^2) +
-    (100 - si_snr), with clean_mag = stft_mag(clean, sub=0)."""
-    cleaned, cleaned_mag, _, _ = denoise_fused(model, inp_bits, inp_exp, noisy)
+    (100 - si_snr), with clean_mag = stft_mag(clean, sub=0).  ``boundary`` as in ``denoise_fused`` (the same numbers either way)."""
+    cleaned, cleaned_mag, _, _ = denoise_fused(model, inp_bits, inp_exp, noisy, boundary=boundary)
     clean_mag = stft_mag(clean, sub=0.0)
     score = si_snr(cleaned[..., : clean.shape[-1]], clean.to(torch.float32))
     loss = lam * torch.mean((cleaned_mag - clean_mag) ** 2, dim=(1, 2)) + (100.0 - score)

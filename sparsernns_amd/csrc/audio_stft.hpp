@@ -5,6 +5,11 @@
 //
 //   k_stft_mag     audio (B,T) -> x = |Z| - sub, (B,n_seg,257) frame-major [+ the complex spectrum Z]
 //   k_mask_istft   audio (B,T), mask (B,n_seg,257) -> cleaned audio (B,(n_seg-1)*128) [+ cleaned_mag = |Z| * (1 + mask)]
+//   k_stft_mag_i16 / k_mask_istft_i16: the same two with the model's int16 boundary (s5fxp_model_forward_i16): x leaves as
+//                  fromfp(|Z| - sub, FLOOR) at (x_bits, x_exp), the mask arrives as int16 at mask_exp -- 2 bytes per value, and
+//                  the same audio bit for bit, since both conversions restate 16-bit integers.  The bodies are shared as text
+//                  (audio_stft_mag_body.inc, audio_mask_istft_body.inc) with the boundary type as a compile-time constant, as
+//                  the encoder's and decoder's are (proj_p.hpp): the float kernels keep their instruction streams.
 //
 // Framing.  With p the signal between 256 zeros on each side and zero-filled up to a whole hop, frame k is p[128k .. 128k+511]
 // (hops k..k+3 of p), n_seg = ceil(T/128) + 1.  Output hop o of the inverse (samples 128o .. 128o+127, hop o+2 of p) is the
@@ -25,6 +30,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "fxp_prims.hpp"
 
 namespace s5 {
 namespace stft {
@@ -198,18 +205,18 @@ __global__ __launch_bounds__(256) void k_stft_mag(const float *__restrict__ audi
                                                   float *__restrict__ x, float2 *__restrict__ spec)
 {
 #pragma clang fp contract(off)
-    __shared__ Smem sm;
-    const int64_t b = blockIdx.x / tiles, k0 = (int64_t)(blockIdx.x % tiles) * FR;
-    make_twiddles(sm);
-    forward_tile(sm, audio + b * T, T, k0);
-    const int nfr = (int)(n_seg - k0 < FR ? n_seg - k0 : FR);
-    const int64_t base = (b * n_seg + k0) * NBIN;
-    for (int i = threadIdx.x; i < nfr * NBIN; i += 256) {
-        const int fr = i / NBIN, k = i - fr * NBIN;
-        const float2 z = bin_from_packed(sm.b + fr * FSTR, sm.tw, k);
-        x[base + i] = cabs(z) - sub;
-        if (spec) spec[base + i] = z;
-    }
+    constexpr bool I16 = false;
+    [[maybe_unused]] constexpr int x_bits = 0, x_exp = 0;
+#include "audio_stft_mag_body.inc"
+}
+
+// x = fxp_from_fp(|Z| - sub, FLOOR) at (x_bits <= 16, x_exp) of the very float k_stft_mag stores (fxp_prims.hpp fromfp)
+__global__ __launch_bounds__(256) void k_stft_mag_i16(const float *__restrict__ audio, int64_t T, int64_t n_seg, int tiles, float sub,
+                                                      int x_bits, int x_exp, int16_t *__restrict__ x, float2 *__restrict__ spec)
+{
+#pragma clang fp contract(off)
+    constexpr bool I16 = true;
+#include "audio_stft_mag_body.inc"
 }
 
 // grid = B * tiles, tiles = ceil((n_seg - 1) / 13); workgroup (b, o0 / 13) writes output hops o0 .. o0+12 from frames
@@ -219,53 +226,19 @@ __global__ __launch_bounds__(256) void k_mask_istft(const float *__restrict__ au
                                                     float *__restrict__ cleaned_mag)
 {
 #pragma clang fp contract(off)
-    __shared__ Smem sm;
-    const int64_t b = blockIdx.x / tiles, o0 = (int64_t)(blockIdx.x % tiles) * OH, k0 = o0 - 1;
-    // this thread's 1 + mask values (elements threadIdx.x + 256 j of the tile's 16 x 257), asked for before the forward
-    // transform so that they arrive behind it; a frame outside 0..n_seg-1 contributes nothing
-    constexpr int NJ = (FR * NBIN + 255) / 256;
-    const int64_t base = (b * n_seg + k0) * NBIN;
-    float f[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int i = threadIdx.x + 256 * j;
-        const int64_t kf = k0 + i / NBIN;
-        f[j] = (mask && i < FR * NBIN && kf >= 0 && kf < n_seg) ? 1.0f + mask[base + i] : 1.0f;
-    }
-    make_twiddles(sm);
-    forward_tile(sm, audio + b * T, T, k0);
-    // Z' = Z * (1 + mask) into plane A
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int i = threadIdx.x + 256 * j;
-        if (i >= FR * NBIN) break;
-        const int fr = i / NBIN, k = i - fr * NBIN;
-        const int64_t kf = k0 + fr;
-        float2 z = make_float2(0.0f, 0.0f);
-        if (kf >= 0 && kf < n_seg) {
-            z = bin_from_packed(sm.b + fr * FSTR, sm.tw, k);
-            // frames 0, 14 and 15 of a tile are frames 13, 1 and 2 of its neighbours: a tile reports its frames 1..13, the
-            // last tile of a sequence also what lies beyond them
-            if (cleaned_mag && fr >= 1 && (fr <= OH || o0 + OH >= n_seg - 1)) cleaned_mag[base + i] = cabs(z) * f[j];
-            z = make_float2(z.x * f[j], z.y * f[j]);
-        }
-        sm.a[fr * FSTR + k] = z;
-    }
-    __syncthreads();
-    inverse_tile(sm);
-    const int64_t n_out = n_seg - 1;
-    const int noh = (int)(n_out - o0 < OH ? n_out - o0 : OH);
-    const float *seg = reinterpret_cast<const float *>(sm.a);
-    float *dst = out + b * n_out * HOP + o0 * HOP;
-    for (int i = threadIdx.x; i < noh * HOP; i += 256) {
-        const int j = i >> 7, s = i & 127;
-        const int64_t o = o0 + j;
-        float acc = 0.0f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc += seg[(j + q) * (2 * FSTR) + HOP * (3 - q) + s];
-        const float cover = 4.0f - (o == 0 ? 1.0f : 0.0f) - (o == n_out - 1 ? 1.0f : 0.0f);
-        dst[i] = acc / cover;
-    }
+    constexpr bool I16 = false;
+    [[maybe_unused]] constexpr int mask_exp = 0;
+#include "audio_mask_istft_body.inc"
+}
+
+// the mask as the decoder leaves it (int16 at mask_exp): 1 + to_float(mask) is the float route's factor
+__global__ __launch_bounds__(256) void k_mask_istft_i16(const float *__restrict__ audio, const int16_t *__restrict__ mask, int mask_exp,
+                                                        int64_t T, int64_t n_seg, int tiles, float *__restrict__ out,
+                                                        float *__restrict__ cleaned_mag)
+{
+#pragma clang fp contract(off)
+    constexpr bool I16 = true;
+#include "audio_mask_istft_body.inc"
 }
 
 } // namespace stft

@@ -1,4 +1,7 @@
-// proj_dec_body.inc -- the body of k_dec_p and k_dec_pf (proj_p.hpp), included by both with F32 = false / true.
+// proj_dec_body.inc -- the body of k_dec_p, k_dec_pf and k_dec_ps (proj_p.hpp), included by each with IO = IO_I32 / IO_F32 /
+// IO_I16.
+    constexpr bool F32 = IO == IO_F32, I16 = IO == IO_I16;
+    constexpr unsigned YB = I16 ? 2u : 4u; // bytes of an output value
     {
         const int64_t g = blockIdx.y;
         gshift(a.x, g * go.ws); gshift(a.y, g * go.y); gshift(a.xe.dyn, g * go.ws); gshift(a.status, g * go.status);
@@ -132,15 +135,19 @@
             // then puts at the top of the next tile -- for the rows prefetched BEFORE these stores -- degenerates to
             // vmcnt(0): every tile would begin by waiting for the previous tile's stores to be acknowledged.
             const bool okc = col < a.M;
-            char *yl = okc ? reinterpret_cast<char *>(a.y + n0 * a.M) + 4u * (unsigned)((32 * sub + 4 * h) * a.M + col)
+            char *ybase; // this tile's first output row
+            if constexpr (I16) ybase = reinterpret_cast<char *>(reinterpret_cast<int16_t *>(a.y) + n0 * a.M);
+            else ybase = reinterpret_cast<char *>(a.y + n0 * a.M);
+            char *yl = okc ? ybase + YB * (unsigned)((32 * sub + 4 * h) * a.M + col)
                            : reinterpret_cast<char *>(as_global(&g_store_sink[l]));
-            const unsigned ystep = okc ? 4u * (unsigned)a.M : 0u;
+            const unsigned ystep = okc ? YB * (unsigned)a.M : 0u;
             if (n0 + FT <= a.N) {
                 char *yp = yl; // a running pointer: sixteen hoisted offsets per column tile would cost the kernel its occupancy
 #pragma unroll
                 for (int i = 0; i < 16; ++i) { // frames (i & 3) + 8 * (i >> 2)
                     const int32_t v = sat(asr(acc[i], rs), so);
                     if constexpr (F32) *reinterpret_cast<float *>(yp) = tofloat(sat(wadd(v, bev[c]), so), a.out_exp);
+                    else if constexpr (I16) *reinterpret_cast<int16_t *>(yp) = (int16_t)sat(wadd(v, bev[c]), so);
                     else *reinterpret_cast<int32_t *>(yp) = sat(wadd(v, bev[c]), so);
                     yp += (i & 3) == 3 ? 5 * ystep : ystep;
                 }
@@ -152,6 +159,7 @@
                     if (nb + fo < a.N) {
                         const int32_t v = sat(asr(acc[i], rs), so);
                         if constexpr (F32) *reinterpret_cast<float *>(yp) = tofloat(sat(wadd(v, bev[c]), so), a.out_exp);
+                        else if constexpr (I16) *reinterpret_cast<int16_t *>(yp) = (int16_t)sat(wadd(v, bev[c]), so);
                         else *reinterpret_cast<int32_t *>(yp) = sat(wadd(v, bev[c]), so);
                     }
                     yp += (i & 3) == 3 ? 5 * ystep : ystep;

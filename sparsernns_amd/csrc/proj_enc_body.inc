@@ -1,4 +1,6 @@
-// proj_enc_body.inc -- the body of k_enc_p and k_enc_pf (proj_p.hpp), included by both with F32 = false / true.
+// proj_enc_body.inc -- the body of k_enc_p, k_enc_pf and k_enc_ps (proj_p.hpp), included by each with IO = IO_I32 / IO_F32 /
+// IO_I16.
+    constexpr bool F32 = IO == IO_F32, I16 = IO == IO_I16;
     {
         const int64_t g = blockIdx.y;
         gshift(a.x, g * go.x); gshift(a.y, g * go.ws); gshift(a.status, g * go.status); gshift(ext, g * go.ws);
@@ -41,18 +43,33 @@
     // The prefetch is issued behind the compiler's back (scan_quad.hpp vm_wait): its own wait at the first use -- a tile
     // later, behind phase B's stores -- would be vmcnt(0), every tile opening with a wait for the previous tile's stores.
     constexpr int RA = NT <= 3 ? RPW : 3, RB = RPW - RA;
-    v4i rawa[RA], rawb[RB > 0 ? RB : 1];
+    using RowVec = std::conditional_t<I16, v2i, v4i>; // a lane's four elements of a row
+    constexpr unsigned RVB = I16 ? 8u : 16u;
+    RowVec rawa[RA], rawb[RB > 0 ? RB : 1];
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     auto row_base = [&](int64_t tl, int i) { // wave-uniform
         int64_t n = tl * FT + wave_u + NW * i;
         n = n < a.N ? n : a.N - 1;
-        return reinterpret_cast<const char *>(a.x + n * K);
+        if constexpr (I16) return reinterpret_cast<const char *>(reinterpret_cast<const int16_t *>(a.x) + n * K);
+        else return reinterpret_cast<const char *>(a.x + n * K);
     };
     auto row_ptr = [&](int64_t tl, int i) {
-        return reinterpret_cast<const v4i *>(row_base(tl, i) + 16 * l); // 4-byte aligned 16-byte load
+        return reinterpret_cast<const RowVec *>(row_base(tl, i) + (int)RVB * l); // 4-byte aligned 16-byte load (int16: 2-byte aligned, 8 bytes)
     };
-    auto convert_row = [&](const v4i &q, int f, bool &wide) {
-        int32_t v[4] = {q[0], q[1], q[2], q[3]};
+    auto load_hidden = [&](const char *base) { return gload_hidden<RowVec>(base, RVB * (unsigned)l); };
+    auto convert_row = [&](const auto &q, int f, bool &wide) { // (generic: the arm of the other row type is not instantiated)
+        constexpr bool Q16 = sizeof(q) == 8;
+        static_assert(Q16 == I16, "row vector");
+        if constexpr (Q16) {
+            if (!a.conv) { // uniform: the loaded pairs are the perms' operands
+                *reinterpret_cast<int32_t *>(Xl + f * KP + 4 * l) = (int32_t)(perm((unsigned)q[1], (unsigned)q[0], 0x06040200u) ^ 0x80808080u);
+                *reinterpret_cast<int32_t *>(Xh + f * KP + 4 * l) = (int32_t)perm((unsigned)q[1], (unsigned)q[0], 0x07050301u);
+                return;
+            }
+        }
+        int32_t v[4];
+        if constexpr (Q16) unpack4_i16(q, v);
+        else { v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3]; }
         if constexpr (F32) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = fromfp(__int_as_float(q[e]), sc, a.xb);
@@ -61,8 +78,10 @@
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = cv(v[e]);
         }
+        if constexpr (!Q16) { // (an int16 input cannot be wide)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) wide |= (v[e] != (int32_t)(int16_t)v[e]);
+            for (int e = 0; e < 4; ++e) wide |= (v[e] != (int32_t)(int16_t)v[e]);
+        }
         const unsigned p01 = perm((unsigned)v[1], (unsigned)v[0], 0x05010400u), p23 = perm((unsigned)v[3], (unsigned)v[2], 0x05010400u);
         *reinterpret_cast<int32_t *>(Xl + f * KP + 4 * l) = (int32_t)(perm(p23, p01, 0x05040100u) ^ 0x80808080u);
         *reinterpret_cast<int32_t *>(Xh + f * KP + 4 * l) = (int32_t)perm(p23, p01, 0x07060302u);
@@ -70,7 +89,7 @@
     int64_t tile = blockIdx.x;
     if (tile < tiles) {
 #pragma unroll
-        for (int i = 0; i < RA; ++i) rawa[i] = gload16_hidden(row_base(tile, i), 16u * (unsigned)l);
+        for (int i = 0; i < RA; ++i) rawa[i] = load_hidden(row_base(tile, i));
     }
     bool wide = false;
     __syncthreads();
@@ -102,16 +121,18 @@
             const int f = e / rem, k = 256 + e % rem;
             int64_t n = n0 + f;
             n = n < a.N ? n : a.N - 1;
-            int32_t xv = a.x[n * K + k];
+            int32_t xv;
+            if constexpr (I16) xv = reinterpret_cast<const int16_t *>(a.x)[n * K + k];
+            else xv = a.x[n * K + k];
             if constexpr (F32) xv = fromfp(__int_as_float(xv), sc, a.xb);
             const int32_t v = cv(xv);
-            wide |= (v != (int32_t)(int16_t)v);
+            if constexpr (!I16) wide |= (v != (int32_t)(int16_t)v);
             Xl[f * KP + k] = (int8_t)((v & 0xff) ^ 0x80);
             Xh[f * KP + k] = (int8_t)(v >> 8);
         }
         if (tile + gridDim.x < tiles) {
 #pragma unroll
-            for (int i = 0; i < RA; ++i) rawa[i] = gload16_hidden(row_base(tile + gridDim.x, i), 16u * (unsigned)l); // in flight during phase B
+            for (int i = 0; i < RA; ++i) rawa[i] = load_hidden(row_base(tile + gridDim.x, i)); // in flight during phase B
         }
         PHASE_MARK(3, l); // tail column + prefetch issue
         __syncthreads();

@@ -399,10 +399,14 @@ __device__ __forceinline__ void mfma_nplanes(v16i &acc, const v4i (&w)[KSTEPS], 
 // the ReLU); the atomics are spread over ext_reps replicas (mfma_bn.hpp EXT_REPS).
 // LDS: [cs128 Np][bias_eff Np][X hi][X lo][ext hi H][ext lo H]
 // ---------------------------------------------------------------------------------------------
+// The element type of the model boundary (x of the encoder, y of the decoder): one body per kernel, shared as text, with the
+// type as a compile-time constant.
+enum { IO_I32 = 0, IO_F32 = 1, IO_I16 = 2 };
+
 template <int NT>
 __global__ __launch_bounds__(384, 3) void k_enc_p(EncArgs a, float *ext, int ext_reps, GroupOff go)
 {
-    constexpr bool F32 = false;
+    constexpr int IO = IO_I32;
 #include "proj_enc_body.inc"
 }
 
@@ -416,7 +420,18 @@ __global__ __launch_bounds__(384, 3) void k_enc_p(EncArgs a, float *ext, int ext
 template <int NT>
 __global__ __launch_bounds__(384, 3) void k_enc_pf(EncArgs a, float *ext, int ext_reps, GroupOff go)
 {
-    constexpr bool F32 = true;
+    constexpr int IO = IO_F32;
+#include "proj_enc_body.inc"
+}
+
+// k_enc_p for an int16 input (s5fxp_model_forward_i16): a.x holds int16 rows of 2 K bytes, 2-byte aligned.  A lane's four
+// elements are two dwords, loaded as they lie (gload8_hidden): with the input at the encoder's configuration they are the
+// operands of the byte-plane perms as loaded, otherwise they are sign-extended for the change_cfg first.  Every value is an
+// int16, so the wide-input check has nothing to find.  LDS, phase B, its stores and the vm_wait counts are k_enc_p's.
+template <int NT>
+__global__ __launch_bounds__(384, 3) void k_enc_ps(EncArgs a, float *ext, int ext_reps, GroupOff go)
+{
+    constexpr int IO = IO_I16;
 #include "proj_enc_body.inc"
 }
 
@@ -444,7 +459,7 @@ struct DecResid {
 template <int KS, bool RESID = false>
 __global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_p(DecArgs a, DecResid rz, GroupOff go)
 {
-    constexpr bool F32 = false;
+    constexpr int IO = IO_I32;
 #include "proj_dec_body.inc"
 }
 
@@ -455,7 +470,19 @@ __global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_p(DecArgs
 template <int KS, bool RESID>
 __global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_pf(DecArgs a, DecResid rz, GroupOff go)
 {
-    constexpr bool F32 = true;
+    constexpr int IO = IO_F32;
+#include "proj_dec_body.inc"
+}
+
+// k_dec_p with an int16 output (s5fxp_model_forward_i16; the host has checked out_bits <= 16, so the narrowing loses
+// nothing): one 2-byte store per value on the same running pointer with a row step of 2 M bytes -- 64 contiguous bytes of
+// one output row per half wave and store, the same 48 stores per tile; ragged column tiles still go to g_store_sink.
+// (Registers: at KS = 6 both forms are budgeted for two workgroups per CU -- k_dec_p<6, false> spills two registers under its
+// bound of three.  Measured at 32 x 4096 frames: 39.0 us against k_dec_p<6, false>'s 43.7, profiles/r13_i16_io_kernel_stats.txt.)
+template <int KS, bool RESID>
+__global__ __launch_bounds__(384, KS == 6 ? 2 : 3) void k_dec_ps(DecArgs a, DecResid rz, GroupOff go)
+{
+    constexpr int IO = IO_I16;
 #include "proj_dec_body.inc"
 }
 

@@ -304,6 +304,31 @@ extern "C" int s5fxp_mask_istft(const float *audio, const float *mask, int B, in
     return launch_rc();
 }
 
+// ... with the model's int16 boundary (s5fxp_model_forward_i16) on the model's side of both
+extern "C" int s5fxp_stft_mag_i16(const float *audio, int B, int64_t T, float sub, int x_bits, int x_exp, int16_t *x, float *spec,
+                                  void *stream)
+{
+    if (!audio || !x || B < 1 || x_bits < 1 || x_bits > 16 || x_exp < 0 || x_exp > 31) return S5FXP_EBADARG;
+    if (T < stft::NFFT) return S5FXP_EUNSUPPORTED;
+    const int64_t n_seg = s5fxp_stft_frames(T), tiles = (n_seg + stft::FR - 1) / stft::FR;
+    if (tiles * B > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
+    hipLaunchKernelGGL(stft::k_stft_mag_i16, dim3((unsigned)(tiles * B)), dim3(256), 0, S(stream), audio, T, n_seg, (int)tiles, sub,
+                       x_bits, x_exp, x, reinterpret_cast<float2 *>(spec));
+    return launch_rc();
+}
+
+extern "C" int s5fxp_mask_istft_i16(const float *audio, const int16_t *mask, int mask_exp, int B, int64_t T, float *out,
+                                    float *cleaned_mag, void *stream)
+{
+    if (!audio || !out || B < 1 || mask_exp < 0 || mask_exp > 31) return S5FXP_EBADARG;
+    if (T < stft::NFFT) return S5FXP_EUNSUPPORTED;
+    const int64_t n_seg = s5fxp_stft_frames(T), tiles = (n_seg - 1 + stft::OH - 1) / stft::OH;
+    if (tiles * B > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
+    hipLaunchKernelGGL(stft::k_mask_istft_i16, dim3((unsigned)(tiles * B)), dim3(256), 0, S(stream), audio, mask, mask_exp, T, n_seg,
+                       (int)tiles, out, cleaned_mag);
+    return launch_rc();
+}
+
 // The same framing for a live signal (audio_stream.hpp): whole hops in, cleaned hops out, the caller's state between calls.
 extern "C" size_t s5fxp_stream_audio_state_bytes(void) { return stft::STATE_FLOATS * sizeof(float); }
 
@@ -1028,7 +1053,7 @@ extern "C" int s5fxp_model_forward_f32(const s5fxp_model *m, const float *x, int
     if (G > 1) {
         // the same split as s5fxp_model_forward: one set of fused launches, or one (fused or generic) forward per group
         if (m->fast && !traces && !opts->allreduce && fast_bn_ext(m) && stream_extent_ok(m, L))
-            return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), G, ws_one, true);
+            return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), G, ws_one, IO_F32);
         const size_t plane = (size_t)m->n_layers * 2 * B * (m->P ? m->P : 1);
         for (int g = 0; g < G; ++g) {
             s5fxp_forward_opts o = *opts;
@@ -1044,7 +1069,7 @@ extern "C" int s5fxp_model_forward_f32(const s5fxp_model *m, const float *x, int
         return S5FXP_OK;
     }
     if (!stream_extent_ok(m, L)) return S5FXP_EBADARG;
-    if (m->fast) return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), 1, 0, true);
+    if (m->fast) return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), 1, 0, IO_F32);
     // generic: the three steps, on int32 copies staged behind the int forward's workspace
     const size_t ws_int = s5fxp_workspace_bytes(m, B, L);
     const int64_t N = (int64_t)B * L;
@@ -1054,6 +1079,55 @@ extern "C" int s5fxp_model_forward_f32(const s5fxp_model *m, const float *x, int
     if ((rc = s5fxp_from_fp(x, xi, N * m->d_in, x_bits, x_exp, S5FXP_FLOOR, stream))) return rc;
     if ((rc = s5fxp_model_forward(m, xi, x_bits, x_exp, B, L, yi, workspace, ws_int, status, traces, opts, stream))) return rc;
     return s5fxp_to_float(yi, y, N * m->d_out, m->dec.out_exp, stream);
+}
+
+// The same forward with an int16 model boundary: x is 16-bit data and the decoder saturates to out_bits <= 16, so both tensors
+// cross in 2 bytes per value.  A fused model reads and writes int16 inside its encoder and decoder kernels (proj_p.hpp
+// k_enc_ps / k_dec_ps) on the int forward's workspace; a generic one stages int32 copies behind the int forward's workspace and
+// runs k_widen_i16 -> the int forward -> k_narrow_i16.
+extern "C" size_t s5fxp_workspace_bytes_i16(const s5fxp_model *m, int B, int L)
+{
+    return s5fxp_workspace_bytes_f32(m, B, L); // the same staging: 4 bytes per element of both tensors on the generic path
+}
+
+extern "C" int s5fxp_model_forward_i16(const s5fxp_model *m, const int16_t *x, int x_bits, int x_exp, int B, int L, int16_t *y,
+                                       void *workspace, size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces,
+                                       const s5fxp_forward_opts *opts, void *stream)
+{
+    if (!m || !x || !y || !workspace || !status || B < 1 || L < 1 || x_bits < 1 || x_bits > 16) return S5FXP_EBADARG;
+    if (m->dec.out_bits > 16) return S5FXP_EUNSUPPORTED; // the narrowing of y would lose bits
+    const int G = opts && opts->groups > 1 ? opts->groups : 1;
+    const size_t ws_one = s5fxp_workspace_bytes_i16(m, B, L);
+    if (workspace_bytes < (size_t)G * ws_one) return S5FXP_EWORKSPACE;
+    if (G > 1) {
+        // the same split as s5fxp_model_forward: one set of fused launches, or one (fused or generic) forward per group
+        if (m->fast && !traces && !opts->allreduce && fast_bn_ext(m) && stream_extent_ok(m, L))
+            return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), G, ws_one, IO_I16);
+        const size_t plane = (size_t)m->n_layers * 2 * B * (m->P ? m->P : 1);
+        for (int g = 0; g < G; ++g) {
+            s5fxp_forward_opts o = *opts;
+            o.groups = 1;
+            if (o.state_in) o.state_in += g * plane;
+            if (o.state_out) o.state_out += g * plane;
+            const int rc = s5fxp_model_forward_i16(m, x + (size_t)g * B * L * m->d_in, x_bits, x_exp, B, L, y + (size_t)g * B * L * m->d_out,
+                                                   reinterpret_cast<char *>(workspace) + g * ws_one, ws_one,
+                                                   status + (size_t)g * S5FXP_STATUS_WORDS, traces ? traces + (size_t)g * m->n_layers : nullptr,
+                                                   &o, stream);
+            if (rc) return rc;
+        }
+        return S5FXP_OK;
+    }
+    if (!stream_extent_ok(m, L)) return S5FXP_EBADARG;
+    if (m->fast) return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), 1, 0, IO_I16);
+    // generic: widen, the int forward, narrow, on int32 copies staged behind the int forward's workspace
+    const size_t ws_int = s5fxp_workspace_bytes(m, B, L);
+    const int64_t N = (int64_t)B * L;
+    int32_t *xi = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(workspace) + ws_int);
+    int32_t *yi = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(xi) + al256((size_t)N * m->d_in * 4));
+    hipLaunchKernelGGL(k_widen_i16, dim3(ew_grid(N * m->d_in)), dim3(256), 0, S(stream), x, xi, N * m->d_in);
+    if (int rc = s5fxp_model_forward(m, xi, x_bits, x_exp, B, L, yi, workspace, ws_int, status, traces, opts, stream)) return rc;
+    hipLaunchKernelGGL(k_narrow_i16, dim3(ew_grid(N * m->d_out)), dim3(256), 0, S(stream), (const int32_t *)yi, y, N * m->d_out);
+    return launch_rc();
 }
 
 // FxpSequenceLayer.forward for ONE layer of a created model (fxpmodel.py:1110-1161): BatchNorm -> SSM -> ReLU -> out2 ->

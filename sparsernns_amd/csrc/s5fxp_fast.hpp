@@ -125,12 +125,13 @@ bool fast_eligible(const s5fxp_model_desc *d)
 }
 
 // get(k, ch) -> weight; result rows are channels, padded and strided for conflict-free 16-byte LDS reads
+// min_np: rows the consuming kernel loads whatever M is (zero rows beyond M; the per-channel arrays sized by Np follow)
 template <class Get>
-void pack_mfma(Packer &p, Get get, int K, int M, MfmaWDev &o)
+void pack_mfma(Packer &p, Get get, int K, int M, MfmaWDev &o, int min_np = 0)
 {
     const int Kpad = (K + 31) / 32 * 32;
     const int Kp = ((Kpad / 16) % 2 == 0) ? Kpad + 16 : Kpad;
-    const int Np = (M + 31) / 32 * 32;
+    const int Np = std::max((M + 31) / 32 * 32, min_np);
     std::vector<int8_t> wt((size_t)Np * Kp, 0);
     std::vector<int32_t> cs(Np, 0);
     for (int ch = 0; ch < M; ++ch) {
@@ -248,7 +249,10 @@ void pack_fast(Packer &p, const s5fxp_model_desc *d, FastModel *f)
         }
     }
     const s5fxp_dense_desc &dd = d->decoder;
-    pack_mfma(p, [&](int k, int ch) { return dd.weight[(size_t)k * dd.M + ch]; }, dd.K, dd.M, f->dec);
+    // the decoder kernels (proj_p.hpp k_dec_p: six waves x three column tiles) load the weight rows, cs128 and bias_eff of all
+    // 288 columns they can serve and mask only the stores: a narrower decoder (d_out = 1 packs 32 rows) is padded with zero
+    // rows, or those loads would run up to 28 KB past the packed arrays -- past the end of the blob, where they were appended last
+    pack_mfma(p, [&](int k, int ch) { return dd.weight[(size_t)k * dd.M + ch]; }, dd.K, dd.M, f->dec, 288);
     pack_bias_eff(p, dd, f->dec.w.Np, f->dec);
 }
 
@@ -533,7 +537,8 @@ struct FusedForward {
     int G, B, L;
     char *ws;
     size_t ws_stride; // bytes between the groups' workspaces (0: this forward's size)
-    bool f32 = false; // s5fxp_model_forward_f32: float32 input and output, converted inside the encoder and the decoder
+    int io = IO_I32;  // the model boundary (proj_p.hpp): IO_F32 (s5fxp_model_forward_f32) and IO_I16 (s5fxp_model_forward_i16) convert inside
+                      // the encoder and the decoder
 
     const FastModel &F = *m->fast;
     const ModelCfg &cfg = m->cfg;
@@ -547,7 +552,7 @@ struct FusedForward {
     const FastWs w = fast_ws(m, B, L);
     LayerDyn *dyn = reinterpret_cast<LayerDyn *>(ws + w.dyn);
     const int64_t carry_stride = (int64_t)m->n_layers * 2 * B * (m->P ? m->P : 1) * 4;
-    const GroupOff go{N * m->d_in * 4, N * m->d_out * 4, (int64_t)(ws_stride ? ws_stride : w.total), 4 * S5FXP_STATUS_WORDS,
+    const GroupOff go{N * m->d_in * (io == IO_I16 ? 2 : 4), N * m->d_out * (io == IO_I16 ? 2 : 4), (int64_t)(ws_stride ? ws_stride : w.total), 4 * S5FXP_STATUS_WORDS,
                       carry_stride, carry_stride};
 
     // ---- the plan
@@ -674,7 +679,7 @@ struct FusedForward {
     {
         const DenseDev &e = m->enc;
         EncArgs a{};
-        // f32: float rows, read as their bits by k_enc_pf
+        // IO_F32: float rows, read as their bits by k_enc_pf; IO_I16: int16 rows, read by k_enc_ps
         a.x = reinterpret_cast<const int32_t *>(x); a.y = h; a.w = F.enc.w; a.bias_eff = F.enc.bias_eff; a.N = N; a.K = e.K; a.M = e.M;
         a.xb = x_bits; a.xe = x_exp; a.inp_bits = e.inp_bits; a.inp_exp = e.inp_exp;
         a.conv = (x_bits > e.inp_bits || x_exp > e.inp_exp) ? 1 : 0;
@@ -686,7 +691,7 @@ struct FusedForward {
         // lets the last workgroup derive layer 0's BatchNorm exponents (mfma_bn.hpp ResidTail)
         float *ext0 = bn_ext ? ext(0) : nullptr;
         const int ext_reps = (ext0 && !allreduce) ? EXT_REPS : 1; // the consumer (k_bproj_p's prologue) folds the replicas
-        auto kernel = nt_kernel(sh.nt, [&](auto n) { return f32 ? k_enc_pf<decltype(n)::value> : k_enc_p<decltype(n)::value>; });
+        auto kernel = nt_kernel(sh.nt, [&](auto n) { return io == IO_F32 ? k_enc_pf<decltype(n)::value> : io == IO_I16 ? k_enc_ps<decltype(n)::value> : k_enc_p<decltype(n)::value>; });
         launch(kernel, grid_enc, 384, smem, nullptr, nullptr, a, ext0, ext_reps);
         return S5FXP_OK;
     }
@@ -948,7 +953,7 @@ struct FusedForward {
         const DenseDev &e = m->dec;
         DecResid dz{};
         DecArgs a{};
-        // f32: k_dec_pf stores float bits
+        // IO_F32: k_dec_pf stores float bits; IO_I16: k_dec_ps stores int16
         a.x = h; a.y = reinterpret_cast<int32_t *>(y); a.w = F.dec.w; a.bias_eff = F.dec.bias_eff; a.N = N; a.H = H; a.M = e.M;
         a.xb = hb; a.xe = he; a.inp_bits = e.inp_bits; a.inp_exp = e.inp_exp; a.w_exp = e.w_exp;
         a.out_bits = e.out_bits; a.out_exp = e.out_exp; a.status = status;
@@ -965,18 +970,21 @@ struct FusedForward {
         // 192 channels: 2 x 4 vectors of prefetch, one workgroup per CU
         auto kernel = nt_kernel(sh.nt, [&](auto n) {
             constexpr int NT = decltype(n)::value;
-            return f32 ? (dec_resid >= 0 ? k_dec_pf<NT, true> : k_dec_pf<NT, false>) : (dec_resid >= 0 ? k_dec_p<NT, true> : k_dec_p<NT, false>);
+            return io == IO_F32   ? (dec_resid >= 0 ? k_dec_pf<NT, true> : k_dec_pf<NT, false>)
+                   : io == IO_I16 ? (dec_resid >= 0 ? k_dec_ps<NT, true> : k_dec_ps<NT, false>)
+                                  : (dec_resid >= 0 ? k_dec_p<NT, true> : k_dec_p<NT, false>);
         });
         launch(kernel, grid_dec, 384, smem, nullptr, nullptr, a, dz);
     }
 };
 
-// x / y: int32 tensors, or float32 ones with f32 (s5fxp_model_forward_f32); the same 4 bytes per element either way
+// x / y: int32 tensors, float32 ones with io = IO_F32 (s5fxp_model_forward_f32; the same 4 bytes per element) or int16 ones with
+// io = IO_I16 (s5fxp_model_forward_i16; 2 bytes per element, 2-byte aligned)
 int forward_fast(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int B, int L, void *y, void *workspace,
                  int32_t *status, const s5fxp_layer_trace *traces, const s5fxp_forward_opts *opts, hipStream_t st, int G = 1,
-                 size_t ws_stride = 0, bool f32 = false)
+                 size_t ws_stride = 0, int io = IO_I32)
 {
-    FusedForward f{m, opts, traces, status, st, G, B, L, reinterpret_cast<char *>(workspace), ws_stride, f32};
+    FusedForward f{m, opts, traces, status, st, G, B, L, reinterpret_cast<char *>(workspace), ws_stride, io};
     int rc;
     f.clear_status();
     if ((rc = f.encoder(x, x_bits, x_exp))) return rc;

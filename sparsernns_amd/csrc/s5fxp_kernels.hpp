@@ -736,6 +736,11 @@ __global__ void k_to_float(const int32_t *__restrict__ x, float *__restrict__ y,
     S5_GRID_STRIDE(i, n) y[i] = tofloat(x[i], exp);
 }
 
+// the int16 model boundary of a generic forward (s5fxp_model_forward_i16): sign-extend in, narrow out (the decoder has
+// saturated to out_bits <= 16)
+__global__ void k_widen_i16(const int16_t *__restrict__ x, int32_t *__restrict__ y, int64_t n) { S5_GRID_STRIDE(i, n) y[i] = x[i]; }
+__global__ void k_narrow_i16(const int32_t *__restrict__ x, int16_t *__restrict__ y, int64_t n) { S5_GRID_STRIDE(i, n) y[i] = (int16_t)x[i]; }
+
 __global__ void k_change_cfg(const int32_t *__restrict__ x, int32_t *__restrict__ y, int64_t n, int bits, int exp,
                              int bits2, int exp2)
 {

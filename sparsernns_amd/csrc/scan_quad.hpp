@@ -88,6 +88,19 @@ __device__ __forceinline__ v4i_ gload16_hidden(const char *base, unsigned off)
     asm volatile("global_load_dwordx4 %0, %1, %2" : "=&v"(r) : "v"(off), "s"(base) : "memory");
     return r;
 }
+// ... and its 8-byte form (a lane's four int16 of a row, proj_p.hpp k_enc_ps), under the same discipline
+using v2i_ = __attribute__((ext_vector_type(2))) int;
+__device__ __forceinline__ v2i_ gload8_hidden(const char *base, unsigned off)
+{
+    v2i_ r;
+    asm volatile("global_load_dwordx2 %0, %1, %2" : "=&v"(r) : "v"(off), "s"(base) : "memory");
+    return r;
+}
+template <class V> __device__ __forceinline__ V gload_hidden(const char *base, unsigned off) // V: 16 or 8 bytes
+{
+    if constexpr (sizeof(V) == 16) return gload16_hidden(base, off);
+    else return gload8_hidden(base, off);
+}
 template <int NEWER, class T, int N>
 __device__ __forceinline__ void vm_wait(T (&regs)[N])
 {

@@ -1,5 +1,6 @@
-"""Fused forward of the fixed-point S5 model: Python driver of ``s5fxp_model_forward`` (int32 in and out) and
-``s5fxp_model_forward_f32`` (float32 in and out, the reference's validation step, sparseRNNs/fxprun.py:63-88).
+"""Fused forward of the fixed-point S5 model: Python driver of ``s5fxp_model_forward`` (int32 in and out),
+``s5fxp_model_forward_f32`` (float32 in and out, the reference's validation step, sparseRNNs/fxprun.py:63-88) and
+``s5fxp_model_forward_i16`` (int16 in and out: the same integers in half the bytes).
 
 ``Engine`` takes the INTEGER model in the reference's ``export()`` layout
 (sparseRNNs/fxpmodel.py:1441-1458 and the nested exports it gathers), hands it to the C ABI,
@@ -163,12 +164,18 @@ class Engine:
             st = self._status[lane] = torch.zeros(groups * _lib.STATUS_WORDS, dtype=torch.int32, device=self.device)
         return st
 
-    def workspace(self, B: int, L: int, lane: int = 0, groups: int = 1, f32: bool = False) -> torch.Tensor:
+    # the three model boundaries: dtype of x and y -> (workspace query, forward entry, its name)
+    _IO = {torch.int32: (lib.s5fxp_workspace_bytes, lib.s5fxp_model_forward, "s5fxp_model_forward"),
+           torch.float32: (lib.s5fxp_workspace_bytes_f32, lib.s5fxp_model_forward_f32, "s5fxp_model_forward_f32"),
+           torch.int16: (lib.s5fxp_workspace_bytes_i16, lib.s5fxp_model_forward_i16, "s5fxp_model_forward_i16")}
+
+    def workspace(self, B: int, L: int, lane: int = 0, groups: int = 1, io: torch.dtype = torch.int32) -> torch.Tensor:
+        """The lane's workspace for forwards of this shape and I/O type (`io`: torch.int32, float32 or int16)."""
         key, ws = self._wsl.get(lane, (None, None))
-        if key != (B, L, groups, f32):
-            per = lib.s5fxp_workspace_bytes_f32(self._h, B, L) if f32 else lib.s5fxp_workspace_bytes(self._h, B, L)
+        if key != (B, L, groups, io):
+            per = self._IO[io][0](self._h, B, L)
             ws = torch.empty(groups * per, dtype=torch.uint8, device=self.device)
-            self._wsl[lane] = ((B, L, groups, f32), ws)
+            self._wsl[lane] = ((B, L, groups, io), ws)
         return ws
 
     def enqueue(self, x: torch.Tensor, x_bits: int, x_exp: int, y: torch.Tensor, B: int, L: int,
@@ -186,16 +193,16 @@ class Engine:
         read the status words and repeat with _lib.FWD_EXACT when ST_REDO is set (``forward`` does).
 
         x and y are both int32 (``s5fxp_model_forward``) or both float32 (``s5fxp_model_forward_f32``: x_bits / x_exp are then
-        the quantisation target of the float input, and y receives to_float of the output)."""
-        if x.dtype == torch.int32 and y.dtype == torch.int32:
-            f32 = False
-        elif x.dtype == torch.float32 and y.dtype == torch.float32:
-            f32 = True
-        else:
-            raise ValueError(f"x and y must both be int32 or both float32, got {x.dtype} and {y.dtype}")
+        the quantisation target of the float input, and y receives to_float of the output) or both int16
+        (``s5fxp_model_forward_i16``: the int forward on the sign-extended x, y narrowed; x_bits <= 16 and a model whose
+        output has at most 16 bits).  int16 tensors need no more than their own 2-byte alignment: views into larger buffers
+        are fine as long as they are contiguous."""
+        if x.dtype != y.dtype or x.dtype not in self._IO:
+            raise ValueError(f"x and y must both be int32, both float32 or both int16, got {x.dtype} and {y.dtype}")
+        io = x.dtype
         if groups > 1 and (traces is not None or allreduce is not None):
             raise ValueError("a grouped forward takes neither traces nor a cross-rank hook: run the groups one by one")
-        ws = self.workspace(B, L, lane, groups, f32)
+        ws = self.workspace(B, L, lane, groups, io)
         self._groups[lane] = groups
         tr = None
         if traces is not None:
@@ -238,7 +245,7 @@ class Engine:
                     raise ValueError(f"{name} must be a contiguous int32 device tensor of shape {want}")
                 setattr(opts, name, t.data_ptr())
         self._cb_keep = opts
-        entry, name = (lib.s5fxp_model_forward_f32, "s5fxp_model_forward_f32") if f32 else (lib.s5fxp_model_forward, "s5fxp_model_forward")
+        _, entry, name = self._IO[io]
         check(entry(self._h, x.data_ptr(), x_bits, x_exp, B, L, y.data_ptr(), ws.data_ptr(), ws.numel(),
                     self.lane_status(lane, groups).data_ptr(), C.cast(tr, C.POINTER(LayerTrace)) if tr is not None else None,
                     C.byref(opts), torch.cuda.current_stream().cuda_stream), name)
@@ -345,6 +352,59 @@ class Engine:
         if B * L == 0:
             raise ValueError("empty chunk")
         y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=torch.float32, device=data.device)
+        new_state = torch.empty((self.n_layers, 2, B, self.P), dtype=torch.int32, device=data.device)
+        self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, B, L, flags=fl, state_in=state, state_out=new_state),
+                        self.check_status)
+        return y, new_state
+
+    # -- int16 in, int16 out ----------------------------------------------------------------------
+    def _int16_input(self, x, x_bits: Optional[int], x_exp: Optional[int]):
+        data = torch.as_tensor(x)
+        if data.dtype != torch.int16:
+            raise ValueError(f"expected an int16 tensor, got {data.dtype}")
+        data = data.to(self.device).contiguous()
+        if data.shape[-1] != self.d_in:
+            raise ValueError(f"expected last dim {self.d_in}, got {tuple(data.shape)}")
+        return (data, self.inp_bits if x_bits is None else int(x_bits), self.inp_exp if x_exp is None else int(x_exp))
+
+    def forward_int16(self, x, x_bits: Optional[int] = None, x_exp: Optional[int] = None, check_status: bool = True,
+                      allreduce: Optional[Callable] = None) -> torch.Tensor:
+        """``forward`` with int16 tensors at the model boundary: x int16 (B,L,d_in) or (L,d_in) at (x_bits, x_exp) -- default: the
+        encoder's input configuration -- -> int16 (.., d_out) at (out_bits, out_exp), the very integers ``forward`` returns
+        for the same values as int32.  On the fused path the encoder reads and the decoder writes int16; a model whose output
+        is wider than 16 bits raises NotImplementedError.  check_status / allreduce as in ``forward``."""
+        data, xb, xe = self._int16_input(x, x_bits, x_exp)
+        B, L = (1, data.shape[0]) if data.ndim == 2 else (data.shape[0], data.shape[1])
+        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=torch.int16, device=data.device)
+        if B * L == 0:
+            return y
+        if not check_status or allreduce:
+            self.enqueue(data, xb, xe, y, B, L, allreduce=allreduce)  # self-contained: exact re-run enqueued, gated
+            if check_status:
+                self.check_status()
+        else:
+            self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, B, L, flags=fl), self.check_status)
+        return y
+
+    def forward_batches_int16(self, x, batch: int, x_bits: Optional[int] = None, x_exp: Optional[int] = None) -> torch.Tensor:
+        """``forward_batches`` int16 in and out: x (G * batch, L, d_in) -> (G * batch, L, d_out), one set of launches."""
+        data, xb, xe = self._int16_input(x, x_bits, x_exp)
+        if data.ndim != 3 or data.shape[0] % batch:
+            raise ValueError(f"expected (G * {batch}, L, {self.d_in}), got {tuple(data.shape)}")
+        G, L = data.shape[0] // batch, data.shape[1]
+        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=torch.int16, device=data.device)
+        if G * batch * L:
+            self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, batch, L, flags=fl, groups=G), self.check_status)
+        return y
+
+    def forward_chunk_int16(self, x, state: Optional[torch.Tensor] = None, x_bits: Optional[int] = None,
+                            x_exp: Optional[int] = None):
+        """``forward_chunk`` int16 in and out: returns (y int16, new_state); `state` is not modified."""
+        data, xb, xe = self._int16_input(x, x_bits, x_exp)
+        B, L = (1, data.shape[0]) if data.ndim == 2 else (data.shape[0], data.shape[1])
+        if B * L == 0:
+            raise ValueError("empty chunk")
+        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=torch.int16, device=data.device)
         new_state = torch.empty((self.n_layers, 2, B, self.P), dtype=torch.int32, device=data.device)
         self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, B, L, flags=fl, state_in=state, state_out=new_state),
                         self.check_status)
@@ -643,8 +703,9 @@ class InflightRunner:
 
     def submit(self, x: torch.Tensor, x_bits: int, x_exp: int, y: torch.Tensor, B: int, L: int, check: bool = True,
                scan_events: Optional[list] = None, groups: int = 1) -> int:
-        """check=False skips the status check of the lane's previous batch (only sound when every batch of the lane
-        is the same input, as in bench.py: the last check then speaks for all)."""
+        """x and y: both int32, both float32 or both int16, as ``Engine.enqueue`` takes them.  check=False skips the status
+        check of the lane's previous batch (only sound when every batch of the lane is the same input, as in bench.py: the
+        last check then speaks for all)."""
         lane = self._next
         self._next = (lane + 1) % self.depth
         if check:

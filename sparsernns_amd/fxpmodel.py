@@ -624,6 +624,13 @@ class FxpRegressionModel(FxpModule):  # :1380-1458
                 self._generic_engine = Engine(self.export(), flags=self.engine_flags | MODEL_FORCE_GENERIC)
             return self._generic_engine.forward_float(x, allreduce=self.exponent_allreduce)
 
+    def forward_int16(self, x, x_bits=None, x_exp=None):
+        """int16 (B,L,d_in) at (x_bits, x_exp) -- default: the encoder's input configuration -- -> int16 (B,L,d_out) at the
+        model's output configuration: the integers of ``forward`` in 2 bytes per value at both ends.  int16 values cannot exceed
+        what the fused kernels take, so there is no fallback; a model whose output is wider than 16 bits raises
+        NotImplementedError."""
+        return self.engine().forward_int16(x, x_bits, x_exp, allreduce=self.exponent_allreduce)
+
     def export(self):
         encoder_data, decoder_data = self.encoder.export(), self.decoder.export()
         return dict(

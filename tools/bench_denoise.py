@@ -5,11 +5,13 @@ B clips of T = 480000 samples (3751 STFT frames, the N-DNS clip), per batch:
       parent commit, built there) loaded next to this one, otherwise this tree's -- the function is the same text in both;
   (b) audio.denoise_fused: k_stft_mag -> model -> k_mask_istft;
   (c) the two new launches alone (stft_mag, mask_istft with cleaned_mag, on a fixed mask);
-  (d) (a) without its model call (the torch chain alone, on a fixed mask).
+  (d) (a) without its model call (the torch chain alone, on a fixed mask);
+  (e) audio.denoise_fused(boundary="int16"): k_stft_mag_i16 -> the int16 forward -> k_mask_istft_i16, 2 bytes per value across
+      the model's boundary instead of 4 -- the same cleaned audio as (b) bit for bit, which the tool checks.
 Every shape is warmed up first; then the variants alternate in one process, each timed with device events, for --reps
 repetitions.  Reports median, p10, p90 in us per batch, frames/s, and for (c) the achieved bytes/s on the algorithmic bytes
 (front 512 + 1028, back 512 + 1028 + 512 + 1028 per frame) and its share of the 8 TB/s HBM peak.
-  python tools/bench_denoise.py [--reps 14] [--B 32,1] [--only abcd] [--parent-root DIR] [--out FILE.json]
+  python tools/bench_denoise.py [--reps 14] [--B 32,1] [--only abcde] [--parent-root DIR] [--out FILE.json]
 --only a or b with few reps is the workload of a rocprofv3 --kernel-trace --stats run (launch counts)."""
 import argparse
 import importlib.util
@@ -45,7 +47,7 @@ def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=14)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--only", default="abcd")
+    ap.add_argument("--only", default="abcde")
     ap.add_argument("--B", default="32,1")
     ap.add_argument("--T", type=int, default=480000)
     ap.add_argument("--parent-root", default=None)
@@ -102,7 +104,10 @@ def main() -> int:
             cleaned_mag = mag * (1.0 + mask_t)
             return x, p_audio.stft_mixer(cleaned_mag, phase), cleaned_mag
 
-        runs = {k: v for k, v in (("a", run_a), ("b", run_b), ("c", run_c), ("d", run_d)) if k in args.only}
+        def run_e():
+            return audio.denoise_fused(model, ib, ie, noisy, boundary="int16")
+
+        runs = {k: v for k, v in (("a", run_a), ("b", run_b), ("c", run_c), ("d", run_d), ("e", run_e)) if k in args.only}
         for _ in range(args.warmup):
             for fn in runs.values():
                 fn()
@@ -137,6 +142,11 @@ def main() -> int:
             out["input_words_differing"] = int((torch.floor(xa.double() * 2.0 ** ie) != torch.floor(xb.double() * 2.0 ** ie)).sum())
             out["max_abs_mask_a_minus_b"] = float((model.forward_float(xa) - mb).abs().max())
             out["max_abs_cleaned_a_minus_b"] = float((ca - cb[..., : ca.shape[-1]]).abs().max())
+        if "b" in out and "e" in out:
+            out["e_over_b"] = out["e"]["median"] / out["b"]["median"]
+            (cb, mb_, _, _), (ce, me_, _, _) = run_b(), run_e()
+            out["e_equals_b_bitwise"] = bool(torch.equal(cb, ce) and torch.equal(mb_, me_))
+            assert out["e_equals_b_bitwise"], f"B={B}: the int16 boundary changed the cleaned audio"
         res["batches"][str(B)] = out
         print(f"[bench_denoise] B={B}: " + ", ".join(f"{k} {v['median']:.1f} us" for k, v in out.items() if isinstance(v, dict)), flush=True)
         del noisy, mask, mask_t

@@ -12,7 +12,7 @@ copy, spill or reuse them before the data has landed.  The register audit follow
 tile is waited for at the top of the next -- to the wait that guards it (the hand-written s_waitcnt vmcnt(N), or a compiler wait
 that leaves no more memory operations outstanding than were issued after the load), and fails if an instruction outside the inline-assembly blocks reads or writes one of its destination VGPRs on the
 way.  It also reports .private_segment_fixed_size and .vgpr_spill_count of every kernel with hidden loads.  It audits
-every kernel of the library that has hidden loads (today k_enc_p, k_dec_p, their float twins and the pair recurrence kernels).
+every kernel of the library that has hidden loads (today k_enc_p, k_dec_p, their float and int16 twins and the pair recurrence kernels).
   python tools/check_vmwait.py [--asm FILE.s]    (--asm: audit a given assembly file instead of compiling the library)
 Exit code 0 = consistent."""
 import os
@@ -38,6 +38,12 @@ EXPECT = {
     "_ZN2s57k_dec_pILi2ELb1EE": (48, 2), "_ZN2s57k_dec_pILi5ELb1EE": (48, 2),
     "_ZN2s58k_dec_pfILi2ELb0EE": (48, 0), "_ZN2s58k_dec_pfILi5ELb0EE": (48, 0),
     "_ZN2s58k_dec_pfILi2ELb1EE": (48, 2), "_ZN2s58k_dec_pfILi5ELb1EE": (48, 2),
+    # int16 in / int16 out (k_enc_ps / k_dec_ps, the same bodies again): 8-byte hidden row loads, 2-byte output stores, the same counts
+    "_ZN2s58k_dec_psILi3ELb0EE": (48, 0), "_ZN2s58k_dec_psILi6ELb0EE": (48, 0),
+    "_ZN2s58k_dec_psILi3ELb1EE": (48, 2), "_ZN2s58k_dec_psILi6ELb1EE": (48, 2),
+    "_ZN2s58k_dec_psILi2ELb0EE": (48, 0), "_ZN2s58k_dec_psILi5ELb0EE": (48, 0),
+    "_ZN2s58k_dec_psILi2ELb1EE": (48, 2), "_ZN2s58k_dec_psILi5ELb1EE": (48, 2),
+    "_ZN2s58k_enc_psILi3EE": (4, 0), "_ZN2s58k_enc_psILi6EE": (8, 0),
 }
 
 
