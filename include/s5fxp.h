@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define S5FXP_VERSION 109
+#define S5FXP_VERSION 110
 
 enum {
     S5FXP_OK = 0,
@@ -171,6 +171,43 @@ int s5fxp_stream_stft(const float *audio, int S, int c, int64_t hops_before, flo
 /* mask: (S,F,257) float32 or NULL (zeros); out: (S,O*128) float32, may be NULL when O == 0; cleaned_mag: NULL or (S,F,257). */
 int s5fxp_stream_mask_istft(const float *mask, int S, int c, int64_t hops_before, int final, void *state, float *out,
                             float *cleaned_mag, void *stream);
+
+/* Streams that start, stop and idle on their own: one push serves any subset of a pool of n_slots streams, each entry with
+ * its own hop count, phase and flags, in the same three launches (s5fxp_stream_stft_ragged, s5fxp_model_step_ragged_f32,
+ * s5fxp_stream_mask_istft_ragged).  All three read ONE array of n descriptors from DEVICE memory, owned by the caller (one
+ * host-to-device copy per push); entry e is workgroup e of each launch.  The kernels trust the array as they trust pointers
+ * and sizes: validate it on the host with s5fxp_push_desc_check before it is copied.
+ *   FRESH  the slot starts a new signal: its carry (step) and its audio state (both audio kernels) are taken as all-zero
+ *          bytes, whatever they hold -- a slot is reused after a finished signal without a clearing launch;
+ *   ZEROS  the entry's audio is zeros, whatever `audio` holds (the two trailing hops of a finishing stream);
+ *   FINAL  the entry is the end of its signal (the `final` of s5fxp_stream_mask_istft). */
+enum { S5FXP_PUSH_FRESH = 1, S5FXP_PUSH_ZEROS = 2, S5FXP_PUSH_FINAL = 4 };
+typedef struct {
+    int32_t slot;   /* which stream: index into the caller's carry / audio-state arrays, 0 .. n_slots-1 */
+    int32_t rows;   /* model step: frames of this entry, 0 .. Lmax */
+    int32_t flags;  /* S5FXP_PUSH_* */
+    int32_t hops;   /* audio kernels: hops of this entry, 1 .. cmax */
+    int32_t h4;     /* audio kernels: min(hops_before, 4) of this stream */
+    int32_t reserved[3];
+} s5fxp_push_desc;  /* 32 bytes */
+/* Host only, never touches the device; `host` is the array in host memory.  S5FXP_EBADARG: null array, n < 1, a slot outside
+ * 0..n_slots-1 or named twice (two workgroups would update one state in place), rows outside 0..Lmax, unknown flag bits,
+ * nonzero reserved words; with audio != 0 also cmax outside 1..S5FXP_STREAM_MAX_HOPS, hops outside 1..cmax, h4 outside 0..4,
+ * FRESH with h4 != 0, rows != hops - (h4 == 0).  S5FXP_EUNSUPPORTED: audio != 0 and FINAL with h4 < 4 (a signal below 512
+ * samples), as s5fxp_stream_mask_istft. */
+int s5fxp_push_desc_check(const s5fxp_push_desc *host, int n, int n_slots, int Lmax, int cmax, int audio);
+/* The two audio kernels per entry: entry e uses c = hops, h4, final = FINAL and the state of slot `slot`, and gives bit for
+ * bit what the lock-step entries give one stream with the same c, hops_before, final and state.  Rows are padded to cmax:
+ * audio (n, cmax*128) or NULL (zeros for all), x / mask / cleaned_mag (n, cmax, 257) -- the step's rows with Lmax = cmax,
+ * B = 1 -- out (n, (cmax+1)*128); an entry reads its first c hops and writes its F = c - (h4 == 0) rows and its
+ * O = min(c, max(0, h+c-3)) + final hops at the front of its row and nothing behind them.  state: n_slots *
+ * s5fxp_stream_audio_state_bytes() bytes; a slot no entry names is not touched.  mask NULL = zeros, cleaned_mag NULL = not
+ * wanted.  S5FXP_EBADARG for a null desc / state / x / out, n < 1, n_slots < 1 or cmax outside 1..32, before the device is
+ * touched. */
+int s5fxp_stream_stft_ragged(const float *audio, int n, int cmax, const s5fxp_push_desc *desc, float sub, void *state, int n_slots,
+                             float *x, void *stream);
+int s5fxp_stream_mask_istft_ragged(const float *mask, int n, int cmax, const s5fxp_push_desc *desc, void *state, int n_slots,
+                                   float *out, float *cleaned_mag, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Model level: FxpRegressionModel.forward, fxpmodel.py:1431-1439 (-> 1261-1271 -> 1110-1161).
@@ -420,6 +457,22 @@ int s5fxp_model_step(const s5fxp_model *m, const int32_t *x, int x_bits, int x_e
                      const int32_t *state_in, int32_t *state_out, int32_t *status, void *stream);
 int s5fxp_model_step_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int G, int B, int L, float *y,
                          const int32_t *state_in, int32_t *state_out, int32_t *status, void *stream);
+/* The step with per-entry row counts and carry slots (s5fxp_push_desc above; the array is device memory): grid = n, entry e
+ * runs L = desc[e].rows frames of each of its B sequences on the carry of slot s = desc[e].slot and gives, bit for bit,
+ *   s5fxp_model_step(m, x_e, x_bits, x_exp, 1, B, L, y_e, FRESH ? NULL : state[s], state[s], status_e, ...)
+ * -- the y rows, the carry left in state[s] and all S5FXP_STATUS_WORDS status words.
+ *   x (n,B,Lmax,d_in), y (n,B,Lmax,d_out): padded to Lmax frames per sequence; frames L..Lmax-1 of x are never read and of
+ *   y never written.  state [n_slots][n_layers][2][B][P], updated in place; a slot no entry names is never touched.
+ *   rows == 0: y untouched, the carry untouched (zeroed if FRESH), the status words hold the kernel's initial fill ([1],
+ *   [2], the per-layer constants, zeros elsewhere).
+ *   S5FXP_ST_WIDE_INPUT, the one difference from s5fxp_model_step: the entry stores its status words and stops, leaving
+ *   its y rows and state[s] untouched, so the caller can serve it from the intact carry on the generic engine.
+ * B * Lmax <= S5FXP_STEP_MAX_ROWS.  Host checks as s5fxp_model_step at (B, Lmax), and S5FXP_EBADARG for a null desc or
+ * state or n_slots < 1. */
+int s5fxp_model_step_ragged(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int n, int B, int Lmax, int32_t *y,
+                            const s5fxp_push_desc *desc, int32_t *state, int n_slots, int32_t *status, void *stream);
+int s5fxp_model_step_ragged_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int n, int B, int Lmax, float *y,
+                                const s5fxp_push_desc *desc, int32_t *state, int n_slots, int32_t *status, void *stream);
 
 /* FxpSequenceLayer.forward, fxpmodel.py:1110-1161, for layer `layer` of a created model -- the unit the reference's
  * verification walks (fxprun.py:583-727).  x: (B,L,H) int32 device with configuration (x_bits, x_exp); y: (B,L,H) int32

@@ -28,6 +28,7 @@ STATUS_WORDS = 128
 PATH_GENERIC, PATH_FUSED, PATH_STEP = 1, 2, 3   # status[2]
 STEP_MAX_ROWS = 32
 STREAM_MAX_HOPS = 32
+PUSH_FRESH, PUSH_ZEROS, PUSH_FINAL = 1, 2, 4   # s5fxp_push_desc.flags
 MODEL_DEFAULT, MODEL_FORCE_DENSE, MODEL_FORCE_CSR, MODEL_FORCE_GENERIC, MODEL_NO_RESID_FOLD, MODEL_NO_RESID_LAZY = 0, 1, 2, 4, 8, 16
 
 
@@ -78,6 +79,11 @@ class ForwardOpts(C.Structure):
     _fields_ = [("allreduce", ALLREDUCE_FN), ("allreduce_ctx", VOIDP), ("scan_events", C.POINTER(VOIDP)),
                 ("flags", C.c_int32), ("state_in", VOIDP), ("state_out", VOIDP), ("groups", C.c_int32),
                 ("gate_events", C.POINTER(VOIDP))]
+
+
+class PushDesc(C.Structure):
+    """s5fxp_push_desc: one entry of a ragged push (32 bytes)."""
+    _fields_ = [(n, C.c_int32) for n in ("slot", "rows", "flags", "hops", "h4")] + [("reserved", C.c_int32 * 3)]
 
 
 class S5FxpError(RuntimeError):
@@ -137,6 +143,11 @@ def _load():
         "s5fxp_model_step_ok": (i, [p, i, i]),
         "s5fxp_model_step": (i, [p, p, i, i, i, i, i, p, p, p, p, p]),
         "s5fxp_model_step_f32": (i, [p, p, i, i, i, i, i, p, p, p, p, p]),
+        "s5fxp_push_desc_check": (i, [p, i, i, i, i, i]),
+        "s5fxp_model_step_ragged": (i, [p, p, i, i, i, i, i, p, p, p, i, p, p]),
+        "s5fxp_model_step_ragged_f32": (i, [p, p, i, i, i, i, i, p, p, p, i, p, p]),
+        "s5fxp_stream_stft_ragged": (i, [p, i, i, p, C.c_float, p, i, p, p]),
+        "s5fxp_stream_mask_istft_ragged": (i, [p, i, i, p, p, i, p, p, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale: rebuild
@@ -151,7 +162,9 @@ EXPORTED_SYMBOLS = ("s5fxp_version s5fxp_strerror s5fxp_from_fp s5fxp_to_float s
                     "s5fxp_model_out_exp s5fxp_model_out_bits s5fxp_model_is_fast s5fxp_model_recurrence_kernel s5fxp_model_recurrence_xmax "
                     "s5fxp_model_step_ok s5fxp_model_step s5fxp_model_step_f32 "
                     "s5fxp_stft_frames s5fxp_stft_mag s5fxp_mask_istft s5fxp_stft_mag_i16 s5fxp_mask_istft_i16 s5fxp_stream_audio_state_bytes s5fxp_stream_frames "
-                    "s5fxp_stream_out_hops s5fxp_stream_stft s5fxp_stream_mask_istft").split()
+                    "s5fxp_stream_out_hops s5fxp_stream_stft s5fxp_stream_mask_istft "
+                    "s5fxp_push_desc_check s5fxp_model_step_ragged s5fxp_model_step_ragged_f32 s5fxp_stream_stft_ragged "
+                    "s5fxp_stream_mask_istft_ragged").split()
 
 
 def check(rc: int, what: str = "") -> None:

@@ -11,6 +11,7 @@ importable here: ``tests/test_cpu_suite.py`` checks these functions against it.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 NFFT = 512
@@ -430,3 +431,163 @@ class StreamDenoiser:
         out = (acc / cover[None, :, None])[:, rows - n_out:].reshape(S, n_out * HOP)
         self._state = (window[:, -3 * HOP:].contiguous(), v[:, c:c + 3].contiguous())
         return (out, x, mask, cm) if details else out
+
+
+class SessionDenoiser:
+    """``StreamDenoiser`` for ``slots`` live signals that start, stop and idle on their own: one ``push`` serves any subset
+    of the slots, each with its own hop count and phase, and sessions that end join the same call.
+
+        d = SessionDenoiser(model, slots)
+        out, n_out = d.push([0, 3], hops, counts=[1, 4], finish=[2])   # slots 0 and 3 push samples, slot 2 ends, 1 idles
+        d.start([2])                                                   # slot 2 begins its next signal
+
+    On a GPU a push is three launches whatever the mix (``s5fxp_stream_stft_ragged``, ``s5fxp_model_step_ragged_f32``,
+    ``s5fxp_stream_mask_istft_ragged``) and one small host-to-device copy of the descriptors all three read.  Every session
+    computes, bit for bit, what a ``StreamDenoiser(model, 1)`` fed the same chunks computes.  Results are padded: entry e of a
+    push is ``ids[e]``, then the sessions of ``finish`` in order; its ``n_out[e]`` output hops and ``frames[e]`` rows sit at the
+    front of row e, and what lies behind them is unspecified.  What ``push`` returns is valid until the next push of the same
+    shape.  CPU tensors and models without an engine run one ``StreamDenoiser(model, 1)`` per slot."""
+
+    latency_hops = 3
+
+    def __init__(self, model, slots: int, sub: float = STFT_MAG_MEAN):
+        if slots < 1:
+            raise ValueError("slots must be >= 1")
+        self.model, self.slots, self.sub = model, int(slots), float(sub)
+        self.hops = np.zeros(self.slots, dtype=np.int64)   # hops received per slot
+        self._done = np.zeros(self.slots, dtype=bool)
+        self._fresh = np.ones(self.slots, dtype=bool)      # the slot's next push starts a signal
+        self._pool = None       # the model's SessionPool (kernel route)
+        self._state = None      # kernel route: (slots, state floats)
+        self._each = None       # torch route: one StreamDenoiser(model, 1) per slot
+        self._dev = None
+        self._buf = {}
+
+    def _ids(self, ids, what):
+        ids = np.asarray(ids if isinstance(ids, np.ndarray) else list(ids), dtype=np.int64).reshape(-1)
+        if len(ids):
+            seen = np.zeros(self.slots, dtype=bool)
+            if ids.min() < 0 or ids.max() >= self.slots:
+                raise ValueError(f"{what} must be slots 0 .. {self.slots - 1}, got {ids.tolist()}")
+            seen[ids] = True
+            if int(seen.sum()) != len(ids):
+                raise ValueError(f"{what} name a slot twice: {ids.tolist()}")
+        return ids
+
+    def start(self, ids) -> None:
+        """The slots in `ids` begin a new signal: their next push carries FRESH, so nothing is cleared on the device."""
+        ids = self._ids(ids, "ids")
+        self.hops[ids], self._done[ids], self._fresh[ids] = 0, False, True
+        if self._each is not None:
+            for i in ids:
+                self._each[i].reset()
+
+    def finish(self, ids, check: bool = True, details: bool = False):
+        """The end of the signals in `ids`: ``push`` with only ``finish``."""
+        return self.push((), None, finish=ids, check=check, details=details)
+
+    def push(self, ids, hops, counts=None, finish=(), check: bool = True, details: bool = False):
+        """ids: the slots that push samples; hops: (len(ids), cmax * 128) float32, cmax = 1 .. 32 (None when only sessions
+        finish); counts: hops of each entry, 1 .. cmax (default cmax for all), an entry's samples at the front of its row.
+        Sessions in `finish` end in the same call: two hops of zeros with ``final``.  Returns (cleaned audio (n, (cmax' + 1) *
+        128), n_out), cmax' = max(cmax, 2 if any session finishes), n_out[e] the output hops of entry e; with ``details``
+        (cleaned, n_out, x, mask, cleaned_mag, frames), the three tensors (n, cmax', 257).  ``check`` is SessionPool.push's.
+        When sessions finish in a push whose rows are one hop wide, the samples are first copied into rows two hops wide.
+
+        RuntimeError for a slot whose signal has ended (``start`` it first), NotImplementedError for a signal that ends below
+        four hops (512 samples), ValueError for shapes, counts and slots named twice."""
+        ids = self._ids(ids, "ids")
+        fin = self._ids(finish, "finish") if len(finish) else ids[:0]
+        entries = self._ids(np.concatenate([ids, fin]), "ids and finish together") if len(fin) else ids
+        n = len(entries)
+        if n < 1:
+            raise ValueError("a push names at least one slot")
+        if len(ids):
+            if hops is None or hops.dim() != 2 or hops.shape[0] != len(ids) or hops.shape[1] % HOP or hops.dtype != torch.float32:
+                raise ValueError(f"hops must be ({len(ids)}, cmax * {HOP}) float32")
+            cmax = hops.shape[1] // HOP
+            if not 1 <= cmax <= STREAM_MAX_HOPS:
+                raise ValueError(f"a push takes 1 .. {STREAM_MAX_HOPS} hops, got {cmax}")
+            self._dev = hops.device
+        else:
+            cmax = 0
+            if self._dev is None:
+                raise RuntimeError("no signal has been pushed yet")
+        c = np.full(n, 2, dtype=np.int64)      # a finishing entry is two hops of zeros
+        if counts is None:
+            c[:len(ids)] = cmax
+        else:
+            counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+            if len(counts) != len(ids) or (len(ids) and (counts.min() < 1 or counts.max() > cmax)):
+                raise ValueError(f"counts must be {len(ids)} hop counts 1 .. {cmax}, got {counts.tolist()}")
+            c[:len(ids)] = counts
+        if self._done[entries].any():
+            raise RuntimeError(f"the signal of slots {entries[self._done[entries]].tolist()} has ended: start() them first")
+        h = self.hops[entries]
+        if len(fin) and h[len(ids):].min() < 4:
+            raise NotImplementedError(f"stft needs at least {NFFT} samples: slots {fin[self.hops[fin] < 4].tolist()} have received "
+                                      f"fewer than four hops")
+        final = np.arange(n) >= len(ids)
+        frames = c - (h == 0)
+        n_out = np.minimum(c, np.maximum(0, h + c - 3)) + final
+        cw = max(cmax, 2 if len(fin) else 0)
+        dev = self._dev
+        run = self._push_kernels if dev.type == "cuda" and hasattr(self.model, "engine") else self._push_each
+        res = run(entries, len(ids), hops, cmax, cw, c, h, final, frames, n_out, dev, check, details)
+        self.hops[entries] += c
+        self._fresh[entries] = False
+        self._done[fin] = True
+        return (res[0], n_out) + ((res[1], res[2], res[3], frames) if details else ())
+
+    # -- HIP kernels + SessionPool.push_ragged ------------------------------------------------------
+    def _push_kernels(self, entries, n_push, hops, cmax, cw, c, h, final, frames, n_out, dev, check, details):
+        from . import _lib
+        n, nb = len(entries), NFFT // 2 + 1
+        if self._pool is None:
+            self._pool = self.model.engine().pool(self.slots)
+        if self._state is None:
+            self._state = torch.zeros(self.slots, _lib.lib.s5fxp_stream_audio_state_bytes() // 4, dtype=torch.float32, device=dev)
+        b = self._buf.get((n, cw))
+        if b is None:
+            b = self._buf[(n, cw)] = [torch.empty(n, cw, nb, dtype=torch.float32, device=dev),
+                                      torch.empty(n, (cw + 1) * HOP, dtype=torch.float32, device=dev), None, None]
+        if details and b[2] is None:
+            b[2] = torch.empty(n, cw, nb, dtype=torch.float32, device=dev)
+        x, out, cm = b[0], b[1], b[2] if details else None
+        audio = hops.contiguous() if n_push else None
+        if n_push and cmax != cw:   # sessions finish beside one-hop rows: the launch's rows are two hops wide
+            if b[3] is None:
+                b[3] = torch.zeros(n, cw * HOP, dtype=torch.float32, device=dev)
+            b[3][:n_push, :cmax * HOP] = audio
+            audio = b[3]
+        fresh = self._fresh[entries]
+        flags = (fresh * _lib.PUSH_FRESH + final * (_lib.PUSH_ZEROS | _lib.PUSH_FINAL)).astype(np.int32)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            desc = self._pool.stage_desc(entries, frames, flags, hops=c, h4=np.minimum(h, 4), Lmax=cw, cmax=cw)
+            _lib.check(_lib.lib.s5fxp_stream_stft_ragged(audio.data_ptr() if audio is not None else None, n, cw, desc.data_ptr(),
+                                                         self.sub, self._state.data_ptr(), self.slots, x.data_ptr(), stream),
+                       "s5fxp_stream_stft_ragged")
+            mask = self._pool.push_ragged(entries, x, frames, fresh=entries[fresh] if fresh.any() else (), check=check, desc=desc)
+            _lib.check(_lib.lib.s5fxp_stream_mask_istft_ragged(mask.data_ptr(), n, cw, desc.data_ptr(), self._state.data_ptr(),
+                                                               self.slots, out.data_ptr(), cm.data_ptr() if details else None,
+                                                               stream), "s5fxp_stream_mask_istft_ragged")
+        return out, x, mask, cm
+
+    # -- one StreamDenoiser per slot (CPU tensors, models without an engine) -------------------------
+    def _push_each(self, entries, n_push, hops, cmax, cw, c, h, final, frames, n_out, dev, check, details):
+        n, nb = len(entries), NFFT // 2 + 1
+        if self._each is None:
+            self._each = [StreamDenoiser(self.model, 1, self.sub) for _ in range(self.slots)]
+        out = torch.zeros(n, (cw + 1) * HOP, dtype=torch.float32, device=dev)
+        x, mask, cm = (torch.zeros(n, cw, nb, dtype=torch.float32, device=dev) for _ in range(3))
+        for e, slot in enumerate(entries):
+            d = self._each[slot]
+            if final[e]:
+                r = d.finish(check=check, details=True, device=dev)
+            else:
+                r = d.push(hops[e:e + 1, :int(c[e]) * HOP].contiguous(), check=check, details=True)
+            out[e, :int(n_out[e]) * HOP] = r[0][0]
+            for dst, src in zip((x, mask, cm), r[1:]):
+                dst[e, :int(frames[e])] = src[0]
+        return out, x, mask, cm

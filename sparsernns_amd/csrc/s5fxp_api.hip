@@ -366,6 +366,25 @@ extern "C" int s5fxp_stream_mask_istft(const float *mask, int n, int c, int64_t 
     return launch_rc();
 }
 
+// The two with per-entry c, h4, flags and state slot, read from a device array of descriptors (audio_stream.hpp)
+extern "C" int s5fxp_stream_stft_ragged(const float *audio, int n, int cmax, const s5fxp_push_desc *desc, float sub, void *state,
+                                        int n_slots, float *x, void *stream)
+{
+    if (!desc || !state || !x || n < 1 || n_slots < 1 || cmax < 1 || cmax > stft::STREAM_MAX_HOPS) return S5FXP_EBADARG;
+    hipLaunchKernelGGL(stft::k_stream_stft_ragged, dim3((unsigned)n), dim3(256), 0, S(stream), audio, cmax, desc, sub,
+                       static_cast<float *>(state), x);
+    return launch_rc();
+}
+
+extern "C" int s5fxp_stream_mask_istft_ragged(const float *mask, int n, int cmax, const s5fxp_push_desc *desc, void *state,
+                                              int n_slots, float *out, float *cleaned_mag, void *stream)
+{
+    if (!desc || !state || !out || n < 1 || n_slots < 1 || cmax < 1 || cmax > stft::STREAM_MAX_HOPS) return S5FXP_EBADARG;
+    hipLaunchKernelGGL(stft::k_stream_mask_istft_ragged, dim3((unsigned)n), dim3(256), 0, S(stream), mask, cmax, desc,
+                       static_cast<float *>(state), out, cleaned_mag);
+    return launch_rc();
+}
+
 // -----------------------------------------------------------------------------------------------
 // model level
 // -----------------------------------------------------------------------------------------------

@@ -17,6 +17,8 @@
 //     L <= 32 steps: no pair / quad rung, no range bound, no redo;
 //   * the C projection is exact for int32 states of any width: when every state of the layer (after the complex ReLU)
 //     fits 16 bits -- a workgroup-uniform test -- two byte planes run, otherwise four.
+// Two kernels share the body (s5fxp_step_body.inc): k_model_step, every group B x L rows and carry g, and k_model_step_ragged,
+// every group its own row count and carry slot from a descriptor (s5fxp_model_step_ragged), x and y padded to Lmax frames.
 // LDS (dynamic, sized by R): [PLA: encoder-input / state planes][PLB: u / out2-input / decoder-input planes]
 //   [h int16 R x H][x1 int16 R x H][z int16 R x H][bq int32 2 x R x P].  R = 32 at H = 192: 120 KB; R = 1: 3.4 KB.
 #pragma once
@@ -165,334 +167,28 @@ __device__ __forceinline__ void step_wg_max(float (&v)[NV], float (*red)[STEP_MA
 template <int STEP_THREADS>
 __global__ __launch_bounds__(STEP_THREADS, 2) void k_model_step(StepArgs a)
 {
-    constexpr int STEP_WAVES = STEP_THREADS / 64;
-    extern __shared__ __attribute__((aligned(16))) int8_t step_smem[];
-    __shared__ int32_t s_status[128]; // S5FXP_STATUS_WORDS: built here, stored once at the end
-    __shared__ float s_red[3][STEP_MAX_WAVES];
-    // the layer's per-channel and per-state operands, fetched together at the head of the layer
-    __shared__ LayerDyn s_d;
-    __shared__ int32_t s_lut[8];
-    __shared__ int32_t s_wide;
+#define STEP_RAGGED 0
+#include "s5fxp_step_body.inc"
+#undef STEP_RAGGED
+}
 
-    const StepParams &sp = *a.sp;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-    const int64_t g = blockIdx.x;
-    const int B = a.B, L = a.L, R = B * L, H = sp.H, P = sp.P, HP = sp.hp, nl = sp.n_layers;
-    const int arow = r < R ? r : R - 1; // padding rows of the MFMA tile re-read the last real row
-    const StepLds lds = step_lds(R, H, P, HP, sp.d_in);
-    int8_t *pla = step_smem + lds.pla, *plb = step_smem + lds.plb;
-    int16_t *hb = reinterpret_cast<int16_t *>(step_smem + lds.hb), *x1b = reinterpret_cast<int16_t *>(step_smem + lds.x1),
-            *zb = reinterpret_cast<int16_t *>(step_smem + lds.z);
-    int32_t *bq = reinterpret_cast<int32_t *>(step_smem + lds.bq); // [re | im][row][state]
-    const int KPB = lds.kpb, psb = R * KPB;
+// The same body with per-workgroup rows and an indirection into the carry (include/s5fxp.h s5fxp_model_step_ragged)
+struct StepRaggedArgs {
+    const StepParams *sp;
+    const void *x;                // (n,B,Lmax,d_in) int32, or float32 with f32
+    void *y;                      // (n,B,Lmax,d_out) int32 / float32
+    const s5fxp_push_desc *desc;  // n entries, device memory
+    int32_t *state;               // [n_slots][n_layers][2][B][P], entry e updates slot desc[e].slot in place
+    int32_t *status;              // n x S5FXP_STATUS_WORDS
+    int32_t B, Lmax, x_bits, x_exp, f32;
+};
 
-    for (int i = tid; i < 128; i += STEP_THREADS) {
-        int32_t v = 0;
-        if (i == 1) v = sp.dec.out_exp;
-        else if (i == 2) v = 3; // S5FXP_PATH_STEP
-        else if (i >= 8 && (i - 8) / 8 < nl) v = (i & 7) == 5 ? 6 : ((i & 7) >= 6 ? P : 0);
-        s_status[i] = v;
-    }
-    __syncthreads();
-
-    // ---- input rows -> byte planes (float rows: fxp_from_fp FLOOR first), with the encoder's input conversion
-    // (fxpmodel.py:335-347) and the 16-bit check of the fused encoder (proj_p.hpp k_enc_p)
-    {
-        const StepDense &e = sp.enc;
-        const int K = e.K, KPA = lds.kpa_enc, psa = R * KPA;
-        const bool conv = a.x_bits > e.inp_bits || a.x_exp > e.inp_exp;
-        const float sc = ldexpf(1.f, a.x_exp);
-        const int32_t *xg = as_global(reinterpret_cast<const int32_t *>(a.x)) + g * R * K;
-        bool wide = false;
-        for (int i = tid; i < R * K; i += STEP_THREADS) {
-            const int row = i / K, k = i - row * K;
-            int32_t v = xg[i];
-            if (a.f32) v = fromfp(__int_as_float(v), sc, a.x_bits);
-            if (conv) v = chcfg(v, a.x_bits, a.x_exp, e.inp_bits, e.inp_exp);
-            wide |= v != (int32_t)(int16_t)v;
-            step_put2(pla, psa, row * KPA + k, v);
-        }
-        if (__any(wide) && lane == 0) atomicOr(&s_status[0], ST_WIDE_INPUT);
-        __syncthreads();
-        // ---- encoder + bias + ReLU (fxpmodel.py:331-366, 1263-1266)
-        const int rs = (conv ? e.inp_exp : a.x_exp) + e.w_exp - e.out_exp; // checked by the host
-        const int nks = (K + 31) / 32;
-        for (int tile = wave; tile < HP / 32; tile += STEP_WAVES) {
-            const int col = 32 * tile + r;
-            const v16i acc = step_mm<2>(pla, psa, KPA, arow, h, e.w, col, nks);
-            const int32_t be = as_global(e.bias_eff)[col];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-                if (row < R && col < H) { // (a wave whose lanes all hold padding rows skips the element)
-                    int32_t v = sat(asr(acc[i], rs), e.out_bits);
-                    v = sat(wadd(v, be), e.out_bits);
-                    hb[row * H + col] = (int16_t)(v < 0 ? 0 : v);
-                }
-            }
-        }
-        __syncthreads();
-    }
-
-    int hbits = sp.enc.out_bits, he = sp.enc.out_exp; // the layer input's configuration (he: chosen on the device from layer 1 on)
-    for (int li = 0; li < nl; ++li) {
-        const StepLayer &sl = sp.layers[li];
-        BnArgs bn = sl.bn;
-        bn.xe.stat = he; bn.xe.dyn = nullptr; bn.dyn = nullptr;
-        int32_t *st_exps = s_status + 8 + 8 * li;
-        if (tid < 8) s_lut[tid] = sl.lut[tid];
-        if (tid == 0) s_wide = 0;
-
-        // ---- the four BatchNorm compute_best exponents (fxpmodel.py:892-933): full reductions over the R x H values,
-        // the rule of k_bn_reduce / k_bn_finalize
-        {
-            float v[3] = {0.f, 0.f, 0.f};
-            for (int i = tid; i < R * H; i += STEP_THREADS) {
-                const int c = i % H;
-                const float fx = tofloat(hb[i], he), fm = tofloat(bn.mm[c], bn.me);
-                v[0] = fmaxf(v[0], fabsf(__fadd_rn(fx, fm)));
-                v[1] = fmaxf(v[1], fabsf(fx));
-                v[2] = fmaxf(v[2], fabsf(fm));
-            }
-            step_wg_max<3, STEP_WAVES>(v, s_red);
-            if (tid == 0) {
-                const uint32_t m3[3] = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2])};
-                s_d.bn1 = finalize_add_cb(m3, he, bn.me, bn.b1, s_status);
-                st_exps[0] = s_d.bn1.eo;
-                s_d.bn_e = s_d.bn1.eo;
-            }
-            __syncthreads();
-        }
-        {
-            LayerDyn d = s_d;
-            float v[1] = {0.f};
-            for (int i = tid; i < R * H; i += STEP_THREADS) {
-                const int c = i % H;
-                const int32_t t = bn_chain<1>(bn, d, hb[i], c);
-                v[0] = fmaxf(v[0], fabsf(__fmul_rn(tofloat(t, d.bn1.eo), tofloat(bn.isv[c], bn.ie))));
-            }
-            step_wg_max<1, STEP_WAVES>(v, s_red);
-            if (tid == 0) {
-                finalize_mul_cb(__float_as_uint(v[0]), s_d.bn1.eo, bn.ie, bn.b2, s_d.rs2, s_d.e2, s_status);
-                st_exps[1] = s_d.e2;
-                s_d.bn_e = s_d.e2;
-            }
-            __syncthreads();
-        }
-        if (bn.scale) {
-            LayerDyn d = s_d;
-            float v[1] = {0.f};
-            for (int i = tid; i < R * H; i += STEP_THREADS) {
-                const int c = i % H;
-                const int32_t t = bn_chain<2>(bn, d, hb[i], c);
-                v[0] = fmaxf(v[0], fabsf(__fmul_rn(tofloat(t, d.e2), tofloat(bn.scale[c], bn.se))));
-            }
-            step_wg_max<1, STEP_WAVES>(v, s_red);
-            if (tid == 0) {
-                finalize_mul_cb(__float_as_uint(v[0]), s_d.e2, bn.se, bn.b3, s_d.rs3, s_d.e3, s_status);
-                st_exps[2] = s_d.e3;
-                s_d.bn_e = s_d.e3;
-            }
-            __syncthreads();
-        }
-        if (bn.bias) {
-            LayerDyn d = s_d;
-            float v[3] = {0.f, 0.f, 0.f};
-            for (int i = tid; i < R * H; i += STEP_THREADS) {
-                const int c = i % H;
-                const int32_t t = bn_chain<3>(bn, d, hb[i], c);
-                const float ft = tofloat(t, bn.scale ? d.e3 : d.e2), fb = tofloat(bn.bias[c], bn.be);
-                v[0] = fmaxf(v[0], fabsf(__fadd_rn(ft, fb)));
-                v[1] = fmaxf(v[1], fabsf(ft));
-                v[2] = fmaxf(v[2], fabsf(fb));
-            }
-            step_wg_max<3, STEP_WAVES>(v, s_red);
-            if (tid == 0) {
-                const uint32_t m3[3] = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2])};
-                s_d.bn4 = finalize_add_cb(m3, bn.scale ? s_d.e3 : s_d.e2, bn.be, bn.b4, s_status);
-                st_exps[3] = s_d.bn4.eo;
-                s_d.bn_e = s_d.bn4.eo;
-            }
-            __syncthreads();
-        }
-        const LayerDyn d = s_d;
-
-        // ---- u = change_cfg(BatchNorm(x)) -> byte planes (fxpmodel.py:620-624)
-        for (int i = tid; i < R * H; i += STEP_THREADS) {
-            const int row = i / H, c = i - row * H;
-            step_put2(plb, psb, row * KPB + c, bn_chain<5>(bn, d, hb[i], c));
-        }
-        __syncthreads();
-
-        // ---- B projection, Bu saturate and the shift to the state exponent (fxpmodel.py:626-644, 158-167)
-        for (int tile = wave; tile < 2 * P / 32; tile += STEP_WAVES) {
-            const int col = 32 * tile + r, c = col >= P ? 1 : 0, p = col - c * P;
-            const v16i acc = step_mm<2>(plb, psb, KPB, arow, h, sl.bproj, col, HP / 32);
-            const int rs = c ? sl.rs_bim : sl.rs_bre, bits = c ? sl.bim_bits : sl.bre_bits, sh = c ? sl.sh_im : sl.sh_re;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-                if (row < R) {
-                    const int32_t bu = sat(asr(acc[i], rs), bits);
-                    bq[(c * R + row) * P + p] = sh > 0 ? asr(bu, sh) : wshl(bu, -sh);
-                }
-            }
-        }
-        __syncthreads();
-
-        // ---- the recurrence from the carry, 32-bit wrap arithmetic (fxpmodel.py:147-172); carry out; complex ReLU
-        // (fxpmodel.py:740-742).  A thread owns one (sequence, state): it reads its carry before it writes it, so
-        // state_out may be state_in.  The states replace Bu in place.
-        {
-            const size_t plane = (size_t)B * P;
-            const size_t cbase = ((size_t)g * nl + li) * 2 * plane;
-            bool wide = false;
-            for (int i = tid; i < B * P; i += STEP_THREADS) {
-                const int b = i / P, p = i - b * P;
-                const int32_t Ar = as_global(sl.a_re)[p], Ai = as_global(sl.a_im)[p];
-                int32_t xr = a.state_in ? as_global(a.state_in)[cbase + i] : 0;
-                int32_t xi = a.state_in ? as_global(a.state_in)[cbase + plane + i] : 0;
-                for (int t = 0; t < L; ++t) {
-                    const int o = (b * L + t) * P + p;
-                    scan_step(Ar, Ai, sl.ea_re, sl.ea_im, bq[o], bq[R * P + o], xr, xi);
-                    int32_t sr = xr, si = xi;
-                    crelu(sr, si);
-                    wide |= sr != (int32_t)(int16_t)sr || si != (int32_t)(int16_t)si;
-                    bq[o] = sr;
-                    bq[R * P + o] = si;
-                }
-                if (a.state_out) {
-                    as_global(a.state_out)[cbase + i] = xr;
-                    as_global(a.state_out)[cbase + plane + i] = xi;
-                }
-            }
-            if (__any(wide) && lane == 0) atomicOr(&s_wide, 1);
-        }
-        __syncthreads();
-        const bool wide_states = s_wide != 0; // workgroup-uniform
-        const int KPS = lds.kpa_st, pss = R * KPS, npl = wide_states ? 4 : 2;
-        for (int i = tid; i < 2 * R * P; i += STEP_THREADS) {
-            const int c = i / (R * P), rem = i - c * R * P, row = rem / P, p = rem - row * P;
-            int8_t *base = pla + c * npl * pss;
-            if (wide_states) step_put4(base, pss, row * KPS + p, bq[i]);
-            else step_put2(base, pss, row * KPS + p, bq[i]);
-        }
-        if (wide_states && tid == 0) atomicOr(&s_status[0], ST_WIDE_STATE);
-        __syncthreads();
-
-        // ---- C projection + D u + ReLU (fxpmodel.py:746-793, 1125) -> x1 and out2's input planes
-        for (int tile = wave; tile < HP / 32; tile += STEP_WAVES) {
-            const int col = 32 * tile + r;
-            v16i are, aim;
-            if (wide_states) {
-                are = step_mm<4>(pla, pss, KPS, arow, h, sl.cre, col, P / 32);
-                aim = step_mm<4>(pla + 4 * pss, pss, KPS, arow, h, sl.cim, col, P / 32);
-            } else {
-                are = step_mm<2>(pla, pss, KPS, arow, h, sl.cre, col, P / 32);
-                aim = step_mm<2>(pla + 2 * pss, pss, KPS, arow, h, sl.cim, col, P / 32);
-            }
-            const int32_t Dv = as_global(sl.Dpad)[col];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-                if (row < R && col < H) {
-                    const int32_t cr = sat(asr(are[i], sl.rs_cre), sl.y_bits);
-                    const int32_t ci = sat(asr(aim[i], sl.rs_cim), sl.y_bits);
-                    const int32_t cx = sat(wadd(cr, wmul(ci, -1)), sl.y_bits);
-                    const int32_t cx2 = wmul(cx, 2); // not clipped, fxpmodel.py:765-767
-                    const int32_t u = bn_chain<5>(bn, d, hb[row * H + col], col);
-                    const int32_t du = sat(asr(wmul(Dv, u), sl.rs_d), sl.y_bits);
-                    const int32_t yv = sat(wadd(cx2, du), sl.y_bits);
-                    const int32_t x1 = yv < 0 ? 0 : yv;
-                    x1b[row * H + col] = (int16_t)x1;
-                    step_put2(plb, psb, row * KPB + col,
-                              sl.o2_conv ? chcfg(x1, sl.y_bits, sl.y_exp, sl.o2_inp_bits, sl.o2_inp_exp) : x1);
-                }
-            }
-        }
-        __syncthreads();
-
-        // ---- out2 + LUT sigmoid + gate (fxpmodel.py:1133-1137, 97-144, 1075-1093) + the residual add's maxima
-        {
-            float v[3] = {0.f, 0.f, 0.f};
-            for (int tile = wave; tile < HP / 32; tile += STEP_WAVES) {
-                const int col = 32 * tile + r;
-                const v16i acc = step_mm<2>(plb, psb, KPB, arow, h, sl.out2, col, HP / 32);
-                const int32_t be = as_global(sl.o2_bias_eff)[col];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-                    if (row < R && col < H) {
-                        int32_t gq = sat(asr(acc[i], sl.rs_o2), sl.o2_out_bits);
-                        gq = sat(wadd(gq, be), sl.o2_out_bits);
-                        const int32_t s = sigmoid_lut(gq, sl.o2_out_bits, sl.o2_out_exp, sl.sig_x, sl.sig_y, s_lut);
-                        const int32_t lv = chcfg(x1b[row * H + col], sl.y_bits, sl.y_exp, sl.l_bits, sl.l_exp);
-                        const int32_t rv = chcfg(s, sl.o2_out_bits, sl.sig_y, sl.r_bits, sl.r_exp);
-                        const int32_t z = sat(asr(wmul(lv, rv), sl.rs_gate), sl.res_bits);
-                        zb[row * H + col] = (int16_t)z;
-                        const float fz = tofloat(z, sl.res_exp), fs = tofloat(hb[row * H + col], he);
-                        v[0] = fmaxf(v[0], fabsf(__fadd_rn(fz, fs)));
-                        v[1] = fmaxf(v[1], fabsf(fz));
-                        v[2] = fmaxf(v[2], fabsf(fs));
-                    }
-                }
-            }
-            step_wg_max<3, STEP_WAVES>(v, s_red);
-            if (tid == 0) {
-                const uint32_t m3[3] = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2])};
-                s_d.res = finalize_add_cb(m3, sl.res_exp, he, sl.res_bits, s_status);
-                st_exps[4] = s_d.res.eo;
-            }
-            __syncthreads();
-        }
-        // ---- residual compute_best add + ReLU (fxpmodel.py:1147-1159): the next layer's input, in place
-        {
-            const AddCb rp = s_d.res;
-            for (int i = tid; i < R * H; i += STEP_THREADS) {
-                const int32_t rr = add_cb_apply(zb[i], sl.res_bits, hb[i], hbits, rp, sl.res_bits);
-                hb[i] = (int16_t)(rr < 0 ? 0 : rr);
-            }
-            hbits = sl.res_bits;
-            he = rp.eo;
-        }
-        __syncthreads();
-    }
-
-    // ---- decoder (fxpmodel.py:1437, 331-366): its input exponent is the last residual's
-    {
-        const StepDense &e = sp.dec;
-        const bool conv = hbits > e.inp_bits || he > e.inp_exp;
-        int rs = (conv ? e.inp_exp : he) + e.w_exp - e.out_exp;
-        if (rs < 0 || rs > 31) {
-            if (tid == 0) atomicOr(&s_status[0], ST_NEGSHIFT);
-            rs = rs < 0 ? 0 : 31;
-        }
-        for (int i = tid; i < R * H; i += STEP_THREADS) {
-            const int row = i / H, c = i - row * H;
-            const int32_t v = hb[i];
-            step_put2(plb, psb, row * KPB + c, conv ? chcfg(v, hbits, he, e.inp_bits, e.inp_exp) : v);
-        }
-        __syncthreads();
-        const int M = e.M;
-        int32_t *yg = as_global(reinterpret_cast<int32_t *>(a.y)) + g * R * M;
-        for (int tile = wave; tile < (M + 31) / 32; tile += STEP_WAVES) {
-            const int col = 32 * tile + r;
-            const v16i acc = step_mm<2>(plb, psb, KPB, arow, h, e.w, col, HP / 32);
-            const int32_t be = as_global(e.bias_eff)[col];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-                if (row < R && col < M) {
-                    int32_t v = sat(asr(acc[i], rs), e.out_bits);
-                    v = sat(wadd(v, be), e.out_bits);
-                    yg[row * M + col] = a.f32 ? __float_as_int(tofloat(v, e.out_exp)) : v;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    int32_t *stg = as_global(a.status) + g * 128;
-    for (int i = tid; i < 128; i += STEP_THREADS) stg[i] = s_status[i];
+template <int STEP_THREADS>
+__global__ __launch_bounds__(STEP_THREADS, 2) void k_model_step_ragged(StepRaggedArgs a)
+{
+#define STEP_RAGGED 1
+#include "s5fxp_step_body.inc"
+#undef STEP_RAGGED
 }
 
 } // namespace s5
@@ -538,8 +234,8 @@ void fill_step_params(const s5fxp_model *m, StepParams &sp)
     }
 }
 
-int step_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int G, int B, int L, void *y, const int32_t *state_in,
-               int32_t *state_out, int32_t *status, void *stream, bool f32)
+// What both step entries check before the device is touched: arguments, then the model, then the static shifts.
+int step_checks(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int G, int B, int L, void *y, int32_t *status, bool f32)
 {
     if (!m || !x || !y || !status || G < 1 || B < 1 || L < 1 || (int64_t)B * L > STEP_MAX_ROWS || x_bits < 1 || x_bits > 32)
         return S5FXP_EBADARG;
@@ -556,6 +252,23 @@ int step_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int G
         const bool c2 = s.y_bits > o.inp_bits || s.y_exp > o.inp_exp;
         if (!shift_ok((c2 ? o.inp_exp : s.y_exp) + o.w_exp - o.out_exp)) return S5FXP_ENEGSHIFT;
     }
+    return S5FXP_OK;
+}
+
+// Threads of a workgroup for G groups with `smem` bytes of dynamic LDS each.  Workgroups of one CU: eight waves by registers,
+// 160 KB of LDS
+int step_threads(int G, size_t smem)
+{
+    const size_t fit = (160 * 1024) / (smem + STEP_STATIC_LDS);
+    if (G <= STEP_CUS || fit < 2) return 512;
+    if (G <= 2 * STEP_CUS || fit < 4) return 256;
+    return 128;
+}
+
+int step_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int G, int B, int L, void *y, const int32_t *state_in,
+               int32_t *state_out, int32_t *status, void *stream, bool f32)
+{
+    if (const int rc = step_checks(m, x, x_bits, x_exp, G, B, L, y, status, f32)) return rc;
     const size_t smem = step_lds(B * L, m->H, m->P, fast_shape(m->H, m->P).hp, m->d_in).total;
     StepArgs a{};
     a.sp = m->fast->step; a.x = x; a.y = y; a.state_in = state_in; a.state_out = state_out; a.status = status;
@@ -565,11 +278,32 @@ int step_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int G
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         hipLaunchKernelGGL(kernel, dim3((unsigned)G), dim3(threads), smem, S(stream), a);
     };
-    // workgroups of one CU: eight waves by registers, 160 KB of LDS
-    const size_t fit = (160 * 1024) / (smem + STEP_STATIC_LDS);
-    if (G <= STEP_CUS || fit < 2) launch(k_model_step<512>, 512);
-    else if (G <= 2 * STEP_CUS || fit < 4) launch(k_model_step<256>, 256);
+    const int threads = step_threads(G, smem);
+    if (threads == 512) launch(k_model_step<512>, 512);
+    else if (threads == 256) launch(k_model_step<256>, 256);
     else launch(k_model_step<128>, 128);
+    return launch_rc();
+}
+
+// The ragged form: the same checks at (B, Lmax), the dynamic LDS of B * Lmax rows, the same rule on n for the workgroup size.
+int step_ragged_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int n, int B, int Lmax, void *y,
+                      const s5fxp_push_desc *desc, int32_t *state, int n_slots, int32_t *status, void *stream, bool f32)
+{
+    if (!desc || !state || n_slots < 1) return S5FXP_EBADARG;
+    if (const int rc = step_checks(m, x, x_bits, x_exp, n, B, Lmax, y, status, f32)) return rc;
+    const size_t smem = step_lds(B * Lmax, m->H, m->P, fast_shape(m->H, m->P).hp, m->d_in).total;
+    StepRaggedArgs a{};
+    a.sp = m->fast->step; a.x = x; a.y = y; a.desc = desc; a.state = state; a.status = status;
+    a.B = B; a.Lmax = Lmax; a.x_bits = x_bits; a.x_exp = x_exp; a.f32 = f32 ? 1 : 0;
+    auto launch = [&](auto kernel, unsigned threads) {
+        if (smem > 65536)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(threads), smem, S(stream), a);
+    };
+    const int threads = step_threads(n, smem);
+    if (threads == 512) launch(k_model_step_ragged<512>, 512);
+    else if (threads == 256) launch(k_model_step_ragged<256>, 256);
+    else launch(k_model_step_ragged<128>, 128);
     return launch_rc();
 }
 
@@ -591,4 +325,38 @@ extern "C" int s5fxp_model_step_f32(const s5fxp_model *m, const float *x, int x_
                                     const int32_t *state_in, int32_t *state_out, int32_t *status, void *stream)
 {
     return step_entry(m, x, x_bits, x_exp, G, B, L, y, state_in, state_out, status, stream, true);
+}
+
+extern "C" int s5fxp_model_step_ragged(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int n, int B, int Lmax, int32_t *y,
+                                       const s5fxp_push_desc *desc, int32_t *state, int n_slots, int32_t *status, void *stream)
+{
+    return step_ragged_entry(m, x, x_bits, x_exp, n, B, Lmax, y, desc, state, n_slots, status, stream, false);
+}
+
+extern "C" int s5fxp_model_step_ragged_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int n, int B, int Lmax, float *y,
+                                           const s5fxp_push_desc *desc, int32_t *state, int n_slots, int32_t *status, void *stream)
+{
+    return step_ragged_entry(m, x, x_bits, x_exp, n, B, Lmax, y, desc, state, n_slots, status, stream, true);
+}
+
+// Host-only validation of a descriptor array (include/s5fxp.h): the kernels trust what they read.
+extern "C" int s5fxp_push_desc_check(const s5fxp_push_desc *d, int n, int n_slots, int Lmax, int cmax, int audio)
+{
+    if (!d || n < 1 || n_slots < 1 || Lmax < 0) return S5FXP_EBADARG;
+    if (audio && (cmax < 1 || cmax > S5FXP_STREAM_MAX_HOPS)) return S5FXP_EBADARG;
+    const int known = S5FXP_PUSH_FRESH | S5FXP_PUSH_ZEROS | S5FXP_PUSH_FINAL;
+    std::vector<bool> seen((size_t)n_slots, false);
+    bool short_final = false;
+    for (int e = 0; e < n; ++e) {
+        const s5fxp_push_desc &p = d[e];
+        if (p.slot < 0 || p.slot >= n_slots || seen[(size_t)p.slot]) return S5FXP_EBADARG;
+        seen[(size_t)p.slot] = true;
+        if (p.rows < 0 || p.rows > Lmax || (p.flags & ~known) || p.reserved[0] || p.reserved[1] || p.reserved[2]) return S5FXP_EBADARG;
+        if (!audio) continue;
+        if (p.hops < 1 || p.hops > cmax || p.h4 < 0 || p.h4 > 4) return S5FXP_EBADARG;
+        if ((p.flags & S5FXP_PUSH_FRESH) && p.h4 != 0) return S5FXP_EBADARG;
+        if (p.rows != p.hops - (p.h4 == 0 ? 1 : 0)) return S5FXP_EBADARG;
+        if ((p.flags & S5FXP_PUSH_FINAL) && p.h4 < 4) short_final = true;
+    }
+    return short_final ? S5FXP_EUNSUPPORTED : S5FXP_OK;
 }

@@ -576,6 +576,7 @@ class SessionPool:
         self._y: Dict[tuple, torch.Tensor] = {}
         self._err = torch.zeros(self.sessions, dtype=torch.int32, device=engine.device)  # error bits of unchecked pushes
         self._unchecked = False
+        self._desc = None   # push_ragged: (device descriptors, [pinned staging buffer, its copy's event] x 2, turn)
 
     @property
     def state(self) -> torch.Tensor:
@@ -675,6 +676,140 @@ class SessionPool:
         else:
             self._batch(eng, data, xb, xe, y, L, check)
         self.frames += L
+        return FxpArray(y, eng.out_bits, eng.out_exp, True) if fxp else y
+
+
+    # -- sessions that start, stop and idle on their own -----------------------------------------------------
+    def stage_desc(self, ids, rows, flags, hops=None, h4=None, Lmax: int = 0, cmax: int = 0) -> torch.Tensor:
+        """Builds the ``s5fxp_push_desc`` array of a ragged push (one entry per id: sequences or arrays of integers; `hops` /
+        `h4` for the audio kernels), validates it on the host (``s5fxp_push_desc_check``) and copies it to the device without
+        blocking.  Returns the device array, (len(ids), 8) int32, valid until the next call.  Two pinned staging buffers
+        alternate, and one is written again only after the copy that last read it has completed."""
+        n, audio = len(ids), hops is not None
+        if self._desc is None:
+            dev = torch.zeros((self.sessions, 8), dtype=torch.int32, device=self.engine.device)
+            pins = [torch.zeros((self.sessions, 8), dtype=torch.int32).pin_memory() for _ in range(2)]
+            self._desc = [dev, [[p, p.numpy(), torch.cuda.Event(), False] for p in pins], 0]
+        dev, pins, turn = self._desc
+        if not 1 <= n <= self.sessions:
+            raise ValueError(f"a push names 1 .. {self.sessions} sessions, got {n}")
+        pin = pins[turn]
+        if pin[3]:
+            pin[2].synchronize()   # the copy that last read this buffer
+        host = pin[1]
+        host[:n, 0], host[:n, 1], host[:n, 2] = ids, rows, flags
+        if audio:
+            host[:n, 3], host[:n, 4] = hops, h4
+        else:
+            host[:n, 3:5] = 0
+        check(lib.s5fxp_push_desc_check(host.ctypes.data, n, self.sessions, int(Lmax), int(cmax), int(audio)), "s5fxp_push_desc_check")
+        out = dev[:n]
+        out.copy_(pin[0][:n], non_blocking=True)
+        pin[2].record()
+        pin[3] = True
+        self._desc[2] = turn ^ 1
+        return out
+
+    def _entry(self, eng: "Engine", e: int, slot: int, data, xb, xe, y, L: int, fresh: bool, fxp: bool) -> None:
+        """One entry of a ragged push on the per-session route: ``forward_chunk*`` of `eng` on the slot's carry."""
+        if fresh:
+            self._state[slot].zero_()
+        if L == 0:
+            return
+        chunk = data[e][..., :L, :].contiguous()
+        if fxp:
+            out, new = eng.forward_chunk(FxpArray(chunk, xb, xe, True), self._state[slot])
+            out = out.data
+        else:
+            out, new = eng.forward_chunk_float(chunk, self._state[slot], xb, xe)
+        y[e][..., :L, :] = out
+        self._state[slot].copy_(new)
+
+    def push_ragged(self, ids, x, rows, fresh=(), check: bool = True, desc: Optional[torch.Tensor] = None):
+        """One push for any subset of the pool: entry e is session ``ids[e]`` with its first ``rows[e]`` frames (0 .. Lmax) of
+        x[e]; sessions not named idle.  x: (n, Lmax, d_in) (B == 1) or (n, B, Lmax, d_in), an FxpArray or a float32 tensor;
+        ids, rows and fresh are sequences or arrays of integers.  Returns the padded outputs of the same leading shape: frames
+        rows[e] .. Lmax-1 of entry e are never read and their outputs are not written.  Sessions in `fresh` start a new
+        signal: their carry is taken as zeros (no reset needed), and with rows == 0 it is zeroed.  One kernel launch
+        (``s5fxp_model_step_ragged``) updates the carries in place.  Each entry computes what ``push`` computes for that
+        session alone with that chunk.  `desc`: the descriptor array of exactly these ids, rows and fresh, already validated
+        and staged with ``stage_desc`` (audio.SessionDenoiser shares one among its three launches).
+
+        check=True reads the status words: an entry that came back with ST_WIDE_INPUT -- its outputs and carry untouched -- is
+        served from its carry by the generic engine; NEGSHIFT / NEGEXP raise ValueError, and the carries of the sessions of
+        that push are then invalid and need ``reset(ids)``.  check=False folds the status words into the pool as ``push``
+        does.  A model or chunk the step kernel does not serve takes ``Engine.forward_chunk*`` entry by entry: correct, not
+        fast."""
+        eng = self.engine
+        fxp = isinstance(x, FxpArray)
+        if fxp:
+            data, xb, xe = x.data, x.bits, x.exp
+            if data.dtype != torch.int32:
+                raise ValueError(f"expected int32 FxpArray data, got {data.dtype}")
+        else:
+            data = torch.as_tensor(x)
+            if data.dtype != torch.float32:
+                raise ValueError(f"expected an FxpArray or a float32 tensor, got {data.dtype}")
+            xb, xe = eng.inp_bits, eng.inp_exp
+        data = data.to(eng.device).contiguous()
+        ids, rows, B = np.asarray(ids, dtype=np.int64).reshape(-1), np.asarray(rows, dtype=np.int64).reshape(-1), self.B
+        n = len(ids)
+        if data.ndim == 3 and B == 1:
+            Lmax = data.shape[1]
+        elif data.ndim == 4 and data.shape[1] == B:
+            Lmax = data.shape[2]
+        else:
+            raise ValueError(f"expected (n, Lmax, {eng.d_in})" + (f" or (n, {B}, Lmax, {eng.d_in})") + f", got {tuple(data.shape)}")
+        if n < 1 or data.shape[0] != n or len(rows) != n or data.shape[-1] != eng.d_in or Lmax < 1:
+            raise ValueError(f"expected one row count and one ({'' if B == 1 else str(B) + ', '}Lmax >= 1, {eng.d_in}) block per id, "
+                             f"got {n} ids, {len(rows)} row counts and x {tuple(data.shape)}")
+        new = np.zeros(n, dtype=bool) if not len(fresh) else np.isin(ids, np.asarray(fresh, dtype=np.int64))
+        if desc is None:
+            seen = np.zeros(self.sessions, dtype=bool)
+            if ids.min() < 0 or ids.max() >= self.sessions:
+                raise ValueError(f"ids must be sessions 0 .. {self.sessions - 1}, got {ids.tolist()}")
+            seen[ids] = True
+            if int(seen.sum()) != n:
+                raise ValueError(f"a session is named twice: {ids.tolist()}")
+            if rows.min() < 0 or rows.max() > Lmax:
+                raise ValueError(f"rows must be 0 .. {Lmax}, got {rows.tolist()}")
+            if int(new.sum()) != len(set(int(i) for i in fresh)):
+                raise ValueError("fresh names a session that is not in ids")
+        if check:
+            self.check()
+        key = ("ragged", tuple(data.shape[:-1]), data.dtype)
+        y = self._y.get(key)
+        if y is None:
+            y = self._y[key] = torch.empty(key[1] + (eng.d_out,), dtype=data.dtype, device=eng.device)
+        W = _lib.STATUS_WORDS
+        if eng.step_ok(B, Lmax):
+            if desc is None:
+                desc = self.stage_desc(ids, rows, new * _lib.PUSH_FRESH, Lmax=Lmax)
+            entry, name = ((lib.s5fxp_model_step_ragged, "s5fxp_model_step_ragged") if fxp else
+                           (lib.s5fxp_model_step_ragged_f32, "s5fxp_model_step_ragged_f32"))
+            st = eng.lane_status(self._lane, n)
+            eng._groups[self._lane] = n
+            _lib.check(entry(eng._h, data.data_ptr(), xb, xe, n, B, Lmax, y.data_ptr(), desc.data_ptr(), self._state.data_ptr(),
+                             self.sessions, st.data_ptr(), torch.cuda.current_stream().cuda_stream), name)
+            self.last_path = _lib.PATH_STEP
+            if check:
+                bits = st.cpu().numpy()[:n * W].reshape(n, W)[:, 0]
+                for e in np.nonzero(bits & _lib.ST_WIDE_INPUT)[0]:
+                    # the kernel left this entry's outputs and carry alone: the generic engine serves it from that carry
+                    self._entry(eng.generic_twin(), int(e), int(ids[e]), data, xb, xe, y, int(rows[e]), bool(new[e]), fxp)
+                    self.last_path = _lib.PATH_GENERIC
+                self._raise(int(np.bitwise_or.reduce(bits)) & ~_lib.ST_WIDE_INPUT)
+            else:
+                # check() reduces the words with OR: which session a word belongs to does not matter
+                self._err[:n] |= st[:n * W].view(n, W)[:, 0]
+                self._unchecked = True
+        else:
+            for e in range(n):
+                self._entry(eng, e, int(ids[e]), data, xb, xe, y, int(rows[e]), bool(new[e]), fxp)
+            self.last_path = _lib.PATH_FUSED if lib.s5fxp_model_is_fast(eng._h) else _lib.PATH_GENERIC
+        if new.any():
+            self.frames[ids[new]] = 0
+        self.frames[ids] += rows
         return FxpArray(y, eng.out_bits, eng.out_exp, True) if fxp else y
 
 
