@@ -123,24 +123,43 @@ def _audio2d(audio: torch.Tensor) -> torch.Tensor:
     return audio.to(torch.float32).contiguous()
 
 
+def _stft_launch(audio: torch.Tensor, n_seg: int, dtype: torch.dtype, spectrum: bool, entry: str, *extra):
+    """The GPU route of ``stft_mag`` / ``stft_mag_i16``: audio (B, T) float32 on a GPU -> x (B, n_seg, 257) of `dtype` (and the
+    complex64 spectrum) from one launch of `entry`, whose arguments between T and x are `extra`."""
+    from . import _lib
+    B, T = audio.shape
+    shape = (B, n_seg, NFFT // 2 + 1)
+    x = torch.empty(shape, dtype=dtype, device=audio.device)
+    spec = torch.empty(shape, dtype=torch.complex64, device=audio.device) if spectrum else None
+    with torch.cuda.device(audio.device):
+        _lib.check(getattr(_lib.lib, entry)(audio.data_ptr(), B, T, *extra, x.data_ptr(), spec.data_ptr() if spectrum else None,
+                                            torch.cuda.current_stream().cuda_stream), entry)
+    return (x, spec) if spectrum else x
+
+
+def _istft_launch(audio: torch.Tensor, n_seg: int, cleaned_mag: bool, entry: str, *mask):
+    """The GPU route of ``mask_istft`` / ``mask_istft_i16``: one launch of `entry`, whose arguments between audio and B are
+    `mask`."""
+    from . import _lib
+    B, T = audio.shape
+    out = torch.empty(B, (n_seg - 1) * HOP, dtype=torch.float32, device=audio.device)
+    cm = torch.empty((B, n_seg, NFFT // 2 + 1), dtype=torch.float32, device=audio.device) if cleaned_mag else None
+    with torch.cuda.device(audio.device):
+        _lib.check(getattr(_lib.lib, entry)(audio.data_ptr(), *mask, B, T, out.data_ptr(), cm.data_ptr() if cleaned_mag else None,
+                                            torch.cuda.current_stream().cuda_stream), entry)
+    return (out, cm) if cleaned_mag else out
+
+
 def stft_mag(audio: torch.Tensor, sub: float = STFT_MAG_MEAN, spectrum: bool = False):
     """audio (B, T) -> x = |Z| - sub, (B, n_seg, 257) float32 (fxprun.py:64-65: the model's input rows); with ``spectrum``
     also the complex64 spectrum Z, same shape."""
     audio = _audio2d(audio)
-    B, T = audio.shape
-    n_seg = stft_frames(T)
+    n_seg = stft_frames(audio.shape[1])
     if not audio.is_cuda:
         z = stft(audio).transpose(-1, -2).contiguous()
         x = z.abs() - sub
         return (x, z) if spectrum else x
-    from . import _lib
-    x = torch.empty(B, n_seg, NFFT // 2 + 1, dtype=torch.float32, device=audio.device)
-    spec = torch.empty(B, n_seg, NFFT // 2 + 1, dtype=torch.complex64, device=audio.device) if spectrum else None
-    with torch.cuda.device(audio.device):
-        _lib.check(_lib.lib.s5fxp_stft_mag(audio.data_ptr(), B, T, float(sub), x.data_ptr(),
-                                           spec.data_ptr() if spectrum else None,
-                                           torch.cuda.current_stream().cuda_stream), "s5fxp_stft_mag")
-    return (x, spec) if spectrum else x
+    return _stft_launch(audio, n_seg, torch.float32, spectrum, "s5fxp_stft_mag", float(sub))
 
 
 def mask_istft(audio: torch.Tensor, mask, cleaned_mag: bool = False):
@@ -160,14 +179,7 @@ def mask_istft(audio: torch.Tensor, mask, cleaned_mag: bool = False):
         f = 1.0 + mask if mask is not None else torch.ones(shape, dtype=torch.float32)
         out = istft((z * f).transpose(-1, -2))
         return (out, z.abs() * f) if cleaned_mag else out
-    from . import _lib
-    out = torch.empty(B, (n_seg - 1) * HOP, dtype=torch.float32, device=audio.device)
-    cm = torch.empty(shape, dtype=torch.float32, device=audio.device) if cleaned_mag else None
-    with torch.cuda.device(audio.device):
-        _lib.check(_lib.lib.s5fxp_mask_istft(audio.data_ptr(), mask.data_ptr() if mask is not None else None, B, T,
-                                             out.data_ptr(), cm.data_ptr() if cleaned_mag else None,
-                                             torch.cuda.current_stream().cuda_stream), "s5fxp_mask_istft")
-    return (out, cm) if cleaned_mag else out
+    return _istft_launch(audio, n_seg, cleaned_mag, "s5fxp_mask_istft", mask.data_ptr() if mask is not None else None)
 
 
 def _int16_range(bits: int, exp: int, what: str) -> None:
@@ -181,8 +193,7 @@ def stft_mag_i16(audio: torch.Tensor, x_bits: int, x_exp: int, sub: float = STFT
     bytes of the float rows, which are never written."""
     _int16_range(x_bits, x_exp, "stft_mag_i16")
     audio = _audio2d(audio)
-    B, T = audio.shape
-    n_seg = stft_frames(T)
+    n_seg = stft_frames(audio.shape[1])
     if not audio.is_cuda:
         r = stft_mag(audio, sub, spectrum)
         xf, z = r if spectrum else (r, None)
@@ -191,14 +202,7 @@ def stft_mag_i16(audio: torch.Tensor, x_bits: int, x_exp: int, sub: float = STFT
         q = torch.floor(xf * float(2.0 ** int(x_exp)))
         x = torch.nan_to_num(q, nan=0.0, posinf=hi, neginf=-hi - 1.0).clamp(-hi - 1.0, hi).to(torch.int16)
         return (x, z) if spectrum else x
-    from . import _lib
-    x = torch.empty(B, n_seg, NFFT // 2 + 1, dtype=torch.int16, device=audio.device)
-    spec = torch.empty(B, n_seg, NFFT // 2 + 1, dtype=torch.complex64, device=audio.device) if spectrum else None
-    with torch.cuda.device(audio.device):
-        _lib.check(_lib.lib.s5fxp_stft_mag_i16(audio.data_ptr(), B, T, float(sub), int(x_bits), int(x_exp), x.data_ptr(),
-                                               spec.data_ptr() if spectrum else None,
-                                               torch.cuda.current_stream().cuda_stream), "s5fxp_stft_mag_i16")
-    return (x, spec) if spectrum else x
+    return _stft_launch(audio, n_seg, torch.int16, spectrum, "s5fxp_stft_mag_i16", float(sub), int(x_bits), int(x_exp))
 
 
 def mask_istft_i16(audio: torch.Tensor, mask: torch.Tensor, mask_exp: int, cleaned_mag: bool = False):
@@ -214,14 +218,7 @@ def mask_istft_i16(audio: torch.Tensor, mask: torch.Tensor, mask_exp: int, clean
     mask = mask.contiguous()
     if not audio.is_cuda:
         return mask_istft(audio, torch.ldexp(mask.to(torch.float32), torch.tensor(-int(mask_exp))), cleaned_mag)
-    from . import _lib
-    out = torch.empty(B, (n_seg - 1) * HOP, dtype=torch.float32, device=audio.device)
-    cm = torch.empty(shape, dtype=torch.float32, device=audio.device) if cleaned_mag else None
-    with torch.cuda.device(audio.device):
-        _lib.check(_lib.lib.s5fxp_mask_istft_i16(audio.data_ptr(), mask.data_ptr(), int(mask_exp), B, T, out.data_ptr(),
-                                                 cm.data_ptr() if cleaned_mag else None,
-                                                 torch.cuda.current_stream().cuda_stream), "s5fxp_mask_istft_i16")
-    return (out, cm) if cleaned_mag else out
+    return _istft_launch(audio, n_seg, cleaned_mag, "s5fxp_mask_istft_i16", mask.data_ptr(), int(mask_exp))
 
 
 def denoise_fused(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, boundary: str = "float32"):

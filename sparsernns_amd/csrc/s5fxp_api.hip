@@ -281,52 +281,63 @@ extern "C" int s5fxp_assoc_scan_c64(const float *lambda, const float *bu, float 
 // The audio steps either side of the model (audio_stft.hpp).  n_seg = ceil(T / 128) + 1 frames for T >= 512.
 extern "C" int64_t s5fxp_stft_frames(int64_t T) { return T < stft::NFFT ? -1 : (T + stft::HOP - 1) / stft::HOP + 1; }
 
-extern "C" int s5fxp_stft_mag(const float *audio, int B, int64_t T, float sub, float *x, float *spec, void *stream)
+// One checked launch per direction: the arguments and the tile arithmetic the float and the int16 entry share.  extra_ok: the
+// boundary's own argument checks; launch(grid, n_seg, tiles) enqueues its kernel.
+namespace {
+template <class Launch>
+int stft_mag_entry(const float *audio, const void *x, int B, int64_t T, bool extra_ok, Launch launch)
 {
-    if (!audio || !x || B < 1) return S5FXP_EBADARG;
+    if (!audio || !x || B < 1 || !extra_ok) return S5FXP_EBADARG;
     if (T < stft::NFFT) return S5FXP_EUNSUPPORTED;
     const int64_t n_seg = s5fxp_stft_frames(T), tiles = (n_seg + stft::FR - 1) / stft::FR;
     if (tiles * B > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
-    hipLaunchKernelGGL(stft::k_stft_mag, dim3((unsigned)(tiles * B)), dim3(256), 0, S(stream), audio, T, n_seg, (int)tiles, sub, x,
-                       reinterpret_cast<float2 *>(spec));
+    launch(dim3((unsigned)(tiles * B)), n_seg, (int)tiles);
     return launch_rc();
+}
+
+template <class Launch>
+int mask_istft_entry(const float *audio, const float *out, int B, int64_t T, bool extra_ok, Launch launch)
+{
+    if (!audio || !out || B < 1 || !extra_ok) return S5FXP_EBADARG;
+    if (T < stft::NFFT) return S5FXP_EUNSUPPORTED;
+    const int64_t n_seg = s5fxp_stft_frames(T), tiles = (n_seg - 1 + stft::OH - 1) / stft::OH;
+    if (tiles * B > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
+    launch(dim3((unsigned)(tiles * B)), n_seg, (int)tiles);
+    return launch_rc();
+}
+} // namespace
+
+extern "C" int s5fxp_stft_mag(const float *audio, int B, int64_t T, float sub, float *x, float *spec, void *stream)
+{
+    return stft_mag_entry(audio, x, B, T, true, [&](dim3 grid, int64_t n_seg, int tiles) {
+        hipLaunchKernelGGL(stft::k_stft_mag, grid, dim3(256), 0, S(stream), audio, T, n_seg, tiles, sub, x, reinterpret_cast<float2 *>(spec));
+    });
 }
 
 extern "C" int s5fxp_mask_istft(const float *audio, const float *mask, int B, int64_t T, float *out, float *cleaned_mag,
                                 void *stream)
 {
-    if (!audio || !out || B < 1) return S5FXP_EBADARG;
-    if (T < stft::NFFT) return S5FXP_EUNSUPPORTED;
-    const int64_t n_seg = s5fxp_stft_frames(T), tiles = (n_seg - 1 + stft::OH - 1) / stft::OH;
-    if (tiles * B > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
-    hipLaunchKernelGGL(stft::k_mask_istft, dim3((unsigned)(tiles * B)), dim3(256), 0, S(stream), audio, mask, T, n_seg, (int)tiles,
-                       out, cleaned_mag);
-    return launch_rc();
+    return mask_istft_entry(audio, out, B, T, true, [&](dim3 grid, int64_t n_seg, int tiles) {
+        hipLaunchKernelGGL(stft::k_mask_istft, grid, dim3(256), 0, S(stream), audio, mask, T, n_seg, tiles, out, cleaned_mag);
+    });
 }
 
 // ... with the model's int16 boundary (s5fxp_model_forward_i16) on the model's side of both
 extern "C" int s5fxp_stft_mag_i16(const float *audio, int B, int64_t T, float sub, int x_bits, int x_exp, int16_t *x, float *spec,
                                   void *stream)
 {
-    if (!audio || !x || B < 1 || x_bits < 1 || x_bits > 16 || x_exp < 0 || x_exp > 31) return S5FXP_EBADARG;
-    if (T < stft::NFFT) return S5FXP_EUNSUPPORTED;
-    const int64_t n_seg = s5fxp_stft_frames(T), tiles = (n_seg + stft::FR - 1) / stft::FR;
-    if (tiles * B > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
-    hipLaunchKernelGGL(stft::k_stft_mag_i16, dim3((unsigned)(tiles * B)), dim3(256), 0, S(stream), audio, T, n_seg, (int)tiles, sub,
-                       x_bits, x_exp, x, reinterpret_cast<float2 *>(spec));
-    return launch_rc();
+    return stft_mag_entry(audio, x, B, T, x_bits >= 1 && x_bits <= 16 && shift_ok(x_exp), [&](dim3 grid, int64_t n_seg, int tiles) {
+        hipLaunchKernelGGL(stft::k_stft_mag_i16, grid, dim3(256), 0, S(stream), audio, T, n_seg, tiles, sub, x_bits, x_exp, x,
+                           reinterpret_cast<float2 *>(spec));
+    });
 }
 
 extern "C" int s5fxp_mask_istft_i16(const float *audio, const int16_t *mask, int mask_exp, int B, int64_t T, float *out,
                                     float *cleaned_mag, void *stream)
 {
-    if (!audio || !out || B < 1 || mask_exp < 0 || mask_exp > 31) return S5FXP_EBADARG;
-    if (T < stft::NFFT) return S5FXP_EUNSUPPORTED;
-    const int64_t n_seg = s5fxp_stft_frames(T), tiles = (n_seg - 1 + stft::OH - 1) / stft::OH;
-    if (tiles * B > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
-    hipLaunchKernelGGL(stft::k_mask_istft_i16, dim3((unsigned)(tiles * B)), dim3(256), 0, S(stream), audio, mask, mask_exp, T, n_seg,
-                       (int)tiles, out, cleaned_mag);
-    return launch_rc();
+    return mask_istft_entry(audio, out, B, T, shift_ok(mask_exp), [&](dim3 grid, int64_t n_seg, int tiles) {
+        hipLaunchKernelGGL(stft::k_mask_istft_i16, grid, dim3(256), 0, S(stream), audio, mask, mask_exp, T, n_seg, tiles, out, cleaned_mag);
+    });
 }
 
 // The same framing for a live signal (audio_stream.hpp): whole hops in, cleaned hops out, the caller's state between calls.
@@ -818,24 +829,18 @@ struct GenericRun {
     const s5fxp_forward_opts *opts;
     hipStream_t st;
     void *stream;
+
+    const s5fxp_allreduce_max_fn allreduce = opts ? opts->allreduce : nullptr;
+    void *const allreduce_ctx = opts ? opts->allreduce_ctx : nullptr;
+    void **const scan_events = opts ? opts->scan_events : nullptr;
+    const int32_t *const state_in = opts ? opts->state_in : nullptr;
+    int32_t *const state_out = opts ? opts->state_out : nullptr;
+
+    int layers(int first, int last, int32_t *&h, int32_t *&hn, int &hb, DynExp &he) const;
 };
 
-int generic_layers(const GenericRun &g, int first, int last, int32_t *&h, int32_t *&hn, int &hb, DynExp &he)
+int GenericRun::layers(int first, int last, int32_t *&h, int32_t *&hn, int &hb, DynExp &he) const
 {
-    const s5fxp_model *m = g.m;
-    const int B = g.B, L = g.L;
-    const WsLayout &w = g.w;
-    char *ws = g.ws;
-    LayerDyn *dyn = g.dyn;
-    int32_t *status = g.status;
-    const s5fxp_layer_trace *traces = g.traces;
-    hipStream_t st = g.st;
-    void *stream = g.stream;
-    s5fxp_allreduce_max_fn allreduce = g.opts ? g.opts->allreduce : nullptr;
-    void *allreduce_ctx = g.opts ? g.opts->allreduce_ctx : nullptr;
-    void **scan_events = g.opts ? g.opts->scan_events : nullptr;
-    const int32_t *state_in = g.opts ? g.opts->state_in : nullptr;
-    int32_t *state_out = g.opts ? g.opts->state_out : nullptr;
     auto I = [&](size_t off) { return reinterpret_cast<int32_t *>(ws + off); };
     const int64_t N = (int64_t)B * L;
     const int H = m->H, P = m->P;
@@ -844,7 +849,7 @@ int generic_layers(const GenericRun &g, int first, int last, int32_t *&h, int32_
     int rc;
     for (int li = first; li < last; ++li) {
         const LayerDev &l = m->layers[li];
-        const s5fxp_layer_trace *tr = traces ? &traces[li - g.trace_base] : nullptr;
+        const s5fxp_layer_trace *tr = traces ? &traces[li - trace_base] : nullptr;
         LayerDyn *d = dyn + li;
         int32_t *st_exps = status + 8 + 8 * li;
         const s5fxp_ssm_desc &s = l.sd;
@@ -854,7 +859,7 @@ int generic_layers(const GenericRun &g, int first, int last, int32_t *&h, int32_
         const unsigned rg = ew_grid(NH) > 2048 ? 2048 : ew_grid(NH);
         if ((rc = bn_exponent_ops([&](auto op) {
                  hipLaunchKernelGGL(k_bn_reduce<decltype(op)::value>, dim3(rg), dim3(256), 0, st, bn, h, NH, H, d);
-             }, bn, d, status, st_exps, g.opts, st)))
+             }, bn, d, status, st_exps, opts, st)))
             return rc;
 
         // ---- B projection (fused BatchNorm apply + change_cfg), writes the scan-native stream
@@ -966,91 +971,123 @@ void clear_status_generic(const s5fxp_model *m, int first, int last, int32_t *st
     hipLaunchKernelGGL(k_clear2, dim3(1), dim3(256), 0, st, status, (int)S5FXP_STATUS_WORDS, (int32_t *)nullptr, 0, si, m->n_layers, GroupOff{});
 }
 
+// encoder and decoder of the generic forward: one frame-tiled k_dense each
+void launch_dense(const DenseDev &e, const int32_t *x, int xb, DynExp xe, int32_t *y, int64_t N, bool first, int32_t *status, hipStream_t st)
+{
+    DenseArgs a{};
+    a.x = x; a.w = e.w; a.bias = e.bias; a.y = y; a.N = N; a.K = e.K; a.M = e.M; a.mw = mw_for(e.M);
+    a.xb = xb; a.xe = xe; a.inp_bits = e.inp_bits; a.inp_exp = e.inp_exp; a.check_inp = 1;
+    a.w_exp = e.w_exp; a.b_bits = e.b_bits; a.b_exp = e.b_exp; a.out_bits = e.out_bits; a.out_exp = e.out_exp;
+    a.relu = first; a.check24 = first; a.status = status; // the encoder: ReLU, and the 24-bit check of the model's input
+    const unsigned tiles = (unsigned)((N + TN - 1) / TN);
+    if (e.x24 && (first || xb <= 24)) S5_DISPATCH_MW(a.mw, true, k_dense, tiles, st, a);
+    else S5_DISPATCH_MW(a.mw, false, k_dense, tiles, st, a);
+}
+
+// The forward on the generic int32 kernels (arguments checked by forward_entry): encoder, the layers, decoder
+int forward_generic(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int B, int L, int32_t *y, void *workspace,
+                    int32_t *status, const s5fxp_layer_trace *traces, const s5fxp_forward_opts *opts, void *stream)
+{
+    const WsLayout w = ws_layout(m, B, L);
+    hipStream_t st = S(stream);
+    char *ws = reinterpret_cast<char *>(workspace);
+    LayerDyn *dyn = reinterpret_cast<LayerDyn *>(ws + w.dyn);
+    const int64_t N = (int64_t)B * L;
+    int rc;
+    clear_status_generic(m, 0, m->n_layers, status, st);
+    if ((rc = hip_rc(hipMemsetAsync(dyn, 0, sizeof(LayerDyn) * (size_t)(m->n_layers ? m->n_layers : 1), st)))) return rc;
+
+    // ---- encoder + ReLU (fxpmodel.py:1263-1266)
+    int32_t *h = reinterpret_cast<int32_t *>(ws + w.hA), *hn = reinterpret_cast<int32_t *>(ws + w.hB);
+    const DenseDev &e = m->enc;
+    const bool conv = x_bits > e.inp_bits || x_exp > e.inp_exp;
+    if (!shift_ok((conv ? e.inp_exp : x_exp) + e.w_exp - e.out_exp)) return S5FXP_ENEGSHIFT;
+    launch_dense(e, x, x_bits, DynExp{x_exp, nullptr}, h, N, true, status, st);
+    int hb = e.out_bits;
+    DynExp he{e.out_exp, nullptr};
+
+    const GenericRun g{m, B, L, w, ws, dyn, status, traces, 0, opts, st, stream};
+    if ((rc = g.layers(0, m->n_layers, h, hn, hb, he))) return rc;
+
+    // ---- decoder (fxpmodel.py:1437): its input exponent is the last residual's
+    launch_dense(m->dec, h, hb, he, y, N, false, status, st);
+    return launch_rc();
+}
+
+inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// The one forward entry behind s5fxp_model_forward (io = IO_I32: int32 x and y), s5fxp_model_forward_f32 (IO_F32: float32) and
+// s5fxp_model_forward_i16 (IO_I16: int16; the constants of proj_p.hpp).  A fused model converts inside its encoder and decoder
+// kernels (k_enc_pf / k_dec_pf, k_enc_ps / k_dec_ps) on the int forward's workspace; a generic one stages int32 copies of x and y
+// behind the int forward's workspace and converts before and after it: k_from_fp / k_to_float (the float-in, float-out forward
+// of fxprun.py:63-88) or k_widen_i16 / k_narrow_i16.  The checks come in this order: arguments, what the model supports, the
+// workspace, the stream extent.
+int forward_entry(const s5fxp_model *m, int io, const void *x, int x_bits, int x_exp, int B, int L, void *y, void *workspace,
+                  size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces, const s5fxp_forward_opts *opts,
+                  void *stream)
+{
+    if (!m || !x || !y || !workspace || !status || B < 1 || L < 1 || x_bits < 1 || x_bits > (io == IO_I16 ? 16 : 32) ||
+        (io == IO_F32 && !shift_ok(x_exp)))
+        return S5FXP_EBADARG;
+    if (io == IO_F32 && !shift_ok(m->dec.out_exp)) return S5FXP_EUNSUPPORTED; // the range s5fxp_to_float takes
+    if (io == IO_I16 && m->dec.out_bits > 16) return S5FXP_EUNSUPPORTED;       // the narrowing of y would lose bits
+    const int G = opts && opts->groups > 1 ? opts->groups : 1;
+    const size_t ws_one = io == IO_I32   ? s5fxp_workspace_bytes(m, B, L)
+                          : io == IO_F32 ? s5fxp_workspace_bytes_f32(m, B, L)
+                                         : s5fxp_workspace_bytes_i16(m, B, L);
+    if (workspace_bytes < (size_t)G * ws_one) return S5FXP_EWORKSPACE;
+    const size_t N = (size_t)B * L;
+    if (G > 1) {
+        // Grouped call: G independent reference batches of B sequences each.  The fused kernels take them in ONE set of
+        // launches (gridDim.y = G) when nothing couples the groups on the host; otherwise one (fused or generic) forward per group.
+        if (m->fast && !traces && !opts->allreduce && fast_bn_ext(m) && stream_extent_ok(m, L))
+            return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), G, ws_one, io);
+        const size_t esz = io == IO_I16 ? 2 : 4, plane = (size_t)m->n_layers * 2 * B * (m->P ? m->P : 1);
+        for (int g = 0; g < G; ++g) {
+            s5fxp_forward_opts o = *opts;
+            o.groups = 1;
+            if (o.state_in) o.state_in += g * plane;
+            if (o.state_out) o.state_out += g * plane;
+            const int rc = forward_entry(m, io, static_cast<const char *>(x) + g * N * m->d_in * esz, x_bits, x_exp, B, L,
+                                         static_cast<char *>(y) + g * N * m->d_out * esz, static_cast<char *>(workspace) + g * ws_one,
+                                         ws_one, status + (size_t)g * S5FXP_STATUS_WORDS,
+                                         traces ? traces + (size_t)g * m->n_layers : nullptr, &o, stream);
+            if (rc) return rc;
+        }
+        return S5FXP_OK;
+    }
+    if (!stream_extent_ok(m, L)) return S5FXP_EBADARG;
+    if (m->fast) return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), 1, 0, io);
+    if (io == IO_I32)
+        return forward_generic(m, static_cast<const int32_t *>(x), x_bits, x_exp, B, L, static_cast<int32_t *>(y), workspace, status,
+                               traces, opts, stream);
+    // generic, float32 or int16: convert, the int forward, convert back, on int32 copies staged behind the int forward's workspace
+    int32_t *xi = reinterpret_cast<int32_t *>(static_cast<char *>(workspace) + s5fxp_workspace_bytes(m, B, L));
+    int32_t *yi = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(xi) + al256(N * m->d_in * 4));
+    const int64_t nx = (int64_t)N * m->d_in, ny = (int64_t)N * m->d_out;
+    int rc;
+    if (io == IO_F32) {
+        if ((rc = s5fxp_from_fp(static_cast<const float *>(x), xi, nx, x_bits, x_exp, S5FXP_FLOOR, stream))) return rc;
+    } else {
+        hipLaunchKernelGGL(k_widen_i16, dim3(ew_grid(nx)), dim3(256), 0, S(stream), static_cast<const int16_t *>(x), xi, nx);
+    }
+    if ((rc = forward_generic(m, xi, x_bits, x_exp, B, L, yi, workspace, status, traces, opts, stream))) return rc;
+    if (io == IO_F32) return s5fxp_to_float(yi, static_cast<float *>(y), ny, m->dec.out_exp, stream);
+    hipLaunchKernelGGL(k_narrow_i16, dim3(ew_grid(ny)), dim3(256), 0, S(stream), (const int32_t *)yi, static_cast<int16_t *>(y), ny);
+    return launch_rc();
+}
+
 } // namespace
 
 extern "C" int s5fxp_model_forward(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int B, int L,
                                    int32_t *y, void *workspace, size_t workspace_bytes, int32_t *status,
                                    const s5fxp_layer_trace *traces, const s5fxp_forward_opts *opts, void *stream)
 {
-    if (!m || !x || !y || !workspace || !status || B < 1 || L < 1 || x_bits < 1 || x_bits > 32) return S5FXP_EBADARG;
-    const int G = opts && opts->groups > 1 ? opts->groups : 1;
-    const size_t ws_one = s5fxp_workspace_bytes(m, B, L);
-    if (workspace_bytes < (size_t)G * ws_one) return S5FXP_EWORKSPACE;
-    if (G > 1) {
-        // Grouped call: G independent reference batches of B sequences each.  The fused kernels take them in ONE set of
-        // launches (gridDim.y = G) when nothing couples the groups on the host; otherwise one forward per group.
-        if (m->fast && !traces && !opts->allreduce && fast_bn_ext(m) && stream_extent_ok(m, L))
-            return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), G, ws_one);
-        const size_t plane = (size_t)m->n_layers * 2 * B * (m->P ? m->P : 1);
-        for (int g = 0; g < G; ++g) {
-            s5fxp_forward_opts o = *opts;
-            o.groups = 1;
-            if (o.state_in) o.state_in += g * plane;
-            if (o.state_out) o.state_out += g * plane;
-            const int rc = s5fxp_model_forward(m, x + (size_t)g * B * L * m->d_in, x_bits, x_exp, B, L, y + (size_t)g * B * L * m->d_out,
-                                               reinterpret_cast<char *>(workspace) + g * ws_one, ws_one, status + (size_t)g * S5FXP_STATUS_WORDS,
-                                               traces ? traces + (size_t)g * m->n_layers : nullptr, &o, stream);
-            if (rc) return rc;
-        }
-        return S5FXP_OK;
-    }
-    if (!stream_extent_ok(m, L)) return S5FXP_EBADARG;
-    if (m->fast) return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream));
-    const WsLayout w = ws_layout(m, B, L);
-    if (workspace_bytes < w.total) return S5FXP_EWORKSPACE;
-    hipStream_t st = S(stream);
-    char *ws = reinterpret_cast<char *>(workspace);
-    auto I = [&](size_t off) { return reinterpret_cast<int32_t *>(ws + off); };
-    LayerDyn *dyn = reinterpret_cast<LayerDyn *>(ws + w.dyn);
-    const int64_t N = (int64_t)B * L;
-    const unsigned tiles = (unsigned)((N + TN - 1) / TN);
-    int rc;
-    clear_status_generic(m, 0, m->n_layers, status, st);
-    if ((rc = hip_rc(hipMemsetAsync(dyn, 0, sizeof(LayerDyn) * (size_t)(m->n_layers ? m->n_layers : 1), st)))) return rc;
-
-    // ---- encoder + ReLU (fxpmodel.py:1263-1266)
-    int32_t *h = I(w.hA), *hn = I(w.hB);
-    {
-        const DenseDev &e = m->enc;
-        DenseArgs a{};
-        a.x = x; a.w = e.w; a.bias = e.bias; a.y = h; a.N = N; a.K = e.K; a.M = e.M; a.mw = mw_for(e.M);
-        a.xb = x_bits; a.xe = DynExp{x_exp, nullptr}; a.inp_bits = e.inp_bits; a.inp_exp = e.inp_exp; a.check_inp = 1;
-        a.w_exp = e.w_exp; a.b_bits = e.b_bits; a.b_exp = e.b_exp; a.out_bits = e.out_bits; a.out_exp = e.out_exp;
-        a.relu = 1; a.check24 = 1; a.status = status;
-        const bool conv = x_bits > e.inp_bits || x_exp > e.inp_exp;
-        if (!shift_ok((conv ? e.inp_exp : x_exp) + e.w_exp - e.out_exp)) return S5FXP_ENEGSHIFT;
-        if (e.x24) S5_DISPATCH_MW(a.mw, true, k_dense, tiles, st, a);
-        else S5_DISPATCH_MW(a.mw, false, k_dense, tiles, st, a);
-    }
-    int hb = m->enc.out_bits;
-    DynExp he{m->enc.out_exp, nullptr};
-
-    {
-        GenericRun g{m, B, L, w, ws, dyn, status, traces, 0, opts, st, stream};
-        if ((rc = generic_layers(g, 0, m->n_layers, h, hn, hb, he))) return rc;
-    }
-
-    // ---- decoder (fxpmodel.py:1437): its input exponent is the last residual's
-    {
-        const DenseDev &e = m->dec;
-        DenseArgs a{};
-        a.x = h; a.w = e.w; a.bias = e.bias; a.y = y; a.N = N; a.K = e.K; a.M = e.M; a.mw = mw_for(e.M);
-        a.xb = hb; a.xe = he; a.inp_bits = e.inp_bits; a.inp_exp = e.inp_exp; a.check_inp = 1;
-        a.w_exp = e.w_exp; a.b_bits = e.b_bits; a.b_exp = e.b_exp; a.out_bits = e.out_bits; a.out_exp = e.out_exp;
-        a.relu = 0; a.check24 = 0; a.status = status;
-        if (e.x24 && hb <= 24) S5_DISPATCH_MW(a.mw, true, k_dense, tiles, st, a);
-        else S5_DISPATCH_MW(a.mw, false, k_dense, tiles, st, a);
-    }
-    return launch_rc();
+    return forward_entry(m, IO_I32, x, x_bits, x_exp, B, L, y, workspace, workspace_bytes, status, traces, opts, stream);
 }
 
-// The float-in, float-out forward of fxprun.py:63-88.  A fused model converts inside its encoder and decoder kernels (proj_p.hpp
-// k_enc_pf / k_dec_pf) and needs no more workspace than an int forward; a generic one stages the int32 input and output behind
-// the int forward's workspace and runs k_from_fp -> the int forward -> k_to_float.
-namespace {
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-}
-
+// A generic model's float32 / int16 forward stages 4 bytes per element of both tensors behind the int forward's workspace; a
+// fused one needs no more than an int forward (forward_entry)
 extern "C" size_t s5fxp_workspace_bytes_f32(const s5fxp_model *m, int B, int L)
 {
     const size_t ws = s5fxp_workspace_bytes(m, B, L);
@@ -1063,47 +1100,9 @@ extern "C" int s5fxp_model_forward_f32(const s5fxp_model *m, const float *x, int
                                        void *workspace, size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces,
                                        const s5fxp_forward_opts *opts, void *stream)
 {
-    if (!m || !x || !y || !workspace || !status || B < 1 || L < 1 || x_bits < 1 || x_bits > 32 || x_exp < 0 || x_exp > 31)
-        return S5FXP_EBADARG;
-    if (m->dec.out_exp < 0 || m->dec.out_exp > 31) return S5FXP_EUNSUPPORTED; // the range s5fxp_to_float takes
-    const int G = opts && opts->groups > 1 ? opts->groups : 1;
-    const size_t ws_one = s5fxp_workspace_bytes_f32(m, B, L);
-    if (workspace_bytes < (size_t)G * ws_one) return S5FXP_EWORKSPACE;
-    if (G > 1) {
-        // the same split as s5fxp_model_forward: one set of fused launches, or one (fused or generic) forward per group
-        if (m->fast && !traces && !opts->allreduce && fast_bn_ext(m) && stream_extent_ok(m, L))
-            return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), G, ws_one, IO_F32);
-        const size_t plane = (size_t)m->n_layers * 2 * B * (m->P ? m->P : 1);
-        for (int g = 0; g < G; ++g) {
-            s5fxp_forward_opts o = *opts;
-            o.groups = 1;
-            if (o.state_in) o.state_in += g * plane;
-            if (o.state_out) o.state_out += g * plane;
-            const int rc = s5fxp_model_forward_f32(m, x + (size_t)g * B * L * m->d_in, x_bits, x_exp, B, L, y + (size_t)g * B * L * m->d_out,
-                                                   reinterpret_cast<char *>(workspace) + g * ws_one, ws_one,
-                                                   status + (size_t)g * S5FXP_STATUS_WORDS, traces ? traces + (size_t)g * m->n_layers : nullptr,
-                                                   &o, stream);
-            if (rc) return rc;
-        }
-        return S5FXP_OK;
-    }
-    if (!stream_extent_ok(m, L)) return S5FXP_EBADARG;
-    if (m->fast) return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), 1, 0, IO_F32);
-    // generic: the three steps, on int32 copies staged behind the int forward's workspace
-    const size_t ws_int = s5fxp_workspace_bytes(m, B, L);
-    const int64_t N = (int64_t)B * L;
-    int32_t *xi = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(workspace) + ws_int);
-    int32_t *yi = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(xi) + al256((size_t)N * m->d_in * 4));
-    int rc;
-    if ((rc = s5fxp_from_fp(x, xi, N * m->d_in, x_bits, x_exp, S5FXP_FLOOR, stream))) return rc;
-    if ((rc = s5fxp_model_forward(m, xi, x_bits, x_exp, B, L, yi, workspace, ws_int, status, traces, opts, stream))) return rc;
-    return s5fxp_to_float(yi, y, N * m->d_out, m->dec.out_exp, stream);
+    return forward_entry(m, IO_F32, x, x_bits, x_exp, B, L, y, workspace, workspace_bytes, status, traces, opts, stream);
 }
 
-// The same forward with an int16 model boundary: x is 16-bit data and the decoder saturates to out_bits <= 16, so both tensors
-// cross in 2 bytes per value.  A fused model reads and writes int16 inside its encoder and decoder kernels (proj_p.hpp
-// k_enc_ps / k_dec_ps) on the int forward's workspace; a generic one stages int32 copies behind the int forward's workspace and
-// runs k_widen_i16 -> the int forward -> k_narrow_i16.
 extern "C" size_t s5fxp_workspace_bytes_i16(const s5fxp_model *m, int B, int L)
 {
     return s5fxp_workspace_bytes_f32(m, B, L); // the same staging: 4 bytes per element of both tensors on the generic path
@@ -1113,40 +1112,7 @@ extern "C" int s5fxp_model_forward_i16(const s5fxp_model *m, const int16_t *x, i
                                        void *workspace, size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces,
                                        const s5fxp_forward_opts *opts, void *stream)
 {
-    if (!m || !x || !y || !workspace || !status || B < 1 || L < 1 || x_bits < 1 || x_bits > 16) return S5FXP_EBADARG;
-    if (m->dec.out_bits > 16) return S5FXP_EUNSUPPORTED; // the narrowing of y would lose bits
-    const int G = opts && opts->groups > 1 ? opts->groups : 1;
-    const size_t ws_one = s5fxp_workspace_bytes_i16(m, B, L);
-    if (workspace_bytes < (size_t)G * ws_one) return S5FXP_EWORKSPACE;
-    if (G > 1) {
-        // the same split as s5fxp_model_forward: one set of fused launches, or one (fused or generic) forward per group
-        if (m->fast && !traces && !opts->allreduce && fast_bn_ext(m) && stream_extent_ok(m, L))
-            return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), G, ws_one, IO_I16);
-        const size_t plane = (size_t)m->n_layers * 2 * B * (m->P ? m->P : 1);
-        for (int g = 0; g < G; ++g) {
-            s5fxp_forward_opts o = *opts;
-            o.groups = 1;
-            if (o.state_in) o.state_in += g * plane;
-            if (o.state_out) o.state_out += g * plane;
-            const int rc = s5fxp_model_forward_i16(m, x + (size_t)g * B * L * m->d_in, x_bits, x_exp, B, L, y + (size_t)g * B * L * m->d_out,
-                                                   reinterpret_cast<char *>(workspace) + g * ws_one, ws_one,
-                                                   status + (size_t)g * S5FXP_STATUS_WORDS, traces ? traces + (size_t)g * m->n_layers : nullptr,
-                                                   &o, stream);
-            if (rc) return rc;
-        }
-        return S5FXP_OK;
-    }
-    if (!stream_extent_ok(m, L)) return S5FXP_EBADARG;
-    if (m->fast) return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), 1, 0, IO_I16);
-    // generic: widen, the int forward, narrow, on int32 copies staged behind the int forward's workspace
-    const size_t ws_int = s5fxp_workspace_bytes(m, B, L);
-    const int64_t N = (int64_t)B * L;
-    int32_t *xi = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(workspace) + ws_int);
-    int32_t *yi = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(xi) + al256((size_t)N * m->d_in * 4));
-    hipLaunchKernelGGL(k_widen_i16, dim3(ew_grid(N * m->d_in)), dim3(256), 0, S(stream), x, xi, N * m->d_in);
-    if (int rc = s5fxp_model_forward(m, xi, x_bits, x_exp, B, L, yi, workspace, ws_int, status, traces, opts, stream)) return rc;
-    hipLaunchKernelGGL(k_narrow_i16, dim3(ew_grid(N * m->d_out)), dim3(256), 0, S(stream), (const int32_t *)yi, y, N * m->d_out);
-    return launch_rc();
+    return forward_entry(m, IO_I16, x, x_bits, x_exp, B, L, y, workspace, workspace_bytes, status, traces, opts, stream);
 }
 
 // FxpSequenceLayer.forward for ONE layer of a created model (fxpmodel.py:1110-1161): BatchNorm -> SSM -> ReLU -> out2 ->
@@ -1172,13 +1138,13 @@ extern "C" int s5fxp_layer_forward(const s5fxp_model *m, int layer, const int32_
     s5fxp_forward_opts o{};
     if (opts) o = *opts;
     const size_t plane2 = (size_t)2 * B * (m->P ? m->P : 1);
-    if (o.state_in) o.state_in -= (size_t)layer * plane2;   // generic_layers indexes the carry by layer
+    if (o.state_in) o.state_in -= (size_t)layer * plane2;   // GenericRun::layers indexes the carry by layer
     if (o.state_out) o.state_out -= (size_t)layer * plane2;
     int32_t *h = const_cast<int32_t *>(x), *hn = y; // h is only read
     int hb = x_bits;
     DynExp he{x_exp, nullptr};
-    GenericRun g{m, B, L, w, ws, dyn, status, trace, layer, &o, st, stream};
-    if ((rc = generic_layers(g, layer, layer + 1, h, hn, hb, he))) return rc;
+    const GenericRun g{m, B, L, w, ws, dyn, status, trace, layer, &o, st, stream};
+    if ((rc = g.layers(layer, layer + 1, h, hn, hb, he))) return rc;
     if (y_exp_dev && (rc = hip_rc(hipMemcpyAsync(y_exp_dev, he.dyn, sizeof(int32_t), hipMemcpyDeviceToDevice, st)))) return rc;
     return launch_rc();
 }

@@ -272,46 +272,74 @@ class Engine:
         names = ("norm_input_minus_mean", "norm_output_raw", "norm_output_scaled", "norm_output_scaled_bias", "residadd")
         return [{n: int(st[8 + 8 * i + j]) for j, n in enumerate(names)} for i in range(self.n_layers)]
 
+    # -- the three model boundaries: one runner per family, the public methods prepare x and wrap y -----------------------
+    def _boundary_input(self, x, dtype: torch.dtype, x_bits: Optional[int], x_exp: Optional[int]):
+        """x as a contiguous `dtype` tensor on the engine's device; x_bits / x_exp default to the encoder's input configuration."""
+        data = torch.as_tensor(x)
+        if data.dtype != dtype:
+            name = str(dtype).split(".")[-1]
+            raise ValueError(f"expected a{'n' if name[0] == 'i' else ''} {name} tensor, got {data.dtype}")
+        return (data.to(self.device).contiguous(), self.inp_bits if x_bits is None else int(x_bits),
+                self.inp_exp if x_exp is None else int(x_exp))
+
+    def _rows(self, data: torch.Tensor):
+        """(B, L) of x (B,L,d_in) or (L,d_in)."""
+        if data.shape[-1] != self.d_in:
+            raise ValueError(f"expected last dim {self.d_in}, got {tuple(data.shape)}")
+        return (1, data.shape[0]) if data.ndim == 2 else (data.shape[0], data.shape[1])
+
+    def _trace_planes(self, data: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """The trace tensors of one layer for the rows of `data`."""
+        return {k: torch.empty(tuple(data.shape[:-1]) + (self.P if k in ("Bu_re", "Bu_im", "xs_re", "xs_im") else self.H,),
+                               dtype=torch.int32, device=data.device) for k in TRACE_FIELDS}
+
+    def _forward(self, data: torch.Tensor, xb: int, xe: int, out_dtype: torch.dtype, traces: bool, allreduce: Optional[Callable],
+                 check_status: bool):
+        """Returns (y, the traces or None); an empty input gives an empty y without touching the device."""
+        B, L = self._rows(data)
+        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=out_dtype, device=data.device)
+        if B * L == 0:
+            return y, ([] if traces else None)
+        tr = [self._trace_planes(data) for _ in range(self.n_layers)] if traces else None
+        if not check_status or allreduce:
+            # self-contained: the gated exact re-run is part of the one enqueue (never the ladder with a multi-rank hook: ranks
+            # must enqueue the same work)
+            self.enqueue(data, xb, xe, y, B, L, tr, allreduce)
+            if check_status:
+                self.check_status()
+        else:
+            # the status words are read anyway: run optimistically and repeat with the exact kernels if a state left the fast
+            # recurrence's range
+            self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, B, L, tr, flags=fl), self.check_status)
+        return y, tr
+
+    def _forward_batches(self, data: torch.Tensor, xb: int, xe: int, out_dtype: torch.dtype, batch: int) -> torch.Tensor:
+        if data.ndim != 3 or data.shape[-1] != self.d_in or data.shape[0] % batch:
+            raise ValueError(f"expected (G * {batch}, L, {self.d_in}), got {tuple(data.shape)}")
+        G, L = data.shape[0] // batch, data.shape[1]
+        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=out_dtype, device=data.device)
+        if G * batch * L:
+            self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, batch, L, flags=fl, groups=G), self.check_status)
+        return y
+
+    def _forward_chunk(self, data: torch.Tensor, xb: int, xe: int, out_dtype: torch.dtype, state: Optional[torch.Tensor]):
+        B, L = self._rows(data)
+        if B * L == 0:
+            raise ValueError("empty chunk")
+        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=out_dtype, device=data.device)
+        new_state = torch.empty((self.n_layers, 2, B, self.P), dtype=torch.int32, device=data.device)
+        # `state` is never written: a chunk that comes back with ST_REDO is repeated from it on the next rung
+        self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, B, L, flags=fl, state_in=state, state_out=new_state),
+                        self.check_status)
+        return y, new_state
+
+    def _fxp(self, y: torch.Tensor) -> FxpArray:
+        return FxpArray(y, self.out_bits, self.out_exp, True)
+
     def forward(self, x: FxpArray, traces: bool = False, allreduce: Optional[Callable] = None, check_status: bool = True):
         """x: FxpArray (B,L,d_in) or (L,d_in).  Returns an FxpArray (and the traces when asked)."""
-        data = x.data.contiguous()
-        if data.shape[-1] != self.d_in:
-            raise ValueError(f"expected last dim {self.d_in}, got {tuple(data.shape)}")
-        B, L = (1, data.shape[0]) if data.ndim == 2 else (data.shape[0], data.shape[1])
-        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=torch.int32, device=data.device)
-        if B * L == 0:
-            return (FxpArray(y, self.out_bits, self.out_exp, True), []) if traces else FxpArray(y, self.out_bits, self.out_exp, True)
-        tr = None
-        if traces:
-            tr = []
-            for _ in range(self.n_layers):
-                d = {}
-                for k in TRACE_FIELDS:
-                    w = self.P if k in ("Bu_re", "Bu_im", "xs_re", "xs_im") else self.H
-                    d[k] = torch.empty(tuple(data.shape[:-1]) + (w,), dtype=torch.int32, device=data.device)
-                tr.append(d)
-        if not check_status:
-            self.enqueue(data, x.bits, x.exp, y, B, L, tr, allreduce)  # self-contained: exact re-run enqueued, gated
-        else:
-            # the status words are read anyway: run optimistically and repeat with the exact kernels if a state
-            # left the fast recurrence's range (never with a multi-rank hook: ranks must enqueue the same work)
-            if allreduce:  # self-contained: the gated exact kernels are part of the one enqueue
-                self.enqueue(data, x.bits, x.exp, y, B, L, tr, allreduce, flags=0)
-                self.check_status()
-            else:
-                self.run_ladder(lambda fl: self.enqueue(data, x.bits, x.exp, y, B, L, tr, None, flags=fl), self.check_status)
-        out = FxpArray(y, self.out_bits, self.out_exp, True)
-        return (out, tr) if traces else out
-
-
-    def _float_input(self, x: torch.Tensor, x_bits: Optional[int], x_exp: Optional[int]):
-        data = torch.as_tensor(x)
-        if data.dtype != torch.float32:
-            raise ValueError(f"expected a float32 tensor, got {data.dtype}")
-        data = data.to(self.device).contiguous()
-        if data.shape[-1] != self.d_in:
-            raise ValueError(f"expected last dim {self.d_in}, got {tuple(data.shape)}")
-        return (data, self.inp_bits if x_bits is None else int(x_bits), self.inp_exp if x_exp is None else int(x_exp))
+        y, tr = self._forward(x.data.contiguous(), x.bits, x.exp, torch.int32, traces, allreduce, check_status)
+        return (self._fxp(y), tr) if traces else self._fxp(y)
 
     def forward_float(self, x: torch.Tensor, x_bits: Optional[int] = None, x_exp: Optional[int] = None,
                       check_status: bool = True, allreduce: Optional[Callable] = None) -> torch.Tensor:
@@ -319,96 +347,35 @@ class Engine:
         float32 (.., d_out), bit for bit ``forward(fxp_from_fp(x, x_bits, x_exp, FLOOR)).to_float()``.  x_bits / x_exp default
         to the encoder's input configuration.  The conversions run inside the encoder and decoder kernels on the fused path.
         check_status / allreduce as in ``forward``."""
-        data, xb, xe = self._float_input(x, x_bits, x_exp)
-        B, L = (1, data.shape[0]) if data.ndim == 2 else (data.shape[0], data.shape[1])
-        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=torch.float32, device=data.device)
-        if B * L == 0:
-            return y
-        if not check_status or allreduce:
-            self.enqueue(data, xb, xe, y, B, L, allreduce=allreduce)  # self-contained: exact re-run enqueued, gated
-            if check_status:
-                self.check_status()
-        else:
-            self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, B, L, flags=fl), self.check_status)
-        return y
+        return self._forward(*self._boundary_input(x, torch.float32, x_bits, x_exp), torch.float32, False, allreduce, check_status)[0]
 
     def forward_batches_float(self, x: torch.Tensor, batch: int, x_bits: Optional[int] = None,
                               x_exp: Optional[int] = None) -> torch.Tensor:
         """``forward_batches`` float32 in and out: x (G * batch, L, d_in) -> (G * batch, L, d_out), one set of launches."""
-        data, xb, xe = self._float_input(x, x_bits, x_exp)
-        if data.ndim != 3 or data.shape[0] % batch:
-            raise ValueError(f"expected (G * {batch}, L, {self.d_in}), got {tuple(data.shape)}")
-        G, L = data.shape[0] // batch, data.shape[1]
-        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=torch.float32, device=data.device)
-        if G * batch * L:
-            self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, batch, L, flags=fl, groups=G), self.check_status)
-        return y
+        return self._forward_batches(*self._boundary_input(x, torch.float32, x_bits, x_exp), torch.float32, batch)
 
     def forward_chunk_float(self, x: torch.Tensor, state: Optional[torch.Tensor] = None, x_bits: Optional[int] = None,
                             x_exp: Optional[int] = None):
         """``forward_chunk`` float32 in and out: returns (y float32, new_state); `state` is not modified."""
-        data, xb, xe = self._float_input(x, x_bits, x_exp)
-        B, L = (1, data.shape[0]) if data.ndim == 2 else (data.shape[0], data.shape[1])
-        if B * L == 0:
-            raise ValueError("empty chunk")
-        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=torch.float32, device=data.device)
-        new_state = torch.empty((self.n_layers, 2, B, self.P), dtype=torch.int32, device=data.device)
-        self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, B, L, flags=fl, state_in=state, state_out=new_state),
-                        self.check_status)
-        return y, new_state
+        return self._forward_chunk(*self._boundary_input(x, torch.float32, x_bits, x_exp), torch.float32, state)
 
     # -- int16 in, int16 out ----------------------------------------------------------------------
-    def _int16_input(self, x, x_bits: Optional[int], x_exp: Optional[int]):
-        data = torch.as_tensor(x)
-        if data.dtype != torch.int16:
-            raise ValueError(f"expected an int16 tensor, got {data.dtype}")
-        data = data.to(self.device).contiguous()
-        if data.shape[-1] != self.d_in:
-            raise ValueError(f"expected last dim {self.d_in}, got {tuple(data.shape)}")
-        return (data, self.inp_bits if x_bits is None else int(x_bits), self.inp_exp if x_exp is None else int(x_exp))
-
     def forward_int16(self, x, x_bits: Optional[int] = None, x_exp: Optional[int] = None, check_status: bool = True,
                       allreduce: Optional[Callable] = None) -> torch.Tensor:
         """``forward`` with int16 tensors at the model boundary: x int16 (B,L,d_in) or (L,d_in) at (x_bits, x_exp) -- default: the
         encoder's input configuration -- -> int16 (.., d_out) at (out_bits, out_exp), the very integers ``forward`` returns
         for the same values as int32.  On the fused path the encoder reads and the decoder writes int16; a model whose output
         is wider than 16 bits raises NotImplementedError.  check_status / allreduce as in ``forward``."""
-        data, xb, xe = self._int16_input(x, x_bits, x_exp)
-        B, L = (1, data.shape[0]) if data.ndim == 2 else (data.shape[0], data.shape[1])
-        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=torch.int16, device=data.device)
-        if B * L == 0:
-            return y
-        if not check_status or allreduce:
-            self.enqueue(data, xb, xe, y, B, L, allreduce=allreduce)  # self-contained: exact re-run enqueued, gated
-            if check_status:
-                self.check_status()
-        else:
-            self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, B, L, flags=fl), self.check_status)
-        return y
+        return self._forward(*self._boundary_input(x, torch.int16, x_bits, x_exp), torch.int16, False, allreduce, check_status)[0]
 
     def forward_batches_int16(self, x, batch: int, x_bits: Optional[int] = None, x_exp: Optional[int] = None) -> torch.Tensor:
         """``forward_batches`` int16 in and out: x (G * batch, L, d_in) -> (G * batch, L, d_out), one set of launches."""
-        data, xb, xe = self._int16_input(x, x_bits, x_exp)
-        if data.ndim != 3 or data.shape[0] % batch:
-            raise ValueError(f"expected (G * {batch}, L, {self.d_in}), got {tuple(data.shape)}")
-        G, L = data.shape[0] // batch, data.shape[1]
-        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=torch.int16, device=data.device)
-        if G * batch * L:
-            self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, batch, L, flags=fl, groups=G), self.check_status)
-        return y
+        return self._forward_batches(*self._boundary_input(x, torch.int16, x_bits, x_exp), torch.int16, batch)
 
     def forward_chunk_int16(self, x, state: Optional[torch.Tensor] = None, x_bits: Optional[int] = None,
                             x_exp: Optional[int] = None):
         """``forward_chunk`` int16 in and out: returns (y int16, new_state); `state` is not modified."""
-        data, xb, xe = self._int16_input(x, x_bits, x_exp)
-        B, L = (1, data.shape[0]) if data.ndim == 2 else (data.shape[0], data.shape[1])
-        if B * L == 0:
-            raise ValueError("empty chunk")
-        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=torch.int16, device=data.device)
-        new_state = torch.empty((self.n_layers, 2, B, self.P), dtype=torch.int32, device=data.device)
-        self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, B, L, flags=fl, state_in=state, state_out=new_state),
-                        self.check_status)
-        return y, new_state
+        return self._forward_chunk(*self._boundary_input(x, torch.int16, x_bits, x_exp), torch.int16, state)
 
     def layer_forward(self, layer: int, x: FxpArray, traces: bool = False):
         """One ``FxpSequenceLayer.forward`` (sparseRNNs/fxpmodel.py:1110-1161) through ``s5fxp_layer_forward``: x is the
@@ -423,11 +390,8 @@ class Engine:
         self._groups[0] = 1
         tr, d = None, None
         if traces:
-            tr = (LayerTrace * 1)()
-            d = {}
+            tr, d = (LayerTrace * 1)(), self._trace_planes(data)
             for k in TRACE_FIELDS:
-                wd = self.P if k in ("Bu_re", "Bu_im", "xs_re", "xs_im") else self.H
-                d[k] = torch.empty(tuple(data.shape[:-1]) + (wd,), dtype=torch.int32, device=data.device)
                 setattr(tr[0], k, d[k].data_ptr())
         e = torch.zeros(1, dtype=torch.int32, device=data.device)
         check(lib.s5fxp_layer_forward(self._h, layer, data.data_ptr(), x.bits, x.exp, B, L, y.data_ptr(), e.data_ptr(), ws.data_ptr(),
@@ -442,14 +406,7 @@ class Engine:
         """x: (G * batch, L, d_in) -- G independent reference batches of `batch` sequences each (the reference's
         run_validation loop over a loader, sparseRNNs/fxprun.py:53-88, several batches per call).  Returns what G calls of
         ``forward`` would, as one (G * batch, L, d_out) FxpArray, from ONE set of kernel launches."""
-        data = x.data.contiguous()
-        if data.ndim != 3 or data.shape[-1] != self.d_in or data.shape[0] % batch:
-            raise ValueError(f"expected (G * {batch}, L, {self.d_in}), got {tuple(data.shape)}")
-        G, L = data.shape[0] // batch, data.shape[1]
-        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=torch.int32, device=data.device)
-        if G * batch * L:
-            self.run_ladder(lambda fl: self.enqueue(data, x.bits, x.exp, y, batch, L, flags=fl, groups=G), self.check_status)
-        return FxpArray(y, self.out_bits, self.out_exp, True)
+        return self._fxp(self._forward_batches(x.data.contiguous(), x.bits, x.exp, torch.int32, batch))
 
     # -- streaming ------------------------------------------------------------------------------
     def zero_state(self, B: int) -> torch.Tensor:
@@ -461,18 +418,8 @@ class Engine:
         Returns (y, new_state).  What comes out is what the reference computes for THIS chunk when its recurrences
         (sparseRNNs/fxpmodel.py:147-172, the carry is an explicit argument of the step function) start from `state`;
         every chunk is its own compute_best batch.  `state` is not modified."""
-        data = x.data.contiguous()
-        if data.shape[-1] != self.d_in:
-            raise ValueError(f"expected last dim {self.d_in}, got {tuple(data.shape)}")
-        B, L = (1, data.shape[0]) if data.ndim == 2 else (data.shape[0], data.shape[1])
-        if B * L == 0:
-            raise ValueError("empty chunk")
-        y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=torch.int32, device=data.device)
-        new_state = torch.empty((self.n_layers, 2, B, self.P), dtype=torch.int32, device=data.device)
-        # `state` is never written: a chunk that comes back with ST_REDO is repeated from it on the next rung
-        self.run_ladder(lambda fl: self.enqueue(data, x.bits, x.exp, y, B, L, flags=fl, state_in=state, state_out=new_state),
-                        self.check_status)
-        return FxpArray(y, self.out_bits, self.out_exp, True), new_state
+        y, new_state = self._forward_chunk(x.data.contiguous(), x.bits, x.exp, torch.int32, state)
+        return self._fxp(y), new_state
 
     def stream(self, B: int = 1) -> "StreamingSession":
         return StreamingSession(self, B)

@@ -593,6 +593,18 @@ class FxpRegressionModel(FxpModule):  # :1380-1458
             self._engine = Engine(self.export(), flags=self.engine_flags)
         return self._engine
 
+    def _with_generic_fallback(self, run):
+        """run(engine) on the fused engine; an input that holds values beyond its nominal bits (legal in the reference,
+        OverflowError from the fused kernels) goes to the 32-bit kernels instead."""
+        try:
+            return run(self.engine())
+        except OverflowError:
+            from ._lib import MODEL_FORCE_GENERIC
+            from .engine import Engine
+            if self._generic_engine is None:
+                self._generic_engine = Engine(self.export(), flags=self.engine_flags | MODEL_FORCE_GENERIC)
+            return run(self._generic_engine)
+
     def forward(self, x, integration_timesteps: int = 10):
         if self.padded:
             x, _ = x
@@ -602,27 +614,12 @@ class FxpRegressionModel(FxpModule):  # :1380-1458
             y = self.decoder(h)
             self.sow("intermediates", "output", y)
             return y
-        try:
-            return self.engine().forward(x, allreduce=self.exponent_allreduce)
-        except OverflowError:
-            # the input holds values beyond its nominal bits (legal in the reference): 32-bit kernels
-            from ._lib import MODEL_FORCE_GENERIC
-            from .engine import Engine
-            if self._generic_engine is None:
-                self._generic_engine = Engine(self.export(), flags=self.engine_flags | MODEL_FORCE_GENERIC)
-            return self._generic_engine.forward(x, allreduce=self.exponent_allreduce)
+        return self._with_generic_fallback(lambda eng: eng.forward(x, allreduce=self.exponent_allreduce))
 
     def forward_float(self, x):
         """float32 (B,L,d_in) -> float32 (B,L,d_out): ``forward(fxp_from_fp(x, inp_bits, inp_exp, FLOOR)).to_float()`` in one
         engine call (fxprun.py:63-88), with the same fallback to the 32-bit kernels as ``forward``."""
-        try:
-            return self.engine().forward_float(x, allreduce=self.exponent_allreduce)
-        except OverflowError:
-            from ._lib import MODEL_FORCE_GENERIC
-            from .engine import Engine
-            if self._generic_engine is None:
-                self._generic_engine = Engine(self.export(), flags=self.engine_flags | MODEL_FORCE_GENERIC)
-            return self._generic_engine.forward_float(x, allreduce=self.exponent_allreduce)
+        return self._with_generic_fallback(lambda eng: eng.forward_float(x, allreduce=self.exponent_allreduce))
 
     def forward_int16(self, x, x_bits=None, x_exp=None):
         """int16 (B,L,d_in) at (x_bits, x_exp) -- default: the encoder's input configuration -- -> int16 (B,L,d_out) at the
