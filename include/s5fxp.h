@@ -282,9 +282,11 @@ size_t s5fxp_model_blob_bytes(const s5fxp_model_desc *desc);
  * S5FXP_MODEL_NO_RESID_FOLD: the fused path's gate kernel stores z and the residual add reads z and the layer input again,
  * instead of the one uint16 plane of their aligned sum (same results; for measurements and tests).
  * S5FXP_MODEL_NO_RESID_LAZY: the residual pass between two layers stores the shifted sum as a plane of its own again, instead of
- * leaving the uint16 plane to the next layer's kernels, which shift it as they load it (same results; for measurements and tests). */
+ * leaving the uint16 plane to the next layer's kernels, which shift it as they load it (same results; for measurements and tests).
+ * S5FXP_MODEL_NO_GATE_EXT: that residual pass reads the uint16 plane for its per-channel extremes again, instead of taking them
+ * from the gate kernel, which gathers them as it stores the plane (same results; for measurements and tests). */
 enum { S5FXP_MODEL_DEFAULT = 0, S5FXP_MODEL_FORCE_DENSE = 1, S5FXP_MODEL_FORCE_CSR = 2, S5FXP_MODEL_FORCE_GENERIC = 4,
-       S5FXP_MODEL_NO_RESID_FOLD = 8, S5FXP_MODEL_NO_RESID_LAZY = 16 };
+       S5FXP_MODEL_NO_RESID_FOLD = 8, S5FXP_MODEL_NO_RESID_LAZY = 16, S5FXP_MODEL_NO_GATE_EXT = 32 };
 int s5fxp_model_create(const s5fxp_model_desc *desc, void *dev_blob, size_t blob_bytes, int flags, void *stream,
                        s5fxp_model **out);
 void s5fxp_model_destroy(s5fxp_model *m);

@@ -30,6 +30,7 @@ STEP_MAX_ROWS = 32
 STREAM_MAX_HOPS = 32
 PUSH_FRESH, PUSH_ZEROS, PUSH_FINAL = 1, 2, 4   # s5fxp_push_desc.flags
 MODEL_DEFAULT, MODEL_FORCE_DENSE, MODEL_FORCE_CSR, MODEL_FORCE_GENERIC, MODEL_NO_RESID_FOLD, MODEL_NO_RESID_LAZY = 0, 1, 2, 4, 8, 16
+MODEL_NO_GATE_EXT = 32
 
 
 class DenseDesc(C.Structure):

@@ -681,6 +681,12 @@ struct ResidLazyArgs {
     float *ext;
     int32_t ext_reps;
     int32_t *status;
+    // gate_ext: the gate kernel has left the extremes of U in `ext`, all ext_reps replicas, in U units
+    // (mfma_fused.hpp CGateFoldArgs::ext_next).  One workgroup per group: the head as always, then every word of the block goes
+    // decode -> resolve_u16 -> encode, in place.  The map is monotone, so resolving each replica and letting the B projection's
+    // prologue fold them (a float maximum) equals folding first and resolving the fold, which is what the reading pass does.
+    // A word no workgroup wrote stays zero, below every encoded value.  `u` is not dereferenced.
+    int32_t head_only;
 };
 template <bool RESID, bool USUM>
 __global__ __launch_bounds__(RESID_THREADS, 5) void k_resid_minmax16(ResidLazyArgs a, GroupOff go)
@@ -697,7 +703,7 @@ __global__ __launch_bounds__(RESID_THREADS, 5) void k_resid_minmax16(ResidLazyAr
     const int H = a.H, G = H >> 3, R = RESID_THREADS / G;
     const int g = threadIdx.x % G, rl = threadIdx.x / G;
     const int64_t lo_n = (int64_t)blockIdx.x * a.span;
-    const int cnt = rl < R ? (int)((lo_n + a.span < a.N ? lo_n + a.span : a.N) - lo_n) : 0;
+    const int cnt = rl < R && !a.head_only ? (int)((lo_n + a.span < a.N ? lo_n + a.span : a.N) - lo_n) : 0;
     const char *ub = reinterpret_cast<const char *>(u + lo_n * H);
     const unsigned rowb = 2u * (unsigned)H, toff = (unsigned)rl * rowb + 16u * (unsigned)g, kstep = (unsigned)R * rowb;
     auto fetch = [&](v4i(&q)[4], int i0) {
@@ -722,6 +728,20 @@ __global__ __launch_bounds__(RESID_THREADS, 5) void k_resid_minmax16(ResidLazyAr
         p = sp;
     } else {
         p = hd.d->res;
+    }
+    if (a.head_only) {
+        if (!ext) return;
+        const SatB so = sat_bounds(a.res_bits);
+        const int lsh = p.post > 0 ? p.post : 0, rsh = p.post < 0 ? -p.post : 0;
+        // (the grid is (1, G) by contract, s5fxp_fast.hpp residual(): one workgroup owns its group's block, every word resolved once)
+        for (int i = threadIdx.x; i < a.ext_reps * 2 * H; i += RESID_THREADS) {
+            const float e = ext[i];
+            if (e == 0.f) continue;
+            const bool is_max = i % (2 * H) >= H;
+            const int32_t v = resolve_u16(is_max ? (int32_t)(e - EXT_BIAS) : (int32_t)(EXT_BIAS - e), lsh, rsh, so);
+            ext[i] = is_max ? EXT_BIAS + (float)v : EXT_BIAS - (float)v;
+        }
+        return;
     }
     uint32_t lo[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[4] = {0u, 0u, 0u, 0u};
     for (int i0 = 0; i0 + rl < cnt; i0 += step) {

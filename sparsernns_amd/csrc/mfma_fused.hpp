@@ -106,11 +106,19 @@ __host__ __device__ __forceinline__ int sigdir_lds_bytes(int bits) { return ((2 
 // skip_dyn != nullptr (resid_lazy): `skip` is the previous layer's U plane, not its shifted copy, and this is
 // that layer's LayerDyn: every skip row vector goes through resolve_u16_pair (mfma_bn.hpp) with its res.post before it feeds
 // bn16_row8 and the skip tile, so that everything downstream sees the layer input as before.
+// ext_next != nullptr (gate_ext): the next layer's block of per-channel extremes (mfma_bn.hpp EXT_REPS replicas of
+// 2H biased floats).  The kernel gathers the extremes of the U it stores -- packed uint16 running minima / maxima of the thread's
+// eight channels, valid frames only -- folds them through the dead tiles at its end and leaves them there IN U UNITS, one
+// atomicMax per (bound, channel) and workgroup; the head-only residual pass (mfma_bn.hpp ResidLazyArgs::head_only) turns them
+// into the extremes of the layer input.  nullptr: the last layer (its U goes to the decoder) and every route that reads the plane.
 struct CGateFoldArgs : CGateArgs {
     const LayerDyn *skip_dyn;
+    float *ext_next;
 };
 __device__ __forceinline__ const LayerDyn *skip_dyn_of(const CGateArgs &) { return nullptr; }
 __device__ __forceinline__ const LayerDyn *skip_dyn_of(const CGateFoldArgs &a) { return a.skip_dyn; }
+__device__ __forceinline__ float *ext_next_of(const CGateArgs &) { return nullptr; }
+__device__ __forceinline__ float *ext_next_of(const CGateFoldArgs &a) { return a.ext_next; }
 
 // S16: the state stream holds int16, written with saturation by k_scan_quad_asm16 (a.xmax <= 32766 then: a saturated
 // state fails the range check like any other state beyond the bound)

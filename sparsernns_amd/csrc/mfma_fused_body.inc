@@ -76,6 +76,16 @@
     if constexpr (GBN) bn = bn16_setup(a.bn, *a.bn.dyn, bntab, H); // the B projection of this layer has published the exponents
     std::conditional_t<UREC, Bn16Row, int> brow{};
     if constexpr (UREC) brow = bn16_row_setup(a.bn, *a.bn.dyn, 8 * (int)(threadIdx.x % VPF)); // ... and so here
+    // FOLD: the eight operand words of a channel group go behind the tiles, [group][m0..3, iv0..3], and every staging call reads
+    // its group's back into short-lived registers: the eight registers they held for the whole kernel are the ones the running
+    // extremes below (gate_ext) live in.  VPF x 32 bytes of LDS more; the five workgroups per CU stay (s5fxp_fast.hpp gate()).
+    [[maybe_unused]] v4i *brow_lds = reinterpret_cast<v4i *>(St + FT * TROW);
+    if constexpr (FOLD) {
+        if (threadIdx.x < VPF) {
+            brow_lds[2 * threadIdx.x] = v4i{(int)brow.m[0], (int)brow.m[1], (int)brow.m[2], (int)brow.m[3]};
+            brow_lds[2 * threadIdx.x + 1] = v4i{(int)brow.iv[0], (int)brow.iv[1], (int)brow.iv[2], (int)brow.iv[3]};
+        }
+    }
     const int dsh = a.out_exp - a.sig_x, dbias = 1 << (a.sigdir_bits - 1);
     const int skip_e = a.skip_e.get();
     const float kz = ldexpf(1.f, skip_e - a.res_exp); // fz + fs = 2^-skip_e * (z * kz + s), exactly
@@ -183,6 +193,19 @@
             z1[q] = (int)sum_u16_pair(usum, (uint32_t)z1[q], (uint32_t)s1[q]);
         }
     };
+    // FOLD (gate_ext, mfma_fused.hpp CGateFoldArgs::ext_next): running extremes of the U this thread stores, as packed uint16
+    // pairs of its eight channels.  Only what is stored counts: a frame beyond nvalid_prev holds values of padded steps.
+    // (Every fold kernel keeps them, also the one whose ext_next is null -- the last layer, the engines that read the plane: a
+    // uniform branch around the eight packed instructions per vector would pin the pointer or a flag in the scalar registers the
+    // kernel is short of, DESIGN.md 4i; the per-launch time of the three layers' launches is the same with and without.)
+    uint32_t elo[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu}, ehi[4] = {0u, 0u, 0u, 0u};
+    auto ext_u = [&](const v2i &z0, const v2i &z1) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            elo[q] = pk_min_u(elo[q], (uint32_t)z0[q]); ehi[q] = pk_max_u(ehi[q], (uint32_t)z0[q]);
+            elo[2 + q] = pk_min_u(elo[2 + q], (uint32_t)z1[q]); ehi[2 + q] = pk_max_u(ehi[2 + q], (uint32_t)z1[q]);
+        }
+    };
     // COAL: a thread moves the SAME vectors of the z tile out and of the u tile in, so the tile changes owner without a barrier
     auto tiles_in_out = [&](bool incoming) {
 #pragma unroll
@@ -193,7 +216,10 @@
             if (zb_prev) {
                 v2i z0 = *reinterpret_cast<const v2i *>(cu), z1 = *reinterpret_cast<const v2i *>(cu + 8);
                 if constexpr (FOLD) fold_z(z0, z1, cs_);
-                if (f < nvalid_prev) *reinterpret_cast<v4i *>(zb_prev + 2u * (unsigned)(f * H + 8 * og)) = v4i{z0[0], z0[1], z1[0], z1[1]};
+                if (f < nvalid_prev) {
+                    *reinterpret_cast<v4i *>(zb_prev + 2u * (unsigned)(f * H + 8 * og)) = v4i{z0[0], z0[1], z1[0], z1[1]};
+                    if constexpr (FOLD) ext_u(z0, z1);
+                }
             }
             if (incoming) {
                 const v4i &uv = urow[UREC ? 0 : i]; // (UREC calls this for the last tile's z only)
@@ -208,6 +234,12 @@
     // once per call.  Frames clamped past nvalid recompute a valid row, as the loads re-read one.
     auto tiles_in_urec = [&](auto arm_c) {
         constexpr int ARM = decltype(arm_c)::value;
+        auto br = brow;
+        if constexpr (FOLD) {
+            const v4i bm = brow_lds[2 * (threadIdx.x % VPF)], bi = brow_lds[2 * (threadIdx.x % VPF) + 1];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { br.m[k] = (uint32_t)bm[k]; br.iv[k] = (uint32_t)bi[k]; }
+        }
 #pragma unroll
         for (int i = 0; i < NVC; ++i) {
             const int v = threadIdx.x + NTHR * i, f = v / VPF, og = v % VPF;
@@ -216,10 +248,13 @@
             if (zb_prev) {
                 v2i z0 = *reinterpret_cast<const v2i *>(cu), z1 = *reinterpret_cast<const v2i *>(cu + 8);
                 if constexpr (FOLD) fold_z(z0, z1, cs_);
-                if (f < nvalid_prev) *reinterpret_cast<v4i *>(zb_prev + 2u * (unsigned)(f * H + 8 * og)) = v4i{z0[0], z0[1], z1[0], z1[1]};
+                if (f < nvalid_prev) {
+                    *reinterpret_cast<v4i *>(zb_prev + 2u * (unsigned)(f * H + 8 * og)) = v4i{z0[0], z0[1], z1[0], z1[1]};
+                    if constexpr (FOLD) ext_u(z0, z1);
+                }
             }
             if constexpr (FOLD) resolve_skip(srow[i]);
-            const v4i uv = bn16_row8<ARM>(brow, srow[i]);
+            const v4i uv = bn16_row8<ARM>(br, srow[i]);
             *reinterpret_cast<v2i *>(cu) = v2i{uv[0], uv[1]};
             *reinterpret_cast<v2i *>(cu + 8) = v2i{uv[2], uv[3]};
             *reinterpret_cast<v2i *>(cs_) = v2i{srow[i][0], srow[i][1]};
@@ -517,6 +552,22 @@
         }
     }
     if constexpr (COAL) tiles_in_out(false); // the last tile's z
+    // FOLD, gate_ext: the tiles are dead.  Behind a barrier (other threads' vectors lie where this one writes) every thread parks
+    // its eight packed words in the tile space: [bound][thread][pair]
+    [[maybe_unused]] float *ext_next = nullptr;
+    [[maybe_unused]] uint32_t *ext_lds = reinterpret_cast<uint32_t *>(Ut);
+    if constexpr (FOLD) {
+        static_assert(2 * NTHR * 16 <= 2 * FT * TROW, "the parked extremes fit the two tiles");
+        ext_next = ext_next_of(a_k);
+        if (ext_next) { // (a kernel argument: uniform)
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < 2; ++q) { // (8-byte accesses, like every access to the tiles)
+                *reinterpret_cast<v2i *>(ext_lds + 4 * threadIdx.x + 2 * q) = v2i{(int)elo[2 * q], (int)elo[2 * q + 1]};
+                *reinterpret_cast<v2i *>(ext_lds + 4 * (NTHR + threadIdx.x) + 2 * q) = v2i{(int)ehi[2 * q], (int)ehi[2 * q + 1]};
+            }
+        }
+    }
     // ---- range flag and the three maxima (scaled back: power-of-two factors, exact)
     if (S16) {
         const int hi = pmax[0] > pmax[1] ? pmax[0] : pmax[1], lo = pmin[0] < pmin[1] ? pmin[0] : pmin[1];
@@ -541,4 +592,27 @@
         float x = red[threadIdx.x * 16];
         for (int w = 1; w < NW; ++w) x = fmaxf(x, red[threadIdx.x * 16 + w]);
         atomicMax(a.dynw->mx + a.mx_slot + threadIdx.x, __float_as_uint(x));
+    }
+    // FOLD, gate_ext: one thread per (bound, channel) folds the NTHR / VPF threads that own the channel's group (the barrier above
+    // stands between their stores and these loads) and issues one biased-float atomicMax into this workgroup's replica of the
+    // next layer's extremes: EXT_BIAS -+ U as the read-only pass encodes h, but in U units (U <= 65534 is exact in float32)
+    // A workgroup that had no tile (the launcher's grid_for() never makes one: the grid is at most the tile count) holds the
+    // identities alone and publishes nothing: its replica's words keep their zeros or what the other workgroups left there.
+    if constexpr (FOLD) {
+        if (ext_next && (int64_t)blockIdx.x < tiles) {
+            gshift_nn(ext_next, (int64_t)blockIdx.y * go.ws);
+            for (int item = threadIdx.x; item < 2 * H; item += NTHR) {
+                const bool is_max = item >= H;
+                const int c = is_max ? item - H : item;
+                const uint16_t *src = reinterpret_cast<const uint16_t *>(ext_lds + (is_max ? 4 * NTHR : 0)) + 8 * (c >> 3) + (c & 7);
+                int32_t v = is_max ? 0 : 65535;
+#pragma unroll 4
+                for (int k = 0; k < NTHR / VPF; ++k) {
+                    const int32_t t = src[8 * VPF * k];
+                    v = is_max ? max(v, t) : min(v, t);
+                }
+                atomicMax(reinterpret_cast<uint32_t *>(ext_next) + (int)(blockIdx.x % EXT_REPS) * 2 * H + item,
+                          __float_as_uint(is_max ? EXT_BIAS + (float)v : EXT_BIAS - (float)v));
+            }
+        }
     }

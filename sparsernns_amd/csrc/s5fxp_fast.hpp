@@ -367,6 +367,7 @@ struct LayerPlan {
     bool gate_urec;   // the 32-frame gate kernel rebuilds u in its tile staging (k_cgate_p<.., UREC>; off: S5FXP_GATE_BN=0)
     bool resid_fold;  // the gate kernel stores the residual add's aligned sum U, its consumer reads that one plane (FusedForward::plan_layers)
     bool resid_lazy;  // ... and between this layer and the next nobody stores the shifted sum: the U plane is the next layer's input
+    bool gate_ext;    // ... and the gate kernel gathers the extremes of U itself: the residual pass between the two is its head alone
     GateForm gate;
     const MfmaW *w_bproj, *w_cre, *w_cim; // full or compacted; w_bproj: the pair-ordered packing on the pair rungs
     const int32_t *a_re, *a_im;           // Lambda_bar of the slots
@@ -460,6 +461,7 @@ inline auto bproj_traced_kernel(const FastShape &sh)
 // (k_cgate_p has two overloads, told apart by the argument block: the pointer type names the one that is meant)
 using GateKernel = void (*)(const CGateArgs, GroupOff);
 using GateFoldKernel = void (*)(const CGateFoldArgs, GroupOff);
+constexpr size_t GATE_FOLD_LDS_5WG = 32000; // LDS bytes per workgroup up to which five 192-thread workgroups share a CU (see gate())
 // (k_resid_minmax16 likewise: the storing pass and the read-only one of a lazy layer, mfma_bn.hpp ResidLazyArgs)
 using ResidKernel = void (*)(const int16_t *, const int16_t *, int16_t *, int32_t *, int64_t, int, int64_t, int, int, ResidHead, float *, int,
                              int32_t *, GroupOff);
@@ -624,6 +626,13 @@ struct FusedForward {
         // with S5FXP_MODEL_NO_RESID_LAZY keeps the storing pass (the A/B partner).
         for (int li = 0; li + 1 < m->n_layers; ++li)
             p[li].resid_lazy = p[li].resid_fold && p[li + 1].resid_fold && !(m->flags & S5FXP_MODEL_NO_RESID_LAZY);
+        // gate_ext: the lazy pass reads the U plane only for its per-channel extremes, and the gate kernel held
+        // every U it stored in registers a moment earlier.  So the gate kernel keeps packed running extremes and leaves them in
+        // the next layer's block of extremes, in U units (mfma_fused.hpp CGateFoldArgs::ext_next); the pass shrinks to one
+        // workgroup per group that derives the result shift as before and resolves the block in place (mfma_bn.hpp
+        // ResidLazyArgs::head_only).  The block is zeroed by clear_status() at the head of the forward, ahead of every gate
+        // kernel.  A model created with S5FXP_MODEL_NO_GATE_EXT keeps the reading pass (the A/B partner).
+        for (int li = 0; li + 1 < m->n_layers; ++li) p[li].gate_ext = p[li].resid_lazy && !(m->flags & S5FXP_MODEL_NO_GATE_EXT);
         return p;
     }
     int16_t *I16(size_t off) const { return reinterpret_cast<int16_t *>(ws + off); }
@@ -853,10 +862,19 @@ struct FusedForward {
             const size_t smem32 = 5 * HP * 4 + 32 + sig_lds + 2 * 32 * (size_t)(2 * p.P + 16) + 2 * 32 * (HP + 16) + 192 +
                                   2 * 32 * (2 * HP + 8);
             if (p.resid_fold) {
+                // the fold overload parks the BatchNorm operands of its 12 channel groups behind the tiles (mfma_fused_body.inc):
+                // 31 328 + 384 = 31 712 bytes with an 11-bit sigmoid table.  Five workgroups per CU -- what grid_gate32 is sized
+                // for -- stay resident up to GATE_FOLD_LDS_5WG bytes each (measured: tools/probe_lds_budget.hip,
+                // profiles/r14_gate_ext_lds_budget.txt); beyond it the launch still gives the same results, in two rounds.
+                // 288 bytes are left: whoever adds LDS to this kernel re-runs the probe and the per-kernel trace.
+                const size_t smem_fold = smem32 + (size_t)(H / 8) * 32;
+                // (A layer with a larger sigmoid table or more state slots is beyond it with or without these 384 bytes.)
+                static_assert(GATE_FOLD_LDS_5WG * 5 <= 160 * 1024, "five workgroups per CU");
                 CGateFoldArgs fa{};
                 static_cast<CGateArgs &>(fa) = a;
                 fa.skip_dyn = h_lazy;
-                launch(gate_fold_kernel(p), grid_gate32, 192, smem32, gev0, gev1, fa);
+                fa.ext_next = p.gate_ext ? ext(li + 1) : nullptr;
+                launch(gate_fold_kernel(p), grid_gate32, 192, smem_fold, gev0, gev1, fa);
             } else launch(gate_kernel(p, sh), grid_gate32, 192, smem32, gev0, gev1, a);
         } else {
             // phase-split fused kernel (mfma_fused.hpp): six waves per workgroup, 64-frame tiles, no weights in LDS
@@ -924,7 +942,10 @@ struct FusedForward {
                 ResidLazyArgs a{};
                 a.u = zp; a.N = N; a.span = rm_span; a.H = H; a.res_bits = l.res_bits; a.hd = resid_head(li);
                 a.ext = ext(li + 1); a.ext_reps = ext_reps; a.status = status;
-                launch(static_cast<ResidLazyKernel>(k_resid_minmax16<true, true>), rm_grid, RESID_THREADS, 0, nullptr, nullptr, a);
+                // gate_ext: the extremes are in `ext` already, in U units; one workgroup per group resolves them and reads no plane
+                a.head_only = layer[li].gate_ext ? 1 : 0;
+                if (a.head_only) a.u = nullptr;
+                launch(static_cast<ResidLazyKernel>(k_resid_minmax16<true, true>), a.head_only ? 1u : rm_grid, RESID_THREADS, 0, nullptr, nullptr, a);
                 std::swap(h, zp);
                 h_lazy = dyn + li;
                 hb = l.res_bits;
