@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define S5FXP_VERSION 110
+#define S5FXP_VERSION 111
 
 enum {
     S5FXP_OK = 0,
@@ -147,6 +147,25 @@ int s5fxp_mask_istft(const float *audio, const float *mask, int B, int64_t T, fl
 int s5fxp_stft_mag_i16(const float *audio, int B, int64_t T, float sub, int x_bits, int x_exp, int16_t *x, float *spec, void *stream);
 int s5fxp_mask_istft_i16(const float *audio, const int16_t *mask, int mask_exp, int B, int64_t T, float *out, float *cleaned_mag,
                          void *stream);
+
+/* The last stage of the validation step, fxprun.py:79-88, folded into the masked inverse: si_snr = si_snr_jax(cleaned, clean)
+ * (train_helpers.py:15-53; the cleaned audio is the `target` argument, as fxprun.py:82 calls it) over the T samples of the
+ * clip, mag_mse = mean((cleaned_mag - clean_mag)^2) over (n_seg,257) with clean_mag = s5fxp_stft_mag(clean, sub = 0), and
+ * loss = lam * mag_mse + (100 - si_snr), one float32 each per sequence, in two launches.  clean: (B,T) float32, the same T as
+ * audio; mask as in s5fxp_mask_istft[_i16].  out and cleaned_mag are what s5fxp_mask_istft[_i16] writes, bit for bit, and may
+ * each be NULL: the plane is then never stored.  si_snr, mag_mse, loss: (B) float32; mag_mse and loss may be NULL.  The sums
+ * behind the scores are taken in double on the float32 values the planes would hold (clean_mag bit for bit
+ * s5fxp_stft_mag's), in a fixed order, without atomics: two calls give identical bits, with or without the planes.
+ * workspace: s5fxp_score_workspace_bytes(B, T) bytes of device memory, 8-byte aligned, overwritten by the call (0 for B < 1
+ * or T < 512).  S5FXP_EBADARG for a null audio, clean, workspace or si_snr, B < 1 or mask_exp outside 0..31;
+ * S5FXP_EUNSUPPORTED for T < 512; S5FXP_EWORKSPACE for a workspace that is too small -- all before the device is touched. */
+size_t s5fxp_score_workspace_bytes(int B, int64_t T);
+int s5fxp_mask_istft_score(const float *audio, const float *clean, const float *mask, int B, int64_t T, float lam,
+                           float *out, float *cleaned_mag, void *workspace, size_t workspace_bytes,
+                           float *si_snr, float *mag_mse, float *loss, void *stream);
+int s5fxp_mask_istft_score_i16(const float *audio, const float *clean, const int16_t *mask, int mask_exp, int B, int64_t T,
+                               float lam, float *out, float *cleaned_mag, void *workspace, size_t workspace_bytes,
+                               float *si_snr, float *mag_mse, float *loss, void *stream);
 
 /* The same framing for a live signal: whole hops of 128 samples in, cleaned hops out (a caller zero-fills its last hop, as
  * scipy's padded=True does).  S streams advance in lock step.  With h = hops_before hops received and a push of c hops

@@ -119,6 +119,9 @@ def _load():
         "s5fxp_mask_istft": (i, [p, p, i, i64, p, p, p]),
         "s5fxp_stft_mag_i16": (i, [p, i, i64, C.c_float, i, i, p, p, p]),
         "s5fxp_mask_istft_i16": (i, [p, p, i, i, i64, p, p, p]),
+        "s5fxp_score_workspace_bytes": (C.c_size_t, [i, i64]),
+        "s5fxp_mask_istft_score": (i, [p, p, p, i, i64, C.c_float, p, p, p, C.c_size_t, p, p, p, p]),
+        "s5fxp_mask_istft_score_i16": (i, [p, p, p, i, i, i64, C.c_float, p, p, p, C.c_size_t, p, p, p, p]),
         "s5fxp_stream_audio_state_bytes": (C.c_size_t, []),
         "s5fxp_stream_frames": (i64, [i64, i]),
         "s5fxp_stream_out_hops": (i64, [i64, i, i]),
@@ -162,7 +165,8 @@ EXPORTED_SYMBOLS = ("s5fxp_version s5fxp_strerror s5fxp_from_fp s5fxp_to_float s
                     "s5fxp_model_create s5fxp_model_destroy s5fxp_workspace_bytes s5fxp_model_forward s5fxp_model_forward_f32 s5fxp_workspace_bytes_f32 s5fxp_model_forward_i16 s5fxp_workspace_bytes_i16 s5fxp_layer_forward s5fxp_model_layer_out_bits s5fxp_model_live_states "
                     "s5fxp_model_out_exp s5fxp_model_out_bits s5fxp_model_is_fast s5fxp_model_recurrence_kernel s5fxp_model_recurrence_xmax "
                     "s5fxp_model_step_ok s5fxp_model_step s5fxp_model_step_f32 "
-                    "s5fxp_stft_frames s5fxp_stft_mag s5fxp_mask_istft s5fxp_stft_mag_i16 s5fxp_mask_istft_i16 s5fxp_stream_audio_state_bytes s5fxp_stream_frames "
+                    "s5fxp_stft_frames s5fxp_stft_mag s5fxp_mask_istft s5fxp_stft_mag_i16 s5fxp_mask_istft_i16 s5fxp_score_workspace_bytes s5fxp_mask_istft_score "
+                    "s5fxp_mask_istft_score_i16 s5fxp_stream_audio_state_bytes s5fxp_stream_frames "
                     "s5fxp_stream_out_hops s5fxp_stream_stft s5fxp_stream_mask_istft "
                     "s5fxp_push_desc_check s5fxp_model_step_ragged s5fxp_model_step_ragged_f32 s5fxp_stream_stft_ragged "
                     "s5fxp_stream_mask_istft_ragged").split()

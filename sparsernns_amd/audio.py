@@ -267,6 +267,82 @@ def validate_batch(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, clea
     return loss, score
 
 
+def score_fused(noisy: torch.Tensor, clean: torch.Tensor, mask, lam: float = 0.001, mask_exp=None, cleaned: bool = False,
+                cleaned_mag: bool = False):
+    """fxprun.py:76-88 behind the model in two launches (csrc/audio_score.hpp): ``mask_istft`` of ``noisy`` (B, T) with
+    ``mask`` (B, n_seg, 257), scored against ``clean`` (B, T) -> (loss, si_snr, mag_mse), one float32 per sequence, as
+    ``validate_batch`` defines them (mag_mse = mean((cleaned_mag - clean_mag)^2)).  With ``cleaned`` / ``cleaned_mag`` the
+    planes of ``mask_istft`` follow, bit for bit; without them they are never stored.  An int16 mask with its ``mask_exp``
+    takes the int16 entry (the same scores bit for bit as for its to_float()); ``mask=None`` is all zeros.  On a GPU the sums
+    are taken in double on the very float32 values the planes would hold; CPU tensors take torch code with
+    ``validate_batch``'s arithmetic."""
+    noisy = _audio2d(noisy)
+    B, T = noisy.shape
+    n_seg = stft_frames(T)
+    shape = (B, n_seg, NFFT // 2 + 1)
+    if clean.dim() != 2 or tuple(clean.shape) != (B, T) or clean.device != noisy.device:
+        raise ValueError(f"clean must be {(B, T)} on {noisy.device}, got {tuple(clean.shape)} on {clean.device}")
+    clean = clean.to(torch.float32).contiguous()
+    i16 = mask is not None and mask.dtype == torch.int16
+    if i16:
+        if mask_exp is None:
+            raise ValueError("an int16 mask needs its mask_exp")
+        _int16_range(16, mask_exp, "score_fused")
+    elif mask_exp is not None:
+        raise ValueError("mask_exp goes with an int16 mask")
+    if mask is not None:
+        if tuple(mask.shape) != shape or mask.device != noisy.device:
+            raise ValueError(f"mask must be {shape} on {noisy.device}, got {tuple(mask.shape)} on {mask.device}")
+        mask = mask.contiguous() if i16 else mask.to(torch.float32).contiguous()
+    if not noisy.is_cuda:
+        if i16:
+            mask = torch.ldexp(mask.to(torch.float32), torch.tensor(-int(mask_exp)))
+        out, cm = mask_istft(noisy, mask, cleaned_mag=True)
+        score = si_snr(out[..., :T], clean)
+        mse = torch.mean((cm - stft_mag(clean, sub=0.0)) ** 2, dim=(1, 2))
+        loss = lam * mse + (100.0 - score)
+    else:
+        from . import _lib
+        dev = noisy.device
+        out = torch.empty(B, (n_seg - 1) * HOP, dtype=torch.float32, device=dev) if cleaned else None
+        cm = torch.empty(shape, dtype=torch.float32, device=dev) if cleaned_mag else None
+        scores = torch.empty(3, B, dtype=torch.float32, device=dev)
+        ws_bytes = _lib.lib.s5fxp_score_workspace_bytes(B, T)
+        ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        entry, m = ("s5fxp_mask_istft_score_i16", (ptr(mask), int(mask_exp))) if i16 else ("s5fxp_mask_istft_score", (ptr(mask),))
+        with torch.cuda.device(dev):
+            _lib.check(getattr(_lib.lib, entry)(noisy.data_ptr(), clean.data_ptr(), *m, B, T, float(lam), ptr(out), ptr(cm),
+                                                ws.data_ptr(), ws_bytes, scores[1].data_ptr(), scores[2].data_ptr(),
+                                                scores[0].data_ptr(), torch.cuda.current_stream().cuda_stream), entry)
+        loss, score, mse = scores[0], scores[1], scores[2]
+    return (loss, score, mse) + ((out,) if cleaned else ()) + ((cm,) if cleaned_mag else ())
+
+
+def validate_fused(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, clean: torch.Tensor, lam: float = 0.001,
+                   boundary: str = "float32"):
+    """``validate_batch`` as stft_mag -> model -> score_fused: (loss, si_snr), one value per sequence, without the cleaned audio
+    or a magnitude plane ever being stored -- on a GPU three launches plus the forward.  The model's route is chosen as in
+    ``denoise_fused``, ``boundary`` included; the numbers are ``validate_batch``'s up to the rounding of its float32 sums."""
+    from .fxparray import RoundingMode, fxp_from_fp
+
+    if boundary not in ("float32", "int16"):
+        raise ValueError(f'boundary must be "float32" or "int16", got {boundary!r}')
+    if boundary == "int16":
+        if getattr(model, "store_intermediates", False):
+            raise ValueError("a model that stores intermediates runs op by op on FxpArrays: use the float32 boundary")
+        mask = model.forward_int16(stft_mag_i16(noisy, inp_bits, inp_exp), inp_bits, inp_exp)
+        out_exp = model.out_exp if hasattr(model, "out_exp") else model.engine().out_exp
+        return score_fused(noisy, clean, mask, lam, mask_exp=out_exp)[:2]
+    x = stft_mag(noisy)
+    if hasattr(model, "forward_float") and not getattr(model, "store_intermediates", False) and _takes(model, inp_bits, inp_exp):
+        mask = model.forward_float(x)
+    else:
+        fx = fxp_from_fp(x, bits=inp_bits, exp=inp_exp, signed=True, round_mode=RoundingMode.FLOOR)
+        mask = model(fx).to_float()
+    return score_fused(noisy, clean, mask, lam)[:2]
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # The loop for a live signal: csrc/audio_stream.hpp (s5fxp_stream_stft / s5fxp_stream_mask_istft) either side of
 # SessionPool.push.

@@ -8,6 +8,7 @@
 #include "scan_assoc.hpp"
 #include "audio_stft.hpp"
 #include "audio_stream.hpp"
+#include "audio_score.hpp"
 
 #include <hip/hip_ext.h>
 
@@ -337,6 +338,54 @@ extern "C" int s5fxp_mask_istft_i16(const float *audio, const int16_t *mask, int
 {
     return mask_istft_entry(audio, out, B, T, shift_ok(mask_exp), [&](dim3 grid, int64_t n_seg, int tiles) {
         hipLaunchKernelGGL(stft::k_mask_istft_i16, grid, dim3(256), 0, S(stream), audio, mask, mask_exp, T, n_seg, tiles, out, cleaned_mag);
+    });
+}
+
+// The masked inverse with the validation step's scores (audio_score.hpp): the tile sums go through `workspace`, a second small
+// launch forms si_snr, mag_mse and loss per sequence.
+extern "C" size_t s5fxp_score_workspace_bytes(int B, int64_t T)
+{
+    if (B < 1 || T < stft::NFFT) return 0;
+    const int64_t tiles = (s5fxp_stft_frames(T) - 1 + stft::OH - 1) / stft::OH;
+    return (size_t)B * (size_t)tiles * stft::NSUM * sizeof(double);
+}
+
+namespace {
+template <class Launch>
+int score_entry(const float *audio, const float *clean, int B, int64_t T, float lam, const void *workspace, size_t workspace_bytes,
+                float *si_snr, float *mag_mse, float *loss, bool extra_ok, void *stream, Launch launch)
+{
+    if (!audio || !clean || !workspace || !si_snr || B < 1 || !extra_ok) return S5FXP_EBADARG;
+    if (T < stft::NFFT) return S5FXP_EUNSUPPORTED;
+    const int64_t n_seg = s5fxp_stft_frames(T), tiles = (n_seg - 1 + stft::OH - 1) / stft::OH;
+    if (tiles * B > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
+    if (workspace_bytes < s5fxp_score_workspace_bytes(B, T)) return S5FXP_EWORKSPACE;
+    launch(dim3((unsigned)(tiles * B)), n_seg, (int)tiles);
+    hipLaunchKernelGGL(stft::k_score_finalize, dim3((unsigned)B), dim3(64), 0, S(stream), static_cast<const double *>(workspace),
+                       (int)tiles, T, n_seg, lam, si_snr, mag_mse, loss);
+    return launch_rc();
+}
+} // namespace
+
+extern "C" int s5fxp_mask_istft_score(const float *audio, const float *clean, const float *mask, int B, int64_t T, float lam,
+                                      float *out, float *cleaned_mag, void *workspace, size_t workspace_bytes, float *si_snr,
+                                      float *mag_mse, float *loss, void *stream)
+{
+    return score_entry(audio, clean, B, T, lam, workspace, workspace_bytes, si_snr, mag_mse, loss, true, stream,
+                       [&](dim3 grid, int64_t n_seg, int tiles) {
+        hipLaunchKernelGGL(stft::k_mask_istft_score, grid, dim3(256), 0, S(stream), audio, clean, mask, T, n_seg, tiles, out, cleaned_mag,
+                           static_cast<double *>(workspace));
+    });
+}
+
+extern "C" int s5fxp_mask_istft_score_i16(const float *audio, const float *clean, const int16_t *mask, int mask_exp, int B, int64_t T,
+                                          float lam, float *out, float *cleaned_mag, void *workspace, size_t workspace_bytes,
+                                          float *si_snr, float *mag_mse, float *loss, void *stream)
+{
+    return score_entry(audio, clean, B, T, lam, workspace, workspace_bytes, si_snr, mag_mse, loss, shift_ok(mask_exp), stream,
+                       [&](dim3 grid, int64_t n_seg, int tiles) {
+        hipLaunchKernelGGL(stft::k_mask_istft_score_i16, grid, dim3(256), 0, S(stream), audio, clean, mask, mask_exp, T, n_seg, tiles, out,
+                           cleaned_mag, static_cast<double *>(workspace));
     });
 }
 
