@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define S5FXP_VERSION 111
+#define S5FXP_VERSION 112
 
 enum {
     S5FXP_OK = 0,
@@ -316,8 +316,8 @@ size_t s5fxp_workspace_bytes(const s5fxp_model *m, int B, int L);
 /* Number of int32 words in the device status buffer, and its layout:
  *   [0] error bits (S5FXP_ST_*), [1] decoder output exponent,
  *   [2] which kernels this forward ran: S5FXP_PATH_GENERIC (one-lane / VALU kernels, any int32 operands),
- *       S5FXP_PATH_FUSED (the int8-MFMA tile kernels + the quad / pair recurrence kernels) or S5FXP_PATH_STEP (the
- *       one-launch kernel of s5fxp_model_step),
+ *       S5FXP_PATH_FUSED (the int8-MFMA tile kernels + the quad / pair recurrence kernels), S5FXP_PATH_STEP (the
+ *       one-launch kernel of s5fxp_model_step) or S5FXP_PATH_CLIP (the one-launch kernel of s5fxp_model_clips),
  *   [8 + 8*l + 0..4] layer l: exponents chosen by the 4 BatchNorm ops and the residual add,
  *   [8 + 8*l + 5]    layer l: the recurrence kernel that was enqueued first, coded as s5fxp_model_recurrence_kernel
  *                    (5 = the exact 32-bit quad chain of a S5FXP_FWD_EXACT forward, 6 = the 32-bit recurrence inside
@@ -327,7 +327,7 @@ size_t s5fxp_workspace_bytes(const s5fxp_model *m, int B, int L);
  *   [8 + 8*l + 7]    layer l: the state slots its two recurrence streams hold: [8 + 8*l + 6], or fewer -- the live states
  *                    rounded up to an even number -- when the LDS-fed pair kernel runs a layer compacted to 32 slots. */
 #define S5FXP_STATUS_WORDS 128
-enum { S5FXP_PATH_GENERIC = 1, S5FXP_PATH_FUSED = 2, S5FXP_PATH_STEP = 3 };
+enum { S5FXP_PATH_GENERIC = 1, S5FXP_PATH_FUSED = 2, S5FXP_PATH_STEP = 3, S5FXP_PATH_CLIP = 4 };
 enum {
     S5FXP_ST_NEGSHIFT = 1,   /* a data-dependent shift came out negative: the reference raises ValueError */
     S5FXP_ST_NEGEXP = 2,     /* a compute_best exponent came out negative (1 << exp fails in the reference) */
@@ -494,6 +494,38 @@ int s5fxp_model_step_ragged(const s5fxp_model *m, const int32_t *x, int x_bits, 
                             const s5fxp_push_desc *desc, int32_t *state, int n_slots, int32_t *status, void *stream);
 int s5fxp_model_step_ragged_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int n, int B, int Lmax, float *y,
                                 const s5fxp_push_desc *desc, int32_t *state, int n_slots, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Clips: n independent sequences of DIFFERENT lengths in ONE kernel launch (grid = n, one workgroup per clip, looping over
+ * 32-row tiles).  Clip e is one reference batch of B = 1 sequence of len_e = clamp(lens[e], 0, Lmax) frames and gets, bit for
+ * bit, what s5fxp_model_forward(m, x_e, x_bits, x_exp, 1, len_e, ...) computes for it alone with that carry -- its own
+ * compute_best exponents, status words and carry.  A clip's result does not depend on what else is in the launch.
+ *   x (n,Lmax,d_in), y (n,Lmax,d_out): int32, or float32 for _f32 (fxp_from_fp FLOOR in, to_float out; x_exp 0..31), padded
+ *   to Lmax frames per clip; frames len_e..Lmax-1 of x are never read and of y never written.  lens: n int32, device memory.
+ *   carry [n][n_layers][2][P]: state_in NULL = zeros, state_out NULL = not wanted, state_out == state_in is allowed.
+ *   workspace: s5fxp_clips_workspace_bytes(m, n, Lmax) bytes of device memory, 2-byte aligned: per clip two int16 planes of
+ *   Lmax x H (the layer input and the gate output), written and read by that clip's workgroup only.
+ *   status: n * S5FXP_STATUS_WORDS words, written completely by the kernel, laid out as s5fxp_model_step's with
+ *   [2] = S5FXP_PATH_CLIP.  S5FXP_ST_WIDE_STATE is the OR over the clip's tiles.
+ *   len_e == 0: y untouched, state_out[e] = state_in[e] (zeros for NULL), the status words hold the kernel's initial fill.
+ *   S5FXP_ST_WIDE_INPUT (a value beyond 16 bits after the encoder's input conversion, in any frame of the clip): the clip
+ *   stores its status words and stops, leaving its y rows and state_out[e] untouched, as s5fxp_model_step_ragged does; the
+ *   caller serves it on a generic model.  The other clips of the launch are not affected.
+ * One CU serves one clip, tile after tile: the entry is for MANY short clips.  A single long clip, or a few, belong on
+ * s5fxp_model_forward, which spreads one sequence over the chip (DESIGN.md §4o has the measured break-even).
+ * Checked before the device is touched: S5FXP_EBADARG for a null model / x / y / lens / status / workspace, n < 1, Lmax < 1
+ * or Lmax > 2^20, x_bits outside 1..32 (and x_exp outside 0..31 for _f32) or workspace_bytes too small;
+ * S5FXP_EUNSUPPORTED for a model that s5fxp_model_is_fast() does not report; S5FXP_ENEGSHIFT for the static shifts
+ * s5fxp_model_step checks.  No traces, no cross-rank hook, no flags, no redo, no B > 1. */
+size_t s5fxp_clips_workspace_bytes(const s5fxp_model *m, int n, int Lmax); /* 0: bad argument */
+/* 1: s5fxp_model_clips serves this model at Lmax; 0: it does not (generic model, Lmax > 2^20); -1: bad argument */
+int s5fxp_model_clips_ok(const s5fxp_model *m, int Lmax);
+int s5fxp_model_clips(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int n, int Lmax, const int32_t *lens,
+                      int32_t *y, const int32_t *state_in, int32_t *state_out, void *workspace, size_t workspace_bytes,
+                      int32_t *status, void *stream);
+int s5fxp_model_clips_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int n, int Lmax, const int32_t *lens,
+                          float *y, const int32_t *state_in, int32_t *state_out, void *workspace, size_t workspace_bytes,
+                          int32_t *status, void *stream);
 
 /* FxpSequenceLayer.forward, fxpmodel.py:1110-1161, for layer `layer` of a created model -- the unit the reference's
  * verification walks (fxprun.py:583-727).  x: (B,L,H) int32 device with configuration (x_bits, x_exp); y: (B,L,H) int32

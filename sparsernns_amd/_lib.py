@@ -25,7 +25,7 @@ S5FXP_OK, S5FXP_EBADARG, S5FXP_ENEGSHIFT, S5FXP_EUNSUPPORTED, S5FXP_EHIP, S5FXP_
 ST_NEGSHIFT, ST_NEGEXP, ST_WIDE_STATE, ST_WIDE_INPUT, ST_REDO = 1, 2, 4, 8, 16
 FWD_DEFER_REDO, FWD_EXACT, FWD_NO_PAIR = 1, 2, 4
 STATUS_WORDS = 128
-PATH_GENERIC, PATH_FUSED, PATH_STEP = 1, 2, 3   # status[2]
+PATH_GENERIC, PATH_FUSED, PATH_STEP, PATH_CLIP = 1, 2, 3, 4   # status[2]
 STEP_MAX_ROWS = 32
 STREAM_MAX_HOPS = 32
 PUSH_FRESH, PUSH_ZEROS, PUSH_FINAL = 1, 2, 4   # s5fxp_push_desc.flags
@@ -150,6 +150,10 @@ def _load():
         "s5fxp_push_desc_check": (i, [p, i, i, i, i, i]),
         "s5fxp_model_step_ragged": (i, [p, p, i, i, i, i, i, p, p, p, i, p, p]),
         "s5fxp_model_step_ragged_f32": (i, [p, p, i, i, i, i, i, p, p, p, i, p, p]),
+        "s5fxp_clips_workspace_bytes": (C.c_size_t, [p, i, i]),
+        "s5fxp_model_clips_ok": (i, [p, i]),
+        "s5fxp_model_clips": (i, [p, p, i, i, i, i, p, p, p, p, p, C.c_size_t, p, p]),
+        "s5fxp_model_clips_f32": (i, [p, p, i, i, i, i, p, p, p, p, p, C.c_size_t, p, p]),
         "s5fxp_stream_stft_ragged": (i, [p, i, i, p, C.c_float, p, i, p, p]),
         "s5fxp_stream_mask_istft_ragged": (i, [p, i, i, p, p, i, p, p, p]),
     }
@@ -169,7 +173,8 @@ EXPORTED_SYMBOLS = ("s5fxp_version s5fxp_strerror s5fxp_from_fp s5fxp_to_float s
                     "s5fxp_mask_istft_score_i16 s5fxp_stream_audio_state_bytes s5fxp_stream_frames "
                     "s5fxp_stream_out_hops s5fxp_stream_stft s5fxp_stream_mask_istft "
                     "s5fxp_push_desc_check s5fxp_model_step_ragged s5fxp_model_step_ragged_f32 s5fxp_stream_stft_ragged "
-                    "s5fxp_stream_mask_istft_ragged").split()
+                    "s5fxp_stream_mask_istft_ragged "
+                    "s5fxp_clips_workspace_bytes s5fxp_model_clips_ok s5fxp_model_clips s5fxp_model_clips_f32").split()
 
 
 def check(rc: int, what: str = "") -> None:

@@ -719,6 +719,7 @@ int bn_exponent_ops(Reduce reduce, const BnArgs &bn, LayerDyn *d, int32_t *statu
 
 #include "s5fxp_fast.hpp"
 #include "s5fxp_step.hpp"
+#include "s5fxp_clip.hpp"
 
 namespace {
 

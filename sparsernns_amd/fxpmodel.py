@@ -621,6 +621,13 @@ class FxpRegressionModel(FxpModule):  # :1380-1458
         engine call (fxprun.py:63-88), with the same fallback to the 32-bit kernels as ``forward``."""
         return self._with_generic_fallback(lambda eng: eng.forward_float(x, allreduce=self.exponent_allreduce))
 
+    def forward_clips(self, xs):
+        """A list of FxpArray (L_e, d_in) of any lengths -> the list of FxpArray (L_e, d_out) that ``forward`` gives each clip on
+        its own (own compute_best exponents), from ONE kernel launch (``Engine.forward_clips``); a clip with values beyond
+        16 bits is served by the 32-bit kernels.  One CU walks one clip: meant for many short clips, a single long one
+        belongs on ``forward``."""
+        return self.engine().forward_clips(xs)
+
     def forward_int16(self, x, x_bits=None, x_exp=None):
         """int16 (B,L,d_in) at (x_bits, x_exp) -- default: the encoder's input configuration -- -> int16 (B,L,d_out) at the
         model's output configuration: the integers of ``forward`` in 2 bytes per value at both ends.  int16 values cannot exceed
