@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define S5FXP_VERSION 112
+#define S5FXP_VERSION 113
 
 enum {
     S5FXP_OK = 0,
@@ -147,6 +147,26 @@ int s5fxp_mask_istft(const float *audio, const float *mask, int B, int64_t T, fl
 int s5fxp_stft_mag_i16(const float *audio, int B, int64_t T, float sub, int x_bits, int x_exp, int16_t *x, float *spec, void *stream);
 int s5fxp_mask_istft_i16(const float *audio, const int16_t *mask, int mask_exp, int B, int64_t T, float *out, float *cleaned_mag,
                          void *stream);
+
+/* The two steps for n clips of DIFFERENT lengths, one launch each: with s5fxp_model_clips_f32 between them the denoising loop for
+ * n utterances is three launches.  Clip e is row e of audio (n,Tmax) float32 with T_e = clamp(samples[e], 0, Tmax) samples --
+ * samples: n int32 in device memory, trusted as the lens of s5fxp_model_clips are -- and len_e = ceil(T_e / 128) + 1 frames.  All
+ * row tensors are padded to Lmax = s5fxp_stft_frames(Tmax) frames per clip, the layout s5fxp_model_clips_f32 takes: x, mask,
+ * cleaned_mag (n,Lmax,257) float32, spec (n,Lmax,257) complex64, out (n,(Lmax-1)*128) float32.
+ *   s5fxp_stft_mag_clips writes rows 0..len_e-1 of x (and of spec, unless NULL) and, unless lens is NULL, lens[e] = len_e: the
+ *   model launch takes its lengths from the device, with no host step between the launches.  Rows len_e..Lmax-1 are never
+ *   written, samples T_e..Tmax-1 of an audio row never read.
+ *   s5fxp_mask_istft_clips writes the first (len_e-1)*128 samples of out[e] and rows 0..len_e-1 of cleaned_mag (unless NULL) and
+ *   nothing behind them; mask (NULL: zeros) rows from len_e on are never read.
+ * Clip e gets, bit for bit, what s5fxp_stft_mag / s5fxp_mask_istft compute for it alone at B = 1, T = T_e, whatever else is in
+ * the launch: a frame's transform and an output hop's sum do not depend on the workgroup that computes them.  No atomics.
+ * A clip below 512 samples has no frames: lens[e] = 0, nothing else of it is written, and s5fxp_model_clips skips it.
+ * Checked before the device is touched: S5FXP_EBADARG for a null audio, samples, x or out, n < 1 or Tmax > (2^20 - 1) * 128 (Lmax
+ * stays within s5fxp_model_clips' cap); S5FXP_EUNSUPPORTED for Tmax < 512. */
+int s5fxp_stft_mag_clips(const float *audio, int n, int64_t Tmax, const int32_t *samples, float sub, float *x, float *spec,
+                         int32_t *lens, void *stream);
+int s5fxp_mask_istft_clips(const float *audio, const float *mask, int n, int64_t Tmax, const int32_t *samples, float *out,
+                           float *cleaned_mag, void *stream);
 
 /* The last stage of the validation step, fxprun.py:79-88, folded into the masked inverse: si_snr = si_snr_jax(cleaned, clean)
  * (train_helpers.py:15-53; the cleaned audio is the `target` argument, as fxprun.py:82 calls it) over the T samples of the

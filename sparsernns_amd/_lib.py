@@ -119,6 +119,8 @@ def _load():
         "s5fxp_mask_istft": (i, [p, p, i, i64, p, p, p]),
         "s5fxp_stft_mag_i16": (i, [p, i, i64, C.c_float, i, i, p, p, p]),
         "s5fxp_mask_istft_i16": (i, [p, p, i, i, i64, p, p, p]),
+        "s5fxp_stft_mag_clips": (i, [p, i, i64, p, C.c_float, p, p, p, p]),
+        "s5fxp_mask_istft_clips": (i, [p, p, i, i64, p, p, p, p]),
         "s5fxp_score_workspace_bytes": (C.c_size_t, [i, i64]),
         "s5fxp_mask_istft_score": (i, [p, p, p, i, i64, C.c_float, p, p, p, C.c_size_t, p, p, p, p]),
         "s5fxp_mask_istft_score_i16": (i, [p, p, p, i, i, i64, C.c_float, p, p, p, C.c_size_t, p, p, p, p]),
@@ -174,7 +176,8 @@ EXPORTED_SYMBOLS = ("s5fxp_version s5fxp_strerror s5fxp_from_fp s5fxp_to_float s
                     "s5fxp_stream_out_hops s5fxp_stream_stft s5fxp_stream_mask_istft "
                     "s5fxp_push_desc_check s5fxp_model_step_ragged s5fxp_model_step_ragged_f32 s5fxp_stream_stft_ragged "
                     "s5fxp_stream_mask_istft_ragged "
-                    "s5fxp_clips_workspace_bytes s5fxp_model_clips_ok s5fxp_model_clips s5fxp_model_clips_f32").split()
+                    "s5fxp_clips_workspace_bytes s5fxp_model_clips_ok s5fxp_model_clips s5fxp_model_clips_f32 "
+                    "s5fxp_stft_mag_clips s5fxp_mask_istft_clips").split()
 
 
 def check(rc: int, what: str = "") -> None:

@@ -255,6 +255,149 @@ def denoise_fused(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, bound
     return cleaned, cleaned_mag, x, mask
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The same loop for n clips of DIFFERENT lengths: s5fxp_stft_mag_clips -> s5fxp_model_clips_f32 -> s5fxp_mask_istft_clips, one
+# launch each.  Clip e is row e of audio (n, Tmax) with T_e = clamp(samples[e], 0, Tmax) samples; every row tensor is padded to
+# Lmax = stft_frames(Tmax) frames.  A clip below 512 samples has no frames (lens[e] = 0) and nothing of it is written.
+# ---------------------------------------------------------------------------------------------------------------------
+def _clips_args(audio: torch.Tensor, samples: torch.Tensor):
+    audio = _audio2d(audio)
+    n, Tmax = audio.shape
+    Lmax = stft_frames(Tmax)
+    if n < 1:
+        raise ValueError("a launch holds at least one clip")
+    if samples.dtype != torch.int32 or tuple(samples.shape) != (n,) or samples.device != audio.device:
+        raise ValueError(f"samples must be int32 ({n},) on {audio.device}, got {samples.dtype} {tuple(samples.shape)} on {samples.device}")
+    return audio, samples.contiguous(), n, Tmax, Lmax
+
+
+def _clips_out(given, want, what: str):
+    """The caller's output tensors (`out=`), checked against want = [(shape, dtype, device), ...], or fresh ones."""
+    if given is None:
+        return [torch.empty(shape, dtype=dtype, device=dev) for shape, dtype, dev in want]
+    given = list(given)
+    if len(given) != len(want):
+        raise ValueError(f"{what}: out must hold {len(want)} tensors, got {len(given)}")
+    for t, (shape, dtype, dev) in zip(given, want):
+        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{what}: out needs a contiguous {dtype} {shape} on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return given
+
+
+def _clip_lengths(samples: torch.Tensor, Tmax: int):
+    """Host copies of (T_e, len_e) as the kernels derive them."""
+    T = [min(max(int(v), 0), Tmax) for v in samples.tolist()]
+    return T, [0 if t < NFFT else -(-t // HOP) + 1 for t in T]
+
+
+def stft_mag_clips(audio: torch.Tensor, samples: torch.Tensor, sub: float = STFT_MAG_MEAN, spectrum: bool = False, out=None):
+    """``stft_mag`` for n clips of different lengths in ONE launch: audio (n, Tmax) float32, padded; samples (n,) int32 on the
+    audio's device -> (x, lens[, spec]): x (n, Lmax, 257) float32 with clip e in rows 0 .. lens[e]-1, lens (n,) int32 on the
+    device -- what ``Engine.clips`` takes, with no host step in between -- and with ``spectrum`` the complex64 spectrum.  Rows
+    x[e, :lens[e]] are bit for bit ``stft_mag(audio[e:e+1, :T_e])[0]``.  Rows from lens[e] on are never written (``out``: the
+    tensors to write into, in the order returned; otherwise they are fresh and that padding is unspecified) and samples from
+    T_e on never read.  A clip below 512 samples gets lens[e] = 0."""
+    audio, samples, n, Tmax, Lmax = _clips_args(audio, samples)
+    dev, shape = audio.device, (n, Lmax, NFFT // 2 + 1)
+    res = _clips_out(out, [(shape, torch.float32, dev), ((n,), torch.int32, dev)] + ([(shape, torch.complex64, dev)] if spectrum else []),
+                     "stft_mag_clips")
+    x, lens, spec = res[0], res[1], res[2] if spectrum else None
+    if not audio.is_cuda:
+        T, L = _clip_lengths(samples, Tmax)
+        for e in range(n):
+            lens[e] = L[e]
+            if L[e]:
+                r = stft_mag(audio[e:e + 1, :T[e]], sub, spectrum)
+                x[e, :L[e]] = r[0][0] if spectrum else r[0]
+                if spectrum:
+                    spec[e, :L[e]] = r[1][0]
+        return tuple(res)
+    from . import _lib
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib.s5fxp_stft_mag_clips(audio.data_ptr(), n, Tmax, samples.data_ptr(), float(sub), x.data_ptr(),
+                                                 spec.data_ptr() if spectrum else None, lens.data_ptr(),
+                                                 torch.cuda.current_stream().cuda_stream), "s5fxp_stft_mag_clips")
+    return tuple(res)
+
+
+def mask_istft_clips(audio: torch.Tensor, samples: torch.Tensor, mask, cleaned_mag: bool = False, out=None):
+    """``mask_istft`` for n clips of different lengths in ONE launch: audio, samples as ``stft_mag_clips``; mask (n, Lmax, 257)
+    float32 (rows from len_e on are never read) or None (zeros) -> cleaned audio (n, (Lmax - 1) * 128), clip e in its first
+    (len_e - 1) * 128 samples, bit for bit ``mask_istft(audio[e:e+1, :T_e], mask[e:e+1, :len_e])[0]``; with ``cleaned_mag`` also
+    |Z| * (1 + mask), (n, Lmax, 257).  Nothing behind a clip's end is written (``out`` as in ``stft_mag_clips``)."""
+    audio, samples, n, Tmax, Lmax = _clips_args(audio, samples)
+    dev, shape = audio.device, (n, Lmax, NFFT // 2 + 1)
+    if mask is not None:
+        if tuple(mask.shape) != shape or mask.device != dev:
+            raise ValueError(f"mask must be {shape} on {dev}, got {tuple(mask.shape)} on {mask.device}")
+        mask = mask.to(torch.float32).contiguous()
+    res = _clips_out(out, [((n, (Lmax - 1) * HOP), torch.float32, dev)] + ([(shape, torch.float32, dev)] if cleaned_mag else []),
+                     "mask_istft_clips")
+    o, cm = res[0], res[1] if cleaned_mag else None
+    if not audio.is_cuda:
+        T, L = _clip_lengths(samples, Tmax)
+        for e in range(n):
+            if L[e]:
+                r = mask_istft(audio[e:e + 1, :T[e]], mask[e:e + 1, :L[e]] if mask is not None else None, cleaned_mag)
+                o[e, :(L[e] - 1) * HOP] = r[0][0] if cleaned_mag else r[0]
+                if cleaned_mag:
+                    cm[e, :L[e]] = r[1][0]
+        return (o, cm) if cleaned_mag else o
+    from . import _lib
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib.s5fxp_mask_istft_clips(audio.data_ptr(), mask.data_ptr() if mask is not None else None, n, Tmax,
+                                                   samples.data_ptr(), o.data_ptr(), cm.data_ptr() if cleaned_mag else None,
+                                                   torch.cuda.current_stream().cuda_stream), "s5fxp_mask_istft_clips")
+    return (o, cm) if cleaned_mag else o
+
+
+def denoise_clips(model, inp_bits: int, inp_exp: int, clips, lane=0):
+    """``denoise_fused`` for a list of 1-D float audio clips of any lengths >= 512 (below: NotImplementedError, before any
+    launch; an empty list gives []).  Returns per clip (cleaned ((len_e - 1) * 128,), cleaned_mag, x, mask), the last three
+    (len_e, 257): bit for bit the tuple ``denoise_fused(model, inp_bits, inp_exp, clip[None])`` returns, without the batch axis.
+
+    On a GPU, for a model on the fused path that does not store intermediates and takes (inp_bits, inp_exp) at its encoder, that
+    is THREE launches whatever n: the audio is padded once, ``stft_mag_clips`` writes the padded rows and the frame counts,
+    ``Engine.clips`` runs on those very tensors, the status words are read once (a clip flagged ST_WIDE_INPUT gets its mask rows
+    from the generic engine), ``mask_istft_clips`` follows.  Any other model or device takes ``denoise_fused`` clip by clip.
+
+    One CU walks one clip through the model, tile after tile, so the launch is as long as its longest clip: this is for MANY
+    clips.  A single long clip, or a few, belong on ``denoise_fused``, which spreads a sequence over the chip."""
+    clips = [torch.as_tensor(c) for c in clips]
+    for c in clips:
+        if c.dim() != 1:
+            raise ValueError(f"every clip must be 1-D audio, got {tuple(c.shape)}")
+        stft_frames(int(c.shape[0]))
+    if not clips:
+        return []
+    Ts = [int(c.shape[0]) for c in clips]
+    Tmax, Lmax, dev = max(Ts), stft_frames(max(Ts)), clips[0].device
+    one_launch = (all(c.is_cuda and c.device == dev for c in clips) and hasattr(model, "engine") and hasattr(model, "forward_float")
+                  and not getattr(model, "store_intermediates", False) and _takes(model, inp_bits, inp_exp)
+                  and model.engine().clips_ok(Lmax))
+    if not one_launch:
+        return [tuple(t[0] for t in denoise_fused(model, inp_bits, inp_exp, c[None])) for c in clips]
+    from . import _lib
+    eng, n = model.engine(), len(clips)
+    audio = torch.nn.utils.rnn.pad_sequence([c.to(torch.float32) for c in clips], batch_first=True)
+    samples = torch.tensor(Ts, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        x, lens = stft_mag_clips(audio, samples)
+        mask = eng.clips(x, lens, lane=lane)
+        st = eng.lane_status(lane, n)[:n * _lib.STATUS_WORDS].cpu().numpy().reshape(n, _lib.STATUS_WORDS)
+        bad = int(np.bitwise_or.reduce(st[:, 0] & ~_lib.ST_WIDE_INPUT))
+        if bad & _lib.ST_NEGSHIFT:
+            raise ValueError("invalid result_exp: a data-dependent shift came out negative (fxparray.py:619-621)")
+        if bad & _lib.ST_NEGEXP:
+            raise ValueError("a compute_best exponent came out negative")
+        L = [stft_frames(T) for T in Ts]
+        for e in np.nonzero(st[:, 0] & _lib.ST_WIDE_INPUT)[0]:
+            mask[e, :L[e]] = eng.generic_twin()._forward(x[e, :L[e]].contiguous(), eng.inp_bits, eng.inp_exp, torch.float32, False,
+                                                         None, True)[0]
+        cleaned, cm = mask_istft_clips(audio, samples, mask, cleaned_mag=True)
+    return [(cleaned[e, :(L[e] - 1) * HOP], cm[e, :L[e]], x[e, :L[e]], mask[e, :L[e]]) for e in range(n)]
+
+
 def validate_batch(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, clean: torch.Tensor, lam: float = 0.001,
                    boundary: str = "float32"):
     """fxprun.py:79-88: (loss, si_snr), one value per sequence: si_snr = si_snr(cleaned, clean) -- the cleaned audio is the

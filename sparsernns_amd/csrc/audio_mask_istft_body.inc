@@ -1,10 +1,11 @@
-// audio_mask_istft_body.inc -- the body of k_mask_istft and k_mask_istft_i16 (audio_stft.hpp), included by both with I16 = false / true.
+// audio_mask_istft_body.inc -- the body of k_mask_istft, k_mask_istft_i16 and k_mask_istft_clips (audio_stft.hpp), included with
+// I16 = false / true.  T, n_seg, a_pitch and f_pitch as in audio_stft_mag_body.inc; a row of `out` is f_pitch - 1 hops.
     __shared__ Smem sm;
     const int64_t b = blockIdx.x / tiles, o0 = (int64_t)(blockIdx.x % tiles) * OH, k0 = o0 - 1;
     // this thread's 1 + mask values (elements threadIdx.x + 256 j of the tile's 16 x 257), asked for before the forward
     // transform so that they arrive behind it; a frame outside 0..n_seg-1 contributes nothing
     constexpr int NJ = (FR * NBIN + 255) / 256;
-    const int64_t base = (b * n_seg + k0) * NBIN;
+    const int64_t base = (b * f_pitch + k0) * NBIN;
     float f[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -14,7 +15,7 @@
         else f[j] = (mask && i < FR * NBIN && kf >= 0 && kf < n_seg) ? 1.0f + mask[base + i] : 1.0f;
     }
     make_twiddles(sm);
-    forward_tile(sm, audio + b * T, T, k0);
+    forward_tile(sm, audio + b * a_pitch, T, k0);
     // Z' = Z * (1 + mask) into plane A
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -37,7 +38,7 @@
     const int64_t n_out = n_seg - 1;
     const int noh = (int)(n_out - o0 < OH ? n_out - o0 : OH);
     const float *seg = reinterpret_cast<const float *>(sm.a);
-    float *dst = out + b * n_out * HOP + o0 * HOP;
+    float *dst = out + b * (f_pitch - 1) * HOP + o0 * HOP;
     for (int i = threadIdx.x; i < noh * HOP; i += 256) {
         const int j = i >> 7, s = i & 127;
         const int64_t o = o0 + j;

@@ -10,6 +10,7 @@
 //                  the same audio bit for bit, since both conversions restate 16-bit integers.  The bodies are shared as text
 //                  (audio_stft_mag_body.inc, audio_mask_istft_body.inc) with the boundary type as a compile-time constant, as
 //                  the encoder's and decoder's are (proj_p.hpp): the float kernels keep their instruction streams.
+//   k_stft_mag_clips / k_mask_istft_clips: the same two bodies for n clips of different lengths in one launch (at the end).
 //
 // Framing.  With p the signal between 256 zeros on each side and zero-filled up to a whole hop, frame k is p[128k .. 128k+511]
 // (hops k..k+3 of p), n_seg = ceil(T/128) + 1.  Output hop o of the inverse (samples 128o .. 128o+127, hop o+2 of p) is the
@@ -207,6 +208,7 @@ __global__ __launch_bounds__(256) void k_stft_mag(const float *__restrict__ audi
 #pragma clang fp contract(off)
     constexpr bool I16 = false;
     [[maybe_unused]] constexpr int x_bits = 0, x_exp = 0;
+    const int64_t a_pitch = T, f_pitch = n_seg;
 #include "audio_stft_mag_body.inc"
 }
 
@@ -216,6 +218,7 @@ __global__ __launch_bounds__(256) void k_stft_mag_i16(const float *__restrict__ 
 {
 #pragma clang fp contract(off)
     constexpr bool I16 = true;
+    const int64_t a_pitch = T, f_pitch = n_seg;
 #include "audio_stft_mag_body.inc"
 }
 
@@ -228,6 +231,7 @@ __global__ __launch_bounds__(256) void k_mask_istft(const float *__restrict__ au
 #pragma clang fp contract(off)
     constexpr bool I16 = false;
     [[maybe_unused]] constexpr int mask_exp = 0;
+    const int64_t a_pitch = T, f_pitch = n_seg;
 #include "audio_mask_istft_body.inc"
 }
 
@@ -238,6 +242,48 @@ __global__ __launch_bounds__(256) void k_mask_istft_i16(const float *__restrict_
 {
 #pragma clang fp contract(off)
     constexpr bool I16 = true;
+    const int64_t a_pitch = T, f_pitch = n_seg;
+#include "audio_mask_istft_body.inc"
+}
+
+// Clips: n sequences of DIFFERENT lengths in one launch, the bodies above with each clip's geometry read from `samples`.  Clip e
+// is row e of audio (n, a_pitch = Tmax) with T = clamp(samples[e], 0, Tmax) samples and n_seg = ceil(T / 128) + 1 frames (0 below
+// 512 samples) in row e of tensors padded to f_pitch = Lmax = frames(Tmax) rows, the layout s5fxp_model_clips_f32 takes.  The grid
+// is cut for the longest clip; a workgroup whose tile lies behind its clip's end leaves before the first barrier and LDS write (the
+// test depends on blockIdx and samples[e] only, so a whole workgroup goes or stays).  A frame's transform and an output hop's sum
+// do not depend on the tile that computes them: every clip gets the bits of k_stft_mag / k_mask_istft at B = 1, T = T_e.
+__device__ __forceinline__ int64_t clip_samples(const int32_t *__restrict__ samples, int e, int64_t Tmax)
+{
+    const int64_t s = samples[e];
+    return s < 0 ? 0 : s > Tmax ? Tmax : s;
+}
+__device__ __forceinline__ int64_t clip_frames(int64_t T) { return T < NFFT ? 0 : (T + HOP - 1) / HOP + 1; }
+
+// grid = n * tiles, tiles = ceil(Lmax / 16); lens: NULL or (n), lens[e] = n_seg of clip e for s5fxp_model_clips
+__global__ __launch_bounds__(256) void k_stft_mag_clips(const float *__restrict__ audio, int64_t a_pitch, int64_t f_pitch, int tiles,
+                                                        const int32_t *__restrict__ samples, float sub, float *__restrict__ x,
+                                                        float2 *__restrict__ spec, int32_t *__restrict__ lens)
+{
+#pragma clang fp contract(off)
+    constexpr bool I16 = false;
+    [[maybe_unused]] constexpr int x_bits = 0, x_exp = 0;
+    const int64_t T = clip_samples(samples, blockIdx.x / tiles, a_pitch), n_seg = clip_frames(T);
+    if (lens && blockIdx.x % tiles == 0 && threadIdx.x == 0) lens[blockIdx.x / tiles] = (int32_t)n_seg;
+    if ((int64_t)(blockIdx.x % tiles) * FR >= n_seg) return;
+#include "audio_stft_mag_body.inc"
+}
+
+// grid = n * tiles, tiles = ceil((Lmax - 1) / 13); clip e writes the first (n_seg - 1) * 128 samples of its row of out
+// (n, (Lmax - 1) * 128)
+__global__ __launch_bounds__(256) void k_mask_istft_clips(const float *__restrict__ audio, const float *__restrict__ mask, int64_t a_pitch,
+                                                          int64_t f_pitch, int tiles, const int32_t *__restrict__ samples,
+                                                          float *__restrict__ out, float *__restrict__ cleaned_mag)
+{
+#pragma clang fp contract(off)
+    constexpr bool I16 = false;
+    [[maybe_unused]] constexpr int mask_exp = 0;
+    const int64_t T = clip_samples(samples, blockIdx.x / tiles, a_pitch), n_seg = clip_frames(T);
+    if ((int64_t)(blockIdx.x % tiles) * OH >= n_seg - 1) return;
 #include "audio_mask_istft_body.inc"
 }
 

@@ -341,6 +341,38 @@ extern "C" int s5fxp_mask_istft_i16(const float *audio, const int16_t *mask, int
     });
 }
 
+// ... for n clips of different lengths in one launch each (k_stft_mag_clips / k_mask_istft_clips): the rows are padded to Tmax
+// samples and Lmax = frames(Tmax) frames, the clip's own length comes from `samples` on the device
+namespace {
+int clips_audio_args(const void *audio, const void *samples, const void *io, int n, int64_t Tmax)
+{
+    if (!audio || !samples || !io || n < 1 || Tmax > ((1ll << 20) - 1) * stft::HOP) return S5FXP_EBADARG;
+    return Tmax < stft::NFFT ? S5FXP_EUNSUPPORTED : S5FXP_OK;
+}
+} // namespace
+
+extern "C" int s5fxp_stft_mag_clips(const float *audio, int n, int64_t Tmax, const int32_t *samples, float sub, float *x, float *spec,
+                                    int32_t *lens, void *stream)
+{
+    if (const int rc = clips_audio_args(audio, samples, x, n, Tmax)) return rc;
+    const int64_t Lmax = s5fxp_stft_frames(Tmax), tiles = (Lmax + stft::FR - 1) / stft::FR;
+    if (tiles * n > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
+    hipLaunchKernelGGL(stft::k_stft_mag_clips, dim3((unsigned)(tiles * n)), dim3(256), 0, S(stream), audio, Tmax, Lmax, (int)tiles,
+                       samples, sub, x, reinterpret_cast<float2 *>(spec), lens);
+    return launch_rc();
+}
+
+extern "C" int s5fxp_mask_istft_clips(const float *audio, const float *mask, int n, int64_t Tmax, const int32_t *samples, float *out,
+                                      float *cleaned_mag, void *stream)
+{
+    if (const int rc = clips_audio_args(audio, samples, out, n, Tmax)) return rc;
+    const int64_t Lmax = s5fxp_stft_frames(Tmax), tiles = (Lmax - 1 + stft::OH - 1) / stft::OH;
+    if (tiles * n > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
+    hipLaunchKernelGGL(stft::k_mask_istft_clips, dim3((unsigned)(tiles * n)), dim3(256), 0, S(stream), audio, mask, Tmax, Lmax,
+                       (int)tiles, samples, out, cleaned_mag);
+    return launch_rc();
+}
+
 // The masked inverse with the validation step's scores (audio_score.hpp): the tile sums go through `workspace`, a second small
 // launch forms si_snr, mag_mse and loss per sequence.
 extern "C" size_t s5fxp_score_workspace_bytes(int B, int64_t T)

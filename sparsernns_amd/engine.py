@@ -255,7 +255,8 @@ class Engine:
         forward word [0] of the returned array carries the error bits of ALL groups (the per-group words follow at
         multiples of STATUS_WORDS)."""
         groups = self._groups.get(lane, 1)
-        st = self.lane_status(lane, groups).cpu().numpy()[:groups * _lib.STATUS_WORDS].copy()
+        # sliced on the device: a lane that once served a launch of many clips keeps its longer tensor
+        st = self.lane_status(lane, groups)[:groups * _lib.STATUS_WORDS].cpu().numpy().copy()
         for g in range(1, groups):
             st[0] |= st[g * _lib.STATUS_WORDS]
         if st[0] & _lib.ST_NEGSHIFT:
