@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define S5FXP_VERSION 113
+#define S5FXP_VERSION 114
 
 enum {
     S5FXP_OK = 0,
@@ -186,6 +186,25 @@ int s5fxp_mask_istft_score(const float *audio, const float *clean, const float *
 int s5fxp_mask_istft_score_i16(const float *audio, const float *clean, const int16_t *mask, int mask_exp, int B, int64_t T,
                                float lam, float *out, float *cleaned_mag, void *workspace, size_t workspace_bytes,
                                float *si_snr, float *mag_mse, float *loss, void *stream);
+
+/* The scored inverse for n clips of DIFFERENT lengths, in two launches whatever n: the layouts of s5fxp_mask_istft_clips, with
+ * clean (n,Tmax) float32 padded like audio and sharing its `samples`.  Clip e is scored over its own T_e samples and len_e
+ * frames: padding enters neither N, the means nor the MSE denominator.  mask (n,Lmax,257) or NULL (zeros); out
+ * (n,(Lmax-1)*128) and cleaned_mag (n,Lmax,257) are what s5fxp_mask_istft_clips writes, padding untouched, and may each be
+ * NULL; si_snr, mag_mse, loss: (n) float32, mag_mse and loss may be NULL.  Every score and every plane of clip e is bit for bit
+ * what s5fxp_mask_istft_score gives for it alone at B = 1, T = T_e: a tile's sums depend on the clip's own geometry only, and
+ * the clip's own tiles are added in the same order.  A clip below 512 samples has no frames: its three scores are quiet NaNs and
+ * nothing else of it is written.
+ * workspace: s5fxp_score_clips_workspace_bytes(n, Tmax) = 48 * n * ceil((s5fxp_stft_frames(Tmax) - 1) / 13) bytes of device
+ * memory, 8-byte aligned, overwritten where a clip has tiles (0 for n < 1, Tmax < 512 or Tmax > (2^20 - 1) * 128).
+ * Checked before the device is touched, in this order: S5FXP_EBADARG for a null audio, clean, samples, workspace or si_snr,
+ * n < 1 or Tmax > (2^20 - 1) * 128; S5FXP_EUNSUPPORTED for Tmax < 512 or a grid beyond 2^31 - 1; S5FXP_EWORKSPACE for a
+ * workspace that is too small. */
+size_t s5fxp_score_clips_workspace_bytes(int n, int64_t Tmax);
+int s5fxp_mask_istft_score_clips(const float *audio, const float *clean, const float *mask, int n, int64_t Tmax,
+                                 const int32_t *samples, float lam, float *out, float *cleaned_mag,
+                                 void *workspace, size_t workspace_bytes,
+                                 float *si_snr, float *mag_mse, float *loss, void *stream);
 
 /* The same framing for a live signal: whole hops of 128 samples in, cleaned hops out (a caller zero-fills its last hop, as
  * scipy's padded=True does).  S streams advance in lock step.  With h = hops_before hops received and a push of c hops

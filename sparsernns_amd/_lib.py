@@ -124,6 +124,8 @@ def _load():
         "s5fxp_score_workspace_bytes": (C.c_size_t, [i, i64]),
         "s5fxp_mask_istft_score": (i, [p, p, p, i, i64, C.c_float, p, p, p, C.c_size_t, p, p, p, p]),
         "s5fxp_mask_istft_score_i16": (i, [p, p, p, i, i, i64, C.c_float, p, p, p, C.c_size_t, p, p, p, p]),
+        "s5fxp_score_clips_workspace_bytes": (C.c_size_t, [i, i64]),
+        "s5fxp_mask_istft_score_clips": (i, [p, p, p, i, i64, p, C.c_float, p, p, p, C.c_size_t, p, p, p, p]),
         "s5fxp_stream_audio_state_bytes": (C.c_size_t, []),
         "s5fxp_stream_frames": (i64, [i64, i]),
         "s5fxp_stream_out_hops": (i64, [i64, i, i]),
@@ -177,7 +179,7 @@ EXPORTED_SYMBOLS = ("s5fxp_version s5fxp_strerror s5fxp_from_fp s5fxp_to_float s
                     "s5fxp_push_desc_check s5fxp_model_step_ragged s5fxp_model_step_ragged_f32 s5fxp_stream_stft_ragged "
                     "s5fxp_stream_mask_istft_ragged "
                     "s5fxp_clips_workspace_bytes s5fxp_model_clips_ok s5fxp_model_clips s5fxp_model_clips_f32 "
-                    "s5fxp_stft_mag_clips s5fxp_mask_istft_clips").split()
+                    "s5fxp_stft_mag_clips s5fxp_mask_istft_clips s5fxp_score_clips_workspace_bytes s5fxp_mask_istft_score_clips").split()
 
 
 def check(rc: int, what: str = "") -> None:

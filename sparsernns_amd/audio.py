@@ -351,32 +351,25 @@ def mask_istft_clips(audio: torch.Tensor, samples: torch.Tensor, mask, cleaned_m
     return (o, cm) if cleaned_mag else o
 
 
-def denoise_clips(model, inp_bits: int, inp_exp: int, clips, lane=0):
-    """``denoise_fused`` for a list of 1-D float audio clips of any lengths >= 512 (below: NotImplementedError, before any
-    launch; an empty list gives []).  Returns per clip (cleaned ((len_e - 1) * 128,), cleaned_mag, x, mask), the last three
-    (len_e, 257): bit for bit the tuple ``denoise_fused(model, inp_bits, inp_exp, clip[None])`` returns, without the batch axis.
-
-    On a GPU, for a model on the fused path that does not store intermediates and takes (inp_bits, inp_exp) at its encoder, that
-    is THREE launches whatever n: the audio is padded once, ``stft_mag_clips`` writes the padded rows and the frame counts,
-    ``Engine.clips`` runs on those very tensors, the status words are read once (a clip flagged ST_WIDE_INPUT gets its mask rows
-    from the generic engine), ``mask_istft_clips`` follows.  Any other model or device takes ``denoise_fused`` clip by clip.
-
-    One CU walks one clip through the model, tile after tile, so the launch is as long as its longest clip: this is for MANY
-    clips.  A single long clip, or a few, belong on ``denoise_fused``, which spreads a sequence over the chip (DESIGN.md §4o)."""
+def _clips_front(model, inp_bits: int, inp_exp: int, clips, lane):
+    """What ``denoise_clips`` and ``validate_clips`` share in front of the inverse: the checks of the clip list, and on the
+    one-launch route the padding, ``stft_mag_clips``, ``Engine.clips`` and the one read of the status words.  Returns
+    (clips, front) with front = (audio, samples, x, mask, L) -- padded tensors and the frame counts -- or None where the clips
+    go through the per-clip functions (and for an empty list)."""
     clips = [torch.as_tensor(c) for c in clips]
     for c in clips:
         if c.dim() != 1:
             raise ValueError(f"every clip must be 1-D audio, got {tuple(c.shape)}")
         stft_frames(int(c.shape[0]))
     if not clips:
-        return []
+        return clips, None
     Ts = [int(c.shape[0]) for c in clips]
     Tmax, Lmax, dev = max(Ts), stft_frames(max(Ts)), clips[0].device
     one_launch = (all(c.is_cuda and c.device == dev for c in clips) and hasattr(model, "engine") and hasattr(model, "forward_float")
                   and not getattr(model, "store_intermediates", False) and _takes(model, inp_bits, inp_exp)
                   and model.engine().clips_ok(Lmax))
     if not one_launch:
-        return [tuple(t[0] for t in denoise_fused(model, inp_bits, inp_exp, c[None])) for c in clips]
+        return clips, None
     from . import _lib
     eng, n = model.engine(), len(clips)
     audio = torch.nn.utils.rnn.pad_sequence([c.to(torch.float32) for c in clips], batch_first=True)
@@ -394,8 +387,27 @@ def denoise_clips(model, inp_bits: int, inp_exp: int, clips, lane=0):
         for e in np.nonzero(st[:, 0] & _lib.ST_WIDE_INPUT)[0]:
             mask[e, :L[e]] = eng.generic_twin()._forward(x[e, :L[e]].contiguous(), eng.inp_bits, eng.inp_exp, torch.float32, False,
                                                          None, True)[0]
-        cleaned, cm = mask_istft_clips(audio, samples, mask, cleaned_mag=True)
-    return [(cleaned[e, :(L[e] - 1) * HOP], cm[e, :L[e]], x[e, :L[e]], mask[e, :L[e]]) for e in range(n)]
+    return clips, (audio, samples, x, mask, L)
+
+
+def denoise_clips(model, inp_bits: int, inp_exp: int, clips, lane=0):
+    """``denoise_fused`` for a list of 1-D float audio clips of any lengths >= 512 (below: NotImplementedError, before any
+    launch; an empty list gives []).  Returns per clip (cleaned ((len_e - 1) * 128,), cleaned_mag, x, mask), the last three
+    (len_e, 257): bit for bit the tuple ``denoise_fused(model, inp_bits, inp_exp, clip[None])`` returns, without the batch axis.
+
+    On a GPU, for a model on the fused path that does not store intermediates and takes (inp_bits, inp_exp) at its encoder, that
+    is THREE launches whatever n: the audio is padded once, ``stft_mag_clips`` writes the padded rows and the frame counts,
+    ``Engine.clips`` runs on those very tensors, the status words are read once (a clip flagged ST_WIDE_INPUT gets its mask rows
+    from the generic engine), ``mask_istft_clips`` follows.  Any other model or device takes ``denoise_fused`` clip by clip.
+
+    One CU walks one clip through the model, tile after tile, so the launch is as long as its longest clip: this is for MANY
+    clips.  A single long clip, or a few, belong on ``denoise_fused``, which spreads a sequence over the chip (DESIGN.md §4o)."""
+    clips, front = _clips_front(model, inp_bits, inp_exp, clips, lane)
+    if front is None:
+        return [tuple(t[0] for t in denoise_fused(model, inp_bits, inp_exp, c[None])) for c in clips]
+    audio, samples, x, mask, L = front
+    cleaned, cm = mask_istft_clips(audio, samples, mask, cleaned_mag=True)
+    return [(cleaned[e, :(L[e] - 1) * HOP], cm[e, :L[e]], x[e, :L[e]], mask[e, :L[e]]) for e in range(len(clips))]
 
 
 def validate_batch(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, clean: torch.Tensor, lam: float = 0.001,
@@ -484,6 +496,87 @@ def validate_fused(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, clea
         fx = fxp_from_fp(x, bits=inp_bits, exp=inp_exp, signed=True, round_mode=RoundingMode.FLOOR)
         mask = model(fx).to_float()
     return score_fused(noisy, clean, mask, lam)[:2]
+
+
+def score_clips(noisy: torch.Tensor, clean: torch.Tensor, samples: torch.Tensor, mask, lam: float = 0.001, cleaned: bool = False,
+                cleaned_mag: bool = False, out=None):
+    """``score_fused`` for n clips of different lengths in TWO launches whatever n (csrc/audio_score.hpp:
+    k_mask_istft_score_clips, k_score_finalize_clips): noisy and clean (n, Tmax) float32, padded; samples (n,) int32 on their
+    device; mask (n, Lmax, 257) float32 or None (zeros), the layouts of ``mask_istft_clips`` -> (loss, si_snr, mag_mse), each
+    (n,) float32.  Clip e is scored over its own T_e samples and len_e frames -- padding enters neither N, the means nor the MSE
+    denominator -- and gets bit for bit ``score_fused(noisy[e:e+1, :T_e], clean[e:e+1, :T_e], mask[e:e+1, :len_e])``.  With
+    ``cleaned`` / ``cleaned_mag`` the planes of ``mask_istft_clips`` follow, bit for bit, nothing written behind a clip's end
+    (``out``: the plane tensors to write into, in the order returned); without them they are never stored.  A clip below 512
+    samples has no frames: its three scores are NaN and nothing else of it is written."""
+    noisy, samples, n, Tmax, Lmax = _clips_args(noisy, samples)
+    dev, shape = noisy.device, (n, Lmax, NFFT // 2 + 1)
+    if clean.dim() != 2 or tuple(clean.shape) != (n, Tmax) or clean.device != dev:
+        raise ValueError(f"clean must be {(n, Tmax)} on {dev}, got {tuple(clean.shape)} on {clean.device}")
+    clean = clean.to(torch.float32).contiguous()
+    if mask is not None:
+        if tuple(mask.shape) != shape or mask.device != dev:
+            raise ValueError(f"mask must be {shape} on {dev}, got {tuple(mask.shape)} on {mask.device}")
+        mask = mask.to(torch.float32).contiguous()
+    planes = _clips_out(out, ([((n, (Lmax - 1) * HOP), torch.float32, dev)] if cleaned else [])
+                        + ([(shape, torch.float32, dev)] if cleaned_mag else []), "score_clips")
+    o, cm = planes[0] if cleaned else None, planes[-1] if cleaned_mag else None
+    scores = torch.empty(3, n, dtype=torch.float32, device=dev)
+    if not noisy.is_cuda:
+        T, L = _clip_lengths(samples, Tmax)
+        for e in range(n):
+            if not L[e]:
+                scores[:, e] = float("nan")
+                continue
+            r = score_fused(noisy[e:e + 1, :T[e]], clean[e:e + 1, :T[e]], mask[e:e + 1, :L[e]] if mask is not None else None, lam,
+                            cleaned=cleaned, cleaned_mag=cleaned_mag)
+            scores[0, e], scores[1, e], scores[2, e] = r[0][0], r[1][0], r[2][0]
+            if cleaned:
+                o[e, :(L[e] - 1) * HOP] = r[3][0]
+            if cleaned_mag:
+                cm[e, :L[e]] = r[-1][0]
+        return (scores[0], scores[1], scores[2]) + tuple(planes)
+    from . import _lib
+    ws_bytes = _lib.lib.s5fxp_score_clips_workspace_bytes(n, Tmax)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib.s5fxp_mask_istft_score_clips(noisy.data_ptr(), clean.data_ptr(), ptr(mask), n, Tmax, samples.data_ptr(),
+                                                         float(lam), ptr(o), ptr(cm), ws.data_ptr(), ws_bytes, scores[1].data_ptr(),
+                                                         scores[2].data_ptr(), scores[0].data_ptr(),
+                                                         torch.cuda.current_stream().cuda_stream), "s5fxp_mask_istft_score_clips")
+    return (scores[0], scores[1], scores[2]) + tuple(planes)
+
+
+def validate_clips(model, inp_bits: int, inp_exp: int, noisy_clips, clean_clips, lam: float = 0.001, lane=0):
+    """``validate_fused`` for lists of 1-D float audio clips of any lengths >= 512 (below: NotImplementedError, before any
+    launch): clean_clips[e] has noisy_clips[e]'s length (otherwise, or for lists of different counts, ValueError).  Returns
+    (loss, si_snr), (n,) float32 each (two empty tensors for empty lists): per clip bit for bit
+    ``validate_fused(model, inp_bits, inp_exp, noisy[None], clean[None], lam)`` on the float32 boundary.
+
+    Under ``denoise_clips``' conditions for its one-launch route, with the clean clips on the noisy clips' device, that is FOUR
+    launches whatever n: ``stft_mag_clips`` -> ``Engine.clips`` -> the scored inverse -> its finalize (``score_clips``); the
+    status words are read once, before the scored inverse (a clip flagged ST_WIDE_INPUT gets its mask rows from the generic
+    engine).  Any other model or device takes ``validate_fused`` clip by clip.
+
+    One CU walks one clip through the model, tile after tile, so the launch is as long as its longest clip: this is for MANY
+    clips.  A single long clip, or a few, belong on ``validate_fused``, which spreads a sequence over the chip."""
+    noisy_clips, clean_clips = list(noisy_clips), [torch.as_tensor(c) for c in clean_clips]
+    if len(noisy_clips) != len(clean_clips):
+        raise ValueError(f"{len(noisy_clips)} noisy clips but {len(clean_clips)} clean ones")
+    for e, (c, r) in enumerate(zip(noisy_clips, clean_clips)):
+        if tuple(r.shape) != tuple(torch.as_tensor(c).shape):
+            raise ValueError(f"clean clip {e} must be {tuple(torch.as_tensor(c).shape)}, got {tuple(r.shape)}")
+    same_device = all(r.device == torch.as_tensor(c).device for c, r in zip(noisy_clips, clean_clips))
+    # clean clips elsewhere: no model qualifies for the one-launch route
+    noisy_clips, front = _clips_front(model if same_device else None, inp_bits, inp_exp, noisy_clips, lane)
+    if not noisy_clips:
+        return torch.empty(0, dtype=torch.float32), torch.empty(0, dtype=torch.float32)
+    if front is None:
+        r = [validate_fused(model, inp_bits, inp_exp, c[None], k[None], lam) for c, k in zip(noisy_clips, clean_clips)]
+        return torch.cat([t[0] for t in r]), torch.cat([t[1] for t in r])
+    audio, samples, _, mask, _ = front
+    clean = torch.nn.utils.rnn.pad_sequence([c.to(torch.float32) for c in clean_clips], batch_first=True)
+    return score_clips(audio, clean, samples, mask, lam)[:2]
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1,9 +1,11 @@
-// audio_mask_istft_score_body.inc -- the body of k_mask_istft_score and k_mask_istft_score_i16 (audio_score.hpp), included by
-// both with I16 = false / true: audio_mask_istft_body.inc with the clean clip's transform in front and the sums folded in.
+// audio_mask_istft_score_body.inc -- the body of k_mask_istft_score, k_mask_istft_score_i16 and k_mask_istft_score_clips
+// (audio_score.hpp), included with I16 = false / true: audio_mask_istft_body.inc with the clean clip's transform in front and the
+// sums folded in.  T, n_seg, a_pitch and f_pitch as in audio_stft_mag_body.inc (clean is pitched like audio); the tile sums go to
+// partials at pitch `tiles`, the grid's.
     __shared__ Smem sm;
     const int64_t b = blockIdx.x / tiles, o0 = (int64_t)(blockIdx.x % tiles) * OH, k0 = o0 - 1;
     constexpr int NJ = (FR * NBIN + 255) / 256;
-    const int64_t base = (b * n_seg + k0) * NBIN;
+    const int64_t base = (b * f_pitch + k0) * NBIN;
     // of the tile's frames fr = 0..15 (frame k0 + fr of the sequence) fr_lo..fr_hi exist; the tile owns 1..own_hi of them, as
     // audio_mask_istft_body.inc reports them in cleaned_mag: its frames 1..13, the last tile of a sequence also what lies beyond
     const int fr_lo = k0 < 0 ? 1 : 0, fr_hi = (int)(n_seg - 1 - k0 < FR - 1 ? n_seg - 1 - k0 : FR - 1);
@@ -11,7 +13,7 @@
     // the clean clip first, in the planes the noisy tile will take: |Z_clean| of this thread's elements (threadIdx.x + 256 j of
     // the tile's 16 x 257) stays in registers
     make_twiddles(sm);
-    forward_tile(sm, clean + b * T, T, k0);
+    forward_tile(sm, clean + b * a_pitch, T, k0);
     float cm[NJ];
     // this phase's lane masks are computed from a thread index the compiler cannot match with the later loops', or it keeps
     // 17 of them in scalar registers across both transforms and spills
@@ -32,7 +34,7 @@
         if constexpr (I16) f[j] = (mask && fr >= fr_lo && fr <= fr_hi) ? 1.0f + tofloat(mask[base + i], mask_exp) : 1.0f;
         else f[j] = (mask && fr >= fr_lo && fr <= fr_hi) ? 1.0f + mask[base + i] : 1.0f;
     }
-    forward_tile(sm, audio + b * T, T, k0);
+    forward_tile(sm, audio + b * a_pitch, T, k0);
     double sum[NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     // Z' = Z * (1 + mask) into plane A
 #pragma unroll
@@ -57,8 +59,8 @@
     const int64_t n_out = n_seg - 1;
     const int noh = (int)(n_out - o0 < OH ? n_out - o0 : OH);
     const float *seg = reinterpret_cast<const float *>(sm.a);
-    float *dst = out ? out + b * n_out * HOP + o0 * HOP : nullptr;
-    const float *ref = clean + b * T;
+    float *dst = out ? out + b * (f_pitch - 1) * HOP + o0 * HOP : nullptr;
+    const float *ref = clean + b * a_pitch;
     for (int i = threadIdx.x; i < noh * HOP; i += 256) {
         const int j = i >> 7, s = i & 127;
         const int64_t o = o0 + j, g = o0 * HOP + i;

@@ -9,6 +9,7 @@
 //                             |Z| * (1 + mask) of the noisy clip where that is formed; every cleaned sample meets its clean
 //                             sample (a second read of the clean hops, from the L2) where it would be stored.
 //   k_score_finalize          grid = B: the tile sums of a sequence in index order, then the three scores.
+//   k_mask_istft_score_clips / k_score_finalize_clips: the two for n clips of different lengths (at the end).
 //
 // Ownership.  Neighbouring tiles overlap by three frames; a tile counts the frames it reports in cleaned_mag -- its frames
 // 1..13, the last tile of a sequence also what lies beyond them -- so every frame 0..n_seg-1 is counted once.  Output hops
@@ -44,6 +45,7 @@ __global__ __launch_bounds__(256) void k_mask_istft_score(const float *__restric
 #pragma clang fp contract(off)
     constexpr bool I16 = false;
     [[maybe_unused]] constexpr int mask_exp = 0;
+    const int64_t a_pitch = T, f_pitch = n_seg;
 #include "audio_mask_istft_score_body.inc"
 }
 
@@ -54,6 +56,7 @@ __global__ __launch_bounds__(256) void k_mask_istft_score_i16(const float *__res
 {
 #pragma clang fp contract(off)
     constexpr bool I16 = true;
+    const int64_t a_pitch = T, f_pitch = n_seg;
 #include "audio_mask_istft_score_body.inc"
 }
 
@@ -64,25 +67,51 @@ __global__ __launch_bounds__(64) void k_score_finalize(const double *__restrict_
                                                        float *__restrict__ loss)
 {
 #pragma clang fp contract(off)
-    const int c = threadIdx.x;
-    double s = 0.0;
-    if (c < NSUM) {
-        const double *p = partials + (int64_t)blockIdx.x * tiles * NSUM + c;
-#pragma unroll 8
-        for (int t = 0; t < tiles; ++t) s += p[(int64_t)t * NSUM];
+    const int pitch = tiles;
+#include "audio_score_finalize_body.inc"
+}
+
+// Clips: n sequences of DIFFERENT lengths in two launches, the layout and the geometry of k_mask_istft_clips (audio_stft.hpp);
+// clean is (n, Tmax), padded like audio, and clip e is scored over its own T_e samples and len_e frames.  A tile's six sums depend
+// on that tile's frames and on the clip's own T and n_seg only, and the finalize adds the clip's own tiles in the same order with
+// the same expressions: every score, and every plane, has the bits of k_mask_istft_score / k_score_finalize at B = 1, T = T_e.
+//
+// grid = n * tiles, tiles = ceil((Lmax - 1) / 13); partials: (n, tiles, NSUM) double.  A workgroup whose tile lies behind its
+// clip's end leaves before the first barrier and LDS write and writes no partial.
+__global__ __launch_bounds__(256) void k_mask_istft_score_clips(const float *__restrict__ audio, const float *__restrict__ clean,
+                                                                const float *__restrict__ mask, int64_t a_pitch, int64_t f_pitch,
+                                                                int tiles, const int32_t *__restrict__ samples,
+                                                                float *__restrict__ out, float *__restrict__ cleaned_mag,
+                                                                double *__restrict__ partials)
+{
+#pragma clang fp contract(off)
+    constexpr bool I16 = false;
+    [[maybe_unused]] constexpr int mask_exp = 0;
+    const int64_t T = clip_samples(samples, blockIdx.x / tiles, a_pitch), n_seg = clip_frames(T);
+    if ((int64_t)(blockIdx.x % tiles) * OH >= n_seg - 1) return;
+#include "audio_mask_istft_score_body.inc"
+}
+
+// grid = n, one wave; pitch: the tiles of the grid above.  Only the tiles whose workgroups stayed, 0 .. ceil((len_e - 1) / 13) - 1, are
+// read.  A clip without frames gets a quiet NaN in all three scores.
+__global__ __launch_bounds__(64) void k_score_finalize_clips(const double *__restrict__ partials, int pitch, int64_t Tmax,
+                                                             const int32_t *__restrict__ samples, float lam,
+                                                             float *__restrict__ si_snr, float *__restrict__ mag_mse,
+                                                             float *__restrict__ loss)
+{
+#pragma clang fp contract(off)
+    const int64_t T = clip_samples(samples, blockIdx.x, Tmax), n_seg = clip_frames(T);
+    if (n_seg == 0) {
+        if (threadIdx.x == 0) {
+            const float nan = __builtin_nanf("");
+            si_snr[blockIdx.x] = nan;
+            if (mag_mse) mag_mse[blockIdx.x] = nan;
+            if (loss) loss[blockIdx.x] = nan;
+        }
+        return;
     }
-    const double st = __shfl(s, 0), se = __shfl(s, 1), st2 = __shfl(s, 2), se2 = __shfl(s, 3), ste = __shfl(s, 4),
-                 sd2 = __shfl(s, 5);
-    if (c) return;
-    const double N = (double)T;
-    const double nt = st2 - st * st / N, ne = se2 - se * se / N, dot = ste - st * se / N;
-    const double P = dot * dot / nt;
-    const double nz = ne - P > 0.0 ? ne - P : 0.0;
-    const double score = 10.0 * log10(P / (nz + 1e-8) + 1e-8);
-    const double mse = sd2 / ((double)n_seg * NBIN);
-    si_snr[blockIdx.x] = (float)score;
-    if (mag_mse) mag_mse[blockIdx.x] = (float)mse;
-    if (loss) loss[blockIdx.x] = (float)((double)lam * mse + (100.0 - score));
+    const int tiles = (int)((n_seg - 1 + OH - 1) / OH);
+#include "audio_score_finalize_body.inc"
 }
 
 } // namespace stft

@@ -421,6 +421,31 @@ extern "C" int s5fxp_mask_istft_score_i16(const float *audio, const float *clean
     });
 }
 
+// ... for n clips of different lengths (k_mask_istft_score_clips / k_score_finalize_clips): the layouts of s5fxp_mask_istft_clips,
+// clean padded like audio, one score per clip over its own length
+extern "C" size_t s5fxp_score_clips_workspace_bytes(int n, int64_t Tmax)
+{
+    if (n < 1 || Tmax < stft::NFFT || Tmax > ((1ll << 20) - 1) * stft::HOP) return 0;
+    const int64_t tiles = (s5fxp_stft_frames(Tmax) - 1 + stft::OH - 1) / stft::OH;
+    return (size_t)n * (size_t)tiles * stft::NSUM * sizeof(double);
+}
+
+extern "C" int s5fxp_mask_istft_score_clips(const float *audio, const float *clean, const float *mask, int n, int64_t Tmax,
+                                            const int32_t *samples, float lam, float *out, float *cleaned_mag, void *workspace,
+                                            size_t workspace_bytes, float *si_snr, float *mag_mse, float *loss, void *stream)
+{
+    if (!clean || !workspace) return S5FXP_EBADARG;
+    if (const int rc = clips_audio_args(audio, samples, si_snr, n, Tmax)) return rc;
+    const int64_t Lmax = s5fxp_stft_frames(Tmax), tiles = (Lmax - 1 + stft::OH - 1) / stft::OH;
+    if (tiles * n > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
+    if (workspace_bytes < s5fxp_score_clips_workspace_bytes(n, Tmax)) return S5FXP_EWORKSPACE;
+    hipLaunchKernelGGL(stft::k_mask_istft_score_clips, dim3((unsigned)(tiles * n)), dim3(256), 0, S(stream), audio, clean, mask, Tmax,
+                       Lmax, (int)tiles, samples, out, cleaned_mag, static_cast<double *>(workspace));
+    hipLaunchKernelGGL(stft::k_score_finalize_clips, dim3((unsigned)n), dim3(64), 0, S(stream), static_cast<const double *>(workspace),
+                       (int)tiles, Tmax, samples, lam, si_snr, mag_mse, loss);
+    return launch_rc();
+}
+
 // The same framing for a live signal (audio_stream.hpp): whole hops in, cleaned hops out, the caller's state between calls.
 extern "C" size_t s5fxp_stream_audio_state_bytes(void) { return stft::STATE_FLOATS * sizeof(float); }
 
