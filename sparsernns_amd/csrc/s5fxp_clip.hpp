@@ -3,7 +3,8 @@
 // exponents, status words and carry.  Bit for bit s5fxp_model_forward(B = 1, L = len_e) on that clip alone.
 // Included by s5fxp_api.hip after s5fxp_step.hpp: it is the step kernel's stages (s5fxp_step_body.inc) restructured into
 // loops over 32-row tiles -- step_mm, step_put2 / step_put4, step_wg_max, StepParams and the generic kernels' primitives,
-// op for op; no new arithmetic.
+// op for op; no new arithmetic.  The BatchNorm exponent reductions are the step kernel's function (step_bn_exps); the other
+// stages are a copy of the body's text, pinned to it by tests/test_clips.py::test_one_tile_equals_the_step_kernel.
 //
 // What outlives a tile lives in a workgroup-private scratch in device memory (the caller's workspace): per clip two int16
 // planes of Lmax x H, the layer input h and the gate output z.  The tensor-wide maxima (four BatchNorm exponents, the
@@ -141,77 +142,9 @@ __global__ __launch_bounds__(STEP_THREADS, 2) void k_model_clips(ClipArgs a)
         int32_t *st_exps = s_status + 8 + 8 * li;
         if (tid < 8) s_lut[tid] = sl.lut[tid];
 
-        // ---- the four BatchNorm compute_best exponents (fxpmodel.py:892-933): full reductions over the len x H values of h
-        {
-            float v[3] = {0.f, 0.f, 0.f};
-            for (int i = tid; i < LH; i += STEP_THREADS) {
-                const int c = i % H;
-                const float fx = tofloat(hg[i], he), fm = tofloat(bn.mm[c], bn.me);
-                v[0] = fmaxf(v[0], fabsf(__fadd_rn(fx, fm)));
-                v[1] = fmaxf(v[1], fabsf(fx));
-                v[2] = fmaxf(v[2], fabsf(fm));
-            }
-            step_wg_max<3, STEP_WAVES>(v, s_red);
-            if (tid == 0) {
-                const uint32_t m3[3] = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2])};
-                s_d.bn1 = finalize_add_cb(m3, he, bn.me, bn.b1, s_status);
-                st_exps[0] = s_d.bn1.eo;
-                s_d.bn_e = s_d.bn1.eo;
-            }
-            __syncthreads();
-        }
-        {
-            LayerDyn d = s_d;
-            float v[1] = {0.f};
-            for (int i = tid; i < LH; i += STEP_THREADS) {
-                const int c = i % H;
-                const int32_t t = bn_chain<1>(bn, d, hg[i], c);
-                v[0] = fmaxf(v[0], fabsf(__fmul_rn(tofloat(t, d.bn1.eo), tofloat(bn.isv[c], bn.ie))));
-            }
-            step_wg_max<1, STEP_WAVES>(v, s_red);
-            if (tid == 0) {
-                finalize_mul_cb(__float_as_uint(v[0]), s_d.bn1.eo, bn.ie, bn.b2, s_d.rs2, s_d.e2, s_status);
-                st_exps[1] = s_d.e2;
-                s_d.bn_e = s_d.e2;
-            }
-            __syncthreads();
-        }
-        if (bn.scale) {
-            LayerDyn d = s_d;
-            float v[1] = {0.f};
-            for (int i = tid; i < LH; i += STEP_THREADS) {
-                const int c = i % H;
-                const int32_t t = bn_chain<2>(bn, d, hg[i], c);
-                v[0] = fmaxf(v[0], fabsf(__fmul_rn(tofloat(t, d.e2), tofloat(bn.scale[c], bn.se))));
-            }
-            step_wg_max<1, STEP_WAVES>(v, s_red);
-            if (tid == 0) {
-                finalize_mul_cb(__float_as_uint(v[0]), s_d.e2, bn.se, bn.b3, s_d.rs3, s_d.e3, s_status);
-                st_exps[2] = s_d.e3;
-                s_d.bn_e = s_d.e3;
-            }
-            __syncthreads();
-        }
-        if (bn.bias) {
-            LayerDyn d = s_d;
-            float v[3] = {0.f, 0.f, 0.f};
-            for (int i = tid; i < LH; i += STEP_THREADS) {
-                const int c = i % H;
-                const int32_t t = bn_chain<3>(bn, d, hg[i], c);
-                const float ft = tofloat(t, bn.scale ? d.e3 : d.e2), fb = tofloat(bn.bias[c], bn.be);
-                v[0] = fmaxf(v[0], fabsf(__fadd_rn(ft, fb)));
-                v[1] = fmaxf(v[1], fabsf(ft));
-                v[2] = fmaxf(v[2], fabsf(fb));
-            }
-            step_wg_max<3, STEP_WAVES>(v, s_red);
-            if (tid == 0) {
-                const uint32_t m3[3] = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2])};
-                s_d.bn4 = finalize_add_cb(m3, bn.scale ? s_d.e3 : s_d.e2, bn.be, bn.b4, s_status);
-                st_exps[3] = s_d.bn4.eo;
-                s_d.bn_e = s_d.bn4.eo;
-            }
-            __syncthreads();
-        }
+        // ---- the four BatchNorm compute_best exponents over the len x H values of h, re-read from the scratch: the step
+        // kernel's function (s5fxp_step.hpp step_bn_exps)
+        step_bn_exps<STEP_THREADS>(hg, LH, H, bn, he, s_d, s_status, st_exps, s_red);
         const LayerDyn d = s_d;
 
         // ---- the tiles: u -> B projection -> recurrence -> C projection -> out2 -> gate -> z rows in the scratch.
@@ -431,16 +364,7 @@ int clips_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int 
     a.sp = m->fast->step; a.x = x; a.y = y; a.lens = lens; a.state_in = state_in; a.state_out = state_out;
     a.scratch = reinterpret_cast<int16_t *>(workspace); a.status = status;
     a.Lmax = Lmax; a.x_bits = x_bits; a.x_exp = x_exp; a.f32 = f32 ? 1 : 0;
-    auto launch = [&](auto kernel, unsigned threads) {
-        if (smem > 65536)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(threads), smem, S(stream), a);
-    };
-    const int threads = step_threads(n, smem);
-    if (threads == 512) launch(k_model_clips<512>, 512);
-    else if (threads == 256) launch(k_model_clips<256>, 256);
-    else launch(k_model_clips<128>, 128);
-    return launch_rc();
+    return step_launch(n, smem, a, k_model_clips<512>, k_model_clips<256>, k_model_clips<128>, stream);
 }
 
 } // namespace

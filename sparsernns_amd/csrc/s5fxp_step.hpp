@@ -19,6 +19,9 @@
 //     fits 16 bits -- a workgroup-uniform test -- two byte planes run, otherwise four.
 // Two kernels share the body (s5fxp_step_body.inc): k_model_step, every group B x L rows and carry g, and k_model_step_ragged,
 // every group its own row count and carry slot from a descriptor (s5fxp_model_step_ragged), x and y padded to Lmax frames.
+// The clip kernel (s5fxp_clip.hpp) repeats the body's stages over 32-row tiles.  One stage is a function both call,
+// step_bn_exps below (the four BatchNorm exponent reductions); the others are still text in both and have to be kept
+// equal by hand (DESIGN.md 4o says why they stayed).  The three entries share one launcher, step_launch.
 // LDS (dynamic, sized by R): [PLA: encoder-input / state planes][PLB: u / out2-input / decoder-input planes]
 //   [h int16 R x H][x1 int16 R x H][z int16 R x H][bq int32 2 x R x P].  R = 32 at H = 192: 120 KB; R = 1: 3.4 KB.
 #pragma once
@@ -161,6 +164,88 @@ __device__ __forceinline__ void step_wg_max(float (&v)[NV], float (*red)[STEP_MA
     __syncthreads();
 }
 
+// ---- the four BatchNorm compute_best exponents (fxpmodel.py:892-933): full reductions over the n values of h, the rule of
+// k_bn_reduce / k_bn_finalize.  One function for the step kernels (h in LDS, n = R * H) and the clip kernel (h in the
+// workgroup's scratch, n = len * H): it is inlined, so h keeps the address space its kernel gave it.  Each reduction ends
+// behind a barrier; after the last one s_d is complete for every thread.
+template <int STEP_THREADS>
+__device__ __forceinline__ void step_bn_exps(const int16_t *hsrc, int n, int H, const BnArgs &bn, int he, LayerDyn &s_d,
+                                             int32_t *s_status, int32_t *st_exps, float (*s_red)[STEP_MAX_WAVES])
+{
+    constexpr int STEP_WAVES = STEP_THREADS / 64;
+    const int tid = threadIdx.x;
+    {
+        float v[3] = {0.f, 0.f, 0.f};
+        for (int i = tid; i < n; i += STEP_THREADS) {
+            const int c = i % H;
+            const float fx = tofloat(hsrc[i], he), fm = tofloat(bn.mm[c], bn.me);
+            v[0] = fmaxf(v[0], fabsf(__fadd_rn(fx, fm)));
+            v[1] = fmaxf(v[1], fabsf(fx));
+            v[2] = fmaxf(v[2], fabsf(fm));
+        }
+        step_wg_max<3, STEP_WAVES>(v, s_red);
+        if (tid == 0) {
+            const uint32_t m3[3] = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2])};
+            s_d.bn1 = finalize_add_cb(m3, he, bn.me, bn.b1, s_status);
+            st_exps[0] = s_d.bn1.eo;
+            s_d.bn_e = s_d.bn1.eo;
+        }
+        __syncthreads();
+    }
+    {
+        LayerDyn d = s_d;
+        float v[1] = {0.f};
+        for (int i = tid; i < n; i += STEP_THREADS) {
+            const int c = i % H;
+            const int32_t t = bn_chain<1>(bn, d, hsrc[i], c);
+            v[0] = fmaxf(v[0], fabsf(__fmul_rn(tofloat(t, d.bn1.eo), tofloat(bn.isv[c], bn.ie))));
+        }
+        step_wg_max<1, STEP_WAVES>(v, s_red);
+        if (tid == 0) {
+            finalize_mul_cb(__float_as_uint(v[0]), s_d.bn1.eo, bn.ie, bn.b2, s_d.rs2, s_d.e2, s_status);
+            st_exps[1] = s_d.e2;
+            s_d.bn_e = s_d.e2;
+        }
+        __syncthreads();
+    }
+    if (bn.scale) {
+        LayerDyn d = s_d;
+        float v[1] = {0.f};
+        for (int i = tid; i < n; i += STEP_THREADS) {
+            const int c = i % H;
+            const int32_t t = bn_chain<2>(bn, d, hsrc[i], c);
+            v[0] = fmaxf(v[0], fabsf(__fmul_rn(tofloat(t, d.e2), tofloat(bn.scale[c], bn.se))));
+        }
+        step_wg_max<1, STEP_WAVES>(v, s_red);
+        if (tid == 0) {
+            finalize_mul_cb(__float_as_uint(v[0]), s_d.e2, bn.se, bn.b3, s_d.rs3, s_d.e3, s_status);
+            st_exps[2] = s_d.e3;
+            s_d.bn_e = s_d.e3;
+        }
+        __syncthreads();
+    }
+    if (bn.bias) {
+        LayerDyn d = s_d;
+        float v[3] = {0.f, 0.f, 0.f};
+        for (int i = tid; i < n; i += STEP_THREADS) {
+            const int c = i % H;
+            const int32_t t = bn_chain<3>(bn, d, hsrc[i], c);
+            const float ft = tofloat(t, bn.scale ? d.e3 : d.e2), fb = tofloat(bn.bias[c], bn.be);
+            v[0] = fmaxf(v[0], fabsf(__fadd_rn(ft, fb)));
+            v[1] = fmaxf(v[1], fabsf(ft));
+            v[2] = fmaxf(v[2], fabsf(fb));
+        }
+        step_wg_max<3, STEP_WAVES>(v, s_red);
+        if (tid == 0) {
+            const uint32_t m3[3] = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2])};
+            s_d.bn4 = finalize_add_cb(m3, bn.scale ? s_d.e3 : s_d.e2, bn.be, bn.b4, s_status);
+            st_exps[3] = s_d.bn4.eo;
+            s_d.bn_e = s_d.bn4.eo;
+        }
+        __syncthreads();
+    }
+}
+
 // STEP_THREADS: 512 when the groups are at most one per CU (eight waves shorten one group's chain of stages); 256 or 128
 // when there are more groups than CUs and several fit a CU (the kernel needs up to 256 registers per lane, so a CU holds
 // eight waves of it: one, two or four workgroups)
@@ -265,6 +350,19 @@ int step_threads(int G, size_t smem)
     return 128;
 }
 
+// One launch of G workgroups with `smem` bytes of dynamic LDS each, on the instantiation step_threads chooses.  What the step,
+// the ragged step and the clip entries share behind their argument checks.
+template <class Args>
+int step_launch(int G, size_t smem, const Args &a, void (*k512)(Args), void (*k256)(Args), void (*k128)(Args), void *stream)
+{
+    const int threads = step_threads(G, smem);
+    void (*kernel)(Args) = threads == 512 ? k512 : (threads == 256 ? k256 : k128);
+    if (smem > 65536)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)G), dim3((unsigned)threads), smem, S(stream), a);
+    return launch_rc();
+}
+
 int step_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int G, int B, int L, void *y, const int32_t *state_in,
                int32_t *state_out, int32_t *status, void *stream, bool f32)
 {
@@ -273,16 +371,7 @@ int step_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int G
     StepArgs a{};
     a.sp = m->fast->step; a.x = x; a.y = y; a.state_in = state_in; a.state_out = state_out; a.status = status;
     a.B = B; a.L = L; a.x_bits = x_bits; a.x_exp = x_exp; a.f32 = f32 ? 1 : 0;
-    auto launch = [&](auto kernel, unsigned threads) {
-        if (smem > 65536)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(kernel, dim3((unsigned)G), dim3(threads), smem, S(stream), a);
-    };
-    const int threads = step_threads(G, smem);
-    if (threads == 512) launch(k_model_step<512>, 512);
-    else if (threads == 256) launch(k_model_step<256>, 256);
-    else launch(k_model_step<128>, 128);
-    return launch_rc();
+    return step_launch(G, smem, a, k_model_step<512>, k_model_step<256>, k_model_step<128>, stream);
 }
 
 // The ragged form: the same checks at (B, Lmax), the dynamic LDS of B * Lmax rows, the same rule on n for the workgroup size.
@@ -295,16 +384,7 @@ int step_ragged_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp
     StepRaggedArgs a{};
     a.sp = m->fast->step; a.x = x; a.y = y; a.desc = desc; a.state = state; a.status = status;
     a.B = B; a.Lmax = Lmax; a.x_bits = x_bits; a.x_exp = x_exp; a.f32 = f32 ? 1 : 0;
-    auto launch = [&](auto kernel, unsigned threads) {
-        if (smem > 65536)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(threads), smem, S(stream), a);
-    };
-    const int threads = step_threads(n, smem);
-    if (threads == 512) launch(k_model_step_ragged<512>, 512);
-    else if (threads == 256) launch(k_model_step_ragged<256>, 256);
-    else launch(k_model_step_ragged<128>, 128);
-    return launch_rc();
+    return step_launch(n, smem, a, k_model_step_ragged<512>, k_model_step_ragged<256>, k_model_step_ragged<128>, stream);
 }
 
 } // namespace

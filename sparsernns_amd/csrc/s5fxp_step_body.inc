@@ -4,7 +4,8 @@
 //                  a.desc[e]; x and y are padded to Lmax frames per sequence, so row b * L + t of the group is frame t of
 //                  sequence b there.  Only the input staging and the decoder's stores see that; the LDS regions are laid out
 //                  for the entry's own R = B * L.
-// The two share every line that computes, so they cannot drift.
+// The two share every line that computes, so they cannot drift.  The clip kernel (s5fxp_clip.hpp) holds a copy of these
+// stages over tiles, except step_bn_exps (s5fxp_step.hpp), which both call: a change to any other stage is made in both.
     constexpr int STEP_WAVES = STEP_THREADS / 64;
     extern __shared__ __attribute__((aligned(16))) int8_t step_smem[];
     __shared__ int32_t s_status[128]; // S5FXP_STATUS_WORDS: built here, stored once at the end
@@ -121,78 +122,8 @@
         if (tid < 8) s_lut[tid] = sl.lut[tid];
         if (tid == 0) s_wide = 0;
 
-        // ---- the four BatchNorm compute_best exponents (fxpmodel.py:892-933): full reductions over the R x H values,
-        // the rule of k_bn_reduce / k_bn_finalize
-        {
-            float v[3] = {0.f, 0.f, 0.f};
-            for (int i = tid; i < R * H; i += STEP_THREADS) {
-                const int c = i % H;
-                const float fx = tofloat(hb[i], he), fm = tofloat(bn.mm[c], bn.me);
-                v[0] = fmaxf(v[0], fabsf(__fadd_rn(fx, fm)));
-                v[1] = fmaxf(v[1], fabsf(fx));
-                v[2] = fmaxf(v[2], fabsf(fm));
-            }
-            step_wg_max<3, STEP_WAVES>(v, s_red);
-            if (tid == 0) {
-                const uint32_t m3[3] = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2])};
-                s_d.bn1 = finalize_add_cb(m3, he, bn.me, bn.b1, s_status);
-                st_exps[0] = s_d.bn1.eo;
-                s_d.bn_e = s_d.bn1.eo;
-            }
-            __syncthreads();
-        }
-        {
-            LayerDyn d = s_d;
-            float v[1] = {0.f};
-            for (int i = tid; i < R * H; i += STEP_THREADS) {
-                const int c = i % H;
-                const int32_t t = bn_chain<1>(bn, d, hb[i], c);
-                v[0] = fmaxf(v[0], fabsf(__fmul_rn(tofloat(t, d.bn1.eo), tofloat(bn.isv[c], bn.ie))));
-            }
-            step_wg_max<1, STEP_WAVES>(v, s_red);
-            if (tid == 0) {
-                finalize_mul_cb(__float_as_uint(v[0]), s_d.bn1.eo, bn.ie, bn.b2, s_d.rs2, s_d.e2, s_status);
-                st_exps[1] = s_d.e2;
-                s_d.bn_e = s_d.e2;
-            }
-            __syncthreads();
-        }
-        if (bn.scale) {
-            LayerDyn d = s_d;
-            float v[1] = {0.f};
-            for (int i = tid; i < R * H; i += STEP_THREADS) {
-                const int c = i % H;
-                const int32_t t = bn_chain<2>(bn, d, hb[i], c);
-                v[0] = fmaxf(v[0], fabsf(__fmul_rn(tofloat(t, d.e2), tofloat(bn.scale[c], bn.se))));
-            }
-            step_wg_max<1, STEP_WAVES>(v, s_red);
-            if (tid == 0) {
-                finalize_mul_cb(__float_as_uint(v[0]), s_d.e2, bn.se, bn.b3, s_d.rs3, s_d.e3, s_status);
-                st_exps[2] = s_d.e3;
-                s_d.bn_e = s_d.e3;
-            }
-            __syncthreads();
-        }
-        if (bn.bias) {
-            LayerDyn d = s_d;
-            float v[3] = {0.f, 0.f, 0.f};
-            for (int i = tid; i < R * H; i += STEP_THREADS) {
-                const int c = i % H;
-                const int32_t t = bn_chain<3>(bn, d, hb[i], c);
-                const float ft = tofloat(t, bn.scale ? d.e3 : d.e2), fb = tofloat(bn.bias[c], bn.be);
-                v[0] = fmaxf(v[0], fabsf(__fadd_rn(ft, fb)));
-                v[1] = fmaxf(v[1], fabsf(ft));
-                v[2] = fmaxf(v[2], fabsf(fb));
-            }
-            step_wg_max<3, STEP_WAVES>(v, s_red);
-            if (tid == 0) {
-                const uint32_t m3[3] = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2])};
-                s_d.bn4 = finalize_add_cb(m3, bn.scale ? s_d.e3 : s_d.e2, bn.be, bn.b4, s_status);
-                st_exps[3] = s_d.bn4.eo;
-                s_d.bn_e = s_d.bn4.eo;
-            }
-            __syncthreads();
-        }
+        // ---- the four BatchNorm compute_best exponents over the R x H values of h: the stage the clip kernel shares
+        step_bn_exps<STEP_THREADS>(hb, R * H, H, bn, he, s_d, s_status, st_exps, s_red);
         const LayerDyn d = s_d;
 
         // ---- u = change_cfg(BatchNorm(x)) -> byte planes (fxpmodel.py:620-624)

@@ -379,6 +379,40 @@ def test_float_entry_and_carry_hand_over(ds):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# 8. up to one tile the clip kernel and the step kernel are the same stages
+# ------------------------------------------------------------------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("ds", (0.25, 1.0))
+def test_one_tile_equals_the_step_kernel(ds):
+    """The clip kernel is the step body's stages over tiles (one of them a shared function, the others a copy of the text);
+    a clip of at most 32 frames is one tile, so Engine.clips and Engine.step(B=1, L=len, groups=1) on the same rows and
+    carry must agree in every bit: y, the carry out and all 128 status words but word 2, the path code.  No oracle: one
+    kernel is the other's reference, which is what keeps the two copies from drifting."""
+    import torch
+    from sparsernns_amd import _lib
+    model, qc, dims, cm = _synth(ds)
+    eng = model.engine()
+    lens = (1, 7, 32)
+    parts = [_fx(qc, dims, L, seed=800 + L) for L in lens]
+    clips, bits, exp = [p[0] for p in parts], parts[0][1], parts[0][2]
+    rng = np.random.Generator(np.random.PCG64(14))
+    states = rng.integers(-3000, 3000, (len(lens), dims["n_layers"], 2, dims["P"]), dtype=np.int64).astype(np.int32)
+    assert states.any(axis=(1, 2, 3)).all()
+    y, sout, st = _launch(eng, _pad(clips, 32), lens, bits, exp, states)
+    assert (st[:, 2] == _lib.PATH_CLIP).all()
+    for e, (L, clip) in enumerate(zip(lens, clips)):
+        carry = torch.from_numpy(states[e][None, :, :, None, :].copy()).cuda()   # (1, nl, 2, B = 1, P), replaced in place
+        ys = eng.step(torch.from_numpy(np.ascontiguousarray(clip[None, None])).cuda(), carry, None, 1, L, 1, bits, exp, lane=1)
+        torch.cuda.synchronize()
+        sts = eng.lane_status(1, 1).cpu().numpy()[:_lib.STATUS_WORDS].copy()
+        assert sts[2] == _lib.PATH_STEP, (ds, L, sts[:8])
+        assert np.array_equal(ys.cpu().numpy()[0, 0], y[e, :L]), (ds, L, "y")
+        assert np.array_equal(carry.cpu().numpy()[0, :, :, 0], sout[e]), (ds, L, "carry")
+        keep = np.arange(_lib.STATUS_WORDS) != 2
+        assert np.array_equal(sts[keep], st[e][keep]), (ds, L, sts[:32], st[e][:32])
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # arguments on a real handle
 # ------------------------------------------------------------------------------------------------------------------
 @gpu

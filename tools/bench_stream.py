@@ -189,6 +189,7 @@ def merge(args) -> int:
     first = json.load(open(new[0]))
     rec["steps"], rec["device"] = first["steps"], first.get("device")
     pd, ph = pool(par, "baseline_device_us"), pool(par, "baseline_host_us")
+    ps = pool(par, "step_device_us")   # a parent that has the step kernel too: its step against this tree's
     fields = ("baseline_device_us", "baseline_host_us", "step_device_us", "step_host_us", "step_sync_host_us")
     mine = {f: pool(new, f) for f in fields}
     ok = True
@@ -201,6 +202,11 @@ def merge(args) -> int:
         s["host_ratio_parent_over_step"] = s["parent_host_us"]["median"] / s["new_tree_step_host_us"]["median"]
         s["meets_half"] = s["new_tree_step_device_us"]["median"] <= 0.5 * s["parent_device_us"]["median"]
         ok = ok and s["meets_half"] and s["outputs_equal"]
+        if k in ps:   # no slower than the parent's step: its median plus its own spread (max - min) in the same call
+            p = s["parent_step_device_us"] = _stats(ps[k])
+            s["step_within_parent_spread"] = s["new_tree_step_device_us"]["median"] <= p["median"] + (p["max"] - p["min"])
+            print(f"[bench_stream] {k}: parent's step {p['median']:.1f} ({p['min']:.1f}-{p['max']:.1f}) us, this tree's "
+                  f"{s['new_tree_step_device_us']['median']:.1f} us: {'within' if s['step_within_parent_spread'] else 'BEYOND'} the parent's spread")
         rec["shapes"][k] = s
         print(f"[bench_stream] {k}: parent {s['parent_device_us']['median']:.1f} us, step {s['new_tree_step_device_us']['median']:.1f} us "
               f"(x{s['device_ratio_parent_over_step']:.1f}); host {s['parent_host_us']['median']:.0f} -> {s['new_tree_step_host_us']['median']:.0f} us")

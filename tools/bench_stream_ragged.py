@@ -251,13 +251,40 @@ def bench_mixed(audio, model, args, b32):
     return res
 
 
+def merge(args) -> int:
+    """Two trees alternating in one GPU call: per shape the device time of arm b (the ragged step and audio kernels), and of the
+    mixed tick d, repetitions pooled per tree; the new tree is within the bar when its median <= the parent's + (max - min)."""
+    new, par = [json.load(open(f)) for f in args.new.split(",")], [json.load(open(f)) for f in args.parent.split(",")]
+    rec = dict(tool="tools/bench_stream_ragged.py", commit=args.commit, parent_commit=args.parent_commit, unit="us per tick",
+               order="parent tree and new tree alternating in one GPU call; repetitions pooled per tree", device=new[0].get("device"),
+               steps=new[0]["steps"], shapes={})
+    rows = [(k, lambda r, k=k: r["shapes"][k]["b_device_us"]["reps"]) for k in new[0]["shapes"]]
+    rows.append(("mixed_d", lambda r: r["mixed"]["d_device_us"]["reps"]))
+    for k, get in rows:
+        p, n = _stats([v for r in par for v in get(r)]), _stats([v for r in new for v in get(r)])
+        ok = n["median"] <= p["median"] + (p["max"] - p["min"])
+        rec["shapes"][k] = dict(parent_device_us=p, new_tree_device_us=n, within_parent_spread=ok)
+        print(f"[bench_stream_ragged] {k}: parent {p['median']:.1f} ({p['min']:.1f}-{p['max']:.1f}) us, this tree {n['median']:.1f} "
+              f"({n['min']:.1f}-{n['max']:.1f}) us: {'within' if ok else 'BEYOND'} the parent's spread")
+    with open(args.merge, "w") as f:
+        json.dump(rec, f, indent=1)
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--shapes", default=None, help="subset, e.g. 0.5:32:1,1.0:256:1")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--merge", default=None, help="OUT.json: pool arm b (and the mixed tick d) of --new and --parent runs of two trees")
+    ap.add_argument("--new", default="")
+    ap.add_argument("--parent", default="")
+    ap.add_argument("--commit", default=None)
+    ap.add_argument("--parent-commit", default=None)
     args = ap.parse_args()
+    if args.merge:
+        return merge(args)
     if args.steps < 200 or args.reps < 7:
         print("[bench_stream_ragged] note: fewer than 200 steps or 7 repetitions is a rehearsal, not a measurement", flush=True)
 
