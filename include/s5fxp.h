@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define S5FXP_VERSION 114
+#define S5FXP_VERSION 115
 
 enum {
     S5FXP_OK = 0,
@@ -609,6 +609,66 @@ int s5fxp_model_recurrence_kernel(const s5fxp_model *m, int layer);
  * a default (not DEFER_REDO) forward on the fused path checks min(that, 32767), the reach of its 16-bit state planes.
  * 0: no bound (generic 32-bit recurrence), -1: bad argument. */
 int s5fxp_model_recurrence_xmax(const s5fxp_model *m, int layer);
+
+/* ------------------------------------------------------------------------------------------
+ * The FLOAT model, whole: the forward every integer path approximates and is calibrated from (the reference's float
+ * S5 model with prenorm BatchNorm on running statistics, relufication, GLU "half1": sparseRNNs/model/layers.py:181-243,
+ * model/ssm.py:84-185).  float32 throughout; the scan is s5fxp_assoc_scan_c64, the four kernels around it contract on the
+ * exact f32 MFMA (csrc/float_model.hpp).  2 + 3 * n_layers launches.  Results agree with a float64 evaluation to float32
+ * rounding (tests/test_float_model.py states the bounds), not bit for bit with any other float32 implementation.
+ *
+ * Parameters are HOST pointers, as in s5fxp_model_desc; s5fxp_float_model_create packs them into the caller's device blob:
+ * every tensor on a 256-byte boundary, the encoder kernel as (260,H) with rows 257..259 zero (K padded to the MFMA's k = 4),
+ * the decoder kernel as (H,272) with columns 257..271 zero, inv_std = 1 / sqrtf(var + 1e-5f), B_bar as (H,2P) and C as (2P,H)
+ * with re / im interleaved along P (the im rows of C negated), scale = 1 and bias = 0 where the model has none.
+ * Served: d_in = d_out = 257 and (H, P) = (48, 32), (96, 64), (144, 96), (192, 128); anything else S5FXP_EUNSUPPORTED. */
+typedef struct {
+    const float *mean, *var;     /* (H) BatchNorm running statistics */
+    const float *scale, *bias;   /* (H) or NULL */
+    const float *lambda_bar;     /* (P) complex64, re / im interleaved: the discretised diagonal */
+    const float *B_bar;          /* (P,H) complex64 */
+    const float *C;              /* (H,P) complex64 */
+    const float *D;              /* (H) */
+    const float *w2, *b2;        /* out2: (H,H) kernel, (H) bias */
+} s5fxp_float_layer_desc;
+
+typedef struct {
+    int32_t n_layers, d_in, H, P, d_out;
+    const float *enc_w, *enc_b;  /* (d_in,H), (H) */
+    const s5fxp_float_layer_desc *layers;
+    const float *dec_w, *dec_b;  /* (H,d_out), (d_out) */
+} s5fxp_float_model_desc;
+
+typedef struct s5fxp_float_model s5fxp_float_model; /* opaque host handle */
+
+/* Bytes of the packed blob; 0 for a description s5fxp_float_model_create refuses. */
+size_t s5fxp_float_model_blob_bytes(const s5fxp_float_model_desc *desc);
+/* The blob exactly as s5fxp_float_model_create uploads it, written to HOST memory (never touches the device). */
+int s5fxp_float_model_pack(const s5fxp_float_model_desc *desc, void *host_blob, size_t blob_bytes);
+/* S5FXP_EBADARG for a null or non-positive field, S5FXP_EUNSUPPORTED for a shape outside the list above, S5FXP_EWORKSPACE
+ * for a blob that is too small -- all before the device is touched. */
+int s5fxp_float_model_create(const s5fxp_float_model_desc *desc, void *dev_blob, size_t blob_bytes, void *stream,
+                             s5fxp_float_model **out);
+void s5fxp_float_model_destroy(s5fxp_float_model *m);
+
+/* Device workspace of one forward: two (N,H) planes for the layer input and output and the (N,P) complex64 planes Bu and xs,
+ * N = B * L -- one pair shared by all layers, or with trace != 0 one pair per layer, kept: floats
+ * [2 N H][layer 0: Bu, xs][layer 1: ...].  0: bad argument. */
+size_t s5fxp_float_workspace_bytes(const s5fxp_float_model *m, int B, int L, int trace);
+/* Bytes of the trace buffer: per layer five (N,H) float32 planes u, y, g_in, g, h' (the layer's output), layer after layer. */
+size_t s5fxp_float_trace_bytes(const s5fxp_float_model *m, int B, int L);
+
+/* x: (B,L,257) float32 device; y: (B,L,257) float32 device.
+ * stats: NULL, or 4 + 10 * n_layers float32 in device memory, the absmax observers in the key order of the reference's
+ * calibration run: encoder.inp, encoder.out, per layer u, Bu_re, Bu_im, x_re, x_im (raw states), y, out2.inp, out2.out,
+ * gate.l, gate.r, then decoder.inp, decoder.out.  The entry only ever RAISES the array (one atomic max per observer and
+ * workgroup, on the value's bits): zero it before the first batch and stream a calibration set through.  A NaN in a plane
+ * reaches its observer as NaN.
+ * trace: NULL, or s5fxp_float_trace_bytes of device memory that receives every intermediate plane; Bu and xs of every layer
+ * are then left in the workspace.  y and stats are bit-identical with and without it.
+ * S5FXP_EBADARG for a null model / x / y / workspace or B, L < 1; S5FXP_EWORKSPACE for a workspace that is too small. */
+int s5fxp_float_model_forward(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats, float *trace,
+                              void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

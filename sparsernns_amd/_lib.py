@@ -87,6 +87,19 @@ class PushDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("slot", "rows", "flags", "hops", "h4")] + [("reserved", C.c_int32 * 3)]
 
 
+F32P = C.POINTER(C.c_float)
+
+
+class FloatLayerDesc(C.Structure):
+    """s5fxp_float_layer_desc: host pointers to one layer's float parameters."""
+    _fields_ = [(n, F32P) for n in ("mean", "var", "scale", "bias", "lambda_bar", "B_bar", "C", "D", "w2", "b2")]
+
+
+class FloatModelDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_layers", "d_in", "H", "P", "d_out")] + [
+        ("enc_w", F32P), ("enc_b", F32P), ("layers", C.POINTER(FloatLayerDesc)), ("dec_w", F32P), ("dec_b", F32P)]
+
+
 class S5FxpError(RuntimeError):
     pass
 
@@ -160,6 +173,13 @@ def _load():
         "s5fxp_model_clips_f32": (i, [p, p, i, i, i, i, p, p, p, p, p, C.c_size_t, p, p]),
         "s5fxp_stream_stft_ragged": (i, [p, i, i, p, C.c_float, p, i, p, p]),
         "s5fxp_stream_mask_istft_ragged": (i, [p, i, i, p, p, i, p, p, p]),
+        "s5fxp_float_model_blob_bytes": (C.c_size_t, [C.POINTER(FloatModelDesc)]),
+        "s5fxp_float_model_pack": (i, [C.POINTER(FloatModelDesc), p, C.c_size_t]),
+        "s5fxp_float_model_create": (i, [C.POINTER(FloatModelDesc), p, C.c_size_t, p, C.POINTER(p)]),
+        "s5fxp_float_model_destroy": (None, [p]),
+        "s5fxp_float_workspace_bytes": (C.c_size_t, [p, i, i, i]),
+        "s5fxp_float_trace_bytes": (C.c_size_t, [p, i, i]),
+        "s5fxp_float_model_forward": (i, [p, p, i, i, p, p, p, p, C.c_size_t, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale: rebuild
@@ -179,7 +199,9 @@ EXPORTED_SYMBOLS = ("s5fxp_version s5fxp_strerror s5fxp_from_fp s5fxp_to_float s
                     "s5fxp_push_desc_check s5fxp_model_step_ragged s5fxp_model_step_ragged_f32 s5fxp_stream_stft_ragged "
                     "s5fxp_stream_mask_istft_ragged "
                     "s5fxp_clips_workspace_bytes s5fxp_model_clips_ok s5fxp_model_clips s5fxp_model_clips_f32 "
-                    "s5fxp_stft_mag_clips s5fxp_mask_istft_clips s5fxp_score_clips_workspace_bytes s5fxp_mask_istft_score_clips").split()
+                    "s5fxp_stft_mag_clips s5fxp_mask_istft_clips s5fxp_score_clips_workspace_bytes s5fxp_mask_istft_score_clips "
+                    "s5fxp_float_model_blob_bytes s5fxp_float_model_pack s5fxp_float_model_create s5fxp_float_model_destroy "
+                    "s5fxp_float_workspace_bytes s5fxp_float_trace_bytes s5fxp_float_model_forward").split()
 
 
 def check(rc: int, what: str = "") -> None:

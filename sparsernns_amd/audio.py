@@ -498,6 +498,21 @@ def validate_fused(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, clea
     return score_fused(noisy, clean, mask, lam)[:2]
 
 
+def denoise_float(float_engine, noisy: torch.Tensor):
+    """``denoise_fused`` with the FLOAT model (``floatmodel.FloatEngine``) in the middle: stft_mag -> FloatEngine.forward ->
+    mask_istft -> (cleaned audio, cleaned magnitude, x, mask).  What the fixed-point loop approximates, on the same clips."""
+    x = stft_mag(noisy)
+    mask = float_engine.forward(x)
+    cleaned, cleaned_mag = mask_istft(noisy, mask, cleaned_mag=True)
+    return cleaned, cleaned_mag, x, mask
+
+
+def validate_float(float_engine, noisy: torch.Tensor, clean: torch.Tensor, lam: float = 0.001):
+    """``validate_fused`` with the FLOAT model: stft_mag -> FloatEngine.forward -> score_fused -> (loss, si_snr), one value per
+    sequence.  The difference to ``validate_fused`` on the same clips is the cost of quantisation in dB."""
+    return score_fused(noisy, clean, float_engine.forward(stft_mag(noisy)), lam)[:2]
+
+
 def score_clips(noisy: torch.Tensor, clean: torch.Tensor, samples: torch.Tensor, mask, lam: float = 0.001, cleaned: bool = False,
                 cleaned_mag: bool = False, out=None):
     """``score_fused`` for n clips of different lengths in TWO launches whatever n (csrc/audio_score.hpp:

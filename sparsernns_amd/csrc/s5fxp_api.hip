@@ -9,6 +9,7 @@
 #include "audio_stft.hpp"
 #include "audio_stream.hpp"
 #include "audio_score.hpp"
+#include "float_model.hpp"
 
 #include <hip/hip_ext.h>
 
@@ -1264,6 +1265,213 @@ extern "C" int s5fxp_model_live_states(const s5fxp_model *m, int layer)
 extern "C" int s5fxp_model_layer_out_bits(const s5fxp_model *m, int layer)
 {
     return m && layer >= 0 && layer < m->n_layers ? m->layers[layer].res_bits : -1;
+}
+
+// -----------------------------------------------------------------------------------------------
+// the float model (float_model.hpp)
+// -----------------------------------------------------------------------------------------------
+struct s5fxp_float_model {
+    int n_layers = 0, H = 0, P = 0, DS = 0;
+    const float *enc_w = nullptr, *enc_b = nullptr, *dec_w = nullptr, *dec_b = nullptr;
+    struct Layer {
+        FNormArgs nm{};
+        const float *lam = nullptr, *bcat = nullptr, *ccat = nullptr, *D = nullptr, *w2 = nullptr, *b2 = nullptr;
+    };
+    std::vector<Layer> layers;
+};
+
+namespace {
+
+int float_validate(const s5fxp_float_model_desc *d)
+{
+    if (!d || d->n_layers < 1 || d->n_layers > 64 || !d->layers || !d->enc_w || !d->enc_b || !d->dec_w || !d->dec_b) return S5FXP_EBADARG;
+    if (d->d_in < 1 || d->d_out < 1 || d->H < 1 || d->P < 1) return S5FXP_EBADARG;
+    for (int i = 0; i < d->n_layers; ++i) {
+        const s5fxp_float_layer_desc &l = d->layers[i];
+        if (!l.mean || !l.var || !l.lambda_bar || !l.B_bar || !l.C || !l.D || !l.w2 || !l.b2) return S5FXP_EBADARG;
+    }
+    const int DS = d->H / 48;
+    if (d->d_in != FM_DIN || d->d_out != FM_DIN || DS < 1 || DS > 4 || d->H != 48 * DS || d->P != 32 * DS) return S5FXP_EUNSUPPORTED;
+    return S5FXP_OK;
+}
+
+// One pass lays the blob out (host == nullptr: sizes only).  Every tensor starts on a 256-byte boundary; pads are zero.
+struct FloatPacker {
+    size_t off = 0; // in floats
+    float *host = nullptr;
+    const float *dev = nullptr;
+    float *take(size_t n, const float *&d)
+    {
+        float *h = host ? host + off : nullptr;
+        d = dev + off;
+        off = (off + n + 63) & ~(size_t)63;
+        return h;
+    }
+};
+
+size_t float_pack(const s5fxp_float_model_desc *d, FloatPacker &p, s5fxp_float_model *m)
+{
+    const int H = d->H, P = d->P;
+    s5fxp_float_model tmp;
+    s5fxp_float_model &o = m ? *m : tmp;
+    o.layers.resize(d->n_layers);
+    if (float *w = p.take((size_t)FM_KENC * H, o.enc_w)) std::memcpy(w, d->enc_w, (size_t)FM_DIN * H * sizeof(float));
+    if (float *b = p.take(H, o.enc_b)) std::memcpy(b, d->enc_b, H * sizeof(float));
+    for (int i = 0; i < d->n_layers; ++i) {
+        const s5fxp_float_layer_desc &l = d->layers[i];
+        s5fxp_float_model::Layer &L = o.layers[i];
+        if (float *v = p.take(H, L.nm.mean)) std::memcpy(v, l.mean, H * sizeof(float));
+        if (float *v = p.take(H, L.nm.istd))
+            for (int h = 0; h < H; ++h) v[h] = 1.0f / sqrtf(l.var[h] + 1e-5f);
+        if (float *v = p.take(H, L.nm.scale))
+            for (int h = 0; h < H; ++h) v[h] = l.scale ? l.scale[h] : 1.0f;
+        if (float *v = p.take(H, L.nm.bias))
+            for (int h = 0; h < H; ++h) v[h] = l.bias ? l.bias[h] : 0.0f;
+        if (float *v = p.take(2 * P, L.lam)) std::memcpy(v, l.lambda_bar, 2 * P * sizeof(float));
+        if (float *v = p.take((size_t)H * 2 * P, L.bcat)) // (H,2P): [h][2p + c] = B_bar[p][h].c
+            for (int q = 0; q < P; ++q)
+                for (int h = 0; h < H; ++h)
+                    for (int c = 0; c < 2; ++c) v[(size_t)h * 2 * P + 2 * q + c] = l.B_bar[((size_t)q * H + h) * 2 + c];
+        if (float *v = p.take((size_t)2 * P * H, L.ccat)) // (2P,H): [2p][h] = C_re[h][p], [2p+1][h] = -C_im[h][p]
+            for (int h = 0; h < H; ++h)
+                for (int q = 0; q < P; ++q) {
+                    v[(size_t)(2 * q) * H + h] = l.C[((size_t)h * P + q) * 2];
+                    v[(size_t)(2 * q + 1) * H + h] = -l.C[((size_t)h * P + q) * 2 + 1];
+                }
+        if (float *v = p.take(H, L.D)) std::memcpy(v, l.D, H * sizeof(float));
+        if (float *v = p.take((size_t)H * H, L.w2)) std::memcpy(v, l.w2, (size_t)H * H * sizeof(float));
+        if (float *v = p.take(H, L.b2)) std::memcpy(v, l.b2, H * sizeof(float));
+    }
+    if (float *w = p.take((size_t)H * FM_MDEC, o.dec_w))
+        for (int h = 0; h < H; ++h) std::memcpy(w + (size_t)h * FM_MDEC, d->dec_w + (size_t)h * FM_DIN, FM_DIN * sizeof(float));
+    if (float *b = p.take(FM_MDEC, o.dec_b)) std::memcpy(b, d->dec_b, FM_DIN * sizeof(float));
+    return p.off * sizeof(float);
+}
+
+constexpr long long FM_GRID_CAP = 512; // workgroups per launch: the weights are loaded into registers once per workgroup
+
+#define S5_DISPATCH_DS(ds, KERNEL, grid, stream, args)                                                \
+    do {                                                                                              \
+        if ((ds) == 1) hipLaunchKernelGGL((KERNEL(1)), dim3(grid), dim3(256), 0, stream, args);       \
+        else if ((ds) == 2) hipLaunchKernelGGL((KERNEL(2)), dim3(grid), dim3(256), 0, stream, args);  \
+        else if ((ds) == 3) hipLaunchKernelGGL((KERNEL(3)), dim3(grid), dim3(256), 0, stream, args);  \
+        else hipLaunchKernelGGL((KERNEL(4)), dim3(grid), dim3(256), 0, stream, args);                 \
+    } while (0)
+#define S5_K_FENC(ds) k_fenc<ds>
+#define S5_K_FDEC(ds) k_fdec<ds>
+#define S5_K_FBPROJ_T(ds) k_fbproj<ds, true>
+#define S5_K_FBPROJ(ds) k_fbproj<ds, false>
+#define S5_K_FGATE_T(ds) k_fgate<ds, true>
+#define S5_K_FGATE(ds) k_fgate<ds, false>
+
+} // namespace
+
+extern "C" size_t s5fxp_float_model_blob_bytes(const s5fxp_float_model_desc *desc)
+{
+    if (float_validate(desc) != S5FXP_OK) return 0;
+    FloatPacker p;
+    return float_pack(desc, p, nullptr);
+}
+
+extern "C" int s5fxp_float_model_pack(const s5fxp_float_model_desc *desc, void *host_blob, size_t blob_bytes)
+{
+    if (!host_blob) return S5FXP_EBADARG;
+    int rc = float_validate(desc);
+    if (rc) return rc;
+    const size_t need = s5fxp_float_model_blob_bytes(desc);
+    if (blob_bytes < need) return S5FXP_EWORKSPACE;
+    std::memset(host_blob, 0, need);
+    FloatPacker p;
+    p.host = static_cast<float *>(host_blob);
+    p.dev = p.host;
+    float_pack(desc, p, nullptr);
+    return S5FXP_OK;
+}
+
+extern "C" int s5fxp_float_model_create(const s5fxp_float_model_desc *desc, void *dev_blob, size_t blob_bytes, void *stream,
+                                        s5fxp_float_model **out)
+{
+    if (!out || !dev_blob) return S5FXP_EBADARG;
+    *out = nullptr;
+    int rc = float_validate(desc);
+    if (rc) return rc;
+    const size_t need = s5fxp_float_model_blob_bytes(desc);
+    if (blob_bytes < need) return S5FXP_EWORKSPACE;
+    s5fxp_float_model *m = new (std::nothrow) s5fxp_float_model();
+    if (!m) return S5FXP_EBADARG;
+    m->n_layers = desc->n_layers; m->H = desc->H; m->P = desc->P; m->DS = desc->H / 48;
+    std::vector<float> host(need / sizeof(float), 0.0f);
+    FloatPacker p;
+    p.host = host.data();
+    p.dev = static_cast<const float *>(dev_blob);
+    float_pack(desc, p, m);
+    // pageable-memory async copies are staged by the runtime before returning, so `host` may go
+    rc = hip_rc(hipMemcpyAsync(dev_blob, host.data(), need, hipMemcpyHostToDevice, S(stream)));
+    if (!rc) rc = hip_rc(hipStreamSynchronize(S(stream))); // creation is not on the hot path
+    if (rc) {
+        delete m;
+        return rc;
+    }
+    *out = m;
+    return S5FXP_OK;
+}
+
+extern "C" void s5fxp_float_model_destroy(s5fxp_float_model *m) { delete m; }
+
+extern "C" size_t s5fxp_float_workspace_bytes(const s5fxp_float_model *m, int B, int L, int trace)
+{
+    if (!m || B < 1 || L < 1) return 0;
+    const size_t N = (size_t)B * L;
+    return (2 * N * m->H + (size_t)(trace ? m->n_layers : 1) * 2 * N * 2 * m->P) * sizeof(float);
+}
+
+extern "C" size_t s5fxp_float_trace_bytes(const s5fxp_float_model *m, int B, int L)
+{
+    if (!m || B < 1 || L < 1) return 0;
+    return (size_t)m->n_layers * 5 * (size_t)B * L * m->H * sizeof(float);
+}
+
+extern "C" int s5fxp_float_model_forward(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats,
+                                         float *trace, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!m || !x || !y || !workspace || B < 1 || L < 1) return S5FXP_EBADARG;
+    if (workspace_bytes < s5fxp_float_workspace_bytes(m, B, L, trace != nullptr)) return S5FXP_EWORKSPACE;
+    const long long N = (long long)B * L;
+    const size_t NH = (size_t)N * m->H, NP2 = (size_t)N * 2 * m->P;
+    const long long tiles = (N + FM_FT - 1) / FM_FT;
+    const unsigned grid = (unsigned)(tiles < FM_GRID_CAP ? tiles : FM_GRID_CAP);
+    hipStream_t st = S(stream);
+    unsigned *obs = reinterpret_cast<unsigned *>(stats);
+    float *ws = static_cast<float *>(workspace);
+    float *hbuf[2] = {ws, ws + NH};
+    float *planes = ws + 2 * NH; // per layer (trace) or shared: Bu, xs
+    int rc;
+
+    float *h = hbuf[0];
+    FEncArgs ea{x, m->enc_w, m->enc_b, h, obs, N};
+    S5_DISPATCH_DS(m->DS, S5_K_FENC, grid, st, ea);
+    if ((rc = launch_rc())) return rc;
+    for (int i = 0; i < m->n_layers; ++i) {
+        const s5fxp_float_model::Layer &l = m->layers[i];
+        float *bu = planes + (trace ? (size_t)i * 2 * NP2 : 0), *xs = bu + NP2;
+        float *tr = trace ? trace + (size_t)i * 5 * NH : nullptr; // u, y, g_in, g, h'
+        float *hout = trace ? tr + 4 * NH : hbuf[(i + 1) & 1];
+        unsigned *lo = obs ? obs + 2 + 10 * i : nullptr;
+        FBprojArgs ba{h, l.nm, l.bcat, bu, tr, lo, N};
+        if (trace) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_T, grid, st, ba);
+        else S5_DISPATCH_DS(m->DS, S5_K_FBPROJ, grid, st, ba);
+        if ((rc = launch_rc())) return rc;
+        if ((rc = s5fxp_assoc_scan_c64(l.lam, bu, xs, nullptr, nullptr, B, L, m->P, 0, stream))) return rc;
+        FGateArgs ga{xs, h, l.nm, l.ccat, l.D, l.w2, l.b2, hout, tr ? tr + NH : nullptr, tr ? tr + 2 * NH : nullptr,
+                     tr ? tr + 3 * NH : nullptr, lo ? lo + 3 : nullptr, N};
+        if (trace) S5_DISPATCH_DS(m->DS, S5_K_FGATE_T, grid, st, ga);
+        else S5_DISPATCH_DS(m->DS, S5_K_FGATE, grid, st, ga);
+        if ((rc = launch_rc())) return rc;
+        h = hout;
+    }
+    FDecArgs da{h, m->dec_w, m->dec_b, y, obs ? obs + 2 + 10 * m->n_layers : nullptr, N};
+    S5_DISPATCH_DS(m->DS, S5_K_FDEC, grid, st, da);
+    return launch_rc();
 }
 
 #ifdef S5_PHASE_PROF

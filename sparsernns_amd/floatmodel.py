@@ -1,0 +1,242 @@
+"""The FLOAT model on the device: ``synth.float_forward`` (``calibrate_bn=False``) as HIP kernels, with calibration observers.
+
+``FloatEngine`` wraps ``s5fxp_float_model_*`` (include/s5fxp.h, csrc/float_model.hpp): encoder, per layer
+B projection -> ``s5fxp_assoc_scan_c64`` -> gate, decoder -- 2 + 3 * n_layers launches, every contraction on the exact f32
+MFMA.  The 4 + 10 * n_layers absmax observers that ``synth.derive_qconfig`` needs are gathered by the same kernels into one
+device array (``STAT_KEYS`` gives its order), so a calibration set streams through in batches without a host pass.
+
+Results agree with ``synth.float_forward`` to float32 rounding (the summation order differs), not bit for bit.  Without a
+GPU, or for a shape the kernels refuse, ``FloatEngine`` runs ``synth.float_forward`` itself and says so: ``on_device`` is False.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Iterable, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib, synth
+from ._lib import check, lib
+
+F32 = np.float32
+
+
+def stat_keys(n_layers: int) -> List[str]:
+    """The observers in the order ``synth.float_forward`` records them -- the layout of the device array."""
+    keys = ["encoder.inp", "encoder.out"]
+    for i in range(n_layers):
+        keys += [f"l{i}.{k}" for k in ("u", "Bu_re", "Bu_im", "x_re", "x_im", "y", "out2.inp", "out2.out", "gate.l", "gate.r")]
+    return keys + ["decoder.inp", "decoder.out"]
+
+
+STAT_KEYS = stat_keys(3)  # the N-DNS recipe's three layers; stat_keys(n) for any other depth
+TRACE_PLANES = ("u", "y", "g_in", "g", "h_out")  # per layer, (N,H) each: the trace buffer's order
+
+
+def _f32(a) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(a, dtype=F32))
+
+
+def _c64(a) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(a, dtype=np.complex64))
+
+
+class _Desc:
+    """``s5fxp_float_model_desc`` over a modeldict, with the host arrays it points to kept alive."""
+
+    def __init__(self, modeldict: dict, n_layers: int):
+        enc = modeldict["encoder"]
+        self.keep: list = []
+        self.layers = (_lib.FloatLayerDesc * n_layers)()
+        for i in range(n_layers):
+            layer = enc[f"layers_{i}"]
+            nm = layer["norm"]
+            lam_bar, B_bar, Cc = synth.zoh(layer["mixer"])
+            d = self.layers[i]
+            d.mean, d.var = self._p(_f32(nm["mean"])), self._p(_f32(nm["var"]))
+            d.scale = self._p(_f32(nm["scale"])) if "scale" in nm else None
+            d.bias = self._p(_f32(nm["bias"])) if "bias" in nm else None
+            d.lambda_bar, d.B_bar, d.C = self._p(_c64(lam_bar)), self._p(_c64(B_bar)), self._p(_c64(Cc))
+            d.D = self._p(_f32(layer["mixer"]["D"]))
+            d.w2, d.b2 = self._p(_f32(layer["out2"]["kernel"])), self._p(_f32(layer["out2"]["bias"]))
+        ew, dw = _f32(enc["encoder"]["kernel"]), _f32(modeldict["decoder"]["kernel"])
+        P = int(np.asarray(enc["layers_0"]["mixer"]["Lambda_re"]).shape[0])
+        self.d_in, self.H, self.P, self.d_out = int(ew.shape[0]), int(ew.shape[1]), P, int(dw.shape[1])
+        self.desc = _lib.FloatModelDesc(n_layers=n_layers, d_in=self.d_in, H=self.H, P=P, d_out=self.d_out,
+                                        enc_w=self._p(ew), enc_b=self._p(_f32(enc["encoder"]["bias"])), layers=self.layers,
+                                        dec_w=self._p(dw), dec_b=self._p(_f32(modeldict["decoder"]["bias"])))
+
+    def _p(self, arr: np.ndarray):
+        self.keep.append(arr)
+        return arr.view(F32).ctypes.data_as(_lib.F32P)
+
+
+def supported(modeldict: dict, n_layers: int) -> bool:
+    """True when the kernels serve this shape (the four recipe shapes at 257 columns)."""
+    return lib.s5fxp_float_model_blob_bytes(C.byref(_Desc(modeldict, n_layers).desc)) > 0
+
+
+def pack_blob(modeldict: dict, n_layers: int) -> np.ndarray:
+    """The packed parameter blob as ``s5fxp_float_model_create`` uploads it, as host float32 (no GPU needed)."""
+    d = _Desc(modeldict, n_layers)
+    nbytes = lib.s5fxp_float_model_blob_bytes(C.byref(d.desc))
+    if nbytes == 0:
+        raise NotImplementedError(f"the float kernels do not serve d_in={d.d_in} H={d.H} P={d.P} d_out={d.d_out}")
+    blob = np.empty(nbytes // 4, dtype=F32)
+    check(lib.s5fxp_float_model_pack(C.byref(d.desc), blob.ctypes.data, nbytes), "s5fxp_float_model_pack")
+    return blob
+
+
+class FloatEngine:
+    """The float forward of one modeldict.  ``forward`` mirrors ``synth.float_forward`` in keys and dtypes."""
+
+    def __init__(self, modeldict: dict, n_layers: int, device: Optional[torch.device] = None):
+        self.modeldict, self.n_layers = modeldict, int(n_layers)
+        self.keys = stat_keys(self.n_layers)
+        d = _Desc(modeldict, self.n_layers)
+        self.d_in, self.H, self.P, self.d_out = d.d_in, d.H, d.P, d.d_out
+        self._h = None
+        self.on_device = bool(torch.cuda.is_available()) and lib.s5fxp_float_model_blob_bytes(C.byref(d.desc)) > 0
+        if not self.on_device:
+            self.device = torch.device("cpu")
+            return
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        nbytes = lib.s5fxp_float_model_blob_bytes(C.byref(d.desc))
+        self.blob = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+        handle = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(lib.s5fxp_float_model_create(C.byref(d.desc), self.blob.data_ptr(), nbytes,
+                                               torch.cuda.current_stream().cuda_stream, C.byref(handle)), "s5fxp_float_model_create")
+        self._h = handle
+        self._ws: Dict[bool, torch.Tensor] = {}
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib.s5fxp_float_model_destroy(h)
+            self._h = None
+
+    # -- device side ---------------------------------------------------------------------------
+    def new_stats(self) -> torch.Tensor:
+        """A zeroed observer array: 4 + 10 * n_layers float32 on the engine's device."""
+        return torch.zeros(len(self.keys), dtype=torch.float32, device=self.device)
+
+    def stats_dict(self, stats_dev: torch.Tensor) -> Dict[str, float]:
+        return {k: float(v) for k, v in zip(self.keys, stats_dev.cpu().numpy())}
+
+    def _workspace(self, B: int, L: int, trace: bool) -> torch.Tensor:
+        n = lib.s5fxp_float_workspace_bytes(self._h, B, L, int(trace)) // 4
+        ws = self._ws.get(trace)
+        if ws is None or ws.numel() < n:
+            ws = self._ws[trace] = torch.empty(n, dtype=torch.float32, device=self.device)
+        return ws
+
+    def forward_device(self, x: torch.Tensor, stats_dev: Optional[torch.Tensor] = None, trace: bool = False):
+        """x (B,L,257) float32 on the device -> y (B,L,257); ``stats_dev`` (``new_stats``) is raised in place.  With ``trace``
+        also (trace buffer, workspace): the planes of ``forward_traced`` as flat tensors.  Stream-ordered, no sync."""
+        if not self.on_device:
+            raise RuntimeError("FloatEngine.forward_device needs the kernels (on_device is False)")
+        if x.dim() != 3 or x.shape[2] != self.d_in or x.dtype != torch.float32 or x.device != self.device:
+            raise ValueError(f"x must be float32 (B, L, {self.d_in}) on {self.device}, got {x.dtype} {tuple(x.shape)} on {x.device}")
+        if stats_dev is not None and (stats_dev.dtype != torch.float32 or stats_dev.numel() != len(self.keys)
+                                      or stats_dev.device != self.device or not stats_dev.is_contiguous()):
+            raise ValueError(f"stats must be {len(self.keys)} contiguous float32 on {self.device}")
+        x = x.contiguous()
+        B, L = int(x.shape[0]), int(x.shape[1])
+        y = torch.empty(B, L, self.d_out, dtype=torch.float32, device=self.device)
+        ws = self._workspace(B, L, trace)
+        tr = torch.empty(lib.s5fxp_float_trace_bytes(self._h, B, L) // 4, dtype=torch.float32, device=self.device) if trace else None
+        with torch.cuda.device(self.device):
+            check(lib.s5fxp_float_model_forward(self._h, x.data_ptr(), B, L, y.data_ptr(),
+                                                None if stats_dev is None else stats_dev.data_ptr(),
+                                                None if tr is None else tr.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                                torch.cuda.current_stream().cuda_stream), "s5fxp_float_model_forward")
+        return (y, tr, ws) if trace else y
+
+    def forward_traced(self, x) -> dict:
+        """Every plane of one forward, as device tensors: ``h_enc`` (B,L,H), ``out`` (B,L,257), ``stats`` (the observer array
+        of this forward alone) and per layer ``l{i}.u / y / g_in / g / h_out`` (B,L,H) float32 and ``l{i}.Bu / xs`` (B,L,P)
+        complex64 (``xs`` raw, before the complex ReLU)."""
+        xd = self._to_device(x)
+        B, L = int(xd.shape[0]), int(xd.shape[1])
+        st = self.new_stats()
+        y, tr, ws = self.forward_device(xd, st, trace=True)
+        NH, NP2 = B * L * self.H, B * L * 2 * self.P
+        out = dict(out=y, stats=st, h_enc=ws[:NH].view(B, L, self.H).clone())
+        for i in range(self.n_layers):
+            for j, name in enumerate(TRACE_PLANES):
+                out[f"l{i}.{name}"] = tr[(5 * i + j) * NH:(5 * i + j + 1) * NH].view(B, L, self.H)
+            base = 2 * NH + 2 * i * NP2
+            out[f"l{i}.Bu"] = torch.view_as_complex(ws[base:base + NP2].view(B, L, self.P, 2).clone())
+            out[f"l{i}.xs"] = torch.view_as_complex(ws[base + NP2:base + 2 * NP2].view(B, L, self.P, 2).clone())
+        return out
+
+    def _to_device(self, x) -> torch.Tensor:
+        if isinstance(x, torch.Tensor):
+            return x.to(device=self.device, dtype=torch.float32)
+        return torch.from_numpy(_f32(x)).to(self.device)
+
+    # -- the mirror of synth.float_forward -----------------------------------------------------
+    def forward(self, x, stats: Optional[dict] = None, activations: Optional[dict] = None):
+        """x (B,L,257) float32, NumPy array or tensor -> the model's output of the same kind.  ``stats`` is updated by maximum
+        under ``synth.float_forward``'s keys; ``activations`` receives sequence 0 under the reference's keys (``pre_C`` = the
+        rectified states)."""
+        as_tensor = isinstance(x, torch.Tensor)
+        if not self.on_device:
+            xn = x.detach().cpu().numpy().astype(F32) if as_tensor else np.asarray(x, dtype=F32)
+            y = synth.float_forward(self.modeldict, xn, self.n_layers, stats=stats, activations=activations)
+            return torch.from_numpy(y) if as_tensor else y
+        xd = self._to_device(x)
+        if activations is not None:
+            t = self.forward_traced(xd)
+            y, st = t["out"], t["stats"]
+            self._fill_activations(t, activations)
+        else:
+            st = self.new_stats() if stats is not None else None
+            y = self.forward_device(xd, st)
+        if stats is not None:
+            for k, v in self.stats_dict(st).items():
+                stats[k] = max(stats.get(k, 0.0), v)
+        return y.to(x.device) if as_tensor else y.cpu().numpy()
+
+    def _fill_activations(self, t: dict, activations: dict) -> None:
+        from .ssm import complex_relu
+        enc = activations.setdefault("encoder", {})
+        h = t["h_enc"]
+        for i in range(self.n_layers):
+            act = enc.setdefault(f"layers_{i}", {})
+            _, B_bar, _ = synth.zoh(self.modeldict["encoder"][f"layers_{i}"]["mixer"])
+            y, g = t[f"l{i}.y"][0], t[f"l{i}.g"][0]
+            n = lambda v: v.cpu().numpy()
+            act.update(input=n(h[0]), pre_s5=n(t[f"l{i}.u"][0]), pre_C=n(complex_relu(t[f"l{i}.xs"][0])), pre_GLU=n(y),
+                       post_GLU=n(torch.clamp_min(y, 0) * g), __call__=n(t[f"l{i}.h_out"][0]))
+            act["mixer"] = dict(B_bar=B_bar.astype(np.complex64), __call__=n(y))
+            act["out2"] = dict(__call__=n(t[f"l{i}.g_in"][0]))
+            h = t[f"l{i}.h_out"]
+        activations["__call__"] = t["out"][0].cpu().numpy()
+
+
+def calibrate(modeldict: dict, batches: Iterable, n_layers: int, quantization: str = "w8a16",
+              state_headroom_bits: int = 0, engine: Optional[FloatEngine] = None) -> Tuple[dict, dict]:
+    """Streams ``batches`` (each (B,L,257) float32) through the float model and derives the fixed-point configuration from
+    the observers, exactly as ``synth.make_model`` does after its dry run -> (stats, fxp_qconfig).  On a GPU the observers
+    stay in one device array across the batches and are read back once."""
+    eng = engine if engine is not None else FloatEngine(modeldict, n_layers)
+    stats: dict = {}
+    if eng.on_device:
+        st = eng.new_stats()
+        for x in batches:
+            eng.forward_device(eng._to_device(x), st)
+        stats = eng.stats_dict(st)
+    else:
+        for x in batches:
+            eng.forward(x, stats=stats)
+    if not stats:
+        raise ValueError("calibrate needs at least one batch")
+    qc = synth.derive_qconfig(modeldict, stats, n_layers, synth.PRECISIONS[quantization])
+    for k in ("x_re", "x_im"):
+        qc["blocks"]["ssm"]["activations"][k]["exp"] -= state_headroom_bits
+    synth.cap_result_exponents(qc)
+    synth._assert_exps_nonnegative(qc)
+    return stats, qc

@@ -69,7 +69,7 @@ def load_export(npz_path: str, meta_path: str) -> dict:
     return dict(params=params, qconfig=meta["export_qconfig"]), meta
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m sparsernns_amd.fxprun", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     src = ap.add_mutually_exclusive_group(required=True)
@@ -97,11 +97,19 @@ def main(argv=None) -> int:
     ap.add_argument("--verify", action="store_true",
                     help="run_verification: op-by-op forward with store_intermediates, compared with the fused engine and, stage by "
                          "stage, with the float model's activations")
+    ap.add_argument("--float-side", dest="float_side", choices=("numpy", "device"), default="numpy",
+                    help="--verify without --activations: where the float model's intermediates come from: synth.float_forward on "
+                         "the host (numpy) or floatmodel.FloatEngine's HIP kernels (device)")
     ap.add_argument("--export", type=str, default=None, help="write the integer model as PREFIX.npz / PREFIX.json")
     ap.add_argument("--check-golden", action="store_true",
                     help="--model only: the npz also holds an integer input `x` and the output `y` some other implementation "
                          "produced for it (the reference's fxpmodel_io.pkl through tools/reference_pickles_to_npz.py export, or "
                          "tests/golden/*.npz): run x and compare bit for bit")
+    return ap
+
+
+def main(argv=None) -> int:
+    ap = build_parser()
     args = ap.parse_args(argv)
 
     import torch
@@ -195,15 +203,22 @@ def main(argv=None) -> int:
         # ---- fixed point vs float, stage by stage (fxprun.py:553-731, fxpreporter.py)
         from . import fxputils
         from .fxpreporter import Reporter, verification_report
+        float_side = "sparsernns_amd.synth.float_forward"
         if args.activations:
             acts = fxputils.load_tree_npz(args.activations)
         else:
             acts = {}
-            synth.float_forward(md, x[:1], dims["n_layers"], activations=acts)
+            if args.float_side == "device":
+                from .floatmodel import FloatEngine
+                feng = FloatEngine(md, dims["n_layers"])
+                feng.forward(x[:1], activations=acts)
+                float_side = "sparsernns_amd.floatmodel.FloatEngine (" + ("HIP kernels" if feng.on_device else "host fallback") + ")"
+            else:
+                synth.float_forward(md, x[:1], dims["n_layers"], activations=acts)
             if args.write_activations:
                 fxputils.save_tree_npz(args.write_activations, acts)
         rep = Reporter(args.report, header=dict(quantization=args.quantization, batch=B, seq_len=L, input_bits=inp_bits, input_exp=inp_exp,
-                                                float_side=args.activations or "sparsernns_amd.synth.float_forward"))
+                                                float_side=args.activations or float_side))
         verification_report(eager, FxpArray(fx.data[:1], fx.bits, fx.exp), x[0], acts, rep, seq_len=L)
         rep.save()
         w = rep.worst()
