@@ -670,6 +670,27 @@ size_t s5fxp_float_trace_bytes(const s5fxp_float_model *m, int B, int L);
 int s5fxp_float_model_forward(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats, float *trace,
                               void *workspace, size_t workspace_bytes, void *stream);
 
+/* The same forward, which also gathers one HISTOGRAM OVER THE FLOAT32 EXPONENT FIELD per observer.  For a
+ * float32 v with E = (bits(v) >> 23) & 0xff the bin is clamp(E - 87, 0, 63): bin b in 1..62 holds
+ * 2^(b + S5FXP_FLOAT_HIST_EMIN) <= |v| < 2^(b + S5FXP_FLOAT_HIST_EMIN + 1), bin 0 everything below 2^-39 (zero and subnormals
+ * included), bin 63 |v| >= 2^23, infinities and NaN.  So the sum of the bins from k + 40 on is exactly the number of values
+ * with |v| >= 2^k, for -39 <= k <= 23 -- every threshold of a fixed-point configuration is such a power of two.
+ * hist: NULL, or (4 + 10 * n_layers) * S5FXP_FLOAT_HIST_BINS 64-bit counters in device memory, 8-byte aligned, one row per
+ * observer in the order of stats (gate.l has a row of its own, equal to out2.inp's).  A value enters its row exactly where
+ * it enters its observer: rows beyond N and padded columns never do.  The entry only ever ADDS to the array (per workgroup
+ * one 64-bit atomic add for every counter it found non-zero): zero it before the first batch.
+ * With hist == NULL the kernels launched are those of the entry above; y, stats and the trace planes are bit-identical with
+ * and without hist, and the workspace and trace sizes are the same.
+ * Wrap rule: a workgroup counts in 32-bit words of LDS and adds them to hist once, at its end.  It sees at most
+ * ceil(tiles / grid) * 32 rows * 272 values of one observer (tiles = ceil(B L / 32), grid = min(tiles, 512)); a B * L at
+ * which that product reaches 2^32 (B * L above about 8.08e9) is refused with S5FXP_EBADARG when hist is given.
+ * S5FXP_EBADARG also for a hist that is not 8-byte aligned; otherwise the errors of the entry above. */
+#define S5FXP_FLOAT_HIST_BINS 64
+#define S5FXP_FLOAT_HIST_EMIN (-40)
+int s5fxp_float_model_forward_hist(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats,
+                                   unsigned long long *hist, float *trace, void *workspace, size_t workspace_bytes,
+                                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,23 @@
 //
 // TRACE additionally stores the planes nothing downstream reads (u; y, g_in, g).  It changes no arithmetic: outputs and
 // observers are bit-identical in the two modes.
+//
+// HIST (the k_*_hist kernels) additionally counts every value that enters an observer into that observer's
+// histogram over the float32 exponent field: bin = clamp(E - 87, 0, 63), E = (bits >> 23) & 0xff, at the very statement where
+// the value enters the observer, under the same masks.  Counts accumulate in LDS as 32-bit words, FM_HIST_COPIES private
+// copies per workgroup chosen by the lane (a plane really uses two or three bins, so one copy would serialise a wave's
+// 64 atomics on them; with 16 copies laid out [bin][copy] at most four lanes meet on a word and the copies of a bin lie in
+// 16 different banks).  At the end of the kernel the copies are summed in 64 bits and every NON-ZERO sum is added to the
+// global array with one 64-bit atomicAdd.  Wrap rule: a workgroup sees at most ceil(tiles / grid) * 32 rows * 272 values of
+// one observer; the entry refuses (S5FXP_EBADARG) an N at which that reaches 2^32 (fm_hist_rows_ok), so no flush is needed
+// before the end.
+//
+// The four kernels are written once, in float_model_kernels.inc, which this header includes twice: with FM_HIST 0 it gives
+// k_fenc, k_fbproj, k_fgate, k_fdec -- token for token the kernels as they were before the histogram, so their instruction
+// streams do not move -- and with FM_HIST 1 k_fenc_hist, ... with one more argument.  The flag is a preprocessor one and not
+// a template parameter because both alternatives change the existing kernels: a template parameter changes their mangled
+// names (and their kernarg layout, if the argument struct grows), and a shared __device__ body behind thin __global__
+// wrappers compiles to different code than the same text inside the kernel (measured: tools/disasm_compare.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -37,6 +54,59 @@ __device__ inline float fm_relu(float v) { return v < 0.f ? 0.f : v; }
 __device__ inline float fm_bn(float h, float mean, float istd, float sc, float bi)
 {
     return __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(h, mean), istd), sc), bi);
+}
+
+constexpr int FM_HIST_BINS = 64;   // S5FXP_FLOAT_HIST_BINS
+constexpr int FM_HIST_EMIN = -40;  // S5FXP_FLOAT_HIST_EMIN: bin b in 1..62 holds 2^(b + EMIN) <= |v| < 2^(b + EMIN + 1)
+#ifndef S5_FM_HIST_COPIES
+#define S5_FM_HIST_COPIES 16       // -DS5_FM_HIST_COPIES=1 builds the single-copy arm of tools/bench_float_hist.py
+#endif
+constexpr int FM_HIST_COPIES = S5_FM_HIST_COPIES; // a power of two, at most 64
+constexpr int fm_hist_words(int planes) { return planes * FM_HIST_BINS * FM_HIST_COPIES; }
+// the most rows a launch of `grid` workgroups may walk with 32-bit LDS counters
+constexpr bool fm_hist_rows_ok(long long tiles, long long grid)
+{
+    return (tiles + grid - 1) / grid <= 0xffffffffll / (FM_FT * FM_MDEC);
+}
+__device__ inline int fm_hist_bin(float v)
+{
+    const int e = (int)((__float_as_uint(v) >> 23) & 0xffu) - (127 + FM_HIST_EMIN);
+    return e < 0 ? 0 : e > FM_HIST_BINS - 1 ? FM_HIST_BINS - 1 : e;
+}
+// one value into LDS plane `plane` of the workgroup's histograms
+__device__ inline void fm_hist_add(unsigned *sh, int plane, float v)
+{
+    atomicAdd(sh + (plane * FM_HIST_BINS + fm_hist_bin(v)) * FM_HIST_COPIES + (threadIdx.x & (FM_HIST_COPIES - 1)), 1u);
+}
+// the workgroup's histograms: static LDS of the kernels that count, none in the others
+template <int PLANES>
+__device__ inline unsigned *fm_hist_lds()
+{
+    __shared__ unsigned sh[fm_hist_words(PLANES)];
+    return sh;
+}
+template <int PLANES>
+__device__ inline void fm_hist_zero(unsigned *sh)
+{
+    for (int i = threadIdx.x; i < fm_hist_words(PLANES); i += 256) sh[i] = 0u;
+    __syncthreads();
+}
+// LDS plane i goes to row i of `hist`, or to row i + 1 from DUP_ROW on; plane DUP_SRC is added to row DUP_ROW as well
+// (gate.l repeats out2.inp).  Only non-zero sums touch global memory.
+template <int PLANES, int DUP_SRC = -1, int DUP_ROW = -1>
+__device__ inline void fm_hist_flush(const unsigned *sh, unsigned long long *hist)
+{
+    __syncthreads();
+    for (int i = threadIdx.x; i < PLANES * FM_HIST_BINS; i += 256) {
+        unsigned long long n = 0;
+#pragma unroll
+        for (int c = 0; c < FM_HIST_COPIES; ++c) n += sh[i * FM_HIST_COPIES + c];
+        if (n == 0) continue;
+        const int plane = i / FM_HIST_BINS, bin = i - plane * FM_HIST_BINS;
+        const int row = DUP_ROW >= 0 && plane >= DUP_ROW ? plane + 1 : plane;
+        atomicAdd(hist + row * FM_HIST_BINS + bin, n);
+        if (plane == DUP_SRC) atomicAdd(hist + DUP_ROW * FM_HIST_BINS + bin, n);
+    }
 }
 constexpr int fm_lda(int K) { return (K + 31) / 32 * 32 + 4; } // row stride of an LDS tile: 16 rows x 4 k spread over the banks
 
@@ -99,9 +169,7 @@ __device__ inline void fm_obs_flush(const unsigned (&m)[NOBS], unsigned *slots, 
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// encoder: h = relu(x W + b); observers [0] encoder.inp, [1] encoder.out (before the ReLU)
-// ------------------------------------------------------------------------------------------------------------------
+// the kernels' arguments (float_model_kernels.inc says what each kernel computes)
 struct FEncArgs {
     const float *x;  // (N,257)
     const float *w;  // (260,H), rows 257..259 zero
@@ -110,74 +178,6 @@ struct FEncArgs {
     unsigned *stats; // 2 words or NULL
     long long N;
 };
-
-template <int DS>
-__global__ __launch_bounds__(256) void k_fenc(FEncArgs a)
-{
-    constexpr int H = 48 * DS, HT = 3 * DS, NT = (HT + 3) / 4, KS = FM_KENC / 4, LDA = fm_lda(FM_KENC);
-    __shared__ float sx[FM_FT * LDA];
-    __shared__ unsigned sobs[FM_WAVES * 2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float breg[NT][KS];
-    fm_load_w<KS, NT>(breg, a.w, H, HT);
-    float bias[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int t = wave + FM_WAVES * nt;
-        bias[nt] = t < HT ? a.b[t * 16 + (lane & 15)] : 0.f;
-    }
-    unsigned om[2] = {0u, 0u};
-    const long long tiles = (a.N + FM_FT - 1) / FM_FT;
-    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const long long r0 = tile * FM_FT;
-        const int rows = (int)(a.N - r0 < FM_FT ? a.N - r0 : FM_FT);
-        // rows are 257 floats: dword loads, all of a thread's issued before the first is used.  Addresses are clamped into the
-        // tile's valid rows and columns, so no load is conditional; what lies outside is replaced by zero afterwards.
-        const float *src = a.x + (size_t)r0 * FM_DIN;
-        constexpr int PER = (FM_FT * FM_KENC + 255) / 256;
-        float v[PER];
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int i = threadIdx.x + 256 * j, r = i / FM_KENC, c = i - r * FM_KENC;
-            const int rc = r < rows ? r : rows - 1, cc = c < FM_DIN ? c : FM_DIN - 1;
-            v[j] = src[(size_t)rc * FM_DIN + cc];
-        }
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int i = threadIdx.x + 256 * j, r = i / FM_KENC, c = i - r * FM_KENC;
-            if (i >= FM_FT * FM_KENC) continue; // the last round is partial: 8320 = 32.5 x 256
-            const bool ok = r < rows && c < FM_DIN;
-            const float w = ok ? v[j] : 0.f;
-            if (ok) om[0] = fm_umax(om[0], fm_absbits(w));
-            sx[r * LDA + c] = w;
-        }
-        __syncthreads();
-        fm_f32x4 acc[2][NT];
-        fm_mma<KS, NT>(acc, sx, LDA, breg, HT);
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const int t = wave + FM_WAVES * nt;
-                if (t >= HT) continue;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = rt * 16 + (lane >> 4) * 4 + r;
-                    if (row >= rows) continue;
-                    const float v = __fadd_rn(acc[rt][nt][r], bias[nt]);
-                    om[1] = fm_umax(om[1], fm_absbits(v));
-                    a.h[(size_t)(r0 + row) * H + t * 16 + (lane & 15)] = fm_relu(v);
-                }
-            }
-        __syncthreads();
-    }
-    fm_obs_flush<2>(om, sobs, a.stats);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// B projection: u = BatchNorm(h); Bu = u B_bar^T as ONE real product against bcat (H, 2P) whose columns interleave re and
-// im, so the result is the (N,P) complex64 plane the scan takes.  Observers [0] u, [1] Bu_re, [2] Bu_im.
-// ------------------------------------------------------------------------------------------------------------------
 struct FNormArgs {
     const float *mean, *istd, *scale, *bias; // (H) each; scale = 1 / bias = 0 where the model has none (exact)
 };
@@ -190,69 +190,6 @@ struct FBprojArgs {
     unsigned *stats;   // 3 words or NULL
     long long N;
 };
-
-template <int DS, bool TRACE>
-__global__ __launch_bounds__(256) void k_fbproj(FBprojArgs a)
-{
-    constexpr int H = 48 * DS, P2 = 64 * DS, PT = 4 * DS, NT = DS, KS = H / 4, LDA = fm_lda(H);
-    __shared__ float su[FM_FT * LDA];
-    __shared__ float snm[4 * H];
-    __shared__ unsigned sobs[FM_WAVES * 3];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float breg[NT][KS];
-    fm_load_w<KS, NT>(breg, a.bcat, P2, PT);
-    for (int i = threadIdx.x; i < H; i += 256) {
-        snm[i] = a.nm.mean[i]; snm[H + i] = a.nm.istd[i]; snm[2 * H + i] = a.nm.scale[i]; snm[3 * H + i] = a.nm.bias[i];
-    }
-    __syncthreads();
-    unsigned om_u = 0u, om_bu = 0u; // a lane's Bu columns all have the lane's parity: even = re, odd = im
-    const long long tiles = (a.N + FM_FT - 1) / FM_FT;
-    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const long long r0 = tile * FM_FT;
-        const int rows = (int)(a.N - r0 < FM_FT ? a.N - r0 : FM_FT);
-        for (int i = threadIdx.x; i < FM_FT * (H / 4); i += 256) {
-            const int r = i / (H / 4), c = (i - r * (H / 4)) * 4;
-            float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r < rows) {
-                const float4 h = *reinterpret_cast<const float4 *>(a.h + (size_t)(r0 + r) * H + c);
-                u.x = fm_bn(h.x, snm[c], snm[H + c], snm[2 * H + c], snm[3 * H + c]);
-                u.y = fm_bn(h.y, snm[c + 1], snm[H + c + 1], snm[2 * H + c + 1], snm[3 * H + c + 1]);
-                u.z = fm_bn(h.z, snm[c + 2], snm[H + c + 2], snm[2 * H + c + 2], snm[3 * H + c + 2]);
-                u.w = fm_bn(h.w, snm[c + 3], snm[H + c + 3], snm[2 * H + c + 3], snm[3 * H + c + 3]);
-                om_u = fm_umax(fm_umax(fm_umax(om_u, fm_absbits(u.x)), fm_umax(fm_absbits(u.y), fm_absbits(u.z))), fm_absbits(u.w));
-                if (TRACE) *reinterpret_cast<float4 *>(a.u_trace + (size_t)(r0 + r) * H + c) = u;
-            }
-            *reinterpret_cast<float4 *>(su + r * LDA + c) = u;
-        }
-        __syncthreads();
-        fm_f32x4 acc[2][NT];
-        fm_mma<KS, NT>(acc, su, LDA, breg, PT);
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const int t = wave + FM_WAVES * nt; // < PT always: PT = 4 * NT
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = rt * 16 + (lane >> 4) * 4 + r;
-                    if (row >= rows) continue;
-                    const float v = acc[rt][nt][r];
-                    om_bu = fm_umax(om_bu, fm_absbits(v));
-                    a.bu[(size_t)(r0 + row) * P2 + t * 16 + (lane & 15)] = v;
-                }
-            }
-        __syncthreads();
-    }
-    const unsigned om[3] = {om_u, (lane & 1) ? 0u : om_bu, (lane & 1) ? om_bu : 0u};
-    fm_obs_flush<3>(om, sobs, a.stats);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// gate: complex ReLU on the raw states, y = 2 (x_re C_re^T - x_im C_im^T) + D u as ONE real product of the interleaved
-// rectified states against ccat (2P,H) = rows (C_re^T, -C_im^T) interleaved, with u rebuilt from the layer input;
-// x1 = relu(y), g_in = x1 W2 + b2, g = sigmoid(g_in), h' = relu(x1 g + h).
-// Observers [0] x_re, [1] x_im (raw states), [2] y, [3] out2.inp, [4] out2.out, [5] gate.l (= out2.inp), [6] gate.r.
-// ------------------------------------------------------------------------------------------------------------------
 struct FGateArgs {
     const float *xs; // (N,2P) raw states, complex64
     const float *h;  // (N,H) layer input
@@ -266,109 +203,6 @@ struct FGateArgs {
     unsigned *stats;   // 7 words or NULL
     long long N;
 };
-
-template <int DS, bool TRACE>
-__global__ __launch_bounds__(256) void k_fgate(FGateArgs a)
-{
-    constexpr int H = 48 * DS, P = 32 * DS, P2 = 64 * DS, HT = 3 * DS, NT = (HT + 3) / 4, KS1 = P2 / 4, KS2 = H / 4;
-    constexpr int LD1 = fm_lda(P2), LDH = fm_lda(H);
-    __shared__ float sxs[FM_FT * LD1];
-    __shared__ float sh[FM_FT * LDH];
-    __shared__ float sx1[FM_FT * LDH];
-    __shared__ float spar[6 * H]; // mean, istd, scale, bias, D, b2
-    __shared__ unsigned sobs[FM_WAVES * 7];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float bc[NT][KS1], bw[NT][KS2];
-    fm_load_w<KS1, NT>(bc, a.ccat, H, HT);
-    fm_load_w<KS2, NT>(bw, a.w2, H, HT);
-    for (int i = threadIdx.x; i < H; i += 256) {
-        spar[i] = a.nm.mean[i]; spar[H + i] = a.nm.istd[i]; spar[2 * H + i] = a.nm.scale[i]; spar[3 * H + i] = a.nm.bias[i];
-        spar[4 * H + i] = a.D[i]; spar[5 * H + i] = a.b2[i];
-    }
-    __syncthreads();
-    unsigned o_xre = 0u, o_xim = 0u, o_y = 0u, o_x1 = 0u, o_gin = 0u, o_g = 0u;
-    const long long tiles = (a.N + FM_FT - 1) / FM_FT;
-    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const long long r0 = tile * FM_FT;
-        const int rows = (int)(a.N - r0 < FM_FT ? a.N - r0 : FM_FT);
-        for (int i = threadIdx.x; i < FM_FT * P; i += 256) {
-            const int r = i / P, p = i - r * P;
-            float2 v = make_float2(0.f, 0.f);
-            if (r < rows) {
-                v = *reinterpret_cast<const float2 *>(a.xs + (size_t)(r0 + r) * P2 + 2 * p);
-                o_xre = fm_umax(o_xre, fm_absbits(v.x));
-                o_xim = fm_umax(o_xim, fm_absbits(v.y));
-                const bool keep = v.x > 0.f || (v.x == 0.f && v.y > 0.f);
-                if (!keep) v = make_float2(0.f, 0.f);
-            }
-            *reinterpret_cast<float2 *>(sxs + r * LD1 + 2 * p) = v;
-        }
-        for (int i = threadIdx.x; i < FM_FT * (H / 4); i += 256) {
-            const int r = i / (H / 4), c = (i - r * (H / 4)) * 4;
-            float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r < rows) h = *reinterpret_cast<const float4 *>(a.h + (size_t)(r0 + r) * H + c);
-            *reinterpret_cast<float4 *>(sh + r * LDH + c) = h;
-        }
-        __syncthreads();
-        fm_f32x4 acc[2][NT];
-        fm_mma<KS1, NT>(acc, sxs, LD1, bc, HT);
-        float x1v[2][NT][4];
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const int t = wave + FM_WAVES * nt;
-                if (t >= HT) continue;
-                const int col = t * 16 + (lane & 15);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = rt * 16 + (lane >> 4) * 4 + r;
-                    const float u = fm_bn(sh[row * LDH + col], spar[col], spar[H + col], spar[2 * H + col], spar[3 * H + col]);
-                    const float y = __fadd_rn(__fmul_rn(2.f, acc[rt][nt][r]), __fmul_rn(spar[4 * H + col], u));
-                    const float x1 = fm_relu(y);
-                    x1v[rt][nt][r] = x1;
-                    sx1[row * LDH + col] = x1;
-                    if (row < rows) {
-                        o_y = fm_umax(o_y, fm_absbits(y));
-                        o_x1 = fm_umax(o_x1, fm_absbits(x1));
-                        if (TRACE) a.y_trace[(size_t)(r0 + row) * H + col] = y;
-                    }
-                }
-            }
-        __syncthreads();
-        fm_mma<KS2, NT>(acc, sx1, LDH, bw, HT);
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const int t = wave + FM_WAVES * nt;
-                if (t >= HT) continue;
-                const int col = t * 16 + (lane & 15);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = rt * 16 + (lane >> 4) * 4 + r;
-                    if (row >= rows) continue;
-                    const float gin = __fadd_rn(acc[rt][nt][r], spar[5 * H + col]);
-                    const float g = 1.f / (1.f + expf(-gin));
-                    o_gin = fm_umax(o_gin, fm_absbits(gin));
-                    o_g = fm_umax(o_g, fm_absbits(g));
-                    const size_t o = (size_t)(r0 + row) * H + col;
-                    a.hout[o] = fm_relu(__fadd_rn(__fmul_rn(x1v[rt][nt][r], g), sh[row * LDH + col]));
-                    if (TRACE) {
-                        a.gin_trace[o] = gin;
-                        a.g_trace[o] = g;
-                    }
-                }
-            }
-        __syncthreads();
-    }
-    const unsigned om[7] = {o_xre, o_xim, o_y, o_x1, o_gin, o_x1, o_g};
-    fm_obs_flush<7>(om, sobs, a.stats);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// decoder: out = h Wd + bd; observers [0] decoder.inp, [1] decoder.out.  The 257 columns leave a masked last tile.
-// ------------------------------------------------------------------------------------------------------------------
 struct FDecArgs {
     const float *h;  // (N,H)
     const float *w;  // (H,272), columns 257..271 zero
@@ -378,57 +212,34 @@ struct FDecArgs {
     long long N;
 };
 
-template <int DS>
-__global__ __launch_bounds__(256) void k_fdec(FDecArgs a)
-{
-    constexpr int H = 48 * DS, NT = (FM_DEC_TILES + 3) / 4, KS = H / 4, LDA = fm_lda(H);
-    __shared__ float sh[FM_FT * LDA];
-    __shared__ unsigned sobs[FM_WAVES * 2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float breg[NT][KS];
-    fm_load_w<KS, NT>(breg, a.w, FM_MDEC, FM_DEC_TILES);
-    float bias[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int t = wave + FM_WAVES * nt;
-        bias[nt] = t < FM_DEC_TILES ? a.b[t * 16 + (lane & 15)] : 0.f;
-    }
-    unsigned om[2] = {0u, 0u};
-    const long long tiles = (a.N + FM_FT - 1) / FM_FT;
-    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const long long r0 = tile * FM_FT;
-        const int rows = (int)(a.N - r0 < FM_FT ? a.N - r0 : FM_FT);
-        for (int i = threadIdx.x; i < FM_FT * (H / 4); i += 256) {
-            const int r = i / (H / 4), c = (i - r * (H / 4)) * 4;
-            float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r < rows) {
-                h = *reinterpret_cast<const float4 *>(a.h + (size_t)(r0 + r) * H + c);
-                om[0] = fm_umax(fm_umax(fm_umax(om[0], fm_absbits(h.x)), fm_umax(fm_absbits(h.y), fm_absbits(h.z))), fm_absbits(h.w));
-            }
-            *reinterpret_cast<float4 *>(sh + r * LDA + c) = h;
-        }
-        __syncthreads();
-        fm_f32x4 acc[2][NT];
-        fm_mma<KS, NT>(acc, sh, LDA, breg, FM_DEC_TILES);
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const int t = wave + FM_WAVES * nt;
-                if (t >= FM_DEC_TILES) continue;
-                const int col = t * 16 + (lane & 15);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = rt * 16 + (lane >> 4) * 4 + r;
-                    if (row >= rows || col >= FM_DIN) continue;
-                    const float v = __fadd_rn(acc[rt][nt][r], bias[nt]);
-                    om[1] = fm_umax(om[1], fm_absbits(v));
-                    a.out[(size_t)(r0 + row) * FM_DIN + col] = v;
-                }
-            }
-        __syncthreads();
-    }
-    fm_obs_flush<2>(om, sobs, a.stats);
-}
+#define FM_HIST 0
+#define FM_KERNEL(name) name
+#define FM_HIST_PARAM
+#define FM_HIST_BEGIN(planes)
+#define FM_HIST_ADD(plane, v)
+#define FM_HIST_END(...)
+#include "float_model_kernels.inc"
+#undef FM_HIST
+#undef FM_KERNEL
+#undef FM_HIST_PARAM
+#undef FM_HIST_BEGIN
+#undef FM_HIST_ADD
+#undef FM_HIST_END
+
+#define FM_HIST 1
+#define FM_KERNEL(name) name##_hist
+#define FM_HIST_PARAM , unsigned long long *hist
+#define FM_HIST_BEGIN(planes)                       \
+    unsigned *const shist = fm_hist_lds<planes>(); \
+    fm_hist_zero<planes>(shist)
+#define FM_HIST_ADD(plane, v) fm_hist_add(shist, plane, v)
+#define FM_HIST_END(...) fm_hist_flush<__VA_ARGS__>(shist, hist)
+#include "float_model_kernels.inc"
+#undef FM_HIST
+#undef FM_KERNEL
+#undef FM_HIST_PARAM
+#undef FM_HIST_BEGIN
+#undef FM_HIST_ADD
+#undef FM_HIST_END
 
 } // namespace s5

@@ -1,0 +1,323 @@
+// float_model_kernels.inc -- the float model's four tile kernels, included by float_model.hpp twice (no include guard):
+// FM_HIST 0 gives k_fenc / k_fbproj / k_fgate / k_fdec, FM_HIST 1 gives k_fenc_hist / ... which take `hist` as well and count
+// every value into its observer's exponent histogram where it enters the observer.  With FM_HIST 0 every FM_HIST_* macro is
+// empty.  Not a translation unit of its own; everything it uses is declared in float_model.hpp, inside namespace s5.
+
+// ------------------------------------------------------------------------------------------------------------------
+// encoder: h = relu(x W + b); observers [0] encoder.inp, [1] encoder.out (before the ReLU)
+// ------------------------------------------------------------------------------------------------------------------
+
+template <int DS>
+__global__ __launch_bounds__(256) void FM_KERNEL(k_fenc)(FEncArgs a FM_HIST_PARAM) // hist: rows encoder.inp, encoder.out
+{
+    constexpr int H = 48 * DS, HT = 3 * DS, NT = (HT + 3) / 4, KS = FM_KENC / 4, LDA = fm_lda(FM_KENC);
+    __shared__ float sx[FM_FT * LDA];
+    __shared__ unsigned sobs[FM_WAVES * 2];
+    FM_HIST_BEGIN(2);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float breg[NT][KS];
+    fm_load_w<KS, NT>(breg, a.w, H, HT);
+    float bias[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int t = wave + FM_WAVES * nt;
+        bias[nt] = t < HT ? a.b[t * 16 + (lane & 15)] : 0.f;
+    }
+    unsigned om[2] = {0u, 0u};
+    const long long tiles = (a.N + FM_FT - 1) / FM_FT;
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const long long r0 = tile * FM_FT;
+        const int rows = (int)(a.N - r0 < FM_FT ? a.N - r0 : FM_FT);
+        // rows are 257 floats: dword loads, all of a thread's issued before the first is used.  Addresses are clamped into the
+        // tile's valid rows and columns, so no load is conditional; what lies outside is replaced by zero afterwards.
+        const float *src = a.x + (size_t)r0 * FM_DIN;
+        constexpr int PER = (FM_FT * FM_KENC + 255) / 256;
+        float v[PER];
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int i = threadIdx.x + 256 * j, r = i / FM_KENC, c = i - r * FM_KENC;
+            const int rc = r < rows ? r : rows - 1, cc = c < FM_DIN ? c : FM_DIN - 1;
+            v[j] = src[(size_t)rc * FM_DIN + cc];
+        }
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int i = threadIdx.x + 256 * j, r = i / FM_KENC, c = i - r * FM_KENC;
+            if (i >= FM_FT * FM_KENC) continue; // the last round is partial: 8320 = 32.5 x 256
+            const bool ok = r < rows && c < FM_DIN;
+            const float w = ok ? v[j] : 0.f;
+            if (ok) {
+                om[0] = fm_umax(om[0], fm_absbits(w));
+                FM_HIST_ADD(0, w);
+            }
+            sx[r * LDA + c] = w;
+        }
+        __syncthreads();
+        fm_f32x4 acc[2][NT];
+        fm_mma<KS, NT>(acc, sx, LDA, breg, HT);
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const int t = wave + FM_WAVES * nt;
+                if (t >= HT) continue;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = rt * 16 + (lane >> 4) * 4 + r;
+                    if (row >= rows) continue;
+                    const float v = __fadd_rn(acc[rt][nt][r], bias[nt]);
+                    om[1] = fm_umax(om[1], fm_absbits(v));
+                    FM_HIST_ADD(1, v);
+                    a.h[(size_t)(r0 + row) * H + t * 16 + (lane & 15)] = fm_relu(v);
+                }
+            }
+        __syncthreads();
+    }
+    fm_obs_flush<2>(om, sobs, a.stats);
+    FM_HIST_END(2);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// B projection: u = BatchNorm(h); Bu = u B_bar^T as ONE real product against bcat (H, 2P) whose columns interleave re and
+// im, so the result is the (N,P) complex64 plane the scan takes.  Observers [0] u, [1] Bu_re, [2] Bu_im.
+// ------------------------------------------------------------------------------------------------------------------
+
+template <int DS, bool TRACE>
+__global__ __launch_bounds__(256) void FM_KERNEL(k_fbproj)(FBprojArgs a FM_HIST_PARAM) // hist: rows u, Bu_re, Bu_im
+{
+    constexpr int H = 48 * DS, P2 = 64 * DS, PT = 4 * DS, NT = DS, KS = H / 4, LDA = fm_lda(H);
+    __shared__ float su[FM_FT * LDA];
+    __shared__ float snm[4 * H];
+    __shared__ unsigned sobs[FM_WAVES * 3];
+    FM_HIST_BEGIN(3);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float breg[NT][KS];
+    fm_load_w<KS, NT>(breg, a.bcat, P2, PT);
+    for (int i = threadIdx.x; i < H; i += 256) {
+        snm[i] = a.nm.mean[i]; snm[H + i] = a.nm.istd[i]; snm[2 * H + i] = a.nm.scale[i]; snm[3 * H + i] = a.nm.bias[i];
+    }
+    __syncthreads();
+    unsigned om_u = 0u, om_bu = 0u; // a lane's Bu columns all have the lane's parity: even = re, odd = im
+    const long long tiles = (a.N + FM_FT - 1) / FM_FT;
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const long long r0 = tile * FM_FT;
+        const int rows = (int)(a.N - r0 < FM_FT ? a.N - r0 : FM_FT);
+        for (int i = threadIdx.x; i < FM_FT * (H / 4); i += 256) {
+            const int r = i / (H / 4), c = (i - r * (H / 4)) * 4;
+            float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (r < rows) {
+                const float4 h = *reinterpret_cast<const float4 *>(a.h + (size_t)(r0 + r) * H + c);
+                u.x = fm_bn(h.x, snm[c], snm[H + c], snm[2 * H + c], snm[3 * H + c]);
+                u.y = fm_bn(h.y, snm[c + 1], snm[H + c + 1], snm[2 * H + c + 1], snm[3 * H + c + 1]);
+                u.z = fm_bn(h.z, snm[c + 2], snm[H + c + 2], snm[2 * H + c + 2], snm[3 * H + c + 2]);
+                u.w = fm_bn(h.w, snm[c + 3], snm[H + c + 3], snm[2 * H + c + 3], snm[3 * H + c + 3]);
+                om_u = fm_umax(fm_umax(fm_umax(om_u, fm_absbits(u.x)), fm_umax(fm_absbits(u.y), fm_absbits(u.z))), fm_absbits(u.w));
+                FM_HIST_ADD(0, u.x);
+                FM_HIST_ADD(0, u.y);
+                FM_HIST_ADD(0, u.z);
+                FM_HIST_ADD(0, u.w);
+                if (TRACE) *reinterpret_cast<float4 *>(a.u_trace + (size_t)(r0 + r) * H + c) = u;
+            }
+            *reinterpret_cast<float4 *>(su + r * LDA + c) = u;
+        }
+        __syncthreads();
+        fm_f32x4 acc[2][NT];
+        fm_mma<KS, NT>(acc, su, LDA, breg, PT);
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const int t = wave + FM_WAVES * nt; // < PT always: PT = 4 * NT
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = rt * 16 + (lane >> 4) * 4 + r;
+                    if (row >= rows) continue;
+                    const float v = acc[rt][nt][r];
+                    om_bu = fm_umax(om_bu, fm_absbits(v));
+                    FM_HIST_ADD(1 + (lane & 1), v);
+                    a.bu[(size_t)(r0 + row) * P2 + t * 16 + (lane & 15)] = v;
+                }
+            }
+        __syncthreads();
+    }
+    const unsigned om[3] = {om_u, (lane & 1) ? 0u : om_bu, (lane & 1) ? om_bu : 0u};
+    fm_obs_flush<3>(om, sobs, a.stats);
+    FM_HIST_END(3);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// gate: complex ReLU on the raw states, y = 2 (x_re C_re^T - x_im C_im^T) + D u as ONE real product of the interleaved
+// rectified states against ccat (2P,H) = rows (C_re^T, -C_im^T) interleaved, with u rebuilt from the layer input;
+// x1 = relu(y), g_in = x1 W2 + b2, g = sigmoid(g_in), h' = relu(x1 g + h).
+// Observers [0] x_re, [1] x_im (raw states), [2] y, [3] out2.inp, [4] out2.out, [5] gate.l (= out2.inp), [6] gate.r.
+// ------------------------------------------------------------------------------------------------------------------
+
+template <int DS, bool TRACE>
+__global__ __launch_bounds__(256) void FM_KERNEL(k_fgate)(FGateArgs a FM_HIST_PARAM) // hist: the layer's rows x_re .. gate.r
+{
+    constexpr int H = 48 * DS, P = 32 * DS, P2 = 64 * DS, HT = 3 * DS, NT = (HT + 3) / 4, KS1 = P2 / 4, KS2 = H / 4;
+    constexpr int LD1 = fm_lda(P2), LDH = fm_lda(H);
+    __shared__ float sxs[FM_FT * LD1];
+    __shared__ float sh[FM_FT * LDH];
+    __shared__ float sx1[FM_FT * LDH];
+    __shared__ float spar[6 * H]; // mean, istd, scale, bias, D, b2
+    __shared__ unsigned sobs[FM_WAVES * 7];
+    FM_HIST_BEGIN(6); // LDS planes: x_re, x_im, y, out2.inp (= gate.l), out2.out, gate.r
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float bc[NT][KS1], bw[NT][KS2];
+    fm_load_w<KS1, NT>(bc, a.ccat, H, HT);
+    fm_load_w<KS2, NT>(bw, a.w2, H, HT);
+    for (int i = threadIdx.x; i < H; i += 256) {
+        spar[i] = a.nm.mean[i]; spar[H + i] = a.nm.istd[i]; spar[2 * H + i] = a.nm.scale[i]; spar[3 * H + i] = a.nm.bias[i];
+        spar[4 * H + i] = a.D[i]; spar[5 * H + i] = a.b2[i];
+    }
+    __syncthreads();
+    unsigned o_xre = 0u, o_xim = 0u, o_y = 0u, o_x1 = 0u, o_gin = 0u, o_g = 0u;
+    const long long tiles = (a.N + FM_FT - 1) / FM_FT;
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const long long r0 = tile * FM_FT;
+        const int rows = (int)(a.N - r0 < FM_FT ? a.N - r0 : FM_FT);
+        for (int i = threadIdx.x; i < FM_FT * P; i += 256) {
+            const int r = i / P, p = i - r * P;
+            float2 v = make_float2(0.f, 0.f);
+            if (r < rows) {
+                v = *reinterpret_cast<const float2 *>(a.xs + (size_t)(r0 + r) * P2 + 2 * p);
+                o_xre = fm_umax(o_xre, fm_absbits(v.x));
+                o_xim = fm_umax(o_xim, fm_absbits(v.y));
+                FM_HIST_ADD(0, v.x);
+                FM_HIST_ADD(1, v.y);
+                const bool keep = v.x > 0.f || (v.x == 0.f && v.y > 0.f);
+                if (!keep) v = make_float2(0.f, 0.f);
+            }
+            *reinterpret_cast<float2 *>(sxs + r * LD1 + 2 * p) = v;
+        }
+        for (int i = threadIdx.x; i < FM_FT * (H / 4); i += 256) {
+            const int r = i / (H / 4), c = (i - r * (H / 4)) * 4;
+            float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (r < rows) h = *reinterpret_cast<const float4 *>(a.h + (size_t)(r0 + r) * H + c);
+            *reinterpret_cast<float4 *>(sh + r * LDH + c) = h;
+        }
+        __syncthreads();
+        fm_f32x4 acc[2][NT];
+        fm_mma<KS1, NT>(acc, sxs, LD1, bc, HT);
+        float x1v[2][NT][4];
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const int t = wave + FM_WAVES * nt;
+                if (t >= HT) continue;
+                const int col = t * 16 + (lane & 15);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = rt * 16 + (lane >> 4) * 4 + r;
+                    const float u = fm_bn(sh[row * LDH + col], spar[col], spar[H + col], spar[2 * H + col], spar[3 * H + col]);
+                    const float y = __fadd_rn(__fmul_rn(2.f, acc[rt][nt][r]), __fmul_rn(spar[4 * H + col], u));
+                    const float x1 = fm_relu(y);
+                    x1v[rt][nt][r] = x1;
+                    sx1[row * LDH + col] = x1;
+                    if (row < rows) {
+                        o_y = fm_umax(o_y, fm_absbits(y));
+                        o_x1 = fm_umax(o_x1, fm_absbits(x1));
+                        FM_HIST_ADD(2, y);
+                        FM_HIST_ADD(3, x1);
+                        if (TRACE) a.y_trace[(size_t)(r0 + row) * H + col] = y;
+                    }
+                }
+            }
+        __syncthreads();
+        fm_mma<KS2, NT>(acc, sx1, LDH, bw, HT);
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const int t = wave + FM_WAVES * nt;
+                if (t >= HT) continue;
+                const int col = t * 16 + (lane & 15);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = rt * 16 + (lane >> 4) * 4 + r;
+                    if (row >= rows) continue;
+                    const float gin = __fadd_rn(acc[rt][nt][r], spar[5 * H + col]);
+                    const float g = 1.f / (1.f + expf(-gin));
+                    o_gin = fm_umax(o_gin, fm_absbits(gin));
+                    o_g = fm_umax(o_g, fm_absbits(g));
+                    FM_HIST_ADD(4, gin);
+                    FM_HIST_ADD(5, g);
+                    const size_t o = (size_t)(r0 + row) * H + col;
+                    a.hout[o] = fm_relu(__fadd_rn(__fmul_rn(x1v[rt][nt][r], g), sh[row * LDH + col]));
+                    if (TRACE) {
+                        a.gin_trace[o] = gin;
+                        a.g_trace[o] = g;
+                    }
+                }
+            }
+        __syncthreads();
+    }
+    const unsigned om[7] = {o_xre, o_xim, o_y, o_x1, o_gin, o_x1, o_g};
+    fm_obs_flush<7>(om, sobs, a.stats);
+    FM_HIST_END(6, 3, 5); // plane 3 goes to out2.inp and to gate.l
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// decoder: out = h Wd + bd; observers [0] decoder.inp, [1] decoder.out.  The 257 columns leave a masked last tile.
+// ------------------------------------------------------------------------------------------------------------------
+
+template <int DS>
+__global__ __launch_bounds__(256) void FM_KERNEL(k_fdec)(FDecArgs a FM_HIST_PARAM) // hist: rows decoder.inp, decoder.out
+{
+    constexpr int H = 48 * DS, NT = (FM_DEC_TILES + 3) / 4, KS = H / 4, LDA = fm_lda(H);
+    __shared__ float sh[FM_FT * LDA];
+    __shared__ unsigned sobs[FM_WAVES * 2];
+    FM_HIST_BEGIN(2);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float breg[NT][KS];
+    fm_load_w<KS, NT>(breg, a.w, FM_MDEC, FM_DEC_TILES);
+    float bias[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int t = wave + FM_WAVES * nt;
+        bias[nt] = t < FM_DEC_TILES ? a.b[t * 16 + (lane & 15)] : 0.f;
+    }
+    unsigned om[2] = {0u, 0u};
+    const long long tiles = (a.N + FM_FT - 1) / FM_FT;
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const long long r0 = tile * FM_FT;
+        const int rows = (int)(a.N - r0 < FM_FT ? a.N - r0 : FM_FT);
+        for (int i = threadIdx.x; i < FM_FT * (H / 4); i += 256) {
+            const int r = i / (H / 4), c = (i - r * (H / 4)) * 4;
+            float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (r < rows) {
+                h = *reinterpret_cast<const float4 *>(a.h + (size_t)(r0 + r) * H + c);
+                om[0] = fm_umax(fm_umax(fm_umax(om[0], fm_absbits(h.x)), fm_umax(fm_absbits(h.y), fm_absbits(h.z))), fm_absbits(h.w));
+                FM_HIST_ADD(0, h.x);
+                FM_HIST_ADD(0, h.y);
+                FM_HIST_ADD(0, h.z);
+                FM_HIST_ADD(0, h.w);
+            }
+            *reinterpret_cast<float4 *>(sh + r * LDA + c) = h;
+        }
+        __syncthreads();
+        fm_f32x4 acc[2][NT];
+        fm_mma<KS, NT>(acc, sh, LDA, breg, FM_DEC_TILES);
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const int t = wave + FM_WAVES * nt;
+                if (t >= FM_DEC_TILES) continue;
+                const int col = t * 16 + (lane & 15);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = rt * 16 + (lane >> 4) * 4 + r;
+                    if (row >= rows || col >= FM_DIN) continue;
+                    const float v = __fadd_rn(acc[rt][nt][r], bias[nt]);
+                    om[1] = fm_umax(om[1], fm_absbits(v));
+                    FM_HIST_ADD(1, v);
+                    a.out[(size_t)(r0 + row) * FM_DIN + col] = v;
+                }
+            }
+        __syncthreads();
+    }
+    fm_obs_flush<2>(om, sobs, a.stats);
+    FM_HIST_END(2);
+}

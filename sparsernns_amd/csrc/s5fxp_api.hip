@@ -1350,12 +1350,12 @@ size_t float_pack(const s5fxp_float_model_desc *d, FloatPacker &p, s5fxp_float_m
 
 constexpr long long FM_GRID_CAP = 512; // workgroups per launch: the weights are loaded into registers once per workgroup
 
-#define S5_DISPATCH_DS(ds, KERNEL, grid, stream, args)                                                \
-    do {                                                                                              \
-        if ((ds) == 1) hipLaunchKernelGGL((KERNEL(1)), dim3(grid), dim3(256), 0, stream, args);       \
-        else if ((ds) == 2) hipLaunchKernelGGL((KERNEL(2)), dim3(grid), dim3(256), 0, stream, args);  \
-        else if ((ds) == 3) hipLaunchKernelGGL((KERNEL(3)), dim3(grid), dim3(256), 0, stream, args);  \
-        else hipLaunchKernelGGL((KERNEL(4)), dim3(grid), dim3(256), 0, stream, args);                 \
+#define S5_DISPATCH_DS(ds, KERNEL, grid, stream, ...)                                                        \
+    do {                                                                                                     \
+        if ((ds) == 1) hipLaunchKernelGGL((KERNEL(1)), dim3(grid), dim3(256), 0, stream, __VA_ARGS__);       \
+        else if ((ds) == 2) hipLaunchKernelGGL((KERNEL(2)), dim3(grid), dim3(256), 0, stream, __VA_ARGS__);  \
+        else if ((ds) == 3) hipLaunchKernelGGL((KERNEL(3)), dim3(grid), dim3(256), 0, stream, __VA_ARGS__);  \
+        else hipLaunchKernelGGL((KERNEL(4)), dim3(grid), dim3(256), 0, stream, __VA_ARGS__);                 \
     } while (0)
 #define S5_K_FENC(ds) k_fenc<ds>
 #define S5_K_FDEC(ds) k_fdec<ds>
@@ -1363,6 +1363,68 @@ constexpr long long FM_GRID_CAP = 512; // workgroups per launch: the weights are
 #define S5_K_FBPROJ(ds) k_fbproj<ds, false>
 #define S5_K_FGATE_T(ds) k_fgate<ds, true>
 #define S5_K_FGATE(ds) k_fgate<ds, false>
+#define S5_K_FENC_H(ds) k_fenc_hist<ds>
+#define S5_K_FDEC_H(ds) k_fdec_hist<ds>
+#define S5_K_FBPROJ_TH(ds) k_fbproj_hist<ds, true>
+#define S5_K_FBPROJ_H(ds) k_fbproj_hist<ds, false>
+#define S5_K_FGATE_TH(ds) k_fgate_hist<ds, true>
+#define S5_K_FGATE_H(ds) k_fgate_hist<ds, false>
+
+static_assert(FM_HIST_BINS == S5FXP_FLOAT_HIST_BINS && FM_HIST_EMIN == S5FXP_FLOAT_HIST_EMIN, "include/s5fxp.h and float_model.hpp");
+
+// the one forward of both entries: hist == nullptr launches exactly the kernels without the histogram
+int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats, unsigned long long *hist,
+                  float *trace, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!m || !x || !y || !workspace || B < 1 || L < 1) return S5FXP_EBADARG;
+    if (reinterpret_cast<uintptr_t>(hist) % sizeof(unsigned long long)) return S5FXP_EBADARG;
+    const long long N = (long long)B * L;
+    const long long tiles = (N + FM_FT - 1) / FM_FT;
+    const unsigned grid = (unsigned)(tiles < FM_GRID_CAP ? tiles : FM_GRID_CAP);
+    if (hist && !fm_hist_rows_ok(tiles, grid)) return S5FXP_EBADARG; // a 32-bit LDS counter could wrap
+    if (workspace_bytes < s5fxp_float_workspace_bytes(m, B, L, trace != nullptr)) return S5FXP_EWORKSPACE;
+    const size_t NH = (size_t)N * m->H, NP2 = (size_t)N * 2 * m->P;
+    hipStream_t st = S(stream);
+    unsigned *obs = reinterpret_cast<unsigned *>(stats);
+    float *ws = static_cast<float *>(workspace);
+    float *hbuf[2] = {ws, ws + NH};
+    float *planes = ws + 2 * NH; // per layer (trace) or shared: Bu, xs
+    int rc;
+
+    float *h = hbuf[0];
+    FEncArgs ea{x, m->enc_w, m->enc_b, h, obs, N};
+    if (hist) S5_DISPATCH_DS(m->DS, S5_K_FENC_H, grid, st, ea, hist);
+    else S5_DISPATCH_DS(m->DS, S5_K_FENC, grid, st, ea);
+    if ((rc = launch_rc())) return rc;
+    for (int i = 0; i < m->n_layers; ++i) {
+        const s5fxp_float_model::Layer &l = m->layers[i];
+        float *bu = planes + (trace ? (size_t)i * 2 * NP2 : 0), *xs = bu + NP2;
+        float *tr = trace ? trace + (size_t)i * 5 * NH : nullptr; // u, y, g_in, g, h'
+        float *hout = trace ? tr + 4 * NH : hbuf[(i + 1) & 1];
+        unsigned *lo = obs ? obs + 2 + 10 * i : nullptr;
+        unsigned long long *lh = hist ? hist + (size_t)(2 + 10 * i) * FM_HIST_BINS : nullptr;
+        FBprojArgs ba{h, l.nm, l.bcat, bu, tr, lo, N};
+        if (hist && trace) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_TH, grid, st, ba, lh);
+        else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_H, grid, st, ba, lh);
+        else if (trace) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_T, grid, st, ba);
+        else S5_DISPATCH_DS(m->DS, S5_K_FBPROJ, grid, st, ba);
+        if ((rc = launch_rc())) return rc;
+        if ((rc = s5fxp_assoc_scan_c64(l.lam, bu, xs, nullptr, nullptr, B, L, m->P, 0, stream))) return rc;
+        FGateArgs ga{xs, h, l.nm, l.ccat, l.D, l.w2, l.b2, hout, tr ? tr + NH : nullptr, tr ? tr + 2 * NH : nullptr,
+                     tr ? tr + 3 * NH : nullptr, lo ? lo + 3 : nullptr, N};
+        unsigned long long *gh = lh ? lh + 3 * FM_HIST_BINS : nullptr;
+        if (hist && trace) S5_DISPATCH_DS(m->DS, S5_K_FGATE_TH, grid, st, ga, gh);
+        else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FGATE_H, grid, st, ga, gh);
+        else if (trace) S5_DISPATCH_DS(m->DS, S5_K_FGATE_T, grid, st, ga);
+        else S5_DISPATCH_DS(m->DS, S5_K_FGATE, grid, st, ga);
+        if ((rc = launch_rc())) return rc;
+        h = hout;
+    }
+    FDecArgs da{h, m->dec_w, m->dec_b, y, obs ? obs + 2 + 10 * m->n_layers : nullptr, N};
+    if (hist) S5_DISPATCH_DS(m->DS, S5_K_FDEC_H, grid, st, da, hist + (size_t)(2 + 10 * m->n_layers) * FM_HIST_BINS);
+    else S5_DISPATCH_DS(m->DS, S5_K_FDEC, grid, st, da);
+    return launch_rc();
+}
 
 } // namespace
 
@@ -1434,44 +1496,14 @@ extern "C" size_t s5fxp_float_trace_bytes(const s5fxp_float_model *m, int B, int
 extern "C" int s5fxp_float_model_forward(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats,
                                          float *trace, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!m || !x || !y || !workspace || B < 1 || L < 1) return S5FXP_EBADARG;
-    if (workspace_bytes < s5fxp_float_workspace_bytes(m, B, L, trace != nullptr)) return S5FXP_EWORKSPACE;
-    const long long N = (long long)B * L;
-    const size_t NH = (size_t)N * m->H, NP2 = (size_t)N * 2 * m->P;
-    const long long tiles = (N + FM_FT - 1) / FM_FT;
-    const unsigned grid = (unsigned)(tiles < FM_GRID_CAP ? tiles : FM_GRID_CAP);
-    hipStream_t st = S(stream);
-    unsigned *obs = reinterpret_cast<unsigned *>(stats);
-    float *ws = static_cast<float *>(workspace);
-    float *hbuf[2] = {ws, ws + NH};
-    float *planes = ws + 2 * NH; // per layer (trace) or shared: Bu, xs
-    int rc;
+    return float_forward(m, x, B, L, y, stats, nullptr, trace, workspace, workspace_bytes, stream);
+}
 
-    float *h = hbuf[0];
-    FEncArgs ea{x, m->enc_w, m->enc_b, h, obs, N};
-    S5_DISPATCH_DS(m->DS, S5_K_FENC, grid, st, ea);
-    if ((rc = launch_rc())) return rc;
-    for (int i = 0; i < m->n_layers; ++i) {
-        const s5fxp_float_model::Layer &l = m->layers[i];
-        float *bu = planes + (trace ? (size_t)i * 2 * NP2 : 0), *xs = bu + NP2;
-        float *tr = trace ? trace + (size_t)i * 5 * NH : nullptr; // u, y, g_in, g, h'
-        float *hout = trace ? tr + 4 * NH : hbuf[(i + 1) & 1];
-        unsigned *lo = obs ? obs + 2 + 10 * i : nullptr;
-        FBprojArgs ba{h, l.nm, l.bcat, bu, tr, lo, N};
-        if (trace) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_T, grid, st, ba);
-        else S5_DISPATCH_DS(m->DS, S5_K_FBPROJ, grid, st, ba);
-        if ((rc = launch_rc())) return rc;
-        if ((rc = s5fxp_assoc_scan_c64(l.lam, bu, xs, nullptr, nullptr, B, L, m->P, 0, stream))) return rc;
-        FGateArgs ga{xs, h, l.nm, l.ccat, l.D, l.w2, l.b2, hout, tr ? tr + NH : nullptr, tr ? tr + 2 * NH : nullptr,
-                     tr ? tr + 3 * NH : nullptr, lo ? lo + 3 : nullptr, N};
-        if (trace) S5_DISPATCH_DS(m->DS, S5_K_FGATE_T, grid, st, ga);
-        else S5_DISPATCH_DS(m->DS, S5_K_FGATE, grid, st, ga);
-        if ((rc = launch_rc())) return rc;
-        h = hout;
-    }
-    FDecArgs da{h, m->dec_w, m->dec_b, y, obs ? obs + 2 + 10 * m->n_layers : nullptr, N};
-    S5_DISPATCH_DS(m->DS, S5_K_FDEC, grid, st, da);
-    return launch_rc();
+extern "C" int s5fxp_float_model_forward_hist(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats,
+                                              unsigned long long *hist, float *trace, void *workspace, size_t workspace_bytes,
+                                              void *stream)
+{
+    return float_forward(m, x, B, L, y, stats, hist, trace, workspace, workspace_bytes, stream);
 }
 
 #ifdef S5_PHASE_PROF

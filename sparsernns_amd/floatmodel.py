@@ -5,12 +5,18 @@ B projection -> ``s5fxp_assoc_scan_c64`` -> gate, decoder -- 2 + 3 * n_layers la
 MFMA.  The 4 + 10 * n_layers absmax observers that ``synth.derive_qconfig`` needs are gathered by the same kernels into one
 device array (``STAT_KEYS`` gives its order), so a calibration set streams through in batches without a host pass.
 
+The same kernels can gather, per observer, a histogram over the float32 exponent field (``exp_hist``): every
+threshold of a fixed-point configuration is a power of two, so the histogram answers exactly which share of a calibration
+set saturates or falls below one LSB (``range_report``), and lets the calibration ignore a stated share of outliers
+(``clip_absmax``, ``calibrate_clipped``).
+
 Results agree with ``synth.float_forward`` to float32 rounding (the summation order differs), not bit for bit.  Without a
 GPU, or for a shape the kernels refuse, ``FloatEngine`` runs ``synth.float_forward`` itself and says so: ``on_device`` is False.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, Iterable, List, Optional, Tuple
 
 import numpy as np
@@ -32,6 +38,26 @@ def stat_keys(n_layers: int) -> List[str]:
 
 STAT_KEYS = stat_keys(3)  # the N-DNS recipe's three layers; stat_keys(n) for any other depth
 TRACE_PLANES = ("u", "y", "g_in", "g", "h_out")  # per layer, (N,H) each: the trace buffer's order
+
+
+HIST_BINS = 64   # S5FXP_FLOAT_HIST_BINS
+HIST_EMIN = -40  # S5FXP_FLOAT_HIST_EMIN: bin b in 1..62 holds 2^(b + HIST_EMIN) <= |v| < 2^(b + HIST_EMIN + 1)
+HIST_KMIN, HIST_KMAX = HIST_EMIN + 1, HIST_EMIN + HIST_BINS - 1  # the thresholds 2^k a histogram answers exactly: -39 .. 23
+
+
+def exp_hist(v) -> np.ndarray:
+    """int64[64]: the histogram of ``v`` (taken as float32) over the exponent field E = (bits >> 23) & 0xff, bin
+    clamp(E - 87, 0, 63).  Bin 0 holds everything below 2^-39 (zero, subnormals), bin 63 |v| >= 2^23, infinities and NaN."""
+    bits = np.ascontiguousarray(np.asarray(v, dtype=F32)).view(np.uint32)
+    E = ((bits >> 23) & 0xff).astype(np.int64)
+    return np.bincount(np.clip(E - (127 + HIST_EMIN), 0, HIST_BINS - 1).ravel(), minlength=HIST_BINS).astype(np.int64)
+
+
+def tail_count(row, k: int) -> int:
+    """T(k) = #{|v| >= 2^k}, exact for HIST_KMIN <= k <= HIST_KMAX."""
+    if not HIST_KMIN <= k <= HIST_KMAX:
+        raise ValueError(f"the histogram answers thresholds 2^{HIST_KMIN} .. 2^{HIST_KMAX}, not 2^{k}")
+    return int(np.asarray(row)[k - HIST_EMIN:].sum())
 
 
 def _f32(a) -> np.ndarray:
@@ -125,6 +151,13 @@ class FloatEngine:
     def stats_dict(self, stats_dev: torch.Tensor) -> Dict[str, float]:
         return {k: float(v) for k, v in zip(self.keys, stats_dev.cpu().numpy())}
 
+    def new_hist(self) -> torch.Tensor:
+        """A zeroed histogram array: (4 + 10 * n_layers, 64) int64 on the engine's device, rows in ``keys`` order."""
+        return torch.zeros(len(self.keys), HIST_BINS, dtype=torch.int64, device=self.device)
+
+    def hist_dict(self, hist_dev: torch.Tensor) -> Dict[str, np.ndarray]:
+        return {k: row.copy() for k, row in zip(self.keys, hist_dev.cpu().numpy())}
+
     def _workspace(self, B: int, L: int, trace: bool) -> torch.Tensor:
         n = lib.s5fxp_float_workspace_bytes(self._h, B, L, int(trace)) // 4
         ws = self._ws.get(trace)
@@ -132,9 +165,11 @@ class FloatEngine:
             ws = self._ws[trace] = torch.empty(n, dtype=torch.float32, device=self.device)
         return ws
 
-    def forward_device(self, x: torch.Tensor, stats_dev: Optional[torch.Tensor] = None, trace: bool = False):
-        """x (B,L,257) float32 on the device -> y (B,L,257); ``stats_dev`` (``new_stats``) is raised in place.  With ``trace``
-        also (trace buffer, workspace): the planes of ``forward_traced`` as flat tensors.  Stream-ordered, no sync."""
+    def forward_device(self, x: torch.Tensor, stats_dev: Optional[torch.Tensor] = None, trace: bool = False,
+                       hist_dev: Optional[torch.Tensor] = None):
+        """x (B,L,257) float32 on the device -> y (B,L,257); ``stats_dev`` (``new_stats``) is raised in place, ``hist_dev``
+        (``new_hist``) is added to in place.  With ``trace`` also (trace buffer, workspace): the planes of ``forward_traced``
+        as flat tensors.  Stream-ordered, no sync."""
         if not self.on_device:
             raise RuntimeError("FloatEngine.forward_device needs the kernels (on_device is False)")
         if x.dim() != 3 or x.shape[2] != self.d_in or x.dtype != torch.float32 or x.device != self.device:
@@ -142,28 +177,40 @@ class FloatEngine:
         if stats_dev is not None and (stats_dev.dtype != torch.float32 or stats_dev.numel() != len(self.keys)
                                       or stats_dev.device != self.device or not stats_dev.is_contiguous()):
             raise ValueError(f"stats must be {len(self.keys)} contiguous float32 on {self.device}")
+        if hist_dev is not None and (hist_dev.dtype != torch.int64 or hist_dev.numel() != len(self.keys) * HIST_BINS
+                                     or hist_dev.device != self.device or not hist_dev.is_contiguous()):
+            raise ValueError(f"hist must be {len(self.keys)} x {HIST_BINS} contiguous int64 on {self.device}")
         x = x.contiguous()
         B, L = int(x.shape[0]), int(x.shape[1])
         y = torch.empty(B, L, self.d_out, dtype=torch.float32, device=self.device)
         ws = self._workspace(B, L, trace)
         tr = torch.empty(lib.s5fxp_float_trace_bytes(self._h, B, L) // 4, dtype=torch.float32, device=self.device) if trace else None
+        st = None if stats_dev is None else stats_dev.data_ptr()
         with torch.cuda.device(self.device):
-            check(lib.s5fxp_float_model_forward(self._h, x.data_ptr(), B, L, y.data_ptr(),
-                                                None if stats_dev is None else stats_dev.data_ptr(),
-                                                None if tr is None else tr.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                                torch.cuda.current_stream().cuda_stream), "s5fxp_float_model_forward")
+            if hist_dev is None:
+                check(lib.s5fxp_float_model_forward(self._h, x.data_ptr(), B, L, y.data_ptr(), st,
+                                                    None if tr is None else tr.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                                    torch.cuda.current_stream().cuda_stream), "s5fxp_float_model_forward")
+            else:
+                check(lib.s5fxp_float_model_forward_hist(self._h, x.data_ptr(), B, L, y.data_ptr(), st, hist_dev.data_ptr(),
+                                                         None if tr is None else tr.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                                         torch.cuda.current_stream().cuda_stream),
+                      "s5fxp_float_model_forward_hist")
         return (y, tr, ws) if trace else y
 
-    def forward_traced(self, x) -> dict:
+    def forward_traced(self, x, hist: bool = False) -> dict:
         """Every plane of one forward, as device tensors: ``h_enc`` (B,L,H), ``out`` (B,L,257), ``stats`` (the observer array
-        of this forward alone) and per layer ``l{i}.u / y / g_in / g / h_out`` (B,L,H) float32 and ``l{i}.Bu / xs`` (B,L,P)
+        of this forward alone), with ``hist`` also ``hist`` (its histogram array), and per layer ``l{i}.u / y / g_in / g / h_out`` (B,L,H) float32 and ``l{i}.Bu / xs`` (B,L,P)
         complex64 (``xs`` raw, before the complex ReLU)."""
         xd = self._to_device(x)
         B, L = int(xd.shape[0]), int(xd.shape[1])
         st = self.new_stats()
-        y, tr, ws = self.forward_device(xd, st, trace=True)
+        hd = self.new_hist() if hist else None
+        y, tr, ws = self.forward_device(xd, st, trace=True, hist_dev=hd)
         NH, NP2 = B * L * self.H, B * L * 2 * self.P
         out = dict(out=y, stats=st, h_enc=ws[:NH].view(B, L, self.H).clone())
+        if hist:
+            out["hist"] = hd
         for i in range(self.n_layers):
             for j, name in enumerate(TRACE_PLANES):
                 out[f"l{i}.{name}"] = tr[(5 * i + j) * NH:(5 * i + j + 1) * NH].view(B, L, self.H)
@@ -178,23 +225,28 @@ class FloatEngine:
         return torch.from_numpy(_f32(x)).to(self.device)
 
     # -- the mirror of synth.float_forward -----------------------------------------------------
-    def forward(self, x, stats: Optional[dict] = None, activations: Optional[dict] = None):
+    def forward(self, x, stats: Optional[dict] = None, activations: Optional[dict] = None, hist: Optional[dict] = None):
         """x (B,L,257) float32, NumPy array or tensor -> the model's output of the same kind.  ``stats`` is updated by maximum
-        under ``synth.float_forward``'s keys; ``activations`` receives sequence 0 under the reference's keys (``pre_C`` = the
+        and ``hist`` by addition (int64[64] rows) under ``synth.float_forward``'s keys; ``activations`` receives sequence 0 under the reference's keys (``pre_C`` = the
         rectified states)."""
         as_tensor = isinstance(x, torch.Tensor)
         if not self.on_device:
             xn = x.detach().cpu().numpy().astype(F32) if as_tensor else np.asarray(x, dtype=F32)
-            y = synth.float_forward(self.modeldict, xn, self.n_layers, stats=stats, activations=activations)
+            y = synth.float_forward(self.modeldict, xn, self.n_layers, stats=stats, activations=activations, hist=hist)
             return torch.from_numpy(y) if as_tensor else y
         xd = self._to_device(x)
+        hd = None
         if activations is not None:
-            t = self.forward_traced(xd)
-            y, st = t["out"], t["stats"]
+            t = self.forward_traced(xd, hist=hist is not None)
+            y, st, hd = t["out"], t["stats"], t.get("hist")
             self._fill_activations(t, activations)
         else:
             st = self.new_stats() if stats is not None else None
-            y = self.forward_device(xd, st)
+            hd = self.new_hist() if hist is not None else None
+            y = self.forward_device(xd, st, hist_dev=hd)
+        if hist is not None:
+            for k, row in self.hist_dict(hd).items():
+                hist[k] = hist.get(k, 0) + row
         if stats is not None:
             for k, v in self.stats_dict(st).items():
                 stats[k] = max(stats.get(k, 0.0), v)
@@ -240,3 +292,88 @@ def calibrate(modeldict: dict, batches: Iterable, n_layers: int, quantization: s
     synth.cap_result_exponents(qc)
     synth._assert_exps_nonnegative(qc)
     return stats, qc
+
+
+def clip_absmax(stats: dict, hist: dict, clip_fraction: float, keep=("x_re", "x_im")) -> dict:
+    """The observers a calibration that may ignore ``clip_fraction`` of every tensor's values works from.  Per key, with
+    n = sum(hist) and T(k) = #{|v| >= 2^k}: k* = min{k in [-39, 23] : T(k) <= floor(clip_fraction * n)}, and the effective
+    absmax is min(absmax, nextafter(float32(2^k*), 0)) -- the largest value that still needs only k* integer bits; without
+    such a k it is absmax.  Keys whose last component is in ``keep`` pass through: the reference never clips the SSM state,
+    it wraps (fxpmodel.py:147-172), so the state's exponent stays on its absmax.  ``clip_fraction`` = 0 changes nothing, by
+    construction: T(k) = 0 means absmax < 2^k already."""
+    if not 0.0 <= clip_fraction < 1.0:
+        raise ValueError(f"clip_fraction must be in [0, 1), got {clip_fraction}")
+    out = {}
+    for key, absmax in stats.items():
+        out[key] = absmax
+        if key.split(".")[-1] in keep:
+            continue
+        row = np.asarray(hist[key], dtype=np.int64)
+        allow = int(math.floor(clip_fraction * int(row.sum())))
+        tails = np.cumsum(row[::-1])[::-1]  # tails[b] = count in the bins b ..
+        for k in range(HIST_KMIN, HIST_KMAX + 1):
+            if int(tails[k - HIST_EMIN]) <= allow:
+                out[key] = min(absmax, float(np.nextafter(F32(2.0 ** k), F32(0))))
+                break
+    return out
+
+
+def calibrate_clipped(modeldict: dict, batches: Iterable, n_layers: int, clip_fraction: float, quantization: str = "w8a16",
+                      state_headroom_bits: int = 0, keep=("x_re", "x_im"),
+                      engine: Optional[FloatEngine] = None) -> Tuple[dict, dict, dict, dict]:
+    """``calibrate`` with the histograms carried next to the observers -> (stats, hist, effective, fxp_qconfig): the
+    configuration is derived from ``effective = clip_absmax(stats, hist, clip_fraction, keep)``.  On a GPU both arrays stay
+    on the device across the batches and are read back once."""
+    eng = engine if engine is not None else FloatEngine(modeldict, n_layers)
+    stats: dict = {}
+    hist: dict = {}
+    if eng.on_device:
+        st, hd = eng.new_stats(), eng.new_hist()
+        n = 0
+        for x in batches:
+            eng.forward_device(eng._to_device(x), st, hist_dev=hd)
+            n += 1
+        if n:
+            stats, hist = eng.stats_dict(st), eng.hist_dict(hd)
+    else:
+        for x in batches:
+            eng.forward(x, stats=stats, hist=hist)
+    if not stats:
+        raise ValueError("calibrate_clipped needs at least one batch")
+    effective = clip_absmax(stats, hist, clip_fraction, keep)
+    qc = synth.derive_qconfig(modeldict, effective, n_layers, synth.PRECISIONS[quantization])
+    for k in ("x_re", "x_im"):
+        qc["blocks"]["ssm"]["activations"][k]["exp"] -= state_headroom_bits
+    synth.cap_result_exponents(qc)
+    synth._assert_exps_nonnegative(qc)
+    return stats, hist, effective, qc
+
+
+def quantiser_of(key: str, fxp_qconfig: dict) -> Tuple[int, int]:
+    """(bits, exp) of the entry of ``fxp_qconfig`` that quantises the tensor observed under ``key``."""
+    parts = key.split(".")
+    if parts[0] in ("encoder", "decoder"):
+        d = fxp_qconfig[parts[0]]
+        return int(d[f"{parts[1]}_bits"]), int(d[f"{parts[1]}_exp"])
+    b = fxp_qconfig["blocks"]
+    if parts[1] == "out2":
+        return int(b["out2"][f"{parts[2]}_bits"]), int(b["out2"][f"{parts[2]}_exp"])
+    if parts[1] == "gate":
+        return int(b["multgate"][f"{parts[2]}_bits"]), int(b["multgate"][f"{parts[2]}_exp"])
+    a = b["ssm"]["activations"][parts[1]]
+    return int(a["bits"]), int(a["exp"])
+
+
+def range_report(hist: dict, fxp_qconfig: dict, n_layers: int) -> Dict[str, dict]:
+    """Per observed tensor, what its quantiser (``quantiser_of``: bits, exp) does to the calibration set:
+    ``total`` values seen, ``saturates`` = T(bits - 1 - exp) / total, the share with |v| >= 2^(bits - 1 - exp), and
+    ``below_lsb`` = 1 - T(-exp) / total, the share with |v| < 2^-exp.  Exact but for one case: a value equal to
+    -2^(bits - 1 - exp) is representable and is counted as saturating.  ``ValueError`` for a threshold outside 2^-39 .. 2^23."""
+    out = {}
+    for key in stat_keys(n_layers):
+        bits, exp = quantiser_of(key, fxp_qconfig)
+        row = np.asarray(hist[key], dtype=np.int64)
+        total = int(row.sum())
+        sat, lsb = tail_count(row, bits - 1 - exp), tail_count(row, -exp)
+        out[key] = dict(total=total, saturates=sat / total if total else 0.0, below_lsb=1.0 - lsb / total if total else 0.0)
+    return out

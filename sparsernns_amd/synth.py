@@ -146,8 +146,9 @@ def zoh(mixer: dict):
 
 
 def float_forward(modeldict: dict, x: np.ndarray, n_layers: int, calibrate_bn: bool = False,
-                  stats: Optional[dict] = None, activations: Optional[dict] = None) -> np.ndarray:
-    """x: (B,L,d_in) float32.  Records absmax observers into ``stats`` when given, and -- for the verification report
+                  stats: Optional[dict] = None, activations: Optional[dict] = None, hist: Optional[dict] = None) -> np.ndarray:
+    """x: (B,L,d_in) float32.  Records absmax observers into ``stats`` when given, adds the exponent histogram of every
+    observed tensor (``floatmodel.exp_hist``, int64[64]) to ``hist`` under the same key when given, and -- for the verification report
     (sparsernns_amd/fxpreporter.py) -- the float intermediates of sequence 0 into ``activations`` under the keys the
     reference's float model sows (sparseRNNs/model/layers.py:181-243: input, pre_s5, pre_C, pre_GLU, out2/__call__, the
     layer's __call__; ssm.py: mixer/__call__, B_bar; post_GLU = the second drop/__call__ that fxprun.py:688-698 reads)."""
@@ -155,6 +156,9 @@ def float_forward(modeldict: dict, x: np.ndarray, n_layers: int, calibrate_bn: b
     def obs(key, v):
         if stats is not None:
             stats[key] = max(stats.get(key, 0.0), float(np.abs(v).max()))
+        if hist is not None:
+            from .floatmodel import exp_hist
+            hist[key] = hist.get(key, 0) + exp_hist(v)
 
     enc = modeldict["encoder"]
     obs("encoder.inp", x)
