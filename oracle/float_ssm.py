@@ -1,7 +1,8 @@
 """oracle/float_ssm.py -- TEST INFRASTRUCTURE: CPU restatement of the FLOAT model's SSM (sparseRNNs/model/ssm.py).
 
-Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this.  PARITY UNPINNED: the reference
-needs JAX (absent here) and holds no fixtures for this path; what is restated is
+Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this.  PARITY UNPINNED: this is the
+FLOAT model, which needs flax and jax.lax.associative_scan -- outside what the NumPy stand-in for the reference's integer
+files covers (oracle/jaxlike.py) -- and the reference holds no fixtures for it; what is restated is
   * binary_operator                (ssm.py:54-77 with identity quantisers: (A_j A_i, A_j b_i + b_j), complex64)
   * jax.lax.associative_scan       (third-party, jax >= 0.5.0 per pyproject.toml:26; its published algorithm: combine
                                     adjacent pairs, scan the half-length sequence recursively, interleave)

@@ -7,12 +7,14 @@ the HIP path can be checked; it is never the thing that is shipped or measured.
 Only ``tests/``, ``__graft_entry__.smoke()`` and the ``cpu_baseline`` leg of
 ``bench.py`` may import it.
 
-PARITY UNPINNED.  The reference has no tests, golden vectors or fixtures for this
-path and JAX is not installed in the build container (``import jax`` raises
-ModuleNotFoundError), so the reference itself cannot be run to pin this oracle.
-It is pinned only by (a) known-answer values derived by hand from the reference's
-formulas (tests/test_oracle_kat.py) and (b) bit-for-bit agreement with a second,
-independently written scalar C restatement (oracle/s5fxp_ref.c).
+PROGRAM LOGIC PINNED, ARITHMETIC PARITY UNPINNED.  JAX is not installed here, but the reference's
+own fxparray.py / fxputils.py / fxpmodel.py run in place under a strict NumPy stand-in
+(oracle/jaxlike.py, oracle/refload.py).  tests/golden/ref_* hold what they compute -- an op table
+and seven models with every named intermediate -- and tests/test_reference_pin.py holds this file
+to them, besides (a) known-answer values derived by hand from the reference's formulas
+(tests/test_oracle_kat.py) and (b) bit-for-bit agreement with a second, independently written
+scalar C restatement (oracle/s5fxp_ref.c).  What stays unpinned is XLA's arithmetic: the list
+below is encoded here and in the stand-in alike and cannot be checked against a real JAX offline.
 
 JAX semantics encoded here (reference runs with jax_enable_x64 off):
   * every integer array is int32, + - * << wrap modulo 2**32, >> is arithmetic;
@@ -129,10 +131,10 @@ def matmul32(a: np.ndarray, b: np.ndarray) -> np.ndarray:
 
 
 def f32_to_i32(x: np.ndarray) -> np.ndarray:
-    """XLA convert f32 -> s32: truncate toward zero, saturating."""
+    """XLA convert f32 -> s32: truncate toward zero, saturating; NaN gives 0."""
     x = np.asarray(x, dtype=F32)
     y = np.trunc(x.astype(np.float64))
-    y = np.clip(y, -(2.0**31), 2.0**31 - 1)
+    y = np.where(np.isnan(y), 0.0, np.clip(y, -(2.0**31), 2.0**31 - 1))
     return y.astype(np.int64).astype(I32)
 
 

@@ -6,10 +6,12 @@
  * oracle/_build/libs5fxp_ref.so and may be loaded only by tests/, __graft_entry__.smoke()
  * and the cpu_baseline leg of bench.py.  The product (sparsernns_amd/) never links it.
  *
- * PARITY UNPINNED: the reference (stevenabreu7/SparseRNNs) ships no tests or golden vectors
- * for this path and JAX is not installed here, so neither oracle half can be checked against
- * the reference itself; they are checked against hand-derived known answers and against each
- * other.
+ * PROGRAM LOGIC PINNED, ARITHMETIC PARITY UNPINNED: the reference (stevenabreu7/SparseRNNs) ships
+ * no tests or golden vectors for this path, but its own integer code runs in place under a NumPy
+ * stand-in for JAX (oracle/jaxlike.py); tests/test_reference_pin.py holds this file to the outputs
+ * and trace planes that run recorded (tests/golden/ref_*), next to hand-derived known answers and
+ * the other oracle half.  XLA's arithmetic itself (int32 wrap, float32 maxima and log2) is assumed
+ * as stated in oracle/jaxlike.py and cannot be checked against a real JAX here.
  *
  * It consumes the INTEGER model (what the reference's export() emits: fxpmodel.py:368-393,
  * 819-847,946-968,1163-1207) and follows, op by op:

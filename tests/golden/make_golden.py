@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Generates the golden fixtures under tests/golden/ (committed; rerun only when the spec changes).
 
-PARITY UNPINNED: the reference cannot run here (no JAX), so these vectors come from
-the CPU oracle (oracle/fxp_oracle.py), which both oracle halves and the HIP path must then reproduce
-bit for bit.  They pin the semantics against regressions; they are not reference outputs.
+These vectors come from the CPU oracle (oracle/fxp_oracle.py), which both oracle halves and the HIP path
+must then reproduce bit for bit.  They pin the semantics against regressions; they are NOT reference outputs
+-- those are tests/golden/ref_*, written by make_reference_golden.py from the reference's own integer code
+run under a NumPy stand-in for JAX.  PARITY UNPINNED only in what that stand-in has to assume: XLA's
+arithmetic (oracle/jaxlike.py lists it), which cannot be checked offline.
 
 Each fixture holds: the float modeldict leaves + fxp_qconfig (json), the integer input, every
 intermediate the oracle names, and the output.

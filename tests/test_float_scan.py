@@ -3,7 +3,7 @@
 Floating point: the tolerance is stated here.  A prefix sum's rounding depends on its combination tree (the reference's is
 jax.lax.associative_scan's, ours is segment folds + sweeps over the segment aggregates), so the bar is: every state within
 TOL * max|x| of the float64 sequential recurrence, and no further from it than a few times the error of the oracle's
-complex64 restatement of the reference's own tree.  PARITY UNPINNED (no JAX here, no reference fixtures for this path).
+complex64 restatement of the reference's own tree.  PARITY UNPINNED (the float model: outside the stand-in that pins the integer path; no reference fixtures).
 """
 import numpy as np
 import pytest
