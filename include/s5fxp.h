@@ -691,6 +691,22 @@ int s5fxp_float_model_forward_hist(const s5fxp_float_model *m, const float *x, i
                                    unsigned long long *hist, float *trace, void *workspace, size_t workspace_bytes,
                                    void *stream);
 
+/* The float forward over n CLIPS OF DIFFERENT LENGTHS in the same 2 + 3 * n_layers launches.
+ * x: (n,Lmax,257) float32 device, padded; y: (n,Lmax,257) float32 device, padded.
+ * lens: n int32 in DEVICE memory, exactly what s5fxp_stft_mag_clips writes; clip e has len_e = clamp(lens[e], 0, Lmax) frames.
+ * Rows t < len_e of y, and what stats and hist receive, are bit for bit those of s5fxp_float_model_forward[_hist] on clip e
+ * alone (B = 1, L = len_e).  Rows from len_e on of x are never read and of y never written, and no padding row enters an
+ * observer or a histogram: a clip with len_e == 0 leaves y untouched and contributes nothing, and a launch whose clips are
+ * all empty returns 0 and changes nothing.
+ * stats, hist: as in s5fxp_float_model_forward_hist -- NULL switches each off, stats is only raised, hist only added to; with
+ * hist == NULL the kernels without the histogram run, and y and stats are bit-identical with and without hist.
+ * workspace: s5fxp_float_workspace_bytes(m, n, Lmax, 0).  There are no trace planes.
+ * Errors, all before the device is touched: S5FXP_EBADARG for a null model / x / y / lens / workspace, for n < 1 or Lmax < 1,
+ * for a hist that is not 8-byte aligned, and, when hist is given, for an n * ceil(Lmax / 32) at which the wrap rule above is
+ * reached (tiles = n * ceil(Lmax / 32)); S5FXP_EWORKSPACE for a workspace that is too small. */
+int s5fxp_float_model_clips(const s5fxp_float_model *m, const float *x, int n, int Lmax, const int32_t *lens, float *y,
+                            float *stats, unsigned long long *hist, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -181,6 +181,7 @@ def _load():
         "s5fxp_float_trace_bytes": (C.c_size_t, [p, i, i]),
         "s5fxp_float_model_forward": (i, [p, p, i, i, p, p, p, p, C.c_size_t, p]),
         "s5fxp_float_model_forward_hist": (i, [p, p, i, i, p, p, p, p, p, C.c_size_t, p]),
+        "s5fxp_float_model_clips": (i, [p, p, i, i, p, p, p, p, p, C.c_size_t, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale: rebuild
@@ -203,7 +204,7 @@ EXPORTED_SYMBOLS = ("s5fxp_version s5fxp_strerror s5fxp_from_fp s5fxp_to_float s
                     "s5fxp_stft_mag_clips s5fxp_mask_istft_clips s5fxp_score_clips_workspace_bytes s5fxp_mask_istft_score_clips "
                     "s5fxp_float_model_blob_bytes s5fxp_float_model_pack s5fxp_float_model_create s5fxp_float_model_destroy "
                     "s5fxp_float_workspace_bytes s5fxp_float_trace_bytes s5fxp_float_model_forward "
-                    "s5fxp_float_model_forward_hist").split()
+                    "s5fxp_float_model_forward_hist s5fxp_float_model_clips").split()
 
 
 def check(rc: int, what: str = "") -> None:

@@ -594,6 +594,64 @@ def validate_clips(model, inp_bits: int, inp_exp: int, noisy_clips, clean_clips,
     return score_clips(audio, clean, samples, mask, lam)[:2]
 
 
+def _float_clips_front(float_engine, clips, one_launch: bool = True):
+    """``_clips_front`` with the FLOAT model in the middle: the same checks of the clip list, and where every clip lies on the
+    engine's device the padding, ``stft_mag_clips`` and ``FloatEngine.forward_clips_device`` on those very tensors.  Returns
+    (clips, front), front = (audio, samples, x, mask, L) or None for the per-clip route (and for an empty list)."""
+    clips = [torch.as_tensor(c) for c in clips]
+    for c in clips:
+        if c.dim() != 1:
+            raise ValueError(f"every clip must be 1-D audio, got {tuple(c.shape)}")
+        stft_frames(int(c.shape[0]))
+    if not clips or not one_launch or not float_engine.on_device or not all(c.is_cuda and c.device == float_engine.device for c in clips):
+        return clips, None
+    Ts = [int(c.shape[0]) for c in clips]
+    audio = torch.nn.utils.rnn.pad_sequence([c.to(torch.float32) for c in clips], batch_first=True)
+    samples = torch.tensor(Ts, dtype=torch.int32, device=audio.device)
+    with torch.cuda.device(audio.device):
+        x, lens = stft_mag_clips(audio, samples)
+        mask = float_engine.forward_clips_device(x, lens)
+    return clips, (audio, samples, x, mask, [stft_frames(T) for T in Ts])
+
+
+def denoise_float_clips(float_engine, clips):
+    """``denoise_float`` for a list of 1-D float audio clips of any lengths >= 512 (below: NotImplementedError, before any
+    launch; an empty list gives []).  Returns what ``denoise_clips`` returns, per clip (cleaned ((len_e - 1) * 128,),
+    cleaned_mag, x, mask): bit for bit the tuple ``denoise_float(float_engine, clip[None])`` returns, without the batch axis.
+    With the engine and every clip on one GPU that is ``stft_mag_clips`` -> ``FloatEngine.forward_clips_device`` ->
+    ``mask_istft_clips``, whatever n; otherwise ``denoise_float`` clip by clip."""
+    clips, front = _float_clips_front(float_engine, clips)
+    if front is None:
+        return [tuple(t[0] for t in denoise_float(float_engine, c[None])) for c in clips]
+    audio, samples, x, mask, L = front
+    cleaned, cm = mask_istft_clips(audio, samples, mask, cleaned_mag=True)
+    return [(cleaned[e, :(L[e] - 1) * HOP], cm[e, :L[e]], x[e, :L[e]], mask[e, :L[e]]) for e in range(len(clips))]
+
+
+def validate_float_clips(float_engine, noisy_clips, clean_clips, lam: float = 0.001):
+    """``validate_float`` for lists of 1-D float audio clips, with ``validate_clips``' checks of the two lists -> (loss, si_snr),
+    (n,) float32 each (two empty tensors for empty lists): per clip bit for bit
+    ``validate_float(float_engine, noisy[None], clean[None], lam)``.  With the engine and all clips on one GPU that is
+    ``stft_mag_clips`` -> ``FloatEngine.forward_clips_device`` -> ``score_clips``; otherwise ``validate_float`` clip by clip.
+    The difference to ``validate_clips`` on the same clips is the cost of quantisation in dB."""
+    noisy_clips, clean_clips = list(noisy_clips), [torch.as_tensor(c) for c in clean_clips]
+    if len(noisy_clips) != len(clean_clips):
+        raise ValueError(f"{len(noisy_clips)} noisy clips but {len(clean_clips)} clean ones")
+    for e, (c, r) in enumerate(zip(noisy_clips, clean_clips)):
+        if tuple(r.shape) != tuple(torch.as_tensor(c).shape):
+            raise ValueError(f"clean clip {e} must be {tuple(torch.as_tensor(c).shape)}, got {tuple(r.shape)}")
+    same_device = all(r.device == torch.as_tensor(c).device for c, r in zip(noisy_clips, clean_clips))
+    noisy_clips, front = _float_clips_front(float_engine, noisy_clips, one_launch=same_device)
+    if not noisy_clips:
+        return torch.empty(0, dtype=torch.float32), torch.empty(0, dtype=torch.float32)
+    if front is None:
+        r = [validate_float(float_engine, c[None], k[None], lam) for c, k in zip(noisy_clips, clean_clips)]
+        return torch.cat([t[0] for t in r]), torch.cat([t[1] for t in r])
+    audio, samples, _, mask, _ = front
+    clean = torch.nn.utils.rnn.pad_sequence([c.to(torch.float32) for c in clean_clips], batch_first=True)
+    return score_clips(audio, clean, samples, mask, lam)[:2]
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # The loop for a live signal: csrc/audio_stream.hpp (s5fxp_stream_stft / s5fxp_stream_mask_istft) either side of
 # SessionPool.push.

@@ -25,7 +25,12 @@
 // one observer; the entry refuses (S5FXP_EBADARG) an N at which that reaches 2^32 (fm_hist_rows_ok), so no flush is needed
 // before the end.
 //
-// The four kernels are written once, in float_model_kernels.inc, which this header includes twice: with FM_HIST 0 it gives
+// CLIPS (the k_*_clips and k_*_clips_hist kernels) run n clips of different lengths, padded to Lmax rows each, in
+// one launch: a tile belongs to one clip (FClipMap), holds the rows the clip has there and is skipped when it has none, so
+// every clip gets bit for bit what the rectangular kernels give it alone and no padding row is read, written or observed.
+// They are two more inclusions of float_model_kernels.inc (FM_CLIPS 1), for the reason given below for FM_HIST.
+//
+// The four kernels are written once, in float_model_kernels.inc, which this header includes once per form: with FM_HIST 0 it gives
 // k_fenc, k_fbproj, k_fgate, k_fdec -- token for token the kernels as they were before the histogram, so their instruction
 // streams do not move -- and with FM_HIST 1 k_fenc_hist, ... with one more argument.  The flag is a preprocessor one and not
 // a template parameter because both alternatives change the existing kernels: a template parameter changes their mangled
@@ -212,12 +217,47 @@ struct FDecArgs {
     long long N;
 };
 
+// a clip-form launch: tile i of n * tpc belongs to clip i / tpc at t0 = 32 * (i % tpc), so no tile straddles two clips
+struct FClipMap {
+    const int *lens; // (n) device; clamped to 0..Lmax where it is read
+    int Lmax, tpc;   // rows per clip of every plane; tpc = ceil(Lmax / 32)
+    long long tiles; // n * tpc
+};
+
+// FM_TILES: the launch's tile count.  FM_TILE: declares the tile's first row r0 and its valid row prefix `rows`.
+#define FM_TILES_RECT(N) (((N) + FM_FT - 1) / FM_FT)
+#define FM_TILE_RECT(tile, N, r0, rows)   \
+    const long long r0 = tile * FM_FT; \
+    const int rows = (int)(N - r0 < FM_FT ? N - r0 : FM_FT)
+// the clip's tile: rows = clamp(len - t0, 0, 32) stays a contiguous prefix; a tile without rows is left before its first
+// load (workgroup-uniform, so the barriers stay matched)
+#define FM_TILE_CLIP(tile, N, r0, rows)                                                              \
+    const int clip_ = (int)(tile / cm.tpc), t0_ = FM_FT * (int)(tile - (long long)clip_ * cm.tpc); \
+    const int raw_ = cm.lens[clip_], len_ = raw_ < cm.Lmax ? raw_ : cm.Lmax;                         \
+    const int rows = len_ - t0_ < FM_FT ? len_ - t0_ : FM_FT;                                        \
+    if (rows <= 0) continue;                                                                         \
+    const long long r0 = (long long)clip_ * cm.Lmax + t0_
+
+#define FM_HIST_OFF_BEGIN(planes)
+#define FM_HIST_OFF_ADD(plane, v)
+#define FM_HIST_OFF_END(...)
+#define FM_HIST_ON_BEGIN(planes)                    \
+    unsigned *const shist = fm_hist_lds<planes>(); \
+    fm_hist_zero<planes>(shist)
+#define FM_HIST_ON_ADD(plane, v) fm_hist_add(shist, plane, v)
+#define FM_HIST_ON_END(...) fm_hist_flush<__VA_ARGS__>(shist, hist)
+
 #define FM_HIST 0
+#define FM_CLIPS 0
 #define FM_KERNEL(name) name
+#define FM_CLIPS_PARAM
 #define FM_HIST_PARAM
-#define FM_HIST_BEGIN(planes)
-#define FM_HIST_ADD(plane, v)
-#define FM_HIST_END(...)
+#define FM_TILES FM_TILES_RECT
+#define FM_TILE FM_TILE_RECT
+#define FM_GATE_ATTR
+#define FM_HIST_BEGIN FM_HIST_OFF_BEGIN
+#define FM_HIST_ADD FM_HIST_OFF_ADD
+#define FM_HIST_END FM_HIST_OFF_END
 #include "float_model_kernels.inc"
 #undef FM_HIST
 #undef FM_KERNEL
@@ -229,15 +269,60 @@ struct FDecArgs {
 #define FM_HIST 1
 #define FM_KERNEL(name) name##_hist
 #define FM_HIST_PARAM , unsigned long long *hist
-#define FM_HIST_BEGIN(planes)                       \
-    unsigned *const shist = fm_hist_lds<planes>(); \
-    fm_hist_zero<planes>(shist)
-#define FM_HIST_ADD(plane, v) fm_hist_add(shist, plane, v)
-#define FM_HIST_END(...) fm_hist_flush<__VA_ARGS__>(shist, hist)
+#define FM_HIST_BEGIN FM_HIST_ON_BEGIN
+#define FM_HIST_ADD FM_HIST_ON_ADD
+#define FM_HIST_END FM_HIST_ON_END
+#include "float_model_kernels.inc"
+#undef FM_HIST
+#undef FM_CLIPS
+#undef FM_KERNEL
+#undef FM_CLIPS_PARAM
+#undef FM_HIST_PARAM
+#undef FM_TILES
+#undef FM_TILE
+#undef FM_GATE_ATTR
+#undef FM_HIST_BEGIN
+#undef FM_HIST_ADD
+#undef FM_HIST_END
+
+// the clip forms: the same text over FClipMap's tile mapping
+#define FM_HIST 0
+#define FM_CLIPS 1
+#define FM_KERNEL(name) name##_clips
+#define FM_CLIPS_PARAM , FClipMap cm
+#define FM_HIST_PARAM
+#define FM_TILES(N) cm.tiles
+#define FM_TILE FM_TILE_CLIP
+// the clip mapping's row addresses cost k_fgate_clips<2> ten VGPRs (246 for the rectangular kernel's 236), one granule past
+// two waves per SIMD, and at one wave it ran 196 us for the rectangular kernel's 122; asked for two, the allocator fits 240
+// without scratch
+#define FM_GATE_ATTR __attribute__((amdgpu_waves_per_eu(DS == 2 ? 2 : 1)))
+#define FM_HIST_BEGIN FM_HIST_OFF_BEGIN
+#define FM_HIST_ADD FM_HIST_OFF_ADD
+#define FM_HIST_END FM_HIST_OFF_END
 #include "float_model_kernels.inc"
 #undef FM_HIST
 #undef FM_KERNEL
 #undef FM_HIST_PARAM
+#undef FM_HIST_BEGIN
+#undef FM_HIST_ADD
+#undef FM_HIST_END
+
+#define FM_HIST 1
+#define FM_KERNEL(name) name##_clips_hist
+#define FM_HIST_PARAM , unsigned long long *hist
+#define FM_HIST_BEGIN FM_HIST_ON_BEGIN
+#define FM_HIST_ADD FM_HIST_ON_ADD
+#define FM_HIST_END FM_HIST_ON_END
+#include "float_model_kernels.inc"
+#undef FM_HIST
+#undef FM_CLIPS
+#undef FM_KERNEL
+#undef FM_CLIPS_PARAM
+#undef FM_HIST_PARAM
+#undef FM_TILES
+#undef FM_TILE
+#undef FM_GATE_ATTR
 #undef FM_HIST_BEGIN
 #undef FM_HIST_ADD
 #undef FM_HIST_END

@@ -1,14 +1,16 @@
-// float_model_kernels.inc -- the float model's four tile kernels, included by float_model.hpp twice (no include guard):
+// float_model_kernels.inc -- the float model's four tile kernels, included by float_model.hpp four times (no include guard):
 // FM_HIST 0 gives k_fenc / k_fbproj / k_fgate / k_fdec, FM_HIST 1 gives k_fenc_hist / ... which take `hist` as well and count
 // every value into its observer's exponent histogram where it enters the observer.  With FM_HIST 0 every FM_HIST_* macro is
-// empty.  Not a translation unit of its own; everything it uses is declared in float_model.hpp, inside namespace s5.
+// empty.  FM_CLIPS 1 gives k_fenc_clips / ... and k_fenc_clips_hist / ..., which take an FClipMap as well: FM_TILES and
+// FM_TILE then map a tile to a clip's rows (and skip it when the clip has none there) instead of to rows 32*tile.. of N.
+// Not a translation unit of its own; everything it uses is declared in float_model.hpp, inside namespace s5.
 
 // ------------------------------------------------------------------------------------------------------------------
 // encoder: h = relu(x W + b); observers [0] encoder.inp, [1] encoder.out (before the ReLU)
 // ------------------------------------------------------------------------------------------------------------------
 
 template <int DS>
-__global__ __launch_bounds__(256) void FM_KERNEL(k_fenc)(FEncArgs a FM_HIST_PARAM) // hist: rows encoder.inp, encoder.out
+__global__ __launch_bounds__(256) void FM_KERNEL(k_fenc)(FEncArgs a FM_CLIPS_PARAM FM_HIST_PARAM) // hist: rows encoder.inp, encoder.out
 {
     constexpr int H = 48 * DS, HT = 3 * DS, NT = (HT + 3) / 4, KS = FM_KENC / 4, LDA = fm_lda(FM_KENC);
     __shared__ float sx[FM_FT * LDA];
@@ -24,10 +26,9 @@ __global__ __launch_bounds__(256) void FM_KERNEL(k_fenc)(FEncArgs a FM_HIST_PARA
         bias[nt] = t < HT ? a.b[t * 16 + (lane & 15)] : 0.f;
     }
     unsigned om[2] = {0u, 0u};
-    const long long tiles = (a.N + FM_FT - 1) / FM_FT;
+    const long long tiles = FM_TILES(a.N);
     for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const long long r0 = tile * FM_FT;
-        const int rows = (int)(a.N - r0 < FM_FT ? a.N - r0 : FM_FT);
+        FM_TILE(tile, a.N, r0, rows); // const long long r0, const int rows: the tile's first row and its valid prefix
         // rows are 257 floats: dword loads, all of a thread's issued before the first is used.  Addresses are clamped into the
         // tile's valid rows and columns, so no load is conditional; what lies outside is replaced by zero afterwards.
         const float *src = a.x + (size_t)r0 * FM_DIN;
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(256) void FM_KERNEL(k_fenc)(FEncArgs a FM_HIST_PARA
 // ------------------------------------------------------------------------------------------------------------------
 
 template <int DS, bool TRACE>
-__global__ __launch_bounds__(256) void FM_KERNEL(k_fbproj)(FBprojArgs a FM_HIST_PARAM) // hist: rows u, Bu_re, Bu_im
+__global__ __launch_bounds__(256) void FM_KERNEL(k_fbproj)(FBprojArgs a FM_CLIPS_PARAM FM_HIST_PARAM) // hist: rows u, Bu_re, Bu_im
 {
     constexpr int H = 48 * DS, P2 = 64 * DS, PT = 4 * DS, NT = DS, KS = H / 4, LDA = fm_lda(H);
     __shared__ float su[FM_FT * LDA];
@@ -97,10 +98,9 @@ __global__ __launch_bounds__(256) void FM_KERNEL(k_fbproj)(FBprojArgs a FM_HIST_
     }
     __syncthreads();
     unsigned om_u = 0u, om_bu = 0u; // a lane's Bu columns all have the lane's parity: even = re, odd = im
-    const long long tiles = (a.N + FM_FT - 1) / FM_FT;
+    const long long tiles = FM_TILES(a.N);
     for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const long long r0 = tile * FM_FT;
-        const int rows = (int)(a.N - r0 < FM_FT ? a.N - r0 : FM_FT);
+        FM_TILE(tile, a.N, r0, rows); // const long long r0, const int rows: the tile's first row and its valid prefix
         for (int i = threadIdx.x; i < FM_FT * (H / 4); i += 256) {
             const int r = i / (H / 4), c = (i - r * (H / 4)) * 4;
             float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void FM_KERNEL(k_fbproj)(FBprojArgs a FM_HIST_
 // ------------------------------------------------------------------------------------------------------------------
 
 template <int DS, bool TRACE>
-__global__ __launch_bounds__(256) void FM_KERNEL(k_fgate)(FGateArgs a FM_HIST_PARAM) // hist: the layer's rows x_re .. gate.r
+__global__ __launch_bounds__(256) FM_GATE_ATTR void FM_KERNEL(k_fgate)(FGateArgs a FM_CLIPS_PARAM FM_HIST_PARAM) // hist: the layer's rows x_re .. gate.r
 {
     constexpr int H = 48 * DS, P = 32 * DS, P2 = 64 * DS, HT = 3 * DS, NT = (HT + 3) / 4, KS1 = P2 / 4, KS2 = H / 4;
     constexpr int LD1 = fm_lda(P2), LDH = fm_lda(H);
@@ -172,10 +172,9 @@ __global__ __launch_bounds__(256) void FM_KERNEL(k_fgate)(FGateArgs a FM_HIST_PA
     }
     __syncthreads();
     unsigned o_xre = 0u, o_xim = 0u, o_y = 0u, o_x1 = 0u, o_gin = 0u, o_g = 0u;
-    const long long tiles = (a.N + FM_FT - 1) / FM_FT;
+    const long long tiles = FM_TILES(a.N);
     for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const long long r0 = tile * FM_FT;
-        const int rows = (int)(a.N - r0 < FM_FT ? a.N - r0 : FM_FT);
+        FM_TILE(tile, a.N, r0, rows); // const long long r0, const int rows: the tile's first row and its valid prefix
         for (int i = threadIdx.x; i < FM_FT * P; i += 256) {
             const int r = i / P, p = i - r * P;
             float2 v = make_float2(0.f, 0.f);
@@ -263,7 +262,7 @@ __global__ __launch_bounds__(256) void FM_KERNEL(k_fgate)(FGateArgs a FM_HIST_PA
 // ------------------------------------------------------------------------------------------------------------------
 
 template <int DS>
-__global__ __launch_bounds__(256) void FM_KERNEL(k_fdec)(FDecArgs a FM_HIST_PARAM) // hist: rows decoder.inp, decoder.out
+__global__ __launch_bounds__(256) void FM_KERNEL(k_fdec)(FDecArgs a FM_CLIPS_PARAM FM_HIST_PARAM) // hist: rows decoder.inp, decoder.out
 {
     constexpr int H = 48 * DS, NT = (FM_DEC_TILES + 3) / 4, KS = H / 4, LDA = fm_lda(H);
     __shared__ float sh[FM_FT * LDA];
@@ -279,10 +278,9 @@ __global__ __launch_bounds__(256) void FM_KERNEL(k_fdec)(FDecArgs a FM_HIST_PARA
         bias[nt] = t < FM_DEC_TILES ? a.b[t * 16 + (lane & 15)] : 0.f;
     }
     unsigned om[2] = {0u, 0u};
-    const long long tiles = (a.N + FM_FT - 1) / FM_FT;
+    const long long tiles = FM_TILES(a.N);
     for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const long long r0 = tile * FM_FT;
-        const int rows = (int)(a.N - r0 < FM_FT ? a.N - r0 : FM_FT);
+        FM_TILE(tile, a.N, r0, rows); // const long long r0, const int rows: the tile's first row and its valid prefix
         for (int i = threadIdx.x; i < FM_FT * (H / 4); i += 256) {
             const int r = i / (H / 4), c = (i - r * (H / 4)) * 4;
             float4 h = make_float4(0.f, 0.f, 0.f, 0.f);

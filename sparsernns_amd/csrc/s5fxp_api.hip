@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <numeric>
 #include <vector>
 
 using namespace s5;
@@ -1426,7 +1427,80 @@ int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, floa
     return launch_rc();
 }
 
+#define S5_K_FENC_C(ds) k_fenc_clips<ds>
+#define S5_K_FDEC_C(ds) k_fdec_clips<ds>
+#define S5_K_FBPROJ_C(ds) k_fbproj_clips<ds, false>
+#define S5_K_FGATE_C(ds) k_fgate_clips<ds, false>
+#define S5_K_FENC_CH(ds) k_fenc_clips_hist<ds>
+#define S5_K_FDEC_CH(ds) k_fdec_clips_hist<ds>
+#define S5_K_FBPROJ_CH(ds) k_fbproj_clips_hist<ds, false>
+#define S5_K_FGATE_CH(ds) k_fgate_clips_hist<ds, false>
+
+// the clip forward: the same eleven-kernel chain over tiles that belong to one clip each; no trace planes
+int float_forward_clips(const s5fxp_float_model *m, const float *x, int n, int Lmax, const int32_t *lens, float *y, float *stats,
+                        unsigned long long *hist, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!m || !x || !y || !lens || !workspace || n < 1 || Lmax < 1) return S5FXP_EBADARG;
+    if (reinterpret_cast<uintptr_t>(hist) % sizeof(unsigned long long)) return S5FXP_EBADARG;
+    const int tpc = (int)(((long long)Lmax + FM_FT - 1) / FM_FT);
+    const long long N = (long long)n * Lmax, tiles = (long long)n * tpc;
+    unsigned grid = (unsigned)(tiles < FM_GRID_CAP ? tiles : FM_GRID_CAP);
+    // A stride that shares a factor with tpc ties a workgroup to few tile positions: at 512 and tpc = 16 it would see the same
+    // position of every clip it visits, the workgroups of the early positions all the work and those of the late ones next to
+    // none.  A stride coprime to tpc walks every workgroup through all positions.
+    if (tiles > grid)
+        while (std::gcd(grid, (unsigned)tpc) != 1) --grid;
+    if (hist && !fm_hist_rows_ok(tiles, grid)) return S5FXP_EBADARG; // a 32-bit LDS counter could wrap
+    if (workspace_bytes < s5fxp_float_workspace_bytes(m, n, Lmax, 0)) return S5FXP_EWORKSPACE;
+    const int64_t scan_grid = (int64_t)n * ((m->P + ASSOC_PT - 1) / ASSOC_PT);
+    if (scan_grid > 0x7fffffffll) return S5FXP_EBADARG;
+    const size_t NH = (size_t)N * m->H, NP2 = (size_t)N * 2 * m->P;
+    hipStream_t st = S(stream);
+    unsigned *obs = reinterpret_cast<unsigned *>(stats);
+    float *ws = static_cast<float *>(workspace);
+    float *hbuf[2] = {ws, ws + NH};
+    float *bu = ws + 2 * NH, *xs = bu + NP2;
+    const FClipMap cm{lens, Lmax, tpc, tiles};
+    int rc;
+
+    float *h = hbuf[0];
+    FEncArgs ea{x, m->enc_w, m->enc_b, h, obs, N};
+    if (hist) S5_DISPATCH_DS(m->DS, S5_K_FENC_CH, grid, st, ea, cm, hist);
+    else S5_DISPATCH_DS(m->DS, S5_K_FENC_C, grid, st, ea, cm);
+    if ((rc = launch_rc())) return rc;
+    for (int i = 0; i < m->n_layers; ++i) {
+        const s5fxp_float_model::Layer &l = m->layers[i];
+        float *hout = hbuf[(i + 1) & 1];
+        unsigned *lo = obs ? obs + 2 + 10 * i : nullptr;
+        unsigned long long *lh = hist ? hist + (size_t)(2 + 10 * i) * FM_HIST_BINS : nullptr;
+        FBprojArgs ba{h, l.nm, l.bcat, bu, nullptr, lo, N};
+        if (hist) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_CH, grid, st, ba, cm, lh);
+        else S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_C, grid, st, ba, cm);
+        if ((rc = launch_rc())) return rc;
+        ScanAssocClipsArgs sa{reinterpret_cast<const float2 *>(l.lam), reinterpret_cast<const float2 *>(bu),
+                              reinterpret_cast<float2 *>(xs), lens, n, Lmax, m->P};
+        hipLaunchKernelGGL(k_scan_assoc_c64_clips, dim3((unsigned)scan_grid), dim3(64 * ASSOC_WAVES), 0, st, sa);
+        if ((rc = launch_rc())) return rc;
+        FGateArgs ga{xs, h, l.nm, l.ccat, l.D, l.w2, l.b2, hout, nullptr, nullptr, nullptr, lo ? lo + 3 : nullptr, N};
+        if (hist) S5_DISPATCH_DS(m->DS, S5_K_FGATE_CH, grid, st, ga, cm, lh + 3 * FM_HIST_BINS);
+        else S5_DISPATCH_DS(m->DS, S5_K_FGATE_C, grid, st, ga, cm);
+        if ((rc = launch_rc())) return rc;
+        h = hout;
+    }
+    FDecArgs da{h, m->dec_w, m->dec_b, y, obs ? obs + 2 + 10 * m->n_layers : nullptr, N};
+    if (hist) S5_DISPATCH_DS(m->DS, S5_K_FDEC_CH, grid, st, da, cm, hist + (size_t)(2 + 10 * m->n_layers) * FM_HIST_BINS);
+    else S5_DISPATCH_DS(m->DS, S5_K_FDEC_C, grid, st, da, cm);
+    return launch_rc();
+}
+
 } // namespace
+
+extern "C" int s5fxp_float_model_clips(const s5fxp_float_model *m, const float *x, int n, int Lmax, const int32_t *lens, float *y,
+                                       float *stats, unsigned long long *hist, void *workspace, size_t workspace_bytes,
+                                       void *stream)
+{
+    return float_forward_clips(m, x, n, Lmax, lens, y, stats, hist, workspace, workspace_bytes, stream);
+}
 
 extern "C" size_t s5fxp_float_model_blob_bytes(const s5fxp_float_model_desc *desc)
 {

@@ -127,4 +127,87 @@ __global__ __launch_bounds__(64 * ASSOC_WAVES) void k_scan_assoc_c64(ScanAssocAr
     if (a.x_last && live && have_last) a.x_last[(size_t)b * a.P + p] = make_float2(xlast.re, xlast.im);
 }
 
+// The clip form: sequence b runs over len = clamp(lens[b], 0, Lmax) steps of its Lmax-strided rows and touches nothing
+// past them.  Forward, from a zero state, no x_last.  The tree is organised by position (chunks from t = 0, segments of
+// 16 steps, steps past the end enter as zeros), and a state at step t is folded from the carry and u[0..t] alone, so what
+// it stores for t < len is bit for bit what k_scan_assoc_c64 stores for (B = 1, L = len): the statements below are that
+// kernel's with reverse = 0 and x0 = nullptr, and L replaced by len everywhere but in the sequence's stride.
+struct ScanAssocClipsArgs {
+    const float2 *lambda; // (P) complex64
+    const float2 *bu;     // (n,Lmax,P) complex64
+    float2 *xs;           // (n,Lmax,P)
+    const int32_t *lens;  // (n) device
+    int32_t n, Lmax, P;
+};
+
+__global__ __launch_bounds__(64 * ASSOC_WAVES) void k_scan_assoc_c64_clips(ScanAssocClipsArgs a)
+{
+    __shared__ cf32 agg[2][ASSOC_WAVES][ASSOC_PT];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pl = lane & 15, s4 = lane >> 4;
+    const int ptiles = (a.P + ASSOC_PT - 1) / ASSOC_PT;
+    const int b = blockIdx.x / ptiles, p = (blockIdx.x % ptiles) * ASSOC_PT + pl;
+    const int raw = a.lens[b], len = raw < 0 ? 0 : raw > a.Lmax ? a.Lmax : raw; // workgroup-uniform
+    if (len == 0) return;
+    const bool live = p < a.P;
+    const cf32 A = live ? cf32{a.lambda[p].x, a.lambda[p].y} : cf32{0.f, 0.f};
+    double pr = A.re, pi = A.im; // the powers of A as in k_scan_assoc_c64
+    cf32 A16, A32, A48, A64;
+#pragma unroll
+    for (int q = 1; q <= 6; ++q) {
+        const double r2 = pr * pr - pi * pi, i2 = 2.0 * pr * pi;
+        pr = r2; pi = i2;
+        if (q == 4) A16 = {(float)pr, (float)pi};
+        if (q == 5) A32 = {(float)pr, (float)pi};
+        if (q == 6) A64 = {(float)pr, (float)pi};
+    }
+    {
+        const double r16 = (double)A16.re, i16 = (double)A16.im, r32 = (double)A32.re, i32 = (double)A32.im;
+        A48 = {(float)(r16 * r32 - i16 * i32), (float)(r16 * i32 + i16 * r32)};
+    }
+    const cf32 Aseg = s4 == 0 ? cf32{1.f, 0.f} : s4 == 1 ? A16 : s4 == 2 ? A32 : A48;
+    const ptrdiff_t step = (ptrdiff_t)a.P;
+    const float2 *src = a.bu + (size_t)b * a.Lmax * (size_t)a.P + p;
+    float2 *dst = a.xs + (size_t)b * a.Lmax * (size_t)a.P + p;
+    cf32 carry{0.f, 0.f};
+    const int seg = wave * 4 + s4;
+    int buf = 0;
+    for (int t0 = 0; t0 < len; t0 += ASSOC_CHUNK, buf ^= 1) {
+        const int ts = t0 + seg * ASSOC_SEG;
+        const ptrdiff_t off0 = (ptrdiff_t)ts * step;
+        cf32 u[ASSOC_SEG];
+#pragma unroll
+        for (int k = 0; k < ASSOC_SEG; ++k) {
+            float2 v = make_float2(0.f, 0.f);
+            if (live && ts + k < len) v = src[off0 + k * step];
+            u[k] = {v.x, v.y};
+        }
+        cf32 e = u[0];
+#pragma unroll
+        for (int k = 1; k < ASSOC_SEG; ++k) e = cfma(A, e, u[k]);
+        cf32 inc = e, o = cshfl_up(inc, 16);
+        if (s4 >= 1) inc = cfma(A16, o, inc);
+        o = cshfl_up(inc, 32);
+        if (s4 >= 2) inc = cfma(A32, o, inc);
+        if (s4 == 3) agg[buf][wave][pl] = inc;
+        cf32 exc = cshfl_up(inc, 16);
+        if (s4 == 0) exc = {0.f, 0.f};
+        __syncthreads();
+        cf32 cw = carry, call = carry;
+#pragma unroll
+        for (int w = 0; w < ASSOC_WAVES; ++w) {
+            const cf32 g = agg[buf][w][pl];
+            call = cfma(A64, call, g);
+            if (w < wave) cw = call;
+        }
+        carry = call;
+        cf32 x = cfma(Aseg, cw, exc);
+#pragma unroll
+        for (int k = 0; k < ASSOC_SEG; ++k) {
+            x = cfma(A, x, u[k]);
+            if (live && ts + k < len) dst[off0 + k * step] = make_float2(x.re, x.im);
+        }
+    }
+}
+
 } // namespace s5

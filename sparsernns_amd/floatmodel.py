@@ -10,6 +10,10 @@ threshold of a fixed-point configuration is a power of two, so the histogram ans
 set saturates or falls below one LSB (``range_report``), and lets the calibration ignore a stated share of outliers
 (``clip_absmax``, ``calibrate_clipped``).
 
+Clips of different lengths go through in the same launches (``forward_clips``, ``forward_clips_device``): every
+clip gets what its own forward gives, and padding frames are never read, written or observed, so a calibration set that is
+ragged is calibrated on its real frames only (``calibrate`` / ``calibrate_clipped`` take ``(x, lens)`` pairs).
+
 Results agree with ``synth.float_forward`` to float32 rounding (the summation order differs), not bit for bit.  Without a
 GPU, or for a shape the kernels refuse, ``FloatEngine`` runs ``synth.float_forward`` itself and says so: ``on_device`` is False.
 """
@@ -198,6 +202,69 @@ class FloatEngine:
                       "s5fxp_float_model_forward_hist")
         return (y, tr, ws) if trace else y
 
+    def forward_clips_device(self, x: torch.Tensor, lens, stats_dev: Optional[torch.Tensor] = None,
+                             hist_dev: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """n clips of different lengths in the launches of ONE forward (``s5fxp_float_model_clips``): x
+        (n,Lmax,257) float32 on the device, padded; lens (n,) int32 on the device, as ``audio.stft_mag_clips`` writes it, clip e
+        having len_e = clamp(lens[e], 0, Lmax) frames -> y (n,Lmax,257).  y[e, :len_e], ``stats_dev`` and ``hist_dev`` get bit for
+        bit what ``forward_device(x[e:e+1, :len_e], ...)`` gives clip after clip: padding rows are never read, never written and
+        never observed.  ``out``: the tensor to write into; otherwise y is fresh and its padding unspecified.  Stream-ordered,
+        no sync."""
+        if not self.on_device:
+            raise RuntimeError("FloatEngine.forward_clips_device needs the kernels (on_device is False)")
+        if x.dim() != 3 or x.shape[2] != self.d_in or x.dtype != torch.float32 or x.device != self.device:
+            raise ValueError(f"x must be float32 (n, Lmax, {self.d_in}) on {self.device}, got {x.dtype} {tuple(x.shape)} on {x.device}")
+        n, Lmax = int(x.shape[0]), int(x.shape[1])
+        if not isinstance(lens, torch.Tensor) or lens.dtype != torch.int32 or tuple(lens.shape) != (n,) or lens.device != self.device:
+            raise ValueError(f"lens must be an int32 ({n},) tensor on {self.device}")
+        if stats_dev is not None and (stats_dev.dtype != torch.float32 or stats_dev.numel() != len(self.keys)
+                                      or stats_dev.device != self.device or not stats_dev.is_contiguous()):
+            raise ValueError(f"stats must be {len(self.keys)} contiguous float32 on {self.device}")
+        if hist_dev is not None and (hist_dev.dtype != torch.int64 or hist_dev.numel() != len(self.keys) * HIST_BINS
+                                     or hist_dev.device != self.device or not hist_dev.is_contiguous()):
+            raise ValueError(f"hist must be {len(self.keys)} x {HIST_BINS} contiguous int64 on {self.device}")
+        shape = (n, Lmax, self.d_out)
+        if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device
+                                or not out.is_contiguous()):
+            raise ValueError(f"out must be contiguous float32 {shape} on {self.device}")
+        x, lens = x.contiguous(), lens.contiguous()
+        y = out if out is not None else torch.empty(shape, dtype=torch.float32, device=self.device)
+        ws = self._workspace(n, Lmax, False)
+        with torch.cuda.device(self.device):
+            check(lib.s5fxp_float_model_clips(self._h, x.data_ptr(), n, Lmax, lens.data_ptr(), y.data_ptr(),
+                                              None if stats_dev is None else stats_dev.data_ptr(),
+                                              None if hist_dev is None else hist_dev.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                              torch.cuda.current_stream().cuda_stream), "s5fxp_float_model_clips")
+        return y
+
+    def forward_clips(self, clips, stats: Optional[dict] = None, hist: Optional[dict] = None) -> list:
+        """A list of (len_e, 257) float32 clips, NumPy arrays or tensors -> the list of the model's outputs, each of its clip's
+        kind: per clip what ``forward(clip[None])[0]`` returns, ``stats`` and ``hist`` updated as by those calls.  On the
+        device the clips are padded once and take ``forward_clips_device``; otherwise ``synth.float_forward`` runs clip by
+        clip."""
+        clips = list(clips)
+        for c in clips:
+            if len(c.shape) != 2 or c.shape[1] != self.d_in:
+                raise ValueError(f"every clip must be (len, {self.d_in}), got {tuple(c.shape)}")
+        if not self.on_device:
+            return [self.forward(c[None], stats=stats, hist=hist)[0] for c in clips]
+        if not clips:
+            return []
+        ls = [int(c.shape[0]) for c in clips]
+        x = torch.zeros(len(clips), max(max(ls), 1), self.d_in, dtype=torch.float32, device=self.device)
+        for e, c in enumerate(clips):
+            x[e, :ls[e]] = self._to_device(c)
+        st = self.new_stats() if stats is not None else None
+        hd = self.new_hist() if hist is not None else None
+        y = self.forward_clips_device(x, torch.tensor(ls, dtype=torch.int32, device=self.device), st, hd)
+        if hist is not None:
+            for k, row in self.hist_dict(hd).items():
+                hist[k] = hist.get(k, 0) + row
+        if stats is not None:
+            for k, v in self.stats_dict(st).items():
+                stats[k] = max(stats.get(k, 0.0), v)
+        return [y[e, :ls[e]].to(c.device) if isinstance(c, torch.Tensor) else y[e, :ls[e]].cpu().numpy() for e, c in enumerate(clips)]
+
     def forward_traced(self, x, hist: bool = False) -> dict:
         """Every plane of one forward, as device tensors: ``h_enc`` (B,L,H), ``out`` (B,L,257), ``stats`` (the observer array
         of this forward alone), with ``hist`` also ``hist`` (its histogram array), and per layer ``l{i}.u / y / g_in / g / h_out`` (B,L,H) float32 and ``l{i}.Bu / xs`` (B,L,P)
@@ -269,21 +336,50 @@ class FloatEngine:
         activations["__call__"] = t["out"][0].cpu().numpy()
 
 
+def _clip_pair(item):
+    """(x, lens) when a calibration item is a pair of a padded (n,Lmax,257) batch and its n clip lengths, else None."""
+    if isinstance(item, (tuple, list)) and len(item) == 2 and getattr(item[0], "ndim", 0) == 3:
+        return item[0], item[1]
+    return None
+
+
+def _observe(eng: "FloatEngine", item, st, hd, stats: Optional[dict], hist: Optional[dict]) -> None:
+    """One calibration item through the engine: a pair takes the clip entry, so that its padding is never observed; a plain
+    (B,L,257) batch the rectangular one.  Device arrays ``st`` / ``hd`` on the device, the dicts off it."""
+    pair = _clip_pair(item)
+    if eng.on_device:
+        if pair is None:
+            eng.forward_device(eng._to_device(item), st, hist_dev=hd)
+        else:
+            lens = torch.as_tensor(pair[1]).to(device=eng.device, dtype=torch.int32)
+            eng.forward_clips_device(eng._to_device(pair[0]), lens, st, hd)
+    elif pair is None:
+        eng.forward(item, stats=stats, hist=hist)
+    else:
+        x, Lmax = pair[0], int(pair[0].shape[1])
+        lens = [min(max(int(v), 0), Lmax) for v in torch.as_tensor(pair[1]).tolist()]
+        if len(lens) != int(x.shape[0]):
+            raise ValueError(f"{int(x.shape[0])} clips but {len(lens)} lengths")
+        eng.forward_clips([x[e, :n] for e, n in enumerate(lens) if n], stats=stats, hist=hist)
+
+
 def calibrate(modeldict: dict, batches: Iterable, n_layers: int, quantization: str = "w8a16",
               state_headroom_bits: int = 0, engine: Optional[FloatEngine] = None) -> Tuple[dict, dict]:
     """Streams ``batches`` (each (B,L,257) float32) through the float model and derives the fixed-point configuration from
     the observers, exactly as ``synth.make_model`` does after its dry run -> (stats, fxp_qconfig).  On a GPU the observers
-    stay in one device array across the batches and are read back once."""
+    stay in one device array across the batches and are read back once.  An item may also be a pair (x, lens) of clips of
+    different lengths, x padded to (n,Lmax,257) and lens n integers (tensor, array or list): it takes the clip entry
+    (``forward_clips_device``), so no padding frame is observed.  Both kinds may be mixed."""
     eng = engine if engine is not None else FloatEngine(modeldict, n_layers)
     stats: dict = {}
     if eng.on_device:
         st = eng.new_stats()
         for x in batches:
-            eng.forward_device(eng._to_device(x), st)
+            _observe(eng, x, st, None, None, None)
         stats = eng.stats_dict(st)
     else:
         for x in batches:
-            eng.forward(x, stats=stats)
+            _observe(eng, x, None, None, stats, None)
     if not stats:
         raise ValueError("calibrate needs at least one batch")
     qc = synth.derive_qconfig(modeldict, stats, n_layers, synth.PRECISIONS[quantization])
@@ -323,7 +419,8 @@ def calibrate_clipped(modeldict: dict, batches: Iterable, n_layers: int, clip_fr
                       engine: Optional[FloatEngine] = None) -> Tuple[dict, dict, dict, dict]:
     """``calibrate`` with the histograms carried next to the observers -> (stats, hist, effective, fxp_qconfig): the
     configuration is derived from ``effective = clip_absmax(stats, hist, clip_fraction, keep)``.  On a GPU both arrays stay
-    on the device across the batches and are read back once."""
+    on the device across the batches and are read back once.  Items may be pairs (x, lens) as in ``calibrate``: the histograms
+    then hold no padding, so neither ``range_report``'s denominators nor the allowance floor(clip_fraction * n) grow by it."""
     eng = engine if engine is not None else FloatEngine(modeldict, n_layers)
     stats: dict = {}
     hist: dict = {}
@@ -331,13 +428,13 @@ def calibrate_clipped(modeldict: dict, batches: Iterable, n_layers: int, clip_fr
         st, hd = eng.new_stats(), eng.new_hist()
         n = 0
         for x in batches:
-            eng.forward_device(eng._to_device(x), st, hist_dev=hd)
+            _observe(eng, x, st, hd, None, None)
             n += 1
         if n:
             stats, hist = eng.stats_dict(st), eng.hist_dict(hd)
     else:
         for x in batches:
-            eng.forward(x, stats=stats, hist=hist)
+            _observe(eng, x, None, None, stats, hist)
     if not stats:
         raise ValueError("calibrate_clipped needs at least one batch")
     effective = clip_absmax(stats, hist, clip_fraction, keep)
