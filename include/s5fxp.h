@@ -707,6 +707,35 @@ int s5fxp_float_model_forward_hist(const s5fxp_float_model *m, const float *x, i
 int s5fxp_float_model_clips(const s5fxp_float_model *m, const float *x, int n, int Lmax, const int32_t *lens, float *y,
                             float *stats, unsigned long long *hist, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The float forward with chosen tensors FAKE-QUANTISED: every observed tensor has a site, and a site that is
+ * on replaces the value, in the statement right after it entered its observer, by
+ *     q(v) = clamp(R(v * 2^exp), -2^(bits-1), 2^(bits-1) - 1) * 2^-exp,   R = floor or round-half-to-even by `mode`,
+ * the clamp left out when saturate == 0.  NaN stays NaN; either zero may come out.  Within the accepted fields both products
+ * and the rounded integer are exact in float32, so q is one exactly defined float32 function (floatmodel.fake_quant).
+ * Observers keep their place and meaning: under fake quantisation one reports the range its tensor has when everything
+ * upstream is quantised.  u is quantised in both kernels that build it, Bu before it is stored (the scan runs on quantised
+ * Bu), the raw state where the gate kernel reads it, before the complex ReLU, which decides on the quantised pair; the
+ * rounding inside the integer recurrence is not modelled, and the scan itself is unchanged.  gate.l and out2.inp quantise
+ * the same value, each for its own consumer.  The trace planes u, y, g_in, g, the workspace's Bu and y hold what
+ * downstream consumed (post-quantiser); xs stays raw.
+ * fq: NULL, or 4 + 10 * n_layers sites in HOST memory in the order of stats, read before the entry returns.  bits == 0
+ * switches a site off.  With fq == NULL or every site off the kernels launched are exactly those of
+ * s5fxp_float_model_forward / s5fxp_float_model_clips.  There is no histogram together with fake quantisation.
+ * S5FXP_EBADARG, before the device is touched, for bits outside {0, 2..24}, exp outside -24..40, an unknown mode, a saturate
+ * other than 0 / 1, and saturate == 1 on a state site (x_re, x_im: the integer model wraps its state, it does not clip it);
+ * every other argument, error, and the workspace and trace sizes as in the entries without fq. */
+typedef struct {
+    int8_t bits, exp;
+    uint8_t mode, saturate;
+} s5fxp_float_fq_site;
+enum { S5FXP_FQ_FLOOR = 0, S5FXP_FQ_NEAREST = 1 };
+int s5fxp_float_model_forward_fq(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats,
+                                 const s5fxp_float_fq_site *fq, float *trace, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+int s5fxp_float_model_clips_fq(const s5fxp_float_model *m, const float *x, int n, int Lmax, const int32_t *lens, float *y,
+                               float *stats, const s5fxp_float_fq_site *fq, void *workspace, size_t workspace_bytes,
+                               void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,11 @@ class PushDesc(C.Structure):
 F32P = C.POINTER(C.c_float)
 
 
+class FloatFqSite(C.Structure):
+    """s5fxp_float_fq_site: one site of a fake-quantised float forward (4 bytes; bits 0: off)."""
+    _fields_ = [("bits", C.c_int8), ("exp", C.c_int8), ("mode", C.c_uint8), ("saturate", C.c_uint8)]
+
+
 class FloatLayerDesc(C.Structure):
     """s5fxp_float_layer_desc: host pointers to one layer's float parameters."""
     _fields_ = [(n, F32P) for n in ("mean", "var", "scale", "bias", "lambda_bar", "B_bar", "C", "D", "w2", "b2")]
@@ -182,6 +187,8 @@ def _load():
         "s5fxp_float_model_forward": (i, [p, p, i, i, p, p, p, p, C.c_size_t, p]),
         "s5fxp_float_model_forward_hist": (i, [p, p, i, i, p, p, p, p, p, C.c_size_t, p]),
         "s5fxp_float_model_clips": (i, [p, p, i, i, p, p, p, p, p, C.c_size_t, p]),
+        "s5fxp_float_model_forward_fq": (i, [p, p, i, i, p, p, p, p, p, C.c_size_t, p]),
+        "s5fxp_float_model_clips_fq": (i, [p, p, i, i, p, p, p, p, p, C.c_size_t, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale: rebuild
@@ -204,7 +211,8 @@ EXPORTED_SYMBOLS = ("s5fxp_version s5fxp_strerror s5fxp_from_fp s5fxp_to_float s
                     "s5fxp_stft_mag_clips s5fxp_mask_istft_clips s5fxp_score_clips_workspace_bytes s5fxp_mask_istft_score_clips "
                     "s5fxp_float_model_blob_bytes s5fxp_float_model_pack s5fxp_float_model_create s5fxp_float_model_destroy "
                     "s5fxp_float_workspace_bytes s5fxp_float_trace_bytes s5fxp_float_model_forward "
-                    "s5fxp_float_model_forward_hist s5fxp_float_model_clips").split()
+                    "s5fxp_float_model_forward_hist s5fxp_float_model_clips "
+                    "s5fxp_float_model_forward_fq s5fxp_float_model_clips_fq").split()
 
 
 def check(rc: int, what: str = "") -> None:

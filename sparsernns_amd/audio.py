@@ -498,19 +498,21 @@ def validate_fused(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, clea
     return score_fused(noisy, clean, mask, lam)[:2]
 
 
-def denoise_float(float_engine, noisy: torch.Tensor):
+def denoise_float(float_engine, noisy: torch.Tensor, fq=None):
     """``denoise_fused`` with the FLOAT model (``floatmodel.FloatEngine``) in the middle: stft_mag -> FloatEngine.forward ->
-    mask_istft -> (cleaned audio, cleaned magnitude, x, mask).  What the fixed-point loop approximates, on the same clips."""
+    mask_istft -> (cleaned audio, cleaned magnitude, x, mask).  What the fixed-point loop approximates, on the same clips.
+    ``fq`` (``floatmodel.fq_spec``) goes to the model's forward: the float loop with chosen tensors fake-quantised."""
     x = stft_mag(noisy)
-    mask = float_engine.forward(x)
+    mask = float_engine.forward(x, fq=fq)
     cleaned, cleaned_mag = mask_istft(noisy, mask, cleaned_mag=True)
     return cleaned, cleaned_mag, x, mask
 
 
-def validate_float(float_engine, noisy: torch.Tensor, clean: torch.Tensor, lam: float = 0.001):
+def validate_float(float_engine, noisy: torch.Tensor, clean: torch.Tensor, lam: float = 0.001, fq=None):
     """``validate_fused`` with the FLOAT model: stft_mag -> FloatEngine.forward -> score_fused -> (loss, si_snr), one value per
-    sequence.  The difference to ``validate_fused`` on the same clips is the cost of quantisation in dB."""
-    return score_fused(noisy, clean, float_engine.forward(stft_mag(noisy)), lam)[:2]
+    sequence.  The difference to ``validate_fused`` on the same clips is the cost of quantisation in dB; the difference
+    between a call with ``fq`` (``floatmodel.fq_spec``) and one without is the SI-SNR cost of those quantisers alone."""
+    return score_fused(noisy, clean, float_engine.forward(stft_mag(noisy), fq=fq), lam)[:2]
 
 
 def score_clips(noisy: torch.Tensor, clean: torch.Tensor, samples: torch.Tensor, mask, lam: float = 0.001, cleaned: bool = False,
@@ -594,7 +596,7 @@ def validate_clips(model, inp_bits: int, inp_exp: int, noisy_clips, clean_clips,
     return score_clips(audio, clean, samples, mask, lam)[:2]
 
 
-def _float_clips_front(float_engine, clips, one_launch: bool = True):
+def _float_clips_front(float_engine, clips, one_launch: bool = True, fq=None):
     """``_clips_front`` with the FLOAT model in the middle: the same checks of the clip list, and where every clip lies on the
     engine's device the padding, ``stft_mag_clips`` and ``FloatEngine.forward_clips_device`` on those very tensors.  Returns
     (clips, front), front = (audio, samples, x, mask, L) or None for the per-clip route (and for an empty list)."""
@@ -610,30 +612,30 @@ def _float_clips_front(float_engine, clips, one_launch: bool = True):
     samples = torch.tensor(Ts, dtype=torch.int32, device=audio.device)
     with torch.cuda.device(audio.device):
         x, lens = stft_mag_clips(audio, samples)
-        mask = float_engine.forward_clips_device(x, lens)
+        mask = float_engine.forward_clips_device(x, lens, fq=fq)
     return clips, (audio, samples, x, mask, [stft_frames(T) for T in Ts])
 
 
-def denoise_float_clips(float_engine, clips):
+def denoise_float_clips(float_engine, clips, fq=None):
     """``denoise_float`` for a list of 1-D float audio clips of any lengths >= 512 (below: NotImplementedError, before any
     launch; an empty list gives []).  Returns what ``denoise_clips`` returns, per clip (cleaned ((len_e - 1) * 128,),
     cleaned_mag, x, mask): bit for bit the tuple ``denoise_float(float_engine, clip[None])`` returns, without the batch axis.
     With the engine and every clip on one GPU that is ``stft_mag_clips`` -> ``FloatEngine.forward_clips_device`` ->
-    ``mask_istft_clips``, whatever n; otherwise ``denoise_float`` clip by clip."""
-    clips, front = _float_clips_front(float_engine, clips)
+    ``mask_istft_clips``, whatever n; otherwise ``denoise_float`` clip by clip.  ``fq`` as in ``denoise_float``."""
+    clips, front = _float_clips_front(float_engine, clips, fq=fq)
     if front is None:
-        return [tuple(t[0] for t in denoise_float(float_engine, c[None])) for c in clips]
+        return [tuple(t[0] for t in denoise_float(float_engine, c[None], fq=fq)) for c in clips]
     audio, samples, x, mask, L = front
     cleaned, cm = mask_istft_clips(audio, samples, mask, cleaned_mag=True)
     return [(cleaned[e, :(L[e] - 1) * HOP], cm[e, :L[e]], x[e, :L[e]], mask[e, :L[e]]) for e in range(len(clips))]
 
 
-def validate_float_clips(float_engine, noisy_clips, clean_clips, lam: float = 0.001):
+def validate_float_clips(float_engine, noisy_clips, clean_clips, lam: float = 0.001, fq=None):
     """``validate_float`` for lists of 1-D float audio clips, with ``validate_clips``' checks of the two lists -> (loss, si_snr),
     (n,) float32 each (two empty tensors for empty lists): per clip bit for bit
     ``validate_float(float_engine, noisy[None], clean[None], lam)``.  With the engine and all clips on one GPU that is
     ``stft_mag_clips`` -> ``FloatEngine.forward_clips_device`` -> ``score_clips``; otherwise ``validate_float`` clip by clip.
-    The difference to ``validate_clips`` on the same clips is the cost of quantisation in dB."""
+    The difference to ``validate_clips`` on the same clips is the cost of quantisation in dB.  ``fq`` as in ``validate_float``."""
     noisy_clips, clean_clips = list(noisy_clips), [torch.as_tensor(c) for c in clean_clips]
     if len(noisy_clips) != len(clean_clips):
         raise ValueError(f"{len(noisy_clips)} noisy clips but {len(clean_clips)} clean ones")
@@ -641,11 +643,11 @@ def validate_float_clips(float_engine, noisy_clips, clean_clips, lam: float = 0.
         if tuple(r.shape) != tuple(torch.as_tensor(c).shape):
             raise ValueError(f"clean clip {e} must be {tuple(torch.as_tensor(c).shape)}, got {tuple(r.shape)}")
     same_device = all(r.device == torch.as_tensor(c).device for c, r in zip(noisy_clips, clean_clips))
-    noisy_clips, front = _float_clips_front(float_engine, noisy_clips, one_launch=same_device)
+    noisy_clips, front = _float_clips_front(float_engine, noisy_clips, one_launch=same_device, fq=fq)
     if not noisy_clips:
         return torch.empty(0, dtype=torch.float32), torch.empty(0, dtype=torch.float32)
     if front is None:
-        r = [validate_float(float_engine, c[None], k[None], lam) for c, k in zip(noisy_clips, clean_clips)]
+        r = [validate_float(float_engine, c[None], k[None], lam, fq=fq) for c, k in zip(noisy_clips, clean_clips)]
         return torch.cat([t[0] for t in r]), torch.cat([t[1] for t in r])
     audio, samples, _, mask, _ = front
     clean = torch.nn.utils.rnn.pad_sequence([c.to(torch.float32) for c in clean_clips], batch_first=True)

@@ -30,6 +30,11 @@
 // every clip gets bit for bit what the rectangular kernels give it alone and no padding row is read, written or observed.
 // They are two more inclusions of float_model_kernels.inc (FM_CLIPS 1), for the reason given below for FM_HIST.
 //
+// FQ (the k_*_fq and k_*_clips_fq kernels) fake-quantise chosen observed tensors: a site that is on replaces the
+// value, right after it entered its observer, by q(v) = clamp(R(v 2^exp), lo, hi) 2^-exp (fm_fq: four VALU operations, none
+// of which can be contracted).  The sites reach a kernel as one more by-value parameter, FFq<n>, so that no argument struct of
+// the existing kernels grows.  Two more inclusions (FM_FQ 1), built without the histogram.
+//
 // The four kernels are written once, in float_model_kernels.inc, which this header includes once per form: with FM_HIST 0 it gives
 // k_fenc, k_fbproj, k_fgate, k_fdec -- token for token the kernels as they were before the histogram, so their instruction
 // streams do not move -- and with FM_HIST 1 k_fenc_hist, ... with one more argument.  The flag is a preprocessor one and not
@@ -59,6 +64,27 @@ __device__ inline float fm_relu(float v) { return v < 0.f ? 0.f : v; }
 __device__ inline float fm_bn(float h, float mean, float istd, float sc, float bi)
 {
     return __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(h, mean), istd), sc), bi);
+}
+
+// one fake-quantisation site, prepared on the host: scale = 2^exp, inv_scale = 2^-exp, lo = -2^(bits-1), hi = 2^(bits-1) - 1
+constexpr unsigned FM_FQF_ON = 1u, FM_FQF_NEAREST = 2u, FM_FQF_SATURATE = 4u;
+struct FqSite {
+    float scale, inv_scale, lo, hi;
+    unsigned flags; // 0: the site is off
+};
+template <int N>
+struct FFq {
+    FqSite s[N];
+};
+// flags is a kernel argument, so the three tests are scalar branches.  The clamp is two compare-and-selects and not
+// fmin / fmax / med3, which would swallow a NaN: both comparisons are false for one, so it passes.
+__device__ inline float fm_fq(float v, const FqSite &s)
+{
+    if (!(s.flags & FM_FQF_ON)) return v;
+    float t = __fmul_rn(v, s.scale);
+    t = (s.flags & FM_FQF_NEAREST) ? rintf(t) : floorf(t);
+    if (s.flags & FM_FQF_SATURATE) t = t < s.lo ? s.lo : t > s.hi ? s.hi : t;
+    return __fmul_rn(t, s.inv_scale);
 }
 
 constexpr int FM_HIST_BINS = 64;   // S5FXP_FLOAT_HIST_BINS
@@ -247,6 +273,22 @@ struct FClipMap {
 #define FM_HIST_ON_ADD(plane, v) fm_hist_add(shist, plane, v)
 #define FM_HIST_ON_END(...) fm_hist_flush<__VA_ARGS__>(shist, hist)
 
+#define FM_FQ_OFF(site, v) (v)
+#define FM_FQ2_OFF(odd, site_odd, site_even, v) (v)
+#define FM_FQ_V4_OFF(site, v)
+#define FM_FQ_V2_OFF(site_x, site_y, v)
+#define FM_FQ_ON(site, v) fm_fq(v, fq.s[site])
+#define FM_FQ_V4_ON(site, v) v = make_float4(fm_fq(v.x, fq.s[site]), fm_fq(v.y, fq.s[site]), fm_fq(v.z, fq.s[site]), fm_fq(v.w, fq.s[site]))
+#define FM_FQ_V2_ON(site_x, site_y, v) v = make_float2(fm_fq(v.x, fq.s[site_x]), fm_fq(v.y, fq.s[site_y]))
+#define FM_FQ2_ON(odd, site_odd, site_even, v) ((odd) ? fm_fq(v, fq.s[site_odd]) : fm_fq(v, fq.s[site_even]))
+
+// the four forms without fake quantisation
+#define FM_FQ_PARAM(n)
+#define FM_FQ FM_FQ_OFF
+#define FM_FQ2 FM_FQ2_OFF
+#define FM_FQ_V4 FM_FQ_V4_OFF
+#define FM_FQ_V2 FM_FQ_V2_OFF
+
 #define FM_HIST 0
 #define FM_CLIPS 0
 #define FM_KERNEL(name) name
@@ -326,5 +368,60 @@ struct FClipMap {
 #undef FM_HIST_BEGIN
 #undef FM_HIST_ADD
 #undef FM_HIST_END
+#undef FM_FQ_PARAM
+#undef FM_FQ
+#undef FM_FQ2
+#undef FM_FQ_V4
+#undef FM_FQ_V2
+
+// the fake-quantising forms, rectangular and clips, both without the histogram
+#define FM_HIST 0
+#define FM_HIST_PARAM
+#define FM_HIST_BEGIN FM_HIST_OFF_BEGIN
+#define FM_HIST_ADD FM_HIST_OFF_ADD
+#define FM_HIST_END FM_HIST_OFF_END
+#define FM_FQ_PARAM(n) , FFq<n> fq
+#define FM_FQ FM_FQ_ON
+#define FM_FQ2 FM_FQ2_ON
+#define FM_FQ_V4 FM_FQ_V4_ON
+#define FM_FQ_V2 FM_FQ_V2_ON
+
+#define FM_CLIPS 0
+#define FM_KERNEL(name) name##_fq
+#define FM_CLIPS_PARAM
+#define FM_TILES FM_TILES_RECT
+#define FM_TILE FM_TILE_RECT
+#define FM_GATE_ATTR
+#include "float_model_kernels.inc"
+#undef FM_CLIPS
+#undef FM_KERNEL
+#undef FM_CLIPS_PARAM
+#undef FM_TILES
+#undef FM_TILE
+#undef FM_GATE_ATTR
+
+#define FM_CLIPS 1
+#define FM_KERNEL(name) name##_clips_fq
+#define FM_CLIPS_PARAM , FClipMap cm
+#define FM_TILES(N) cm.tiles
+#define FM_TILE FM_TILE_CLIP
+#define FM_GATE_ATTR __attribute__((amdgpu_waves_per_eu(DS == 2 ? 2 : 1))) // as k_fgate_clips
+#include "float_model_kernels.inc"
+#undef FM_HIST
+#undef FM_CLIPS
+#undef FM_KERNEL
+#undef FM_CLIPS_PARAM
+#undef FM_HIST_PARAM
+#undef FM_TILES
+#undef FM_TILE
+#undef FM_GATE_ATTR
+#undef FM_HIST_BEGIN
+#undef FM_HIST_ADD
+#undef FM_HIST_END
+#undef FM_FQ_PARAM
+#undef FM_FQ
+#undef FM_FQ2
+#undef FM_FQ_V4
+#undef FM_FQ_V2
 
 } // namespace s5

@@ -3,6 +3,11 @@
 // every value into its observer's exponent histogram where it enters the observer.  With FM_HIST 0 every FM_HIST_* macro is
 // empty.  FM_CLIPS 1 gives k_fenc_clips / ... and k_fenc_clips_hist / ..., which take an FClipMap as well: FM_TILES and
 // FM_TILE then map a tile to a clip's rows (and skip it when the clip has none there) instead of to rows 32*tile.. of N.
+// FM_FQ 1 gives k_fenc_fq / ... and k_fenc_clips_fq / ... (DESIGN.md 4u), which take the kernel's fake-quantisation sites `fq` as
+// well: FM_FQ(site, v) is then fm_fq(v, fq.s[site]), the value the site hands downstream, placed right behind the statement
+// where v enters its observer; FM_FQ2 chooses between two sites by a lane predicate; FM_FQ_V4 / FM_FQ_V2 are statements that
+// quantise a float4 by one site / a float2 by one site per component in place.  With FM_FQ 0 the first two are (v) and the
+// statements are empty.
 // Not a translation unit of its own; everything it uses is declared in float_model.hpp, inside namespace s5.
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -10,7 +15,7 @@
 // ------------------------------------------------------------------------------------------------------------------
 
 template <int DS>
-__global__ __launch_bounds__(256) void FM_KERNEL(k_fenc)(FEncArgs a FM_CLIPS_PARAM FM_HIST_PARAM) // hist: rows encoder.inp, encoder.out
+__global__ __launch_bounds__(256) void FM_KERNEL(k_fenc)(FEncArgs a FM_CLIPS_PARAM FM_HIST_PARAM FM_FQ_PARAM(2)) // hist: rows encoder.inp, encoder.out
 {
     constexpr int H = 48 * DS, HT = 3 * DS, NT = (HT + 3) / 4, KS = FM_KENC / 4, LDA = fm_lda(FM_KENC);
     __shared__ float sx[FM_FT * LDA];
@@ -50,7 +55,7 @@ __global__ __launch_bounds__(256) void FM_KERNEL(k_fenc)(FEncArgs a FM_CLIPS_PAR
                 om[0] = fm_umax(om[0], fm_absbits(w));
                 FM_HIST_ADD(0, w);
             }
-            sx[r * LDA + c] = w;
+            sx[r * LDA + c] = FM_FQ(0, w);
         }
         __syncthreads();
         fm_f32x4 acc[2][NT];
@@ -68,7 +73,7 @@ __global__ __launch_bounds__(256) void FM_KERNEL(k_fenc)(FEncArgs a FM_CLIPS_PAR
                     const float v = __fadd_rn(acc[rt][nt][r], bias[nt]);
                     om[1] = fm_umax(om[1], fm_absbits(v));
                     FM_HIST_ADD(1, v);
-                    a.h[(size_t)(r0 + row) * H + t * 16 + (lane & 15)] = fm_relu(v);
+                    a.h[(size_t)(r0 + row) * H + t * 16 + (lane & 15)] = fm_relu(FM_FQ(1, v));
                 }
             }
         __syncthreads();
@@ -83,7 +88,7 @@ __global__ __launch_bounds__(256) void FM_KERNEL(k_fenc)(FEncArgs a FM_CLIPS_PAR
 // ------------------------------------------------------------------------------------------------------------------
 
 template <int DS, bool TRACE>
-__global__ __launch_bounds__(256) void FM_KERNEL(k_fbproj)(FBprojArgs a FM_CLIPS_PARAM FM_HIST_PARAM) // hist: rows u, Bu_re, Bu_im
+__global__ __launch_bounds__(256) void FM_KERNEL(k_fbproj)(FBprojArgs a FM_CLIPS_PARAM FM_HIST_PARAM FM_FQ_PARAM(3)) // hist: rows u, Bu_re, Bu_im
 {
     constexpr int H = 48 * DS, P2 = 64 * DS, PT = 4 * DS, NT = DS, KS = H / 4, LDA = fm_lda(H);
     __shared__ float su[FM_FT * LDA];
@@ -115,6 +120,7 @@ __global__ __launch_bounds__(256) void FM_KERNEL(k_fbproj)(FBprojArgs a FM_CLIPS
                 FM_HIST_ADD(0, u.y);
                 FM_HIST_ADD(0, u.z);
                 FM_HIST_ADD(0, u.w);
+                FM_FQ_V4(0, u);
                 if (TRACE) *reinterpret_cast<float4 *>(a.u_trace + (size_t)(r0 + r) * H + c) = u;
             }
             *reinterpret_cast<float4 *>(su + r * LDA + c) = u;
@@ -134,7 +140,7 @@ __global__ __launch_bounds__(256) void FM_KERNEL(k_fbproj)(FBprojArgs a FM_CLIPS
                     const float v = acc[rt][nt][r];
                     om_bu = fm_umax(om_bu, fm_absbits(v));
                     FM_HIST_ADD(1 + (lane & 1), v);
-                    a.bu[(size_t)(r0 + row) * P2 + t * 16 + (lane & 15)] = v;
+                    a.bu[(size_t)(r0 + row) * P2 + t * 16 + (lane & 15)] = FM_FQ2(lane & 1, 2, 1, v);
                 }
             }
         __syncthreads();
@@ -149,10 +155,11 @@ __global__ __launch_bounds__(256) void FM_KERNEL(k_fbproj)(FBprojArgs a FM_CLIPS
 // rectified states against ccat (2P,H) = rows (C_re^T, -C_im^T) interleaved, with u rebuilt from the layer input;
 // x1 = relu(y), g_in = x1 W2 + b2, g = sigmoid(g_in), h' = relu(x1 g + h).
 // Observers [0] x_re, [1] x_im (raw states), [2] y, [3] out2.inp, [4] out2.out, [5] gate.l (= out2.inp), [6] gate.r.
+// Sites: [0] u (the layer's u, rebuilt here exactly as k_fbproj quantised it), then [1 + i] for observer [i].
 // ------------------------------------------------------------------------------------------------------------------
 
 template <int DS, bool TRACE>
-__global__ __launch_bounds__(256) FM_GATE_ATTR void FM_KERNEL(k_fgate)(FGateArgs a FM_CLIPS_PARAM FM_HIST_PARAM) // hist: the layer's rows x_re .. gate.r
+__global__ __launch_bounds__(256) FM_GATE_ATTR void FM_KERNEL(k_fgate)(FGateArgs a FM_CLIPS_PARAM FM_HIST_PARAM FM_FQ_PARAM(8)) // hist: the layer's rows x_re .. gate.r
 {
     constexpr int H = 48 * DS, P = 32 * DS, P2 = 64 * DS, HT = 3 * DS, NT = (HT + 3) / 4, KS1 = P2 / 4, KS2 = H / 4;
     constexpr int LD1 = fm_lda(P2), LDH = fm_lda(H);
@@ -184,6 +191,7 @@ __global__ __launch_bounds__(256) FM_GATE_ATTR void FM_KERNEL(k_fgate)(FGateArgs
                 o_xim = fm_umax(o_xim, fm_absbits(v.y));
                 FM_HIST_ADD(0, v.x);
                 FM_HIST_ADD(1, v.y);
+                FM_FQ_V2(1, 2, v);
                 const bool keep = v.x > 0.f || (v.x == 0.f && v.y > 0.f);
                 if (!keep) v = make_float2(0.f, 0.f);
             }
@@ -209,17 +217,18 @@ __global__ __launch_bounds__(256) FM_GATE_ATTR void FM_KERNEL(k_fgate)(FGateArgs
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = rt * 16 + (lane >> 4) * 4 + r;
-                    const float u = fm_bn(sh[row * LDH + col], spar[col], spar[H + col], spar[2 * H + col], spar[3 * H + col]);
+                    const float u = FM_FQ(0, fm_bn(sh[row * LDH + col], spar[col], spar[H + col], spar[2 * H + col], spar[3 * H + col]));
                     const float y = __fadd_rn(__fmul_rn(2.f, acc[rt][nt][r]), __fmul_rn(spar[4 * H + col], u));
-                    const float x1 = fm_relu(y);
-                    x1v[rt][nt][r] = x1;
-                    sx1[row * LDH + col] = x1;
+                    const float yq = FM_FQ(3, y);
+                    const float x1 = fm_relu(yq);
+                    x1v[rt][nt][r] = FM_FQ(6, x1);      // gate.l: the factor of x1 g
+                    sx1[row * LDH + col] = FM_FQ(4, x1); // out2.inp: the operand of the out2 contraction
                     if (row < rows) {
                         o_y = fm_umax(o_y, fm_absbits(y));
                         o_x1 = fm_umax(o_x1, fm_absbits(x1));
                         FM_HIST_ADD(2, y);
                         FM_HIST_ADD(3, x1);
-                        if (TRACE) a.y_trace[(size_t)(r0 + row) * H + col] = y;
+                        if (TRACE) a.y_trace[(size_t)(r0 + row) * H + col] = yq;
                     }
                 }
             }
@@ -237,16 +246,18 @@ __global__ __launch_bounds__(256) FM_GATE_ATTR void FM_KERNEL(k_fgate)(FGateArgs
                     const int row = rt * 16 + (lane >> 4) * 4 + r;
                     if (row >= rows) continue;
                     const float gin = __fadd_rn(acc[rt][nt][r], spar[5 * H + col]);
-                    const float g = 1.f / (1.f + expf(-gin));
+                    const float ginq = FM_FQ(5, gin);
+                    const float g = 1.f / (1.f + expf(-ginq));
+                    const float gq = FM_FQ(7, g);
                     o_gin = fm_umax(o_gin, fm_absbits(gin));
                     o_g = fm_umax(o_g, fm_absbits(g));
                     FM_HIST_ADD(4, gin);
                     FM_HIST_ADD(5, g);
                     const size_t o = (size_t)(r0 + row) * H + col;
-                    a.hout[o] = fm_relu(__fadd_rn(__fmul_rn(x1v[rt][nt][r], g), sh[row * LDH + col]));
+                    a.hout[o] = fm_relu(__fadd_rn(__fmul_rn(x1v[rt][nt][r], gq), sh[row * LDH + col]));
                     if (TRACE) {
-                        a.gin_trace[o] = gin;
-                        a.g_trace[o] = g;
+                        a.gin_trace[o] = ginq;
+                        a.g_trace[o] = gq;
                     }
                 }
             }
@@ -262,7 +273,7 @@ __global__ __launch_bounds__(256) FM_GATE_ATTR void FM_KERNEL(k_fgate)(FGateArgs
 // ------------------------------------------------------------------------------------------------------------------
 
 template <int DS>
-__global__ __launch_bounds__(256) void FM_KERNEL(k_fdec)(FDecArgs a FM_CLIPS_PARAM FM_HIST_PARAM) // hist: rows decoder.inp, decoder.out
+__global__ __launch_bounds__(256) void FM_KERNEL(k_fdec)(FDecArgs a FM_CLIPS_PARAM FM_HIST_PARAM FM_FQ_PARAM(2)) // hist: rows decoder.inp, decoder.out
 {
     constexpr int H = 48 * DS, NT = (FM_DEC_TILES + 3) / 4, KS = H / 4, LDA = fm_lda(H);
     __shared__ float sh[FM_FT * LDA];
@@ -291,6 +302,7 @@ __global__ __launch_bounds__(256) void FM_KERNEL(k_fdec)(FDecArgs a FM_CLIPS_PAR
                 FM_HIST_ADD(0, h.y);
                 FM_HIST_ADD(0, h.z);
                 FM_HIST_ADD(0, h.w);
+                FM_FQ_V4(0, h);
             }
             *reinterpret_cast<float4 *>(sh + r * LDA + c) = h;
         }
@@ -311,7 +323,7 @@ __global__ __launch_bounds__(256) void FM_KERNEL(k_fdec)(FDecArgs a FM_CLIPS_PAR
                     const float v = __fadd_rn(acc[rt][nt][r], bias[nt]);
                     om[1] = fm_umax(om[1], fm_absbits(v));
                     FM_HIST_ADD(1, v);
-                    a.out[(size_t)(r0 + row) * FM_DIN + col] = v;
+                    a.out[(size_t)(r0 + row) * FM_DIN + col] = FM_FQ(1, v);
                 }
             }
         __syncthreads();

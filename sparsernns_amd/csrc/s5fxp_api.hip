@@ -1371,14 +1371,61 @@ constexpr long long FM_GRID_CAP = 512; // workgroups per launch: the weights are
 #define S5_K_FGATE_TH(ds) k_fgate_hist<ds, true>
 #define S5_K_FGATE_H(ds) k_fgate_hist<ds, false>
 
+#define S5_K_FENC_Q(ds) k_fenc_fq<ds>
+#define S5_K_FDEC_Q(ds) k_fdec_fq<ds>
+#define S5_K_FBPROJ_TQ(ds) k_fbproj_fq<ds, true>
+#define S5_K_FBPROJ_Q(ds) k_fbproj_fq<ds, false>
+#define S5_K_FGATE_TQ(ds) k_fgate_fq<ds, true>
+#define S5_K_FGATE_Q(ds) k_fgate_fq<ds, false>
+
 static_assert(FM_HIST_BINS == S5FXP_FLOAT_HIST_BINS && FM_HIST_EMIN == S5FXP_FLOAT_HIST_EMIN, "include/s5fxp.h and float_model.hpp");
 
-// the one forward of both entries: hist == nullptr launches exactly the kernels without the histogram
+// The sites of a fake-quantised forward, checked and prepared on the host: in stats order, 2 for the encoder,
+// per layer u, Bu_re, Bu_im, x_re, x_im, y, out2.inp, out2.out, gate.l, gate.r, 2 for the decoder.
+struct FqPlan {
+    bool any = false;
+    std::vector<FqSite> s;
+    FFq<2> enc() const { return {{s[0], s[1]}}; }
+    FFq<3> bproj(int i) const { const FqSite *l = &s[2 + 10 * i]; return {{l[0], l[1], l[2]}}; }
+    FFq<8> gate(int i) const // u, then the gate kernel's seven observers
+    {
+        const FqSite *l = &s[2 + 10 * i];
+        return {{l[0], l[3], l[4], l[5], l[6], l[7], l[8], l[9]}};
+    }
+    FFq<2> dec() const { return {{s[s.size() - 2], s[s.size() - 1]}}; }
+};
+
+// S5FXP_EBADARG for a site the kernels do not serve; fq == nullptr or every site off leaves plan.any false
+int fq_plan(const s5fxp_float_fq_site *fq, int n_layers, FqPlan &plan)
+{
+    if (!fq) return S5FXP_OK;
+    const int n = 4 + 10 * n_layers;
+    plan.s.assign(n, FqSite{1.f, 1.f, 0.f, 0.f, 0u});
+    for (int j = 0; j < n; ++j) {
+        const s5fxp_float_fq_site &q = fq[j];
+        if (q.bits == 0) continue;
+        const int k = j >= 2 && j < n - 2 ? (j - 2) % 10 : -1;
+        const bool state = k == 3 || k == 4; // x_re, x_im: the integer model wraps its state
+        if (q.bits < 2 || q.bits > 24 || q.exp < -24 || q.exp > 40 || q.mode > S5FXP_FQ_NEAREST || q.saturate > 1 ||
+            (state && q.saturate))
+            return S5FXP_EBADARG;
+        const float half = ldexpf(1.f, q.bits - 1);
+        plan.s[j] = FqSite{ldexpf(1.f, q.exp), ldexpf(1.f, -q.exp), -half, half - 1.f,
+                           FM_FQF_ON | (q.mode == S5FXP_FQ_NEAREST ? FM_FQF_NEAREST : 0u) | (q.saturate ? FM_FQF_SATURATE : 0u)};
+        plan.any = true;
+    }
+    return S5FXP_OK;
+}
+
+// the one forward of the three entries: hist == nullptr launches exactly the kernels without the histogram, and fq == nullptr
+// or all off exactly those without fake quantisation (the two are never given together)
 int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats, unsigned long long *hist,
-                  float *trace, void *workspace, size_t workspace_bytes, void *stream)
+                  const s5fxp_float_fq_site *fq, float *trace, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!m || !x || !y || !workspace || B < 1 || L < 1) return S5FXP_EBADARG;
     if (reinterpret_cast<uintptr_t>(hist) % sizeof(unsigned long long)) return S5FXP_EBADARG;
+    FqPlan qp;
+    if (fq_plan(fq, m->n_layers, qp)) return S5FXP_EBADARG;
     const long long N = (long long)B * L;
     const long long tiles = (N + FM_FT - 1) / FM_FT;
     const unsigned grid = (unsigned)(tiles < FM_GRID_CAP ? tiles : FM_GRID_CAP);
@@ -1394,7 +1441,8 @@ int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, floa
 
     float *h = hbuf[0];
     FEncArgs ea{x, m->enc_w, m->enc_b, h, obs, N};
-    if (hist) S5_DISPATCH_DS(m->DS, S5_K_FENC_H, grid, st, ea, hist);
+    if (qp.any) S5_DISPATCH_DS(m->DS, S5_K_FENC_Q, grid, st, ea, qp.enc());
+    else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FENC_H, grid, st, ea, hist);
     else S5_DISPATCH_DS(m->DS, S5_K_FENC, grid, st, ea);
     if ((rc = launch_rc())) return rc;
     for (int i = 0; i < m->n_layers; ++i) {
@@ -1405,7 +1453,9 @@ int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, floa
         unsigned *lo = obs ? obs + 2 + 10 * i : nullptr;
         unsigned long long *lh = hist ? hist + (size_t)(2 + 10 * i) * FM_HIST_BINS : nullptr;
         FBprojArgs ba{h, l.nm, l.bcat, bu, tr, lo, N};
-        if (hist && trace) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_TH, grid, st, ba, lh);
+        if (qp.any && trace) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_TQ, grid, st, ba, qp.bproj(i));
+        else if (qp.any) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_Q, grid, st, ba, qp.bproj(i));
+        else if (hist && trace) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_TH, grid, st, ba, lh);
         else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_H, grid, st, ba, lh);
         else if (trace) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_T, grid, st, ba);
         else S5_DISPATCH_DS(m->DS, S5_K_FBPROJ, grid, st, ba);
@@ -1414,7 +1464,9 @@ int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, floa
         FGateArgs ga{xs, h, l.nm, l.ccat, l.D, l.w2, l.b2, hout, tr ? tr + NH : nullptr, tr ? tr + 2 * NH : nullptr,
                      tr ? tr + 3 * NH : nullptr, lo ? lo + 3 : nullptr, N};
         unsigned long long *gh = lh ? lh + 3 * FM_HIST_BINS : nullptr;
-        if (hist && trace) S5_DISPATCH_DS(m->DS, S5_K_FGATE_TH, grid, st, ga, gh);
+        if (qp.any && trace) S5_DISPATCH_DS(m->DS, S5_K_FGATE_TQ, grid, st, ga, qp.gate(i));
+        else if (qp.any) S5_DISPATCH_DS(m->DS, S5_K_FGATE_Q, grid, st, ga, qp.gate(i));
+        else if (hist && trace) S5_DISPATCH_DS(m->DS, S5_K_FGATE_TH, grid, st, ga, gh);
         else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FGATE_H, grid, st, ga, gh);
         else if (trace) S5_DISPATCH_DS(m->DS, S5_K_FGATE_T, grid, st, ga);
         else S5_DISPATCH_DS(m->DS, S5_K_FGATE, grid, st, ga);
@@ -1422,7 +1474,8 @@ int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, floa
         h = hout;
     }
     FDecArgs da{h, m->dec_w, m->dec_b, y, obs ? obs + 2 + 10 * m->n_layers : nullptr, N};
-    if (hist) S5_DISPATCH_DS(m->DS, S5_K_FDEC_H, grid, st, da, hist + (size_t)(2 + 10 * m->n_layers) * FM_HIST_BINS);
+    if (qp.any) S5_DISPATCH_DS(m->DS, S5_K_FDEC_Q, grid, st, da, qp.dec());
+    else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FDEC_H, grid, st, da, hist + (size_t)(2 + 10 * m->n_layers) * FM_HIST_BINS);
     else S5_DISPATCH_DS(m->DS, S5_K_FDEC, grid, st, da);
     return launch_rc();
 }
@@ -1435,13 +1488,20 @@ int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, floa
 #define S5_K_FDEC_CH(ds) k_fdec_clips_hist<ds>
 #define S5_K_FBPROJ_CH(ds) k_fbproj_clips_hist<ds, false>
 #define S5_K_FGATE_CH(ds) k_fgate_clips_hist<ds, false>
+#define S5_K_FENC_CQ(ds) k_fenc_clips_fq<ds>
+#define S5_K_FDEC_CQ(ds) k_fdec_clips_fq<ds>
+#define S5_K_FBPROJ_CQ(ds) k_fbproj_clips_fq<ds, false>
+#define S5_K_FGATE_CQ(ds) k_fgate_clips_fq<ds, false>
 
 // the clip forward: the same eleven-kernel chain over tiles that belong to one clip each; no trace planes
 int float_forward_clips(const s5fxp_float_model *m, const float *x, int n, int Lmax, const int32_t *lens, float *y, float *stats,
-                        unsigned long long *hist, void *workspace, size_t workspace_bytes, void *stream)
+                        unsigned long long *hist, const s5fxp_float_fq_site *fq, void *workspace, size_t workspace_bytes,
+                        void *stream)
 {
     if (!m || !x || !y || !lens || !workspace || n < 1 || Lmax < 1) return S5FXP_EBADARG;
     if (reinterpret_cast<uintptr_t>(hist) % sizeof(unsigned long long)) return S5FXP_EBADARG;
+    FqPlan qp;
+    if (fq_plan(fq, m->n_layers, qp)) return S5FXP_EBADARG;
     const int tpc = (int)(((long long)Lmax + FM_FT - 1) / FM_FT);
     const long long N = (long long)n * Lmax, tiles = (long long)n * tpc;
     unsigned grid = (unsigned)(tiles < FM_GRID_CAP ? tiles : FM_GRID_CAP);
@@ -1465,7 +1525,8 @@ int float_forward_clips(const s5fxp_float_model *m, const float *x, int n, int L
 
     float *h = hbuf[0];
     FEncArgs ea{x, m->enc_w, m->enc_b, h, obs, N};
-    if (hist) S5_DISPATCH_DS(m->DS, S5_K_FENC_CH, grid, st, ea, cm, hist);
+    if (qp.any) S5_DISPATCH_DS(m->DS, S5_K_FENC_CQ, grid, st, ea, cm, qp.enc());
+    else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FENC_CH, grid, st, ea, cm, hist);
     else S5_DISPATCH_DS(m->DS, S5_K_FENC_C, grid, st, ea, cm);
     if ((rc = launch_rc())) return rc;
     for (int i = 0; i < m->n_layers; ++i) {
@@ -1474,7 +1535,8 @@ int float_forward_clips(const s5fxp_float_model *m, const float *x, int n, int L
         unsigned *lo = obs ? obs + 2 + 10 * i : nullptr;
         unsigned long long *lh = hist ? hist + (size_t)(2 + 10 * i) * FM_HIST_BINS : nullptr;
         FBprojArgs ba{h, l.nm, l.bcat, bu, nullptr, lo, N};
-        if (hist) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_CH, grid, st, ba, cm, lh);
+        if (qp.any) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_CQ, grid, st, ba, cm, qp.bproj(i));
+        else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_CH, grid, st, ba, cm, lh);
         else S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_C, grid, st, ba, cm);
         if ((rc = launch_rc())) return rc;
         ScanAssocClipsArgs sa{reinterpret_cast<const float2 *>(l.lam), reinterpret_cast<const float2 *>(bu),
@@ -1482,13 +1544,15 @@ int float_forward_clips(const s5fxp_float_model *m, const float *x, int n, int L
         hipLaunchKernelGGL(k_scan_assoc_c64_clips, dim3((unsigned)scan_grid), dim3(64 * ASSOC_WAVES), 0, st, sa);
         if ((rc = launch_rc())) return rc;
         FGateArgs ga{xs, h, l.nm, l.ccat, l.D, l.w2, l.b2, hout, nullptr, nullptr, nullptr, lo ? lo + 3 : nullptr, N};
-        if (hist) S5_DISPATCH_DS(m->DS, S5_K_FGATE_CH, grid, st, ga, cm, lh + 3 * FM_HIST_BINS);
+        if (qp.any) S5_DISPATCH_DS(m->DS, S5_K_FGATE_CQ, grid, st, ga, cm, qp.gate(i));
+        else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FGATE_CH, grid, st, ga, cm, lh + 3 * FM_HIST_BINS);
         else S5_DISPATCH_DS(m->DS, S5_K_FGATE_C, grid, st, ga, cm);
         if ((rc = launch_rc())) return rc;
         h = hout;
     }
     FDecArgs da{h, m->dec_w, m->dec_b, y, obs ? obs + 2 + 10 * m->n_layers : nullptr, N};
-    if (hist) S5_DISPATCH_DS(m->DS, S5_K_FDEC_CH, grid, st, da, cm, hist + (size_t)(2 + 10 * m->n_layers) * FM_HIST_BINS);
+    if (qp.any) S5_DISPATCH_DS(m->DS, S5_K_FDEC_CQ, grid, st, da, cm, qp.dec());
+    else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FDEC_CH, grid, st, da, cm, hist + (size_t)(2 + 10 * m->n_layers) * FM_HIST_BINS);
     else S5_DISPATCH_DS(m->DS, S5_K_FDEC_C, grid, st, da, cm);
     return launch_rc();
 }
@@ -1499,7 +1563,14 @@ extern "C" int s5fxp_float_model_clips(const s5fxp_float_model *m, const float *
                                        float *stats, unsigned long long *hist, void *workspace, size_t workspace_bytes,
                                        void *stream)
 {
-    return float_forward_clips(m, x, n, Lmax, lens, y, stats, hist, workspace, workspace_bytes, stream);
+    return float_forward_clips(m, x, n, Lmax, lens, y, stats, hist, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int s5fxp_float_model_clips_fq(const s5fxp_float_model *m, const float *x, int n, int Lmax, const int32_t *lens, float *y,
+                                          float *stats, const s5fxp_float_fq_site *fq, void *workspace, size_t workspace_bytes,
+                                          void *stream)
+{
+    return float_forward_clips(m, x, n, Lmax, lens, y, stats, nullptr, fq, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t s5fxp_float_model_blob_bytes(const s5fxp_float_model_desc *desc)
@@ -1570,14 +1641,21 @@ extern "C" size_t s5fxp_float_trace_bytes(const s5fxp_float_model *m, int B, int
 extern "C" int s5fxp_float_model_forward(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats,
                                          float *trace, void *workspace, size_t workspace_bytes, void *stream)
 {
-    return float_forward(m, x, B, L, y, stats, nullptr, trace, workspace, workspace_bytes, stream);
+    return float_forward(m, x, B, L, y, stats, nullptr, nullptr, trace, workspace, workspace_bytes, stream);
 }
 
 extern "C" int s5fxp_float_model_forward_hist(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats,
                                               unsigned long long *hist, float *trace, void *workspace, size_t workspace_bytes,
                                               void *stream)
 {
-    return float_forward(m, x, B, L, y, stats, hist, trace, workspace, workspace_bytes, stream);
+    return float_forward(m, x, B, L, y, stats, hist, nullptr, trace, workspace, workspace_bytes, stream);
+}
+
+extern "C" int s5fxp_float_model_forward_fq(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats,
+                                            const s5fxp_float_fq_site *fq, float *trace, void *workspace, size_t workspace_bytes,
+                                            void *stream)
+{
+    return float_forward(m, x, B, L, y, stats, nullptr, fq, trace, workspace, workspace_bytes, stream);
 }
 
 #ifdef S5_PHASE_PROF

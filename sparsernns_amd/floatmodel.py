@@ -14,6 +14,10 @@ Clips of different lengths go through in the same launches (``forward_clips``, `
 clip gets what its own forward gives, and padding frames are never read, written or observed, so a calibration set that is
 ragged is calibrated on its real frames only (``calibrate`` / ``calibrate_clipped`` take ``(x, lens)`` pairs).
 
+Chosen observed tensors can be fake-quantised inside the forward (``fake_quant``, ``fq_spec``, ``fq=`` on every forward;
+DESIGN.md §4u): a site that is on rounds its tensor to the grid of its quantiser right after the observer saw it, so
+``sensitivity`` can say which of the 34 quantisers costs the output its SQNR, one at a time and all together.
+
 Results agree with ``synth.float_forward`` to float32 rounding (the summation order differs), not bit for bit.  Without a
 GPU, or for a shape the kernels refuse, ``FloatEngine`` runs ``synth.float_forward`` itself and says so: ``on_device`` is False.
 """
@@ -62,6 +66,28 @@ def tail_count(row, k: int) -> int:
     if not HIST_KMIN <= k <= HIST_KMAX:
         raise ValueError(f"the histogram answers thresholds 2^{HIST_KMIN} .. 2^{HIST_KMAX}, not 2^{k}")
     return int(np.asarray(row)[k - HIST_EMIN:].sum())
+
+
+FQ_SITE = np.dtype([("bits", np.int8), ("exp", np.int8), ("mode", np.uint8), ("saturate", np.uint8)])  # s5fxp_float_fq_site
+FQ_MODES = ("floor", "nearest")  # S5FXP_FQ_FLOOR, S5FXP_FQ_NEAREST
+FQ_BITS, FQ_EXPS = (2, 24), (-24, 40)  # the fields the entries accept; bits 0 switches a site off
+STATE_SITES = ("x_re", "x_im")  # never saturate: the integer model wraps its state (fxpmodel.py:147-172)
+
+
+def fake_quant(v, bits: int, exp: int, mode: str = "floor", saturate: bool = True) -> np.ndarray:
+    """The quantiser of the fake-quantised forward, float32 -> float32:
+    q(v) = clamp(R(v * 2^exp), -2^(bits-1), 2^(bits-1) - 1) * 2^-exp, R = floor (the integer model's shifts and input
+    conversion) or round-half-to-even (``mode="nearest"``); without ``saturate`` the clamp is left out; NaN stays NaN.
+    Computed in float64 and cast: for bits 2..24 and exp -24..40 both products and the rounded integer are exact in float32
+    (as long as v * 2^exp is a normal number), so this is the function the kernels compute with four float32 operations.
+    The reference of every fake-quantisation test."""
+    if mode not in FQ_MODES:
+        raise ValueError(f"mode must be one of {FQ_MODES}, got {mode!r}")
+    a = np.asarray(v, dtype=F32).astype(np.float64) * 2.0 ** int(exp)
+    r = np.floor(a) if mode == "floor" else np.rint(a)
+    if saturate:
+        r = np.clip(r, -2.0 ** (int(bits) - 1), 2.0 ** (int(bits) - 1) - 1)  # np.clip hands a NaN through
+    return (r * 2.0 ** -int(exp)).astype(F32)
 
 
 def _f32(a) -> np.ndarray:
@@ -162,6 +188,11 @@ class FloatEngine:
     def hist_dict(self, hist_dev: torch.Tensor) -> Dict[str, np.ndarray]:
         return {k: row.copy() for k, row in zip(self.keys, hist_dev.cpu().numpy())}
 
+    def _fq_arg(self, fq, hist) -> Optional[np.ndarray]:
+        if fq is not None and hist is not None:
+            raise ValueError("fake quantisation together with the histogram is not offered: pass fq or hist, not both")
+        return _check_fq(fq, self.keys)
+
     def _workspace(self, B: int, L: int, trace: bool) -> torch.Tensor:
         n = lib.s5fxp_float_workspace_bytes(self._h, B, L, int(trace)) // 4
         ws = self._ws.get(trace)
@@ -170,12 +201,15 @@ class FloatEngine:
         return ws
 
     def forward_device(self, x: torch.Tensor, stats_dev: Optional[torch.Tensor] = None, trace: bool = False,
-                       hist_dev: Optional[torch.Tensor] = None):
+                       hist_dev: Optional[torch.Tensor] = None, fq=None):
         """x (B,L,257) float32 on the device -> y (B,L,257); ``stats_dev`` (``new_stats``) is raised in place, ``hist_dev``
         (``new_hist``) is added to in place.  With ``trace`` also (trace buffer, workspace): the planes of ``forward_traced``
-        as flat tensors.  Stream-ordered, no sync."""
+        as flat tensors.  ``fq`` (``fq_spec``) fake-quantises the observed tensors whose site is on, each right
+        after it entered its observer (``s5fxp_float_model_forward_fq``); not together with ``hist_dev``.  Stream-ordered, no
+        sync."""
         if not self.on_device:
             raise RuntimeError("FloatEngine.forward_device needs the kernels (on_device is False)")
+        fq = self._fq_arg(fq, hist_dev)
         if x.dim() != 3 or x.shape[2] != self.d_in or x.dtype != torch.float32 or x.device != self.device:
             raise ValueError(f"x must be float32 (B, L, {self.d_in}) on {self.device}, got {x.dtype} {tuple(x.shape)} on {x.device}")
         if stats_dev is not None and (stats_dev.dtype != torch.float32 or stats_dev.numel() != len(self.keys)
@@ -191,7 +225,11 @@ class FloatEngine:
         tr = torch.empty(lib.s5fxp_float_trace_bytes(self._h, B, L) // 4, dtype=torch.float32, device=self.device) if trace else None
         st = None if stats_dev is None else stats_dev.data_ptr()
         with torch.cuda.device(self.device):
-            if hist_dev is None:
+            if fq is not None:
+                check(lib.s5fxp_float_model_forward_fq(self._h, x.data_ptr(), B, L, y.data_ptr(), st, fq.ctypes.data,
+                                                       None if tr is None else tr.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                                       torch.cuda.current_stream().cuda_stream), "s5fxp_float_model_forward_fq")
+            elif hist_dev is None:
                 check(lib.s5fxp_float_model_forward(self._h, x.data_ptr(), B, L, y.data_ptr(), st,
                                                     None if tr is None else tr.data_ptr(), ws.data_ptr(), ws.numel() * 4,
                                                     torch.cuda.current_stream().cuda_stream), "s5fxp_float_model_forward")
@@ -203,15 +241,16 @@ class FloatEngine:
         return (y, tr, ws) if trace else y
 
     def forward_clips_device(self, x: torch.Tensor, lens, stats_dev: Optional[torch.Tensor] = None,
-                             hist_dev: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                             hist_dev: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, fq=None) -> torch.Tensor:
         """n clips of different lengths in the launches of ONE forward (``s5fxp_float_model_clips``): x
         (n,Lmax,257) float32 on the device, padded; lens (n,) int32 on the device, as ``audio.stft_mag_clips`` writes it, clip e
         having len_e = clamp(lens[e], 0, Lmax) frames -> y (n,Lmax,257).  y[e, :len_e], ``stats_dev`` and ``hist_dev`` get bit for
         bit what ``forward_device(x[e:e+1, :len_e], ...)`` gives clip after clip: padding rows are never read, never written and
-        never observed.  ``out``: the tensor to write into; otherwise y is fresh and its padding unspecified.  Stream-ordered,
-        no sync."""
+        never observed.  ``out``: the tensor to write into; otherwise y is fresh and its padding unspecified.  ``fq`` as in
+        ``forward_device`` (``s5fxp_float_model_clips_fq``).  Stream-ordered, no sync."""
         if not self.on_device:
             raise RuntimeError("FloatEngine.forward_clips_device needs the kernels (on_device is False)")
+        fq = self._fq_arg(fq, hist_dev)
         if x.dim() != 3 or x.shape[2] != self.d_in or x.dtype != torch.float32 or x.device != self.device:
             raise ValueError(f"x must be float32 (n, Lmax, {self.d_in}) on {self.device}, got {x.dtype} {tuple(x.shape)} on {x.device}")
         n, Lmax = int(x.shape[0]), int(x.shape[1])
@@ -231,23 +270,30 @@ class FloatEngine:
         y = out if out is not None else torch.empty(shape, dtype=torch.float32, device=self.device)
         ws = self._workspace(n, Lmax, False)
         with torch.cuda.device(self.device):
+            if fq is not None:
+                check(lib.s5fxp_float_model_clips_fq(self._h, x.data_ptr(), n, Lmax, lens.data_ptr(), y.data_ptr(),
+                                                     None if stats_dev is None else stats_dev.data_ptr(), fq.ctypes.data,
+                                                     ws.data_ptr(), ws.numel() * 4, torch.cuda.current_stream().cuda_stream),
+                      "s5fxp_float_model_clips_fq")
+                return y
             check(lib.s5fxp_float_model_clips(self._h, x.data_ptr(), n, Lmax, lens.data_ptr(), y.data_ptr(),
                                               None if stats_dev is None else stats_dev.data_ptr(),
                                               None if hist_dev is None else hist_dev.data_ptr(), ws.data_ptr(), ws.numel() * 4,
                                               torch.cuda.current_stream().cuda_stream), "s5fxp_float_model_clips")
         return y
 
-    def forward_clips(self, clips, stats: Optional[dict] = None, hist: Optional[dict] = None) -> list:
+    def forward_clips(self, clips, stats: Optional[dict] = None, hist: Optional[dict] = None, fq=None) -> list:
         """A list of (len_e, 257) float32 clips, NumPy arrays or tensors -> the list of the model's outputs, each of its clip's
         kind: per clip what ``forward(clip[None])[0]`` returns, ``stats`` and ``hist`` updated as by those calls.  On the
         device the clips are padded once and take ``forward_clips_device``; otherwise ``synth.float_forward`` runs clip by
-        clip."""
+        clip.  ``fq`` as in ``forward``."""
+        fq = self._fq_arg(fq, hist)
         clips = list(clips)
         for c in clips:
             if len(c.shape) != 2 or c.shape[1] != self.d_in:
                 raise ValueError(f"every clip must be (len, {self.d_in}), got {tuple(c.shape)}")
         if not self.on_device:
-            return [self.forward(c[None], stats=stats, hist=hist)[0] for c in clips]
+            return [self.forward(c[None], stats=stats, hist=hist, fq=fq)[0] for c in clips]
         if not clips:
             return []
         ls = [int(c.shape[0]) for c in clips]
@@ -256,7 +302,7 @@ class FloatEngine:
             x[e, :ls[e]] = self._to_device(c)
         st = self.new_stats() if stats is not None else None
         hd = self.new_hist() if hist is not None else None
-        y = self.forward_clips_device(x, torch.tensor(ls, dtype=torch.int32, device=self.device), st, hd)
+        y = self.forward_clips_device(x, torch.tensor(ls, dtype=torch.int32, device=self.device), st, hd, fq=fq)
         if hist is not None:
             for k, row in self.hist_dict(hd).items():
                 hist[k] = hist.get(k, 0) + row
@@ -265,15 +311,18 @@ class FloatEngine:
                 stats[k] = max(stats.get(k, 0.0), v)
         return [y[e, :ls[e]].to(c.device) if isinstance(c, torch.Tensor) else y[e, :ls[e]].cpu().numpy() for e, c in enumerate(clips)]
 
-    def forward_traced(self, x, hist: bool = False) -> dict:
+    def forward_traced(self, x, hist: bool = False, fq=None) -> dict:
         """Every plane of one forward, as device tensors: ``h_enc`` (B,L,H), ``out`` (B,L,257), ``stats`` (the observer array
         of this forward alone), with ``hist`` also ``hist`` (its histogram array), and per layer ``l{i}.u / y / g_in / g / h_out`` (B,L,H) float32 and ``l{i}.Bu / xs`` (B,L,P)
-        complex64 (``xs`` raw, before the complex ReLU)."""
+        complex64 (``xs`` raw, before the complex ReLU).  Under ``fq`` the planes hold what downstream consumed: ``u``, ``y``,
+        ``g_in``, ``g``, ``Bu`` and ``out`` are post-quantiser, ``xs`` stays raw (its site acts where the gate kernel reads it)."""
+        if fq is not None and hist:
+            raise ValueError("fake quantisation together with the histogram is not offered: pass fq or hist, not both")
         xd = self._to_device(x)
         B, L = int(xd.shape[0]), int(xd.shape[1])
         st = self.new_stats()
         hd = self.new_hist() if hist else None
-        y, tr, ws = self.forward_device(xd, st, trace=True, hist_dev=hd)
+        y, tr, ws = self.forward_device(xd, st, trace=True, hist_dev=hd, fq=fq)
         NH, NP2 = B * L * self.H, B * L * 2 * self.P
         out = dict(out=y, stats=st, h_enc=ws[:NH].view(B, L, self.H).clone())
         if hist:
@@ -292,25 +341,28 @@ class FloatEngine:
         return torch.from_numpy(_f32(x)).to(self.device)
 
     # -- the mirror of synth.float_forward -----------------------------------------------------
-    def forward(self, x, stats: Optional[dict] = None, activations: Optional[dict] = None, hist: Optional[dict] = None):
+    def forward(self, x, stats: Optional[dict] = None, activations: Optional[dict] = None, hist: Optional[dict] = None,
+                fq=None):
         """x (B,L,257) float32, NumPy array or tensor -> the model's output of the same kind.  ``stats`` is updated by maximum
         and ``hist`` by addition (int64[64] rows) under ``synth.float_forward``'s keys; ``activations`` receives sequence 0 under the reference's keys (``pre_C`` = the
-        rectified states)."""
+        rectified states).  ``fq`` (``fq_spec``) fake-quantises the observed tensors whose site is on; not
+        together with ``hist``."""
+        fq = self._fq_arg(fq, hist)
         as_tensor = isinstance(x, torch.Tensor)
         if not self.on_device:
             xn = x.detach().cpu().numpy().astype(F32) if as_tensor else np.asarray(x, dtype=F32)
-            y = synth.float_forward(self.modeldict, xn, self.n_layers, stats=stats, activations=activations, hist=hist)
+            y = synth.float_forward(self.modeldict, xn, self.n_layers, stats=stats, activations=activations, hist=hist, fq=fq)
             return torch.from_numpy(y) if as_tensor else y
         xd = self._to_device(x)
         hd = None
         if activations is not None:
-            t = self.forward_traced(xd, hist=hist is not None)
+            t = self.forward_traced(xd, hist=hist is not None, fq=fq)
             y, st, hd = t["out"], t["stats"], t.get("hist")
             self._fill_activations(t, activations)
         else:
             st = self.new_stats() if stats is not None else None
             hd = self.new_hist() if hist is not None else None
-            y = self.forward_device(xd, st, hist_dev=hd)
+            y = self.forward_device(xd, st, hist_dev=hd, fq=fq)
         if hist is not None:
             for k, row in self.hist_dict(hd).items():
                 hist[k] = hist.get(k, 0) + row
@@ -459,6 +511,117 @@ def quantiser_of(key: str, fxp_qconfig: dict) -> Tuple[int, int]:
         return int(b["multgate"][f"{parts[2]}_bits"]), int(b["multgate"][f"{parts[2]}_exp"])
     a = b["ssm"]["activations"][parts[1]]
     return int(a["bits"]), int(a["exp"])
+
+
+def _site_error(key: str, bits: int, exp: int, mode: int, saturate: int) -> Optional[str]:
+    """Why ``s5fxp_float_model_forward_fq`` would refuse this site, or None."""
+    if bits == 0:
+        return None
+    if not FQ_BITS[0] <= bits <= FQ_BITS[1]:
+        return f"{key}: bits {bits} outside {FQ_BITS[0]}..{FQ_BITS[1]}"
+    if not FQ_EXPS[0] <= exp <= FQ_EXPS[1]:
+        return f"{key}: exp {exp} outside {FQ_EXPS[0]}..{FQ_EXPS[1]}"
+    if mode not in (0, 1):
+        return f"{key}: unknown mode {mode}"
+    if saturate not in (0, 1) or (saturate and key.split(".")[-1] in STATE_SITES):
+        return f"{key}: saturate {saturate} (the state sites never saturate)"
+    return None
+
+
+def fq_spec(fxp_qconfig: dict, n_layers: int, sites=None, mode: str = "floor") -> np.ndarray:
+    """The fake-quantisation spec of a forward: one ``FQ_SITE`` entry (bits, exp, mode, saturate) per observer, in
+    ``stat_keys`` order, (bits, exp) taken from ``quantiser_of``.  ``sites``: the keys to switch on (None: all of them);
+    every other entry is zero, i.e. off.  The state sites ``x_re`` / ``x_im`` never saturate, every other site does.
+    ``ValueError`` for an unknown key or mode and for a quantiser the entry would refuse, naming the key."""
+    if mode not in FQ_MODES:
+        raise ValueError(f"mode must be one of {FQ_MODES}, got {mode!r}")
+    keys = stat_keys(n_layers)
+    on = set(keys) if sites is None else set(sites)
+    unknown = sorted(on - set(keys))
+    if unknown:
+        raise ValueError(f"unknown observer keys {unknown}")
+    spec = np.zeros(len(keys), dtype=FQ_SITE)
+    for j, key in enumerate(keys):
+        if key not in on:
+            continue
+        bits, exp = quantiser_of(key, fxp_qconfig)
+        sat = int(key.split(".")[-1] not in STATE_SITES)
+        err = _site_error(key, bits, exp, FQ_MODES.index(mode), sat)
+        if err or bits == 0:
+            raise ValueError(f"fq_spec: {err or key + ': bits 0'}")
+        spec[j] = (bits, exp, FQ_MODES.index(mode), sat)
+    return spec
+
+
+def _check_fq(fq, keys) -> Optional[np.ndarray]:
+    """``fq`` as the contiguous FQ_SITE array the entries read, checked as they check it (ValueError names the key)."""
+    if fq is None:
+        return None
+    fq = np.ascontiguousarray(fq)
+    if fq.dtype != FQ_SITE or fq.shape != (len(keys),):
+        raise ValueError(f"fq must be an FQ_SITE array of {len(keys)} entries (fq_spec), got {fq.dtype} {fq.shape}")
+    for key, s in zip(keys, fq):
+        err = _site_error(key, int(s["bits"]), int(s["exp"]), int(s["mode"]), int(s["saturate"]))
+        if err:
+            raise ValueError(f"fq: {err}")
+    return fq
+
+
+def _real_frames(eng: "FloatEngine", item, fq) -> torch.Tensor:
+    """The model's output on the real frames of one calibration item, flat float64, on the engine's device."""
+    pair = _clip_pair(item)
+    if pair is None:
+        if eng.on_device:
+            return eng.forward_device(eng._to_device(item), fq=fq).double().flatten()
+        xn = item.detach().cpu().numpy() if isinstance(item, torch.Tensor) else item
+        return torch.from_numpy(eng.forward(np.asarray(xn, dtype=F32), fq=fq)).double().flatten()
+    x, Lmax = pair[0], int(pair[0].shape[1])
+    if eng.on_device:
+        lens = torch.as_tensor(pair[1]).to(device=eng.device, dtype=torch.int32)
+        y = eng.forward_clips_device(eng._to_device(x), lens, fq=fq)
+        real = torch.arange(Lmax, device=eng.device)[None, :] < lens.clamp(0, Lmax)[:, None]
+        return y[real].double().flatten()  # y's padding is unspecified: select, do not multiply
+    lens = [min(max(int(v), 0), Lmax) for v in torch.as_tensor(pair[1]).tolist()]
+    if len(lens) != int(x.shape[0]):
+        raise ValueError(f"{int(x.shape[0])} clips but {len(lens)} lengths")
+    ys = eng.forward_clips([x[e, :n] for e, n in enumerate(lens) if n], fq=fq)
+    return torch.cat([torch.as_tensor(y).double().flatten() for y in ys]) if ys else torch.zeros(0, dtype=torch.float64)
+
+
+def sensitivity(modeldict: dict, batches: Iterable, fxp_qconfig: dict, n_layers: int, groups=None, mode: str = "floor",
+                engine: Optional[FloatEngine] = None) -> Dict[str, float]:
+    """Which quantiser costs the accuracy: the output SQNR of the float model with one group of sites fake-quantised at a
+    time -> {group: sqnr_db} plus ``"all"`` (every group on at once).  ``groups`` maps a name to the observer keys it
+    switches on; the default is one group per key.  ``batches`` as for ``calibrate``: (B,L,257) batches, or pairs (x, lens)
+    that take the clip entry, of which only the real frames count.  Per batch one plain forward, one forward per group and
+    one with all groups run on the same input; sqnr_db = 10 log10(sum y^2 / sum (y_fq - y)^2), both sums accumulated in
+    float64 over all batches (on the device when the engine is); a zero difference gives inf.  What the figure does not
+    hold: quantised weights, and the rounding inside the integer recurrence (the state site quantises the scan's output)."""
+    eng = engine if engine is not None else FloatEngine(modeldict, n_layers)
+    keys = stat_keys(n_layers)
+    groups = {k: [k] for k in keys} if groups is None else {str(g): list(ks) for g, ks in dict(groups).items()}
+    if "all" in groups:
+        raise ValueError('"all" names the run with every group on; call a group something else')
+    specs = {g: fq_spec(fxp_qconfig, n_layers, ks, mode) for g, ks in groups.items()}
+    specs["all"] = fq_spec(fxp_qconfig, n_layers, [k for ks in groups.values() for k in ks], mode)
+    num, den, n = None, {}, 0
+    for item in batches:
+        y = _real_frames(eng, item, None)
+        e = (y * y).sum()
+        num = e if num is None else num + e
+        for g, spec in specs.items():
+            d = _real_frames(eng, item, spec) - y
+            e = (d * d).sum()
+            den[g] = e if g not in den else den[g] + e
+        n += 1
+    if not n:
+        raise ValueError("sensitivity needs at least one batch")
+    num = float(num)
+    out = {}
+    for g in specs:
+        d = float(den[g])
+        out[g] = math.inf if d == 0.0 else 10.0 * math.log10(num / d) if num > 0.0 else -math.inf
+    return out
 
 
 def range_report(hist: dict, fxp_qconfig: dict, n_layers: int) -> Dict[str, dict]:

@@ -146,12 +146,18 @@ def zoh(mixer: dict):
 
 
 def float_forward(modeldict: dict, x: np.ndarray, n_layers: int, calibrate_bn: bool = False,
-                  stats: Optional[dict] = None, activations: Optional[dict] = None, hist: Optional[dict] = None) -> np.ndarray:
+                  stats: Optional[dict] = None, activations: Optional[dict] = None, hist: Optional[dict] = None,
+                  fq=None) -> np.ndarray:
     """x: (B,L,d_in) float32.  Records absmax observers into ``stats`` when given, adds the exponent histogram of every
     observed tensor (``floatmodel.exp_hist``, int64[64]) to ``hist`` under the same key when given, and -- for the verification report
     (sparsernns_amd/fxpreporter.py) -- the float intermediates of sequence 0 into ``activations`` under the keys the
     reference's float model sows (sparseRNNs/model/layers.py:181-243: input, pre_s5, pre_C, pre_GLU, out2/__call__, the
-    layer's __call__; ssm.py: mixer/__call__, B_bar; post_GLU = the second drop/__call__ that fxprun.py:688-698 reads)."""
+    layer's __call__; ssm.py: mixer/__call__, B_bar; post_GLU = the second drop/__call__ that fxprun.py:688-698 reads).
+
+    ``fq`` (``floatmodel.fq_spec``): every observed tensor whose site is on is replaced by
+    ``floatmodel.fake_quant`` of itself right after it entered its observer, so everything downstream -- the later observers
+    included -- sees the quantised value.  The state site acts on the raw scan output, before the complex ReLU; the rounding
+    inside the integer recurrence is not modelled.  ``fq=None`` changes nothing, to the bit."""
 
     def obs(key, v):
         if stats is not None:
@@ -160,11 +166,26 @@ def float_forward(modeldict: dict, x: np.ndarray, n_layers: int, calibrate_bn: b
             from .floatmodel import exp_hist
             hist[key] = hist.get(key, 0) + exp_hist(v)
 
+    site = {}
+    if fq is not None:
+        from .floatmodel import FQ_MODES, fake_quant, stat_keys
+        keys = stat_keys(n_layers)
+        if len(fq) != len(keys):
+            raise ValueError(f"fq must have one entry per observer ({len(keys)}), got {len(fq)}")
+        site = {k: s for k, s in zip(keys, fq) if int(s["bits"])}
+
+    def q(key, v):
+        s = site.get(key)
+        if s is None:
+            return v
+        return fake_quant(v, int(s["bits"]), int(s["exp"]), FQ_MODES[int(s["mode"])], bool(s["saturate"]))
+
     enc = modeldict["encoder"]
     obs("encoder.inp", x)
+    x = q("encoder.inp", x)
     h = x @ enc["encoder"]["kernel"] + enc["encoder"]["bias"]
     obs("encoder.out", h)
-    h = np.maximum(h, 0)
+    h = np.maximum(q("encoder.out", h), 0)
     act_enc = activations.setdefault("encoder", {}) if activations is not None else None
     for i in range(n_layers):
         layer = enc[f"layers_{i}"]
@@ -180,10 +201,13 @@ def float_forward(modeldict: dict, x: np.ndarray, n_layers: int, calibrate_bn: b
         if "bias" in nm:
             u = u + nm["bias"]
         obs(f"l{i}.u", u)
+        u = q(f"l{i}.u", u)
         lam_bar, B_bar, C = zoh(layer["mixer"])
         Bu = u.astype(np.complex64) @ B_bar.T
         obs(f"l{i}.Bu_re", Bu.real)
         obs(f"l{i}.Bu_im", Bu.imag)
+        if f"l{i}.Bu_re" in site or f"l{i}.Bu_im" in site:
+            Bu = (q(f"l{i}.Bu_re", Bu.real) + 1j * q(f"l{i}.Bu_im", Bu.imag)).astype(np.complex64)
         xs = np.empty_like(Bu)
         st = np.zeros((Bu.shape[0], Bu.shape[2]), dtype=np.complex64)
         for t in range(Bu.shape[1]):
@@ -191,17 +215,22 @@ def float_forward(modeldict: dict, x: np.ndarray, n_layers: int, calibrate_bn: b
             xs[:, t] = st
         obs(f"l{i}.x_re", xs.real)
         obs(f"l{i}.x_im", xs.imag)
+        if f"l{i}.x_re" in site or f"l{i}.x_im" in site:
+            xs = (q(f"l{i}.x_re", xs.real) + 1j * q(f"l{i}.x_im", xs.imag)).astype(np.complex64)
         keep = (xs.real > 0) | ((xs.real == 0) & (xs.imag > 0))
         xs = np.where(keep, xs, 0)
         y = 2 * (xs.real @ C.real.T - xs.imag @ C.imag.T) + layer["mixer"]["D"] * u
         obs(f"l{i}.y", y)
+        y = q(f"l{i}.y", y)
         x1 = np.maximum(y, 0)
         obs(f"l{i}.out2.inp", x1)
-        g_in = x1 @ layer["out2"]["kernel"] + layer["out2"]["bias"]
+        g_in = q(f"l{i}.out2.inp", x1) @ layer["out2"]["kernel"] + layer["out2"]["bias"]
         obs(f"l{i}.out2.out", g_in)
+        g_in = q(f"l{i}.out2.out", g_in)
         g = 1 / (1 + np.exp(-g_in))
         obs(f"l{i}.gate.l", x1)
         obs(f"l{i}.gate.r", g)
+        x1, g = q(f"l{i}.gate.l", x1), q(f"l{i}.gate.r", g)
         h = np.maximum(x1 * g + skip, 0).astype(F32)
         if act is not None:
             act.update(input=skip[0].astype(F32), pre_s5=u[0].astype(F32), pre_C=xs[0].astype(np.complex64), pre_GLU=y[0].astype(F32),
@@ -209,8 +238,9 @@ def float_forward(modeldict: dict, x: np.ndarray, n_layers: int, calibrate_bn: b
             act["mixer"] = dict(B_bar=B_bar.astype(np.complex64), __call__=y[0].astype(F32))
             act["out2"] = dict(__call__=g_in[0].astype(F32))
     obs("decoder.inp", h)
-    out = h @ modeldict["decoder"]["kernel"] + modeldict["decoder"]["bias"]
+    out = q("decoder.inp", h) @ modeldict["decoder"]["kernel"] + modeldict["decoder"]["bias"]
     obs("decoder.out", out)
+    out = q("decoder.out", out)
     if activations is not None:
         activations["__call__"] = out[0].astype(F32)
     return out.astype(F32)
