@@ -28,19 +28,20 @@
 // CLIPS (the k_*_clips and k_*_clips_hist kernels) run n clips of different lengths, padded to Lmax rows each, in
 // one launch: a tile belongs to one clip (FClipMap), holds the rows the clip has there and is skipped when it has none, so
 // every clip gets bit for bit what the rectangular kernels give it alone and no padding row is read, written or observed.
-// They are two more inclusions of float_model_kernels.inc (FM_CLIPS 1), for the reason given below for FM_HIST.
 //
 // FQ (the k_*_fq and k_*_clips_fq kernels) fake-quantise chosen observed tensors: a site that is on replaces the
 // value, right after it entered its observer, by q(v) = clamp(R(v 2^exp), lo, hi) 2^-exp (fm_fq: four VALU operations, none
 // of which can be contracted).  The sites reach a kernel as one more by-value parameter, FFq<n>, so that no argument struct of
-// the existing kernels grows.  Two more inclusions (FM_FQ 1), built without the histogram.
+// the existing kernels grows.  Built without the histogram.
 //
-// The four kernels are written once, in float_model_kernels.inc, which this header includes once per form: with FM_HIST 0 it gives
-// k_fenc, k_fbproj, k_fgate, k_fdec -- token for token the kernels as they were before the histogram, so their instruction
-// streams do not move -- and with FM_HIST 1 k_fenc_hist, ... with one more argument.  The flag is a preprocessor one and not
-// a template parameter because both alternatives change the existing kernels: a template parameter changes their mangled
-// names (and their kernarg layout, if the argument struct grows), and a shared __device__ body behind thin __global__
-// wrappers compiles to different code than the same text inside the kernel (measured: tools/disasm_compare.py).
+// The four kernels are written once, in float_model_kernels.inc, which this header includes once per form, six times: plain
+// (k_fenc, k_fbproj, k_fgate, k_fdec), _hist, _clips, _clips_hist, _fq and _clips_fq.  A form is three preprocessor flags
+// (FM_HIST, FM_CLIPS, FM_FAKEQ) and a name suffix; the .inc derives everything else from them and cleans up after itself.
+// With all flags 0 the text is token for token the kernels as they were before any other form existed, so their instruction
+// streams do not move.  The flags are preprocessor ones and not template parameters because both alternatives change the
+// existing kernels: a template parameter changes their mangled names (and their kernarg layout, if the argument struct
+// grows), and a shared __device__ body behind thin __global__ wrappers compiles to different code than the same text inside
+// the kernel (measured: tools/disasm_compare.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -250,178 +251,42 @@ struct FClipMap {
     long long tiles; // n * tpc
 };
 
-// FM_TILES: the launch's tile count.  FM_TILE: declares the tile's first row r0 and its valid row prefix `rows`.
-#define FM_TILES_RECT(N) (((N) + FM_FT - 1) / FM_FT)
-#define FM_TILE_RECT(tile, N, r0, rows)   \
-    const long long r0 = tile * FM_FT; \
-    const int rows = (int)(N - r0 < FM_FT ? N - r0 : FM_FT)
-// the clip's tile: rows = clamp(len - t0, 0, 32) stays a contiguous prefix; a tile without rows is left before its first
-// load (workgroup-uniform, so the barriers stay matched)
-#define FM_TILE_CLIP(tile, N, r0, rows)                                                              \
-    const int clip_ = (int)(tile / cm.tpc), t0_ = FM_FT * (int)(tile - (long long)clip_ * cm.tpc); \
-    const int raw_ = cm.lens[clip_], len_ = raw_ < cm.Lmax ? raw_ : cm.Lmax;                         \
-    const int rows = len_ - t0_ < FM_FT ? len_ - t0_ : FM_FT;                                        \
-    if (rows <= 0) continue;                                                                         \
-    const long long r0 = (long long)clip_ * cm.Lmax + t0_
-
-#define FM_HIST_OFF_BEGIN(planes)
-#define FM_HIST_OFF_ADD(plane, v)
-#define FM_HIST_OFF_END(...)
-#define FM_HIST_ON_BEGIN(planes)                    \
-    unsigned *const shist = fm_hist_lds<planes>(); \
-    fm_hist_zero<planes>(shist)
-#define FM_HIST_ON_ADD(plane, v) fm_hist_add(shist, plane, v)
-#define FM_HIST_ON_END(...) fm_hist_flush<__VA_ARGS__>(shist, hist)
-
-#define FM_FQ_OFF(site, v) (v)
-#define FM_FQ2_OFF(odd, site_odd, site_even, v) (v)
-#define FM_FQ_V4_OFF(site, v)
-#define FM_FQ_V2_OFF(site_x, site_y, v)
-#define FM_FQ_ON(site, v) fm_fq(v, fq.s[site])
-#define FM_FQ_V4_ON(site, v) v = make_float4(fm_fq(v.x, fq.s[site]), fm_fq(v.y, fq.s[site]), fm_fq(v.z, fq.s[site]), fm_fq(v.w, fq.s[site]))
-#define FM_FQ_V2_ON(site_x, site_y, v) v = make_float2(fm_fq(v.x, fq.s[site_x]), fm_fq(v.y, fq.s[site_y]))
-#define FM_FQ2_ON(odd, site_odd, site_even, v) ((odd) ? fm_fq(v, fq.s[site_odd]) : fm_fq(v, fq.s[site_even]))
-
-// the four forms without fake quantisation
-#define FM_FQ_PARAM(n)
-#define FM_FQ FM_FQ_OFF
-#define FM_FQ2 FM_FQ2_OFF
-#define FM_FQ_V4 FM_FQ_V4_OFF
-#define FM_FQ_V2 FM_FQ_V2_OFF
-
+// The six forms of the four kernels.  An inclusion states its three flags and its kernel-name suffix and nothing else; what
+// follows from them is defined at the head of float_model_kernels.inc and undefined, the flags included, at its foot.
 #define FM_HIST 0
 #define FM_CLIPS 0
+#define FM_FAKEQ 0
 #define FM_KERNEL(name) name
-#define FM_CLIPS_PARAM
-#define FM_HIST_PARAM
-#define FM_TILES FM_TILES_RECT
-#define FM_TILE FM_TILE_RECT
-#define FM_GATE_ATTR
-#define FM_HIST_BEGIN FM_HIST_OFF_BEGIN
-#define FM_HIST_ADD FM_HIST_OFF_ADD
-#define FM_HIST_END FM_HIST_OFF_END
 #include "float_model_kernels.inc"
-#undef FM_HIST
-#undef FM_KERNEL
-#undef FM_HIST_PARAM
-#undef FM_HIST_BEGIN
-#undef FM_HIST_ADD
-#undef FM_HIST_END
 
 #define FM_HIST 1
-#define FM_KERNEL(name) name##_hist
-#define FM_HIST_PARAM , unsigned long long *hist
-#define FM_HIST_BEGIN FM_HIST_ON_BEGIN
-#define FM_HIST_ADD FM_HIST_ON_ADD
-#define FM_HIST_END FM_HIST_ON_END
-#include "float_model_kernels.inc"
-#undef FM_HIST
-#undef FM_CLIPS
-#undef FM_KERNEL
-#undef FM_CLIPS_PARAM
-#undef FM_HIST_PARAM
-#undef FM_TILES
-#undef FM_TILE
-#undef FM_GATE_ATTR
-#undef FM_HIST_BEGIN
-#undef FM_HIST_ADD
-#undef FM_HIST_END
-
-// the clip forms: the same text over FClipMap's tile mapping
-#define FM_HIST 0
-#define FM_CLIPS 1
-#define FM_KERNEL(name) name##_clips
-#define FM_CLIPS_PARAM , FClipMap cm
-#define FM_HIST_PARAM
-#define FM_TILES(N) cm.tiles
-#define FM_TILE FM_TILE_CLIP
-// the clip mapping's row addresses cost k_fgate_clips<2> ten VGPRs (246 for the rectangular kernel's 236), one granule past
-// two waves per SIMD, and at one wave it ran 196 us for the rectangular kernel's 122; asked for two, the allocator fits 240
-// without scratch
-#define FM_GATE_ATTR __attribute__((amdgpu_waves_per_eu(DS == 2 ? 2 : 1)))
-#define FM_HIST_BEGIN FM_HIST_OFF_BEGIN
-#define FM_HIST_ADD FM_HIST_OFF_ADD
-#define FM_HIST_END FM_HIST_OFF_END
-#include "float_model_kernels.inc"
-#undef FM_HIST
-#undef FM_KERNEL
-#undef FM_HIST_PARAM
-#undef FM_HIST_BEGIN
-#undef FM_HIST_ADD
-#undef FM_HIST_END
-
-#define FM_HIST 1
-#define FM_KERNEL(name) name##_clips_hist
-#define FM_HIST_PARAM , unsigned long long *hist
-#define FM_HIST_BEGIN FM_HIST_ON_BEGIN
-#define FM_HIST_ADD FM_HIST_ON_ADD
-#define FM_HIST_END FM_HIST_ON_END
-#include "float_model_kernels.inc"
-#undef FM_HIST
-#undef FM_CLIPS
-#undef FM_KERNEL
-#undef FM_CLIPS_PARAM
-#undef FM_HIST_PARAM
-#undef FM_TILES
-#undef FM_TILE
-#undef FM_GATE_ATTR
-#undef FM_HIST_BEGIN
-#undef FM_HIST_ADD
-#undef FM_HIST_END
-#undef FM_FQ_PARAM
-#undef FM_FQ
-#undef FM_FQ2
-#undef FM_FQ_V4
-#undef FM_FQ_V2
-
-// the fake-quantising forms, rectangular and clips, both without the histogram
-#define FM_HIST 0
-#define FM_HIST_PARAM
-#define FM_HIST_BEGIN FM_HIST_OFF_BEGIN
-#define FM_HIST_ADD FM_HIST_OFF_ADD
-#define FM_HIST_END FM_HIST_OFF_END
-#define FM_FQ_PARAM(n) , FFq<n> fq
-#define FM_FQ FM_FQ_ON
-#define FM_FQ2 FM_FQ2_ON
-#define FM_FQ_V4 FM_FQ_V4_ON
-#define FM_FQ_V2 FM_FQ_V2_ON
-
 #define FM_CLIPS 0
-#define FM_KERNEL(name) name##_fq
-#define FM_CLIPS_PARAM
-#define FM_TILES FM_TILES_RECT
-#define FM_TILE FM_TILE_RECT
-#define FM_GATE_ATTR
+#define FM_FAKEQ 0
+#define FM_KERNEL(name) name##_hist
 #include "float_model_kernels.inc"
-#undef FM_CLIPS
-#undef FM_KERNEL
-#undef FM_CLIPS_PARAM
-#undef FM_TILES
-#undef FM_TILE
-#undef FM_GATE_ATTR
 
+#define FM_HIST 0
 #define FM_CLIPS 1
-#define FM_KERNEL(name) name##_clips_fq
-#define FM_CLIPS_PARAM , FClipMap cm
-#define FM_TILES(N) cm.tiles
-#define FM_TILE FM_TILE_CLIP
-#define FM_GATE_ATTR __attribute__((amdgpu_waves_per_eu(DS == 2 ? 2 : 1))) // as k_fgate_clips
+#define FM_FAKEQ 0
+#define FM_KERNEL(name) name##_clips
 #include "float_model_kernels.inc"
-#undef FM_HIST
-#undef FM_CLIPS
-#undef FM_KERNEL
-#undef FM_CLIPS_PARAM
-#undef FM_HIST_PARAM
-#undef FM_TILES
-#undef FM_TILE
-#undef FM_GATE_ATTR
-#undef FM_HIST_BEGIN
-#undef FM_HIST_ADD
-#undef FM_HIST_END
-#undef FM_FQ_PARAM
-#undef FM_FQ
-#undef FM_FQ2
-#undef FM_FQ_V4
-#undef FM_FQ_V2
+
+#define FM_HIST 1
+#define FM_CLIPS 1
+#define FM_FAKEQ 0
+#define FM_KERNEL(name) name##_clips_hist
+#include "float_model_kernels.inc"
+
+#define FM_HIST 0
+#define FM_CLIPS 0
+#define FM_FAKEQ 1
+#define FM_KERNEL(name) name##_fq
+#include "float_model_kernels.inc"
+
+#define FM_HIST 0
+#define FM_CLIPS 1
+#define FM_FAKEQ 1
+#define FM_KERNEL(name) name##_clips_fq
+#include "float_model_kernels.inc"
 
 } // namespace s5

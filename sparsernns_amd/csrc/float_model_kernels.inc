@@ -1,14 +1,80 @@
-// float_model_kernels.inc -- the float model's four tile kernels, included by float_model.hpp four times (no include guard):
-// FM_HIST 0 gives k_fenc / k_fbproj / k_fgate / k_fdec, FM_HIST 1 gives k_fenc_hist / ... which take `hist` as well and count
-// every value into its observer's exponent histogram where it enters the observer.  With FM_HIST 0 every FM_HIST_* macro is
-// empty.  FM_CLIPS 1 gives k_fenc_clips / ... and k_fenc_clips_hist / ..., which take an FClipMap as well: FM_TILES and
-// FM_TILE then map a tile to a clip's rows (and skip it when the clip has none there) instead of to rows 32*tile.. of N.
-// FM_FQ 1 gives k_fenc_fq / ... and k_fenc_clips_fq / ... (DESIGN.md 4u), which take the kernel's fake-quantisation sites `fq` as
-// well: FM_FQ(site, v) is then fm_fq(v, fq.s[site]), the value the site hands downstream, placed right behind the statement
-// where v enters its observer; FM_FQ2 chooses between two sites by a lane predicate; FM_FQ_V4 / FM_FQ_V2 are statements that
-// quantise a float4 by one site / a float2 by one site per component in place.  With FM_FQ 0 the first two are (v) and the
-// statements are empty.
+// float_model_kernels.inc -- the float model's four tile kernels (encoder, B projection, gate, decoder), written once.
+// float_model.hpp includes this file once per form, six times (no include guard), and states before each inclusion only what
+// tells the form from the others: three 0/1 flags and the kernel-name suffix,
+//   FM_HIST    count every value into its observer's exponent histogram where it enters the observer (DESIGN.md 4s);
+//   FM_CLIPS   run n clips of different lengths: a tile maps to one clip's rows through an FClipMap (DESIGN.md 4t);
+//   FM_FAKEQ   fake-quantise the observed tensors whose site is on (DESIGN.md 4u); built without the histogram;
+//   FM_KERNEL(name)  name##_suffix: none, _hist, _clips, _clips_hist, _fq, _clips_fq.
+// The prologue below derives from the flags every macro the kernel text uses, the epilogue at the foot undefines them and
+// the flags and FM_KERNEL with them, so no macro state goes from one inclusion to the next:
+//   FM_CLIPS_PARAM, FM_HIST_PARAM, FM_FQ_PARAM(n)  the parameters a form takes after the kernel's argument struct:
+//       `FClipMap cm`, `unsigned long long *hist`, `FFq<n> fq`, each only in its form;
+//   FM_TILES(N), FM_TILE(tile, N, r0, rows)  the launch's tile count, and the declaration of a tile's first row r0 and its
+//       valid row prefix `rows`: rows 32 * tile .. of N, or the rows the tile's clip has there (a tile without rows is
+//       skipped);
+//   FM_GATE_ATTR  the gate kernel's occupancy attribute in the clip forms;
+//   FM_HIST_BEGIN(planes), FM_HIST_ADD(plane, v), FM_HIST_END(planes[, dup_src, dup_row])  the workgroup's LDS histograms:
+//       set up, one value in, flush; all three empty without FM_HIST;
+//   FM_FQ(site, v)  fm_fq(v, fq.s[site]), the value the site hands downstream, placed right behind the statement where v
+//       enters its observer; FM_FQ2(odd, site_odd, site_even, v) chooses between two sites by a lane predicate;
+//       FM_FQ_V4(site, v) / FM_FQ_V2(site_x, site_y, v) are statements that quantise a float4 by one site / a float2 by one
+//       site per component in place.  Without FM_FAKEQ the first two are (v) and the statements are empty.
 // Not a translation unit of its own; everything it uses is declared in float_model.hpp, inside namespace s5.
+#if !defined(FM_HIST) || !defined(FM_CLIPS) || !defined(FM_FAKEQ) || !defined(FM_KERNEL) || (FM_HIST && FM_FAKEQ)
+#error "float_model_kernels.inc: define FM_HIST, FM_CLIPS, FM_FAKEQ (0/1, not FM_HIST with FM_FAKEQ) and FM_KERNEL(name)"
+#endif
+
+#if FM_CLIPS
+#define FM_CLIPS_PARAM , FClipMap cm
+#define FM_TILES(N) cm.tiles
+// the clip's tile: rows = clamp(len - t0, 0, 32) stays a contiguous prefix; a tile without rows is left before its first
+// load (workgroup-uniform, so the barriers stay matched)
+#define FM_TILE(tile, N, r0, rows)                                                                   \
+    const int clip_ = (int)(tile / cm.tpc), t0_ = FM_FT * (int)(tile - (long long)clip_ * cm.tpc); \
+    const int raw_ = cm.lens[clip_], len_ = raw_ < cm.Lmax ? raw_ : cm.Lmax;                         \
+    const int rows = len_ - t0_ < FM_FT ? len_ - t0_ : FM_FT;                                        \
+    if (rows <= 0) continue;                                                                         \
+    const long long r0 = (long long)clip_ * cm.Lmax + t0_
+// the clip mapping's row addresses cost k_fgate_clips<2> ten VGPRs (246 for the rectangular kernel's 236), one granule past
+// two waves per SIMD, and at one wave it ran 196 us for the rectangular kernel's 122; asked for two, the allocator fits 240
+// without scratch
+#define FM_GATE_ATTR __attribute__((amdgpu_waves_per_eu(DS == 2 ? 2 : 1)))
+#else
+#define FM_CLIPS_PARAM
+#define FM_TILES(N) (((N) + FM_FT - 1) / FM_FT)
+#define FM_TILE(tile, N, r0, rows)     \
+    const long long r0 = tile * FM_FT; \
+    const int rows = (int)(N - r0 < FM_FT ? N - r0 : FM_FT)
+#define FM_GATE_ATTR
+#endif
+
+#if FM_HIST
+#define FM_HIST_PARAM , unsigned long long *hist
+#define FM_HIST_BEGIN(planes)                       \
+    unsigned *const shist = fm_hist_lds<planes>(); \
+    fm_hist_zero<planes>(shist)
+#define FM_HIST_ADD(plane, v) fm_hist_add(shist, plane, v)
+#define FM_HIST_END(...) fm_hist_flush<__VA_ARGS__>(shist, hist)
+#else
+#define FM_HIST_PARAM
+#define FM_HIST_BEGIN(planes)
+#define FM_HIST_ADD(plane, v)
+#define FM_HIST_END(...)
+#endif
+
+#if FM_FAKEQ
+#define FM_FQ_PARAM(n) , FFq<n> fq
+#define FM_FQ(site, v) fm_fq(v, fq.s[site])
+#define FM_FQ2(odd, site_odd, site_even, v) ((odd) ? fm_fq(v, fq.s[site_odd]) : fm_fq(v, fq.s[site_even]))
+#define FM_FQ_V4(site, v) v = make_float4(fm_fq(v.x, fq.s[site]), fm_fq(v.y, fq.s[site]), fm_fq(v.z, fq.s[site]), fm_fq(v.w, fq.s[site]))
+#define FM_FQ_V2(site_x, site_y, v) v = make_float2(fm_fq(v.x, fq.s[site_x]), fm_fq(v.y, fq.s[site_y]))
+#else
+#define FM_FQ_PARAM(n)
+#define FM_FQ(site, v) (v)
+#define FM_FQ2(odd, site_odd, site_even, v) (v)
+#define FM_FQ_V4(site, v)
+#define FM_FQ_V2(site_x, site_y, v)
+#endif
 
 // ------------------------------------------------------------------------------------------------------------------
 // encoder: h = relu(x W + b); observers [0] encoder.inp, [1] encoder.out (before the ReLU)
@@ -331,3 +397,21 @@ __global__ __launch_bounds__(256) void FM_KERNEL(k_fdec)(FDecArgs a FM_CLIPS_PAR
     fm_obs_flush<2>(om, sobs, a.stats);
     FM_HIST_END(2);
 }
+
+#undef FM_HIST
+#undef FM_CLIPS
+#undef FM_FAKEQ
+#undef FM_KERNEL
+#undef FM_CLIPS_PARAM
+#undef FM_TILES
+#undef FM_TILE
+#undef FM_GATE_ATTR
+#undef FM_HIST_PARAM
+#undef FM_HIST_BEGIN
+#undef FM_HIST_ADD
+#undef FM_HIST_END
+#undef FM_FQ_PARAM
+#undef FM_FQ
+#undef FM_FQ2
+#undef FM_FQ_V4
+#undef FM_FQ_V2

@@ -1351,32 +1351,54 @@ size_t float_pack(const s5fxp_float_model_desc *d, FloatPacker &p, s5fxp_float_m
 
 constexpr long long FM_GRID_CAP = 512; // workgroups per launch: the weights are loaded into registers once per workgroup
 
-#define S5_DISPATCH_DS(ds, KERNEL, grid, stream, ...)                                                        \
-    do {                                                                                                     \
-        if ((ds) == 1) hipLaunchKernelGGL((KERNEL(1)), dim3(grid), dim3(256), 0, stream, __VA_ARGS__);       \
-        else if ((ds) == 2) hipLaunchKernelGGL((KERNEL(2)), dim3(grid), dim3(256), 0, stream, __VA_ARGS__);  \
-        else if ((ds) == 3) hipLaunchKernelGGL((KERNEL(3)), dim3(grid), dim3(256), 0, stream, __VA_ARGS__);  \
-        else hipLaunchKernelGGL((KERNEL(4)), dim3(grid), dim3(256), 0, stream, __VA_ARGS__);                 \
-    } while (0)
-#define S5_K_FENC(ds) k_fenc<ds>
-#define S5_K_FDEC(ds) k_fdec<ds>
-#define S5_K_FBPROJ_T(ds) k_fbproj<ds, true>
-#define S5_K_FBPROJ(ds) k_fbproj<ds, false>
-#define S5_K_FGATE_T(ds) k_fgate<ds, true>
-#define S5_K_FGATE(ds) k_fgate<ds, false>
-#define S5_K_FENC_H(ds) k_fenc_hist<ds>
-#define S5_K_FDEC_H(ds) k_fdec_hist<ds>
-#define S5_K_FBPROJ_TH(ds) k_fbproj_hist<ds, true>
-#define S5_K_FBPROJ_H(ds) k_fbproj_hist<ds, false>
-#define S5_K_FGATE_TH(ds) k_fgate_hist<ds, true>
-#define S5_K_FGATE_H(ds) k_fgate_hist<ds, false>
+// Local to float_forward<CLIPS> (they use its m, trace and CLIPS) and undefined behind it.  FM_AT_DS: the kernel template k at
+// dim_scale ds; what follows are k's template arguments after DS.  FM_K / FM_K_TRACE: the stage kernel of the launch that
+// runs, at the model's DS -- `rect` (FM_K_TRACE: rect<DS, trace>) or `clip` (the clip forms have no traced kernels:
+// clip<DS, false>).  The other one sits in a discarded statement, so float_forward<true> names no traced clip kernel, which
+// would create it.  The code object lays kernels out in the order the host code first names them; this keeps it: DS 1..4,
+// traced before untraced, every rectangular kernel before the first clip one.
+#define FM_AT_DS(ds, k, ...) \
+    ((ds) <= 2 ? ((ds) == 1 ? k<1, ##__VA_ARGS__> : k<2, ##__VA_ARGS__>) : ((ds) == 3 ? k<3, ##__VA_ARGS__> : k<4, ##__VA_ARGS__>))
+#define FM_RECT_OR_CLIP(rect, clip)       \
+    [&] {                                 \
+        if constexpr (CLIPS) return clip; \
+        else return rect;                 \
+    }()
+#define FM_K(rect, clip) FM_RECT_OR_CLIP(FM_AT_DS(m->DS, rect), FM_AT_DS(m->DS, clip))
+#define FM_K_TRACE(rect, clip) \
+    FM_RECT_OR_CLIP((trace ? FM_AT_DS(m->DS, rect, true) : FM_AT_DS(m->DS, rect, false)), FM_AT_DS(m->DS, clip, false))
 
-#define S5_K_FENC_Q(ds) k_fenc_fq<ds>
-#define S5_K_FDEC_Q(ds) k_fdec_fq<ds>
-#define S5_K_FBPROJ_TQ(ds) k_fbproj_fq<ds, true>
-#define S5_K_FBPROJ_Q(ds) k_fbproj_fq<ds, false>
-#define S5_K_FGATE_TQ(ds) k_fgate_fq<ds, true>
-#define S5_K_FGATE_Q(ds) k_fgate_fq<ds, false>
+// What the rectangular launch (B sequences of L rows) and the clip launch (B clips padded to L rows, lens[e] of them real)
+// differ in
+struct FmTiling {
+    long long N, tiles;
+    unsigned grid;
+    FClipMap cm; // clips only
+};
+
+FmTiling fm_tiling(int B, int L, bool clips, const int32_t *lens)
+{
+    const int tpc = (int)(((long long)L + FM_FT - 1) / FM_FT);
+    FmTiling t{};
+    t.N = (long long)B * L;
+    t.tiles = clips ? (long long)B * tpc : (t.N + FM_FT - 1) / FM_FT;
+    t.grid = (unsigned)(t.tiles < FM_GRID_CAP ? t.tiles : FM_GRID_CAP);
+    // A stride that shares a factor with tpc ties a workgroup to few tile positions: at 512 and tpc = 16 it would see the same
+    // position of every clip it visits, the workgroups of the early positions all the work and those of the late ones next to
+    // none.  A stride coprime to tpc walks every workgroup through all positions.
+    if (clips && t.tiles > t.grid)
+        while (std::gcd(t.grid, (unsigned)tpc) != 1) --t.grid;
+    t.cm = FClipMap{lens, L, tpc, t.tiles};
+    return t;
+}
+
+// One tile-kernel launch: k(a, [the FClipMap,] what k's form takes behind that: nothing, the histogram rows or the FFq<n> sites)
+template <bool CLIPS, class K, class Args, class... Extra>
+void fm_launch(const FmTiling &t, hipStream_t st, K k, const Args &a, Extra... extra)
+{
+    if constexpr (CLIPS) hipLaunchKernelGGL(k, dim3(t.grid), dim3(256), 0, st, a, t.cm, extra...);
+    else hipLaunchKernelGGL(k, dim3(t.grid), dim3(256), 0, st, a, extra...);
+}
 
 static_assert(FM_HIST_BINS == S5FXP_FLOAT_HIST_BINS && FM_HIST_EMIN == S5FXP_FLOAT_HIST_EMIN, "include/s5fxp.h and float_model.hpp");
 
@@ -1417,20 +1439,24 @@ int fq_plan(const s5fxp_float_fq_site *fq, int n_layers, FqPlan &plan)
     return S5FXP_OK;
 }
 
-// the one forward of the three entries: hist == nullptr launches exactly the kernels without the histogram, and fq == nullptr
-// or all off exactly those without fake quantisation (the two are never given together)
-int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats, unsigned long long *hist,
-                  const s5fxp_float_fq_site *fq, float *trace, void *workspace, size_t workspace_bytes, void *stream)
+// The one forward of the five entries, rectangular (B sequences of L rows) or, with CLIPS, B clips padded to L rows of which
+// lens[e] are real (no trace planes).  hist == nullptr launches exactly the kernels without the histogram, and
+// fq == nullptr or all off exactly those without fake quantisation (the two are never given together).
+template <bool CLIPS>
+int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, const int32_t *lens, float *y, float *stats,
+                  unsigned long long *hist, const s5fxp_float_fq_site *fq, float *trace, void *workspace, size_t workspace_bytes,
+                  void *stream)
 {
-    if (!m || !x || !y || !workspace || B < 1 || L < 1) return S5FXP_EBADARG;
+    if (!m || !x || !y || (CLIPS && !lens) || !workspace || B < 1 || L < 1) return S5FXP_EBADARG;
     if (reinterpret_cast<uintptr_t>(hist) % sizeof(unsigned long long)) return S5FXP_EBADARG;
     FqPlan qp;
     if (fq_plan(fq, m->n_layers, qp)) return S5FXP_EBADARG;
-    const long long N = (long long)B * L;
-    const long long tiles = (N + FM_FT - 1) / FM_FT;
-    const unsigned grid = (unsigned)(tiles < FM_GRID_CAP ? tiles : FM_GRID_CAP);
-    if (hist && !fm_hist_rows_ok(tiles, grid)) return S5FXP_EBADARG; // a 32-bit LDS counter could wrap
+    const FmTiling t = fm_tiling(B, L, CLIPS, lens);
+    if (hist && !fm_hist_rows_ok(t.tiles, t.grid)) return S5FXP_EBADARG; // a 32-bit LDS counter could wrap
     if (workspace_bytes < s5fxp_float_workspace_bytes(m, B, L, trace != nullptr)) return S5FXP_EWORKSPACE;
+    const int64_t scan_grid = (int64_t)B * ((m->P + ASSOC_PT - 1) / ASSOC_PT); // of the clip scan
+    if (CLIPS && scan_grid > 0x7fffffffll) return S5FXP_EBADARG;
+    const long long N = t.N;
     const size_t NH = (size_t)N * m->H, NP2 = (size_t)N * 2 * m->P;
     hipStream_t st = S(stream);
     unsigned *obs = reinterpret_cast<unsigned *>(stats);
@@ -1441,9 +1467,9 @@ int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, floa
 
     float *h = hbuf[0];
     FEncArgs ea{x, m->enc_w, m->enc_b, h, obs, N};
-    if (qp.any) S5_DISPATCH_DS(m->DS, S5_K_FENC_Q, grid, st, ea, qp.enc());
-    else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FENC_H, grid, st, ea, hist);
-    else S5_DISPATCH_DS(m->DS, S5_K_FENC, grid, st, ea);
+    if (qp.any) fm_launch<CLIPS>(t, st, FM_K(k_fenc_fq, k_fenc_clips_fq), ea, qp.enc());
+    else if (hist) fm_launch<CLIPS>(t, st, FM_K(k_fenc_hist, k_fenc_clips_hist), ea, hist);
+    else fm_launch<CLIPS>(t, st, FM_K(k_fenc, k_fenc_clips), ea);
     if ((rc = launch_rc())) return rc;
     for (int i = 0; i < m->n_layers; ++i) {
         const s5fxp_float_model::Layer &l = m->layers[i];
@@ -1453,125 +1479,41 @@ int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, floa
         unsigned *lo = obs ? obs + 2 + 10 * i : nullptr;
         unsigned long long *lh = hist ? hist + (size_t)(2 + 10 * i) * FM_HIST_BINS : nullptr;
         FBprojArgs ba{h, l.nm, l.bcat, bu, tr, lo, N};
-        if (qp.any && trace) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_TQ, grid, st, ba, qp.bproj(i));
-        else if (qp.any) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_Q, grid, st, ba, qp.bproj(i));
-        else if (hist && trace) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_TH, grid, st, ba, lh);
-        else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_H, grid, st, ba, lh);
-        else if (trace) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_T, grid, st, ba);
-        else S5_DISPATCH_DS(m->DS, S5_K_FBPROJ, grid, st, ba);
+        if (qp.any) fm_launch<CLIPS>(t, st, FM_K_TRACE(k_fbproj_fq, k_fbproj_clips_fq), ba, qp.bproj(i));
+        else if (hist) fm_launch<CLIPS>(t, st, FM_K_TRACE(k_fbproj_hist, k_fbproj_clips_hist), ba, lh);
+        else fm_launch<CLIPS>(t, st, FM_K_TRACE(k_fbproj, k_fbproj_clips), ba);
         if ((rc = launch_rc())) return rc;
-        if ((rc = s5fxp_assoc_scan_c64(l.lam, bu, xs, nullptr, nullptr, B, L, m->P, 0, stream))) return rc;
+        if constexpr (CLIPS) {
+            ScanAssocClipsArgs sa{reinterpret_cast<const float2 *>(l.lam), reinterpret_cast<const float2 *>(bu),
+                                  reinterpret_cast<float2 *>(xs), lens, B, L, m->P};
+            hipLaunchKernelGGL(k_scan_assoc_c64_clips, dim3((unsigned)scan_grid), dim3(64 * ASSOC_WAVES), 0, st, sa);
+            rc = launch_rc();
+        } else {
+            rc = s5fxp_assoc_scan_c64(l.lam, bu, xs, nullptr, nullptr, B, L, m->P, 0, stream);
+        }
+        if (rc) return rc;
         FGateArgs ga{xs, h, l.nm, l.ccat, l.D, l.w2, l.b2, hout, tr ? tr + NH : nullptr, tr ? tr + 2 * NH : nullptr,
                      tr ? tr + 3 * NH : nullptr, lo ? lo + 3 : nullptr, N};
         unsigned long long *gh = lh ? lh + 3 * FM_HIST_BINS : nullptr;
-        if (qp.any && trace) S5_DISPATCH_DS(m->DS, S5_K_FGATE_TQ, grid, st, ga, qp.gate(i));
-        else if (qp.any) S5_DISPATCH_DS(m->DS, S5_K_FGATE_Q, grid, st, ga, qp.gate(i));
-        else if (hist && trace) S5_DISPATCH_DS(m->DS, S5_K_FGATE_TH, grid, st, ga, gh);
-        else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FGATE_H, grid, st, ga, gh);
-        else if (trace) S5_DISPATCH_DS(m->DS, S5_K_FGATE_T, grid, st, ga);
-        else S5_DISPATCH_DS(m->DS, S5_K_FGATE, grid, st, ga);
+        if (qp.any) fm_launch<CLIPS>(t, st, FM_K_TRACE(k_fgate_fq, k_fgate_clips_fq), ga, qp.gate(i));
+        else if (hist) fm_launch<CLIPS>(t, st, FM_K_TRACE(k_fgate_hist, k_fgate_clips_hist), ga, gh);
+        else fm_launch<CLIPS>(t, st, FM_K_TRACE(k_fgate, k_fgate_clips), ga);
         if ((rc = launch_rc())) return rc;
         h = hout;
     }
     FDecArgs da{h, m->dec_w, m->dec_b, y, obs ? obs + 2 + 10 * m->n_layers : nullptr, N};
-    if (qp.any) S5_DISPATCH_DS(m->DS, S5_K_FDEC_Q, grid, st, da, qp.dec());
-    else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FDEC_H, grid, st, da, hist + (size_t)(2 + 10 * m->n_layers) * FM_HIST_BINS);
-    else S5_DISPATCH_DS(m->DS, S5_K_FDEC, grid, st, da);
+    unsigned long long *dh = hist ? hist + (size_t)(2 + 10 * m->n_layers) * FM_HIST_BINS : nullptr;
+    if (qp.any) fm_launch<CLIPS>(t, st, FM_K(k_fdec_fq, k_fdec_clips_fq), da, qp.dec());
+    else if (hist) fm_launch<CLIPS>(t, st, FM_K(k_fdec_hist, k_fdec_clips_hist), da, dh);
+    else fm_launch<CLIPS>(t, st, FM_K(k_fdec, k_fdec_clips), da);
     return launch_rc();
 }
-
-#define S5_K_FENC_C(ds) k_fenc_clips<ds>
-#define S5_K_FDEC_C(ds) k_fdec_clips<ds>
-#define S5_K_FBPROJ_C(ds) k_fbproj_clips<ds, false>
-#define S5_K_FGATE_C(ds) k_fgate_clips<ds, false>
-#define S5_K_FENC_CH(ds) k_fenc_clips_hist<ds>
-#define S5_K_FDEC_CH(ds) k_fdec_clips_hist<ds>
-#define S5_K_FBPROJ_CH(ds) k_fbproj_clips_hist<ds, false>
-#define S5_K_FGATE_CH(ds) k_fgate_clips_hist<ds, false>
-#define S5_K_FENC_CQ(ds) k_fenc_clips_fq<ds>
-#define S5_K_FDEC_CQ(ds) k_fdec_clips_fq<ds>
-#define S5_K_FBPROJ_CQ(ds) k_fbproj_clips_fq<ds, false>
-#define S5_K_FGATE_CQ(ds) k_fgate_clips_fq<ds, false>
-
-// the clip forward: the same eleven-kernel chain over tiles that belong to one clip each; no trace planes
-int float_forward_clips(const s5fxp_float_model *m, const float *x, int n, int Lmax, const int32_t *lens, float *y, float *stats,
-                        unsigned long long *hist, const s5fxp_float_fq_site *fq, void *workspace, size_t workspace_bytes,
-                        void *stream)
-{
-    if (!m || !x || !y || !lens || !workspace || n < 1 || Lmax < 1) return S5FXP_EBADARG;
-    if (reinterpret_cast<uintptr_t>(hist) % sizeof(unsigned long long)) return S5FXP_EBADARG;
-    FqPlan qp;
-    if (fq_plan(fq, m->n_layers, qp)) return S5FXP_EBADARG;
-    const int tpc = (int)(((long long)Lmax + FM_FT - 1) / FM_FT);
-    const long long N = (long long)n * Lmax, tiles = (long long)n * tpc;
-    unsigned grid = (unsigned)(tiles < FM_GRID_CAP ? tiles : FM_GRID_CAP);
-    // A stride that shares a factor with tpc ties a workgroup to few tile positions: at 512 and tpc = 16 it would see the same
-    // position of every clip it visits, the workgroups of the early positions all the work and those of the late ones next to
-    // none.  A stride coprime to tpc walks every workgroup through all positions.
-    if (tiles > grid)
-        while (std::gcd(grid, (unsigned)tpc) != 1) --grid;
-    if (hist && !fm_hist_rows_ok(tiles, grid)) return S5FXP_EBADARG; // a 32-bit LDS counter could wrap
-    if (workspace_bytes < s5fxp_float_workspace_bytes(m, n, Lmax, 0)) return S5FXP_EWORKSPACE;
-    const int64_t scan_grid = (int64_t)n * ((m->P + ASSOC_PT - 1) / ASSOC_PT);
-    if (scan_grid > 0x7fffffffll) return S5FXP_EBADARG;
-    const size_t NH = (size_t)N * m->H, NP2 = (size_t)N * 2 * m->P;
-    hipStream_t st = S(stream);
-    unsigned *obs = reinterpret_cast<unsigned *>(stats);
-    float *ws = static_cast<float *>(workspace);
-    float *hbuf[2] = {ws, ws + NH};
-    float *bu = ws + 2 * NH, *xs = bu + NP2;
-    const FClipMap cm{lens, Lmax, tpc, tiles};
-    int rc;
-
-    float *h = hbuf[0];
-    FEncArgs ea{x, m->enc_w, m->enc_b, h, obs, N};
-    if (qp.any) S5_DISPATCH_DS(m->DS, S5_K_FENC_CQ, grid, st, ea, cm, qp.enc());
-    else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FENC_CH, grid, st, ea, cm, hist);
-    else S5_DISPATCH_DS(m->DS, S5_K_FENC_C, grid, st, ea, cm);
-    if ((rc = launch_rc())) return rc;
-    for (int i = 0; i < m->n_layers; ++i) {
-        const s5fxp_float_model::Layer &l = m->layers[i];
-        float *hout = hbuf[(i + 1) & 1];
-        unsigned *lo = obs ? obs + 2 + 10 * i : nullptr;
-        unsigned long long *lh = hist ? hist + (size_t)(2 + 10 * i) * FM_HIST_BINS : nullptr;
-        FBprojArgs ba{h, l.nm, l.bcat, bu, nullptr, lo, N};
-        if (qp.any) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_CQ, grid, st, ba, cm, qp.bproj(i));
-        else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_CH, grid, st, ba, cm, lh);
-        else S5_DISPATCH_DS(m->DS, S5_K_FBPROJ_C, grid, st, ba, cm);
-        if ((rc = launch_rc())) return rc;
-        ScanAssocClipsArgs sa{reinterpret_cast<const float2 *>(l.lam), reinterpret_cast<const float2 *>(bu),
-                              reinterpret_cast<float2 *>(xs), lens, n, Lmax, m->P};
-        hipLaunchKernelGGL(k_scan_assoc_c64_clips, dim3((unsigned)scan_grid), dim3(64 * ASSOC_WAVES), 0, st, sa);
-        if ((rc = launch_rc())) return rc;
-        FGateArgs ga{xs, h, l.nm, l.ccat, l.D, l.w2, l.b2, hout, nullptr, nullptr, nullptr, lo ? lo + 3 : nullptr, N};
-        if (qp.any) S5_DISPATCH_DS(m->DS, S5_K_FGATE_CQ, grid, st, ga, cm, qp.gate(i));
-        else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FGATE_CH, grid, st, ga, cm, lh + 3 * FM_HIST_BINS);
-        else S5_DISPATCH_DS(m->DS, S5_K_FGATE_C, grid, st, ga, cm);
-        if ((rc = launch_rc())) return rc;
-        h = hout;
-    }
-    FDecArgs da{h, m->dec_w, m->dec_b, y, obs ? obs + 2 + 10 * m->n_layers : nullptr, N};
-    if (qp.any) S5_DISPATCH_DS(m->DS, S5_K_FDEC_CQ, grid, st, da, cm, qp.dec());
-    else if (hist) S5_DISPATCH_DS(m->DS, S5_K_FDEC_CH, grid, st, da, cm, hist + (size_t)(2 + 10 * m->n_layers) * FM_HIST_BINS);
-    else S5_DISPATCH_DS(m->DS, S5_K_FDEC_C, grid, st, da, cm);
-    return launch_rc();
-}
+#undef FM_AT_DS
+#undef FM_RECT_OR_CLIP
+#undef FM_K
+#undef FM_K_TRACE
 
 } // namespace
-
-extern "C" int s5fxp_float_model_clips(const s5fxp_float_model *m, const float *x, int n, int Lmax, const int32_t *lens, float *y,
-                                       float *stats, unsigned long long *hist, void *workspace, size_t workspace_bytes,
-                                       void *stream)
-{
-    return float_forward_clips(m, x, n, Lmax, lens, y, stats, hist, nullptr, workspace, workspace_bytes, stream);
-}
-
-extern "C" int s5fxp_float_model_clips_fq(const s5fxp_float_model *m, const float *x, int n, int Lmax, const int32_t *lens, float *y,
-                                          float *stats, const s5fxp_float_fq_site *fq, void *workspace, size_t workspace_bytes,
-                                          void *stream)
-{
-    return float_forward_clips(m, x, n, Lmax, lens, y, stats, nullptr, fq, workspace, workspace_bytes, stream);
-}
 
 extern "C" size_t s5fxp_float_model_blob_bytes(const s5fxp_float_model_desc *desc)
 {
@@ -1641,21 +1583,35 @@ extern "C" size_t s5fxp_float_trace_bytes(const s5fxp_float_model *m, int B, int
 extern "C" int s5fxp_float_model_forward(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats,
                                          float *trace, void *workspace, size_t workspace_bytes, void *stream)
 {
-    return float_forward(m, x, B, L, y, stats, nullptr, nullptr, trace, workspace, workspace_bytes, stream);
+    return float_forward<false>(m, x, B, L, nullptr, y, stats, nullptr, nullptr, trace, workspace, workspace_bytes, stream);
 }
 
 extern "C" int s5fxp_float_model_forward_hist(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats,
                                               unsigned long long *hist, float *trace, void *workspace, size_t workspace_bytes,
                                               void *stream)
 {
-    return float_forward(m, x, B, L, y, stats, hist, nullptr, trace, workspace, workspace_bytes, stream);
+    return float_forward<false>(m, x, B, L, nullptr, y, stats, hist, nullptr, trace, workspace, workspace_bytes, stream);
 }
 
 extern "C" int s5fxp_float_model_forward_fq(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats,
                                             const s5fxp_float_fq_site *fq, float *trace, void *workspace, size_t workspace_bytes,
                                             void *stream)
 {
-    return float_forward(m, x, B, L, y, stats, nullptr, fq, trace, workspace, workspace_bytes, stream);
+    return float_forward<false>(m, x, B, L, nullptr, y, stats, nullptr, fq, trace, workspace, workspace_bytes, stream);
+}
+
+extern "C" int s5fxp_float_model_clips(const s5fxp_float_model *m, const float *x, int n, int Lmax, const int32_t *lens, float *y,
+                                       float *stats, unsigned long long *hist, void *workspace, size_t workspace_bytes,
+                                       void *stream)
+{
+    return float_forward<true>(m, x, n, Lmax, lens, y, stats, hist, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int s5fxp_float_model_clips_fq(const s5fxp_float_model *m, const float *x, int n, int Lmax, const int32_t *lens, float *y,
+                                          float *stats, const s5fxp_float_fq_site *fq, void *workspace, size_t workspace_bytes,
+                                          void *stream)
+{
+    return float_forward<true>(m, x, n, Lmax, lens, y, stats, nullptr, fq, nullptr, workspace, workspace_bytes, stream);
 }
 
 #ifdef S5_PHASE_PROF

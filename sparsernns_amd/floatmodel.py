@@ -200,6 +200,50 @@ class FloatEngine:
             ws = self._ws[trace] = torch.empty(n, dtype=torch.float32, device=self.device)
         return ws
 
+    def _device_forward(self, clips: bool, x, lens, stats_dev, hist_dev, out, trace: bool, fq):
+        """The one device forward behind ``forward_device`` and ``forward_clips_device``: the checks of every argument, the
+        buffers and the C entry that serves the form -> (y, trace buffer or None, workspace)."""
+        if not self.on_device:
+            raise RuntimeError(f"FloatEngine.{'forward_clips_device' if clips else 'forward_device'} needs the kernels (on_device is False)")
+        fq = self._fq_arg(fq, hist_dev)
+        if x.dim() != 3 or x.shape[2] != self.d_in or x.dtype != torch.float32 or x.device != self.device:
+            raise ValueError(f"x must be float32 ({'n, Lmax' if clips else 'B, L'}, {self.d_in}) on {self.device}, "
+                             f"got {x.dtype} {tuple(x.shape)} on {x.device}")
+        B, L = int(x.shape[0]), int(x.shape[1])
+        if clips and (not isinstance(lens, torch.Tensor) or lens.dtype != torch.int32 or tuple(lens.shape) != (B,)
+                      or lens.device != self.device):
+            raise ValueError(f"lens must be an int32 ({B},) tensor on {self.device}")
+        if stats_dev is not None and (stats_dev.dtype != torch.float32 or stats_dev.numel() != len(self.keys)
+                                      or stats_dev.device != self.device or not stats_dev.is_contiguous()):
+            raise ValueError(f"stats must be {len(self.keys)} contiguous float32 on {self.device}")
+        if hist_dev is not None and (hist_dev.dtype != torch.int64 or hist_dev.numel() != len(self.keys) * HIST_BINS
+                                     or hist_dev.device != self.device or not hist_dev.is_contiguous()):
+            raise ValueError(f"hist must be {len(self.keys)} x {HIST_BINS} contiguous int64 on {self.device}")
+        shape = (B, L, self.d_out)
+        if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device
+                                or not out.is_contiguous()):
+            raise ValueError(f"out must be contiguous float32 {shape} on {self.device}")
+        x = x.contiguous()
+        lens = lens.contiguous() if clips else None  # both held until the launches are enqueued
+        y = out if out is not None else torch.empty(shape, dtype=torch.float32, device=self.device)
+        ws = self._workspace(B, L, trace)
+        tr = torch.empty(lib.s5fxp_float_trace_bytes(self._h, B, L) // 4, dtype=torch.float32, device=self.device) if trace else None
+        h, xp, yp, trp = self._h, x.data_ptr(), y.data_ptr(), None if tr is None else tr.data_ptr()
+        st, hp = None if stats_dev is None else stats_dev.data_ptr(), None if hist_dev is None else hist_dev.data_ptr()
+        with torch.cuda.device(self.device):
+            tail = (ws.data_ptr(), ws.numel() * 4, torch.cuda.current_stream().cuda_stream)
+            if clips and fq is not None:
+                check(lib.s5fxp_float_model_clips_fq(h, xp, B, L, lens.data_ptr(), yp, st, fq.ctypes.data, *tail), "s5fxp_float_model_clips_fq")
+            elif clips:
+                check(lib.s5fxp_float_model_clips(h, xp, B, L, lens.data_ptr(), yp, st, hp, *tail), "s5fxp_float_model_clips")
+            elif fq is not None:
+                check(lib.s5fxp_float_model_forward_fq(h, xp, B, L, yp, st, fq.ctypes.data, trp, *tail), "s5fxp_float_model_forward_fq")
+            elif hist_dev is not None:
+                check(lib.s5fxp_float_model_forward_hist(h, xp, B, L, yp, st, hp, trp, *tail), "s5fxp_float_model_forward_hist")
+            else:
+                check(lib.s5fxp_float_model_forward(h, xp, B, L, yp, st, trp, *tail), "s5fxp_float_model_forward")
+        return y, tr, ws
+
     def forward_device(self, x: torch.Tensor, stats_dev: Optional[torch.Tensor] = None, trace: bool = False,
                        hist_dev: Optional[torch.Tensor] = None, fq=None):
         """x (B,L,257) float32 on the device -> y (B,L,257); ``stats_dev`` (``new_stats``) is raised in place, ``hist_dev``
@@ -207,37 +251,7 @@ class FloatEngine:
         as flat tensors.  ``fq`` (``fq_spec``) fake-quantises the observed tensors whose site is on, each right
         after it entered its observer (``s5fxp_float_model_forward_fq``); not together with ``hist_dev``.  Stream-ordered, no
         sync."""
-        if not self.on_device:
-            raise RuntimeError("FloatEngine.forward_device needs the kernels (on_device is False)")
-        fq = self._fq_arg(fq, hist_dev)
-        if x.dim() != 3 or x.shape[2] != self.d_in or x.dtype != torch.float32 or x.device != self.device:
-            raise ValueError(f"x must be float32 (B, L, {self.d_in}) on {self.device}, got {x.dtype} {tuple(x.shape)} on {x.device}")
-        if stats_dev is not None and (stats_dev.dtype != torch.float32 or stats_dev.numel() != len(self.keys)
-                                      or stats_dev.device != self.device or not stats_dev.is_contiguous()):
-            raise ValueError(f"stats must be {len(self.keys)} contiguous float32 on {self.device}")
-        if hist_dev is not None and (hist_dev.dtype != torch.int64 or hist_dev.numel() != len(self.keys) * HIST_BINS
-                                     or hist_dev.device != self.device or not hist_dev.is_contiguous()):
-            raise ValueError(f"hist must be {len(self.keys)} x {HIST_BINS} contiguous int64 on {self.device}")
-        x = x.contiguous()
-        B, L = int(x.shape[0]), int(x.shape[1])
-        y = torch.empty(B, L, self.d_out, dtype=torch.float32, device=self.device)
-        ws = self._workspace(B, L, trace)
-        tr = torch.empty(lib.s5fxp_float_trace_bytes(self._h, B, L) // 4, dtype=torch.float32, device=self.device) if trace else None
-        st = None if stats_dev is None else stats_dev.data_ptr()
-        with torch.cuda.device(self.device):
-            if fq is not None:
-                check(lib.s5fxp_float_model_forward_fq(self._h, x.data_ptr(), B, L, y.data_ptr(), st, fq.ctypes.data,
-                                                       None if tr is None else tr.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                                       torch.cuda.current_stream().cuda_stream), "s5fxp_float_model_forward_fq")
-            elif hist_dev is None:
-                check(lib.s5fxp_float_model_forward(self._h, x.data_ptr(), B, L, y.data_ptr(), st,
-                                                    None if tr is None else tr.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                                    torch.cuda.current_stream().cuda_stream), "s5fxp_float_model_forward")
-            else:
-                check(lib.s5fxp_float_model_forward_hist(self._h, x.data_ptr(), B, L, y.data_ptr(), st, hist_dev.data_ptr(),
-                                                         None if tr is None else tr.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                                         torch.cuda.current_stream().cuda_stream),
-                      "s5fxp_float_model_forward_hist")
+        y, tr, ws = self._device_forward(False, x, None, stats_dev, hist_dev, None, trace, fq)
         return (y, tr, ws) if trace else y
 
     def forward_clips_device(self, x: torch.Tensor, lens, stats_dev: Optional[torch.Tensor] = None,
@@ -248,39 +262,16 @@ class FloatEngine:
         bit what ``forward_device(x[e:e+1, :len_e], ...)`` gives clip after clip: padding rows are never read, never written and
         never observed.  ``out``: the tensor to write into; otherwise y is fresh and its padding unspecified.  ``fq`` as in
         ``forward_device`` (``s5fxp_float_model_clips_fq``).  Stream-ordered, no sync."""
-        if not self.on_device:
-            raise RuntimeError("FloatEngine.forward_clips_device needs the kernels (on_device is False)")
-        fq = self._fq_arg(fq, hist_dev)
-        if x.dim() != 3 or x.shape[2] != self.d_in or x.dtype != torch.float32 or x.device != self.device:
-            raise ValueError(f"x must be float32 (n, Lmax, {self.d_in}) on {self.device}, got {x.dtype} {tuple(x.shape)} on {x.device}")
-        n, Lmax = int(x.shape[0]), int(x.shape[1])
-        if not isinstance(lens, torch.Tensor) or lens.dtype != torch.int32 or tuple(lens.shape) != (n,) or lens.device != self.device:
-            raise ValueError(f"lens must be an int32 ({n},) tensor on {self.device}")
-        if stats_dev is not None and (stats_dev.dtype != torch.float32 or stats_dev.numel() != len(self.keys)
-                                      or stats_dev.device != self.device or not stats_dev.is_contiguous()):
-            raise ValueError(f"stats must be {len(self.keys)} contiguous float32 on {self.device}")
-        if hist_dev is not None and (hist_dev.dtype != torch.int64 or hist_dev.numel() != len(self.keys) * HIST_BINS
-                                     or hist_dev.device != self.device or not hist_dev.is_contiguous()):
-            raise ValueError(f"hist must be {len(self.keys)} x {HIST_BINS} contiguous int64 on {self.device}")
-        shape = (n, Lmax, self.d_out)
-        if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device
-                                or not out.is_contiguous()):
-            raise ValueError(f"out must be contiguous float32 {shape} on {self.device}")
-        x, lens = x.contiguous(), lens.contiguous()
-        y = out if out is not None else torch.empty(shape, dtype=torch.float32, device=self.device)
-        ws = self._workspace(n, Lmax, False)
-        with torch.cuda.device(self.device):
-            if fq is not None:
-                check(lib.s5fxp_float_model_clips_fq(self._h, x.data_ptr(), n, Lmax, lens.data_ptr(), y.data_ptr(),
-                                                     None if stats_dev is None else stats_dev.data_ptr(), fq.ctypes.data,
-                                                     ws.data_ptr(), ws.numel() * 4, torch.cuda.current_stream().cuda_stream),
-                      "s5fxp_float_model_clips_fq")
-                return y
-            check(lib.s5fxp_float_model_clips(self._h, x.data_ptr(), n, Lmax, lens.data_ptr(), y.data_ptr(),
-                                              None if stats_dev is None else stats_dev.data_ptr(),
-                                              None if hist_dev is None else hist_dev.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                              torch.cuda.current_stream().cuda_stream), "s5fxp_float_model_clips")
-        return y
+        return self._device_forward(True, x, lens, stats_dev, hist_dev, out, False, fq)[0]
+
+    def _merge(self, st, hd, stats: Optional[dict], hist: Optional[dict]) -> None:
+        """One forward's device arrays into the caller's dicts: ``stats`` by maximum, ``hist`` by addition."""
+        if hist is not None:
+            for k, row in self.hist_dict(hd).items():
+                hist[k] = hist.get(k, 0) + row
+        if stats is not None:
+            for k, v in self.stats_dict(st).items():
+                stats[k] = max(stats.get(k, 0.0), v)
 
     def forward_clips(self, clips, stats: Optional[dict] = None, hist: Optional[dict] = None, fq=None) -> list:
         """A list of (len_e, 257) float32 clips, NumPy arrays or tensors -> the list of the model's outputs, each of its clip's
@@ -303,12 +294,7 @@ class FloatEngine:
         st = self.new_stats() if stats is not None else None
         hd = self.new_hist() if hist is not None else None
         y = self.forward_clips_device(x, torch.tensor(ls, dtype=torch.int32, device=self.device), st, hd, fq=fq)
-        if hist is not None:
-            for k, row in self.hist_dict(hd).items():
-                hist[k] = hist.get(k, 0) + row
-        if stats is not None:
-            for k, v in self.stats_dict(st).items():
-                stats[k] = max(stats.get(k, 0.0), v)
+        self._merge(st, hd, stats, hist)
         return [y[e, :ls[e]].to(c.device) if isinstance(c, torch.Tensor) else y[e, :ls[e]].cpu().numpy() for e, c in enumerate(clips)]
 
     def forward_traced(self, x, hist: bool = False, fq=None) -> dict:
@@ -363,12 +349,7 @@ class FloatEngine:
             st = self.new_stats() if stats is not None else None
             hd = self.new_hist() if hist is not None else None
             y = self.forward_device(xd, st, hist_dev=hd, fq=fq)
-        if hist is not None:
-            for k, row in self.hist_dict(hd).items():
-                hist[k] = hist.get(k, 0) + row
-        if stats is not None:
-            for k, v in self.stats_dict(st).items():
-                stats[k] = max(stats.get(k, 0.0), v)
+        self._merge(st, hd, stats, hist)
         return y.to(x.device) if as_tensor else y.cpu().numpy()
 
     def _fill_activations(self, t: dict, activations: dict) -> None:
@@ -395,6 +376,15 @@ def _clip_pair(item):
     return None
 
 
+def _real_clips(x, lens) -> list:
+    """The host-side reading of an (x, lens) pair: the clips' real frames, x[e, :clamp(lens[e], 0, Lmax)], empty clips dropped."""
+    Lmax = int(x.shape[1])
+    lens = [min(max(int(v), 0), Lmax) for v in torch.as_tensor(lens).tolist()]
+    if len(lens) != int(x.shape[0]):
+        raise ValueError(f"{int(x.shape[0])} clips but {len(lens)} lengths")
+    return [x[e, :n] for e, n in enumerate(lens) if n]
+
+
 def _observe(eng: "FloatEngine", item, st, hd, stats: Optional[dict], hist: Optional[dict]) -> None:
     """One calibration item through the engine: a pair takes the clip entry, so that its padding is never observed; a plain
     (B,L,257) batch the rectangular one.  Device arrays ``st`` / ``hd`` on the device, the dicts off it."""
@@ -408,11 +398,17 @@ def _observe(eng: "FloatEngine", item, st, hd, stats: Optional[dict], hist: Opti
     elif pair is None:
         eng.forward(item, stats=stats, hist=hist)
     else:
-        x, Lmax = pair[0], int(pair[0].shape[1])
-        lens = [min(max(int(v), 0), Lmax) for v in torch.as_tensor(pair[1]).tolist()]
-        if len(lens) != int(x.shape[0]):
-            raise ValueError(f"{int(x.shape[0])} clips but {len(lens)} lengths")
-        eng.forward_clips([x[e, :n] for e, n in enumerate(lens) if n], stats=stats, hist=hist)
+        eng.forward_clips(_real_clips(*pair), stats=stats, hist=hist)
+
+
+def _derive_qconfig(modeldict: dict, absmax: dict, n_layers: int, quantization: str, state_headroom_bits: int) -> dict:
+    """The fixed-point configuration from the observers, as ``synth.make_model`` derives it after its dry run."""
+    qc = synth.derive_qconfig(modeldict, absmax, n_layers, synth.PRECISIONS[quantization])
+    for k in ("x_re", "x_im"):
+        qc["blocks"]["ssm"]["activations"][k]["exp"] -= state_headroom_bits
+    synth.cap_result_exponents(qc)
+    synth._assert_exps_nonnegative(qc)
+    return qc
 
 
 def calibrate(modeldict: dict, batches: Iterable, n_layers: int, quantization: str = "w8a16",
@@ -434,12 +430,7 @@ def calibrate(modeldict: dict, batches: Iterable, n_layers: int, quantization: s
             _observe(eng, x, None, None, stats, None)
     if not stats:
         raise ValueError("calibrate needs at least one batch")
-    qc = synth.derive_qconfig(modeldict, stats, n_layers, synth.PRECISIONS[quantization])
-    for k in ("x_re", "x_im"):
-        qc["blocks"]["ssm"]["activations"][k]["exp"] -= state_headroom_bits
-    synth.cap_result_exponents(qc)
-    synth._assert_exps_nonnegative(qc)
-    return stats, qc
+    return stats, _derive_qconfig(modeldict, stats, n_layers, quantization, state_headroom_bits)
 
 
 def clip_absmax(stats: dict, hist: dict, clip_fraction: float, keep=("x_re", "x_im")) -> dict:
@@ -490,12 +481,7 @@ def calibrate_clipped(modeldict: dict, batches: Iterable, n_layers: int, clip_fr
     if not stats:
         raise ValueError("calibrate_clipped needs at least one batch")
     effective = clip_absmax(stats, hist, clip_fraction, keep)
-    qc = synth.derive_qconfig(modeldict, effective, n_layers, synth.PRECISIONS[quantization])
-    for k in ("x_re", "x_im"):
-        qc["blocks"]["ssm"]["activations"][k]["exp"] -= state_headroom_bits
-    synth.cap_result_exponents(qc)
-    synth._assert_exps_nonnegative(qc)
-    return stats, hist, effective, qc
+    return stats, hist, effective, _derive_qconfig(modeldict, effective, n_layers, quantization, state_headroom_bits)
 
 
 def quantiser_of(key: str, fxp_qconfig: dict) -> Tuple[int, int]:
@@ -575,16 +561,13 @@ def _real_frames(eng: "FloatEngine", item, fq) -> torch.Tensor:
             return eng.forward_device(eng._to_device(item), fq=fq).double().flatten()
         xn = item.detach().cpu().numpy() if isinstance(item, torch.Tensor) else item
         return torch.from_numpy(eng.forward(np.asarray(xn, dtype=F32), fq=fq)).double().flatten()
-    x, Lmax = pair[0], int(pair[0].shape[1])
     if eng.on_device:
+        Lmax = int(pair[0].shape[1])
         lens = torch.as_tensor(pair[1]).to(device=eng.device, dtype=torch.int32)
-        y = eng.forward_clips_device(eng._to_device(x), lens, fq=fq)
+        y = eng.forward_clips_device(eng._to_device(pair[0]), lens, fq=fq)
         real = torch.arange(Lmax, device=eng.device)[None, :] < lens.clamp(0, Lmax)[:, None]
         return y[real].double().flatten()  # y's padding is unspecified: select, do not multiply
-    lens = [min(max(int(v), 0), Lmax) for v in torch.as_tensor(pair[1]).tolist()]
-    if len(lens) != int(x.shape[0]):
-        raise ValueError(f"{int(x.shape[0])} clips but {len(lens)} lengths")
-    ys = eng.forward_clips([x[e, :n] for e, n in enumerate(lens) if n], fq=fq)
+    ys = eng.forward_clips(_real_clips(*pair), fq=fq)
     return torch.cat([torch.as_tensor(y).double().flatten() for y in ys]) if ys else torch.zeros(0, dtype=torch.float64)
 
 

@@ -476,7 +476,7 @@ def test_all_sites_on_every_stage_between_the_quantised_ends_of_its_bound(dim, c
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dim", [0.25, 1.0])
+@pytest.mark.parametrize("dim", [0.25, 0.5, 0.75, 1.0])  # every DS: the only runs of the k_*_clips_fq kernels
 def test_clips_get_what_their_own_forward_gets(dim):
     import torch
 
