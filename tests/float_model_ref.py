@@ -26,10 +26,13 @@ def inv_std32(var):
     return (np.float32(1.0) / np.sqrt(var.astype(np.float32) + np.float32(1e-5))).astype(np.float32)
 
 
-def forward_f64(modeldict, x, n_layers, stats=None):
+def forward_f64(modeldict, x, n_layers, stats=None, planes=None):
+    """``planes``: a dict that receives every observed float64 tensor itself under its observer's key."""
     def obs(key, v):
         if stats is not None:
             stats[key] = max(stats.get(key, 0.0), float(np.abs(v).max()))
+        if planes is not None:
+            planes[key] = v
 
     enc = modeldict["encoder"]
     x = x.astype(F64)
@@ -79,6 +82,38 @@ def scan_f64(lam_bar, Bu):
         st = lam * st + Bu[:, t]
         xs[:, t] = st
     return xs
+
+
+def tree_scan(lam_bar, Bu, reverse=False):
+    """oracle.float_ssm.associative_scan (complex64), the oracle's restatement of the reference's own combination tree,
+    sequence by sequence on the same lambda and Bu.  Bu (B,L,P)."""
+    from oracle import float_ssm
+
+    A = np.broadcast_to(lam_bar.astype(np.complex64), Bu.shape[1:])
+    return np.stack([float_ssm.associative_scan((A, Bu[b].astype(np.complex64)), reverse=reverse)[1] for b in range(Bu.shape[0])])
+
+
+def per_state_errors(xs, ref):
+    """(max over b, t of |xs - ref|, max over b, t of |ref|), one value per state.  xs, ref (B,L,P)."""
+    return np.abs(xs - ref).max(axis=(0, 1)), np.abs(ref).max(axis=(0, 1))
+
+
+def per_state_scan(xs_dev, ref, tree, what):
+    """The per-state scan criterion: for every state p, with scale_p = max |ref[.., p]|,
+        max |xs_dev - ref|[.., p] <= 4 max |tree - ref|[.., p] + 1e-6 scale_p.
+    The measure is the reference's tree, not the code under test; the margin of 4 and the 1e-6 floor are what
+    test_float_scan.py grants the stand-alone scan globally.  A maximum over all states would let a slow state's magnitude
+    hide a fast state's error.  Returns the largest err_dev / err_tree over the states where the tree errs at all."""
+    err_dev, scale = per_state_errors(xs_dev, ref)
+    err_tree, _ = per_state_errors(tree, ref)
+    lim = 4 * err_tree + 1e-6 * scale
+    worst = float((err_dev / np.maximum(lim, 1e-300)).max())
+    some = err_tree > 0
+    ratio = float((err_dev[some] / err_tree[some]).max()) if some.any() else 0.0
+    print(f"{what}: per state worst err / limit {worst:.3f}, largest err_dev / err_tree {ratio:.3f}")
+    bad = np.flatnonzero(err_dev > lim)
+    assert bad.size == 0, (what, bad[:8].tolist(), err_dev[bad[:8]].tolist(), err_tree[bad[:8]].tolist(), scale[bad[:8]].tolist())
+    return ratio
 
 
 def max_rel_deviation(stats, ref):
@@ -144,3 +179,88 @@ def threshold_margin(absmax):
         f = math.log2(absmax / q) - 0.5
         out.append(abs(f - round(f)))
     return min(out)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the checks of one traced device forward, shared by test_float_model.py and test_float_contract.py
+# ----------------------------------------------------------------------------------------------------------------------
+def within(dev, ref, K, S, what):
+    err = np.abs(dev.astype(F64) - ref)
+    lim = bound(K, S)
+    worst = float((err / np.maximum(lim, 1e-300)).max())
+    print(f"{what}: max err {err.max():.3e}, worst err / bound {worst:.3f}")
+    assert (err <= lim).all(), (what, float(err.max()), worst)
+
+
+def check_stages(md, n_layers, x, t, global_scan=True):
+    """Every stage of the traced forward ``t`` (host copies of FloatEngine.forward_traced's planes) of model ``md`` on input
+    ``x`` against a float64 evaluation of that stage on the device's own float32 input planes: the chain bound per stage,
+    the sigmoid within 1e-6, the scan within 1e-5 max|x| (``global_scan``) and within the per-state criterion."""
+    enc = md["encoder"]
+    H = enc["encoder"]["kernel"].shape[1]
+    P = enc["layers_0"]["mixer"]["Lambda_re"].shape[0]
+    v, S = stage_dense(x, enc["encoder"]["kernel"], enc["encoder"]["bias"])
+    within(t["h_enc"], np.maximum(v, 0), 257, S, "encoder")
+    h = t["h_enc"]
+    for i in range(n_layers):
+        layer = enc[f"layers_{i}"]
+        lam_bar, B_bar, Cc = synth.zoh(layer["mixer"])
+        u, y, g_in, g, h_out = (t[f"l{i}.{k}"] for k in ("u", "y", "g_in", "g", "h_out"))
+        Bu, xs = t[f"l{i}.Bu"], t[f"l{i}.xs"]
+        v, S = stage_u(h, layer["norm"])
+        within(u, v, 0, S, f"l{i}.u")
+        (vr, Sr), (vi, Si) = stage_bu(u, B_bar)
+        within(Bu.real, vr, H, Sr, f"l{i}.Bu_re")
+        within(Bu.imag, vi, H, Si, f"l{i}.Bu_im")
+        ref = scan_f64(lam_bar, Bu)
+        err, scale = np.abs(xs - ref).max(), np.abs(ref).max()
+        print(f"l{i}.xs: max err {err:.3e} of max|x| {scale:.3e}")
+        if global_scan:
+            assert err <= 1e-5 * scale
+        per_state_scan(xs, ref, tree_scan(lam_bar, Bu), f"l{i}.xs")
+        v, S = stage_y(xs, u, Cc, layer["mixer"]["D"])
+        within(y, v, P, S, f"l{i}.y")
+        v, S = stage_dense(np.maximum(y, 0), layer["out2"]["kernel"], layer["out2"]["bias"])
+        within(g_in, v, H, S, f"l{i}.g_in")
+        gerr = np.abs(g - sigmoid64(g_in)).max()
+        print(f"l{i}.g: max err {gerr:.3e}")
+        assert gerr <= 1e-6
+        v, S = stage_hout(y, g, h)
+        within(h_out, v, 0, S, f"l{i}.h_out")
+        h = h_out
+    v, S = stage_dense(h, md["decoder"]["kernel"], md["decoder"]["bias"])
+    within(t["out"], v, H, S, "decoder")
+
+
+def check_observers(md, n_layers, x, t):
+    """The observers of the traced forward ``t``: bit for bit the absmax of the device's own planes."""
+    from sparsernns_amd import floatmodel
+
+    want = {"encoder.inp": x, "decoder.inp": t[f"l{n_layers - 1}.h_out"], "decoder.out": t["out"]}
+    for i in range(n_layers):
+        x1 = np.maximum(t[f"l{i}.y"], 0)
+        want.update({f"l{i}.u": t[f"l{i}.u"], f"l{i}.Bu_re": t[f"l{i}.Bu"].real, f"l{i}.Bu_im": t[f"l{i}.Bu"].imag,
+                     f"l{i}.x_re": t[f"l{i}.xs"].real, f"l{i}.x_im": t[f"l{i}.xs"].imag, f"l{i}.y": t[f"l{i}.y"],
+                     f"l{i}.out2.inp": x1, f"l{i}.out2.out": t[f"l{i}.g_in"], f"l{i}.gate.l": x1, f"l{i}.gate.r": t[f"l{i}.g"]})
+    keys = floatmodel.stat_keys(n_layers)
+    assert len(keys) == len(t["stats"])
+    got = dict(zip(keys, t["stats"]))
+    for k, plane in want.items():
+        assert got[k].view(np.uint32) == np.abs(plane).max().astype(np.float32).view(np.uint32), k
+    # encoder.out is observed before the ReLU and the stored plane has it behind it: no device plane to take the absmax of.
+    # It must cover the stored plane and lie within the encoder's chain bound of the float64 stage's absmax.
+    v, S = stage_dense(x, md["encoder"]["encoder"]["kernel"], md["encoder"]["encoder"]["bias"])
+    assert set(got) == set(want) | {"encoder.out"} and got["encoder.out"] >= t["h_enc"].max()
+    assert abs(float(got["encoder.out"]) - np.abs(v).max()) <= bound(257, S).max()
+
+
+def check_hot_equals_traced(eng, x, t):
+    """The hot (non-trace) forward: output and observers bit for bit the traced ones; a NULL stats array leaves y unchanged."""
+    import torch
+
+    xd = torch.from_numpy(x).to(eng.device)
+    st = eng.new_stats()
+    y = eng.forward_device(xd, st)
+    assert np.array_equal(y.cpu().numpy().view(np.uint32), t["out"].view(np.uint32))
+    assert np.array_equal(st.cpu().numpy().view(np.uint32), t["stats"].view(np.uint32))
+    assert torch.equal(eng.forward_device(xd, None), y)

@@ -32,7 +32,9 @@ SETS = {
     "D": (448, _set_d()),            # 40 x 14 = 560 tiles on at most 512 workgroups
 }
 SEEDS = {"A": 41, "B": 42, "C": 43, "D": 44}
-GRID = [(0.25, "A"), (0.5, "A"), (0.75, "A"), (1.0, "A"), (0.25, "B"), (0.25, "C"), (0.25, "D")]
+GRID = [(0.25, "A"), (0.5, "A"), (0.75, "A"), (1.0, "A"), (0.25, "B"), (0.25, "C"), (0.25, "D"),
+        # workgroups that walk several tiles (D), and the scan's chunk carry (C), in the other instantiations of every kernel
+        (0.5, "D"), (0.75, "D"), (1.0, "D"), (1.0, "C")]
 IDS = [f"dim{d}-{s}" for d, s in GRID]
 CPU_LENS, CPU_LMAX = [1, 33, 70], 70
 P_CLIP = 1e-3

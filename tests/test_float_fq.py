@@ -25,6 +25,8 @@ DIMS_FOR = {(2, 70, 12): (0.25, 0.5, 0.75, 1.0), (1, 1, 13): (0.25,), (3, 33, 12
 STRIDE = (0.25, (5, 3300, 14))  # 516 tiles of 32 frames on a launch of at most 512 workgroups: a workgroup walks two tiles
 GRID = [(d, c) for c in CASES for d in DIMS_FOR[c]] + [STRIDE]
 IDS = [f"dim{d}-B{c[0]}L{c[1]}" for d, c in GRID]
+STRIDES_UP = [(d, STRIDE[1]) for d in (0.5, 0.75, 1.0)]  # the same walk in the other three instantiations of every kernel
+STRIDE_UP_IDS = [f"dim{d}-B{c[0]}L{c[1]}" for d, c in STRIDES_UP]
 LAYER_KEYS = ("u", "Bu_re", "Bu_im", "x_re", "x_im", "y", "out2.inp", "out2.out", "gate.l", "gate.r")
 PINNED_SHARE = 0.98  # of every site's elements, at the 8-bit recipes
 
@@ -275,14 +277,21 @@ def host_planes(t):
     return {k: v.cpu().numpy() for k, v in t.items()}
 
 
-@functools.lru_cache(maxsize=None)
-def plain(dim, case, recipe):
-    """One plain traced forward per (dim, case, recipe), shared and never modified; host copies of every plane."""
+def _plain(dim, case, recipe):
     _, _, dims = model(dim, recipe)
     x = make_x(dims, case, recipe)
     out = host_planes(engine(dim, recipe).forward_traced(x))
     out["x"] = x
     return out
+
+
+_plain_small = functools.lru_cache(maxsize=None)(_plain)
+_plain_stride = functools.lru_cache(maxsize=1)(_plain)  # up to 300 MB each: only the latest is kept
+
+
+def plain(dim, case, recipe):
+    """One plain traced forward per (dim, case, recipe), shared and never modified; host copies of every plane."""
+    return (_plain_stride if case == STRIDE[1] else _plain_small)(dim, case, recipe)
 
 
 def plane_order(n_layers):
@@ -291,7 +300,7 @@ def plane_order(n_layers):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dim,case", GRID, ids=IDS)
+@pytest.mark.parametrize("dim,case", GRID + STRIDES_UP, ids=IDS + STRIDE_UP_IDS)
 def test_no_spec_and_an_all_off_spec_are_the_plain_forward(dim, case):
     import torch
     from sparsernns_amd import floatmodel as F
@@ -418,6 +427,17 @@ def on_grid(plane, bits, exp, saturate, what):
 @pytest.mark.parametrize("recipe", RECIPES)
 @pytest.mark.parametrize("dim,case", GRID, ids=IDS)
 def test_all_sites_on_every_stage_between_the_quantised_ends_of_its_bound(dim, case, recipe):
+    check_all_sites_on(dim, case, recipe)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim,case", STRIDES_UP, ids=STRIDE_UP_IDS)
+def test_all_sites_on_where_workgroups_walk_two_tiles_at_the_other_dim_scales(dim, case):
+    """GRID holds the walk at dim_scale 0.25 only; one recipe there, since the walk does not depend on it."""
+    check_all_sites_on(dim, case, "w8a8")
+
+
+def check_all_sites_on(dim, case, recipe):
     from sparsernns_amd import floatmodel as F
 
     md, qc, dims = model(dim, recipe)

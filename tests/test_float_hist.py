@@ -2,7 +2,8 @@
 
 The reference of every test is ``floatmodel.exp_hist``, the NumPy statement of the histogram: bin clamp(E - 87, 0, 63) of the
 float32 exponent field.  On the device a row must equal ``exp_hist`` of the device's OWN plane, integer for integer; the
-calibration rule is checked on constructed histograms and against the host's configuration.
+calibration rule is checked on constructed histograms and against the host's configuration.  The shape at which workgroups
+accumulate over two tiles (STRIDES) runs at every dim_scale: each is a kernel instantiation of its own.
 """
 import ctypes as C
 import functools
@@ -18,7 +19,9 @@ CASES = [(1, 1, 13), (2, 70, 11), (3, 33, 12)]  # test_float_model.py's shapes a
 DIMS_FOR = {(1, 1, 13): (0.25, 0.5), (2, 70, 11): (0.25, 0.5, 0.75, 1.0), (3, 33, 12): (0.25, 0.5)}
 GRID = [(d, c) for c in CASES for d in DIMS_FOR[c]]
 IDS = [f"dim{d}-B{c[0]}L{c[1]}" for d, c in GRID]
-STRIDE = (0.25, (5, 3300, 14))  # 516 tiles of 32 frames on a launch of at most 512 workgroups
+STRIDE_CASE = (5, 3300, 14)  # 516 tiles of 32 frames on a launch of at most 512 workgroups: four workgroups walk two tiles
+STRIDES = [(d, STRIDE_CASE) for d in (0.25, 0.5, 0.75, 1.0)]  # every dim_scale is a kernel instantiation of its own
+STRIDE_IDS = [f"dim{d}-B{c[0]}L{c[1]}" for d, c in STRIDES]
 MARGIN = 2e-4
 P_CLIP = 1e-3
 
@@ -305,15 +308,22 @@ def engine(dim):
     return eng
 
 
-@functools.lru_cache(maxsize=None)
-def traced(dim, case):
-    """One traced forward with histograms per (dim, case), shared and never modified; host copies of every plane."""
+def _traced(dim, case):
     md, _, dims = model(dim)
     x = synth.make_input(case[0], case[1], dims["d_in"], seed=case[2])
     t = engine(dim).forward_traced(x, hist=True)
     out = {k: v.cpu().numpy() for k, v in t.items()}
     out["x"] = x
     return out
+
+
+_traced_small = functools.lru_cache(maxsize=None)(_traced)
+_traced_stride = functools.lru_cache(maxsize=1)(_traced)  # up to 300 MB each: only the latest is kept
+
+
+def traced(dim, case):
+    """One traced forward with histograms per (dim, case), shared and never modified; host copies of every plane."""
+    return (_traced_stride if case == STRIDE_CASE else _traced_small)(dim, case)
 
 
 def device_planes(t, n_layers):
@@ -326,6 +336,7 @@ def device_planes(t, n_layers):
     return want
 
 
+@functools.lru_cache(maxsize=None)  # a (dim, case) that passed is not counted through again; a failure is never cached
 def check_rows_equal_planes(dim, case):
     from sparsernns_amd import floatmodel
 
@@ -349,20 +360,20 @@ def check_rows_equal_planes(dim, case):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dim,case", GRID, ids=IDS)
+@pytest.mark.parametrize("dim,case", GRID + STRIDES, ids=IDS + STRIDE_IDS)
 def test_rows_equal_exp_hist_of_the_device_planes(dim, case):
     check_rows_equal_planes(dim, case)
 
 
 @pytest.mark.gpu
-def test_grid_stride_workgroups_accumulate_over_several_tiles():
-    dim, case = STRIDE
+@pytest.mark.parametrize("dim,case", STRIDES, ids=STRIDE_IDS)
+def test_grid_stride_workgroups_accumulate_over_several_tiles(dim, case):
     assert (case[0] * case[1] + 31) // 32 > 512
     check_rows_equal_planes(dim, case)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dim,case", GRID + [STRIDE], ids=IDS + ["stride"])
+@pytest.mark.parametrize("dim,case", GRID + STRIDES, ids=IDS + STRIDE_IDS)
 def test_hist_changes_nothing_else_and_trace_changes_no_hist(dim, case):
     import torch
     from sparsernns_amd._lib import lib

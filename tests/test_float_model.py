@@ -5,6 +5,15 @@ planes (float_model_ref.stage_*), inside the forward error bound of a float32 fm
 tuned.  Observers: bit for bit the absmax of the device's own planes.  The hot (non-trace) forward must equal the traced one
 bit for bit.  End to end: observers against a float64 model within 8x synth.float_forward's own deviation, and the derived
 fxp_qconfig identical to the host calibration's.
+
+The stage-wise checks also run where workgroups walk several tiles (WALK below), at every dim_scale: a hazard between two
+tiles of a loop, or a slip in its tile indexing, is shared by all six forms of the kernels, so comparing one form with another
+cannot see it.  The scan is held per state as well as globally (float_model_ref.per_state_scan).
+
+Measured on the MI355X, largest error / bound per stage over the six WALK cases ((5,3300) at 0.25 .. 1.0, (3,10930) at 0.5 and
+1.0): encoder 0.020, u 0.241, Bu 0.107, y 0.109, g_in 0.111, h_out 0.125, decoder 0.117; xs 2.4e-7 max|x| against 1e-5.  Per
+state, over all fourteen cases: largest err_dev / (4 err_tree + 1e-6 scale_p) 0.210 ((3,10930) at 1.0), largest
+err_dev / err_tree 2.37 ((2,70) at 0.75, on a state where both errors lie under the 1e-6 floor).
 """
 import ctypes as C
 import functools
@@ -19,6 +28,13 @@ CASES = [(1, 1, 13), (2, 70, 11), (3, 33, 12)]
 DIMS_FOR = {(1, 1, 13): (0.25, 0.5), (2, 70, 11): (0.25, 0.5, 0.75, 1.0), (3, 33, 12): (0.25, 0.5)}
 GRID = [(d, c) for c in CASES for d in DIMS_FOR[c]]
 IDS = [f"dim{d}-B{c[0]}L{c[1]}" for d, c in GRID]
+# Launches are capped at 512 workgroups, each walking 32-frame tiles with a stride of the grid.  (5, 3300): 516 tiles, so
+# workgroups 0..3 walk a second tile (the last of them with 20 valid rows), and 7 chunks of the scan; the smallest shape at
+# which a tile loop runs twice.  (3, 10930): 1025 tiles, workgroup 0 walks three and its last one is partial.
+WALK2, WALK3 = (5, 3300, 14), (3, 10930, 15)
+WALK = [(d, WALK2) for d in (0.25, 0.5, 0.75, 1.0)] + [(d, WALK3) for d in (0.5, 1.0)]
+STAGE_GRID = GRID + WALK  # the stage-wise checks; the end-to-end ones keep GRID, which their preconditions (MARGIN) are tied to
+STAGE_IDS = [f"dim{d}-B{c[0]}L{c[1]}" for d, c in STAGE_GRID]
 MARGIN = 2e-4  # log2 distance every host observer keeps from a threshold of derive_qconfig (precondition of qconfig equality)
 
 
@@ -28,11 +44,15 @@ def model(dim):
     return md, qc, dims
 
 
+def make_x(dim, case):
+    return synth.make_input(case[0], case[1], model(dim)[2]["d_in"], seed=case[2])
+
+
 @functools.lru_cache(maxsize=None)
 def host_run(dim, case):
     """(x, y, stats) of synth.float_forward, and the float64 model's observers."""
     md, _, dims = model(dim)
-    x = synth.make_input(case[0], case[1], dims["d_in"], seed=case[2])
+    x = make_x(dim, case)
     st, st64 = {}, {}
     y = synth.float_forward(md, x, dims["n_layers"], stats=st)
     y64 = R.forward_f64(md, x, dims["n_layers"], stats=st64)
@@ -216,100 +236,43 @@ def engine(dim):
     return eng
 
 
-@functools.lru_cache(maxsize=None)
+def _traced(dim, case):
+    t = engine(dim).forward_traced(make_x(dim, case))
+    out = {k: v.cpu().numpy() for k, v in t.items()}
+    out["x"] = make_x(dim, case)
+    return out
+
+
+_traced_small = functools.lru_cache(maxsize=None)(_traced)
+_traced_walk = functools.lru_cache(maxsize=1)(_traced)  # hundreds of megabytes each: only the latest is kept
+
+
 def traced(dim, case):
-    """One traced forward per (dim, case), shared and never modified; host copies of every plane."""
-    x = host_run(dim, case)[0]
-    t = engine(dim).forward_traced(x)
-    return {k: v.cpu().numpy() for k, v in t.items()}
-
-
-def within(dev, ref, K, S, what):
-    err = np.abs(dev.astype(np.float64) - ref)
-    lim = R.bound(K, S)
-    worst = float((err / np.maximum(lim, 1e-300)).max())
-    print(f"{what}: max err {err.max():.3e}, worst err / bound {worst:.3f}")
-    assert (err <= lim).all(), (what, float(err.max()), worst)
+    """One traced forward per (dim, case), shared and never modified; host copies of every plane, and the input as ``x``."""
+    return (_traced_walk if case in (WALK2, WALK3) else _traced_small)(dim, case)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dim,case", GRID, ids=IDS)
+@pytest.mark.parametrize("dim,case", STAGE_GRID, ids=STAGE_IDS)
 def test_every_stage_within_the_float32_chain_bound(dim, case):
     md, _, dims = model(dim)
-    H, P = dims["H"], dims["P"]
-    x = host_run(dim, case)[0]
     t = traced(dim, case)
-    enc = md["encoder"]
-    v, S = R.stage_dense(x, enc["encoder"]["kernel"], enc["encoder"]["bias"])
-    within(t["h_enc"], np.maximum(v, 0), 257, S, "encoder")
-    h = t["h_enc"]
-    for i in range(dims["n_layers"]):
-        layer = enc[f"layers_{i}"]
-        lam_bar, B_bar, Cc = synth.zoh(layer["mixer"])
-        u, y, g_in, g, h_out = (t[f"l{i}.{k}"] for k in ("u", "y", "g_in", "g", "h_out"))
-        Bu, xs = t[f"l{i}.Bu"], t[f"l{i}.xs"]
-        v, S = R.stage_u(h, layer["norm"])
-        within(u, v, 0, S, f"l{i}.u")
-        (vr, Sr), (vi, Si) = R.stage_bu(u, B_bar)
-        within(Bu.real, vr, H, Sr, f"l{i}.Bu_re")
-        within(Bu.imag, vi, H, Si, f"l{i}.Bu_im")
-        ref = R.scan_f64(lam_bar, Bu)
-        err, scale = np.abs(xs - ref).max(), np.abs(ref).max()
-        print(f"l{i}.xs: max err {err:.3e} of max|x| {scale:.3e}")
-        assert err <= 1e-5 * scale
-        v, S = R.stage_y(xs, u, Cc, layer["mixer"]["D"])
-        within(y, v, P, S, f"l{i}.y")
-        v, S = R.stage_dense(np.maximum(y, 0), layer["out2"]["kernel"], layer["out2"]["bias"])
-        within(g_in, v, H, S, f"l{i}.g_in")
-        gerr = np.abs(g - R.sigmoid64(g_in)).max()
-        print(f"l{i}.g: max err {gerr:.3e}")
-        assert gerr <= 1e-6
-        v, S = R.stage_hout(y, g, h)
-        within(h_out, v, 0, S, f"l{i}.h_out")
-        h = h_out
-    v, S = R.stage_dense(h, md["decoder"]["kernel"], md["decoder"]["bias"])
-    within(t["out"], v, H, S, "decoder")
+    R.check_stages(md, dims["n_layers"], t["x"], t)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dim,case", GRID, ids=IDS)
+@pytest.mark.parametrize("dim,case", STAGE_GRID, ids=STAGE_IDS)
 def test_observers_are_the_absmax_of_the_device_planes(dim, case):
-    from sparsernns_amd import floatmodel
-
-    _, _, dims = model(dim)
-    x = host_run(dim, case)[0]
+    md, _, dims = model(dim)
     t = traced(dim, case)
-    want = {"encoder.inp": x, "decoder.inp": t[f"l{dims['n_layers'] - 1}.h_out"], "decoder.out": t["out"]}
-    for i in range(dims["n_layers"]):
-        x1 = np.maximum(t[f"l{i}.y"], 0)
-        want.update({f"l{i}.u": t[f"l{i}.u"], f"l{i}.Bu_re": t[f"l{i}.Bu"].real, f"l{i}.Bu_im": t[f"l{i}.Bu"].imag,
-                     f"l{i}.x_re": t[f"l{i}.xs"].real, f"l{i}.x_im": t[f"l{i}.xs"].imag, f"l{i}.y": t[f"l{i}.y"],
-                     f"l{i}.out2.inp": x1, f"l{i}.out2.out": t[f"l{i}.g_in"], f"l{i}.gate.l": x1, f"l{i}.gate.r": t[f"l{i}.g"]})
-    got = dict(zip(floatmodel.STAT_KEYS, t["stats"]))
-    for k, plane in want.items():
-        assert got[k].view(np.uint32) == np.abs(plane).max().astype(np.float32).view(np.uint32), k
-    # encoder.out is observed before the ReLU and the stored plane has it behind it: no device plane to take the absmax of.
-    # It must cover the stored plane and lie within the encoder's chain bound of the float64 stage's absmax.
-    md = model(dim)[0]
-    v, S = R.stage_dense(x, md["encoder"]["encoder"]["kernel"], md["encoder"]["encoder"]["bias"])
-    assert set(got) == set(want) | {"encoder.out"} and got["encoder.out"] >= t["h_enc"].max()
-    assert abs(float(got["encoder.out"]) - np.abs(v).max()) <= R.bound(257, S).max()
+    R.check_observers(md, dims["n_layers"], t["x"], t)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dim,case", GRID, ids=IDS)
+@pytest.mark.parametrize("dim,case", STAGE_GRID, ids=STAGE_IDS)
 def test_hot_forward_equals_the_traced_forward(dim, case):
-    import torch
-
-    eng = engine(dim)
-    x = torch.from_numpy(host_run(dim, case)[0]).to(eng.device)
     t = traced(dim, case)
-    st = eng.new_stats()
-    y = eng.forward_device(x, st)
-    assert np.array_equal(y.cpu().numpy().view(np.uint32), t["out"].view(np.uint32))
-    assert np.array_equal(st.cpu().numpy().view(np.uint32), t["stats"].view(np.uint32))
-    # a NULL stats array leaves y unchanged
-    assert torch.equal(eng.forward_device(x, None), y)
+    R.check_hot_equals_traced(engine(dim), t["x"], t)
 
 
 @pytest.mark.gpu
