@@ -169,6 +169,33 @@
             for (int j = 0; j < (HP - H) / 4; ++j) *reinterpret_cast<v2i *>(t + 8 * j) = v2i{0, 0};
         }
     }
+    // EARLY (the 32-frame UREC forms at KS = 1): phase A's items are mapped over the live state slots, and a tile's states are
+    // requested at the top of the tile, in front of the staging, as loads the compiler cannot see (see the tile loop).
+    //   The stream holds live_slots slots (0: all P); PL = live_slots up to a multiple of 4 (the quad transposes need whole
+    // quads), ITEMS = (FT / 4) PL: one round of the workgroup for PL <= 24, otherwise a second round on wave 0.  A thread's
+    // (group, slot) of round i never changes: half-word i of `items` holds group | slot << 3, or 0xffff for no item.  The
+    // columns p >= PL of the Sl / Sh planes (re and im halves) are written here, once, with the bytes of a zero state: nothing
+    // else touches the planes (the row tiles, which also park the extremes at the end, lie behind X1).
+    // KS = 2 (three rounds, 142 registers) keeps the general form below.
+    constexpr bool EARLY = UREC && S16 && KS == 1 && FT == 32;
+    [[maybe_unused]] uint32_t items = 0;
+    static_assert(!EARLY || (ROUNDS <= 2 && FT / 4 <= 8), "a half-word per round: three bits of group, the slot above them");
+    [[maybe_unused]] auto item_of = [&](int i) { return (int)((items >> (16 * i)) & 0xffffu); };
+    if constexpr (EARLY) {
+        const int PL = a.live_slots > 0 ? (a.live_slots + 3) & ~3 : P;
+#pragma unroll
+        for (int i = 0; i < ROUNDS; ++i) {
+            const int q = threadIdx.x + NTHR * i, grp = q / PL;
+            items |= (uint32_t)(q < (FT / 4) * PL ? grp | ((q - grp * PL) << 3) : 0xffff) << (16 * i);
+        }
+        for (int i = threadIdx.x; i < FT * ((P - PL) >> 2); i += NTHR) {
+            const int f = i / ((P - PL) >> 2), c = PL + 4 * (i % ((P - PL) >> 2));
+            *reinterpret_cast<int32_t *>(Sl + f * KPS + c) = (int32_t)0x80808080u;
+            *reinterpret_cast<int32_t *>(Sh + f * KPS + c) = 0;
+            *reinterpret_cast<int32_t *>(Sl + f * KPS + P + c) = (int32_t)0x80808080u;
+            *reinterpret_cast<int32_t *>(Sh + f * KPS + P + c) = 0;
+        }
+    }
     TileWalk<FT> walk((int64_t)blockIdx.x, sr, gridDim.x);
     if ((int64_t)blockIdx.x < tiles) {
         if constexpr (COAL) {
@@ -272,14 +299,103 @@
         // thread: the kernel sits at its register cap)
         char *zb = reinterpret_cast<char *>(a.z + n0 * H);
         const int64_t tile_next = tile + gridDim.x;
+        // EARLY: this tile's states, all rounds, requested here: they are the only loads of the loop whose result the issuing
+        // tile needs, and behind the staging every wave waited a full round trip for them (and, vmcnt retiring in order, for the
+        // acknowledgement of the U stores the staging had just issued).  The staging holds no accumulator, so their registers
+        // are free there.  The loads are hidden from the compiler (scan_quad.hpp gload8_hidden): its own wait at their first
+        // use would be vmcnt(0) behind the stores.  First the rows requested a tile ago must have landed (they have, long
+        // since): a wait the compiler places for them inside the staging would count the state loads it cannot see as well.
+        //   `xs` is only ever read by this kernel (the recurrence wrote it in an earlier launch), so moving its loads across
+        // the U stores changes nothing.
+        // A lane without an item, or on a slot the stream does not hold, re-reads slot 0 (always stored); its words are zeroed.
+        constexpr int XW = PAIR ? 2 : 1; // hidden loads per round
+        [[maybe_unused]] std::conditional_t<PAIR, v2i, v4i> xq[EARLY ? XW * ROUNDS : 1] = {}; // (a round the wave does not run stays zero)
+        [[maybe_unused]] const bool full_prev = zb_prev && nvalid_prev == FT; // wave-uniform
+        auto item_offset = [&](int i, int &o) { // the 4-step block and the byte offset of the thread's item of round i
+            const int it = item_of(i), grp = it & 7;
+            int p = it >> 3;
+            p = it != 0xffff && (a.live_slots <= 0 || p < a.live_slots) ? p : 0;
+            o = 4 * grp;
+            if (o >= nvalid) o = (nvalid - 1) & ~3; // partial tile: re-read the last block (results unused)
+            return PAIR ? 2u * (unsigned)(((((o >> 3) << 5) + p) << 4) + (o & 4)) : 16u * (unsigned)((o >> 2) * P + p);
+        };
+        if constexpr (EARLY) {
+            prologue_loads_done();
+            const char *xb = reinterpret_cast<const char *>(reinterpret_cast<const int16_t *>(a.xs) +
+                                                            (PAIR ? pair_word(b0, t0 >> 3, 0, a.TB >> 1, P) << 1 : native_word(b0, t0, 0, 0, a.TB, P)));
+#pragma unroll
+            for (int i = 0; i < ROUNDS; ++i) {
+                if (i > 0 && __builtin_amdgcn_readfirstlane(item_of(i)) == 0xffff) break; // wave-uniform: no item of this round in the wave
+                int o;
+                const unsigned xo = item_offset(i, o);
+                if constexpr (PAIR) { xq[2 * i] = gload8_hidden(xb, xo); xq[2 * i + 1] = gload8_hidden(xb, xo + 16); }
+                else xq[i] = gload16_hidden(xb, xo);
+            }
+        }
         if constexpr (UREC) { // z of the previous tile out, skip of this one in, and u made from it
             if (brow.arm == ROW_PACKED) tiles_in_urec(std::integral_constant<int, ROW_PACKED>{});
             else if (brow.arm == ROW_SHIFTED) tiles_in_urec(std::integral_constant<int, ROW_SHIFTED>{});
             else tiles_in_urec(std::integral_constant<int, ROW_GENERIC>{});
+            if constexpr (EARLY) {
+                // Behind a full previous tile (zb_prev set, every frame valid: wave-uniform) each of the staging's NVC guarded
+                // store instructions has been issued exactly once since the requests, whatever the compiler made of the
+                // guards -- a branch around the store that a non-empty exec mask does not take, or the mask alone -- so the
+                // states have landed when at most NVC operations are outstanding.  (Two copies of the staging, the second
+                // with the guards compiled out, do not fit the registers: 20 to 44 bytes of scratch.)  Every other tile (the
+                // first, one behind a partial tile) drains, as the encoder and decoder do for their partial tile.
+                // tools/check_vmwait.py counts the stores between the requests and this wait in the compiled code.
+                vm_wait_or_drain<NVC>(full_prev, xq);
+            }
         } else if constexpr (COAL) tiles_in_out(true); // z of the previous tile out, u and skip of this one in
         // ---- phase A: stream items -> byte planes
+        if constexpr (EARLY) {
 #pragma unroll
-        for (int i = 0; i < ROUNDS; ++i) {
+            for (int i = 0; i < ROUNDS; ++i) {
+                if (i > 0 && __builtin_amdgcn_readfirstlane(item_of(i)) == 0xffff) break;
+                if (item_of(i) != 0xffff) {
+                    const int grp = item_of(i) & 7, p = item_of(i) >> 3;
+                    int o;
+                    item_offset(i, o);
+                    const int nlive = nvalid - o; // >= 1; >= 4 everywhere but in a sequence's last block (see below)
+                    const bool held = a.live_slots <= 0 || p < a.live_slots;
+                    int32_t w[4];
+                    if constexpr (PAIR) { // lane A: [im0 im2 | re1 re3], lane B: [re0 re2 | im1 im3] (per half)
+                        const v2i qa = held ? xq[2 * i] : v2i{0, 0}, qb = held ? xq[2 * i + 1] : v2i{0, 0};
+                        w[0] = (int32_t)perm((unsigned)qa[0], (unsigned)qb[0], 0x05040100u);
+                        w[1] = (int32_t)perm((unsigned)qb[1], (unsigned)qa[1], 0x05040100u);
+                        w[2] = (int32_t)perm((unsigned)qa[0], (unsigned)qb[0], 0x07060302u);
+                        w[3] = (int32_t)perm((unsigned)qb[1], (unsigned)qa[1], 0x07060302u);
+                    } else { // re of steps 0..3, then im of steps 0..3, as int16
+                        const v4i q4 = held ? xq[i] : v4i{0, 0, 0, 0};
+                        w[0] = (int32_t)perm((unsigned)q4[2], (unsigned)q4[0], 0x05040100u);
+                        w[1] = (int32_t)perm((unsigned)q4[2], (unsigned)q4[0], 0x07060302u);
+                        w[2] = (int32_t)perm((unsigned)q4[3], (unsigned)q4[1], 0x05040100u);
+                        w[3] = (int32_t)perm((unsigned)q4[3], (unsigned)q4[1], 0x07060302u);
+                    }
+                    if (nlive < 4) {
+#pragma unroll
+                        for (int j = 1; j < 4; ++j) w[j] = j < nlive ? w[j] : 0;
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { // range check and complex ReLU, as in the general form below
+                        pmax = __builtin_elementwise_max(pmax, __builtin_bit_cast(v2i16, w[j]));
+                        pmin = __builtin_elementwise_min(pmin, __builtin_bit_cast(v2i16, w[j]));
+                        const bool keep = ((int32_t)((uint32_t)w[j] << 16) + (w[j] >> 16)) > 0;
+                        w[j] = keep ? w[j] : 0;
+                    }
+                    quad_transpose(w, l);
+                    const unsigned t01 = perm((unsigned)w[1], (unsigned)w[0], 0x05010400u), u01 = perm((unsigned)w[1], (unsigned)w[0], 0x07030602u);
+                    const unsigned t23 = perm((unsigned)w[3], (unsigned)w[2], 0x05010400u), u23 = perm((unsigned)w[3], (unsigned)w[2], 0x07030602u);
+                    const int row = (4 * grp + (l & 3)) * KPS + (p & ~3);
+                    *reinterpret_cast<int32_t *>(Sl + row) = (int32_t)(perm(t23, t01, 0x05040100u) ^ 0x80808080u);
+                    *reinterpret_cast<int32_t *>(Sh + row) = (int32_t)perm(t23, t01, 0x07060302u);
+                    *reinterpret_cast<int32_t *>(Sl + row + P) = (int32_t)(perm(u23, u01, 0x05040100u) ^ 0x80808080u);
+                    *reinterpret_cast<int32_t *>(Sh + row + P) = (int32_t)perm(u23, u01, 0x07060302u);
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < (EARLY ? 0 : ROUNDS); ++i) {
             const int q = threadIdx.x + NTHR * i;
             if (ROUNDS * NTHR == ITEMS || q < ITEMS) {
                 const int grp = q / P, p = q % P;
@@ -580,18 +696,23 @@
     mx[0] = ldexpf(mx[0], -skip_e);
     mx[1] = ldexpf(mx[1], -a.res_exp);
     mx[2] = ldexpf(mx[2], -skip_e);
+    // EARLY: the thread index behind an empty statement, so that what the tail derives from it (the wave index, the word of the
+    // maxima) is computed here: kept across the tile loop for these uses alone, two such values were spilled
+    unsigned tx = threadIdx.x;
+    if constexpr (EARLY) asm volatile("" : "+v"(tx));
+    const int wave_r = EARLY ? (int)(tx >> 6) : wave;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         float x = mx[i];
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
-        if (l == 0) red[i * 16 + wave] = x;
+        if (l == 0) red[i * 16 + wave_r] = x;
     }
     __syncthreads();
-    if (threadIdx.x < 3) {
-        float x = red[threadIdx.x * 16];
-        for (int w = 1; w < NW; ++w) x = fmaxf(x, red[threadIdx.x * 16 + w]);
-        atomicMax(a.dynw->mx + a.mx_slot + threadIdx.x, __float_as_uint(x));
+    if (tx < 3) {
+        float x = red[tx * 16];
+        for (int w = 1; w < NW; ++w) x = fmaxf(x, red[tx * 16 + w]);
+        atomicMax(a.dynw->mx + a.mx_slot + tx, __float_as_uint(x));
     }
     // FOLD, gate_ext: one thread per (bound, channel) folds the NTHR / VPF threads that own the channel's group (the barrier above
     // stands between their stores and these loads) and issues one biased-float atomicMax into this workgroup's replica of the

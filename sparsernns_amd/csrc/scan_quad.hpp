@@ -111,6 +111,20 @@ __device__ __forceinline__ void vm_wait(T (&regs)[N])
     for (int i = 0; i < N; ++i) asm volatile("" : "+v"(regs[i]));
 }
 
+// The same wait where the count holds on some paths only: `counted` (wave-uniform) says that exactly NEWER operations have been
+// issued since the loads; otherwise everything is drained first.  One statement, so that no path leads around both waits.
+template <int NEWER, class T, int N>
+__device__ __forceinline__ void vm_wait_or_drain(bool counted, T (&regs)[N])
+{
+    static_assert(NEWER >= 0 && NEWER < 64, "vmcnt is a 6-bit counter");
+    asm volatile("s_cmp_lg_u32 %0, 0\n\ts_cbranch_scc1 1f\n\ts_waitcnt vmcnt(0)\n1:\n\ts_waitcnt vmcnt(%1)"
+                 :
+                 : "s"(__builtin_amdgcn_readfirstlane((int)counted)), "n"(NEWER) // (a scalar register also where the compiler keeps the flag per lane)
+                 : "memory", "scc");
+#pragma unroll
+    for (int i = 0; i < N; ++i) asm volatile("" : "+v"(regs[i]));
+}
+
 // word index of (sequence b, step t, state p, component c) in a scan-native stream with TB blocks/sequence
 __device__ __forceinline__ int64_t native_word(int64_t b, int t, int p, int c, int TB, int P)
 {
