@@ -118,6 +118,19 @@ int s5fxp_scan(const int32_t *bu_re, const int32_t *bu_im, const int32_t *a_re, 
 int s5fxp_assoc_scan_c64(const float *lambda, const float *bu, float *xs, const float *x0, float *x_last, int B, int L,
                          int P, int reverse, void *stream);
 
+/* The float recurrence with the integer model's per-step rounding (csrc/scan_fq.hpp; the reference of every
+ * test is floatmodel.fq_scan).  With F(v, e) = floor(v * 2^e) * 2^-e of the exact real v,
+ *   xr' = (F(ar xr, exp_re) - F(ai xi, exp_re)) + F(br, exp_re),  xi' = (F(ar xi, exp_im) + F(ai xr, exp_im)) + F(bi, exp_im),
+ * sequentially over time: the statement of fxpmodel.py:147-172 on values instead of integers, for equal exponent pairs and
+ * without the int32 wrap.  Inside the domain (every |x| * 2^exp < 2^24, every v * 2^exp a normal number or zero) the result
+ * is exact, bit for bit that of the float64 statement.  lambda: (P) complex64; bu, xs: (B,L,P) complex64; x0, x_last: (B,P)
+ * or NULL as in s5fxp_assoc_scan_c64; lens: DEVICE int32 (B) or NULL: sequence b runs clamp(lens[b], 0, L) steps of its
+ * L-strided rows, nothing behind them is read or written, and x_last[b] is its state after those steps.
+ * S5FXP_EBADARG, before the device is touched: a NULL lambda / bu / xs, B, L or P < 1, an exponent outside -24..40, and a
+ * shape whose grid or whose 32-bit row offsets do not fit ((64 / P + 2) * L * P * 8 bytes must stay below 2^32). */
+int s5fxp_fq_scan_c64(const float *lambda, const float *bu, float *xs, const float *x0, float *x_last, const int32_t *lens,
+                      int B, int L, int P, int exp_re, int exp_im, void *stream);
+
 /* The audio steps either side of the model in the N-DNS validation loop, sparseRNNs/fxprun.py:63-78, with the framing of
  * train_helpers.py:1382-1412 (scipy.signal.stft / istft: nperseg = nfft = 512, hop 128, boxcar window, one-sided,
  * boundary="zeros", padded=True, scaling="spectrum").  No model handle, no workspace.  Tensors are frame-major:
@@ -723,12 +736,18 @@ int s5fxp_float_model_clips(const s5fxp_float_model *m, const float *x, int n, i
  * s5fxp_float_model_forward / s5fxp_float_model_clips.  There is no histogram together with fake quantisation.
  * S5FXP_EBADARG, before the device is touched, for bits outside {0, 2..24}, exp outside -24..40, an unknown mode, a saturate
  * other than 0 / 1, and saturate == 1 on a state site (x_re, x_im: the integer model wraps its state, it does not clip it);
- * every other argument, error, and the workspace and trace sizes as in the entries without fq. */
+ * every other argument, error, and the workspace and trace sizes as in the entries without fq.
+ * mode S5FXP_FQ_STEP is accepted on the state sites x_re / x_im only, on both of a layer together and with
+ * saturate == 0: that layer's recurrence is then s5fxp_fq_scan_c64 at the two sites' exponents in place of the associative
+ * scan (for clips with lens), so the rounding of the integer recurrence is inside the loop and fed back through the pole.
+ * The gate kernel gets the two sites as off (the states are on their grids already); the observers keep their place; bits
+ * is checked and unused.  S5FXP_EBADARG for the mode on any other site, on one state site of a layer only, and for a shape
+ * s5fxp_fq_scan_c64 refuses.  A spec without step sites launches exactly what it launched without this mode. */
 typedef struct {
     int8_t bits, exp;
     uint8_t mode, saturate;
 } s5fxp_float_fq_site;
-enum { S5FXP_FQ_FLOOR = 0, S5FXP_FQ_NEAREST = 1 };
+enum { S5FXP_FQ_FLOOR = 0, S5FXP_FQ_NEAREST = 1, S5FXP_FQ_STEP = 2 };
 int s5fxp_float_model_forward_fq(const s5fxp_float_model *m, const float *x, int B, int L, float *y, float *stats,
                                  const s5fxp_float_fq_site *fq, float *trace, void *workspace, size_t workspace_bytes,
                                  void *stream);

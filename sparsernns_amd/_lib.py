@@ -132,6 +132,7 @@ def _load():
         "s5fxp_sigmoid": (i, [p, p, i64, i, i, i, i, I32P, p]),
         "s5fxp_scan": (i, [p, p, p, p, p, p, i, i, i, i, i, i, i, i, i, i, p]),
         "s5fxp_assoc_scan_c64": (i, [p, p, p, p, p, i, i, i, i, p]),
+        "s5fxp_fq_scan_c64": (i, [p, p, p, p, p, p, i, i, i, i, i, p]),
         "s5fxp_stft_frames": (i64, [i64]),
         "s5fxp_stft_mag": (i, [p, i, i64, C.c_float, p, p, p]),
         "s5fxp_mask_istft": (i, [p, p, i, i64, p, p, p]),
@@ -198,7 +199,7 @@ def _load():
 
 lib = _load()
 EXPORTED_SYMBOLS = ("s5fxp_version s5fxp_strerror s5fxp_from_fp s5fxp_to_float s5fxp_change_cfg s5fxp_dense s5fxp_dense_csr s5fxp_add "
-                    "s5fxp_mul s5fxp_add_cb s5fxp_mul_cb s5fxp_relu s5fxp_sigmoid s5fxp_scan s5fxp_assoc_scan_c64 s5fxp_model_blob_bytes "
+                    "s5fxp_mul s5fxp_add_cb s5fxp_mul_cb s5fxp_relu s5fxp_sigmoid s5fxp_scan s5fxp_assoc_scan_c64 s5fxp_fq_scan_c64 s5fxp_model_blob_bytes "
                     "s5fxp_model_create s5fxp_model_destroy s5fxp_workspace_bytes s5fxp_model_forward s5fxp_model_forward_f32 s5fxp_workspace_bytes_f32 s5fxp_model_forward_i16 s5fxp_workspace_bytes_i16 s5fxp_layer_forward s5fxp_model_layer_out_bits s5fxp_model_live_states "
                     "s5fxp_model_out_exp s5fxp_model_out_bits s5fxp_model_is_fast s5fxp_model_recurrence_kernel s5fxp_model_recurrence_xmax "
                     "s5fxp_model_step_ok s5fxp_model_step s5fxp_model_step_f32 "

@@ -6,6 +6,7 @@
 #include "s5fxp_kernels.hpp"
 #include "mfma_fused.hpp"
 #include "scan_assoc.hpp"
+#include "scan_fq.hpp"
 #include "audio_stft.hpp"
 #include "audio_stream.hpp"
 #include "audio_score.hpp"
@@ -15,6 +16,7 @@
 
 #include <algorithm>
 #include <array>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -278,6 +280,22 @@ extern "C" int s5fxp_assoc_scan_c64(const float *lambda, const float *bu, float 
     a.xs = reinterpret_cast<float2 *>(xs); a.x0 = reinterpret_cast<const float2 *>(x0);
     a.x_last = reinterpret_cast<float2 *>(x_last); a.B = B; a.L = L; a.P = P; a.reverse = reverse ? 1 : 0;
     hipLaunchKernelGGL(k_scan_assoc_c64, dim3((unsigned)grid), dim3(64 * ASSOC_WAVES), 0, S(stream), a);
+    return launch_rc();
+}
+
+extern "C" int s5fxp_fq_scan_c64(const float *lambda, const float *bu, float *xs, const float *x0, float *x_last,
+                                 const int32_t *lens, int B, int L, int P, int exp_re, int exp_im, void *stream)
+{
+    if (!lambda || !bu || !xs || B < 1 || L < 1 || P < 1) return S5FXP_EBADARG;
+    if (exp_re < -24 || exp_re > 40 || exp_im < -24 || exp_im > 40) return S5FXP_EBADARG;
+    const int64_t grid = ((int64_t)B * P + 63) / 64; // one wave per workgroup
+    if (grid > 0x7fffffffll || !fqs_span_ok(L, P)) return S5FXP_EBADARG;
+    ScanFqArgs a{};
+    a.lambda = reinterpret_cast<const float2 *>(lambda); a.bu = reinterpret_cast<const float2 *>(bu);
+    a.xs = reinterpret_cast<float2 *>(xs); a.x0 = reinterpret_cast<const float2 *>(x0);
+    a.x_last = reinterpret_cast<float2 *>(x_last); a.lens = lens; a.B = B; a.L = L; a.P = P;
+    a.sr = ldexpf(1.f, exp_re); a.isr = ldexpf(1.f, -exp_re); a.si = ldexpf(1.f, exp_im); a.isi = ldexpf(1.f, -exp_im);
+    hipLaunchKernelGGL(k_scan_fq_c64, dim3((unsigned)grid), dim3(64), 0, S(stream), a);
     return launch_rc();
 }
 
@@ -1407,6 +1425,8 @@ static_assert(FM_HIST_BINS == S5FXP_FLOAT_HIST_BINS && FM_HIST_EMIN == S5FXP_FLO
 struct FqPlan {
     bool any = false;
     std::vector<FqSite> s;
+    std::vector<int> step_re, step_im; // per layer: the exponents of its state sites in step mode, or INT_MIN (scan mode)
+    bool step(int i) const { return !step_re.empty() && step_re[i] != INT_MIN; }
     FFq<2> enc() const { return {{s[0], s[1]}}; }
     FFq<3> bproj(int i) const { const FqSite *l = &s[2 + 10 * i]; return {{l[0], l[1], l[2]}}; }
     FFq<8> gate(int i) const // u, then the gate kernel's seven observers
@@ -1423,25 +1443,35 @@ int fq_plan(const s5fxp_float_fq_site *fq, int n_layers, FqPlan &plan)
     if (!fq) return S5FXP_OK;
     const int n = 4 + 10 * n_layers;
     plan.s.assign(n, FqSite{1.f, 1.f, 0.f, 0.f, 0u});
+    plan.step_re.assign(n_layers, INT_MIN);
+    plan.step_im.assign(n_layers, INT_MIN);
     for (int j = 0; j < n; ++j) {
         const s5fxp_float_fq_site &q = fq[j];
         if (q.bits == 0) continue;
         const int k = j >= 2 && j < n - 2 ? (j - 2) % 10 : -1;
         const bool state = k == 3 || k == 4; // x_re, x_im: the integer model wraps its state
-        if (q.bits < 2 || q.bits > 24 || q.exp < -24 || q.exp > 40 || q.mode > S5FXP_FQ_NEAREST || q.saturate > 1 ||
-            (state && q.saturate))
+        if (q.bits < 2 || q.bits > 24 || q.exp < -24 || q.exp > 40 || q.mode > S5FXP_FQ_STEP || q.saturate > 1 ||
+            (state && q.saturate) || (q.mode == S5FXP_FQ_STEP && !state))
             return S5FXP_EBADARG;
+        if (q.mode == S5FXP_FQ_STEP) { // the recurrence rounds (s5fxp_fq_scan_c64); the gate kernel's site stays off
+            (k == 3 ? plan.step_re : plan.step_im)[(j - 2) / 10] = q.exp;
+            plan.any = true;
+            continue;
+        }
         const float half = ldexpf(1.f, q.bits - 1);
         plan.s[j] = FqSite{ldexpf(1.f, q.exp), ldexpf(1.f, -q.exp), -half, half - 1.f,
                            FM_FQF_ON | (q.mode == S5FXP_FQ_NEAREST ? FM_FQF_NEAREST : 0u) | (q.saturate ? FM_FQF_SATURATE : 0u)};
         plan.any = true;
     }
+    for (int i = 0; i < n_layers; ++i) // both state sites of a layer step together
+        if ((plan.step_re[i] == INT_MIN) != (plan.step_im[i] == INT_MIN)) return S5FXP_EBADARG;
     return S5FXP_OK;
 }
 
 // The one forward of the five entries, rectangular (B sequences of L rows) or, with CLIPS, B clips padded to L rows of which
 // lens[e] are real (no trace planes).  hist == nullptr launches exactly the kernels without the histogram, and
-// fq == nullptr or all off exactly those without fake quantisation (the two are never given together).
+// fq == nullptr or all off exactly those without fake quantisation (the two are never given together).  A layer whose state
+// sites are in step mode runs k_scan_fq_c64 in place of the associative scan; every other launch is unchanged.
 template <bool CLIPS>
 int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, const int32_t *lens, float *y, float *stats,
                   unsigned long long *hist, const s5fxp_float_fq_site *fq, float *trace, void *workspace, size_t workspace_bytes,
@@ -1456,6 +1486,8 @@ int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, cons
     if (workspace_bytes < s5fxp_float_workspace_bytes(m, B, L, trace != nullptr)) return S5FXP_EWORKSPACE;
     const int64_t scan_grid = (int64_t)B * ((m->P + ASSOC_PT - 1) / ASSOC_PT); // of the clip scan
     if (CLIPS && scan_grid > 0x7fffffffll) return S5FXP_EBADARG;
+    for (int i = 0; i < m->n_layers; ++i) // what s5fxp_fq_scan_c64 would refuse, before anything is launched
+        if (qp.step(i) && (((int64_t)B * m->P + 63) / 64 > 0x7fffffffll || !fqs_span_ok(L, m->P))) return S5FXP_EBADARG;
     const long long N = t.N;
     const size_t NH = (size_t)N * m->H, NP2 = (size_t)N * 2 * m->P;
     hipStream_t st = S(stream);
@@ -1483,7 +1515,9 @@ int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, cons
         else if (hist) fm_launch<CLIPS>(t, st, FM_K_TRACE(k_fbproj_hist, k_fbproj_clips_hist), ba, lh);
         else fm_launch<CLIPS>(t, st, FM_K_TRACE(k_fbproj, k_fbproj_clips), ba);
         if ((rc = launch_rc())) return rc;
-        if constexpr (CLIPS) {
+        if (qp.step(i)) {
+            rc = s5fxp_fq_scan_c64(l.lam, bu, xs, nullptr, nullptr, lens, B, L, m->P, qp.step_re[i], qp.step_im[i], stream);
+        } else if constexpr (CLIPS) {
             ScanAssocClipsArgs sa{reinterpret_cast<const float2 *>(l.lam), reinterpret_cast<const float2 *>(bu),
                                   reinterpret_cast<float2 *>(xs), lens, B, L, m->P};
             hipLaunchKernelGGL(k_scan_assoc_c64_clips, dim3((unsigned)scan_grid), dim3(64 * ASSOC_WAVES), 0, st, sa);

@@ -18,6 +18,12 @@ Chosen observed tensors can be fake-quantised inside the forward (``fake_quant``
 DESIGN.md §4u): a site that is on rounds its tensor to the grid of its quantiser right after the observer saw it, so
 ``sensitivity`` can say which of the 34 quantisers costs the output its SQNR, one at a time and all together.
 
+The two things those sites cannot see are modelled too.  ``fq_spec(..., recurrence="step")`` puts a layer's
+state sites into mode ``FQ_STEP``: its recurrence then floors four exact products and ``Bu`` at every step, as the integer
+recurrence does (``s5fxp_fq_scan_c64``; ``fq_scan`` is the exact statement and the reference of every test).
+``quantised_modeldict`` replaces chosen weight groups by the integer model's dequantised values, and ``sensitivity`` takes
+``recurrence=`` and ``weights=`` to add those rows to its table.
+
 Results agree with ``synth.float_forward`` to float32 rounding (the summation order differs), not bit for bit.  Without a
 GPU, or for a shape the kernels refuse, ``FloatEngine`` runs ``synth.float_forward`` itself and says so: ``on_device`` is False.
 """
@@ -88,6 +94,66 @@ def fake_quant(v, bits: int, exp: int, mode: str = "floor", saturate: bool = Tru
     if saturate:
         r = np.clip(r, -2.0 ** (int(bits) - 1), 2.0 ** (int(bits) - 1) - 1)  # np.clip hands a NaN through
     return (r * 2.0 ** -int(exp)).astype(F32)
+
+
+FQ_STEP = 2  # S5FXP_FQ_STEP: on a layer's two state sites, the recurrence itself rounds at every step (``fq_scan``)
+FQ_STEP_XMAX = 2.0 ** 24  # the domain of ``fq_scan``: every |x| * 2^exp stays below it
+
+
+def fq_scan(lam, bu, exp_re: int, exp_im: int, x0=None, lens=None, domain: str = "ignore"):
+    """The recurrence with the integer model's per-step rounding, the reference of every step-mode test:
+    with F(v, e) = floor(v * 2^e) * 2^-e of the EXACT real v, sequentially over time
+
+        xr' = (F(ar xr, exp_re) - F(ai xi, exp_re)) + F(br, exp_re)
+        xi' = (F(ar xi, exp_im) + F(ai xr, exp_im)) + F(bi, exp_im)
+
+    ``lam`` (P) and ``bu`` (B,L,P) complex64 (taken as float32 pairs), ``x0`` (B,P) or None (zeros), ``lens`` (B) or None:
+    sequence b runs clamp(lens[b], 0, L) steps, its rows behind them are zero -> (xs (B,L,P), x_last (B,P)) complex64,
+    x_last the state after a sequence's last step.  Evaluated in float64, where the product of two float32 is exact.
+    Inside the DOMAIN -- every |x| * 2^exp below 2^24, every product, br and bi times 2^exp a normal float32 or zero -- every
+    sum is exact, so this is one exactly defined float32 function: on grid values it is ``oracle.fxp_oracle.scan`` integer
+    for integer (equal exponent pairs, no int32 wrap), and ``s5fxp_fq_scan_c64`` computes it bit for bit.  ``domain``:
+    "ignore"; "report" -> (xs, x_last, stayed_inside); "raise" -> ValueError when the run left it.  A NaN in ``bu`` makes
+    that state NaN from there on and does not count as leaving the domain."""
+    if domain not in ("ignore", "report", "raise"):
+        raise ValueError(f'domain must be "ignore", "report" or "raise", got {domain!r}')
+    lam, bu = _c64(lam), _c64(bu)
+    if bu.ndim != 3 or lam.shape != bu.shape[2:]:
+        raise ValueError(f"lam must be (P) and bu (B,L,P), got {lam.shape} and {bu.shape}")
+    B, L, P = bu.shape
+    ar, ai = lam.real.astype(np.float64), lam.imag.astype(np.float64)
+    sr, si = 2.0 ** int(exp_re), 2.0 ** int(exp_im)
+    xr, xi = np.zeros((B, P)), np.zeros((B, P))
+    if x0 is not None:
+        x0 = _c64(x0).reshape(B, P)
+        xr, xi = x0.real.astype(np.float64), x0.imag.astype(np.float64)
+    n = np.full(B, L) if lens is None else np.clip(np.asarray(lens, dtype=np.int64).reshape(B), 0, L)
+    tiny = float(np.finfo(F32).tiny)
+    inside = bool((np.abs(xr) * sr < FQ_STEP_XMAX).all() and (np.abs(xi) * si < FQ_STEP_XMAX).all()) if x0 is not None else True
+
+    def F(v, s):
+        nonlocal inside
+        t = v * s
+        a = np.abs(t[live])
+        if inside and ((a != 0) & (a < tiny)).any():
+            inside = False
+        return np.floor(t) / s
+
+    xs = np.zeros((B, L, P), dtype=np.complex64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for t in range(int(n.max()) if B else 0):
+            live = n > t
+            br, bi = bu[:, t].real.astype(np.float64), bu[:, t].imag.astype(np.float64)
+            nr = (F(ar * xr, sr) - F(ai * xi, sr)) + F(br, sr)
+            ni = (F(ar * xi, si) + F(ai * xr, si)) + F(bi, si)
+            xr, xi = np.where(live[:, None], nr, xr), np.where(live[:, None], ni, xi)
+            if inside and ((np.abs(xr[live]) * sr >= FQ_STEP_XMAX).any() or (np.abs(xi[live]) * si >= FQ_STEP_XMAX).any()):
+                inside = False
+            xs[live, t] = (xr + 1j * xi)[live]
+    x_last = (xr + 1j * xi).astype(np.complex64)
+    if domain == "raise" and not inside:
+        raise ValueError("fq_scan: the run left the domain (|x| * 2^exp >= 2^24, or a subnormal v * 2^exp)")
+    return (xs, x_last, inside) if domain == "report" else (xs, x_last)
 
 
 def _f32(a) -> np.ndarray:
@@ -507,20 +573,26 @@ def _site_error(key: str, bits: int, exp: int, mode: int, saturate: int) -> Opti
         return f"{key}: bits {bits} outside {FQ_BITS[0]}..{FQ_BITS[1]}"
     if not FQ_EXPS[0] <= exp <= FQ_EXPS[1]:
         return f"{key}: exp {exp} outside {FQ_EXPS[0]}..{FQ_EXPS[1]}"
-    if mode not in (0, 1):
+    if mode not in (0, 1, FQ_STEP):
         return f"{key}: unknown mode {mode}"
+    if mode == FQ_STEP and key.split(".")[-1] not in STATE_SITES:
+        return f"{key}: step mode is for the state sites {STATE_SITES} only"
     if saturate not in (0, 1) or (saturate and key.split(".")[-1] in STATE_SITES):
         return f"{key}: saturate {saturate} (the state sites never saturate)"
     return None
 
 
-def fq_spec(fxp_qconfig: dict, n_layers: int, sites=None, mode: str = "floor") -> np.ndarray:
+def fq_spec(fxp_qconfig: dict, n_layers: int, sites=None, mode: str = "floor", recurrence: str = "scan") -> np.ndarray:
     """The fake-quantisation spec of a forward: one ``FQ_SITE`` entry (bits, exp, mode, saturate) per observer, in
     ``stat_keys`` order, (bits, exp) taken from ``quantiser_of``.  ``sites``: the keys to switch on (None: all of them);
     every other entry is zero, i.e. off.  The state sites ``x_re`` / ``x_im`` never saturate, every other site does.
+    ``recurrence="step"`` puts every state site that is on into mode ``FQ_STEP``: that layer's recurrence
+    rounds at every step (``fq_scan``) in place of quantising the scan's output; both state sites of a layer must then be on.
     ``ValueError`` for an unknown key or mode and for a quantiser the entry would refuse, naming the key."""
     if mode not in FQ_MODES:
         raise ValueError(f"mode must be one of {FQ_MODES}, got {mode!r}")
+    if recurrence not in ("scan", "step"):
+        raise ValueError(f'recurrence must be "scan" or "step", got {recurrence!r}')
     keys = stat_keys(n_layers)
     on = set(keys) if sites is None else set(sites)
     unknown = sorted(on - set(keys))
@@ -535,8 +607,29 @@ def fq_spec(fxp_qconfig: dict, n_layers: int, sites=None, mode: str = "floor") -
         err = _site_error(key, bits, exp, FQ_MODES.index(mode), sat)
         if err or bits == 0:
             raise ValueError(f"fq_spec: {err or key + ': bits 0'}")
-        spec[j] = (bits, exp, FQ_MODES.index(mode), sat)
+        spec[j] = (bits, exp, FQ_STEP if recurrence == "step" and not sat else FQ_MODES.index(mode), sat)
+    err = _step_pair_error(keys, spec)
+    if err:
+        raise ValueError(f"fq_spec: {err}")
     return spec
+
+
+def _step_pair_error(keys, fq) -> Optional[str]:
+    """Why the entries would refuse the step sites of ``fq`` as a whole, or None: a layer's two state sites step together."""
+    step = {k for k, s in zip(keys, fq) if int(s["bits"]) and int(s["mode"]) == FQ_STEP}
+    for k in sorted(step):
+        other = k[:-2] + ("im" if k.endswith("re") else "re")
+        if other not in step:
+            return f"{k}: step mode on one state site of a layer only ({other} is not in step mode)"
+    return None
+
+
+def step_layers(fq, n_layers: int) -> List[int]:
+    """The layers whose state sites ``fq`` puts into step mode."""
+    if fq is None:
+        return []
+    keys = stat_keys(n_layers)
+    return [i for i in range(n_layers) if int(fq[keys.index(f"l{i}.x_re")]["bits"]) and int(fq[keys.index(f"l{i}.x_re")]["mode"]) == FQ_STEP]
 
 
 def _check_fq(fq, keys) -> Optional[np.ndarray]:
@@ -550,50 +643,139 @@ def _check_fq(fq, keys) -> Optional[np.ndarray]:
         err = _site_error(key, int(s["bits"]), int(s["exp"]), int(s["mode"]), int(s["saturate"]))
         if err:
             raise ValueError(f"fq: {err}")
+    err = _step_pair_error(keys, fq)
+    if err:
+        raise ValueError(f"fq: {err}")
     return fq
 
 
-def _real_frames(eng: "FloatEngine", item, fq) -> torch.Tensor:
-    """The model's output on the real frames of one calibration item, flat float64, on the engine's device."""
+WEIGHT_GROUPS = ("ssm.A", "ssm.B", "ssm.C", "ssm.D", "encoder", "out2", "decoder")
+
+
+def quantised_modeldict(modeldict: dict, fxp_qconfig: dict, n_layers: int, groups=None) -> dict:
+    """``modeldict`` with the chosen weight groups (``WEIGHT_GROUPS``; None: all) replaced by the integer model's dequantised
+    values, ``host_from_fp(v, bits, exp) * 2^-exp`` -- the call ``FxpSSM.setup`` / ``FxpDense.setup`` make, on the same float32
+    inputs -- as a new modeldict that ``FloatEngine``, ``pack_blob``, ``synth.float_forward``, ``calibrate`` and ``sensitivity``
+    accept.  ``ssm.A`` / ``ssm.B`` / ``ssm.C`` are quantised AFTER the ZOH discretisation (the reference's
+    complex64 ``discretize_zoh``) and travel in the mixer dict under ``synth.ZOH_KEY``, which ``synth.zoh`` returns in place
+    of recomputing; ``encoder``, ``out2`` and ``decoder`` are a dense layer's kernel and bias.  The input is not modified, a
+    group left out stays bit-identical, and the BatchNorm constants are never touched (the blob holds 1 / sqrt(var + eps)
+    computed by the packer, and the integer BatchNorm's data-dependent exponents are not modelled)."""
+    import copy
+    from .fxpmodel import discretize_zoh, host_from_fp
+
+    groups = set(WEIGHT_GROUPS if groups is None else groups)
+    unknown = sorted(groups - set(WEIGHT_GROUPS))
+    if unknown:
+        raise ValueError(f"unknown weight groups {unknown}; the groups are {WEIGHT_GROUPS}")
+    out = copy.deepcopy(modeldict)
+
+    def deq(v, bits, exp):
+        return (host_from_fp(v, int(bits), int(exp)).astype(F32) / F32(2.0 ** int(exp))).astype(F32)
+
+    def dense(d, q):
+        d["kernel"] = deq(d["kernel"], q["w_bits"], q["w_exp"])
+        d["bias"] = deq(d["bias"], q["b_bits"], q["b_exp"])
+
+    if "encoder" in groups:
+        dense(out["encoder"]["encoder"], fxp_qconfig["encoder"])
+    if "decoder" in groups:
+        dense(out["decoder"], fxp_qconfig["decoder"])
+    for i in range(n_layers):
+        layer = out["encoder"][f"layers_{i}"]
+        blocks = fxp_qconfig["blocks"]
+        blocks = blocks.get(f"layers_{i}", blocks)  # separate exponents per layer (FxpSequenceLayer.setup)
+        w, md = blocks["ssm"]["weights"], layer["mixer"]
+        if "out2" in groups:
+            dense(layer["out2"], blocks["out2"])
+        if "ssm.D" in groups:
+            md["D"] = deq(md["D"], w["D"]["bits"], w["D"]["exp"])
+        if groups & {"ssm.A", "ssm.B", "ssm.C"}:
+            step = np.exp(np.asarray(md["log_step"], dtype=F32)[:, 0]).astype(F32)  # FxpSSM.setup at step_rescale 1
+            lam_bar, B_bar = discretize_zoh(md["Lambda_re"] + 1j * md["Lambda_im"], md["B"][..., 0] + 1j * md["B"][..., 1], step)
+            Cc = (md["C"][..., 0] + 1j * md["C"][..., 1]).astype(np.complex64)
+            hook = dict(md.get(synth.ZOH_KEY, {}))
+            for g, key, v, k in (("ssm.A", "lam_bar", lam_bar, "A"), ("ssm.B", "B_bar", B_bar, "B"), ("ssm.C", "C", Cc, "C")):
+                if g in groups:
+                    hook[key] = np.empty(v.shape, dtype=np.complex64)
+                    hook[key].real = deq(v.real, w[f"{k}_re"]["bits"], w[f"{k}_re"]["exp"])
+                    hook[key].imag = deq(v.imag, w[f"{k}_im"]["bits"], w[f"{k}_im"]["exp"])
+            md[synth.ZOH_KEY] = hook
+    return out
+
+
+def _real_frames(eng: "FloatEngine", item, fq, st=None) -> torch.Tensor:
+    """The model's output on the real frames of one calibration item, flat float64, on the engine's device.  ``st``: the
+    observers to raise -- a device array (``new_stats``) when the engine is on the device, a dict otherwise."""
     pair = _clip_pair(item)
     if pair is None:
         if eng.on_device:
-            return eng.forward_device(eng._to_device(item), fq=fq).double().flatten()
+            return eng.forward_device(eng._to_device(item), st, fq=fq).double().flatten()
         xn = item.detach().cpu().numpy() if isinstance(item, torch.Tensor) else item
-        return torch.from_numpy(eng.forward(np.asarray(xn, dtype=F32), fq=fq)).double().flatten()
+        return torch.from_numpy(eng.forward(np.asarray(xn, dtype=F32), stats=st, fq=fq)).double().flatten()
     if eng.on_device:
         Lmax = int(pair[0].shape[1])
         lens = torch.as_tensor(pair[1]).to(device=eng.device, dtype=torch.int32)
-        y = eng.forward_clips_device(eng._to_device(pair[0]), lens, fq=fq)
+        y = eng.forward_clips_device(eng._to_device(pair[0]), lens, st, fq=fq)
         real = torch.arange(Lmax, device=eng.device)[None, :] < lens.clamp(0, Lmax)[:, None]
         return y[real].double().flatten()  # y's padding is unspecified: select, do not multiply
-    ys = eng.forward_clips(_real_clips(*pair), fq=fq)
+    ys = eng.forward_clips(_real_clips(*pair), stats=st, fq=fq)
     return torch.cat([torch.as_tensor(y).double().flatten() for y in ys]) if ys else torch.zeros(0, dtype=torch.float64)
 
 
 def sensitivity(modeldict: dict, batches: Iterable, fxp_qconfig: dict, n_layers: int, groups=None, mode: str = "floor",
-                engine: Optional[FloatEngine] = None) -> Dict[str, float]:
+                engine: Optional[FloatEngine] = None, recurrence: str = "scan", weights: Optional[dict] = None) -> Dict[str, float]:
     """Which quantiser costs the accuracy: the output SQNR of the float model with one group of sites fake-quantised at a
     time -> {group: sqnr_db} plus ``"all"`` (every group on at once).  ``groups`` maps a name to the observer keys it
     switches on; the default is one group per key.  ``batches`` as for ``calibrate``: (B,L,257) batches, or pairs (x, lens)
     that take the clip entry, of which only the real frames count.  Per batch one plain forward, one forward per group and
     one with all groups run on the same input; sqnr_db = 10 log10(sum y^2 / sum (y_fq - y)^2), both sums accumulated in
-    float64 over all batches (on the device when the engine is); a zero difference gives inf.  What the figure does not
-    hold: quantised weights, and the rounding inside the integer recurrence (the state site quantises the scan's output)."""
+    float64 over all batches (on the device when the engine is); a zero difference gives inf.
+
+    The two things the sites alone do not hold.  ``recurrence="step"`` adds the row ``"recurrence"``: the
+    state sites of every layer alone, in step mode, so the rounding inside the integer recurrence is fed back through the
+    pole.  ``weights=fxp_qconfig`` adds one row per weight group (``WEIGHT_GROUPS``): the plain activations on
+    ``quantised_modeldict(modeldict, weights, n_layers, [group])``, one more engine each.  ``"all"`` is then every site of
+    ``groups``, in step mode when asked for, on the model with all weight groups quantised; every row is measured against
+    the plain forward of ``modeldict``.  A step-mode run whose ``x_re`` / ``x_im`` observers show that it left the domain of
+    ``fq_scan`` (|x| * 2^exp >= 2^24) is named in the list under ``"left_domain"``, a key that is absent otherwise."""
     eng = engine if engine is not None else FloatEngine(modeldict, n_layers)
     keys = stat_keys(n_layers)
     groups = {k: [k] for k in keys} if groups is None else {str(g): list(ks) for g, ks in dict(groups).items()}
-    if "all" in groups:
-        raise ValueError('"all" names the run with every group on; call a group something else')
-    specs = {g: fq_spec(fxp_qconfig, n_layers, ks, mode) for g, ks in groups.items()}
-    specs["all"] = fq_spec(fxp_qconfig, n_layers, [k for ks in groups.values() for k in ks], mode)
+    reserved = {"all", "left_domain"} | ({"recurrence"} if recurrence == "step" else set()) | (set(WEIGHT_GROUPS) if weights else set())
+    if reserved & set(groups):
+        raise ValueError(f"{sorted(reserved & set(groups))} name rows of the result; call a group something else")
+    if recurrence not in ("scan", "step"):
+        raise ValueError(f'recurrence must be "scan" or "step", got {recurrence!r}')
+    states = [f"l{i}.{k}" for i in range(n_layers) for k in STATE_SITES]
+    runs = {g: (eng, fq_spec(fxp_qconfig, n_layers, ks, mode)) for g, ks in groups.items()}  # row -> (engine, spec)
+    if recurrence == "step":
+        runs["recurrence"] = (eng, fq_spec(fxp_qconfig, n_layers, states, mode, recurrence="step"))
+    all_keys = [k for ks in groups.values() for k in ks]
+    all_eng = eng
+    if weights is not None:
+        for g in WEIGHT_GROUPS:
+            runs[g] = (FloatEngine(quantised_modeldict(modeldict, weights, n_layers, [g]), n_layers), None)
+        all_eng = FloatEngine(quantised_modeldict(modeldict, weights, n_layers), n_layers)
+    if recurrence == "step" and set(states) <= set(all_keys):
+        runs["all"] = (all_eng, fq_spec(fxp_qconfig, n_layers, all_keys, mode, recurrence="step"))
+    elif recurrence == "step":  # the groups leave state sites out: "all" holds the groups and the stepping recurrence
+        spec = fq_spec(fxp_qconfig, n_layers, all_keys, mode)
+        step = runs["recurrence"][1]
+        for j, k in enumerate(keys):
+            if k in states:
+                spec[j] = step[j]
+        runs["all"] = (all_eng, spec)
+    else:
+        runs["all"] = (all_eng, fq_spec(fxp_qconfig, n_layers, all_keys, mode))
+    stepping = {g: (e.new_stats() if e.on_device else {}) for g, (e, spec) in runs.items() if step_layers(spec, n_layers)}
     num, den, n = None, {}, 0
     for item in batches:
         y = _real_frames(eng, item, None)
         e = (y * y).sum()
         num = e if num is None else num + e
-        for g, spec in specs.items():
-            d = _real_frames(eng, item, spec) - y
+        for g, (run_eng, spec) in runs.items():
+            d = _real_frames(run_eng, item, spec, stepping.get(g)).to(y.device) - y
             e = (d * d).sum()
             den[g] = e if g not in den else den[g] + e
         n += 1
@@ -601,9 +783,17 @@ def sensitivity(modeldict: dict, batches: Iterable, fxp_qconfig: dict, n_layers:
         raise ValueError("sensitivity needs at least one batch")
     num = float(num)
     out = {}
-    for g in specs:
+    for g in runs:
         d = float(den[g])
         out[g] = math.inf if d == 0.0 else 10.0 * math.log10(num / d) if num > 0.0 else -math.inf
+    left = []
+    for g, st in stepping.items():
+        seen = runs[g][0].stats_dict(st) if isinstance(st, torch.Tensor) else st
+        spec = runs[g][1]
+        if any(seen.get(k, 0.0) * 2.0 ** int(spec[keys.index(k)]["exp"]) >= FQ_STEP_XMAX for k in states if int(spec[keys.index(k)]["bits"])):
+            left.append(g)
+    if left:
+        out["left_domain"] = left
     return out
 
 

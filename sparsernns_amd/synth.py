@@ -135,7 +135,22 @@ def prune_magnitude(modeldict: dict, sparsity: float) -> dict:
 # float dry run (calibration).  Float semantics of the model the fxp path approximates
 # (model/ssm.py:37-50,84-185; model/layers.py GLU "half1", prenorm BN, relufication).
 # --------------------------------------------------------------------------------------
+ZOH_KEY = "zoh_q"  # a mixer dict's optional {"lam_bar", "B_bar", "C"}: values ``zoh`` returns in place of recomputing them
+
+
 def zoh(mixer: dict):
+    """(Lambda_bar, B_bar, C) complex64 of one mixer.  A mixer that carries ``ZOH_KEY`` (``floatmodel.quantised_modeldict``:
+    the integer model quantises A, B and C AFTER the discretisation) gets the entries it holds as they are; without the key
+    nothing changes, to the bit."""
+    lam_bar, B_bar, C = _zoh(mixer)
+    q = mixer.get(ZOH_KEY)
+    if q:
+        lam_bar, B_bar, C = (np.asarray(q[k], dtype=np.complex64) if k in q else v
+                             for k, v in (("lam_bar", lam_bar), ("B_bar", B_bar), ("C", C)))
+    return lam_bar, B_bar, C
+
+
+def _zoh(mixer: dict):
     lam = (mixer["Lambda_re"] + 1j * mixer["Lambda_im"]).astype(np.complex64)
     step = np.exp(mixer["log_step"][:, 0]).astype(F32)
     lam_bar = np.exp(lam * step).astype(np.complex64)
@@ -157,7 +172,9 @@ def float_forward(modeldict: dict, x: np.ndarray, n_layers: int, calibrate_bn: b
     ``fq`` (``floatmodel.fq_spec``): every observed tensor whose site is on is replaced by
     ``floatmodel.fake_quant`` of itself right after it entered its observer, so everything downstream -- the later observers
     included -- sees the quantised value.  The state site acts on the raw scan output, before the complex ReLU; the rounding
-    inside the integer recurrence is not modelled.  ``fq=None`` changes nothing, to the bit."""
+    inside the integer recurrence is modelled only by a layer whose two state sites are in mode ``floatmodel.FQ_STEP``
+    (DESIGN.md §4v): its recurrence is ``floatmodel.fq_scan`` at the sites' exponents, and its state sites do nothing more.
+    ``fq=None`` changes nothing, to the bit."""
 
     def obs(key, v):
         if stats is not None:
@@ -168,10 +185,12 @@ def float_forward(modeldict: dict, x: np.ndarray, n_layers: int, calibrate_bn: b
 
     site = {}
     if fq is not None:
-        from .floatmodel import FQ_MODES, fake_quant, stat_keys
+        from .floatmodel import FQ_MODES, FQ_STEP, _step_pair_error, fake_quant, fq_scan, stat_keys
         keys = stat_keys(n_layers)
         if len(fq) != len(keys):
             raise ValueError(f"fq must have one entry per observer ({len(keys)}), got {len(fq)}")
+        if _step_pair_error(keys, fq):
+            raise ValueError(f"fq: {_step_pair_error(keys, fq)}")
         site = {k: s for k, s in zip(keys, fq) if int(s["bits"])}
 
     def q(key, v):
@@ -208,14 +227,19 @@ def float_forward(modeldict: dict, x: np.ndarray, n_layers: int, calibrate_bn: b
         obs(f"l{i}.Bu_im", Bu.imag)
         if f"l{i}.Bu_re" in site or f"l{i}.Bu_im" in site:
             Bu = (q(f"l{i}.Bu_re", Bu.real) + 1j * q(f"l{i}.Bu_im", Bu.imag)).astype(np.complex64)
-        xs = np.empty_like(Bu)
-        st = np.zeros((Bu.shape[0], Bu.shape[2]), dtype=np.complex64)
-        for t in range(Bu.shape[1]):
-            st = lam_bar * st + Bu[:, t]
-            xs[:, t] = st
+        sx = site.get(f"l{i}.x_re")
+        step = sx is not None and int(sx["mode"]) == FQ_STEP  # both state sites (floatmodel._check_fq): the recurrence rounds
+        if step:
+            xs, _ = fq_scan(lam_bar, Bu, int(sx["exp"]), int(site[f"l{i}.x_im"]["exp"]))
+        else:
+            xs = np.empty_like(Bu)
+            st = np.zeros((Bu.shape[0], Bu.shape[2]), dtype=np.complex64)
+            for t in range(Bu.shape[1]):
+                st = lam_bar * st + Bu[:, t]
+                xs[:, t] = st
         obs(f"l{i}.x_re", xs.real)
         obs(f"l{i}.x_im", xs.imag)
-        if f"l{i}.x_re" in site or f"l{i}.x_im" in site:
+        if not step and (f"l{i}.x_re" in site or f"l{i}.x_im" in site):
             xs = (q(f"l{i}.x_re", xs.real) + 1j * q(f"l{i}.x_im", xs.imag)).astype(np.complex64)
         keep = (xs.real > 0) | ((xs.real == 0) & (xs.imag > 0))
         xs = np.where(keep, xs, 0)
