@@ -755,6 +755,62 @@ int s5fxp_float_model_clips_fq(const s5fxp_float_model *m, const float *x, int n
                                float *stats, const s5fxp_float_fq_site *fq, void *workspace, size_t workspace_bytes,
                                void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Stage errors: two sides of a forward compared where they lie (csrc/stage_err.hpp).  One call compares up to
+ * 4096 PAIRS of planes in two launches, an accumulate kernel and a finalize kernel, whatever the number of pairs, and leaves
+ * per pair the sums behind the verification report's figures (sparseRNNs/fxpreporter.py:12-24, compute_error).
+ *
+ * A pair is a 3-D box (nb, rows, cols) read from two sides with element strides, so a whole (B,L,H) plane, the real or the
+ * imaginary half of an interleaved complex64 plane (column stride 2), one sequence of a batch and one time bucket of all
+ * sequences are all boxes of the planes the engines leave behind, without a copy.  Strides may be any int64, zero and
+ * negative included; the kernels trust them as they trust pointers.
+ *
+ * Arithmetic, for every element (the NumPy statement is verify.stage_errors_host):
+ *   va = (double)a * 2^-a_exp, exact for any int32 (S5FXP_STAGE_I32), or (double)a of a float32 a (S5FXP_STAGE_F32);
+ *   vb = (double)b; an element whose a or b is an infinity or a NaN is counted in n_nonfinite and enters nothing else;
+ *   with S5FXP_STAGE_RELU_A a negative va is replaced by 0; e = |va - vb|, one rounding; where vb != 0, rel = e / |vb|,
+ *   one rounding.  -0 equals +0.  sum_sq adds the rounded squares e * e, sum_ref_sq the exact squares vb * vb.
+ * hist_abs / hist_rel bin (float)e / (float)rel by the float32 exponent field with the rule of S5FXP_FLOAT_HIST_BINS above
+ * (hist_rel over the elements with vb != 0): each brackets its median to a factor of two and counts the errors at or above
+ * any power of two 2^-39 .. 2^23.
+ * Counts, histograms and the two maxima are exact.  The four sums are taken in double, per thread, then lanes, waves and
+ * workgroups in a fixed order, with no floating-point atomics: two calls give identical bits, and any order of summing n
+ * non-negative doubles is within (n - 1) * 2^-53 relative of the exact sum.
+ *
+ * pairs_host: HOST memory, read before the entry returns.  out_dev: n_pairs records in device memory, 8-byte aligned.
+ * workspace: s5fxp_stage_err_workspace_bytes(n_pairs) bytes of device memory, 256-byte aligned, overwritten by the call
+ * (0 for n_pairs outside 1..4096).  A pair with a zero extent is legal (its pointers may be NULL) and gets an all-zero record.
+ * S5FXP_EBADARG, before the device is touched: a null pairs_host / out_dev / workspace, or a null a / b of a pair that has
+ * elements; n_pairs outside 1..4096; an unknown kind or unknown flag bits; a_exp outside 0..40 on an I32 pair; a negative
+ * extent; and the wrap rule: a workgroup counts in 32-bit words, so a pair of more than (2^32 - 256) * W elements is refused,
+ * W = min(512, max(1, 16384 / n_pairs)) the most workgroups the call gives a pair.  S5FXP_EWORKSPACE for a workspace that is
+ * too small. */
+enum { S5FXP_STAGE_I32 = 0, S5FXP_STAGE_F32 = 1 }; /* s5fxp_stage_pair.a_kind */
+enum { S5FXP_STAGE_RELU_A = 1 };                   /* s5fxp_stage_pair.flags */
+typedef struct {
+    const void *a;       /* device; int32 or float32 by a_kind */
+    int32_t a_kind;
+    int32_t a_exp;       /* S5FXP_STAGE_I32: value = a * 2^-a_exp; S5FXP_STAGE_F32: ignored */
+    const float *b;      /* device; the reference side ("xhat"), float32 */
+    int64_t a_stride[3]; /* elements; batch, row, column */
+    int64_t b_stride[3];
+    int32_t nb, rows, cols;
+    int32_t flags;       /* S5FXP_STAGE_RELU_A: max(a, 0) before comparing */
+} s5fxp_stage_pair;      /* 88 bytes */
+typedef struct {
+    uint64_t n;             /* elements of the box */
+    uint64_t n_nonfinite;   /* of them not compared */
+    uint64_t n_equal;       /* compared with e == 0 */
+    uint64_t n_ref_nonzero; /* compared with vb != 0 */
+    double sum_abs, sum_sq, max_abs; /* of e */
+    double sum_ref_sq;               /* of vb, over the compared elements */
+    double sum_rel, max_rel;         /* of rel */
+    uint64_t hist_abs[S5FXP_FLOAT_HIST_BINS], hist_rel[S5FXP_FLOAT_HIST_BINS];
+} s5fxp_stage_err_rec;      /* 1104 bytes */
+size_t s5fxp_stage_err_workspace_bytes(int n_pairs);
+int s5fxp_stage_err(const s5fxp_stage_pair *pairs_host, int n_pairs, s5fxp_stage_err_rec *out_dev, void *workspace,
+                    size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,24 @@ class FloatModelDesc(C.Structure):
         ("enc_w", F32P), ("enc_b", F32P), ("layers", C.POINTER(FloatLayerDesc)), ("dec_w", F32P), ("dec_b", F32P)]
 
 
+STAGE_I32, STAGE_F32 = 0, 1   # s5fxp_stage_pair.a_kind
+STAGE_RELU_A = 1              # s5fxp_stage_pair.flags
+STAGE_MAX_PAIRS = 4096
+
+
+class StagePair(C.Structure):
+    """s5fxp_stage_pair: one pair of strided (nb, rows, cols) boxes (88 bytes)."""
+    _fields_ = [("a", VOIDP), ("a_kind", C.c_int32), ("a_exp", C.c_int32), ("b", VOIDP), ("a_stride", C.c_int64 * 3),
+                ("b_stride", C.c_int64 * 3), ("nb", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("flags", C.c_int32)]
+
+
+class StageErrRec(C.Structure):
+    """s5fxp_stage_err_rec: the sums of one pair (1104 bytes, 138 8-byte words)."""
+    _fields_ = [(n, C.c_uint64) for n in ("n", "n_nonfinite", "n_equal", "n_ref_nonzero")] + [
+        (n, C.c_double) for n in ("sum_abs", "sum_sq", "max_abs", "sum_ref_sq", "sum_rel", "max_rel")] + [
+        ("hist_abs", C.c_uint64 * 64), ("hist_rel", C.c_uint64 * 64)]
+
+
 class S5FxpError(RuntimeError):
     pass
 
@@ -190,6 +208,8 @@ def _load():
         "s5fxp_float_model_clips": (i, [p, p, i, i, p, p, p, p, p, C.c_size_t, p]),
         "s5fxp_float_model_forward_fq": (i, [p, p, i, i, p, p, p, p, p, C.c_size_t, p]),
         "s5fxp_float_model_clips_fq": (i, [p, p, i, i, p, p, p, p, p, C.c_size_t, p]),
+        "s5fxp_stage_err_workspace_bytes": (C.c_size_t, [i]),
+        "s5fxp_stage_err": (i, [C.POINTER(StagePair), i, p, p, C.c_size_t, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale: rebuild
@@ -213,7 +233,8 @@ EXPORTED_SYMBOLS = ("s5fxp_version s5fxp_strerror s5fxp_from_fp s5fxp_to_float s
                     "s5fxp_float_model_blob_bytes s5fxp_float_model_pack s5fxp_float_model_create s5fxp_float_model_destroy "
                     "s5fxp_float_workspace_bytes s5fxp_float_trace_bytes s5fxp_float_model_forward "
                     "s5fxp_float_model_forward_hist s5fxp_float_model_clips "
-                    "s5fxp_float_model_forward_fq s5fxp_float_model_clips_fq").split()
+                    "s5fxp_float_model_forward_fq s5fxp_float_model_clips_fq "
+                    "s5fxp_stage_err_workspace_bytes s5fxp_stage_err").split()
 
 
 def check(rc: int, what: str = "") -> None:

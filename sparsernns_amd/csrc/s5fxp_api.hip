@@ -11,12 +11,14 @@
 #include "audio_stream.hpp"
 #include "audio_score.hpp"
 #include "float_model.hpp"
+#include "stage_err.hpp"
 
 #include <hip/hip_ext.h>
 
 #include <algorithm>
 #include <array>
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1646,6 +1648,62 @@ extern "C" int s5fxp_float_model_clips_fq(const s5fxp_float_model *m, const floa
                                           void *stream)
 {
     return float_forward<true>(m, x, n, Lmax, lens, y, stats, nullptr, fq, nullptr, workspace, workspace_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Stage errors (stage_err.hpp): up to 4096 pairs of strided boxes compared in two launches.  The workspace holds
+// the device form of the descriptors (one stream-ordered copy), then one partial record per workgroup.
+namespace {
+constexpr size_t stage_desc_bytes(int n_pairs) { return ((size_t)n_pairs * sizeof(stage::DevPair) + 255) / 256 * 256; }
+static_assert(sizeof(s5fxp_stage_err_rec) == stage::REC_WORDS * 8, "s5fxp_stage_err_rec is REC_WORDS 8-byte words");
+} // namespace
+
+extern "C" size_t s5fxp_stage_err_workspace_bytes(int n_pairs)
+{
+    if (n_pairs < 1 || n_pairs > 4096) return 0;
+    return stage_desc_bytes(n_pairs) + (size_t)n_pairs * stage::stage_wgs_cap(n_pairs) * sizeof(s5fxp_stage_err_rec);
+}
+
+extern "C" int s5fxp_stage_err(const s5fxp_stage_pair *pairs_host, int n_pairs, s5fxp_stage_err_rec *out_dev, void *workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    if (!pairs_host || !out_dev || !workspace || n_pairs < 1 || n_pairs > 4096) return S5FXP_EBADARG;
+    const int cap = stage::stage_wgs_cap(n_pairs);
+    std::vector<stage::DevPair> dev((size_t)n_pairs);
+    uint64_t n_max = 0;
+    for (int i = 0; i < n_pairs; ++i) {
+        const s5fxp_stage_pair &p = pairs_host[i];
+        if (p.a_kind != S5FXP_STAGE_I32 && p.a_kind != S5FXP_STAGE_F32) return S5FXP_EBADARG;
+        if (p.flags & ~S5FXP_STAGE_RELU_A) return S5FXP_EBADARG;
+        if (p.a_kind == S5FXP_STAGE_I32 && (p.a_exp < 0 || p.a_exp > 40)) return S5FXP_EBADARG;
+        if (p.nb < 0 || p.rows < 0 || p.cols < 0) return S5FXP_EBADARG;
+        const unsigned __int128 n = (unsigned __int128)p.nb * (unsigned)p.rows * (unsigned)p.cols;
+        if (n && (!p.a || !p.b)) return S5FXP_EBADARG;
+        // the wrap rule: a workgroup's share of the pair, at the most workgroups this call can use, stays below 2^32
+        if (n > (unsigned __int128)cap * 0xffffff00ull) return S5FXP_EBADARG;
+        stage::DevPair &d = dev[i];
+        d.a = static_cast<const uint32_t *>(p.a), d.b = p.b;
+        for (int k = 0; k < 3; ++k) d.as[k] = p.a_stride[k], d.bs[k] = p.b_stride[k];
+        d.n = (uint64_t)n;
+        d.scale = p.a_kind == S5FXP_STAGE_I32 ? std::ldexp(1.0, -p.a_exp) : 1.0;
+        d.rows = (uint32_t)p.rows, d.cols = (uint32_t)p.cols;
+        d.f32 = p.a_kind == S5FXP_STAGE_F32, d.relu = (p.flags & S5FXP_STAGE_RELU_A) != 0;
+        n_max = std::max(n_max, d.n);
+    }
+    if (workspace_bytes < s5fxp_stage_err_workspace_bytes(n_pairs)) return S5FXP_EWORKSPACE;
+    // workgroups per pair from the largest pair: fewer than `cap` only while every share is WG_MIN_ELEMS at most
+    const uint64_t want = (n_max + stage::WG_MIN_ELEMS - 1) / stage::WG_MIN_ELEMS;
+    const int wgs = (int)std::min<uint64_t>((uint64_t)cap, std::max<uint64_t>(want, 1));
+    char *ws = static_cast<char *>(workspace);
+    auto *partials = reinterpret_cast<unsigned long long *>(ws + stage_desc_bytes(n_pairs));
+    // pageable-memory async copies are staged by the runtime before returning, so `dev` may go
+    if (const int rc = hip_rc(hipMemcpyAsync(ws, dev.data(), dev.size() * sizeof(stage::DevPair), hipMemcpyHostToDevice, S(stream))))
+        return rc;
+    hipLaunchKernelGGL(stage::k_stage_err, dim3((unsigned)wgs, (unsigned)n_pairs), dim3(stage::TPB), 0, S(stream),
+                       reinterpret_cast<const stage::DevPair *>(ws), partials);
+    hipLaunchKernelGGL(stage::k_stage_err_finalize, dim3((unsigned)n_pairs), dim3(stage::TPB), 0, S(stream), partials, wgs,
+                       reinterpret_cast<unsigned long long *>(out_dev));
+    return launch_rc();
 }
 
 #ifdef S5_PHASE_PROF

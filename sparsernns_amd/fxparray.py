@@ -321,7 +321,8 @@ def fxp_mul(op1, op2, result_exp: Optional[Union[int, str]] = None, result_exp_f
     if result_bits is None:
         result_bits = result_bits_fn(op1.bits, op2.bits)
     a, b = op1.data.contiguous(), op2.data.contiguous()
-    if b.numel() > a.numel():
+    # the broadcast operand second; at equal sizes that is the one of lower rank (D (H,) times a u of ONE frame, (1,1,H))
+    if b.numel() > a.numel() or (b.numel() == a.numel() and b.ndim > a.ndim):
         a, b, op1, op2 = b, a, op2, op1
     ylen = _bcast_len(a, b)
     out = torch.empty_like(a)

@@ -60,6 +60,20 @@ class Reporter:
             self.results_data.append(dict(name=name + suffix, compared=f"{xrecname} vs {xhatname}", line=line,
                                           xhat_absmax=float(np.max(np.abs(h))) if h.size else 0.0, **m))
 
+    def add_block_metrics(self, name: str, metrics: Dict[str, float], verbose: bool = True, compared: str = "fxp vs float") -> None:
+        """Appends a row whose figures were computed elsewhere (``verify.stage_errors``: the whole batch, on the device).
+        ``metrics`` holds any of ``METRICS`` and whatever else the row should keep; a metric it lacks is NaN in the table (the
+        device rows bracket their medians, ``*_med_lo`` / ``*_med_hi``, instead of computing them)."""
+        m = {k: float(metrics.get(k, float("nan"))) for k in METRICS}
+        med = lambda p: (f"{metrics[p + '_lo']:.3e}..{metrics[p + '_hi']:.3e}" if p + "_lo" in metrics else f"{m[p]:.3e}")
+        line = (f"abs err: mean {m['abs_error_mean']:.3e}, std {m['abs_error_std']:.3e}, max {m['abs_error_max']:.3e}, "
+                f"med {med('abs_error_med')} -- rel err: mean {m['rel_error_mean']:.3e}, med {med('rel_error_med')}, "
+                f"max {m['rel_error_max']:.3e}")
+        if verbose:
+            print(f"{name:<46} {line}")
+        extra = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in metrics.items() if k not in METRICS}
+        self.results_data.append({**extra, "name": name, "compared": compared, "line": line, **m})
+
     def worst(self, metric: str = "rel_error_med") -> dict:
         return max(self.results_data, key=lambda r: r[metric])
 

@@ -23,6 +23,9 @@ replaced by interchange files this repo can read:
                          A.npz is the float side as an npz tree (the reference's ``activations_fp.pkl`` through
                          tools/reference_pickles_to_npz.py); without it the float forward of this package runs on the
                          same float parameters (--synthetic, --params)
+  --verify --stages device [--stage-by stage|sequence|time]
+                         after that report of sequence 0: every stage of the WHOLE batch, compared on the device in one
+                         ``s5fxp_stage_err`` call (sparsernns_amd/verify.py; stages_device.md / .json under --report)
 
 Flags kept from the reference where they mean the same (fxprun.py:98-269): --quantization, --seq_len, --bsz, --export,
 --separate_exponents, and --params_fname / --stats_fname / --inputs_fname / --activations_fname as aliases of the file
@@ -100,6 +103,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--float-side", dest="float_side", choices=("numpy", "device"), default="numpy",
                     help="--verify without --activations: where the float model's intermediates come from: synth.float_forward on "
                          "the host (numpy) or floatmodel.FloatEngine's HIP kernels (device)")
+    ap.add_argument("--stages", choices=("host", "device"), default="host",
+                    help="--verify: device = after the report of sequence 0, compare every stage of the WHOLE batch on the device "
+                         "(verify.compare_engines against floatmodel.FloatEngine; stages_device.md / .json under --report)")
+    ap.add_argument("--stage-by", dest="stage_by", choices=("stage", "sequence", "time"), default="stage",
+                    help="--stages device: one row per stage, per stage and sequence, or per stage and time bucket")
     ap.add_argument("--export", type=str, default=None, help="write the integer model as PREFIX.npz / PREFIX.json")
     ap.add_argument("--check-golden", action="store_true",
                     help="--model only: the npz also holds an integer input `x` and the output `y` some other implementation "
@@ -224,6 +232,23 @@ def main(argv=None) -> int:
         w = rep.worst()
         print(f"[fxprun] verification report: {len(rep.results_data)} stages; largest median relative error {w['rel_error_med']:.3%} "
               f"at {w['name']}" + (f"; written to {args.report}/report.md" if args.report else ""))
+        if args.stages == "device":
+            from . import verify
+            from .floatmodel import FloatEngine
+            feng = FloatEngine(md, dims["n_layers"])
+            if not feng.on_device:
+                print("[fxprun] --stages device: the float kernels do not serve this model", file=sys.stderr)
+                return 2
+            rows = verify.compare_engines(eng, feng, xf, qc, by=args.stage_by)
+            drep = Reporter(None, title="fixed point vs float, stage by stage, whole batch on the device")
+            for r in rows:
+                part = f" [seq {r['sequence']}]" if "sequence" in r else f" [t {r['t0']}..{r['t1'] - 1}]" if "t0" in r else ""
+                drep.add_block_metrics(r["name"] + part, r)
+            if args.report:
+                verify.save_table(rows, args.report, header=dict(quantization=args.quantization, batch=B, seq_len=L, by=args.stage_by,
+                                                                 float_side="sparsernns_amd.floatmodel.FloatEngine (HIP kernels)"))
+            print(f"[fxprun] device stage table: {len(rows)} rows over {B} x {L} frames in one s5fxp_stage_err call"
+                  + (f"; written to {args.report}/stages_device.md" if args.report else ""))
 
     if args.export:
         ex = (model.export() if model is not None else export)
