@@ -189,9 +189,10 @@ int s5fxp_mask_istft_clips(const float *audio, const float *mask, int n, int64_t
  * each be NULL: the plane is then never stored.  si_snr, mag_mse, loss: (B) float32; mag_mse and loss may be NULL.  The sums
  * behind the scores are taken in double on the float32 values the planes would hold (clean_mag bit for bit
  * s5fxp_stft_mag's), in a fixed order, without atomics: two calls give identical bits, with or without the planes.
- * workspace: s5fxp_score_workspace_bytes(B, T) bytes of device memory, 8-byte aligned, overwritten by the call (0 for B < 1
- * or T < 512).  S5FXP_EBADARG for a null audio, clean, workspace or si_snr, B < 1 or mask_exp outside 0..31;
- * S5FXP_EUNSUPPORTED for T < 512; S5FXP_EWORKSPACE for a workspace that is too small -- all before the device is touched. */
+ * workspace: s5fxp_score_workspace_bytes(B, T) bytes of device memory, 8-byte aligned, overwritten by the call (0 for B < 1,
+ * T < 512 or a grid beyond 2^31 - 1, which the entries refuse).  S5FXP_EBADARG for a null audio, clean, workspace or
+ * si_snr, B < 1 or mask_exp outside 0..31;
+ * S5FXP_EUNSUPPORTED for T < 512 or such a grid; S5FXP_EWORKSPACE for a workspace that is too small -- all before the device is touched. */
 size_t s5fxp_score_workspace_bytes(int B, int64_t T);
 int s5fxp_mask_istft_score(const float *audio, const float *clean, const float *mask, int B, int64_t T, float lam,
                            float *out, float *cleaned_mag, void *workspace, size_t workspace_bytes,

@@ -39,6 +39,8 @@ inline unsigned ew_grid(int64_t n)
     return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
 inline bool shift_ok(int s) { return s >= 0 && s <= 31; }
+// tiles * n workgroups fit a grid's x extent (tiles >= 0, n >= 1; the product itself may not fit 64 bits)
+inline bool grid_fits(int64_t tiles, int64_t n) { return tiles <= 0x7fffffffll / n; }
 
 // column split of the frame-tiled matmul: 4 waves x mw columns, mw % 4 == 0
 inline int mw_for(int M) { return ((M + 3) / 4 + 3) / 4 * 4; }
@@ -275,7 +277,7 @@ extern "C" int s5fxp_assoc_scan_c64(const float *lambda, const float *bu, float 
 {
     if (!lambda || !bu || !xs || B < 0 || L < 0 || P < 1) return S5FXP_EBADARG;
     if (B == 0 || L == 0) return S5FXP_OK;
-    const int64_t grid = (int64_t)B * ((P + ASSOC_PT - 1) / ASSOC_PT);
+    const int64_t grid = (int64_t)B * (((int64_t)P + ASSOC_PT - 1) / ASSOC_PT);
     if (grid > 0x7fffffffll) return S5FXP_EBADARG;
     ScanAssocArgs a{};
     a.lambda = reinterpret_cast<const float2 *>(lambda); a.bu = reinterpret_cast<const float2 *>(bu);
@@ -302,7 +304,7 @@ extern "C" int s5fxp_fq_scan_c64(const float *lambda, const float *bu, float *xs
 }
 
 // The audio steps either side of the model (audio_stft.hpp).  n_seg = ceil(T / 128) + 1 frames for T >= 512.
-extern "C" int64_t s5fxp_stft_frames(int64_t T) { return T < stft::NFFT ? -1 : (T + stft::HOP - 1) / stft::HOP + 1; }
+extern "C" int64_t s5fxp_stft_frames(int64_t T) { return T < stft::NFFT ? -1 : T / stft::HOP + (T % stft::HOP != 0) + 1; }
 
 // One checked launch per direction: the arguments and the tile arithmetic the float and the int16 entry share.  extra_ok: the
 // boundary's own argument checks; launch(grid, n_seg, tiles) enqueues its kernel.
@@ -313,7 +315,7 @@ int stft_mag_entry(const float *audio, const void *x, int B, int64_t T, bool ext
     if (!audio || !x || B < 1 || !extra_ok) return S5FXP_EBADARG;
     if (T < stft::NFFT) return S5FXP_EUNSUPPORTED;
     const int64_t n_seg = s5fxp_stft_frames(T), tiles = (n_seg + stft::FR - 1) / stft::FR;
-    if (tiles * B > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
+    if (!grid_fits(tiles, B)) return S5FXP_EUNSUPPORTED;
     launch(dim3((unsigned)(tiles * B)), n_seg, (int)tiles);
     return launch_rc();
 }
@@ -324,7 +326,7 @@ int mask_istft_entry(const float *audio, const float *out, int B, int64_t T, boo
     if (!audio || !out || B < 1 || !extra_ok) return S5FXP_EBADARG;
     if (T < stft::NFFT) return S5FXP_EUNSUPPORTED;
     const int64_t n_seg = s5fxp_stft_frames(T), tiles = (n_seg - 1 + stft::OH - 1) / stft::OH;
-    if (tiles * B > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
+    if (!grid_fits(tiles, B)) return S5FXP_EUNSUPPORTED;
     launch(dim3((unsigned)(tiles * B)), n_seg, (int)tiles);
     return launch_rc();
 }
@@ -401,6 +403,7 @@ extern "C" size_t s5fxp_score_workspace_bytes(int B, int64_t T)
 {
     if (B < 1 || T < stft::NFFT) return 0;
     const int64_t tiles = (s5fxp_stft_frames(T) - 1 + stft::OH - 1) / stft::OH;
+    if (!grid_fits(tiles, B)) return 0; // s5fxp_mask_istft_score refuses it; the size would not fit a size_t either
     return (size_t)B * (size_t)tiles * stft::NSUM * sizeof(double);
 }
 
@@ -412,7 +415,7 @@ int score_entry(const float *audio, const float *clean, int B, int64_t T, float 
     if (!audio || !clean || !workspace || !si_snr || B < 1 || !extra_ok) return S5FXP_EBADARG;
     if (T < stft::NFFT) return S5FXP_EUNSUPPORTED;
     const int64_t n_seg = s5fxp_stft_frames(T), tiles = (n_seg - 1 + stft::OH - 1) / stft::OH;
-    if (tiles * B > 0x7fffffffll) return S5FXP_EUNSUPPORTED;
+    if (!grid_fits(tiles, B)) return S5FXP_EUNSUPPORTED;
     if (workspace_bytes < s5fxp_score_workspace_bytes(B, T)) return S5FXP_EWORKSPACE;
     launch(dim3((unsigned)(tiles * B)), n_seg, (int)tiles);
     hipLaunchKernelGGL(stft::k_score_finalize, dim3((unsigned)B), dim3(64), 0, S(stream), static_cast<const double *>(workspace),
@@ -480,8 +483,8 @@ extern "C" int64_t s5fxp_stream_frames(int64_t hops_before, int c)
 extern "C" int64_t s5fxp_stream_out_hops(int64_t hops_before, int c, int final)
 {
     if (hops_before < 0 || c < 1 || c > stft::STREAM_MAX_HOPS) return -1;
-    const int64_t ready = hops_before + c - 3;
-    return (ready < 0 ? 0 : ready < c ? ready : c) + (final ? 1 : 0);
+    const int64_t ready = hops_before >= 3 ? c : hops_before + c - 3; // min(c, .): hops_before + c may not fit
+    return (ready < 0 ? 0 : ready) + (final ? 1 : 0);
 }
 
 extern "C" int s5fxp_stream_stft(const float *audio, int n, int c, int64_t hops_before, float sub, void *state, float *x,
@@ -603,7 +606,11 @@ struct s5fxp_model {
     std::vector<LayerDev> layers;
     int flags = 0;
     ModelCfg cfg;
-    FastModel *fast = nullptr;
+    FastModel *fast = nullptr; // owned
+    s5fxp_model() = default;
+    s5fxp_model(const s5fxp_model &) = delete;
+    s5fxp_model &operator=(const s5fxp_model &) = delete;
+    ~s5fxp_model(); // behind s5fxp_fast.hpp, where FastModel is complete
 };
 
 namespace {
@@ -611,11 +618,12 @@ namespace {
 struct Packer {
     size_t off = 0;
     char *host = nullptr; // nullptr: size pass
-    char *dev = nullptr;
+    char *dev = nullptr;  // nullptr: size pass, the addresses handed out are null
+    const char *addr() const { return dev ? dev + off : nullptr; }
     const int32_t *put(const int32_t *src, size_t n)
     {
         const size_t bytes = n * sizeof(int32_t);
-        const int32_t *d = reinterpret_cast<const int32_t *>(dev + off);
+        const int32_t *d = reinterpret_cast<const int32_t *>(addr());
         if (host) std::memcpy(host + off, src, bytes);
         off = (off + bytes + 255) & ~(size_t)255;
         return d;
@@ -800,6 +808,8 @@ int bn_exponent_ops(Reduce reduce, const BnArgs &bn, LayerDyn *d, int32_t *statu
 #include "s5fxp_step.hpp"
 #include "s5fxp_clip.hpp"
 
+s5fxp_model::~s5fxp_model() { delete fast; }
+
 namespace {
 
 // m == nullptr: size pass (an upper bound: it includes the MFMA-path tensors whenever the model is eligible)
@@ -873,11 +883,7 @@ extern "C" int s5fxp_model_create(const s5fxp_model_desc *desc, void *dev_blob, 
     return S5FXP_OK;
 }
 
-extern "C" void s5fxp_model_destroy(s5fxp_model *m)
-{
-    if (m) delete m->fast;
-    delete m;
-}
+extern "C" void s5fxp_model_destroy(s5fxp_model *m) { delete m; }
 extern "C" int s5fxp_model_out_exp(const s5fxp_model *m) { return m ? m->dec.out_exp : 0; }
 extern "C" int s5fxp_model_out_bits(const s5fxp_model *m) { return m ? m->dec.out_bits : 0; }
 /* 1 if the int8-MFMA path was packed for this model (it also needs L % 4 == 0 at run time) */
@@ -1320,11 +1326,11 @@ int float_validate(const s5fxp_float_model_desc *d)
 struct FloatPacker {
     size_t off = 0; // in floats
     float *host = nullptr;
-    const float *dev = nullptr;
+    const float *dev = nullptr; // nullptr: size pass, the addresses handed out are null
     float *take(size_t n, const float *&d)
     {
         float *h = host ? host + off : nullptr;
-        d = dev + off;
+        d = dev ? dev + off : nullptr;
         off = (off + n + 63) & ~(size_t)63;
         return h;
     }

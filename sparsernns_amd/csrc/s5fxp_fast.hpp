@@ -47,7 +47,7 @@ namespace {
 
 inline const void *put_raw(Packer &p, const void *src, size_t bytes)
 {
-    const void *d = p.dev + p.off;
+    const void *d = p.addr();
     if (p.host) std::memcpy(p.host + p.off, src, bytes);
     p.off = (p.off + bytes + 255) & ~(size_t)255;
     return d;

@@ -43,7 +43,7 @@ constexpr int FQS_BLK = 16; // steps per register block: 16 float2 in flight beh
 // fit 32 bits.
 inline bool fqs_span_ok(long long L, long long P)
 {
-    return (64 / P + 2) * L * P * (long long)sizeof(float2) < (1ll << 32);
+    return (unsigned __int128)(64 / P + 2) * L * P * sizeof(float2) < ((unsigned __int128)1 << 32); // L * P alone may pass 2^62
 }
 
 // The translation unit is built with the compiler's default contraction, under which __fmul_rn is a plain product that the
