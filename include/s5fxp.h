@@ -363,7 +363,10 @@ int s5fxp_model_create(const s5fxp_model_desc *desc, void *dev_blob, size_t blob
                        s5fxp_model **out);
 void s5fxp_model_destroy(s5fxp_model *m);
 
-/* Device workspace for one forward of B sequences of L frames. */
+/* Device workspace for one forward of B sequences of L frames.  0: a null model, B < 1 or L < 1, or a size that does not fit
+ * a size_t (the sum is formed with checked arithmetic and never wraps; it grows with B and with L, so the answer does not
+ * return from 0 to a size as either grows).  The forwards refuse such a (B, L), and a grouped call whose G-fold of this
+ * value does not fit a size_t, with S5FXP_EWORKSPACE before the device is touched, whatever workspace_bytes claims. */
 size_t s5fxp_workspace_bytes(const s5fxp_model *m, int B, int L);
 
 /* Number of int32 words in the device status buffer, and its layout:
@@ -469,7 +472,8 @@ int s5fxp_model_forward_f32(const s5fxp_model *m, const float *x, int x_bits, in
                             void *workspace, size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces,
                             const s5fxp_forward_opts *opts, void *stream);
 /* Device workspace for one s5fxp_model_forward_f32 of B sequences of L frames: s5fxp_workspace_bytes for a model on the fused
- * path, plus the staged int32 input and output for a generic one.  0: bad argument. */
+ * path, plus the staged int32 input and output for a generic one.  0: bad argument, or a size that does not fit a size_t
+ * (as s5fxp_workspace_bytes; the entry then returns S5FXP_EWORKSPACE). */
 size_t s5fxp_workspace_bytes_f32(const s5fxp_model *m, int B, int L);
 
 /* The same forward with an int16 model boundary: x (B,L,d_in) int16 device at (x_bits 1..16, x_exp), y (B,L,d_out) int16 device.
@@ -484,7 +488,8 @@ int s5fxp_model_forward_i16(const s5fxp_model *m, const int16_t *x, int x_bits, 
                             void *workspace, size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces,
                             const s5fxp_forward_opts *opts, void *stream);
 /* Device workspace for one s5fxp_model_forward_i16: s5fxp_workspace_bytes for a model on the fused path, plus the staged int32
- * input and output for a generic one.  0: bad argument. */
+ * input and output for a generic one.  0: bad argument, or a size that does not fit a size_t (as s5fxp_workspace_bytes; the
+ * entry then returns S5FXP_EWORKSPACE). */
 size_t s5fxp_workspace_bytes_i16(const s5fxp_model *m, int B, int L);
 
 /* Environment (experiments and tests only; read ONCE by s5fxp_model_create and stored in the handle, never by a forward):
@@ -570,7 +575,9 @@ int s5fxp_model_step_ragged_f32(const s5fxp_model *m, const float *x, int x_bits
  * or Lmax > 2^20, x_bits outside 1..32 (and x_exp outside 0..31 for _f32) or workspace_bytes too small;
  * S5FXP_EUNSUPPORTED for a model that s5fxp_model_is_fast() does not report; S5FXP_ENEGSHIFT for the static shifts
  * s5fxp_model_step checks.  No traces, no cross-rank hook, no flags, no redo, no B > 1. */
-size_t s5fxp_clips_workspace_bytes(const s5fxp_model *m, int n, int Lmax); /* 0: bad argument */
+/* 0: bad argument, or a size that does not fit a size_t (the entries then return S5FXP_EBADARG, as for any workspace that
+ * is too small) */
+size_t s5fxp_clips_workspace_bytes(const s5fxp_model *m, int n, int Lmax);
 /* 1: s5fxp_model_clips serves this model at Lmax; 0: it does not (generic model, Lmax > 2^20); -1: bad argument */
 int s5fxp_model_clips_ok(const s5fxp_model *m, int Lmax);
 int s5fxp_model_clips(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int n, int Lmax, const int32_t *lens,
@@ -667,7 +674,8 @@ void s5fxp_float_model_destroy(s5fxp_float_model *m);
 
 /* Device workspace of one forward: two (N,H) planes for the layer input and output and the (N,P) complex64 planes Bu and xs,
  * N = B * L -- one pair shared by all layers, or with trace != 0 one pair per layer, kept: floats
- * [2 N H][layer 0: Bu, xs][layer 1: ...].  0: bad argument. */
+ * [2 N H][layer 0: Bu, xs][layer 1: ...].  0: bad argument, or a size that does not fit a size_t (checked arithmetic, never
+ * a wrapped value); the forwards refuse such a (B, L) with S5FXP_EWORKSPACE before the device is touched. */
 size_t s5fxp_float_workspace_bytes(const s5fxp_float_model *m, int B, int L, int trace);
 /* Bytes of the trace buffer: per layer five (N,H) float32 planes u, y, g_in, g, h' (the layer's output), layer after layer. */
 size_t s5fxp_float_trace_bytes(const s5fxp_float_model *m, int B, int L);

@@ -42,6 +42,14 @@ inline bool shift_ok(int s) { return s >= 0 && s <= 31; }
 // tiles * n workgroups fit a grid's x extent (tiles >= 0, n >= 1; the product itself may not fit 64 bits)
 inline bool grid_fits(int64_t tiles, int64_t n) { return tiles <= 0x7fffffffll / n; }
 
+// Workspace sizes are formed in 128 bits, where no product of three ints and a few small factors can wrap, and narrowed once:
+// a size that does not fit a size_t becomes 0, which every size query returns for "no such workspace" and every entry refuses
+using wide_t = unsigned __int128;
+inline wide_t wide_al256(wide_t v) { return (v + 255) & ~(wide_t)255; }
+inline size_t fit_size(wide_t v) { return v > (wide_t)SIZE_MAX ? 0 : (size_t)v; }
+// time blocks (4 steps each) of an L-frame sequence, padded to a multiple of depth; L + 3 itself may not fit an int
+inline int64_t time_blocks(int L, int depth) { return (((int64_t)L + 3) / 4 + depth - 1) / depth * depth; }
+
 // column split of the frame-tiled matmul: 4 waves x mw columns, mw % 4 == 0
 inline int mw_for(int M) { return ((M + 3) / 4 + 3) / 4 * 4; }
 constexpr int MW_LIMIT = 68;
@@ -918,21 +926,23 @@ struct WsLayout {
 };
 WsLayout ws_layout(const s5fxp_model *m, int B, int L)
 {
-    const size_t N = (size_t)B * L;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     WsLayout w{};
-    w.TB = ((L + 3) / 4 + SCAN_DEPTH - 1) / SCAN_DEPTH * SCAN_DEPTH;
-    size_t off = 0;
-    const size_t nh = al(N * m->H * 4);
+    w.TB = (int)time_blocks(L, SCAN_DEPTH);
+    // the planes' sizes in 128 bits; a layout whose end does not fit a size_t has total == 0 and no meaningful offsets
+    const wide_t nh_w = wide_al256((wide_t)B * L * m->H * 4);
     // + SCAN_DEPTH blocks of padding: the recurrence kernel's ring buffer reads ahead of the last block
-    const size_t ns = al(((size_t)B * w.TB + SCAN_DEPTH) * (m->P ? m->P : 1) * 8 * 4);
+    const wide_t ns_w = wide_al256(((wide_t)B * w.TB + SCAN_DEPTH) * (m->P ? m->P : 1) * 8 * 4);
+    const size_t dyn_b = (size_t)wide_al256(sizeof(LayerDyn) * (size_t)(m->n_layers ? m->n_layers : 1));
+    if (!fit_size(4 * nh_w + 2 * ns_w + dyn_b)) return w;
+    const size_t nh = (size_t)nh_w, ns = (size_t)ns_w;
+    size_t off = 0;
     w.hA = off; off += nh;
     w.hB = off; off += nh;
     w.bq = off; off += ns;
     w.xs = off; off += ns;
     w.x1 = off; off += nh;
     w.z = off; off += nh;
-    w.dyn = off; off += al(sizeof(LayerDyn) * (size_t)(m->n_layers ? m->n_layers : 1));
+    w.dyn = off; off += dyn_b;
     w.total = off;
     return w;
 }
@@ -942,7 +952,10 @@ extern "C" size_t s5fxp_workspace_bytes(const s5fxp_model *m, int B, int L)
 {
     if (!m || B < 1 || L < 1) return 0;
     const size_t g = ws_layout(m, B, L).total;
-    const size_t f = m->fast ? fast_ws(m, B, L).total : 0;
+    if (!g) return 0; // it does not fit a size_t
+    if (!m->fast) return g;
+    const size_t f = fast_ws(m, B, L).total;
+    if (!f) return 0;
     return g > f ? g : f;
 }
 
@@ -1170,6 +1183,8 @@ int forward_entry(const s5fxp_model *m, int io, const void *x, int x_bits, int x
     const size_t ws_one = io == IO_I32   ? s5fxp_workspace_bytes(m, B, L)
                           : io == IO_F32 ? s5fxp_workspace_bytes_f32(m, B, L)
                                          : s5fxp_workspace_bytes_i16(m, B, L);
+    // no workspace can hold it: one forward's size does not fit a size_t (the query's 0), or the G-fold of it does not
+    if (!ws_one || ws_one > SIZE_MAX / (size_t)G) return S5FXP_EWORKSPACE;
     if (workspace_bytes < (size_t)G * ws_one) return S5FXP_EWORKSPACE;
     const size_t N = (size_t)B * L;
     if (G > 1) {
@@ -1227,8 +1242,8 @@ extern "C" size_t s5fxp_workspace_bytes_f32(const s5fxp_model *m, int B, int L)
 {
     const size_t ws = s5fxp_workspace_bytes(m, B, L);
     if (!ws || m->fast) return ws;
-    const size_t N = (size_t)B * L;
-    return ws + al256(N * m->d_in * 4) + al256(N * m->d_out * 4);
+    const wide_t N = (wide_t)B * L;
+    return fit_size(ws + wide_al256(N * m->d_in * 4) + wide_al256(N * m->d_out * 4));
 }
 
 extern "C" int s5fxp_model_forward_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int B, int L, float *y,
@@ -1262,7 +1277,7 @@ extern "C" int s5fxp_layer_forward(const s5fxp_model *m, int layer, const int32_
     if (opts && opts->groups > 1) return S5FXP_EUNSUPPORTED;
     if (!stream_extent_ok(m, L)) return S5FXP_EBADARG;
     const WsLayout w = ws_layout(m, B, L);
-    if (workspace_bytes < w.total) return S5FXP_EWORKSPACE;
+    if (!w.total || workspace_bytes < w.total) return S5FXP_EWORKSPACE; // 0: the size does not fit a size_t
     hipStream_t st = S(stream);
     char *ws = reinterpret_cast<char *>(workspace);
     LayerDyn *dyn = reinterpret_cast<LayerDyn *>(ws + w.dyn);
@@ -1491,7 +1506,8 @@ int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, cons
     if (fq_plan(fq, m->n_layers, qp)) return S5FXP_EBADARG;
     const FmTiling t = fm_tiling(B, L, CLIPS, lens);
     if (hist && !fm_hist_rows_ok(t.tiles, t.grid)) return S5FXP_EBADARG; // a 32-bit LDS counter could wrap
-    if (workspace_bytes < s5fxp_float_workspace_bytes(m, B, L, trace != nullptr)) return S5FXP_EWORKSPACE;
+    const size_t ws_need = s5fxp_float_workspace_bytes(m, B, L, trace != nullptr);
+    if (!ws_need || workspace_bytes < ws_need) return S5FXP_EWORKSPACE; // 0: the size does not fit a size_t
     const int64_t scan_grid = (int64_t)B * ((m->P + ASSOC_PT - 1) / ASSOC_PT); // of the clip scan
     if (CLIPS && scan_grid > 0x7fffffffll) return S5FXP_EBADARG;
     for (int i = 0; i < m->n_layers; ++i) // what s5fxp_fq_scan_c64 would refuse, before anything is launched
@@ -1612,8 +1628,8 @@ extern "C" void s5fxp_float_model_destroy(s5fxp_float_model *m) { delete m; }
 extern "C" size_t s5fxp_float_workspace_bytes(const s5fxp_float_model *m, int B, int L, int trace)
 {
     if (!m || B < 1 || L < 1) return 0;
-    const size_t N = (size_t)B * L;
-    return (2 * N * m->H + (size_t)(trace ? m->n_layers : 1) * 2 * N * 2 * m->P) * sizeof(float);
+    const wide_t N = (wide_t)B * L;
+    return fit_size((2 * N * m->H + (wide_t)(trace ? m->n_layers : 1) * 2 * N * 2 * m->P) * sizeof(float));
 }
 
 extern "C" size_t s5fxp_float_trace_bytes(const s5fxp_float_model *m, int B, int L)

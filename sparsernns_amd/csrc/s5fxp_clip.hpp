@@ -357,7 +357,8 @@ int clips_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int 
     if (!lens || !workspace || Lmax < 1) return S5FXP_EBADARG;
     if (const int rc = step_checks(m, x, x_bits, x_exp, n, 1, 1, y, status, f32)) return rc;
     if (!clips_serves(m, Lmax)) return Lmax > CLIP_MAX_LEN ? S5FXP_EBADARG : S5FXP_EUNSUPPORTED;
-    if (workspace_bytes < (size_t)n * clip_scratch_bytes(m, Lmax) || (reinterpret_cast<uintptr_t>(workspace) & 1)) return S5FXP_EBADARG;
+    const size_t ws_need = fit_size((wide_t)n * clip_scratch_bytes(m, Lmax)); // 0: it does not fit a size_t
+    if (!ws_need || workspace_bytes < ws_need || (reinterpret_cast<uintptr_t>(workspace) & 1)) return S5FXP_EBADARG;
     const int R32 = Lmax < STEP_MAX_ROWS ? Lmax : STEP_MAX_ROWS;
     const size_t smem = step_lds(R32, m->H, m->P, fast_shape(m->H, m->P).hp, m->d_in).total;
     ClipArgs a{};
@@ -372,7 +373,7 @@ int clips_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int 
 extern "C" size_t s5fxp_clips_workspace_bytes(const s5fxp_model *m, int n, int Lmax)
 {
     if (!m || n < 1 || Lmax < 1 || Lmax > CLIP_MAX_LEN) return 0;
-    return (size_t)n * clip_scratch_bytes(m, Lmax);
+    return fit_size((wide_t)n * clip_scratch_bytes(m, Lmax));
 }
 
 extern "C" int s5fxp_model_clips_ok(const s5fxp_model *m, int Lmax)

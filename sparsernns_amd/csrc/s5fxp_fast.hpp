@@ -264,13 +264,16 @@ struct FastWs {
 
 FastWs fast_ws(const s5fxp_model *m, int B, int L)
 {
-    const size_t N = (size_t)B * L;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     FastWs w{};
-    w.TB = ((L + 3) / 4 + SCAN_DEPTH - 1) / SCAN_DEPTH * SCAN_DEPTH;
+    w.TB = (int)time_blocks(L, SCAN_DEPTH);
+    // the planes' sizes in 128 bits; a layout whose end does not fit a size_t has total == 0 and no meaningful offsets
+    const wide_t nh_w = wide_al256((wide_t)B * L * m->H * 2 + 64) + m->cfg.plane_skew; // int16 (+ slack for the 32-byte fragment loads of clamped tail lanes)
+    const wide_t ns_w = wide_al256(((wide_t)B * w.TB + SCAN_DEPTH) * m->P * 8 * 4) + m->cfg.plane_skew;
+    const size_t dyn_b = (size_t)wide_al256(sizeof(LayerDyn) * (size_t)m->n_layers);
+    const size_t ext_b = (size_t)wide_al256(sizeof(float) * 2 * (size_t)m->H * (size_t)m->n_layers * EXT_REPS);
+    if (!fit_size(5 * nh_w + 2 * ns_w + dyn_b + ext_b)) return w;
+    const size_t nh = (size_t)nh_w, ns = (size_t)ns_w;
     size_t off = 0;
-    const size_t nh = al(N * m->H * 2 + 64) + m->cfg.plane_skew; // int16 (+ slack for the 32-byte fragment loads of clamped tail lanes)
-    const size_t ns = al(((size_t)B * w.TB + SCAN_DEPTH) * m->P * 8 * 4) + m->cfg.plane_skew;
     w.hA = off; off += nh;
     w.hB = off; off += nh;
     w.x1 = off; off += nh;
@@ -279,8 +282,8 @@ FastWs fast_ws(const s5fxp_model *m, int B, int L)
     w.bq = off; off += ns;
     w.xs = off; off += ns;
     // per-layer device state and per-channel extremes: contiguous, zeroed by one memset per forward
-    w.dyn = off; off += al(sizeof(LayerDyn) * (size_t)m->n_layers);
-    w.ext = off; off += al(sizeof(float) * 2 * (size_t)m->H * (size_t)m->n_layers * EXT_REPS);
+    w.dyn = off; off += dyn_b;
+    w.ext = off; off += ext_b;
     w.dyn_bytes = off - w.dyn;
     w.total = off;
     return w;
