@@ -498,11 +498,14 @@ size_t s5fxp_workspace_bytes_i16(const s5fxp_model *m, int B, int L);
  *                                                              live-state compaction
  *   S5FXP_NO_DEC_RESID                                         the last layer's residual pass as a launch of its own
  *   S5FXP_NO_LIVE_LANES                                        a compacted layer's recurrence streams keep their padding slots
- *   S5FXP_GATE_BN=0|1                                          where the gate kernel takes the SSM input u from.  Unset: the 32-frame kernel
+ *   S5FXP_GATE_BN=0|1|2                                        where the gate kernel takes the SSM input u from.  Unset: the 32-frame kernel
  *                                                              rebuilds it from the layer input it loads anyway and the B projection does
  *                                                              not store it; 0: u travels through memory (the kernels before that, for A/B
  *                                                              runs); 1: the first experiment, 64-frame tiles with the BatchNorm chain in
- *                                                              the first epilogue (slower than both; kept as the record)
+ *                                                              the first epilogue (slower than both; kept as the record); 2: the gate
+ *                                                              kernel as when unset, and the B projection, which runs the same packed row
+ *                                                              chain at H = 96, keeps its element-wise one (the kernels before that, for A/B
+ *                                                              runs)
  *   S5FXP_CGATE_FT64, S5FXP_WGS_CGATE32=n                      the gate kernel on 64-frame tiles (six-wave workgroups) / workgroups per launch
  *                                                              of the default 32-frame form
  *   S5FXP_WGS_ENC|DEC|CGATE|BPROJ|RESID=n                      workgroups per launch of the tile kernels

@@ -861,6 +861,30 @@ __device__ __forceinline__ Bn16Row bn16_row_setup(const BnArgs &a, const LayerDy
     return p;
 }
 
+// ... or, for a kernel whose threads do NOT keep one channel group (the B projection, proj_p.hpp k_bproj_p<.., ROW>): the uniform
+// part as above (m and iv stay unset), and the operand pairs of all H channels in LDS -- H/2 words of mean pairs, then H/2 words
+// of isv pairs, formed as bn16_row_setup forms m[k] and iv[k]; a thread takes the two 16-byte vectors of its channel group
+// og at word 4 * og of either half.  All threads; call before a __syncthreads().
+__device__ __forceinline__ Bn16Row bn16_row_table(const BnArgs &a, const LayerDyn &d, int32_t *lds, int H)
+{
+    Bn16Row p{};
+    bn16_row_shifts(p, a.xb, a.mb, a.ib, a.b1, a.b2, a.out_bits < a.ub ? a.out_bits : a.ub, d.bn1.shx, d.bn1.post, d.rs2, a.ue - d.bn_e);
+    for (int k = threadIdx.x; k < H / 2; k += blockDim.x) {
+        const int32_t m0 = sat(wshl(a.mm[2 * k], d.bn1.shy), a.mb), m1 = sat(wshl(a.mm[2 * k + 1], d.bn1.shy), a.mb);
+        lds[k] = (int32_t)(((uint32_t)m0 & 0xffffu) | ((uint32_t)m1 << 16));
+        lds[H / 2 + k] = (int32_t)(((uint32_t)a.isv[2 * k] & 0xffffu) | ((uint32_t)a.isv[2 * k + 1] << 16));
+    }
+    return p;
+}
+
+// the B projection's phase A operands in either form: bn16_x4's (Bn16, four LDS tables) or bn16_row8's (Bn16Row, the pair table)
+template <bool ROW>
+__device__ __forceinline__ auto bn_operands(const BnArgs &a, const LayerDyn &d, int32_t *lds, int H)
+{
+    if constexpr (ROW) return bn16_row_table(a, d, lds, H);
+    else return bn16_setup(a, d, lds, H);
+}
+
 // eight consecutive channels of one frame (int16, as loaded) -> their SSM input u (int16, as bn16_x4 + pack4_i16 give it)
 template <int ARM>
 __device__ __forceinline__ v4i bn16_row8(const Bn16Row &p, const v4i &x)

@@ -115,7 +115,11 @@ struct TileWalk {
 // frames; NC == NT / 2 (a layer compacted to its live states, s5fxp_fast.hpp): wave w takes column tile w % NC and the ONE
 // half w / NC -- the workgroup keeps its size, so phase A (the bulk of the kernel) is unchanged; NC == NT / 4 (a 128-state
 // layer on 32 slots): the same, and the waves with w / NC >= 2 sit phase B out.
-template <int KS, int NT, bool TRACE, int SM = 0, int NC = NT>
+// ROW: phase A runs the gate kernel's row chain (mfma_bn.hpp bn16_row8) on the 16-byte vectors as loaded, instead of unpacking
+// them for bn16_x4: u comes out as the packed int16 pairs its store and the byte-plane selectors want.  For layers whose
+// BatchNorm has no scale / bias stage (host-known: s5fxp_fast.hpp bproj_row); the traced kernels need t (pre_s5) and keep
+// bn16_x4.  ROW = false is the code as it was, instruction for instruction (the fallback and the A/B partner: S5FXP_GATE_BN=2).
+template <int KS, int NT, bool TRACE, int SM = 0, int NC = NT, bool ROW = false>
 // (waves per SIMD the registers are budgeted for: 4; 3 at H = 144, whose grid holds two workgroups per CU anyway
 // (s5fxp_fast.hpp FastShape::wide) and whose 5 k-steps of weights do not fit 128 registers next to the prefetch; 2 for the
 // traced kernels, which hold the trace pointers as well and are no hot path)
@@ -127,6 +131,7 @@ __global__ __launch_bounds__(64 * NT, TRACE ? 2 : KS == 5 ? 3 : 4) void k_bproj_
         gshift(a.ext, g * go.ws); gshift(a.status, g * go.status); gshift(a.status_exps, g * go.status);
     }
     static_assert(NC == NT || 2 * NC == NT || 4 * NC == NT, "column tiles per workgroup");
+    static_assert(!ROW || !TRACE, "the traced kernels store pre_s5: bn16_x4");
     // H: the real channels (row stride, vectors per frame, BatchNorm operands); HP: the k extent of the byte planes
     constexpr int H = shape_channels(KS), HP = 32 * KS, FT = 64, KP = 32 * KS + 16, PC = 16 * NC, SUB0_STEP = NT / NC; // halves a wave takes: 2 / SUB0_STEP
     constexpr int VPF = H / 8;             // 16-byte vectors per frame
@@ -136,7 +141,7 @@ __global__ __launch_bounds__(64 * NT, TRACE ? 2 : KS == 5 ? 3 : 4) void k_bproj_
     constexpr int PLANE = FT * KP;
     static_assert(FT * VPF % NTHR == 0, "tile shape");
     extern __shared__ __attribute__((aligned(16))) int8_t smem[];
-    int32_t *tab = reinterpret_cast<int32_t *>(smem);             // 4*H BatchNorm operands
+    int32_t *tab = reinterpret_cast<int32_t *>(smem);             // 4*H BatchNorm operands (ROW: H words of packed pairs)
     int8_t *Xh = smem + 16 * HP, *Xl = Xh + 2 * PLANE;            // [buf][frame][KP]
     zero_plane_tail<H, HP, KP>(Xh, 4 * FT);                       // (visible behind the barrier below)
     const int l = threadIdx.x & 63, r = l & 31, h = l >> 5, wave = threadIdx.x >> 6;
@@ -145,6 +150,11 @@ __global__ __launch_bounds__(64 * NT, TRACE ? 2 : KS == 5 ? 3 : 4) void k_bproj_
     const int64_t tiles = (a.N / a.L) * ((sr.t_len + FT - 1) / FT);
     int64_t tile = blockIdx.x;
 
+    // The two bn16_x4 kernels of the uncompacted H = 192 layer on the pair streams sit at their 128 registers with the prefetch's
+    // three per-thread row offsets kept across the tile loop, two of them in scratch (20 bytes per lane, reloaded per tile).
+    // There the thread index is hidden from the compiler inside fetch, so that the offsets are formed again per tile (a
+    // multiply, a shift and a subtraction each) and nothing spills; every other instantiation keeps its code.
+    constexpr bool REFETCH = KS == 6 && NC == 8 && SM >= 2 && !TRACE && !ROW;
     v4i raw[NV];
     auto fetch = [&](const TileWalk<FT> &tw) {
         const int64_t b = tw.b;
@@ -152,7 +162,12 @@ __global__ __launch_bounds__(64 * NT, TRACE ? 2 : KS == 5 ? 3 : 4) void k_bproj_
         const char *xb = reinterpret_cast<const char *>(a.x + (b * a.L + t) * H); // wave-uniform; 32-bit byte offsets from here
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
-            const int v = threadIdx.x + NTHR * i;
+            int v;
+            if constexpr (REFETCH) {
+                unsigned tid = threadIdx.x;
+                asm volatile("" : "+v"(tid));
+                v = tid + NTHR * i;
+            } else v = threadIdx.x + NTHR * i;
             int f = v / VPF;
             f = f < nv ? f : nv - 1;
             raw[i] = *reinterpret_cast<const v4i *>(xb + 2u * (unsigned)(f * H + 8 * (v % VPF)));
@@ -178,7 +193,8 @@ __global__ __launch_bounds__(64 * NT, TRACE ? 2 : KS == 5 ? 3 : 4) void k_bproj_
     const LayerDyn d = a.ext ? bn_finalize_mm_body(a.bn, a.ext, H, const_cast<LayerDyn *>(a.bn.dyn), a.status, a.status_exps, a.bn.xe.get(), a.ext_reps,
                                                    blockIdx.x == 0)
                              : *a.bn.dyn;
-    const Bn16 bn = bn16_setup(a.bn, d, tab, H);
+    // (ROW: a Bn16Row -- the shifts and the arm; the operand pairs of every channel group are in `tab`)
+    const std::conditional_t<ROW, Bn16Row, Bn16> bn = bn_operands<ROW>(a.bn, d, tab, H);
     // resid_lazy (mfma_bn.hpp ResolveU16): the rows are the previous layer's aligned sum U; that layer's residual pass has
     // published the shift that makes them the layer input.  0: plain rows; otherwise 1 + the arm, chosen once per workgroup
     // (the route exists where the gate kernel that stores U does: H = 96; the other shapes keep their code)
@@ -202,6 +218,46 @@ __global__ __launch_bounds__(64 * NT, TRACE ? 2 : KS == 5 ? 3 : 4) void k_bproj_
         char *ub = reinterpret_cast<char *>(a.u + n0 * H); // wave-uniform base of this tile's rows of u
         int8_t *xh = Xh + (it & 1) * PLANE, *xl = Xl + (it & 1) * PLANE;
         // ---- phase A: BatchNorm chain, u, byte planes
+        if constexpr (ROW) {
+            // ROW: phase A of one tile.  ARM (mfma_bn.hpp ROW_*) is wave-uniform and chosen once per tile, as in the gate kernel
+            // (mfma_fused_body.inc tiles_in_urec).  A thread's NV vectors are NV different channel groups (NTHR is no multiple of
+            // VPF), so each takes its operand pairs from the table: two 16-byte LDS reads where bn16_x4 makes four.  u = bn16_row8 is
+            // pack4_i16 of bn16_x4's u (tools/probe_bn16_row8.hip), so it is stored as it is, and the byte planes take the low and the
+            // high bytes of the pairs with the selectors of the gate kernel's X1 planes.
+            auto phase_a_row = [&](auto arm_c) {
+                constexpr int ARM = decltype(arm_c)::value;
+#pragma unroll
+                for (int i = 0; i < NV; ++i) {
+                    const int v = threadIdx.x + NTHR * i, f = v / VPF, og = v % VPF;
+                    if constexpr (LAZY) {
+                        if (lazy_arm == 1 + RES_RIGHT) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) raw[i][e] = (int)resolve_u16_pair<RES_RIGHT>(rz, (uint32_t)raw[i][e]);
+                        } else if (lazy_arm) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) raw[i][e] = (int)resolve_u16_pair<RES_GENERIC>(rz, (uint32_t)raw[i][e]);
+                        }
+                    }
+                    const v4i bm = *reinterpret_cast<const v4i *>(tab + 4 * og), bi = *reinterpret_cast<const v4i *>(tab + H / 2 + 4 * og);
+                    auto br = bn;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) { br.m[k] = (uint32_t)bm[k]; br.iv[k] = (uint32_t)bi[k]; }
+                    const v4i uv = bn16_row8<ARM>(br, raw[i]);
+                    if (f < nvalid && !a.no_u) *reinterpret_cast<v4i *>(ub + 2u * (unsigned)(f * H + 8 * og)) = uv;
+                    v2i hi, lo;
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        lo[j] = (int)(perm((unsigned)uv[2 * j + 1], (unsigned)uv[2 * j], 0x06040200u) ^ 0x80808080u);
+                        hi[j] = (int)perm((unsigned)uv[2 * j + 1], (unsigned)uv[2 * j], 0x07050301u);
+                    }
+                    *reinterpret_cast<v2i *>(xh + f * KP + 8 * og) = hi;
+                    *reinterpret_cast<v2i *>(xl + f * KP + 8 * og) = lo;
+                }
+            };
+            if (bn.arm == ROW_PACKED) phase_a_row(std::integral_constant<int, ROW_PACKED>{});
+            else if (bn.arm == ROW_SHIFTED) phase_a_row(std::integral_constant<int, ROW_SHIFTED>{});
+            else phase_a_row(std::integral_constant<int, ROW_GENERIC>{});
+        } else
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int v = threadIdx.x + NTHR * i, f = v / VPF, og = v % VPF;

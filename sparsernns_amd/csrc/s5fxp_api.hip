@@ -578,8 +578,10 @@ struct ModelCfg {
     // S5FXP_GATE_BN: where the gate kernel takes the SSM input u = BatchNorm(layer input) from.  Unset: the 32-frame kernel rebuilds
     // it in its tile staging (k_cgate_p<.., UREC>); =0: it is read from memory and the B projection stores it (the kernels before
     // UREC: the A/B partner); any other value: the first experiment, 64-frame tiles with the BatchNorm in the first epilogue
-    // (k_cgate_p<.., GBN>; measured slower: DESIGN.md 4a)
-    bool gate_bn = false, no_gate_urec = false;
+    // (k_cgate_p<.., GBN>; measured slower: DESIGN.md 4a).  =2 leaves the gate kernel at its default and takes the same row chain
+    // out of the B projection instead: its phase A keeps bn16_x4 on every layer (the kernels before k_bproj_p<.., ROW>: the A/B
+    // partner of that change.  A value of this switch, not a name of its own: both select where bn16_row8 runs)
+    bool gate_bn = false, no_gate_urec = false, no_bproj_row = false;
     bool cgate_ft64 = false;   // S5FXP_CGATE_FT64: the packed-epilogue gate kernel on 64-frame tiles with six-wave workgroups (the form before
                                // the 32-frame / three-wave one became the default at dim_scale 0.5)
     int64_t cap_cgate32 = 1280; // S5FXP_WGS_CGATE32: workgroups per launch of the 32-frame gate kernel (5 per CU: all resident)
@@ -598,7 +600,11 @@ struct ModelCfg {
         };
         c.debug_sync = on("S5FXP_DEBUG_SYNC"); c.no_bn_ext = on("S5FXP_NO_BN_EXT"); c.no_pair = on("S5FXP_NO_PAIR");
         c.pair_global = on("S5FXP_PAIR_GLOBAL"); c.no_pk16 = on("S5FXP_NO_PK16"); c.no_compact = on("S5FXP_NO_COMPACT"); c.no_dec_resid = on("S5FXP_NO_DEC_RESID"); c.no_live_lanes = on("S5FXP_NO_LIVE_LANES"); c.cgate_ft64 = on("S5FXP_CGATE_FT64"); c.cap_cgate32 = cap("S5FXP_WGS_CGATE32", c.cap_cgate32);
-        { const char *e = std::getenv("S5FXP_GATE_BN"); c.no_gate_urec = e && std::strcmp(e, "0") == 0; c.gate_bn = e && !c.no_gate_urec; }
+        {
+            const char *e = std::getenv("S5FXP_GATE_BN");
+            c.no_gate_urec = e && std::strcmp(e, "0") == 0; c.no_bproj_row = e && std::strcmp(e, "2") == 0;
+            c.gate_bn = e && !c.no_gate_urec && !c.no_bproj_row;
+        }
         { const char *e = std::getenv("S5FXP_PAIRL_BLOCKS"); c.pairl_blocks = e && std::atoi(e) == 16 ? 16 : 32; }
         { const char *e = std::getenv("S5FXP_PLANE_SKEW"); c.plane_skew = e ? ((size_t)std::atoll(e) & ~(size_t)255) : 0; }
         c.cap_enc = cap("S5FXP_WGS_ENC", c.cap_enc); c.cap_dec = cap("S5FXP_WGS_DEC", c.cap_dec);

@@ -92,6 +92,10 @@ template <class Kernel> auto nt_kernel(int nt, Kernel kernel)
     return nt == 2 ? kernel(std::integral_constant<int, 2>{}) : nt == 3 ? kernel(std::integral_constant<int, 3>{})
          : nt == 5 ? kernel(std::integral_constant<int, 5>{}) : kernel(std::integral_constant<int, 6>{});
 }
+// Shapes whose B projection has the row-chain instantiations (proj_p.hpp k_bproj_p<.., ROW>): H = 96, the shape it was measured
+// at.  (The other three compile without scratch and to fewer registers than their bn16_x4 kernels as well -- DESIGN.md 4a has
+// the table -- but nobody has timed them: they keep the old kernels.)
+constexpr bool bproj_row_shape(int nt) { return nt == 3; }
 
 // The MFMA path runs the N-DNS shapes (FastShape) with <= 8-bit weights and <= 16-bit activations; everything else runs
 // the generic kernels.
@@ -368,6 +372,7 @@ struct LayerPlan {
     bool pk16;        // packed int16 epilogues of the gate kernel (mfma_fused.hpp PK16)
     bool gate_bn;     // the gate kernel recomputes u (S5FXP_GATE_BN)
     bool gate_urec;   // the 32-frame gate kernel rebuilds u in its tile staging (k_cgate_p<.., UREC>; off: S5FXP_GATE_BN=0)
+    bool bproj_row;   // the B projection's phase A runs the same row chain (k_bproj_p<.., ROW>; off: S5FXP_GATE_BN=2)
     bool resid_fold;  // the gate kernel stores the residual add's aligned sum U, its consumer reads that one plane (FusedForward::plan_layers)
     bool resid_lazy;  // ... and between this layer and the next nobody stores the shifted sum: the U plane is the next layer's input
     bool gate_ext;    // ... and the gate kernel gathers the extremes of U itself: the residual pass between the two is its head alone
@@ -418,6 +423,10 @@ LayerPlan plan_layer(const s5fxp_model *m, int li, int fwd_flags, bool traced, b
     // BatchNorm has no scale / bias stage (those models keep reading u).  -50 MB per layer and batch, +5 % frames/s against the
     // kernels that move u through memory, which S5FXP_GATE_BN=0 restores (profiles/r05_gate_urec_*).
     p.gate_urec = p.gate == GATE_FT32 && fold && !l.scale && !l.nbias && !m->cfg.no_gate_urec;
+    // The B projection builds the same u from the same rows, so its phase A runs the same chain (proj_p.hpp k_bproj_p<.., ROW>):
+    // every untraced layer whose BatchNorm has no scale / bias stage, at the shapes that have the instantiations (bproj_row_shape).
+    // It takes its exponents from its own prologue, so it does not need `fold`.  S5FXP_GATE_BN=2 restores bn16_x4 everywhere.
+    p.bproj_row = !traced && bproj_row_shape(sh.nt) && !l.scale && !l.nbias && !m->cfg.no_bproj_row;
     p.w_bproj = r.pair ? &(p.compact ? fl.c_bproj_pair : fl.bproj_pair).w : &(p.compact ? fl.c_bproj : fl.bproj).w;
     p.w_cre = &(p.compact ? fl.c_cre : fl.cre).w;
     p.w_cim = &(p.compact ? fl.c_cim : fl.cim).w;
@@ -445,14 +454,16 @@ template <int NT, class Kernel> auto ks_kernel(int ks, Kernel kernel)
 // waves of the B projection for NT channel tiles (FastShape::bproj_waves as a template argument)
 template <int NT> constexpr int bproj_waves_of() { return NT == 2 ? 2 : NT == 3 ? 4 : NT == 5 ? 6 : 8; }
 
-// k_bproj_p of an untraced layer: SM = the stream its recurrence rung wants (proj_p.hpp), NC = 2 KS column tiles
-template <int SM> auto bproj_kernel(const FastShape &sh, int ks)
+// k_bproj_p of an untraced layer: SM = the stream its recurrence rung wants (proj_p.hpp), NC = 2 KS column tiles, ROW = the
+// row chain in phase A (LayerPlan::bproj_row; only the shapes of bproj_row_shape have those kernels)
+template <int SM, bool ROW = false> auto bproj_kernel(const FastShape &sh, int ks)
 {
     return nt_kernel(sh.nt, [&](auto n) {
         constexpr int NT = decltype(n)::value;
-        return ks_kernel<NT>(ks, [](auto k) { return k_bproj_p<NT, bproj_waves_of<NT>(), false, SM, 2 * decltype(k)::value>; });
+        return ks_kernel<NT>(ks, [](auto k) { return k_bproj_p<NT, bproj_waves_of<NT>(), false, SM, 2 * decltype(k)::value, ROW && bproj_row_shape(NT)>; });
     });
 }
+template <int SM> auto bproj_kernel(const FastShape &sh, int ks, bool row) { return row ? bproj_kernel<SM, true>(sh, ks) : bproj_kernel<SM>(sh, ks); }
 // ... and of a traced one (every state slot, int32 stream)
 inline auto bproj_traced_kernel(const FastShape &sh)
 {
@@ -757,7 +768,8 @@ struct FusedForward {
         // wants; a compacted layer has fewer column tiles (NC)
         const Rung &r = p.rung;
         auto kernel = tr ? bproj_traced_kernel(sh)
-                         : r.pairl ? bproj_kernel<3>(sh, p.ks) : r.pair ? bproj_kernel<2>(sh, p.ks) : r.s16 ? bproj_kernel<1>(sh, p.ks) : bproj_kernel<0>(sh, p.ks);
+                         : r.pairl ? bproj_kernel<3>(sh, p.ks, p.bproj_row) : r.pair ? bproj_kernel<2>(sh, p.ks, p.bproj_row)
+                         : r.s16 ? bproj_kernel<1>(sh, p.ks, p.bproj_row) : bproj_kernel<0>(sh, p.ks, p.bproj_row);
         launch(kernel, grid_bproj, 64 * sh.bproj_waves, smem, nullptr, nullptr, a);
     }
     // the recurrence's arguments on the quad layout (the fast quad kernels, the exact chain and its gated re-run)
