@@ -189,8 +189,8 @@ int s5fxp_mask_istft_clips(const float *audio, const float *mask, int n, int64_t
  * each be NULL: the plane is then never stored.  si_snr, mag_mse, loss: (B) float32; mag_mse and loss may be NULL.  The sums
  * behind the scores are taken in double on the float32 values the planes would hold (clean_mag bit for bit
  * s5fxp_stft_mag's), in a fixed order, without atomics: two calls give identical bits, with or without the planes.
- * workspace: s5fxp_score_workspace_bytes(B, T) bytes of device memory, 8-byte aligned, overwritten by the call (0 for B < 1,
- * T < 512 or a grid beyond 2^31 - 1, which the entries refuse).  S5FXP_EBADARG for a null audio, clean, workspace or
+ * workspace: s5fxp_score_workspace_bytes(B, T) bytes of device memory, 8-byte aligned, overwritten by the call whatever it
+ * held (0 for B < 1, T < 512 or a grid beyond 2^31 - 1, which the entries refuse).  S5FXP_EBADARG for a null audio, clean, workspace or
  * si_snr, B < 1 or mask_exp outside 0..31;
  * S5FXP_EUNSUPPORTED for T < 512 or such a grid; S5FXP_EWORKSPACE for a workspace that is too small -- all before the device is touched. */
 size_t s5fxp_score_workspace_bytes(int B, int64_t T);
@@ -210,7 +210,8 @@ int s5fxp_mask_istft_score_i16(const float *audio, const float *clean, const int
  * the clip's own tiles are added in the same order.  A clip below 512 samples has no frames: its three scores are quiet NaNs and
  * nothing else of it is written.
  * workspace: s5fxp_score_clips_workspace_bytes(n, Tmax) = 48 * n * ceil((s5fxp_stft_frames(Tmax) - 1) / 13) bytes of device
- * memory, 8-byte aligned, overwritten where a clip has tiles (0 for n < 1, Tmax < 512 or Tmax > (2^20 - 1) * 128).
+ * memory, 8-byte aligned, overwritten where a clip has tiles (0 for n < 1, Tmax < 512 or Tmax > (2^20 - 1) * 128); it may hold
+ * anything on entry: the tiles a clip does not have keep their bytes, and no score depends on them.
  * Checked before the device is touched, in this order: S5FXP_EBADARG for a null audio, clean, samples, workspace or si_snr,
  * n < 1 or Tmax > (2^20 - 1) * 128; S5FXP_EUNSUPPORTED for Tmax < 512 or a grid beyond 2^31 - 1; S5FXP_EWORKSPACE for a
  * workspace that is too small. */
@@ -250,7 +251,9 @@ int s5fxp_stream_mask_istft(const float *mask, int S, int c, int64_t hops_before
  * host-to-device copy per push); entry e is workgroup e of each launch.  The kernels trust the array as they trust pointers
  * and sizes: validate it on the host with s5fxp_push_desc_check before it is copied.
  *   FRESH  the slot starts a new signal: its carry (step) and its audio state (both audio kernels) are taken as all-zero
- *          bytes, whatever they hold -- a slot is reused after a finished signal without a clearing launch;
+ *          bytes, whatever they hold -- a slot is reused after a finished signal without a clearing launch.  (A push of c hops
+ *          rewrites the newest c + 3 hops of the audio state and its three segments; the older hops keep their bytes, and no
+ *          later push reads them before it has rewritten them);
  *   ZEROS  the entry's audio is zeros, whatever `audio` holds (the two trailing hops of a finishing stream);
  *   FINAL  the entry is the end of its signal (the `final` of s5fxp_stream_mask_istft). */
 enum { S5FXP_PUSH_FRESH = 1, S5FXP_PUSH_ZEROS = 2, S5FXP_PUSH_FINAL = 4 };
@@ -363,14 +366,18 @@ int s5fxp_model_create(const s5fxp_model_desc *desc, void *dev_blob, size_t blob
                        s5fxp_model **out);
 void s5fxp_model_destroy(s5fxp_model *m);
 
-/* Device workspace for one forward of B sequences of L frames.  0: a null model, B < 1 or L < 1, or a size that does not fit
+/* Device workspace for one forward of B sequences of L frames; it may hold anything on entry: no output depends on what it
+ * held, nor on what the status words, y, state_out and the trace planes held (tests/test_caller_memory.py).  The status words
+ * are always written completely; y, state_out and the trace planes are written completely by a forward that does not come back
+ * with S5FXP_ST_REDO (under S5FXP_FWD_DEFER_REDO they are then invalid, see below).  0: a null model, B < 1 or L < 1, or a size that does not fit
  * a size_t (the sum is formed with checked arithmetic and never wraps; it grows with B and with L, so the answer does not
  * return from 0 to a size as either grows).  The forwards refuse such a (B, L), and a grouped call whose G-fold of this
  * value does not fit a size_t, with S5FXP_EWORKSPACE before the device is touched, whatever workspace_bytes claims. */
 size_t s5fxp_workspace_bytes(const s5fxp_model *m, int B, int L);
 
 /* Number of int32 words in the device status buffer, and its layout:
- *   [0] error bits (S5FXP_ST_*), [1] decoder output exponent,
+ *   [0] error bits (S5FXP_ST_*), [1] decoder output exponent as s5fxp_model_step and s5fxp_model_clips store it (0 from
+ *       s5fxp_model_forward[_f32|_i16] and s5fxp_layer_forward: it is a fact of the model, s5fxp_model_out_exp),
  *   [2] which kernels this forward ran: S5FXP_PATH_GENERIC (one-lane / VALU kernels, any int32 operands),
  *       S5FXP_PATH_FUSED (the int8-MFMA tile kernels + the quad / pair recurrence kernels), S5FXP_PATH_STEP (the
  *       one-launch kernel of s5fxp_model_step) or S5FXP_PATH_CLIP (the one-launch kernel of s5fxp_model_clips),
@@ -565,7 +572,8 @@ int s5fxp_model_step_ragged_f32(const s5fxp_model *m, const float *x, int x_bits
  *   to Lmax frames per clip; frames len_e..Lmax-1 of x are never read and of y never written.  lens: n int32, device memory.
  *   carry [n][n_layers][2][P]: state_in NULL = zeros, state_out NULL = not wanted, state_out == state_in is allowed.
  *   workspace: s5fxp_clips_workspace_bytes(m, n, Lmax) bytes of device memory, 2-byte aligned: per clip two int16 planes of
- *   Lmax x H (the layer input and the gate output), written and read by that clip's workgroup only.
+ *   Lmax x H (the layer input and the gate output), written and read by that clip's workgroup only.  It may hold anything
+ *   on entry: no output depends on what it held.
  *   status: n * S5FXP_STATUS_WORDS words, written completely by the kernel, laid out as s5fxp_model_step's with
  *   [2] = S5FXP_PATH_CLIP.  S5FXP_ST_WIDE_STATE is the OR over the clip's tiles.
  *   len_e == 0: y untouched, state_out[e] = state_in[e] (zeros for NULL), the status words hold the kernel's initial fill.
@@ -678,7 +686,8 @@ void s5fxp_float_model_destroy(s5fxp_float_model *m);
 /* Device workspace of one forward: two (N,H) planes for the layer input and output and the (N,P) complex64 planes Bu and xs,
  * N = B * L -- one pair shared by all layers, or with trace != 0 one pair per layer, kept: floats
  * [2 N H][layer 0: Bu, xs][layer 1: ...].  0: bad argument, or a size that does not fit a size_t (checked arithmetic, never
- * a wrapped value); the forwards refuse such a (B, L) with S5FXP_EWORKSPACE before the device is touched. */
+ * a wrapped value); the forwards refuse such a (B, L) with S5FXP_EWORKSPACE before the device is touched.  The workspace, y and
+ * the trace planes may hold anything on entry, NaN included: nothing of it reaches y, an observer or a histogram. */
 size_t s5fxp_float_workspace_bytes(const s5fxp_float_model *m, int B, int L, int trace);
 /* Bytes of the trace buffer: per layer five (N,H) float32 planes u, y, g_in, g, h' (the layer's output), layer after layer. */
 size_t s5fxp_float_trace_bytes(const s5fxp_float_model *m, int B, int L);
@@ -791,7 +800,8 @@ int s5fxp_float_model_clips_fq(const s5fxp_float_model *m, const float *x, int n
  *
  * pairs_host: HOST memory, read before the entry returns.  out_dev: n_pairs records in device memory, 8-byte aligned.
  * workspace: s5fxp_stage_err_workspace_bytes(n_pairs) bytes of device memory, 256-byte aligned, overwritten by the call
- * (0 for n_pairs outside 1..4096).  A pair with a zero extent is legal (its pointers may be NULL) and gets an all-zero record.
+ * (0 for n_pairs outside 1..4096); it and out_dev may hold anything on entry, every record is written completely.  A pair with
+ * a zero extent is legal (its pointers may be NULL) and gets an all-zero record.
  * S5FXP_EBADARG, before the device is touched: a null pairs_host / out_dev / workspace, or a null a / b of a pair that has
  * elements; n_pairs outside 1..4096; an unknown kind or unknown flag bits; a_exp outside 0..40 on an I32 pair; a negative
  * extent; and the wrap rule: a workgroup counts in 32-bit words, so a pair of more than (2^32 - 256) * W elements is refused,

@@ -437,14 +437,17 @@ def test_all_sites_on_where_workgroups_walk_two_tiles_at_the_other_dim_scales(di
     check_all_sites_on(dim, case, "w8a8")
 
 
-def check_all_sites_on(dim, case, recipe):
+def check_all_sites_on(dim, case, recipe, t=None):
+    """``t``: host copies of the planes of a traced forward of ``make_x(dims, case, recipe)`` under ``full_spec(dim, recipe)`` that
+    the caller ran on buffers of its own (tests/test_caller_memory.py); None: ``forward_traced`` runs it here."""
     from sparsernns_amd import floatmodel as F
 
     md, qc, dims = model(dim, recipe)
     n, H, P = dims["n_layers"], dims["H"], dims["P"]
     x = make_x(dims, case, recipe)
     spec = full_spec(dim, recipe)
-    t = host_planes(engine(dim, recipe).forward_traced(x, fq=spec))
+    if t is None:
+        t = host_planes(engine(dim, recipe).forward_traced(x, fq=spec))
     Q = lambda key: fq_of(key, spec, n)
     shares = {}
     relu = lambda v: np.maximum(v, 0)

@@ -435,13 +435,20 @@ def test_one_layer_in_step_mode(dim, case, recipe):
 @pytest.mark.gpu
 @pytest.mark.parametrize("dim,case,recipe", MODEL_GRID, ids=MODEL_IDS)
 def test_all_sites_on_in_step_mode(dim, case, recipe):
+    check_all_sites_on_in_step_mode(dim, case, recipe)
+
+
+def check_all_sites_on_in_step_mode(dim, case, recipe, t=None):
+    """``t``: host copies of the planes of a traced forward of ``T.make_x(dims, case, recipe)`` under the all-sites step spec that
+    the caller ran on buffers of its own (tests/test_caller_memory.py); None: ``forward_traced`` runs it here."""
     from sparsernns_amd import floatmodel as F
 
     md, qc, dims = T.model(dim, recipe)
     n, H, P = dims["n_layers"], dims["H"], dims["P"]
     x = T.make_x(dims, case, recipe)
     spec = F.fq_spec(qc, n, recurrence="step")
-    t = T.host_planes(T.engine(dim, recipe).forward_traced(x, fq=spec))
+    if t is None:
+        t = T.host_planes(T.engine(dim, recipe).forward_traced(x, fq=spec))
     Q = lambda key: T.fq_of(key, spec, n)
     shares = {}
     relu = lambda v: np.maximum(v, 0)
