@@ -597,6 +597,22 @@ int s5fxp_model_clips(const s5fxp_model *m, const int32_t *x, int x_bits, int x_
 int s5fxp_model_clips_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int n, int Lmax, const int32_t *lens,
                           float *y, const int32_t *state_in, int32_t *state_out, void *workspace, size_t workspace_bytes,
                           int32_t *status, void *stream);
+/* The clip launch WITH TRACE PLANES: the arguments of s5fxp_model_clips[_f32] plus `traces`, n_layers entries
+ * in HOST memory (device pointers, any plane may be NULL), read before the entry returns.  Planes are padded like x / y:
+ * (n,Lmax,H), or (n,Lmax,P) for Bu_* / xs_*, int32.  Rows t < len_e of every plane of clip e are bit for bit what
+ * s5fxp_model_forward(B = 1, L = len_e, traces) stores for that clip alone with that carry -- xs_* the raw states before the
+ * complex ReLU, residadd the sum before the ReLU; rows from len_e on are never written.  y, state_out and all status words are
+ * bit-identical to the untraced entry.  A clip that stops with S5FXP_ST_WIDE_INPUT leaves its trace rows untouched, like its y
+ * rows; len_e == 0 writes nothing.  One launch of the TRACE form of the clip kernel, a diagnostic path: the stages store the
+ * values they hold, and the trace pointers travel as kernel arguments, so a model of more than 8 layers gets
+ * S5FXP_EUNSUPPORTED before the device is touched.  traces == NULL is S5FXP_EBADARG (the untraced entries are the way to run
+ * without traces); every other check and error is that of s5fxp_model_clips. */
+int s5fxp_model_clips_traced(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int n, int Lmax, const int32_t *lens,
+                             int32_t *y, const int32_t *state_in, int32_t *state_out, void *workspace, size_t workspace_bytes,
+                             int32_t *status, const s5fxp_layer_trace *traces, void *stream);
+int s5fxp_model_clips_traced_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int n, int Lmax, const int32_t *lens,
+                                 float *y, const int32_t *state_in, int32_t *state_out, void *workspace, size_t workspace_bytes,
+                                 int32_t *status, const s5fxp_layer_trace *traces, void *stream);
 
 /* FxpSequenceLayer.forward, fxpmodel.py:1110-1161, for layer `layer` of a created model -- the unit the reference's
  * verification walks (fxprun.py:583-727).  x: (B,L,H) int32 device with configuration (x_bits, x_exp); y: (B,L,H) int32
@@ -775,6 +791,16 @@ int s5fxp_float_model_forward_fq(const s5fxp_float_model *m, const float *x, int
 int s5fxp_float_model_clips_fq(const s5fxp_float_model *m, const float *x, int n, int Lmax, const int32_t *lens, float *y,
                                float *stats, const s5fxp_float_fq_site *fq, void *workspace, size_t workspace_bytes,
                                void *stream);
+/* The clip forward WITH TRACE PLANES, with or without fake quantisation (fq may be NULL; no histogram is
+ * offered).  trace: s5fxp_float_trace_bytes(m, n, Lmax) bytes, never NULL (S5FXP_EBADARG); workspace:
+ * s5fxp_float_workspace_bytes(m, n, Lmax, 1), so every layer's Bu and xs stay there, as in the rectangular traced forward.
+ * Every plane is padded like y.  Rows t < len_e of h_enc (the workspace's first plane), of u / y / g_in / g / h' and of Bu / xs
+ * of every layer are bit for bit those of s5fxp_float_model_forward[_fq] with a trace on clip e alone; rows from len_e on are
+ * never written.  y and stats are bit-identical to s5fxp_float_model_clips[_fq].  S5FXP_FQ_STEP layers run s5fxp_fq_scan_c64
+ * with lens.  Every other argument and error as s5fxp_float_model_clips_fq. */
+int s5fxp_float_model_clips_traced(const s5fxp_float_model *m, const float *x, int n, int Lmax, const int32_t *lens, float *y,
+                                   float *stats, const s5fxp_float_fq_site *fq, float *trace, void *workspace,
+                                   size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Stage errors: two sides of a forward compared where they lie (csrc/stage_err.hpp).  One call compares up to
@@ -832,6 +858,37 @@ typedef struct {
 size_t s5fxp_stage_err_workspace_bytes(int n_pairs);
 int s5fxp_stage_err(const s5fxp_stage_pair *pairs_host, int n_pairs, s5fxp_stage_err_rec *out_dev, void *workspace,
                     size_t workspace_bytes, void *stream);
+
+/* The same comparison over CLIPS OF DIFFERENT LENGTHS (k_stage_err_clips).  A pair is a box (nb = clips, rows,
+ * cols) of two PADDED planes, as both traced clip forwards leave them, plus
+ *   lens          nb int32 in device memory: clip b of the box reads lens[b];
+ *   row0          the frame index of the box's row 0 inside its clip (a time bucket t0..t1 is row0 = t0, rows = t1 - t0);
+ *   a_exp_dev, a_exp_stride   device memory or NULL.  When set, the integer side of clip b has the exponent
+ *                 a_exp_dev[b * a_exp_stride], read on the device -- word 8 + 8 l + k of the clips' status words with stride
+ *                 S5FXP_STATUS_WORDS gives every clip its own compute_best exponent -- and box.a_exp is ignored; with NULL
+ *                 box.a_exp is used, as in s5fxp_stage_err.  Ignored for a float32 a.
+ * Element (b, r, c) is compared iff row0 + r < lens[b].  Elements outside belong to no count and are NEVER READ: the padding
+ * of the planes may hold anything, NaN and poison included.  rec.n is the number of elements inside.  A clip whose device
+ * exponent is outside 0..40 contributes its elements to n and n_nonfinite and to nothing else.  The per-element arithmetic,
+ * the record, the two launches (the finalize kernel is s5fxp_stage_err's), no floating-point atomics and identical bits from
+ * run to run, and the 4096-pair cap are those of s5fxp_stage_err; the wrap rule is applied to the PADDED box.  One pair per
+ * stage over all clips is by="stage"; the same box with nb = 1 and lens + e is one clip.
+ * workspace: s5fxp_stage_err_clips_workspace_bytes(n_pairs), 256-byte aligned (the descriptors are larger than
+ * s5fxp_stage_err's; the partial records are the same).
+ * S5FXP_EBADARG, before the device is touched: what s5fxp_stage_err refuses (a_exp only without a_exp_dev), a null lens on a
+ * pair with elements, a negative row0, a non-zero reserved.  S5FXP_EWORKSPACE for a workspace that is too small. */
+struct s5fxp_stage_pair_clips {
+    s5fxp_stage_pair box;     /* nb = clips; a_stride[0] / b_stride[0]: from one clip to the next */
+    const int32_t *lens;      /* device */
+    const int32_t *a_exp_dev; /* device or NULL */
+    int64_t a_exp_stride;     /* int32 words */
+    int32_t row0;
+    int32_t reserved;         /* 0 */
+};                            /* 120 bytes */
+typedef struct s5fxp_stage_pair_clips s5fxp_stage_pair_clips;
+size_t s5fxp_stage_err_clips_workspace_bytes(int n_pairs);
+int s5fxp_stage_err_clips(const s5fxp_stage_pair_clips *pairs_host, int n_pairs, s5fxp_stage_err_rec *out_dev, void *workspace,
+                          size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

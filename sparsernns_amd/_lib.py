@@ -108,6 +108,7 @@ class FloatModelDesc(C.Structure):
 STAGE_I32, STAGE_F32 = 0, 1   # s5fxp_stage_pair.a_kind
 STAGE_RELU_A = 1              # s5fxp_stage_pair.flags
 STAGE_MAX_PAIRS = 4096
+CLIPS_TRACED_MAX_LAYERS = 8   # s5fxp_model_clips_traced: the kernel-argument table of trace pointers
 
 
 class StagePair(C.Structure):
@@ -210,6 +211,12 @@ def _load():
         "s5fxp_float_model_clips_fq": (i, [p, p, i, i, p, p, p, p, p, C.c_size_t, p]),
         "s5fxp_stage_err_workspace_bytes": (C.c_size_t, [i]),
         "s5fxp_stage_err": (i, [C.POINTER(StagePair), i, p, p, C.c_size_t, p]),
+        "s5fxp_model_clips_traced": (i, [p, p, i, i, i, i, p, p, p, p, p, C.c_size_t, p, C.POINTER(LayerTrace), p]),
+        "s5fxp_model_clips_traced_f32": (i, [p, p, i, i, i, i, p, p, p, p, p, C.c_size_t, p, C.POINTER(LayerTrace), p]),
+        "s5fxp_float_model_clips_traced": (i, [p, p, i, i, p, p, p, p, p, p, C.c_size_t, p]),
+        "s5fxp_stage_err_clips_workspace_bytes": (C.c_size_t, [i]),
+        # pairs_host: an array of verify.StagePairClips (s5fxp_stage_pair_clips, 120 bytes)
+        "s5fxp_stage_err_clips": (i, [p, i, p, p, C.c_size_t, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale: rebuild
@@ -234,7 +241,9 @@ EXPORTED_SYMBOLS = ("s5fxp_version s5fxp_strerror s5fxp_from_fp s5fxp_to_float s
                     "s5fxp_float_workspace_bytes s5fxp_float_trace_bytes s5fxp_float_model_forward "
                     "s5fxp_float_model_forward_hist s5fxp_float_model_clips "
                     "s5fxp_float_model_forward_fq s5fxp_float_model_clips_fq "
-                    "s5fxp_stage_err_workspace_bytes s5fxp_stage_err").split()
+                    "s5fxp_stage_err_workspace_bytes s5fxp_stage_err "
+                    "s5fxp_model_clips_traced s5fxp_model_clips_traced_f32 s5fxp_float_model_clips_traced "
+                    "s5fxp_stage_err_clips_workspace_bytes s5fxp_stage_err_clips").split()
 
 
 def check(rc: int, what: str = "") -> None:

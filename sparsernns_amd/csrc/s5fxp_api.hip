@@ -1400,10 +1400,10 @@ constexpr long long FM_GRID_CAP = 512; // workgroups per launch: the weights are
 
 // Local to float_forward<CLIPS> (they use its m, trace and CLIPS) and undefined behind it.  FM_AT_DS: the kernel template k at
 // dim_scale ds; what follows are k's template arguments after DS.  FM_K / FM_K_TRACE: the stage kernel of the launch that
-// runs, at the model's DS -- `rect` (FM_K_TRACE: rect<DS, trace>) or `clip` (the clip forms have no traced kernels:
-// clip<DS, false>).  The other one sits in a discarded statement, so float_forward<true> names no traced clip kernel, which
-// would create it.  The code object lays kernels out in the order the host code first names them; this keeps it: DS 1..4,
-// traced before untraced, every rectangular kernel before the first clip one.
+// runs, at the model's DS -- `rect` or `clip`, FM_K_TRACE: k<DS, trace>; FM_K_TRACE_HIST: the same for the histogram forms,
+// whose clip kernels have no traced instantiation (clip<DS, false>: s5fxp_float_model_clips_traced offers no histogram).  The
+// other one sits in a discarded statement, so float_forward<true> names no traced clip histogram kernel, which would create
+// it.  The code object lays kernels out in the order the host code first names them: DS 1..4, traced before untraced.
 #define FM_AT_DS(ds, k, ...) \
     ((ds) <= 2 ? ((ds) == 1 ? k<1, ##__VA_ARGS__> : k<2, ##__VA_ARGS__>) : ((ds) == 3 ? k<3, ##__VA_ARGS__> : k<4, ##__VA_ARGS__>))
 #define FM_RECT_OR_CLIP(rect, clip)       \
@@ -1412,7 +1412,10 @@ constexpr long long FM_GRID_CAP = 512; // workgroups per launch: the weights are
         else return rect;                 \
     }()
 #define FM_K(rect, clip) FM_RECT_OR_CLIP(FM_AT_DS(m->DS, rect), FM_AT_DS(m->DS, clip))
-#define FM_K_TRACE(rect, clip) \
+#define FM_K_TRACE(rect, clip)                                                                          \
+    FM_RECT_OR_CLIP((trace ? FM_AT_DS(m->DS, rect, true) : FM_AT_DS(m->DS, rect, false)), \
+                    (trace ? FM_AT_DS(m->DS, clip, true) : FM_AT_DS(m->DS, clip, false)))
+#define FM_K_TRACE_HIST(rect, clip) \
     FM_RECT_OR_CLIP((trace ? FM_AT_DS(m->DS, rect, true) : FM_AT_DS(m->DS, rect, false)), FM_AT_DS(m->DS, clip, false))
 
 // What the rectangular launch (B sequences of L rows) and the clip launch (B clips padded to L rows, lens[e] of them real)
@@ -1498,7 +1501,7 @@ int fq_plan(const s5fxp_float_fq_site *fq, int n_layers, FqPlan &plan)
 }
 
 // The one forward of the five entries, rectangular (B sequences of L rows) or, with CLIPS, B clips padded to L rows of which
-// lens[e] are real (no trace planes).  hist == nullptr launches exactly the kernels without the histogram, and
+// lens[e] are real (trace planes: 4x, padded like y, never together with hist).  hist == nullptr launches exactly the kernels without the histogram, and
 // fq == nullptr or all off exactly those without fake quantisation (the two are never given together).  A layer whose state
 // sites are in step mode runs k_scan_fq_c64 in place of the associative scan; every other launch is unchanged.
 template <bool CLIPS>
@@ -1508,6 +1511,7 @@ int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, cons
 {
     if (!m || !x || !y || (CLIPS && !lens) || !workspace || B < 1 || L < 1) return S5FXP_EBADARG;
     if (reinterpret_cast<uintptr_t>(hist) % sizeof(unsigned long long)) return S5FXP_EBADARG;
+    if (CLIPS && hist && trace) return S5FXP_EBADARG; // the clip histogram kernels have no traced form
     FqPlan qp;
     if (fq_plan(fq, m->n_layers, qp)) return S5FXP_EBADARG;
     const FmTiling t = fm_tiling(B, L, CLIPS, lens);
@@ -1542,7 +1546,7 @@ int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, cons
         unsigned long long *lh = hist ? hist + (size_t)(2 + 10 * i) * FM_HIST_BINS : nullptr;
         FBprojArgs ba{h, l.nm, l.bcat, bu, tr, lo, N};
         if (qp.any) fm_launch<CLIPS>(t, st, FM_K_TRACE(k_fbproj_fq, k_fbproj_clips_fq), ba, qp.bproj(i));
-        else if (hist) fm_launch<CLIPS>(t, st, FM_K_TRACE(k_fbproj_hist, k_fbproj_clips_hist), ba, lh);
+        else if (hist) fm_launch<CLIPS>(t, st, FM_K_TRACE_HIST(k_fbproj_hist, k_fbproj_clips_hist), ba, lh);
         else fm_launch<CLIPS>(t, st, FM_K_TRACE(k_fbproj, k_fbproj_clips), ba);
         if ((rc = launch_rc())) return rc;
         if (qp.step(i)) {
@@ -1560,7 +1564,7 @@ int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, cons
                      tr ? tr + 3 * NH : nullptr, lo ? lo + 3 : nullptr, N};
         unsigned long long *gh = lh ? lh + 3 * FM_HIST_BINS : nullptr;
         if (qp.any) fm_launch<CLIPS>(t, st, FM_K_TRACE(k_fgate_fq, k_fgate_clips_fq), ga, qp.gate(i));
-        else if (hist) fm_launch<CLIPS>(t, st, FM_K_TRACE(k_fgate_hist, k_fgate_clips_hist), ga, gh);
+        else if (hist) fm_launch<CLIPS>(t, st, FM_K_TRACE_HIST(k_fgate_hist, k_fgate_clips_hist), ga, gh);
         else fm_launch<CLIPS>(t, st, FM_K_TRACE(k_fgate, k_fgate_clips), ga);
         if ((rc = launch_rc())) return rc;
         h = hout;
@@ -1576,6 +1580,7 @@ int float_forward(const s5fxp_float_model *m, const float *x, int B, int L, cons
 #undef FM_RECT_OR_CLIP
 #undef FM_K
 #undef FM_K_TRACE
+#undef FM_K_TRACE_HIST
 
 } // namespace
 
@@ -1732,6 +1737,72 @@ extern "C" int s5fxp_stage_err(const s5fxp_stage_pair *pairs_host, int n_pairs, 
     hipLaunchKernelGGL(stage::k_stage_err_finalize, dim3((unsigned)n_pairs), dim3(stage::TPB), 0, S(stream), partials, wgs,
                        reinterpret_cast<unsigned long long *>(out_dev));
     return launch_rc();
+}
+
+// The ragged form: the same two launches over padded boxes, masked by the clips' lengths on the device.
+namespace {
+constexpr size_t stage_clips_desc_bytes(int n_pairs) { return ((size_t)n_pairs * sizeof(stage::DevPairClips) + 255) / 256 * 256; }
+static_assert(sizeof(s5fxp_stage_pair_clips) == 120, "s5fxp_stage_pair_clips is 120 bytes (include/s5fxp.h, verify.StagePairClips)");
+} // namespace
+
+extern "C" size_t s5fxp_stage_err_clips_workspace_bytes(int n_pairs)
+{
+    if (n_pairs < 1 || n_pairs > 4096) return 0;
+    return stage_clips_desc_bytes(n_pairs) + (size_t)n_pairs * stage::stage_wgs_cap(n_pairs) * sizeof(s5fxp_stage_err_rec);
+}
+
+extern "C" int s5fxp_stage_err_clips(const s5fxp_stage_pair_clips *pairs_host, int n_pairs, s5fxp_stage_err_rec *out_dev,
+                                     void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!pairs_host || !out_dev || !workspace || n_pairs < 1 || n_pairs > 4096) return S5FXP_EBADARG;
+    const int cap = stage::stage_wgs_cap(n_pairs);
+    std::vector<stage::DevPairClips> dev((size_t)n_pairs);
+    uint64_t n_max = 0;
+    for (int i = 0; i < n_pairs; ++i) {
+        const s5fxp_stage_pair_clips &pc = pairs_host[i];
+        const s5fxp_stage_pair &p = pc.box;
+        if (p.a_kind != S5FXP_STAGE_I32 && p.a_kind != S5FXP_STAGE_F32) return S5FXP_EBADARG;
+        if (p.flags & ~S5FXP_STAGE_RELU_A) return S5FXP_EBADARG;
+        if (p.a_kind == S5FXP_STAGE_I32 && !pc.a_exp_dev && (p.a_exp < 0 || p.a_exp > 40)) return S5FXP_EBADARG;
+        if (p.nb < 0 || p.rows < 0 || p.cols < 0 || pc.row0 < 0 || pc.reserved) return S5FXP_EBADARG;
+        const unsigned __int128 n = (unsigned __int128)p.nb * (unsigned)p.rows * (unsigned)p.cols;
+        if (n && (!p.a || !p.b || !pc.lens)) return S5FXP_EBADARG;
+        // the wrap rule of s5fxp_stage_err, on the padded box
+        if (n > (unsigned __int128)cap * 0xffffff00ull) return S5FXP_EBADARG;
+        stage::DevPairClips &dc = dev[i];
+        stage::DevPair &d = dc.box;
+        d.a = static_cast<const uint32_t *>(p.a), d.b = p.b;
+        for (int k = 0; k < 3; ++k) d.as[k] = p.a_stride[k], d.bs[k] = p.b_stride[k];
+        d.n = (uint64_t)n;
+        d.scale = p.a_kind == S5FXP_STAGE_I32 && !pc.a_exp_dev ? std::ldexp(1.0, -p.a_exp) : 1.0;
+        d.rows = (uint32_t)p.rows, d.cols = (uint32_t)p.cols;
+        d.f32 = p.a_kind == S5FXP_STAGE_F32, d.relu = (p.flags & S5FXP_STAGE_RELU_A) != 0;
+        dc.lens = pc.lens, dc.a_exp_dev = pc.a_exp_dev, dc.a_exp_stride = pc.a_exp_stride, dc.row0 = pc.row0, dc.pad = 0;
+        n_max = std::max(n_max, d.n);
+    }
+    if (workspace_bytes < s5fxp_stage_err_clips_workspace_bytes(n_pairs)) return S5FXP_EWORKSPACE;
+    const uint64_t want = (n_max + stage::WG_MIN_ELEMS - 1) / stage::WG_MIN_ELEMS;
+    const int wgs = (int)std::min<uint64_t>((uint64_t)cap, std::max<uint64_t>(want, 1));
+    char *ws = static_cast<char *>(workspace);
+    auto *partials = reinterpret_cast<unsigned long long *>(ws + stage_clips_desc_bytes(n_pairs));
+    // pageable-memory async copies are staged by the runtime before returning, so `dev` may go
+    if (const int rc = hip_rc(hipMemcpyAsync(ws, dev.data(), dev.size() * sizeof(stage::DevPairClips), hipMemcpyHostToDevice, S(stream))))
+        return rc;
+    hipLaunchKernelGGL(stage::k_stage_err_clips, dim3((unsigned)wgs, (unsigned)n_pairs), dim3(stage::TPB), 0, S(stream),
+                       reinterpret_cast<const stage::DevPairClips *>(ws), partials);
+    hipLaunchKernelGGL(stage::k_stage_err_finalize, dim3((unsigned)n_pairs), dim3(stage::TPB), 0, S(stream), partials, wgs,
+                       reinterpret_cast<unsigned long long *>(out_dev));
+    return launch_rc();
+}
+
+// The clip forward with trace planes: the TRACE instantiations of k_fbproj_clips[_fq] / k_fgate_clips[_fq]; Bu
+// and xs of every layer stay in the workspace, as in the rectangular traced forward.
+extern "C" int s5fxp_float_model_clips_traced(const s5fxp_float_model *m, const float *x, int n, int Lmax, const int32_t *lens,
+                                              float *y, float *stats, const s5fxp_float_fq_site *fq, float *trace, void *workspace,
+                                              size_t workspace_bytes, void *stream)
+{
+    if (!trace) return S5FXP_EBADARG;
+    return float_forward<true>(m, x, n, Lmax, lens, y, stats, nullptr, fq, trace, workspace, workspace_bytes, stream);
 }
 
 #ifdef S5_PHASE_PROF

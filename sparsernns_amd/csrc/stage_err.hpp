@@ -195,6 +195,152 @@ __global__ __launch_bounds__(TPB) void k_stage_err(const DevPair *__restrict__ p
     }
 }
 
+// ---- clips: the same comparison over a padded box of which clip b holds lens[b] frames ----
+//
+//   k_stage_err_clips     k_stage_err's grid, shares and reductions over the PADDED box (nb = clips, rows, cols): a workgroup
+//                         walks its share of the padded index space and compares element (b, r, c) iff row0 + r < lens[b];
+//                         an element outside is never read and belongs to no count, so word 0 of a partial is the number of
+//                         elements inside.  With a_exp_dev the integer side of clip b has the exponent
+//                         a_exp_dev[b * a_exp_stride], read on the device; an exponent outside 0..40 sends the clip's elements to
+//                         n and n_nonfinite and to nothing else.  Finalised by k_stage_err_finalize.
+struct DevPairClips {
+    DevPair box;
+    const int32_t *lens;      // nb, device memory
+    const int32_t *a_exp_dev; // or nullptr: box.scale
+    int64_t a_exp_stride;
+    int32_t row0, pad;
+};
+
+__global__ __launch_bounds__(TPB) void k_stage_err_clips(const DevPairClips *__restrict__ pairs, unsigned long long *__restrict__ partials)
+{
+#pragma clang fp contract(off)
+    __shared__ unsigned sh_hist[2 * FM_HIST_BINS * COPIES];
+    __shared__ double sh_d[TPB / 64][6];
+    __shared__ unsigned sh_c[TPB / 64][4];
+    const int tid = threadIdx.x;
+    const DevPairClips pc = pairs[blockIdx.y];
+    const DevPair &p = pc.box;
+    for (int i = tid; i < 2 * FM_HIST_BINS * COPIES; i += TPB) sh_hist[i] = 0;
+    __syncthreads();
+
+    const uint64_t share = stage_share(p.n, (int)gridDim.x);
+    const uint64_t lo = (uint64_t)blockIdx.x * share;
+    const uint64_t begin = lo < p.n ? lo : p.n, end = begin + share < p.n ? begin + share : p.n;
+    const uint32_t count = (uint32_t)(end - begin); // of the padded box; below 2^32 by the wrap rule
+    const uint32_t iters = (uint32_t)tid < count ? (count - tid + TPB - 1) / TPB : 0;
+
+    double sum_abs = 0, sum_sq = 0, max_abs = 0, sum_ref = 0, sum_rel = 0, max_rel = 0;
+    unsigned n_in = 0, n_nonfin = 0, n_equal = 0, n_nz = 0;
+
+    if (iters) {
+        // k_stage_err's walk, with the clip index carried along
+        const uint64_t e0 = begin + tid, r0 = e0 / p.cols, b0 = r0 / p.rows;
+        uint32_t c = (uint32_t)(e0 - r0 * p.cols), row = (uint32_t)(r0 - b0 * p.rows), b = (uint32_t)b0;
+        int64_t oa = (int64_t)b0 * p.as[0] + (int64_t)row * p.as[1] + (int64_t)c * p.as[2];
+        int64_t ob = (int64_t)b0 * p.bs[0] + (int64_t)row * p.bs[1] + (int64_t)c * p.bs[2];
+        const uint32_t step_r = TPB / p.cols, step_c = TPB - step_r * p.cols;
+        const uint32_t step_b = step_r / p.rows, step_rr = step_r - step_b * p.rows;
+        const int64_t da = (int64_t)step_b * p.as[0] + (int64_t)step_rr * p.as[1] + (int64_t)step_c * p.as[2];
+        const int64_t db = (int64_t)step_b * p.bs[0] + (int64_t)step_rr * p.bs[1] + (int64_t)step_c * p.bs[2];
+        const int64_t da_c = p.as[1] - (int64_t)p.cols * p.as[2], db_c = p.bs[1] - (int64_t)p.cols * p.bs[2]; // column wrap
+        const int64_t da_r = p.as[0] - (int64_t)p.rows * p.as[1], db_r = p.bs[0] - (int64_t)p.rows * p.bs[1]; // row wrap
+        unsigned *const h_abs = sh_hist + (tid & (COPIES - 1)), *const h_rel = h_abs + FM_HIST_BINS * COPIES;
+
+        for (uint32_t k = 0; k < iters; k += UNROLL) {
+            uint32_t ua[UNROLL];
+            float fb[UNROLL];
+            double sc[UNROLL]; // the clip's 2^-exponent; < 0: outside 0..40
+            bool in[UNROLL];
+#pragma unroll
+            for (int j = 0; j < UNROLL; ++j) {
+                in[j] = false;
+                if (k + j < iters) {
+                    // row0 + row < 2^32: both are below 2^31
+                    const int32_t len = pc.lens[b];
+                    in[j] = len > 0 && (uint32_t)pc.row0 + row < (uint32_t)len;
+                    if (in[j]) {
+                        ua[j] = p.a[oa];
+                        fb[j] = p.b[ob];
+                        sc[j] = p.scale;
+                        if (pc.a_exp_dev && !p.f32) {
+                            const int32_t ex = pc.a_exp_dev[(int64_t)b * pc.a_exp_stride];
+                            sc[j] = ex < 0 || ex > 40 ? -1.0 : __longlong_as_double((long long)(1023 - ex) << 52);
+                        }
+                    }
+                }
+                c += step_c, row += step_rr, b += step_b, oa += da, ob += db;
+                if (c >= p.cols) c -= p.cols, ++row, oa += da_c, ob += db_c;
+                if (row >= p.rows) row -= p.rows, ++b, oa += da_r, ob += db_r;
+            }
+#pragma unroll
+            for (int j = 0; j < UNROLL; ++j) {
+                if (!in[j]) continue;
+                ++n_in;
+                double va;
+                bool finite = sc[j] >= 0.0;
+                if (p.f32) {
+                    const float af = __uint_as_float(ua[j]);
+                    finite = (ua[j] & 0x7f800000u) != 0x7f800000u;
+                    va = (double)af;
+                } else {
+                    va = (double)(int32_t)ua[j] * sc[j];
+                }
+                if ((__float_as_uint(fb[j]) & 0x7f800000u) == 0x7f800000u) finite = false;
+                if (!finite) {
+                    ++n_nonfin;
+                    continue;
+                }
+                if (p.relu && va < 0.0) va = 0.0;
+                const double vb = (double)fb[j];
+                const double e = fabs(va - vb);
+                sum_abs += e;
+                sum_sq += e * e;
+                sum_ref += vb * vb;
+                max_abs = e > max_abs ? e : max_abs;
+                n_equal += e == 0.0;
+                atomicAdd(h_abs + fm_hist_bin((float)e) * COPIES, 1u);
+                if (vb != 0.0) {
+                    const double rel = e / fabs(vb);
+                    ++n_nz;
+                    sum_rel += rel;
+                    max_rel = rel > max_rel ? rel : max_rel;
+                    atomicAdd(h_rel + fm_hist_bin((float)rel) * COPIES, 1u);
+                }
+            }
+        }
+    }
+
+    // lanes by shuffles, waves through LDS, in index order
+    const int wave = tid >> 6, lane = tid & 63;
+    const double d[6] = {wave_sum(sum_abs), wave_sum(sum_sq), wave_max(max_abs), wave_sum(sum_ref), wave_sum(sum_rel), wave_max(max_rel)};
+    const unsigned cn[4] = {wave_sum(n_in), wave_sum(n_nonfin), wave_sum(n_equal), wave_sum(n_nz)};
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) sh_d[wave][i] = d[i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sh_c[wave][i] = cn[i];
+    }
+    __syncthreads();
+    unsigned long long *out = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * REC_WORDS;
+    if (tid < 2 * FM_HIST_BINS) { // hist_abs then hist_rel, as the LDS planes lie
+        unsigned long long n = 0;
+#pragma unroll
+        for (int cpy = 0; cpy < COPIES; ++cpy) n += sh_hist[tid * COPIES + cpy];
+        out[W_HIST + tid] = n;
+    } else if (tid < 2 * FM_HIST_BINS + 6) {
+        const int i = tid - 2 * FM_HIST_BINS;
+        double v = sh_d[0][i];
+        const bool is_max = i == 2 || i == 5;
+        for (int w = 1; w < TPB / 64; ++w) v = is_max ? (sh_d[w][i] > v ? sh_d[w][i] : v) : v + sh_d[w][i];
+        out[W_SUM_ABS + i] = (unsigned long long)__double_as_longlong(v);
+    } else if (tid < 2 * FM_HIST_BINS + 10) { // n, n_nonfinite, n_equal, n_ref_nonzero: words 0..3
+        const int i = tid - (2 * FM_HIST_BINS + 6);
+        unsigned long long v = 0;
+        for (int w = 0; w < TPB / 64; ++w) v += sh_c[w][i];
+        out[i] = v;
+    }
+}
+
 // grid = pairs, REC_WORDS threads at least: thread w folds word w of the pair's `wgs` partials in index order
 __global__ __launch_bounds__(TPB) void k_stage_err_finalize(const unsigned long long *__restrict__ partials, int wgs,
                                                             unsigned long long *__restrict__ out)

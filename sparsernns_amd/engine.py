@@ -501,6 +501,21 @@ class Engine:
         of mixed lengths up to 512 frames; 10 .. 19 times faster than per-clip forwards from 256 clips on.  A single clip
         never pays (32 frames: 127 against 93 us; 2048 frames: 6.8 against 0.15 ms): it belongs on ``forward``, which spreads
         it over the chip.  Clips that share one length are 3.6 .. 4 times faster on ``forward_batches``."""
+        return self._clips_launch(x, lens, y, state, state_out, x_bits, x_exp, lane, False, None)[0]
+
+    def clips_traced(self, x, lens: torch.Tensor, y: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
+                     state_out: Optional[torch.Tensor] = None, x_bits: Optional[int] = None, x_exp: Optional[int] = None,
+                     lane=0, traces: Optional[List[Dict[str, torch.Tensor]]] = None):
+        """``clips`` with the eleven trace planes of every layer (``s5fxp_model_clips_traced[_f32]``): still ONE
+        launch, enqueue only, no sync.  Returns ``(y, traces)``: ``traces[l][k]`` for ``k`` in ``TRACE_FIELDS`` is an int32 plane
+        padded like y, (n, Lmax, H) or (n, Lmax, P) for ``Bu_*`` / ``xs_*``; rows t < lens[e] of clip e are bit for bit what
+        ``forward(x[e, :len], traces=True)`` stores, rows from lens[e] on are never written (``torch.empty`` unless `traces`
+        hands in the planes).  y, the carry and the status words are those of ``clips``.  A diagnostic path: the traced kernel
+        stores 11 planes per layer and is slower than ``clips``."""
+        return self._clips_launch(x, lens, y, state, state_out, x_bits, x_exp, lane, True, traces)
+
+    def _clips_launch(self, x, lens, y, state, state_out, x_bits, x_exp, lane, traced: bool, traces):
+        """The checks and the one launch behind ``clips`` and ``clips_traced`` -> (y, the trace planes or None)."""
         if isinstance(x, FxpArray):
             x_bits, x_exp, x = x.bits, x.exp, x.data
         f32 = x.dtype == torch.float32
@@ -521,14 +536,32 @@ class Engine:
         for name, t in (("state", state), ("state_out", state_out)):
             if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != want or not t.is_contiguous() or not t.is_cuda):
                 raise ValueError(f"{name} must be a contiguous int32 device tensor of shape {want}")
+        tail = ()
+        if traced:
+            if traces is None:
+                traces = [self._trace_planes(x) for _ in range(self.n_layers)]
+            if len(traces) != self.n_layers:
+                raise ValueError(f"traces must have {self.n_layers} entries, got {len(traces)}")
+            tr = (LayerTrace * self.n_layers)()
+            for t, planes in zip(tr, traces):
+                for k in TRACE_FIELDS:
+                    pl = planes.get(k)
+                    if pl is None:
+                        continue
+                    w = self.P if k in ("Bu_re", "Bu_im", "xs_re", "xs_im") else self.H
+                    if pl.dtype != torch.int32 or tuple(pl.shape) != (n, Lmax, w) or not pl.is_contiguous() or pl.device != x.device:
+                        raise ValueError(f"trace plane {k} must be a contiguous int32 device tensor of shape {(n, Lmax, w)}")
+                    setattr(t, k, pl.data_ptr())
+            tail = (tr,)
         so = state_out if state_out is not None else state
         ws = self._clips_workspace(n, Lmax, lane)
         self._groups[lane] = n
-        entry, name = (lib.s5fxp_model_clips_f32, "s5fxp_model_clips_f32") if f32 else (lib.s5fxp_model_clips, "s5fxp_model_clips")
-        check(entry(self._h, x.data_ptr(), xb, xe, n, Lmax, lens.data_ptr(), y.data_ptr(),
-                    state.data_ptr() if state is not None else None, so.data_ptr() if so is not None else None,
-                    ws.data_ptr(), ws.numel(), self.lane_status(lane, n).data_ptr(), torch.cuda.current_stream().cuda_stream), name)
-        return y
+        name = "s5fxp_model_clips" + ("_traced" if traced else "") + ("_f32" if f32 else "")
+        check(getattr(lib, name)(self._h, x.data_ptr(), xb, xe, n, Lmax, lens.data_ptr(), y.data_ptr(),
+                                 state.data_ptr() if state is not None else None, so.data_ptr() if so is not None else None,
+                                 ws.data_ptr(), ws.numel(), self.lane_status(lane, n).data_ptr(), *tail,
+                                 torch.cuda.current_stream().cuda_stream), name)
+        return y, traces
 
     def _forward_clips(self, xs, dtype: torch.dtype, xb: int, xe: int, lane) -> List[torch.Tensor]:
         """Pads the clips (each (L_e, d_in) of `dtype`), launches once, reads the status once; a clip the 16-bit planes

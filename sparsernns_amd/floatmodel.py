@@ -266,9 +266,10 @@ class FloatEngine:
             ws = self._ws[trace] = torch.empty(n, dtype=torch.float32, device=self.device)
         return ws
 
-    def _device_forward(self, clips: bool, x, lens, stats_dev, hist_dev, out, trace: bool, fq):
-        """The one device forward behind ``forward_device`` and ``forward_clips_device``: the checks of every argument, the
-        buffers and the C entry that serves the form -> (y, trace buffer or None, workspace)."""
+    def _device_forward(self, clips: bool, x, lens, stats_dev, hist_dev, out, trace: bool, fq, trace_buf=None):
+        """The one device forward behind ``forward_device``, ``forward_clips_device`` and ``forward_clips_traced``: the checks of
+        every argument, the buffers and the C entry that serves the form -> (y, trace buffer or None, workspace).  ``trace_buf``:
+        the trace buffer to write into instead of a fresh one."""
         if not self.on_device:
             raise RuntimeError(f"FloatEngine.{'forward_clips_device' if clips else 'forward_device'} needs the kernels (on_device is False)")
         fq = self._fq_arg(fq, hist_dev)
@@ -293,12 +294,19 @@ class FloatEngine:
         lens = lens.contiguous() if clips else None  # both held until the launches are enqueued
         y = out if out is not None else torch.empty(shape, dtype=torch.float32, device=self.device)
         ws = self._workspace(B, L, trace)
-        tr = torch.empty(lib.s5fxp_float_trace_bytes(self._h, B, L) // 4, dtype=torch.float32, device=self.device) if trace else None
+        nt = lib.s5fxp_float_trace_bytes(self._h, B, L) // 4
+        if trace_buf is not None and (not trace or trace_buf.dtype != torch.float32 or trace_buf.numel() != nt
+                                      or trace_buf.device != self.device or not trace_buf.is_contiguous()):
+            raise ValueError(f"trace_buf must be {nt} contiguous float32 on {self.device}, of a traced forward")
+        tr = trace_buf if trace_buf is not None else torch.empty(nt, dtype=torch.float32, device=self.device) if trace else None
         h, xp, yp, trp = self._h, x.data_ptr(), y.data_ptr(), None if tr is None else tr.data_ptr()
         st, hp = None if stats_dev is None else stats_dev.data_ptr(), None if hist_dev is None else hist_dev.data_ptr()
         with torch.cuda.device(self.device):
             tail = (ws.data_ptr(), ws.numel() * 4, torch.cuda.current_stream().cuda_stream)
-            if clips and fq is not None:
+            if clips and trace:  # with or without fq (forward_clips_traced: no histogram is offered)
+                check(lib.s5fxp_float_model_clips_traced(h, xp, B, L, lens.data_ptr(), yp, st, None if fq is None else fq.ctypes.data,
+                                                         trp, *tail), "s5fxp_float_model_clips_traced")
+            elif clips and fq is not None:
                 check(lib.s5fxp_float_model_clips_fq(h, xp, B, L, lens.data_ptr(), yp, st, fq.ctypes.data, *tail), "s5fxp_float_model_clips_fq")
             elif clips:
                 check(lib.s5fxp_float_model_clips(h, xp, B, L, lens.data_ptr(), yp, st, hp, *tail), "s5fxp_float_model_clips")
@@ -375,10 +383,17 @@ class FloatEngine:
         st = self.new_stats()
         hd = self.new_hist() if hist else None
         y, tr, ws = self.forward_device(xd, st, trace=True, hist_dev=hd, fq=fq)
-        NH, NP2 = B * L * self.H, B * L * 2 * self.P
-        out = dict(out=y, stats=st, h_enc=ws[:NH].view(B, L, self.H).clone())
+        out = self._planes(y, st, tr, ws)
         if hist:
             out["hist"] = hd
+        return out
+
+    def _planes(self, y, st, tr, ws) -> dict:
+        """The dict of ``forward_traced`` from a traced forward's output, observers, trace buffer and workspace; the planes that
+        live in the workspace are copied, the others are views of the trace buffer."""
+        B, L = int(y.shape[0]), int(y.shape[1])
+        NH, NP2 = B * L * self.H, B * L * 2 * self.P
+        out = dict(out=y, stats=st, h_enc=ws[:NH].view(B, L, self.H).clone())
         for i in range(self.n_layers):
             for j, name in enumerate(TRACE_PLANES):
                 out[f"l{i}.{name}"] = tr[(5 * i + j) * NH:(5 * i + j + 1) * NH].view(B, L, self.H)
@@ -386,6 +401,18 @@ class FloatEngine:
             out[f"l{i}.Bu"] = torch.view_as_complex(ws[base:base + NP2].view(B, L, self.P, 2).clone())
             out[f"l{i}.xs"] = torch.view_as_complex(ws[base + NP2:base + 2 * NP2].view(B, L, self.P, 2).clone())
         return out
+
+    def forward_clips_traced(self, x: torch.Tensor, lens: torch.Tensor, fq=None, out: Optional[torch.Tensor] = None,
+                             trace_buf: Optional[torch.Tensor] = None) -> dict:
+        """``forward_traced`` for n clips of different lengths (``s5fxp_float_model_clips_traced``): x
+        (n,Lmax,257) float32 on the device, padded; lens (n,) int32 on the device.  The keys are ``forward_traced``'s and every
+        plane is padded like x: rows t < len_e of clip e are bit for bit those of ``forward_traced(x[e:e+1, :len_e], fq=fq)``,
+        rows from len_e on are never written and hold whatever the buffers held.  ``out`` / ``trace_buf``
+        (``s5fxp_float_trace_bytes`` / 4 float32): the tensors to write into, fresh otherwise.  No histogram.  Stream-ordered,
+        no sync."""
+        st = self.new_stats() if self.on_device else None
+        y, tr, ws = self._device_forward(True, x, lens, st, None, out, True, fq, trace_buf)
+        return self._planes(y, st, tr, ws)
 
     def _to_device(self, x) -> torch.Tensor:
         if isinstance(x, torch.Tensor):
