@@ -614,6 +614,51 @@ int s5fxp_model_clips_traced_f32(const s5fxp_model *m, const float *x, int x_bit
                                  float *y, const int32_t *state_in, int32_t *state_out, void *workspace, size_t workspace_bytes,
                                  int32_t *status, const s5fxp_layer_trace *traces, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Stated exponents: the step, ragged step and clip launches with the five compute_best exponents of every layer given by
+ * the caller instead of chosen from the data of the launch.  A stream then gives the same bits however it
+ * is cut into steps, and those of s5fxp_model_clips_at on the whole signal at the same exponents; with the exponents an
+ * unpinned forward of the whole signal reports, it gives that forward's bits.
+ *   exps: 5 * n_layers int32 in HOST memory, read before the entry returns, in the order of the status words
+ *   [8 + 8*l + 0..4]: the result exponents of BN add(-mean), BN mul(invsq_var), BN mul(scale), BN add(bias) and the residual
+ *   add of layer l.  A slot whose op the layer lacks (no scale, no bias) is ignored.  Model-wide: every group, entry or clip
+ *   of the launch runs at it.
+ * Each _at entry is its namesake with `exps` in front of `stream` and computes what the namesake computes, each of the five
+ * ops using the stated exponent where the namesake finalizes one from a reduction (fxparray.py:420-448, 601-637 with
+ * result_exp given): the same carry, WIDE_INPUT rule, WIDE_STATE, padding rules, rows == 0 / len == 0 rules.  A value beyond
+ * the range an exponent leaves saturates at the op's result bits, as fxp_clip does.  Status words: [0] never carries NEGSHIFT
+ * or NEGEXP (both are refused here, on the host); [8+8l+0..4] hold the stated exponents, 0 for an op the layer lacks; all
+ * other words as the namesake writes them.  The kernels hold no maxima loop and no reduction.
+ * Checked before the device is touched: the namesake's checks, S5FXP_EBADARG for a null exps, then s5fxp_model_exps_check.
+ * Not served at stated exponents: s5fxp_model_forward* (a pinned batch is a clip list), the traced clip entries, exponents in
+ * device memory or per clip. */
+/* The largest exponent op k (0..4, the order above) of `layer` can take: its result bits - 1, the exponent of a result
+ * whose maximum is below 1 (intbits is never negative).  -1 for an op the layer lacks or a bad argument.  Any model. */
+int s5fxp_model_exp_max(const s5fxp_model *m, int layer, int k);
+/* Host only, never touches the device.  S5FXP_EBADARG: a null model or array; S5FXP_EUNSUPPORTED: a model
+ * s5fxp_model_is_fast() does not report, or one of more than 8 layers (the exponents travel as kernel arguments);
+ * S5FXP_EBADARG: an exponent outside 0 .. s5fxp_model_exp_max; S5FXP_ENEGSHIFT: a shift these exponents make negative or
+ * larger than 31 -- with stated exponents every one is static: what finalize_add_cb / finalize_mul_cb flag on the device
+ * (an add's operand and result shifts, a mul's right shift), the change_cfg to the SSM input, the decoder's input
+ * conversion and its right shift. */
+int s5fxp_model_exps_check(const s5fxp_model *m, const int32_t *exps_host);
+int s5fxp_model_step_at(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int G, int B, int L, int32_t *y,
+                        const int32_t *state_in, int32_t *state_out, int32_t *status, const int32_t *exps, void *stream);
+int s5fxp_model_step_at_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int G, int B, int L, float *y,
+                            const int32_t *state_in, int32_t *state_out, int32_t *status, const int32_t *exps, void *stream);
+int s5fxp_model_step_ragged_at(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int n, int B, int Lmax, int32_t *y,
+                               const s5fxp_push_desc *desc, int32_t *state, int n_slots, int32_t *status, const int32_t *exps,
+                               void *stream);
+int s5fxp_model_step_ragged_at_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int n, int B, int Lmax, float *y,
+                                   const s5fxp_push_desc *desc, int32_t *state, int n_slots, int32_t *status, const int32_t *exps,
+                                   void *stream);
+int s5fxp_model_clips_at(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int n, int Lmax, const int32_t *lens,
+                         int32_t *y, const int32_t *state_in, int32_t *state_out, void *workspace, size_t workspace_bytes,
+                         int32_t *status, const int32_t *exps, void *stream);
+int s5fxp_model_clips_at_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int n, int Lmax, const int32_t *lens,
+                             float *y, const int32_t *state_in, int32_t *state_out, void *workspace, size_t workspace_bytes,
+                             int32_t *status, const int32_t *exps, void *stream);
+
 /* FxpSequenceLayer.forward, fxpmodel.py:1110-1161, for layer `layer` of a created model -- the unit the reference's
  * verification walks (fxprun.py:583-727).  x: (B,L,H) int32 device with configuration (x_bits, x_exp); y: (B,L,H) int32
  * device, s5fxp_model_layer_out_bits() bits at the exponent the residual compute_best add chose: written to

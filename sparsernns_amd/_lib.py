@@ -217,6 +217,15 @@ def _load():
         "s5fxp_stage_err_clips_workspace_bytes": (C.c_size_t, [i]),
         # pairs_host: an array of verify.StagePairClips (s5fxp_stage_pair_clips, 120 bytes)
         "s5fxp_stage_err_clips": (i, [p, i, p, p, C.c_size_t, p]),
+        # stated exponents: the namesake's arguments with exps (host int32 array, 5 * n_layers) in front of the stream
+        "s5fxp_model_exp_max": (i, [p, i, i]),
+        "s5fxp_model_exps_check": (i, [p, p]),
+        "s5fxp_model_step_at": (i, [p, p, i, i, i, i, i, p, p, p, p, p, p]),
+        "s5fxp_model_step_at_f32": (i, [p, p, i, i, i, i, i, p, p, p, p, p, p]),
+        "s5fxp_model_step_ragged_at": (i, [p, p, i, i, i, i, i, p, p, p, i, p, p, p]),
+        "s5fxp_model_step_ragged_at_f32": (i, [p, p, i, i, i, i, i, p, p, p, i, p, p, p]),
+        "s5fxp_model_clips_at": (i, [p, p, i, i, i, i, p, p, p, p, p, C.c_size_t, p, p, p]),
+        "s5fxp_model_clips_at_f32": (i, [p, p, i, i, i, i, p, p, p, p, p, C.c_size_t, p, p, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale: rebuild
@@ -243,7 +252,9 @@ EXPORTED_SYMBOLS = ("s5fxp_version s5fxp_strerror s5fxp_from_fp s5fxp_to_float s
                     "s5fxp_float_model_forward_fq s5fxp_float_model_clips_fq "
                     "s5fxp_stage_err_workspace_bytes s5fxp_stage_err "
                     "s5fxp_model_clips_traced s5fxp_model_clips_traced_f32 s5fxp_float_model_clips_traced "
-                    "s5fxp_stage_err_clips_workspace_bytes s5fxp_stage_err_clips").split()
+                    "s5fxp_stage_err_clips_workspace_bytes s5fxp_stage_err_clips "
+                    "s5fxp_model_exp_max s5fxp_model_exps_check s5fxp_model_step_at s5fxp_model_step_at_f32 "
+                    "s5fxp_model_step_ragged_at s5fxp_model_step_ragged_at_f32 s5fxp_model_clips_at s5fxp_model_clips_at_f32").split()
 
 
 def check(rc: int, what: str = "") -> None:

@@ -351,11 +351,12 @@ def mask_istft_clips(audio: torch.Tensor, samples: torch.Tensor, mask, cleaned_m
     return (o, cm) if cleaned_mag else o
 
 
-def _clips_front(model, inp_bits: int, inp_exp: int, clips, lane):
+def _clips_front(model, inp_bits: int, inp_exp: int, clips, lane, exps=None):
     """What ``denoise_clips`` and ``validate_clips`` share in front of the inverse: the checks of the clip list, and on the
     one-launch route the padding, ``stft_mag_clips``, ``Engine.clips`` and the one read of the status words.  Returns
     (clips, front) with front = (audio, samples, x, mask, L) -- padded tensors and the frame counts -- or None where the clips
-    go through the per-clip functions (and for an empty list)."""
+    go through the per-clip functions (and for an empty list).  `exps`: stated exponents for ``Engine.clips``; only the one-launch
+    route honours them, so where that route is closed (or a clip comes back with ST_WIDE_INPUT) this raises."""
     clips = [torch.as_tensor(c) for c in clips]
     for c in clips:
         if c.dim() != 1:
@@ -369,6 +370,8 @@ def _clips_front(model, inp_bits: int, inp_exp: int, clips, lane):
                   and not getattr(model, "store_intermediates", False) and _takes(model, inp_bits, inp_exp)
                   and model.engine().clips_ok(Lmax))
     if not one_launch:
+        if exps is not None:
+            raise NotImplementedError("exps= needs the one-launch clip route: device clips and a model on the fused path")
         return clips, None
     from . import _lib
     eng, n = model.engine(), len(clips)
@@ -376,7 +379,7 @@ def _clips_front(model, inp_bits: int, inp_exp: int, clips, lane):
     samples = torch.tensor(Ts, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         x, lens = stft_mag_clips(audio, samples)
-        mask = eng.clips(x, lens, lane=lane)
+        mask = eng.clips(x, lens, lane=lane, exps=exps)
         st = eng.lane_status(lane, n)[:n * _lib.STATUS_WORDS].cpu().numpy().reshape(n, _lib.STATUS_WORDS)
         bad = int(np.bitwise_or.reduce(st[:, 0] & ~_lib.ST_WIDE_INPUT))
         if bad & _lib.ST_NEGSHIFT:
@@ -384,13 +387,16 @@ def _clips_front(model, inp_bits: int, inp_exp: int, clips, lane):
         if bad & _lib.ST_NEGEXP:
             raise ValueError("a compute_best exponent came out negative")
         L = [stft_frames(T) for T in Ts]
+        if exps is not None and (st[:, 0] & _lib.ST_WIDE_INPUT).any():
+            raise OverflowError("a clip holds input values beyond 16 bits: only the generic engine serves it, and that engine "
+                                "chooses its own exponents")
         for e in np.nonzero(st[:, 0] & _lib.ST_WIDE_INPUT)[0]:
             mask[e, :L[e]] = eng.generic_twin()._forward(x[e, :L[e]].contiguous(), eng.inp_bits, eng.inp_exp, torch.float32, False,
                                                          None, True)[0]
     return clips, (audio, samples, x, mask, L)
 
 
-def denoise_clips(model, inp_bits: int, inp_exp: int, clips, lane=0):
+def denoise_clips(model, inp_bits: int, inp_exp: int, clips, lane=0, exps=None):
     """``denoise_fused`` for a list of 1-D float audio clips of any lengths >= 512 (below: NotImplementedError, before any
     launch; an empty list gives []).  Returns per clip (cleaned ((len_e - 1) * 128,), cleaned_mag, x, mask), the last three
     (len_e, 257): bit for bit the tuple ``denoise_fused(model, inp_bits, inp_exp, clip[None])`` returns, without the batch axis.
@@ -401,8 +407,12 @@ def denoise_clips(model, inp_bits: int, inp_exp: int, clips, lane=0):
     from the generic engine), ``mask_istft_clips`` follows.  Any other model or device takes ``denoise_fused`` clip by clip.
 
     One CU walks one clip through the model, tile after tile, so the launch is as long as its longest clip: this is for MANY
-    clips.  A single long clip, or a few, belong on ``denoise_fused``, which spreads a sequence over the chip."""
-    clips, front = _clips_front(model, inp_bits, inp_exp, clips, lane)
+    clips.  A single long clip, or a few, belong on ``denoise_fused``, which spreads a sequence over the chip.
+
+    exps: an (n_layers, 5) array of stated exponents (``Engine.calibrate_exps``) for the model launch: every clip then runs at
+    them, bit for bit what ``StreamDenoiser(model, 1, exps=exps)`` computes for the same signal however it is pushed.  One-launch
+    route only (NotImplementedError otherwise)."""
+    clips, front = _clips_front(model, inp_bits, inp_exp, clips, lane, exps)
     if front is None:
         return [tuple(t[0] for t in denoise_fused(model, inp_bits, inp_exp, c[None])) for c in clips]
     audio, samples, x, mask, L = front
@@ -564,7 +574,7 @@ def score_clips(noisy: torch.Tensor, clean: torch.Tensor, samples: torch.Tensor,
     return (scores[0], scores[1], scores[2]) + tuple(planes)
 
 
-def validate_clips(model, inp_bits: int, inp_exp: int, noisy_clips, clean_clips, lam: float = 0.001, lane=0):
+def validate_clips(model, inp_bits: int, inp_exp: int, noisy_clips, clean_clips, lam: float = 0.001, lane=0, exps=None):
     """``validate_fused`` for lists of 1-D float audio clips of any lengths >= 512 (below: NotImplementedError, before any
     launch): clean_clips[e] has noisy_clips[e]'s length (otherwise, or for lists of different counts, ValueError).  Returns
     (loss, si_snr), (n,) float32 each (two empty tensors for empty lists): per clip bit for bit
@@ -576,7 +586,9 @@ def validate_clips(model, inp_bits: int, inp_exp: int, noisy_clips, clean_clips,
     engine).  Any other model or device takes ``validate_fused`` clip by clip.
 
     One CU walks one clip through the model, tile after tile, so the launch is as long as its longest clip: this is for MANY
-    clips.  A single long clip, or a few, belong on ``validate_fused``, which spreads a sequence over the chip."""
+    clips.  A single long clip, or a few, belong on ``validate_fused``, which spreads a sequence over the chip.
+
+    exps: stated exponents for the model launch, as ``denoise_clips`` takes them (one-launch route only)."""
     noisy_clips, clean_clips = list(noisy_clips), [torch.as_tensor(c) for c in clean_clips]
     if len(noisy_clips) != len(clean_clips):
         raise ValueError(f"{len(noisy_clips)} noisy clips but {len(clean_clips)} clean ones")
@@ -585,7 +597,7 @@ def validate_clips(model, inp_bits: int, inp_exp: int, noisy_clips, clean_clips,
             raise ValueError(f"clean clip {e} must be {tuple(torch.as_tensor(c).shape)}, got {tuple(r.shape)}")
     same_device = all(r.device == torch.as_tensor(c).device for c, r in zip(noisy_clips, clean_clips))
     # clean clips elsewhere: no model qualifies for the one-launch route
-    noisy_clips, front = _clips_front(model if same_device else None, inp_bits, inp_exp, noisy_clips, lane)
+    noisy_clips, front = _clips_front(model if same_device else None, inp_bits, inp_exp, noisy_clips, lane, exps)
     if not noisy_clips:
         return torch.empty(0, dtype=torch.float32), torch.empty(0, dtype=torch.float32)
     if front is None:
@@ -688,13 +700,20 @@ class StreamDenoiser:
     exponents, so low bits differ (as for ``s5fxp_forward_opts.state_in``).
 
     CPU tensors, and models without an engine (anything with a stateless ``forward_float``), take torch ops with the same
-    bookkeeping.  What ``push`` returns is valid until the next push of the same shape."""
+    bookkeeping.  What ``push`` returns is valid until the next push of the same shape.
+
+    exps: an (n_layers, 5) array of stated exponents (``Engine.calibrate_exps``) for the pool (``SessionPool(exps=)``): no chunk
+    chooses exponents, so the audio is the same however the hops are grouped, and bit for bit that of
+    ``denoise_clips(..., [signal], exps=exps)``.  Needs a model with an engine (NotImplementedError otherwise)."""
 
     latency_hops = 3
 
-    def __init__(self, model, sessions: int, sub: float = STFT_MAG_MEAN):
+    def __init__(self, model, sessions: int, sub: float = STFT_MAG_MEAN, exps=None):
         if sessions < 1:
             raise ValueError("sessions must be >= 1")
+        if exps is not None and not hasattr(model, "engine"):
+            raise NotImplementedError("exps= needs a model with an engine")
+        self.exps = exps
         self.model, self.sessions, self.sub = model, int(sessions), float(sub)
         self.hops = 0
         self._done = False
@@ -760,7 +779,7 @@ class StreamDenoiser:
     def _push_kernels(self, hops, c, dev, final, check, details, h, S, F, n_out):
         from . import _lib
         if self._pool is None:
-            self._pool = self.model.engine().pool(S)
+            self._pool = self.model.engine().pool(S, exps=self.exps)
         if self._state is None:
             self._state = torch.zeros(S, _lib.lib.s5fxp_stream_audio_state_bytes() // 4, dtype=torch.float32, device=dev)
         x, out, cm = self._buffers(dev, F, n_out, details)
@@ -779,7 +798,7 @@ class StreamDenoiser:
     def _mask(self, x, check):
         if hasattr(self.model, "engine"):
             if self._pool is None:
-                self._pool = self.model.engine().pool(self.sessions)
+                self._pool = self.model.engine().pool(self.sessions, exps=self.exps)
             return self._pool.push(x.to(self._pool.engine.device), check=check).to(x.device)
         return self.model.forward_float(x)
 
@@ -830,13 +849,19 @@ class SessionDenoiser:
     computes, bit for bit, what a ``StreamDenoiser(model, 1)`` fed the same chunks computes.  Results are padded: entry e of a
     push is ``ids[e]``, then the sessions of ``finish`` in order; its ``n_out[e]`` output hops and ``frames[e]`` rows sit at the
     front of row e, and what lies behind them is unspecified.  What ``push`` returns is valid until the next push of the same
-    shape.  CPU tensors and models without an engine run one ``StreamDenoiser(model, 1)`` per slot."""
+    shape.  CPU tensors and models without an engine run one ``StreamDenoiser(model, 1)`` per slot.
+
+    exps: stated exponents for the pool, as ``StreamDenoiser`` takes them: every session's audio is then independent of how its
+    hops are grouped and of what shares its pushes."""
 
     latency_hops = 3
 
-    def __init__(self, model, slots: int, sub: float = STFT_MAG_MEAN):
+    def __init__(self, model, slots: int, sub: float = STFT_MAG_MEAN, exps=None):
         if slots < 1:
             raise ValueError("slots must be >= 1")
+        if exps is not None and not hasattr(model, "engine"):
+            raise NotImplementedError("exps= needs a model with an engine")
+        self.exps = exps
         self.model, self.slots, self.sub = model, int(slots), float(sub)
         self.hops = np.zeros(self.slots, dtype=np.int64)   # hops received per slot
         self._done = np.zeros(self.slots, dtype=bool)
@@ -928,7 +953,7 @@ class SessionDenoiser:
         from . import _lib
         n, nb = len(entries), NFFT // 2 + 1
         if self._pool is None:
-            self._pool = self.model.engine().pool(self.slots)
+            self._pool = self.model.engine().pool(self.slots, exps=self.exps)
         if self._state is None:
             self._state = torch.zeros(self.slots, _lib.lib.s5fxp_stream_audio_state_bytes() // 4, dtype=torch.float32, device=dev)
         b = self._buf.get((n, cw))
@@ -962,7 +987,7 @@ class SessionDenoiser:
     def _push_each(self, entries, n_push, hops, cmax, cw, c, h, final, frames, n_out, dev, check, details):
         n, nb = len(entries), NFFT // 2 + 1
         if self._each is None:
-            self._each = [StreamDenoiser(self.model, 1, self.sub) for _ in range(self.slots)]
+            self._each = [StreamDenoiser(self.model, 1, self.sub, exps=self.exps) for _ in range(self.slots)]
         out = torch.zeros(n, (cw + 1) * HOP, dtype=torch.float32, device=dev)
         x, mask, cm = (torch.zeros(n, cw, nb, dtype=torch.float32, device=dev) for _ in range(3))
         for e, slot in enumerate(entries):

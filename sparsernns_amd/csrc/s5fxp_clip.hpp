@@ -59,6 +59,16 @@ struct ClipTraceArgs {
 #define CLIP_TRACE 1
 #include "s5fxp_clip_body.inc"
 
+// The PINNED form (s5fxp_model_clips_at): the same text with the exponents as kernel arguments, behind
+// CLIP_PINNED as the trace statements are behind CLIP_TRACE, so the two kernels above are compiled from the text they had.
+struct ClipPinArgs {
+    ClipArgs c;
+    PinExps pin;
+};
+#define CLIP_TRACE 0
+#define CLIP_PINNED 1
+#include "s5fxp_clip_body.inc"
+
 } // namespace s5
 
 namespace {
@@ -74,8 +84,10 @@ inline bool clips_serves(const s5fxp_model *m, int Lmax)
 
 int clips_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int n, int Lmax, const int32_t *lens, void *y,
                 const int32_t *state_in, int32_t *state_out, void *workspace, size_t workspace_bytes, int32_t *status, void *stream,
-                bool f32, bool traced = false, const s5fxp_layer_trace *traces = nullptr)
+                bool f32, bool traced = false, const s5fxp_layer_trace *traces = nullptr, bool pinned = false,
+                const int32_t *exps = nullptr)
 {
+    if (pinned && !exps) return S5FXP_EBADARG;
     // step_checks at one row (its row limit is the step kernel's, not this one's): arguments, the model, the static shifts
     if (!lens || !workspace || Lmax < 1 || (traced && !traces)) return S5FXP_EBADARG;
     if (const int rc = step_checks(m, x, x_bits, x_exp, n, 1, 1, y, status, f32)) return rc;
@@ -83,6 +95,8 @@ int clips_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int 
     if (traced && m->n_layers > CLIP_TRACE_MAX_LAYERS) return S5FXP_EUNSUPPORTED; // the kernel-argument table's cap
     const size_t ws_need = fit_size((wide_t)n * clip_scratch_bytes(m, Lmax)); // 0: it does not fit a size_t
     if (!ws_need || workspace_bytes < ws_need || (reinterpret_cast<uintptr_t>(workspace) & 1)) return S5FXP_EBADARG;
+    if (pinned)
+        if (const int rc = exps_check(m, exps)) return rc;
     const int R32 = Lmax < STEP_MAX_ROWS ? Lmax : STEP_MAX_ROWS;
     const size_t smem = step_lds(R32, m->H, m->P, fast_shape(m->H, m->P).hp, m->d_in).total;
     ClipArgs a{};
@@ -94,6 +108,10 @@ int clips_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int 
         ta.c = a;
         for (int li = 0; li < m->n_layers; ++li) ta.tr[li] = traces[li]; // the host array is read here, before the entry returns
         return step_launch(n, smem, ta, k_model_clips_traced<512>, k_model_clips_traced<256>, k_model_clips_traced<128>, stream);
+    }
+    if (pinned) {
+        ClipPinArgs pa{a, pin_exps(m, exps)};
+        return step_launch(n, smem, pa, k_model_clips_at<512>, k_model_clips_at<256>, k_model_clips_at<128>, stream);
     }
     return step_launch(n, smem, a, k_model_clips<512>, k_model_clips<256>, k_model_clips<128>, stream);
 }
@@ -124,6 +142,22 @@ extern "C" int s5fxp_model_clips_f32(const s5fxp_model *m, const float *x, int x
                                      int32_t *status, void *stream)
 {
     return clips_entry(m, x, x_bits, x_exp, n, Lmax, lens, y, state_in, state_out, workspace, workspace_bytes, status, stream, true);
+}
+
+extern "C" int s5fxp_model_clips_at(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int n, int Lmax, const int32_t *lens,
+                                    int32_t *y, const int32_t *state_in, int32_t *state_out, void *workspace, size_t workspace_bytes,
+                                    int32_t *status, const int32_t *exps, void *stream)
+{
+    return clips_entry(m, x, x_bits, x_exp, n, Lmax, lens, y, state_in, state_out, workspace, workspace_bytes, status, stream, false,
+                       false, nullptr, true, exps);
+}
+
+extern "C" int s5fxp_model_clips_at_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int n, int Lmax, const int32_t *lens,
+                                        float *y, const int32_t *state_in, int32_t *state_out, void *workspace, size_t workspace_bytes,
+                                        int32_t *status, const int32_t *exps, void *stream)
+{
+    return clips_entry(m, x, x_bits, x_exp, n, Lmax, lens, y, state_in, state_out, workspace, workspace_bytes, status, stream, true,
+                       false, nullptr, true, exps);
 }
 
 extern "C" int s5fxp_model_clips_traced(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int n, int Lmax,

@@ -3,13 +3,28 @@
 //   CLIP_TRACE 0  k_model_clips<STEP_THREADS>(ClipArgs)
 //   CLIP_TRACE 1  k_model_clips_traced<STEP_THREADS>(ClipTraceArgs): the stages also store the values they hold to the
 //                 layer's trace planes (the statements between #if CLIP_TRACE and #endif)
-// The flag is undefined at the foot.  What the text does and how it is kept in step with s5fxp_step_body.inc: s5fxp_clip.hpp.
+// and, with CLIP_TRACE 0, optionally a second one:
+//   CLIP_PINNED 1 k_model_clips_at<STEP_THREADS>(ClipPinArgs): the form of s5fxp_model_clips_at -- the five compute_best
+//                 exponents of a layer are kernel arguments, so the maxima loops and their workgroup reductions are not
+//                 compiled (the statements behind #if CLIP_PINNED / #if !CLIP_PINNED)
+// Both flags are undefined at the foot.  What the text does and how it is kept in step with s5fxp_step_body.inc: s5fxp_clip.hpp.
 #ifndef CLIP_TRACE
 #error "s5fxp_clip_body.inc: define CLIP_TRACE (0/1)"
 #endif
+#ifndef CLIP_PINNED
+#define CLIP_PINNED 0
+#endif
+#if CLIP_PINNED && CLIP_TRACE
+#error "s5fxp_clip_body.inc: the pinned form has no trace planes"
+#endif
 
 template <int STEP_THREADS>
-#if CLIP_TRACE
+#if CLIP_PINNED
+__global__ __launch_bounds__(STEP_THREADS, 2) void k_model_clips_at(ClipPinArgs pa)
+{
+    const ClipArgs &a = pa.c;
+    const PinExps &pin = pa.pin;
+#elif CLIP_TRACE
 __global__ __launch_bounds__(STEP_THREADS, 2) void k_model_clips_traced(ClipTraceArgs ta)
 {
     const ClipArgs &a = ta.c;
@@ -20,7 +35,9 @@ __global__ __launch_bounds__(STEP_THREADS, 2) void k_model_clips(ClipArgs a)
     constexpr int STEP_WAVES = STEP_THREADS / 64;
     extern __shared__ __attribute__((aligned(16))) int8_t step_smem[];
     __shared__ int32_t s_status[128]; // S5FXP_STATUS_WORDS: built here, stored once at the end
+#if !CLIP_PINNED
     __shared__ float s_red[3][STEP_MAX_WAVES];
+#endif
     __shared__ LayerDyn s_d;
     __shared__ int32_t s_lut[8];
     __shared__ int32_t s_wide;
@@ -118,9 +135,14 @@ __global__ __launch_bounds__(STEP_THREADS, 2) void k_model_clips(ClipArgs a)
         const int64_t trow = g * Lmax;
 #endif
 
+#if CLIP_PINNED
+        // ---- the four BatchNorm exponents as stated (s5fxp_step.hpp step_bn_pinned): no pass over h
+        step_bn_pinned(pin.e + 5 * li, bn, he, s_d, st_exps);
+#else
         // ---- the four BatchNorm compute_best exponents over the len x H values of h, re-read from the scratch: the step
         // kernel's function (s5fxp_step.hpp step_bn_exps)
         step_bn_exps<STEP_THREADS>(hg, LH, H, bn, he, s_d, s_status, st_exps, s_red);
+#endif
         const LayerDyn d = s_d;
 
         // ---- the tiles: u -> B projection -> recurrence -> C projection -> out2 -> gate -> z rows in the scratch.
@@ -132,7 +154,9 @@ __global__ __launch_bounds__(STEP_THREADS, 2) void k_model_clips(ClipArgs a)
             xr = as_global(a.state_in)[cbase + tid];
             xi = as_global(a.state_in)[cbase + P + tid];
         }
+#if !CLIP_PINNED
         float rv3[3] = {0.f, 0.f, 0.f}; // the residual add's maxima, over all tiles
+#endif
         for (int t0 = 0; t0 < len; t0 += STEP_MAX_ROWS) {
             const int R = len - t0 < STEP_MAX_ROWS ? len - t0 : STEP_MAX_ROWS, arow = r < R ? r : R - 1;
             if (tid == 0) s_wide = 0;
@@ -268,10 +292,12 @@ __global__ __launch_bounds__(STEP_THREADS, 2) void k_model_clips(ClipArgs a)
                             if (tr.post_GLU) as_global(tr.post_GLU)[o] = z;
                         }
 #endif
+#if !CLIP_PINNED
                         const float fz = tofloat(z, sl.res_exp), fs = tofloat(hb[row * H + col], he);
                         rv3[0] = fmaxf(rv3[0], fabsf(__fadd_rn(fz, fs)));
                         rv3[1] = fmaxf(rv3[1], fabsf(fz));
                         rv3[2] = fmaxf(rv3[2], fabsf(fs));
+#endif
                     }
                 }
             }
@@ -281,12 +307,19 @@ __global__ __launch_bounds__(STEP_THREADS, 2) void k_model_clips(ClipArgs a)
             as_global(a.state_out)[cbase + tid] = xr;
             as_global(a.state_out)[cbase + P + tid] = xi;
         }
+#if CLIP_PINNED
+        if (tid == 0) {
+            s_d.res = pinned_add_cb(pin.e[5 * li + 4], sl.res_exp, he);
+            st_exps[4] = s_d.res.eo;
+        }
+#else
         step_wg_max<3, STEP_WAVES>(rv3, s_red);
         if (tid == 0) {
             const uint32_t m3[3] = {__float_as_uint(rv3[0]), __float_as_uint(rv3[1]), __float_as_uint(rv3[2])};
             s_d.res = finalize_add_cb(m3, sl.res_exp, he, sl.res_bits, s_status);
             st_exps[4] = s_d.res.eo;
         }
+#endif
         __syncthreads();
         // ---- residual compute_best add + ReLU (fxpmodel.py:1147-1159) over all rows: the next layer's input, in place
         {
@@ -343,3 +376,4 @@ __global__ __launch_bounds__(STEP_THREADS, 2) void k_model_clips(ClipArgs a)
     for (int i = tid; i < 128; i += STEP_THREADS) stg[i] = s_status[i];
 }
 #undef CLIP_TRACE
+#undef CLIP_PINNED

@@ -22,6 +22,9 @@
 // The clip kernel (s5fxp_clip.hpp) repeats the body's stages over 32-row tiles.  One stage is a function both call,
 // step_bn_exps below (the four BatchNorm exponent reductions); the others are still text in both and have to be kept
 // equal by hand (DESIGN.md 4o says why they stayed).  The three entries share one launcher, step_launch.
+// Each of the three also has a form at STATED exponents (the _at entries): k_model_step_at,
+// k_model_step_ragged_at and k_model_clips_at are the same bodies with STEP_PINNED / CLIP_PINNED, in which step_bn_pinned
+// stands for step_bn_exps and no maximum is gathered or reduced.
 // LDS (dynamic, sized by R): [PLA: encoder-input / state planes][PLB: u / out2-input / decoder-input planes]
 //   [h int16 R x H][x1 int16 R x H][z int16 R x H][bq int32 2 x R x P].  R = 32 at H = 192: 120 KB; R = 1: 3.4 KB.
 #pragma once
@@ -246,6 +249,55 @@ __device__ __forceinline__ void step_bn_exps(const int16_t *hsrc, int n, int H, 
     }
 }
 
+// ---- stated exponents (the _at entries).  finalize_add_cb / finalize_mul_cb turn ONE float per op, the maximum
+// of the result, into the result exponent eo; every shift follows from eo and the operands' exponents, and the widening of
+// the operands never clips (add_cb_apply).  So an op run at a stated eo is the same statements with eo taken from the caller:
+// the functions below are finalize_*_cb without the float, and without the flags -- s5fxp_model_exps_check has refused on
+// the host every eo that is negative or makes a shift leave 0..31 (-31..31 for an add's post shift).
+constexpr int PIN_MAX_LAYERS = 8; // the exponents travel as kernel arguments (160 bytes), as the trace pointers of the clips do
+
+struct PinExps {
+    int32_t e[5 * PIN_MAX_LAYERS]; // [layer][BN add(-mean), BN mul(invsq_var), BN mul(scale), BN add(bias), residual add]
+};
+
+__device__ __forceinline__ AddCb pinned_add_cb(int eo, int xe, int ye)
+{
+    AddCb p;
+    p.eo = eo;
+    const int ea = xe > ye ? xe : ye;
+    p.shx = ea - xe;
+    p.shy = ea - ye;
+    p.post = eo - ea;
+    return p;
+}
+
+// step_bn_exps at stated exponents: thread 0 fills s_d and the status words, one barrier publishes them (and the layer's
+// s_lut / s_wide stores in front of the call).  A slot whose op the layer lacks is not read; its status word keeps its 0.
+__device__ __forceinline__ void step_bn_pinned(const int32_t *pe, const BnArgs &bn, int he, LayerDyn &s_d, int32_t *st_exps)
+{
+    if (threadIdx.x == 0) {
+        s_d.bn1 = pinned_add_cb(pe[0], he, bn.me);
+        st_exps[0] = pe[0];
+        s_d.e2 = pe[1];
+        s_d.rs2 = pe[0] + bn.ie - pe[1];
+        st_exps[1] = pe[1];
+        int e = pe[1];
+        if (bn.scale) {
+            s_d.e3 = pe[2];
+            s_d.rs3 = e + bn.se - pe[2];
+            st_exps[2] = pe[2];
+            e = pe[2];
+        }
+        if (bn.bias) {
+            s_d.bn4 = pinned_add_cb(pe[3], e, bn.be);
+            st_exps[3] = pe[3];
+            e = pe[3];
+        }
+        s_d.bn_e = e;
+    }
+    __syncthreads();
+}
+
 // STEP_THREADS: 512 when the groups are at most one per CU (eight waves shorten one group's chain of stages); 256 or 128
 // when there are more groups than CUs and several fit a CU (the kernel needs up to 256 registers per lane, so a CU holds
 // eight waves of it: one, two or four workgroups)
@@ -253,7 +305,27 @@ template <int STEP_THREADS>
 __global__ __launch_bounds__(STEP_THREADS, 2) void k_model_step(StepArgs a)
 {
 #define STEP_RAGGED 0
+#define STEP_PINNED 0
 #include "s5fxp_step_body.inc"
+#undef STEP_PINNED
+#undef STEP_RAGGED
+}
+
+// The same body at stated exponents (s5fxp_model_step_at): an argument struct of its own, so StepArgs keeps its layout
+struct StepPinArgs {
+    StepArgs c;
+    PinExps pin;
+};
+
+template <int STEP_THREADS>
+__global__ __launch_bounds__(STEP_THREADS, 2) void k_model_step_at(StepPinArgs pa)
+{
+    const StepArgs &a = pa.c;
+    const PinExps &pin = pa.pin;
+#define STEP_RAGGED 0
+#define STEP_PINNED 1
+#include "s5fxp_step_body.inc"
+#undef STEP_PINNED
 #undef STEP_RAGGED
 }
 
@@ -272,7 +344,26 @@ template <int STEP_THREADS>
 __global__ __launch_bounds__(STEP_THREADS, 2) void k_model_step_ragged(StepRaggedArgs a)
 {
 #define STEP_RAGGED 1
+#define STEP_PINNED 0
 #include "s5fxp_step_body.inc"
+#undef STEP_PINNED
+#undef STEP_RAGGED
+}
+
+struct StepRaggedPinArgs {
+    StepRaggedArgs c;
+    PinExps pin;
+};
+
+template <int STEP_THREADS>
+__global__ __launch_bounds__(STEP_THREADS, 2) void k_model_step_ragged_at(StepRaggedPinArgs pa)
+{
+    const StepRaggedArgs &a = pa.c;
+    const PinExps &pin = pa.pin;
+#define STEP_RAGGED 1
+#define STEP_PINNED 1
+#include "s5fxp_step_body.inc"
+#undef STEP_PINNED
 #undef STEP_RAGGED
 }
 
@@ -363,27 +454,105 @@ int step_launch(int G, size_t smem, const Args &a, void (*k512)(Args), void (*k2
     return launch_rc();
 }
 
-int step_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int G, int B, int L, void *y, const int32_t *state_in,
-               int32_t *state_out, int32_t *status, void *stream, bool f32)
+// The largest exponent op k of a layer can take: its result bits - 1 (intbits >= 0); -1: the layer has no such op
+int exp_max_of(const s5fxp_model *m, int layer, int k)
 {
+    if (!m || layer < 0 || layer >= m->n_layers || k < 0 || k > 4) return -1;
+    const LayerDev &l = m->layers[layer];
+    const BnArgs bn = make_bn(l, layer ? m->layers[layer - 1].res_bits : m->enc.out_bits, DynExp{0, nullptr}, nullptr);
+    if ((k == 2 && !l.scale) || (k == 3 && !l.nbias)) return -1;
+    const int bits[5] = {bn.b1, bn.b2, bn.b3, bn.b4, l.res_bits};
+    return bits[k] - 1;
+}
+
+// What the host can say about a set of stated exponents (include/s5fxp.h s5fxp_model_exps_check): with every exponent
+// stated, every shift of the forward is static.
+int exps_check(const s5fxp_model *m, const int32_t *e)
+{
+    if (!m || !e) return S5FXP_EBADARG;
+    if (!m->fast || !m->fast->step || m->n_layers > PIN_MAX_LAYERS) return S5FXP_EUNSUPPORTED;
+    for (int li = 0; li < m->n_layers; ++li)
+        for (int k = 0; k < 5; ++k) {
+            const int mx = exp_max_of(m, li, k);
+            if (mx >= 0 && (e[5 * li + k] < 0 || e[5 * li + k] > mx)) return S5FXP_EBADARG;
+        }
+    // finalize_add_cb's test: both operand shifts and the result's shift
+    auto add_ok = [](int eo, int xe, int ye) {
+        const int ea = xe > ye ? xe : ye, post = eo - ea;
+        return ea - xe <= 31 && ea - ye <= 31 && post <= 31 && post >= -31;
+    };
+    auto dist_ok = [](int a, int b) { return shift_ok(a > b ? a - b : b - a); }; // the two shifts of a change_cfg
+    int hb = m->enc.out_bits, he = m->enc.out_exp;
+    for (int li = 0; li < m->n_layers; ++li) {
+        const LayerDev &l = m->layers[li];
+        const int32_t *pe = e + 5 * li;
+        if (!add_ok(pe[0], he, l.nd.mean_exp)) return S5FXP_ENEGSHIFT;
+        if (!shift_ok(pe[0] + l.nd.invsq_var_exp - pe[1])) return S5FXP_ENEGSHIFT;
+        int be = pe[1];
+        if (l.scale) {
+            if (!shift_ok(be + l.nd.scale_exp - pe[2])) return S5FXP_ENEGSHIFT;
+            be = pe[2];
+        }
+        if (l.nbias) {
+            if (!add_ok(pe[3], be, l.nd.bias_exp)) return S5FXP_ENEGSHIFT;
+            be = pe[3];
+        }
+        if (!dist_ok(be, l.sd.u_exp)) return S5FXP_ENEGSHIFT; // bn_chain's change_cfg to the SSM input
+        if (!add_ok(pe[4], l.res_exp, he)) return S5FXP_ENEGSHIFT;
+        hb = l.res_bits;
+        he = pe[4];
+    }
+    const DenseDev &d = m->dec;
+    const bool conv = hb > d.inp_bits || he > d.inp_exp;
+    if (conv && !dist_ok(he, d.inp_exp)) return S5FXP_ENEGSHIFT;
+    if (!shift_ok((conv ? d.inp_exp : he) + d.w_exp - d.out_exp)) return S5FXP_ENEGSHIFT;
+    return S5FXP_OK;
+}
+
+// The kernel-argument copy of a checked host array
+PinExps pin_exps(const s5fxp_model *m, const int32_t *e)
+{
+    PinExps p{};
+    std::memcpy(p.e, e, sizeof(int32_t) * 5 * (size_t)m->n_layers);
+    return p;
+}
+
+// exps == nullptr: the entry as it always was; pinned: the _at form, which refuses a null exps
+int step_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int G, int B, int L, void *y, const int32_t *state_in,
+               int32_t *state_out, int32_t *status, void *stream, bool f32, bool pinned = false, const int32_t *exps = nullptr)
+{
+    if (pinned && !exps) return S5FXP_EBADARG;
     if (const int rc = step_checks(m, x, x_bits, x_exp, G, B, L, y, status, f32)) return rc;
+    if (pinned)
+        if (const int rc = exps_check(m, exps)) return rc;
     const size_t smem = step_lds(B * L, m->H, m->P, fast_shape(m->H, m->P).hp, m->d_in).total;
     StepArgs a{};
     a.sp = m->fast->step; a.x = x; a.y = y; a.state_in = state_in; a.state_out = state_out; a.status = status;
     a.B = B; a.L = L; a.x_bits = x_bits; a.x_exp = x_exp; a.f32 = f32 ? 1 : 0;
+    if (pinned) {
+        StepPinArgs pa{a, pin_exps(m, exps)};
+        return step_launch(G, smem, pa, k_model_step_at<512>, k_model_step_at<256>, k_model_step_at<128>, stream);
+    }
     return step_launch(G, smem, a, k_model_step<512>, k_model_step<256>, k_model_step<128>, stream);
 }
 
 // The ragged form: the same checks at (B, Lmax), the dynamic LDS of B * Lmax rows, the same rule on n for the workgroup size.
 int step_ragged_entry(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int n, int B, int Lmax, void *y,
-                      const s5fxp_push_desc *desc, int32_t *state, int n_slots, int32_t *status, void *stream, bool f32)
+                      const s5fxp_push_desc *desc, int32_t *state, int n_slots, int32_t *status, void *stream, bool f32,
+                      bool pinned = false, const int32_t *exps = nullptr)
 {
-    if (!desc || !state || n_slots < 1) return S5FXP_EBADARG;
+    if (!desc || !state || n_slots < 1 || (pinned && !exps)) return S5FXP_EBADARG;
     if (const int rc = step_checks(m, x, x_bits, x_exp, n, B, Lmax, y, status, f32)) return rc;
+    if (pinned)
+        if (const int rc = exps_check(m, exps)) return rc;
     const size_t smem = step_lds(B * Lmax, m->H, m->P, fast_shape(m->H, m->P).hp, m->d_in).total;
     StepRaggedArgs a{};
     a.sp = m->fast->step; a.x = x; a.y = y; a.desc = desc; a.state = state; a.status = status;
     a.B = B; a.Lmax = Lmax; a.x_bits = x_bits; a.x_exp = x_exp; a.f32 = f32 ? 1 : 0;
+    if (pinned) {
+        StepRaggedPinArgs pa{a, pin_exps(m, exps)};
+        return step_launch(n, smem, pa, k_model_step_ragged_at<512>, k_model_step_ragged_at<256>, k_model_step_ragged_at<128>, stream);
+    }
     return step_launch(n, smem, a, k_model_step_ragged<512>, k_model_step_ragged<256>, k_model_step_ragged<128>, stream);
 }
 
@@ -417,6 +586,37 @@ extern "C" int s5fxp_model_step_ragged_f32(const s5fxp_model *m, const float *x,
                                            const s5fxp_push_desc *desc, int32_t *state, int n_slots, int32_t *status, void *stream)
 {
     return step_ragged_entry(m, x, x_bits, x_exp, n, B, Lmax, y, desc, state, n_slots, status, stream, true);
+}
+
+// ---- the same four entries at stated exponents, and what the host can say about a set of them (include/s5fxp.h)
+extern "C" int s5fxp_model_exp_max(const s5fxp_model *m, int layer, int k) { return exp_max_of(m, layer, k); }
+
+extern "C" int s5fxp_model_exps_check(const s5fxp_model *m, const int32_t *exps_host) { return exps_check(m, exps_host); }
+
+extern "C" int s5fxp_model_step_at(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int G, int B, int L, int32_t *y,
+                                   const int32_t *state_in, int32_t *state_out, int32_t *status, const int32_t *exps, void *stream)
+{
+    return step_entry(m, x, x_bits, x_exp, G, B, L, y, state_in, state_out, status, stream, false, true, exps);
+}
+
+extern "C" int s5fxp_model_step_at_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int G, int B, int L, float *y,
+                                       const int32_t *state_in, int32_t *state_out, int32_t *status, const int32_t *exps, void *stream)
+{
+    return step_entry(m, x, x_bits, x_exp, G, B, L, y, state_in, state_out, status, stream, true, true, exps);
+}
+
+extern "C" int s5fxp_model_step_ragged_at(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int n, int B, int Lmax,
+                                          int32_t *y, const s5fxp_push_desc *desc, int32_t *state, int n_slots, int32_t *status,
+                                          const int32_t *exps, void *stream)
+{
+    return step_ragged_entry(m, x, x_bits, x_exp, n, B, Lmax, y, desc, state, n_slots, status, stream, false, true, exps);
+}
+
+extern "C" int s5fxp_model_step_ragged_at_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int n, int B, int Lmax,
+                                              float *y, const s5fxp_push_desc *desc, int32_t *state, int n_slots, int32_t *status,
+                                              const int32_t *exps, void *stream)
+{
+    return step_ragged_entry(m, x, x_bits, x_exp, n, B, Lmax, y, desc, state, n_slots, status, stream, true, true, exps);
 }
 
 // Host-only validation of a descriptor array (include/s5fxp.h): the kernels trust what they read.

@@ -4,12 +4,18 @@
 //                  a.desc[e]; x and y are padded to Lmax frames per sequence, so row b * L + t of the group is frame t of
 //                  sequence b there.  Only the input staging and the decoder's stores see that; the LDS regions are laid out
 //                  for the entry's own R = B * L.
+// STEP_PINNED 1 (with either STEP_RAGGED) is the form of the _at entries, k_model_step_at(StepPinArgs) and
+// k_model_step_ragged_at(StepRaggedPinArgs): the five compute_best exponents of a layer are kernel arguments, so the maxima
+// loops and their workgroup reductions are not compiled -- step_bn_pinned for step_bn_exps, and the residual block takes its
+// shifts from the stated exponent.  Every other statement is shared.
 // The two share every line that computes, so they cannot drift.  The clip kernel (s5fxp_clip.hpp) holds a copy of these
 // stages over tiles, except step_bn_exps (s5fxp_step.hpp), which both call: a change to any other stage is made in both.
     constexpr int STEP_WAVES = STEP_THREADS / 64;
     extern __shared__ __attribute__((aligned(16))) int8_t step_smem[];
     __shared__ int32_t s_status[128]; // S5FXP_STATUS_WORDS: built here, stored once at the end
+#if !STEP_PINNED
     __shared__ float s_red[3][STEP_MAX_WAVES];
+#endif
     // the layer's per-channel and per-state operands, fetched together at the head of the layer
     __shared__ LayerDyn s_d;
     __shared__ int32_t s_lut[8];
@@ -122,8 +128,13 @@
         if (tid < 8) s_lut[tid] = sl.lut[tid];
         if (tid == 0) s_wide = 0;
 
+#if STEP_PINNED
+        // ---- the four BatchNorm exponents as stated: the shifts finalize_*_cb would derive, no reduction
+        step_bn_pinned(pin.e + 5 * li, bn, he, s_d, st_exps);
+#else
         // ---- the four BatchNorm compute_best exponents over the R x H values of h: the stage the clip kernel shares
         step_bn_exps<STEP_THREADS>(hb, R * H, H, bn, he, s_d, s_status, st_exps, s_red);
+#endif
         const LayerDyn d = s_d;
 
         // ---- u = change_cfg(BatchNorm(x)) -> byte planes (fxpmodel.py:620-624)
@@ -237,7 +248,9 @@
 
         // ---- out2 + LUT sigmoid + gate (fxpmodel.py:1133-1137, 97-144, 1075-1093) + the residual add's maxima
         {
+#if !STEP_PINNED
             float v[3] = {0.f, 0.f, 0.f};
+#endif
             for (int tile = wave; tile < HP / 32; tile += STEP_WAVES) {
                 const int col = 32 * tile + r;
                 const v16i acc = step_mm<2>(plb, psb, KPB, arow, h, sl.out2, col, HP / 32);
@@ -253,19 +266,28 @@
                         const int32_t rv = chcfg(s, sl.o2_out_bits, sl.sig_y, sl.r_bits, sl.r_exp);
                         const int32_t z = sat(asr(wmul(lv, rv), sl.rs_gate), sl.res_bits);
                         zb[row * H + col] = (int16_t)z;
+#if !STEP_PINNED
                         const float fz = tofloat(z, sl.res_exp), fs = tofloat(hb[row * H + col], he);
                         v[0] = fmaxf(v[0], fabsf(__fadd_rn(fz, fs)));
                         v[1] = fmaxf(v[1], fabsf(fz));
                         v[2] = fmaxf(v[2], fabsf(fs));
+#endif
                     }
                 }
             }
+#if STEP_PINNED
+            if (tid == 0) {
+                s_d.res = pinned_add_cb(pin.e[5 * li + 4], sl.res_exp, he);
+                st_exps[4] = s_d.res.eo;
+            }
+#else
             step_wg_max<3, STEP_WAVES>(v, s_red);
             if (tid == 0) {
                 const uint32_t m3[3] = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2])};
                 s_d.res = finalize_add_cb(m3, sl.res_exp, he, sl.res_bits, s_status);
                 st_exps[4] = s_d.res.eo;
             }
+#endif
             __syncthreads();
         }
         // ---- residual compute_best add + ReLU (fxpmodel.py:1147-1159): the next layer's input, in place

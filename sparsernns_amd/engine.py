@@ -432,7 +432,7 @@ class Engine:
 
     def step(self, x, state: Optional[torch.Tensor], y: Optional[torch.Tensor] = None, B: int = 1, L: int = 1, groups: int = 1,
              x_bits: Optional[int] = None, x_exp: Optional[int] = None, state_out: Optional[torch.Tensor] = None,
-             lane=0) -> torch.Tensor:
+             lane=0, exps=None) -> torch.Tensor:
         """One short chunk of `groups` independent streams as ONE kernel launch (``s5fxp_model_step``): enqueue only --
         nothing is synchronised, and nothing is allocated when `y` is given.
 
@@ -441,7 +441,10 @@ class Engine:
         (groups, n_layers, 2, B, P) int32, read and -- unless `state_out` names another tensor -- replaced in place; None
         starts from zeros and keeps no carry.  Every group is its own compute_best batch, exactly ``enqueue(...,
         groups=groups)``.  The status words (``lane_status(lane, groups)``, ``check_status(lane)``) are the caller's to
-        read: ST_WIDE_INPUT means the results are invalid (serve the chunk through ``enqueue`` on a generic engine)."""
+        read: ST_WIDE_INPUT means the results are invalid (serve the chunk through ``enqueue`` on a generic engine).
+
+        exps: an (n_layers, 5) array of stated exponents (``exp_max`` has the layout) runs ``s5fxp_model_step_at[_f32]``: no
+        group chooses exponents, so a stream's outputs no longer depend on how it is cut into steps."""
         if isinstance(x, FxpArray):
             x_bits, x_exp, x = x.bits, x.exp, x.data
         f32 = x.dtype == torch.float32
@@ -462,11 +465,52 @@ class Engine:
                 raise ValueError(f"{name} must be a contiguous int32 device tensor of shape {want}")
         so = state_out if state_out is not None else state
         self._groups[lane] = groups
-        entry, name = (lib.s5fxp_model_step_f32, "s5fxp_model_step_f32") if f32 else (lib.s5fxp_model_step, "s5fxp_model_step")
-        check(entry(self._h, x.data_ptr(), xb, xe, groups, B, L, y.data_ptr(), state.data_ptr() if state is not None else None,
-                    so.data_ptr() if so is not None else None, self.lane_status(lane, groups).data_ptr(),
-                    torch.cuda.current_stream().cuda_stream), name)
+        name = "s5fxp_model_step" + ("_at" if exps is not None else "") + ("_f32" if f32 else "")
+        eh = None if exps is None else self._exps_host(exps)   # the entry reads the host array before it returns: keep it alive
+        tail = () if eh is None else (eh.ctypes.data,)
+        check(getattr(lib, name)(self._h, x.data_ptr(), xb, xe, groups, B, L, y.data_ptr(),
+                                 state.data_ptr() if state is not None else None, so.data_ptr() if so is not None else None,
+                                 self.lane_status(lane, groups).data_ptr(), *tail, torch.cuda.current_stream().cuda_stream), name)
         return y
+
+    # -- stated exponents ----------------------------------------------------------------------
+    def _exps_host(self, exps) -> np.ndarray:
+        """`exps` as the contiguous host int32 array the _at entries read, (n_layers, 5)."""
+        e = np.ascontiguousarray(np.asarray(exps, dtype=np.int32))
+        if e.shape != (self.n_layers, 5):
+            raise ValueError(f"exps must have shape ({self.n_layers}, 5), got {e.shape}")
+        return e
+
+    def exp_max(self) -> np.ndarray:
+        """(n_layers, 5) int32: the largest exponent each of a layer's five compute_best ops can take -- BatchNorm add(-mean),
+        mul(invsq_var), mul(scale), add(bias) and the residual add, the order of status words [8 + 8 * l + 0 .. 4] -- and -1
+        where the layer has no such op (``s5fxp_model_exp_max``)."""
+        return np.array([[lib.s5fxp_model_exp_max(self._h, l, k) for k in range(5)] for l in range(self.n_layers)], dtype=np.int32)
+
+    def check_exps(self, exps) -> None:
+        """Raises what the _at entries would refuse `exps` with (``s5fxp_model_exps_check``, host only): ValueError for an
+        exponent outside 0 .. ``exp_max()`` or one that makes a shift negative or larger than 31, NotImplementedError for a
+        model off the fused path or of more than 8 layers."""
+        eh = self._exps_host(exps)
+        rc = lib.s5fxp_model_exps_check(self._h, eh.ctypes.data)
+        if rc == _lib.S5FXP_EBADARG:
+            raise ValueError("s5fxp_model_exps_check: an exponent is outside 0 .. exp_max()")
+        check(rc, "s5fxp_model_exps_check")
+
+    def calibrate_exps(self, clips, headroom: int = 0, lane=0) -> np.ndarray:
+        """Exponents for ``exps=`` from data: runs ``forward_clips`` on `clips` (a list of FxpArray) and takes, per layer and
+        op, the MINIMUM of the exponents the clips chose -- the largest range any of them needed -- over the clips that have
+        frames and no error bit; `headroom` more integer bits are then taken off, not below 0.  Host arithmetic on the status
+        words of the one launch.  Returns (n_layers, 5) int32, 0 where the layer has no such op."""
+        clips = list(clips)
+        self.forward_clips(clips, lane=lane)
+        n, W = len(clips), _lib.STATUS_WORDS
+        st = self.lane_status(lane, n).cpu().numpy()[:n * W].reshape(n, W)
+        ok = np.array([c.data.shape[0] > 0 for c in clips], dtype=bool) & ((st[:, 0] & ~_lib.ST_WIDE_STATE) == 0)
+        if not ok.any():
+            raise ValueError("calibrate_exps: no clip with frames came back without an error bit")
+        e = st[ok][:, 8:8 + 8 * self.n_layers].reshape(-1, self.n_layers, 8)[:, :, :5].min(axis=0)
+        return np.where(self.exp_max() >= 0, np.maximum(e - int(headroom), 0), 0).astype(np.int32)
 
     # -- many clips of different lengths, one launch --------------------------------------------
     def clips_ok(self, Lmax: int) -> bool:
@@ -483,7 +527,7 @@ class Engine:
 
     def clips(self, x, lens: torch.Tensor, y: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
               state_out: Optional[torch.Tensor] = None, x_bits: Optional[int] = None, x_exp: Optional[int] = None,
-              lane=0) -> torch.Tensor:
+              lane=0, exps=None) -> torch.Tensor:
         """n clips of different lengths as ONE kernel launch (``s5fxp_model_clips``): enqueue only -- nothing is
         synchronised, and apart from the lane's scratch nothing is allocated when `y` is given.
 
@@ -500,8 +544,12 @@ class Engine:
         launches (93 .. 165 us) per clip.  Measured break-even: about 5 clips of 128 frames, 15 .. 20 clips
         of mixed lengths up to 512 frames; 10 .. 19 times faster than per-clip forwards from 256 clips on.  A single clip
         never pays (32 frames: 127 against 93 us; 2048 frames: 6.8 against 0.15 ms): it belongs on ``forward``, which spreads
-        it over the chip.  Clips that share one length are 3.6 .. 4 times faster on ``forward_batches``."""
-        return self._clips_launch(x, lens, y, state, state_out, x_bits, x_exp, lane, False, None)[0]
+        it over the chip.  Clips that share one length are 3.6 .. 4 times faster on ``forward_batches``.
+
+        exps: an (n_layers, 5) array of stated exponents (``exp_max`` has the layout; ``calibrate_exps`` makes one from data)
+        runs ``s5fxp_model_clips_at[_f32]``: every clip at those exponents instead of its own, which is what a stream pushed
+        through ``SessionPool(exps=)`` computes for the same signal however it is cut."""
+        return self._clips_launch(x, lens, y, state, state_out, x_bits, x_exp, lane, False, None, exps)[0]
 
     def clips_traced(self, x, lens: torch.Tensor, y: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
                      state_out: Optional[torch.Tensor] = None, x_bits: Optional[int] = None, x_exp: Optional[int] = None,
@@ -514,7 +562,7 @@ class Engine:
         stores 11 planes per layer and is slower than ``clips``."""
         return self._clips_launch(x, lens, y, state, state_out, x_bits, x_exp, lane, True, traces)
 
-    def _clips_launch(self, x, lens, y, state, state_out, x_bits, x_exp, lane, traced: bool, traces):
+    def _clips_launch(self, x, lens, y, state, state_out, x_bits, x_exp, lane, traced: bool, traces, exps=None):
         """The checks and the one launch behind ``clips`` and ``clips_traced`` -> (y, the trace planes or None)."""
         if isinstance(x, FxpArray):
             x_bits, x_exp, x = x.bits, x.exp, x.data
@@ -553,19 +601,23 @@ class Engine:
                         raise ValueError(f"trace plane {k} must be a contiguous int32 device tensor of shape {(n, Lmax, w)}")
                     setattr(t, k, pl.data_ptr())
             tail = (tr,)
+        eh = None if exps is None else self._exps_host(exps)   # read before the entry returns: kept alive until then
+        if eh is not None:
+            tail = (eh.ctypes.data,)
         so = state_out if state_out is not None else state
         ws = self._clips_workspace(n, Lmax, lane)
         self._groups[lane] = n
-        name = "s5fxp_model_clips" + ("_traced" if traced else "") + ("_f32" if f32 else "")
+        name = "s5fxp_model_clips" + ("_traced" if traced else "_at" if exps is not None else "") + ("_f32" if f32 else "")
         check(getattr(lib, name)(self._h, x.data_ptr(), xb, xe, n, Lmax, lens.data_ptr(), y.data_ptr(),
                                  state.data_ptr() if state is not None else None, so.data_ptr() if so is not None else None,
                                  ws.data_ptr(), ws.numel(), self.lane_status(lane, n).data_ptr(), *tail,
                                  torch.cuda.current_stream().cuda_stream), name)
         return y, traces
 
-    def _forward_clips(self, xs, dtype: torch.dtype, xb: int, xe: int, lane) -> List[torch.Tensor]:
+    def _forward_clips(self, xs, dtype: torch.dtype, xb: int, xe: int, lane, exps=None) -> List[torch.Tensor]:
         """Pads the clips (each (L_e, d_in) of `dtype`), launches once, reads the status once; a clip the 16-bit planes
-        cannot hold (ST_WIDE_INPUT) is served on the generic engine on its own.  Returns the (L_e, d_out) outputs."""
+        cannot hold (ST_WIDE_INPUT) is served on the generic engine on its own -- or, with `exps`, raises: the generic engine
+        cannot honour stated exponents.  Returns the (L_e, d_out) outputs."""
         datas = []
         for d in xs:
             d = torch.as_tensor(d)
@@ -582,7 +634,7 @@ class Engine:
         x = torch.zeros((n, Lmax, self.d_in), dtype=dtype, device=self.device)
         for e, d in enumerate(datas):
             x[e, :lens[e]] = d
-        y = self.clips(x, torch.tensor(lens, dtype=torch.int32, device=self.device), x_bits=xb, x_exp=xe, lane=lane)
+        y = self.clips(x, torch.tensor(lens, dtype=torch.int32, device=self.device), x_bits=xb, x_exp=xe, lane=lane, exps=exps)
         st = self.lane_status(lane, n).cpu().numpy()[:n * _lib.STATUS_WORDS].reshape(n, _lib.STATUS_WORDS)
         bad = int(np.bitwise_or.reduce(st[:, 0] & ~_lib.ST_WIDE_INPUT))
         if bad & _lib.ST_NEGSHIFT:
@@ -590,14 +642,18 @@ class Engine:
         if bad & _lib.ST_NEGEXP:
             raise ValueError("a compute_best exponent came out negative")
         out = [y[e, :lens[e]] for e in range(n)]
+        if exps is not None and (st[:, 0] & _lib.ST_WIDE_INPUT).any():
+            raise OverflowError("a clip holds input values beyond 16 bits: only the generic engine serves it, and that engine "
+                                "chooses its own exponents")
         for e in np.nonzero(st[:, 0] & _lib.ST_WIDE_INPUT)[0]:
             out[e] = self.generic_twin()._forward(datas[e].contiguous(), xb, xe, dtype, False, None, True)[0]
         return out
 
-    def forward_clips(self, xs, lane=0) -> List[FxpArray]:
+    def forward_clips(self, xs, lane=0, exps=None) -> List[FxpArray]:
         """xs: a list of FxpArray (L_e, d_in) of one configuration, lengths free (0 included).  Returns the list of
         FxpArray (L_e, d_out) that ``forward`` gives each clip on its own, from ONE kernel launch (``clips``) and one
-        read of the status words.  For many short clips; see ``clips`` for where a long clip belongs."""
+        read of the status words.  For many short clips; see ``clips`` for where a long clip belongs.  With `exps` every
+        clip runs at those stated exponents instead (``clips(..., exps=)``)."""
         xs = list(xs)
         if not xs:
             return []
@@ -605,14 +661,15 @@ class Engine:
         if len(cfg) != 1:
             raise ValueError(f"the clips of one launch share one input configuration, got {sorted(cfg)}")
         (xb, xe), = cfg
-        return [self._fxp(y) for y in self._forward_clips([x.data for x in xs], torch.int32, xb, xe, lane)]
+        return [self._fxp(y) for y in self._forward_clips([x.data for x in xs], torch.int32, xb, xe, lane, exps)]
 
-    def forward_clips_float(self, xs, x_bits: Optional[int] = None, x_exp: Optional[int] = None, lane=0) -> List[torch.Tensor]:
+    def forward_clips_float(self, xs, x_bits: Optional[int] = None, x_exp: Optional[int] = None, lane=0,
+                            exps=None) -> List[torch.Tensor]:
         """The same for float32 clips (L_e, d_in): fxp_from_fp (FLOOR) to (x_bits, x_exp) -- the encoder's input configuration
         by default -- the model, to_float, in the one launch.  Returns float32 tensors (L_e, d_out)."""
         xs = [torch.as_tensor(x) for x in xs]
         return self._forward_clips(xs, torch.float32, self.inp_bits if x_bits is None else int(x_bits),
-                                   self.inp_exp if x_exp is None else int(x_exp), lane)
+                                   self.inp_exp if x_exp is None else int(x_exp), lane, exps)
 
     def generic_twin(self) -> "Engine":
         """The same model on the generic int32 kernels (MODEL_FORCE_GENERIC), built on first use: what serves inputs the
@@ -623,8 +680,8 @@ class Engine:
             self._generic = Engine(self._export, self._flags | _lib.MODEL_FORCE_GENERIC, self.device)
         return self._generic
 
-    def pool(self, sessions: int, B: int = 1) -> "SessionPool":
-        return SessionPool(self, sessions, B)
+    def pool(self, sessions: int, B: int = 1, exps=None) -> "SessionPool":
+        return SessionPool(self, sessions, B, exps)
 
 
 class StreamingSession:
@@ -655,12 +712,24 @@ class SessionPool:
     and reusable output buffers: what ``push`` returns is valid until the next push of the same chunk shape.
 
     Each session's chunk is its own compute_best batch: session s of a pool computes what a ``StreamingSession`` fed the
-    same chunks computes."""
+    same chunks computes.
 
-    def __init__(self, engine: "Engine", sessions: int, B: int = 1):
+    exps: an (n_layers, 5) array of stated exponents (``Engine.exp_max`` has the layout, ``Engine.calibrate_exps`` makes one)
+    replaces that rule: every push runs the _at entries at those exponents, so a session's outputs are the same however its
+    signal is cut into pushes, and equal ``Engine.clips(..., exps=)`` on the whole signal.  A push of more than 32 rows per
+    session is then split into steps of at most 32 rows instead of leaving the step kernel, and a chunk with input values
+    beyond 16 bits raises: the generic engine, which serves such chunks otherwise, chooses its own exponents."""
+
+    def __init__(self, engine: "Engine", sessions: int, B: int = 1, exps=None):
         if sessions < 1 or B < 1:
             raise ValueError("sessions and B must be >= 1")
         self.engine, self.sessions, self.B = engine, int(sessions), int(B)
+        self.exps = None
+        if exps is not None:
+            engine.check_exps(exps)
+            self.exps = engine._exps_host(exps).copy()
+            if not engine.step_ok(self.B, 1):
+                raise NotImplementedError(f"stated exponents need the step kernel, which serves B <= {32} sequences per session")
         shape = (self.sessions, engine.n_layers, 2, self.B, engine.P)
         self._state = torch.zeros(shape, dtype=torch.int32, device=engine.device)
         self._next = torch.zeros(shape, dtype=torch.int32, device=engine.device)
@@ -718,6 +787,30 @@ class SessionPool:
             self.last_path = _lib.PATH_FUSED if lib.s5fxp_model_is_fast(eng._h) else _lib.PATH_GENERIC
         self._state, self._next = self._next, self._state
 
+    def _push_pinned(self, data, xb, xe, y, L: int, check: bool) -> None:
+        """A push at stated exponents: steps of at most 32 // B frames per sequence, each one launch on the carry in place."""
+        eng, S, B = self.engine, self.sessions, self.B
+        step = max(1, 32 // B)
+        d4, y4 = data.view(S, B, L, eng.d_in), y.view(S, B, L, eng.d_out)
+        for t0 in range(0, L, step):
+            t1 = min(L, t0 + step)
+            whole = t0 == 0 and t1 == L
+            xs = d4 if whole else d4[:, :, t0:t1].contiguous()
+            ys = y4 if whole else torch.empty((S, B, t1 - t0, eng.d_out), dtype=y.dtype, device=y.device)
+            eng.step(xs, self._state, ys, B, t1 - t0, S, xb, xe, lane=self._lane, exps=self.exps)
+            if not whole:
+                y4[:, :, t0:t1] = ys
+            st = eng.lane_status(self._lane, S)
+            if check:
+                bits = int(np.bitwise_or.reduce(st.cpu().numpy()[:S * _lib.STATUS_WORDS].reshape(S, _lib.STATUS_WORDS)[:, 0]))
+                if bits & _lib.ST_WIDE_INPUT:
+                    raise OverflowError("a chunk holds input values beyond 16 bits: only the generic engine serves it, and that "
+                                        "engine chooses its own exponents; the carry is invalid, reset the sessions")
+            else:
+                self._err |= st[:S * _lib.STATUS_WORDS].view(S, _lib.STATUS_WORDS)[:, 0]
+                self._unchecked = True
+        self.last_path = _lib.PATH_STEP
+
     def push(self, x, check: bool = True):
         """x: (sessions, L, d_in) (B == 1) or (sessions, B, L, d_in), an FxpArray or a float32 tensor.  Returns the outputs
         of exactly those frames, an FxpArray or a float32 tensor of the same leading shape.  check=False enqueues only:
@@ -750,7 +843,9 @@ class SessionPool:
         y = self._y.get(key)
         if y is None:
             y = self._y[key] = torch.empty(key[0] + (eng.d_out,), dtype=data.dtype, device=eng.device)
-        if eng.step_ok(B, L):
+        if self.exps is not None:
+            self._push_pinned(data, xb, xe, y, L, check)
+        elif eng.step_ok(B, L):
             if check:
                 eng.step(data, self._state, y, B, L, S, xb, xe, state_out=self._next, lane=self._lane)
                 st = eng.lane_status(self._lane, S).cpu().numpy()[:S * _lib.STATUS_WORDS].reshape(S, _lib.STATUS_WORDS)
@@ -876,18 +971,35 @@ class SessionPool:
         if y is None:
             y = self._y[key] = torch.empty(key[1] + (eng.d_out,), dtype=data.dtype, device=eng.device)
         W = _lib.STATUS_WORDS
+        if self.exps is not None and not eng.step_ok(B, Lmax):
+            # stated exponents: the result does not depend on the split, so a long push is steps of at most 32 rows
+            if desc is not None:
+                raise NotImplementedError("a staged descriptor array describes one step: push at most 32 rows per session with it")
+            step = max(1, 32 // B)
+            d4, y4 = data.view(n, B, Lmax, eng.d_in), y.view(n, B, Lmax, eng.d_out)
+            for t0 in range(0, Lmax, step):
+                t1 = min(Lmax, t0 + step)
+                xs = d4[:, :, t0:t1].reshape((n,) + ((B,) if data.ndim == 4 else ()) + (t1 - t0, eng.d_in))
+                part = self.push_ragged(ids, FxpArray(xs, xb, xe, True) if fxp else xs, np.clip(rows - t0, 0, t1 - t0),
+                                        fresh if t0 == 0 else (), check)
+                y4[:, :, t0:t1] = (part.data if fxp else part).view(n, B, t1 - t0, eng.d_out)
+            return FxpArray(y, eng.out_bits, eng.out_exp, True) if fxp else y
         if eng.step_ok(B, Lmax):
             if desc is None:
                 desc = self.stage_desc(ids, rows, new * _lib.PUSH_FRESH, Lmax=Lmax)
-            entry, name = ((lib.s5fxp_model_step_ragged, "s5fxp_model_step_ragged") if fxp else
-                           (lib.s5fxp_model_step_ragged_f32, "s5fxp_model_step_ragged_f32"))
+            name = "s5fxp_model_step_ragged" + ("_at" if self.exps is not None else "") + ("" if fxp else "_f32")
+            tail = () if self.exps is None else (self.exps.ctypes.data,)
             st = eng.lane_status(self._lane, n)
             eng._groups[self._lane] = n
-            _lib.check(entry(eng._h, data.data_ptr(), xb, xe, n, B, Lmax, y.data_ptr(), desc.data_ptr(), self._state.data_ptr(),
-                             self.sessions, st.data_ptr(), torch.cuda.current_stream().cuda_stream), name)
+            _lib.check(getattr(lib, name)(eng._h, data.data_ptr(), xb, xe, n, B, Lmax, y.data_ptr(), desc.data_ptr(),
+                                          self._state.data_ptr(), self.sessions, st.data_ptr(), *tail,
+                                          torch.cuda.current_stream().cuda_stream), name)
             self.last_path = _lib.PATH_STEP
             if check:
                 bits = st.cpu().numpy()[:n * W].reshape(n, W)[:, 0]
+                if self.exps is not None and (bits & _lib.ST_WIDE_INPUT).any():
+                    raise OverflowError("an entry holds input values beyond 16 bits: only the generic engine serves it, and that "
+                                        "engine chooses its own exponents")
                 for e in np.nonzero(bits & _lib.ST_WIDE_INPUT)[0]:
                     # the kernel left this entry's outputs and carry alone: the generic engine serves it from that carry
                     self._entry(eng.generic_twin(), int(e), int(ids[e]), data, xb, xe, y, int(rows[e]), bool(new[e]), fxp)

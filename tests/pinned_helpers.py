@@ -1,0 +1,146 @@
+"""Helpers of tests/test_pinned_exps.py: the NumPy oracle (oracle/fxp_oracle.py) run at STATED exponents through its
+MAX_EXCHANGE hook, and a host restatement of which exponent sets leave every static shift inside 0..31.
+
+The hook sees every compute_best op's float32 maxima in the order the model runs them: per layer BatchNorm add(-mean),
+mul(invsq_var), [mul(scale)], [add(bias)], then the residual add.  Forcing op k's maximum to a float whose intbits is
+ib = result_bits - 1 - e makes the oracle choose the exponent e for it: 0.5 for ib = 0, 1.5 * 2^(ib - 1) otherwise (the add's
+other two maxima only size the operands' widening, which never clips, so forcing them too changes nothing).
+"""
+import contextlib
+
+import numpy as np
+
+from oracle import fxp_oracle as O
+
+F32 = np.float32
+
+
+def op_bits(om) -> np.ndarray:
+    """(n_layers, 5) result bits of the five compute_best ops of every layer, 0 where the layer has no such op."""
+    out = np.zeros((len(om.layers), 5), dtype=np.int32)
+    hb = om.encoder.qc["out_bits"]
+    for i, l in enumerate(om.layers):
+        n = l.norm
+        b1 = max(hb, n.minus_mean.bits)
+        b2 = max(b1, n.invsq_var.bits)
+        b3 = max(b2, n.scale.bits) if n.scale is not None else b2
+        b4 = max(b3, n.bias.bits) if n.bias is not None else b3
+        rb = l.qc["multgate"]["res_bits"]
+        out[i] = (b1, b2, b3 if n.scale is not None else 0, b4 if n.bias is not None else 0, rb)
+        hb = rb
+    return out
+
+
+def exp_max(om) -> np.ndarray:
+    """What Engine.exp_max() must report: result bits - 1, -1 for an absent op."""
+    return op_bits(om) - 1
+
+
+def forced_float(ib: int) -> np.float32:
+    return F32(0.5) if ib == 0 else F32(1.5 * 2.0 ** (ib - 1))
+
+
+class _Hook:
+    """MAX_EXCHANGE callable: records the exponent every op would choose on its own and, with `exps`, forces the stated one.
+    The ops of one forward come in a fixed order, so a call counter modulo the ops per forward names the op."""
+
+    def __init__(self, om, exps=None):
+        bits = op_bits(om)
+        self.slots = [(l, k) for l in range(bits.shape[0]) for k in range(5) if bits[l, k] > 0]
+        self.bits, self.exps, self.calls = bits, None if exps is None else np.asarray(exps), 0
+        self.natural = []   # one (n_layers, 5) array per forward
+
+    def __call__(self, v):
+        l, k = self.slots[self.calls % len(self.slots)]
+        if self.calls % len(self.slots) == 0:
+            self.natural.append(np.zeros_like(self.bits))
+        self.calls += 1
+        self.natural[-1][l, k] = self.bits[l, k] - 1 - O.intbits_f32(v[0], 1e-6)
+        if self.exps is None:
+            return v
+        ib = int(self.bits[l, k]) - 1 - int(self.exps[l, k])
+        assert ib >= 0, (l, k, self.exps[l, k])
+        return np.full_like(v, forced_float(ib))
+
+
+@contextlib.contextmanager
+def hooked(om, exps=None):
+    h, old = _Hook(om, exps), O.MAX_EXCHANGE
+    O.MAX_EXCHANGE = h
+    try:
+        yield h
+    finally:
+        O.MAX_EXCHANGE = old
+
+
+def oracle_run(om, clip, bits, exp, exps=None, chunks=None, state=None):
+    """clip (L, d_in) int32 through the oracle as the chunks `chunks` (default: one) with the carry handed on, at the stated
+    `exps` (None: each chunk's own).  state: (n_layers, 2, P) carry in or None (zeros).
+    Returns (y (L, d_out), carry out (n_layers, 2, P), the exponents each chunk would have chosen / was given)."""
+    L = clip.shape[0]
+    chunks = [L] if chunks is None else list(chunks)
+    assert sum(chunks) == L
+    st = om.zero_state((1,))
+    if state is not None:
+        for i in range(len(st)):
+            st[i][0], st[i][1] = state[i, 0][None].astype(np.int32).copy(), state[i, 1][None].astype(np.int32).copy()
+    ys, at = [], 0
+    with hooked(om, exps) as h:
+        for c in chunks:
+            if c:
+                ys.append(om(O.Fx(clip[None, at:at + c], bits, exp, True), state=st).data[0])
+            at += c
+    y = np.concatenate(ys, axis=0) if ys else np.zeros((0, om.decoder.weight.data.shape[1]), dtype=np.int32)
+    carry = np.stack([np.stack([s[0][0], s[1][0]]) for s in st]).astype(np.int32)
+    return y, carry, (h.natural if exps is None else [np.asarray(exps)] * len(h.natural))
+
+
+def shifts_ok(om, exps) -> bool:
+    """The host rule of s5fxp_model_exps_check for the static shifts, restated from the ops' definitions: an add's two operand
+    shifts and its result shift (fxparray.py:420-448), a mul's right shift (fxparray.py:619-621), the change_cfg to the SSM
+    input, the decoder's input conversion and right shift."""
+    e = np.asarray(exps)
+
+    def add_ok(eo, xe, ye):
+        ea = max(xe, ye)
+        return ea - xe <= 31 and ea - ye <= 31 and -31 <= eo - ea <= 31
+
+    hb, he = om.encoder.qc["out_bits"], om.encoder.qc["out_exp"]
+    for i, l in enumerate(om.layers):
+        n = l.norm
+        if not add_ok(e[i, 0], he, n.minus_mean.exp) or not 0 <= e[i, 0] + n.invsq_var.exp - e[i, 1] <= 31:
+            return False
+        be = e[i, 1]
+        if n.scale is not None:
+            if not 0 <= be + n.scale.exp - e[i, 2] <= 31:
+                return False
+            be = e[i, 2]
+        if n.bias is not None:
+            if not add_ok(e[i, 3], be, n.bias.exp):
+                return False
+            be = e[i, 3]
+        if abs(int(be) - l.mixer.qc["activations"]["u"]["exp"]) > 31:
+            return False
+        if not add_ok(e[i, 4], l.qc["multgate"]["res_exp"], he):
+            return False
+        hb, he = l.qc["multgate"]["res_bits"], e[i, 4]
+    d = om.decoder.qc
+    conv = hb > d["inp_bits"] or he > d["inp_exp"]
+    if conv and abs(int(he) - d["inp_exp"]) > 31:
+        return False
+    return 0 <= (d["inp_exp"] if conv else he) + d["w_exp"] - d["out_exp"] <= 31
+
+
+def shifted(om, base, delta: int) -> np.ndarray:
+    """`base` with every op moved by `delta` where that is legal: inside 0 .. exp_max and with every static shift in range.
+    Ops are moved one after the other, in model order, and an op whose move breaks a shift keeps its value."""
+    mx, e = exp_max(om), np.asarray(base, dtype=np.int32).copy()
+    for l in range(e.shape[0]):
+        for k in range(5):
+            if mx[l, k] < 0:
+                continue
+            old = e[l, k]
+            e[l, k] = min(max(old + delta, 0), mx[l, k])
+            if not shifts_ok(om, e):
+                e[l, k] = old
+    return e
