@@ -17,6 +17,17 @@
     static_assert(FT * VPF % 384 == 0, "tile shape");
     extern __shared__ __attribute__((aligned(16))) int8_t smem[];
     int8_t *Xh = smem, *Xl = Xh + FT * KP;
+    // Phase B writes its values into an LDS tile behind the planes -- the flat image of the tile's FT x M block of y, pitch
+    // exactly M, no padding -- and after the closing barrier all threads move that block out as 16-byte vectors: one wave
+    // instruction covers 1 KB of consecutive addresses, where a store from the accumulator layout covers two 128-byte pieces
+    // of two rows.  Vector v = threadIdx.x + 384 i; a wave issues round i while one of its lanes has a vector.
+    int8_t *Yt = Xl + FT * KP;
+    constexpr int MAXR = (FT * 288 * (int)YB / 16 + 383) / 384;                  // rounds at the widest output (M <= 288)
+    static_assert(MAXR <= 12, "vm_wait_upto12");
+    const unsigned nvec_full = (unsigned)(FT * YB / 16) * (unsigned)a.M;        // 16-byte vectors of a full tile: FT M YB is a multiple of 16
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // the copy-out's store instructions of this wave on a full tile (a partly active last round is issued)
+    const int cnt_full = nvec_full > 64u * wv ? (int)((nvec_full - 64u * wv + 383u) / 384u) : 0;
     zero_plane_tail<H, HP, KP>(Xh, 2 * FT); // (visible behind the first tile's barrier)
     const int l = threadIdx.x & 63, r = l & 31, h = l >> 5, wave = threadIdx.x >> 6;
     const int sub = wave / 3, c0 = wave % 3;
@@ -71,7 +82,7 @@
             if (RESID && !(USUM && rz.usum))
                 rawz[i] = gload16_hidden(reinterpret_cast<const char *>(rz.z + tl * FT * H), 2u * (unsigned)(f * H + 8 * (v % VPF)));
             // issued behind the compiler's back (see vm_wait): its wait-count pass would otherwise guard the first use of
-            // these registers, a tile later, with vmcnt(0) -- behind the 48 stores of this tile's phase B
+            // these registers, a tile later, with vmcnt(0) -- behind the stores of this tile's copy-out
             raw[i] = gload16_hidden(reinterpret_cast<const char *>(a.x + tl * FT * H), 2u * (unsigned)(f * H + 8 * (v % VPF)));
         }
     };
@@ -80,10 +91,10 @@
     prologue_loads_done();
     for (; tile < tiles; tile += gridDim.x) {
         const int64_t n0 = tile * FT;
-        // the prefetched rows are older than the previous tile's 3 x 16 stores per wave (every tile but the tensor's last is
-        // full and stores unconditionally; that last one has no successor)
-        vm_wait<3 * 16>(raw);
-        if (RESID && !(USUM && rz.usum)) vm_wait<3 * 16>(rawz);
+        // the prefetched rows are older than the previous tile's copy-out and nothing else: cnt_full stores of this wave (every
+        // tile but the tensor's last is full; that last one has no successor, and the first tile's rows have arrived)
+        vm_wait_upto12(cnt_full, raw);
+        if (RESID && !(USUM && rz.usum)) vm_wait_upto12(cnt_full, rawz);
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int v = threadIdx.x + 384 * i, f = v / VPF, og = v % VPF;
@@ -114,7 +125,6 @@
         if (tile + gridDim.x < tiles) fetch(tile + gridDim.x);
         __syncthreads();
         const int8_t *rowh = Xh + (32 * sub + r) * KP + 16 * h, *rowl = Xl + (32 * sub + r) * KP + 16 * h;
-        const int64_t nb = n0 + 32 * sub + 4 * h; // frame of accumulator register 0
 #pragma unroll
         for (int c = 0; c < CPW; ++c) {
             const int col = 32 * (c0 + 3 * c) + r;
@@ -129,44 +139,68 @@
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
                 acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(*reinterpret_cast<const v4i *>(rowl + 32 * ks), wreg[c][ks], acc, 0, 0, 0);
-            // Stores without control flow around them on full tiles (all but the tensor's last): lanes of the ragged last
-            // column tile (col >= M) write to a sink word instead of being masked off.  Every conditional store would make
-            // the number of memory operations in flight unknowable to the compiler's wait-count pass, and the wait it
-            // then puts at the top of the next tile -- for the rows prefetched BEFORE these stores -- degenerates to
-            // vmcnt(0): every tile would begin by waiting for the previous tile's stores to be acknowledged.
-            const bool okc = col < a.M;
-            char *ybase; // this tile's first output row
-            if constexpr (I16) ybase = reinterpret_cast<char *>(reinterpret_cast<int16_t *>(a.y) + n0 * a.M);
-            else ybase = reinterpret_cast<char *>(a.y + n0 * a.M);
-            char *yl = okc ? ybase + YB * (unsigned)((32 * sub + 4 * h) * a.M + col)
-                           : reinterpret_cast<char *>(as_global(&g_store_sink[l]));
-            const unsigned ystep = okc ? YB * (unsigned)a.M : 0u;
-            if (n0 + FT <= a.N) {
-                char *yp = yl; // a running pointer: sixteen hoisted offsets per column tile would cost the kernel its occupancy
+            // one LDS store per value; lanes of the ragged last column tile (col >= M) write nothing.  Frames past the end of the
+            // tensor hold copies of its last row (fetch clamps) and are written too: the copy-out leaves them behind
+            if (col < a.M) {
+                // a running pointer formed per tile: sixteen hoisted offsets per column tile would cost the kernel its registers
+                unsigned tq = YB * (unsigned)((32 * sub + 4 * h) * a.M + col);
+                asm volatile("" : "+v"(tq));
+                int8_t *tp = Yt + tq;
+                const unsigned tstep = YB * (unsigned)a.M;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) { // frames (i & 3) + 8 * (i >> 2)
                     const int32_t v = sat(asr(acc[i], rs), so);
-                    if constexpr (F32) *reinterpret_cast<float *>(yp) = tofloat(sat(wadd(v, bev[c]), so), a.out_exp);
-                    else if constexpr (I16) *reinterpret_cast<int16_t *>(yp) = (int16_t)sat(wadd(v, bev[c]), so);
-                    else *reinterpret_cast<int32_t *>(yp) = sat(wadd(v, bev[c]), so);
-                    yp += (i & 3) == 3 ? 5 * ystep : ystep;
+                    if constexpr (F32) *reinterpret_cast<float *>(tp) = tofloat(sat(wadd(v, bev[c]), so), a.out_exp);
+                    else if constexpr (I16) *reinterpret_cast<int16_t *>(tp) = (int16_t)sat(wadd(v, bev[c]), so);
+                    else *reinterpret_cast<int32_t *>(tp) = sat(wadd(v, bev[c]), so);
+                    tp += (i & 3) == 3 ? 5 * tstep : tstep;
                 }
-            } else {
-                char *yp = yl;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int fo = (i & 3) + 8 * (i >> 2);
-                    if (nb + fo < a.N) {
-                        const int32_t v = sat(asr(acc[i], rs), so);
-                        if constexpr (F32) *reinterpret_cast<float *>(yp) = tofloat(sat(wadd(v, bev[c]), so), a.out_exp);
-                        else if constexpr (I16) *reinterpret_cast<int16_t *>(yp) = (int16_t)sat(wadd(v, bev[c]), so);
-                        else *reinterpret_cast<int32_t *>(yp) = sat(wadd(v, bev[c]), so);
-                    }
-                    yp += (i & 3) == 3 ? 5 * ystep : ystep;
-                }
-                prologue_loads_done(); // the tensor's last tile: nothing is left in flight on this path
             }
             __builtin_amdgcn_sched_barrier(0); // one column tile at a time: interleaved, the three of a wave do not fit its registers
         }
-        __syncthreads(); // planes are single-buffered
+        __syncthreads(); // planes are single-buffered; the output tile is complete
+        {
+            // ---- copy-out: the tile's valid bytes, front to back.  The tile's base is aligned to an output element and no
+            // further (a group's y lies B L M elements behind the previous one's), and that is all these stores assume.
+            const int64_t left = a.N - n0;
+            const unsigned nbytes = left >= FT ? 16u * nvec_full : YB * (unsigned)left * (unsigned)a.M, nvec = nbytes >> 4;
+            char *yt; // wave-uniform; 32-bit byte offsets from here
+            if constexpr (I16) yt = reinterpret_cast<char *>(reinterpret_cast<int16_t *>(a.y) + n0 * a.M);
+            else yt = reinterpret_cast<char *>(a.y + n0 * a.M);
+            constexpr int CH = 6; // rounds whose LDS reads are in flight together
+            // the thread index is hidden from the compiler here, so that a round's offsets are formed per tile from one
+            // register: hoisted out of the tile loop, the twelve rounds' LDS and global offsets are forty registers and spill
+            unsigned tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));
+            const unsigned o0 = 16u * tid, vbytes = 16u * nvec;
+#pragma unroll
+            for (int i0 = 0; i0 < MAXR; i0 += CH) {
+                v4i t[CH];
+#pragma unroll
+                for (int i = i0; i < i0 + CH && i < MAXR; ++i) { // (read unconditionally, clamped into the tile: a round nobody stores, the twelfth at M = 257, costs one LDS read)
+                    const unsigned o = o0 + 6144u * i;
+                    t[i - i0] = *reinterpret_cast<const v4i *>(Yt + (o < 16u * nvec_full ? o : 16u * nvec_full - 16u));
+                }
+#pragma unroll
+                for (int i = i0; i < i0 + CH && i < MAXR; ++i) {
+                    const unsigned o = o0 + 6144u * i;
+                    if (6144u * i + 1024u * wv < vbytes) { // wave-uniform: a round this wave has a vector in is one store instruction
+                        if (o < vbytes) {
+                            if constexpr (I16) *reinterpret_cast<v16y_2 *>(yt + o) = t[i - i0];
+                            else *reinterpret_cast<v16y_4 *>(yt + o) = t[i - i0];
+                        }
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (left < FT) {
+                // the tensor's last tile: the remainder behind its whole vectors, one element per thread
+                if (threadIdx.x < (nbytes & 15u) / YB) {
+                    const unsigned o = 16u * nvec + YB * threadIdx.x;
+                    if constexpr (I16) *reinterpret_cast<int16_t *>(yt + o) = *reinterpret_cast<const int16_t *>(Yt + o);
+                    else *reinterpret_cast<int32_t *>(yt + o) = *reinterpret_cast<const int32_t *>(Yt + o);
+                }
+                prologue_loads_done(); // nothing is left in flight on this path
+            }
+        }
     }

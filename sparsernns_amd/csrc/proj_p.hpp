@@ -492,13 +492,24 @@ __global__ __launch_bounds__(384, 3) void k_enc_ps(EncArgs a, float *ext, int ex
 }
 
 // ---------------------------------------------------------------------------------------------
-// where masked-off lanes of a store send their value instead (never read)
-__device__ int32_t g_store_sink[64];
 // Decoder, phase-split: h int16 (N,H) -> dense int32 (N,M), M <= 288.  fxpmodel.py:331-366, 1272-1274.
-// Six waves, 64-frame tiles.  Phase B runs as D = X * W (lane = output column, registers = frames): every
-// store instruction writes 128 contiguous bytes of one output row per half wave.
-// LDS: [X hi][X lo]
+// Six waves, 64-frame tiles.  Phase B runs as D = X * W (lane = output column, registers = frames) and writes its values into
+// an LDS image of the tile's block of y; behind the closing barrier the whole workgroup moves the block out as 16-byte
+// vectors, 1 KB of consecutive addresses per wave instruction (proj_dec_body.inc).
+// LDS: [X hi][X lo][Y tile: 64 x M output elements]
 // ---------------------------------------------------------------------------------------------
+// A 16-byte vector at the alignment of an output element: the copy-out's stores assume no more of a tile's base.
+typedef v4i v16y_4 __attribute__((aligned(4)));
+typedef v4i v16y_2 __attribute__((aligned(2)));
+// dynamic LDS of a decoder workgroup (KS: k-steps of the byte planes, io: the boundary's element type): the two byte planes
+// and the output tile
+__host__ __device__ constexpr size_t dec_lds_bytes(int KS, int io, int M)
+{
+    return 2 * 64 * (size_t)(32 * KS + 16) + 64 * (size_t)M * (io == IO_I16 ? 2 : 4);
+}
+// whether two decoder workgroups share a CU's 160 KB of LDS (the RESID kernels hold 16 static bytes on top of the dynamic ones)
+constexpr size_t CU_LDS_BYTES = 160 * 1024, DEC_STATIC_LDS = 16;
+__host__ __device__ constexpr bool dec_two_per_cu(size_t dynamic_lds) { return 2 * (dynamic_lds + DEC_STATIC_LDS) <= CU_LDS_BYTES; }
 // RESID: the last layer's residual pass (mfma_bn.hpp k_resid_minmax16 without its extremes, which nobody needs after the
 // last layer) happens here, on the way in: a.x is the layer's INPUT (skip), rz.z the gate kernel's output, and
 // h = relu(z + skip) (fxpmodel.py:1147-1159) is formed in registers -- the h plane is neither written nor read back
@@ -512,31 +523,35 @@ struct DecResid {
     int32_t res_bits, skip_bits;
     int32_t usum;
 };
+// (Registers: budgeted for three waves per SIMD, two workgroups per CU -- what the launcher's grid asks for and, with a 4-byte
+// output tile at H <= 96, what the LDS holds; for two waves per SIMD where the tile leaves room for one workgroup, and at
+// KS = 6 with the residual pass or an int16 output, whose weights and prefetch do not fit 168 registers.)
+__host__ __device__ constexpr int dec_waves(int KS, bool RESID, int io)
+{
+    return (KS == 6 && (RESID || io == IO_I16)) || (io != IO_I16 && KS >= 5) ? 2 : 3;
+}
 template <int KS, bool RESID = false>
-__global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_p(DecArgs a, DecResid rz, GroupOff go)
+__global__ __launch_bounds__(384, dec_waves(KS, RESID, IO_I32)) void k_dec_p(DecArgs a, DecResid rz, GroupOff go)
 {
     constexpr int IO = IO_I32;
 #include "proj_dec_body.inc"
 }
 
-// k_dec_p with a float32 output (s5fxp_model_forward_f32): every value is stored as to_float of k_dec_p's result
-// (fxparray.py:72-73, fxp_prims.hpp tofloat, rounded as k_to_float rounds), one 4-byte store per value on the same
-// addresses, so the store count per tile (vm_wait<48>) holds; ragged column tiles still go to g_store_sink.  One body,
-// shared as text for the reason given at k_enc_pf.
+// k_dec_p with a float32 output (s5fxp_model_forward_f32): every value goes into the tile as to_float of k_dec_p's result
+// (fxparray.py:72-73, fxp_prims.hpp tofloat, rounded as k_to_float rounds), the same 4 bytes per value, so the tile, the
+// copy-out and its store count are k_dec_p's.  One body, shared as text for the reason given at k_enc_pf.
 template <int KS, bool RESID>
-__global__ __launch_bounds__(384, KS == 6 && RESID ? 2 : 3) void k_dec_pf(DecArgs a, DecResid rz, GroupOff go)
+__global__ __launch_bounds__(384, dec_waves(KS, RESID, IO_F32)) void k_dec_pf(DecArgs a, DecResid rz, GroupOff go)
 {
     constexpr int IO = IO_F32;
 #include "proj_dec_body.inc"
 }
 
 // k_dec_p with an int16 output (s5fxp_model_forward_i16; the host has checked out_bits <= 16, so the narrowing loses
-// nothing): one 2-byte store per value on the same running pointer with a row step of 2 M bytes -- 64 contiguous bytes of
-// one output row per half wave and store, the same 48 stores per tile; ragged column tiles still go to g_store_sink.
-// (Registers: at KS = 6 both forms are budgeted for two workgroups per CU -- k_dec_p<6, false> spills two registers under its
-// bound of three.  Measured at 32 x 4096 frames: 39.0 us against k_dec_p<6, false>'s 43.7, profiles/r13_i16_io_kernel_stats.txt.)
+// nothing): one 2-byte LDS store per value into a tile of half the size (pitch 2 M bytes), and half as many 16-byte vectors
+// in the copy-out, at 2-byte alignment.
 template <int KS, bool RESID>
-__global__ __launch_bounds__(384, KS == 6 ? 2 : 3) void k_dec_ps(DecArgs a, DecResid rz, GroupOff go)
+__global__ __launch_bounds__(384, dec_waves(KS, RESID, IO_I16)) void k_dec_ps(DecArgs a, DecResid rz, GroupOff go)
 {
     constexpr int IO = IO_I16;
 #include "proj_dec_body.inc"

@@ -1002,15 +1002,18 @@ struct FusedForward {
                 a.x = zp;
             }
         }
-        const size_t smem = 2 * 64 * (size_t)(sh.hp + 16);
-        // 192 channels: 2 x 4 vectors of prefetch, one workgroup per CU
+        // the byte planes and the staged output tile (proj_p.hpp dec_lds_bytes): 80 KB at H = 96 with a 4-byte output, two
+        // workgroups per CU, which is what cap_dec asks for; where only one fits (H >= 144 with a 4-byte output) the grid is
+        // halved, so that all its workgroups are resident at once
+        const size_t smem = dec_lds_bytes(sh.nt, io, e.M);
+        const unsigned grid = dec_two_per_cu(smem) ? grid_dec : grid_for(tiles64, std::max<int64_t>(per_group(cfg.cap_dec, 64) / 2, 1));
         auto kernel = nt_kernel(sh.nt, [&](auto n) {
             constexpr int NT = decltype(n)::value;
             return io == IO_F32   ? (dec_resid >= 0 ? k_dec_pf<NT, true> : k_dec_pf<NT, false>)
                    : io == IO_I16 ? (dec_resid >= 0 ? k_dec_ps<NT, true> : k_dec_ps<NT, false>)
                                   : (dec_resid >= 0 ? k_dec_p<NT, true> : k_dec_p<NT, false>);
         });
-        launch(kernel, grid_dec, 384, smem, nullptr, nullptr, a, dz);
+        launch(kernel, grid, 384, smem, nullptr, nullptr, a, dz);
     }
 };
 

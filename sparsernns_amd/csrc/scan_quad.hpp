@@ -125,6 +125,29 @@ __device__ __forceinline__ void vm_wait_or_drain(bool counted, T (&regs)[N])
     for (int i = 0; i < N; ++i) asm volatile("" : "+v"(regs[i]));
 }
 
+// The same wait where the count is known only at run time: `newer` (wave-uniform, any value >= 0) operations have been issued
+// since the loads, and the wait is vmcnt(min(newer, 12)) -- exact up to 12, and beyond it merely earlier than it had to be.
+// vmcnt takes an immediate, so this is a ladder: scalar compares from 12 down choose the rung to enter at, and the waits stand
+// in rising order behind them, so that the rungs a wave falls through after its own ask for less than it has already waited
+// for.  One statement, as vm_wait_or_drain: no path leads around the waits, in the compiler's layout or in an audit's reading.
+#define S5_VMW_CMP(k) "s_cmp_ge_u32 %0, " #k "\n\ts_cbranch_scc1 1" #k "f\n\t"
+#define S5_VMW_RUNG(k) "1" #k ":\n\ts_waitcnt vmcnt(" #k ")\n"
+template <class T, int N>
+__device__ __forceinline__ void vm_wait_upto12(int newer, T (&regs)[N])
+{
+    asm volatile(S5_VMW_CMP(12) S5_VMW_CMP(11) S5_VMW_CMP(10) S5_VMW_CMP(9) S5_VMW_CMP(8) S5_VMW_CMP(7) S5_VMW_CMP(6) S5_VMW_CMP(5)
+                 S5_VMW_CMP(4) S5_VMW_CMP(3) S5_VMW_CMP(2) S5_VMW_CMP(1) "s_waitcnt vmcnt(0)\n"
+                 S5_VMW_RUNG(1) S5_VMW_RUNG(2) S5_VMW_RUNG(3) S5_VMW_RUNG(4) S5_VMW_RUNG(5) S5_VMW_RUNG(6) S5_VMW_RUNG(7) S5_VMW_RUNG(8)
+                 S5_VMW_RUNG(9) S5_VMW_RUNG(10) S5_VMW_RUNG(11) S5_VMW_RUNG(12)
+                 :
+                 : "s"(__builtin_amdgcn_readfirstlane(newer))
+                 : "memory", "scc");
+#pragma unroll
+    for (int i = 0; i < N; ++i) asm volatile("" : "+v"(regs[i]));
+}
+#undef S5_VMW_CMP
+#undef S5_VMW_RUNG
+
 // word index of (sequence b, step t, state p, component c) in a scan-native stream with TB blocks/sequence
 __device__ __forceinline__ int64_t native_word(int64_t b, int t, int p, int c, int TB, int P)
 {

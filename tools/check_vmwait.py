@@ -4,7 +4,8 @@ by hand, scan_quad.hpp vm_wait) are only right while the compiler issues exactly
 taken from: N stores per wave on a full tile, the same number again on the guarded path of a partial tile.  If a later
 compiler merged or split those stores, vm_wait<N> would return before the prefetch has landed.  This compiles the device
 code to assembly (no GPU needed) and checks, per kernel, that the hand-written wait is there and that the kernel holds
-2 x N tile stores (+ the few prologue stores).
+2 x N tile stores (+ the few prologue stores).  The decoders copy their output tile out of LDS in rounds and wait by a run-time
+count of rounds: there the check is one 16-byte store instruction per round (DEC_EXPECT).
 
 The same loads break in a second way: the compiler does not know their destination registers are being written, so it may
 copy, spill or reuse them before the data has landed.  The register audit follows every hidden load (a global_load inside
@@ -35,26 +36,25 @@ SRC = os.path.join(ROOT, "sparsernns_amd", "csrc", "s5fxp_api.hip")
 GATE_SRC = os.path.join(ROOT, "tools", "gate_kernels.hip")
 # mangled prefix -> (stores per wave and full tile = the wait count, prologue stores allowed on top of 2 x that)
 EXPECT = {
-    "_ZN2s57k_dec_pILi3ELb0EE": (48, 0), "_ZN2s57k_dec_pILi6ELb0EE": (48, 0),
-    "_ZN2s57k_dec_pILi3ELb1EE": (48, 2), "_ZN2s57k_dec_pILi6ELb1EE": (48, 2),
     "_ZN2s57k_enc_pILi3EE": (4, 0), "_ZN2s57k_enc_pILi6EE": (8, 0),
-    # float in / float out (proj_p.hpp k_enc_pf / k_dec_pf: the same bodies, proj_enc_body.inc / proj_dec_body.inc): the same stores
-    "_ZN2s58k_dec_pfILi3ELb0EE": (48, 0), "_ZN2s58k_dec_pfILi6ELb0EE": (48, 0),
-    "_ZN2s58k_dec_pfILi3ELb1EE": (48, 2), "_ZN2s58k_dec_pfILi6ELb1EE": (48, 2),
+    # float in (proj_p.hpp k_enc_pf: the same body, proj_enc_body.inc): the same stores
     "_ZN2s58k_enc_pfILi3EE": (4, 0), "_ZN2s58k_enc_pfILi6EE": (8, 0),
-    # the decoders of the ragged shapes (H = 48, 144): the same 48 stores.  (Their encoders, k_enc_p<2> / <5>, store
-    # conditionally and wait for their prefetch with vmcnt(0); the register audit below covers them.)
-    "_ZN2s57k_dec_pILi2ELb0EE": (48, 0), "_ZN2s57k_dec_pILi5ELb0EE": (48, 0),
-    "_ZN2s57k_dec_pILi2ELb1EE": (48, 2), "_ZN2s57k_dec_pILi5ELb1EE": (48, 2),
-    "_ZN2s58k_dec_pfILi2ELb0EE": (48, 0), "_ZN2s58k_dec_pfILi5ELb0EE": (48, 0),
-    "_ZN2s58k_dec_pfILi2ELb1EE": (48, 2), "_ZN2s58k_dec_pfILi5ELb1EE": (48, 2),
-    # int16 in / int16 out (k_enc_ps / k_dec_ps, the same bodies again): 8-byte hidden row loads, 2-byte output stores, the same counts
-    "_ZN2s58k_dec_psILi3ELb0EE": (48, 0), "_ZN2s58k_dec_psILi6ELb0EE": (48, 0),
-    "_ZN2s58k_dec_psILi3ELb1EE": (48, 2), "_ZN2s58k_dec_psILi6ELb1EE": (48, 2),
-    "_ZN2s58k_dec_psILi2ELb0EE": (48, 0), "_ZN2s58k_dec_psILi5ELb0EE": (48, 0),
-    "_ZN2s58k_dec_psILi2ELb1EE": (48, 2), "_ZN2s58k_dec_psILi5ELb1EE": (48, 2),
+    # (The encoders of the ragged shapes, k_enc_p<2> / <5>, store conditionally and wait for their prefetch with vmcnt(0); the
+    # register audit below covers them.)
+    # int16 in (k_enc_ps, the same body again): 8-byte hidden row loads, the same counts
     "_ZN2s58k_enc_psILi3EE": (4, 0), "_ZN2s58k_enc_psILi6EE": (8, 0),
 }
+
+# The decoders (proj_dec_body.inc) stage a tile of y in LDS and copy it out in rounds of one 16-byte store per lane; a wave waits for
+# its prefetch by the number of rounds it took part in (scan_quad.hpp vm_wait_upto12: a ladder of waits, entered by a run-time
+# count).  That count is right while a round is ONE store instruction: mangled prefix -> (rounds at the widest output = 16-byte
+# stores of the tile loop, prologue stores on top: RESID publishes its AddCb, one of the two a 16-byte store).  The tile loop
+# holds one more store, the element-wise remainder of a tensor's last tile.
+DEC_EXPECT = {}
+for _k, _name, _rounds in (("7k_dec_p", "int32", 12), ("8k_dec_pf", "float32", 12), ("8k_dec_ps", "int16", 6)):
+    for _nt in (2, 3, 5, 6):
+        DEC_EXPECT[f"_ZN2s5{_k}ILi{_nt}ELb0EE"] = (_rounds, 0)
+        DEC_EXPECT[f"_ZN2s5{_k}ILi{_nt}ELb1EE"] = (_rounds, 2)
 
 # the gate kernels that request their states early: mangled prefix (both overloads) -> stores of the staging per wave = the counted wait
 GATE_EXPECT = {
@@ -245,6 +245,20 @@ def main(argv) -> int:
         waits = len(re.findall(rf"s_waitcnt vmcnt\({n}\)\s*$", body, re.M))
         ok = waits >= 1 and stores == 2 * n + extra
         print(f"{key}: {stores} stores (expected {2 * n + extra}), {waits} x vmcnt({n}): {'ok' if ok else 'MISMATCH'}")
+        bad += 0 if ok else 1
+    for key, (rounds, extra) in ({} if gate_only else DEC_EXPECT).items():
+        m = re.search(r"^" + re.escape(key) + r"[^\n]*\n(.*?)^\.Lfunc_end", text, re.S | re.M)
+        if not m:
+            print(f"{key}: kernel not found")
+            bad += 1
+            continue
+        body = m.group(1)
+        stores = len(re.findall(r"^\s*global_store", body, re.M))
+        x4 = len(re.findall(r"^\s*global_store_dwordx4", body, re.M))
+        rungs = [len(re.findall(rf"s_waitcnt vmcnt\({n}\)\s*$", body, re.M)) for n in range(13)]
+        ok = min(rungs) >= 1 and x4 == rounds + (1 if extra else 0) and stores == rounds + 1 + extra
+        print(f"{key}: {x4} 16-byte stores (expected {rounds + (1 if extra else 0)}), {stores} stores in all (expected {rounds + 1 + extra}), "
+              f"wait ladder {'complete' if min(rungs) >= 1 else 'INCOMPLETE'}: {'ok' if ok else 'MISMATCH'}")
         bad += 0 if ok else 1
     for key in GATE_EXPECT:   # both overloads of each (CGateArgs, CGateFoldArgs)
         found = len(re.findall(r"^" + re.escape(key) + r"\w*:", text, re.M))
