@@ -630,8 +630,8 @@ int s5fxp_model_clips_traced_f32(const s5fxp_model *m, const float *x, int x_bit
  * or NEGEXP (both are refused here, on the host); [8+8l+0..4] hold the stated exponents, 0 for an op the layer lacks; all
  * other words as the namesake writes them.  The kernels hold no maxima loop and no reduction.
  * Checked before the device is touched: the namesake's checks, S5FXP_EBADARG for a null exps, then s5fxp_model_exps_check.
- * Not served at stated exponents: s5fxp_model_forward* (a pinned batch is a clip list), the traced clip entries, exponents in
- * device memory or per clip. */
+ * Not served at stated exponents: traced forwards and the traced clip entries, exponents in device memory or per clip or
+ * per sequence, the multi-GPU forward.  (The batch forward is served: s5fxp_model_forward_at* below.) */
 /* The largest exponent op k (0..4, the order above) of `layer` can take: its result bits - 1, the exponent of a result
  * whose maximum is below 1 (intbits is never negative).  -1 for an op the layer lacks or a bad argument.  Any model. */
 int s5fxp_model_exp_max(const s5fxp_model *m, int layer, int k);
@@ -658,6 +658,31 @@ int s5fxp_model_clips_at(const s5fxp_model *m, const int32_t *x, int x_bits, int
 int s5fxp_model_clips_at_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int n, int Lmax, const int32_t *lens,
                              float *y, const int32_t *state_in, int32_t *state_out, void *workspace, size_t workspace_bytes,
                              int32_t *status, const int32_t *exps, void *stream);
+
+/* The batch forward at stated exponents: s5fxp_model_forward / _f32 / _i16 with `exps` in front of `stream`,
+ * on the whole chip like its namesake.  Every sequence of the batch, and every group of a grouped launch (opts->groups), gets
+ * bit for bit the rows s5fxp_model_clips_at[_f32] gives that sequence alone at the same exponents; with opts->state_in /
+ * state_out the carry matches too, chunk for chunk, so a signal cut into several calls gives the rows of one call.  A value
+ * beyond the range an exponent leaves saturates at the op's result bits.  Everything else is the namesake's: the S5FXP_FWD_*
+ * flags and the recurrence rungs they choose, S5FXP_ST_REDO / WIDE_STATE / WIDE_INPUT, live-state compaction, padding, and the
+ * workspace (s5fxp_workspace_bytes*).  Status words: [0] never carries NEGSHIFT or NEGEXP; [2] is S5FXP_PATH_FUSED;
+ * [8+8l+0..4] hold the stated exponents, 0 for an op the layer lacks; [8+8l+5..7] as the namesake writes them.
+ * opts->allreduce is NEVER called: with every exponent stated there is no maximum to exchange, and ranks that pass the same
+ * exps agree without talking.  A grouped call runs its groups one after the other.
+ * Checked before the device is touched, in this order: the namesake's checks; S5FXP_EBADARG for a null exps;
+ * S5FXP_EUNSUPPORTED for a non-null `traces`; s5fxp_model_exps_check (which refuses a generic model).
+ * A fused model whose unpinned forward takes four full reductions per layer (a BatchNorm operand exponent outside 0..15, or a
+ * model created under S5FXP_NO_BN_EXT) is served, not refused: the same kernels read the stated exponents, and the residual
+ * add runs as the two-plane pass of that route. */
+int s5fxp_model_forward_at(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int B, int L, int32_t *y, void *workspace,
+                           size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces, const s5fxp_forward_opts *opts,
+                           const int32_t *exps, void *stream);
+int s5fxp_model_forward_at_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int B, int L, float *y, void *workspace,
+                               size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces,
+                               const s5fxp_forward_opts *opts, const int32_t *exps, void *stream);
+int s5fxp_model_forward_at_i16(const s5fxp_model *m, const int16_t *x, int x_bits, int x_exp, int B, int L, int16_t *y,
+                               void *workspace, size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces,
+                               const s5fxp_forward_opts *opts, const int32_t *exps, void *stream);
 
 /* FxpSequenceLayer.forward, fxpmodel.py:1110-1161, for layer `layer` of a created model -- the unit the reference's
  * verification walks (fxprun.py:583-727).  x: (B,L,H) int32 device with configuration (x_bits, x_exp); y: (B,L,H) int32

@@ -226,6 +226,9 @@ def _load():
         "s5fxp_model_step_ragged_at_f32": (i, [p, p, i, i, i, i, i, p, p, p, i, p, p, p]),
         "s5fxp_model_clips_at": (i, [p, p, i, i, i, i, p, p, p, p, p, C.c_size_t, p, p, p]),
         "s5fxp_model_clips_at_f32": (i, [p, p, i, i, i, i, p, p, p, p, p, C.c_size_t, p, p, p]),
+        "s5fxp_model_forward_at": (i, [p, p, i, i, i, i, p, p, C.c_size_t, p, C.POINTER(LayerTrace), C.POINTER(ForwardOpts), p, p]),
+        "s5fxp_model_forward_at_f32": (i, [p, p, i, i, i, i, p, p, C.c_size_t, p, C.POINTER(LayerTrace), C.POINTER(ForwardOpts), p, p]),
+        "s5fxp_model_forward_at_i16": (i, [p, p, i, i, i, i, p, p, C.c_size_t, p, C.POINTER(LayerTrace), C.POINTER(ForwardOpts), p, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale: rebuild
@@ -254,7 +257,8 @@ EXPORTED_SYMBOLS = ("s5fxp_version s5fxp_strerror s5fxp_from_fp s5fxp_to_float s
                     "s5fxp_model_clips_traced s5fxp_model_clips_traced_f32 s5fxp_float_model_clips_traced "
                     "s5fxp_stage_err_clips_workspace_bytes s5fxp_stage_err_clips "
                     "s5fxp_model_exp_max s5fxp_model_exps_check s5fxp_model_step_at s5fxp_model_step_at_f32 "
-                    "s5fxp_model_step_ragged_at s5fxp_model_step_ragged_at_f32 s5fxp_model_clips_at s5fxp_model_clips_at_f32").split()
+                    "s5fxp_model_step_ragged_at s5fxp_model_step_ragged_at_f32 s5fxp_model_clips_at s5fxp_model_clips_at_f32 "
+                    "s5fxp_model_forward_at s5fxp_model_forward_at_f32 s5fxp_model_forward_at_i16").split()
 
 
 def check(rc: int, what: str = "") -> None:

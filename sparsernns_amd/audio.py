@@ -221,7 +221,17 @@ def mask_istft_i16(audio: torch.Tensor, mask: torch.Tensor, mask_exp: int, clean
     return _istft_launch(audio, n_seg, cleaned_mag, "s5fxp_mask_istft_i16", mask.data_ptr(), int(mask_exp))
 
 
-def denoise_fused(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, boundary: str = "float32"):
+def _forward_at(model, x: torch.Tensor, inp_bits: int, inp_exp: int, exps) -> torch.Tensor:
+    """The model on the rows x (float32 or int16) at stated exponents: ``Engine.forward_float`` / ``forward_int16`` with ``exps=``.
+    There is no 32-bit fallback at stated exponents, so the model needs its fused engine."""
+    if not hasattr(model, "engine") or getattr(model, "store_intermediates", False):
+        raise ValueError("stated exponents need a model with a fused engine that does not store intermediates")
+    eng = model.engine()
+    run = eng.forward_int16 if x.dtype == torch.int16 else eng.forward_float
+    return run(x, inp_bits, inp_exp, exps=exps)
+
+
+def denoise_fused(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, boundary: str = "float32", exps=None):
     """fxprun.py:63-78 as stft_mag -> model -> mask_istft: noisy audio (B, T) -> (cleaned audio, cleaned magnitude, x, mask),
     the last three (B, n_seg, 257).  On a GPU that is two launches plus the forward.
 
@@ -232,7 +242,11 @@ def denoise_fused(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, bound
     a model that stores intermediates (the op-by-op path, which the default route takes for it) is refused with ValueError.
 
     NOT bit-identical to ``denoise``: two FFT implementations differ in the last bits of |Z|, and the FLOOR quantiser turns a
-    few of those differences into one LSB of the model's input.  The model itself stays exact on the ``x`` returned here."""
+    few of those differences into one LSB of the model's input.  The model itself stays exact on the ``x`` returned here.
+
+    exps: an (n_layers, 5) array of stated exponents (``Engine.calibrate_exps``) runs the model's batch forward at them
+    (``Engine.enqueue(..., exps=)``): every sequence gets the mask ``denoise_clips(..., exps=)`` gives it alone, on the whole
+    chip.  None: the forward on the batch's own exponents, as it always was."""
     from .fxparray import RoundingMode, fxp_from_fp
 
     if boundary not in ("float32", "int16"):
@@ -241,12 +255,14 @@ def denoise_fused(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, bound
         if getattr(model, "store_intermediates", False):
             raise ValueError("a model that stores intermediates runs op by op on FxpArrays: use the float32 boundary")
         x = stft_mag_i16(noisy, inp_bits, inp_exp)
-        mask = model.forward_int16(x, inp_bits, inp_exp)
+        mask = model.forward_int16(x, inp_bits, inp_exp) if exps is None else _forward_at(model, x, inp_bits, inp_exp, exps)
         out_exp = model.out_exp if hasattr(model, "out_exp") else model.engine().out_exp
         cleaned, cleaned_mag = mask_istft_i16(noisy, mask, out_exp, cleaned_mag=True)
         return cleaned, cleaned_mag, x, mask
     x = stft_mag(noisy)
-    if hasattr(model, "forward_float") and not getattr(model, "store_intermediates", False) and _takes(model, inp_bits, inp_exp):
+    if exps is not None:
+        mask = _forward_at(model, x, inp_bits, inp_exp, exps)
+    elif hasattr(model, "forward_float") and not getattr(model, "store_intermediates", False) and _takes(model, inp_bits, inp_exp):
         mask = model.forward_float(x)
     else:
         fx = fxp_from_fp(x, bits=inp_bits, exp=inp_exp, signed=True, round_mode=RoundingMode.FLOOR)
@@ -485,10 +501,11 @@ def score_fused(noisy: torch.Tensor, clean: torch.Tensor, mask, lam: float = 0.0
 
 
 def validate_fused(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, clean: torch.Tensor, lam: float = 0.001,
-                   boundary: str = "float32"):
+                   boundary: str = "float32", exps=None):
     """``validate_batch`` as stft_mag -> model -> score_fused: (loss, si_snr), one value per sequence, without the cleaned audio
     or a magnitude plane ever being stored -- on a GPU three launches plus the forward.  The model's route is chosen as in
-    ``denoise_fused``, ``boundary`` included; the numbers are ``validate_batch``'s up to the rounding of its float32 sums."""
+    ``denoise_fused``, ``boundary`` and ``exps`` included; the numbers are ``validate_batch``'s up to the rounding of its
+    float32 sums.  With ``exps`` they are ``validate_clips(..., exps=)``'s on the same clips: the masks are bit-equal."""
     from .fxparray import RoundingMode, fxp_from_fp
 
     if boundary not in ("float32", "int16"):
@@ -496,11 +513,14 @@ def validate_fused(model, inp_bits: int, inp_exp: int, noisy: torch.Tensor, clea
     if boundary == "int16":
         if getattr(model, "store_intermediates", False):
             raise ValueError("a model that stores intermediates runs op by op on FxpArrays: use the float32 boundary")
-        mask = model.forward_int16(stft_mag_i16(noisy, inp_bits, inp_exp), inp_bits, inp_exp)
+        xi = stft_mag_i16(noisy, inp_bits, inp_exp)
+        mask = model.forward_int16(xi, inp_bits, inp_exp) if exps is None else _forward_at(model, xi, inp_bits, inp_exp, exps)
         out_exp = model.out_exp if hasattr(model, "out_exp") else model.engine().out_exp
         return score_fused(noisy, clean, mask, lam, mask_exp=out_exp)[:2]
     x = stft_mag(noisy)
-    if hasattr(model, "forward_float") and not getattr(model, "store_intermediates", False) and _takes(model, inp_bits, inp_exp):
+    if exps is not None:
+        mask = _forward_at(model, x, inp_bits, inp_exp, exps)
+    elif hasattr(model, "forward_float") and not getattr(model, "store_intermediates", False) and _takes(model, inp_bits, inp_exp):
         mask = model.forward_float(x)
     else:
         fx = fxp_from_fp(x, bits=inp_bits, exp=inp_exp, signed=True, round_mode=RoundingMode.FLOOR)

@@ -1176,9 +1176,12 @@ inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 // behind the int forward's workspace and converts before and after it: k_from_fp / k_to_float (the float-in, float-out forward
 // of fxprun.py:63-88) or k_widen_i16 / k_narrow_i16.  The checks come in this order: arguments, what the model supports, the
 // workspace, the stream extent.
+// pinned: the _at entries (stated exponents).  Their own checks follow the namesake's, all before the device is
+// touched: a null exps, traces, s5fxp_model_exps_check (which refuses a generic model).  A fused model that takes the
+// four-reduction route unpinned (fast_bn_ext false) runs the same pinned plan on the two-plane residual (k_resid16).
 int forward_entry(const s5fxp_model *m, int io, const void *x, int x_bits, int x_exp, int B, int L, void *y, void *workspace,
                   size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces, const s5fxp_forward_opts *opts,
-                  void *stream)
+                  void *stream, bool pinned = false, const int32_t *exps = nullptr)
 {
     if (!m || !x || !y || !workspace || !status || B < 1 || L < 1 || x_bits < 1 || x_bits > (io == IO_I16 ? 16 : 32) ||
         (io == IO_F32 && !shift_ok(x_exp)))
@@ -1192,11 +1195,17 @@ int forward_entry(const s5fxp_model *m, int io, const void *x, int x_bits, int x
     // no workspace can hold it: one forward's size does not fit a size_t (the query's 0), or the G-fold of it does not
     if (!ws_one || ws_one > SIZE_MAX / (size_t)G) return S5FXP_EWORKSPACE;
     if (workspace_bytes < (size_t)G * ws_one) return S5FXP_EWORKSPACE;
+    if (pinned) {
+        if (!stream_extent_ok(m, L) || !exps) return S5FXP_EBADARG;
+        if (traces) return S5FXP_EUNSUPPORTED;
+        if (const int rc = exps_check(m, exps)) return rc;
+    }
     const size_t N = (size_t)B * L;
     if (G > 1) {
         // Grouped call: G independent reference batches of B sequences each.  The fused kernels take them in ONE set of
         // launches (gridDim.y = G) when nothing couples the groups on the host; otherwise one (fused or generic) forward per group.
-        if (m->fast && !traces && !opts->allreduce && fast_bn_ext(m) && stream_extent_ok(m, L))
+        // (a pinned forward takes its groups one by one: its kernels read LayerDyn from memory, a mode no grouped launch has run in)
+        if (m->fast && !traces && !opts->allreduce && fast_bn_ext(m) && stream_extent_ok(m, L) && !pinned)
             return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), G, ws_one, io);
         const size_t esz = io == IO_I16 ? 2 : 4, plane = (size_t)m->n_layers * 2 * B * (m->P ? m->P : 1);
         for (int g = 0; g < G; ++g) {
@@ -1207,13 +1216,13 @@ int forward_entry(const s5fxp_model *m, int io, const void *x, int x_bits, int x
             const int rc = forward_entry(m, io, static_cast<const char *>(x) + g * N * m->d_in * esz, x_bits, x_exp, B, L,
                                          static_cast<char *>(y) + g * N * m->d_out * esz, static_cast<char *>(workspace) + g * ws_one,
                                          ws_one, status + (size_t)g * S5FXP_STATUS_WORDS,
-                                         traces ? traces + (size_t)g * m->n_layers : nullptr, &o, stream);
+                                         traces ? traces + (size_t)g * m->n_layers : nullptr, &o, stream, pinned, exps);
             if (rc) return rc;
         }
         return S5FXP_OK;
     }
     if (!stream_extent_ok(m, L)) return S5FXP_EBADARG;
-    if (m->fast) return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), 1, 0, io);
+    if (m->fast) return forward_fast(m, x, x_bits, x_exp, B, L, y, workspace, status, traces, opts, S(stream), 1, 0, io, pinned ? exps : nullptr);
     if (io == IO_I32)
         return forward_generic(m, static_cast<const int32_t *>(x), x_bits, x_exp, B, L, static_cast<int32_t *>(y), workspace, status,
                                traces, opts, stream);
@@ -1269,6 +1278,28 @@ extern "C" int s5fxp_model_forward_i16(const s5fxp_model *m, const int16_t *x, i
                                        const s5fxp_forward_opts *opts, void *stream)
 {
     return forward_entry(m, IO_I16, x, x_bits, x_exp, B, L, y, workspace, workspace_bytes, status, traces, opts, stream);
+}
+
+// The three forwards at stated exponents (include/s5fxp.h)
+extern "C" int s5fxp_model_forward_at(const s5fxp_model *m, const int32_t *x, int x_bits, int x_exp, int B, int L, int32_t *y,
+                                      void *workspace, size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces,
+                                      const s5fxp_forward_opts *opts, const int32_t *exps, void *stream)
+{
+    return forward_entry(m, IO_I32, x, x_bits, x_exp, B, L, y, workspace, workspace_bytes, status, traces, opts, stream, true, exps);
+}
+
+extern "C" int s5fxp_model_forward_at_f32(const s5fxp_model *m, const float *x, int x_bits, int x_exp, int B, int L, float *y,
+                                          void *workspace, size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces,
+                                          const s5fxp_forward_opts *opts, const int32_t *exps, void *stream)
+{
+    return forward_entry(m, IO_F32, x, x_bits, x_exp, B, L, y, workspace, workspace_bytes, status, traces, opts, stream, true, exps);
+}
+
+extern "C" int s5fxp_model_forward_at_i16(const s5fxp_model *m, const int16_t *x, int x_bits, int x_exp, int B, int L, int16_t *y,
+                                          void *workspace, size_t workspace_bytes, int32_t *status, const s5fxp_layer_trace *traces,
+                                          const s5fxp_forward_opts *opts, const int32_t *exps, void *stream)
+{
+    return forward_entry(m, IO_I16, x, x_bits, x_exp, B, L, y, workspace, workspace_bytes, status, traces, opts, stream, true, exps);
 }
 
 // FxpSequenceLayer.forward for ONE layer of a created model (fxpmodel.py:1110-1161): BatchNorm -> SSM -> ReLU -> out2 ->

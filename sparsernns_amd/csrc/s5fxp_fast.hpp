@@ -3,6 +3,7 @@
 // w8a16 fast path:  encoder -> [BN maxima -> B proj -> recurrence -> C proj -> out2/gate -> residual] x L
 // -> decoder, with int16 activations and int32 recurrence streams.
 #pragma once
+#include "pinned_exps.hpp"
 
 namespace s5 {
 struct StepParams; // s5fxp_step.hpp
@@ -555,6 +556,12 @@ struct FusedForward {
     size_t ws_stride; // bytes between the groups' workspaces (0: this forward's size)
     int io = IO_I32;  // the model boundary (proj_p.hpp): IO_F32 (s5fxp_model_forward_f32) and IO_I16 (s5fxp_model_forward_i16) convert inside
                       // the encoder and the decoder
+    // Stated exponents (s5fxp_model_forward_at): 5 * n_layers checked host values (s5fxp_model_exps_check), or
+    // nullptr.  A pinned forward runs the plan of the multi-rank mode -- every kernel reads its layer's LayerDyn from memory,
+    // none derives it (fold is off) -- without that mode's finalize kernels and exchanges: the head launch (k_clear2_at) has
+    // filled every layer's LayerDyn and exponent status words from `exps` before the encoder starts.
+    const int32_t *exps = nullptr;
+    const bool pinned = exps != nullptr;
 
     const FastModel &F = *m->fast;
     const ModelCfg &cfg = m->cfg;
@@ -562,7 +569,7 @@ struct FusedForward {
     const int64_t N = (int64_t)B * L, NH = N * H;
     const FastShape sh = fast_shape(m->H, m->P);
     const bool exact = (fwd_flags & S5FXP_FWD_EXACT) != 0, defer = (fwd_flags & S5FXP_FWD_DEFER_REDO) && !exact;
-    const s5fxp_allreduce_max_fn allreduce = opts ? opts->allreduce : nullptr;
+    const s5fxp_allreduce_max_fn allreduce = opts && !pinned ? opts->allreduce : nullptr; // (pinned: nothing to exchange)
     const int32_t *state_in = opts ? opts->state_in : nullptr;
     int32_t *state_out = opts ? opts->state_out : nullptr;
     const FastWs w = fast_ws(m, B, L);
@@ -575,7 +582,7 @@ struct FusedForward {
     const bool bn_ext = fast_bn_ext(m);
     // single-rank mode folds the two one-workgroup "finalize" kernels of every layer into the residual pass
     // (mfma_bn.hpp k_resid_minmax16); with a multi-rank hook the maxima are exchanged in between, so they stay
-    const bool fold = bn_ext && !allreduce;
+    const bool fold = bn_ext && !allreduce && !pinned;
     const std::array<LayerPlan, 15> layer = plan_layers(); // validate: 8 + 8 * n_layers <= S5FXP_STATUS_WORDS
     // the layer whose residual pass rides on the decoder (proj_p.hpp k_dec_p<.., RESID>), or -1
     const int dec_resid = bn_ext && fold && !traces && !cfg.no_dec_resid ? m->n_layers - 1 : -1;
@@ -693,6 +700,20 @@ struct FusedForward {
             si.slots[li] = layer[li].P;
             si.stream[li] = layer[li].stream_slots;
         }
+        if (pinned) {
+            // the same words, every layer's LayerDyn and its exponent words (pinned_exps.hpp); the block of extremes stays as it is
+            static_assert(PIN_STATUS_WORDS == S5FXP_STATUS_WORDS, "k_clear2_at builds the status block in LDS");
+            PinHeadArgs pa{};
+            pa.si = si;
+            std::memcpy(pa.pin.e, exps, sizeof(int32_t) * 5 * (size_t)m->n_layers);
+            for (int li = 0; li < m->n_layers; ++li) {
+                pa.bn[li] = make_bn(m->layers[li], li ? m->layers[li - 1].res_bits : m->enc.out_bits, DynExp{0, nullptr}, nullptr);
+                pa.res_exp[li] = m->layers[li].res_exp;
+            }
+            pa.enc_exp = m->enc.out_exp; pa.n_layers = m->n_layers;
+            launch(k_clear2_at, 1, 256, 0, nullptr, nullptr, status, dyn, pa);
+            return;
+        }
         launch(k_clear2, 8, 256, 0, nullptr, nullptr, status, (int)S5FXP_STATUS_WORDS, reinterpret_cast<int32_t *>(dyn),
                (int)(w.dyn_bytes / 4), si, m->n_layers);
     }
@@ -712,7 +733,7 @@ struct FusedForward {
         const size_t smem = 4 * (size_t)sh.hp * 4 + 2 * 64 * 304; // cs128 + bias_eff + byte planes + extremes
         // the extremes of the output (layer 0's BatchNorm operand) are gathered on the way; single-rank mode also
         // lets the last workgroup derive layer 0's BatchNorm exponents (mfma_bn.hpp ResidTail)
-        float *ext0 = bn_ext ? ext(0) : nullptr;
+        float *ext0 = bn_ext && !pinned ? ext(0) : nullptr; // (pinned: nobody derives an exponent from them)
         const int ext_reps = (ext0 && !allreduce) ? EXT_REPS : 1; // the consumer (k_bproj_p's prologue) folds the replicas
         auto kernel = nt_kernel(sh.nt, [&](auto n) { return io == IO_F32 ? k_enc_pf<decltype(n)::value> : io == IO_I16 ? k_enc_ps<decltype(n)::value> : k_enc_p<decltype(n)::value>; });
         launch(kernel, grid_enc, 384, smem, nullptr, nullptr, a, ext0, ext_reps);
@@ -724,6 +745,7 @@ struct FusedForward {
     int bn_exponents(int li, const BnArgs &bn) const
     {
         LayerDyn *d = dyn + li;
+        if (pinned) return S5FXP_OK; // the head launch wrote them
         if (!bn_ext) {
             const unsigned rg = std::min(ew_grid(NH / 4), 2048u);
             return bn_exponent_ops([&](auto op) {
@@ -924,6 +946,7 @@ struct FusedForward {
     int res_exponent(int li) const
     {
         LayerDyn *d = dyn + li;
+        if (pinned) return S5FXP_OK; // LayerDyn::res is the head launch's; the maxima the gate kernel left are not read
         if (allreduce) {
             // ranks may differ in `redo`: move the valid maxima to slots 8..10 before they are exchanged
             hipLaunchKernelGGL(k_select_maxima, dim3(1), dim3(64), 0, st, d);
@@ -949,7 +972,7 @@ struct FusedForward {
         const LayerDev &l = m->layers[li];
         const s5fxp_layer_trace *tr = trace(li);
         if (bn_ext) {
-            const bool more = li + 1 < m->n_layers;
+            const bool more = li + 1 < m->n_layers && !pinned; // (pinned: a storing pass that gathers nothing)
             const int ext_reps = (more && fold) ? EXT_REPS : 1; // the next layer's B projection derives its exponents from the extremes
             if (layer[li].resid_lazy) {
                 // the pass reads U for its extremes and stores nothing; the U plane becomes the layer input, and the plane of
@@ -1021,9 +1044,9 @@ struct FusedForward {
 // io = IO_I16 (s5fxp_model_forward_i16; 2 bytes per element, 2-byte aligned)
 int forward_fast(const s5fxp_model *m, const void *x, int x_bits, int x_exp, int B, int L, void *y, void *workspace,
                  int32_t *status, const s5fxp_layer_trace *traces, const s5fxp_forward_opts *opts, hipStream_t st, int G = 1,
-                 size_t ws_stride = 0, int io = IO_I32)
+                 size_t ws_stride = 0, int io = IO_I32, const int32_t *exps = nullptr)
 {
-    FusedForward f{m, opts, traces, status, st, G, B, L, reinterpret_cast<char *>(workspace), ws_stride, io};
+    FusedForward f{m, opts, traces, status, st, G, B, L, reinterpret_cast<char *>(workspace), ws_stride, io, exps};
     int rc;
     f.clear_status();
     if ((rc = f.encoder(x, x_bits, x_exp))) return rc;

@@ -28,6 +28,7 @@
 // LDS (dynamic, sized by R): [PLA: encoder-input / state planes][PLB: u / out2-input / decoder-input planes]
 //   [h int16 R x H][x1 int16 R x H][z int16 R x H][bq int32 2 x R x P].  R = 32 at H = 192: 120 KB; R = 1: 3.4 KB.
 #pragma once
+#include "pinned_exps.hpp"
 
 namespace s5 {
 
@@ -249,54 +250,8 @@ __device__ __forceinline__ void step_bn_exps(const int16_t *hsrc, int n, int H, 
     }
 }
 
-// ---- stated exponents (the _at entries).  finalize_add_cb / finalize_mul_cb turn ONE float per op, the maximum
-// of the result, into the result exponent eo; every shift follows from eo and the operands' exponents, and the widening of
-// the operands never clips (add_cb_apply).  So an op run at a stated eo is the same statements with eo taken from the caller:
-// the functions below are finalize_*_cb without the float, and without the flags -- s5fxp_model_exps_check has refused on
-// the host every eo that is negative or makes a shift leave 0..31 (-31..31 for an add's post shift).
-constexpr int PIN_MAX_LAYERS = 8; // the exponents travel as kernel arguments (160 bytes), as the trace pointers of the clips do
-
-struct PinExps {
-    int32_t e[5 * PIN_MAX_LAYERS]; // [layer][BN add(-mean), BN mul(invsq_var), BN mul(scale), BN add(bias), residual add]
-};
-
-__device__ __forceinline__ AddCb pinned_add_cb(int eo, int xe, int ye)
-{
-    AddCb p;
-    p.eo = eo;
-    const int ea = xe > ye ? xe : ye;
-    p.shx = ea - xe;
-    p.shy = ea - ye;
-    p.post = eo - ea;
-    return p;
-}
-
-// step_bn_exps at stated exponents: thread 0 fills s_d and the status words, one barrier publishes them (and the layer's
-// s_lut / s_wide stores in front of the call).  A slot whose op the layer lacks is not read; its status word keeps its 0.
-__device__ __forceinline__ void step_bn_pinned(const int32_t *pe, const BnArgs &bn, int he, LayerDyn &s_d, int32_t *st_exps)
-{
-    if (threadIdx.x == 0) {
-        s_d.bn1 = pinned_add_cb(pe[0], he, bn.me);
-        st_exps[0] = pe[0];
-        s_d.e2 = pe[1];
-        s_d.rs2 = pe[0] + bn.ie - pe[1];
-        st_exps[1] = pe[1];
-        int e = pe[1];
-        if (bn.scale) {
-            s_d.e3 = pe[2];
-            s_d.rs3 = e + bn.se - pe[2];
-            st_exps[2] = pe[2];
-            e = pe[2];
-        }
-        if (bn.bias) {
-            s_d.bn4 = pinned_add_cb(pe[3], e, bn.be);
-            st_exps[3] = pe[3];
-            e = pe[3];
-        }
-        s_d.bn_e = e;
-    }
-    __syncthreads();
-}
+// ---- stated exponents (the _at entries): PinExps, pinned_add_cb and step_bn_pinned are in pinned_exps.hpp, which the
+// batch forward's head shares (s5fxp_fast.hpp)
 
 // STEP_THREADS: 512 when the groups are at most one per CU (eight waves shorten one group's chain of stages); 256 or 128
 // when there are more groups than CUs and several fit a CU (the kernel needs up to 256 registers per lane, so a CU holds

@@ -168,6 +168,10 @@ class Engine:
     _IO = {torch.int32: (lib.s5fxp_workspace_bytes, lib.s5fxp_model_forward, "s5fxp_model_forward"),
            torch.float32: (lib.s5fxp_workspace_bytes_f32, lib.s5fxp_model_forward_f32, "s5fxp_model_forward_f32"),
            torch.int16: (lib.s5fxp_workspace_bytes_i16, lib.s5fxp_model_forward_i16, "s5fxp_model_forward_i16")}
+    # ... and their forms at stated exponents (``enqueue(..., exps=)``)
+    _IO_AT = {torch.int32: (lib.s5fxp_model_forward_at, "s5fxp_model_forward_at"),
+              torch.float32: (lib.s5fxp_model_forward_at_f32, "s5fxp_model_forward_at_f32"),
+              torch.int16: (lib.s5fxp_model_forward_at_i16, "s5fxp_model_forward_at_i16")}
 
     def workspace(self, B: int, L: int, lane: int = 0, groups: int = 1, io: torch.dtype = torch.int32) -> torch.Tensor:
         """The lane's workspace for forwards of this shape and I/O type (`io`: torch.int32, float32 or int16)."""
@@ -182,8 +186,13 @@ class Engine:
                 traces: Optional[List[Dict[str, torch.Tensor]]] = None, allreduce: Optional[Callable] = None,
                 scan_events: Optional[list] = None, flags: int = 0, lane: int = 0,
                 state_in: Optional[torch.Tensor] = None, state_out: Optional[torch.Tensor] = None, groups: int = 1,
-                gate_events: Optional[list] = None) -> None:
+                gate_events: Optional[list] = None, exps=None) -> None:
         """Launches one forward on the current stream; nothing is synchronised.
+
+        exps: an (n_layers, 5) array of stated exponents (``exp_max`` has the layout, ``calibrate_exps`` makes one from data)
+        runs ``s5fxp_model_forward_at[_f32|_i16]``: every sequence gets the rows ``clips(..., exps=)`` gives it alone, and with
+        state_in / state_out a signal cut into several calls gives the rows of one call.  No traces; `allreduce` is never
+        called.  None: the forward as it always was.
 
         groups = G > 1: x and y hold G * B sequences, G independent reference batches of B sequences each (what G calls
         would compute: own exponents, status words and carry per group) enqueued as ONE set of kernel launches
@@ -200,6 +209,8 @@ class Engine:
         if x.dtype != y.dtype or x.dtype not in self._IO:
             raise ValueError(f"x and y must both be int32, both float32 or both int16, got {x.dtype} and {y.dtype}")
         io = x.dtype
+        if exps is not None and traces is not None:
+            raise NotImplementedError("a forward at stated exponents takes no traces")
         if groups > 1 and (traces is not None or allreduce is not None):
             raise ValueError("a grouped forward takes neither traces nor a cross-rank hook: run the groups one by one")
         ws = self.workspace(B, L, lane, groups, io)
@@ -246,9 +257,15 @@ class Engine:
                 setattr(opts, name, t.data_ptr())
         self._cb_keep = opts
         _, entry, name = self._IO[io]
+        tail = ()
+        if exps is not None:
+            self.check_exps(exps)        # host only: ValueError / NotImplementedError, as the pool and the clip route raise them
+            entry, name = self._IO_AT[io]
+            eh = self._exps_host(exps)   # the entry reads the host array before it returns: kept alive until then
+            tail = (eh.ctypes.data,)
         check(entry(self._h, x.data_ptr(), x_bits, x_exp, B, L, y.data_ptr(), ws.data_ptr(), ws.numel(),
                     self.lane_status(lane, groups).data_ptr(), C.cast(tr, C.POINTER(LayerTrace)) if tr is not None else None,
-                    C.byref(opts), torch.cuda.current_stream().cuda_stream), name)
+                    C.byref(opts), *tail, torch.cuda.current_stream().cuda_stream), name)
 
     def check_status(self, lane: int = 0) -> np.ndarray:
         """Reads the status words back (one sync) and raises what the reference would have raised.  After a grouped
@@ -295,7 +312,7 @@ class Engine:
                                dtype=torch.int32, device=data.device) for k in TRACE_FIELDS}
 
     def _forward(self, data: torch.Tensor, xb: int, xe: int, out_dtype: torch.dtype, traces: bool, allreduce: Optional[Callable],
-                 check_status: bool):
+                 check_status: bool, exps=None):
         """Returns (y, the traces or None); an empty input gives an empty y without touching the device."""
         B, L = self._rows(data)
         y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=out_dtype, device=data.device)
@@ -305,78 +322,79 @@ class Engine:
         if not check_status or allreduce:
             # self-contained: the gated exact re-run is part of the one enqueue (never the ladder with a multi-rank hook: ranks
             # must enqueue the same work)
-            self.enqueue(data, xb, xe, y, B, L, tr, allreduce)
+            self.enqueue(data, xb, xe, y, B, L, tr, allreduce, exps=exps)
             if check_status:
                 self.check_status()
         else:
             # the status words are read anyway: run optimistically and repeat with the exact kernels if a state left the fast
             # recurrence's range
-            self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, B, L, tr, flags=fl), self.check_status)
+            self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, B, L, tr, flags=fl, exps=exps), self.check_status)
         return y, tr
 
-    def _forward_batches(self, data: torch.Tensor, xb: int, xe: int, out_dtype: torch.dtype, batch: int) -> torch.Tensor:
+    def _forward_batches(self, data: torch.Tensor, xb: int, xe: int, out_dtype: torch.dtype, batch: int, exps=None) -> torch.Tensor:
         if data.ndim != 3 or data.shape[-1] != self.d_in or data.shape[0] % batch:
             raise ValueError(f"expected (G * {batch}, L, {self.d_in}), got {tuple(data.shape)}")
         G, L = data.shape[0] // batch, data.shape[1]
         y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=out_dtype, device=data.device)
         if G * batch * L:
-            self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, batch, L, flags=fl, groups=G), self.check_status)
+            self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, batch, L, flags=fl, groups=G, exps=exps), self.check_status)
         return y
 
-    def _forward_chunk(self, data: torch.Tensor, xb: int, xe: int, out_dtype: torch.dtype, state: Optional[torch.Tensor]):
+    def _forward_chunk(self, data: torch.Tensor, xb: int, xe: int, out_dtype: torch.dtype, state: Optional[torch.Tensor], exps=None):
         B, L = self._rows(data)
         if B * L == 0:
             raise ValueError("empty chunk")
         y = torch.empty(tuple(data.shape[:-1]) + (self.d_out,), dtype=out_dtype, device=data.device)
         new_state = torch.empty((self.n_layers, 2, B, self.P), dtype=torch.int32, device=data.device)
         # `state` is never written: a chunk that comes back with ST_REDO is repeated from it on the next rung
-        self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, B, L, flags=fl, state_in=state, state_out=new_state),
+        self.run_ladder(lambda fl: self.enqueue(data, xb, xe, y, B, L, flags=fl, state_in=state, state_out=new_state, exps=exps),
                         self.check_status)
         return y, new_state
 
     def _fxp(self, y: torch.Tensor) -> FxpArray:
         return FxpArray(y, self.out_bits, self.out_exp, True)
 
-    def forward(self, x: FxpArray, traces: bool = False, allreduce: Optional[Callable] = None, check_status: bool = True):
-        """x: FxpArray (B,L,d_in) or (L,d_in).  Returns an FxpArray (and the traces when asked)."""
-        y, tr = self._forward(x.data.contiguous(), x.bits, x.exp, torch.int32, traces, allreduce, check_status)
+    def forward(self, x: FxpArray, traces: bool = False, allreduce: Optional[Callable] = None, check_status: bool = True, exps=None):
+        """x: FxpArray (B,L,d_in) or (L,d_in).  Returns an FxpArray (and the traces when asked).  exps: stated exponents
+        (``enqueue``) -- here and in every ``forward_*`` method below; None is the forward on its own exponents."""
+        y, tr = self._forward(x.data.contiguous(), x.bits, x.exp, torch.int32, traces, allreduce, check_status, exps)
         return (self._fxp(y), tr) if traces else self._fxp(y)
 
     def forward_float(self, x: torch.Tensor, x_bits: Optional[int] = None, x_exp: Optional[int] = None,
-                      check_status: bool = True, allreduce: Optional[Callable] = None) -> torch.Tensor:
+                      check_status: bool = True, allreduce: Optional[Callable] = None, exps=None) -> torch.Tensor:
         """The reference's validation step (sparseRNNs/fxprun.py:63-88) in one call: x float32 (B,L,d_in) or (L,d_in) ->
         float32 (.., d_out), bit for bit ``forward(fxp_from_fp(x, x_bits, x_exp, FLOOR)).to_float()``.  x_bits / x_exp default
         to the encoder's input configuration.  The conversions run inside the encoder and decoder kernels on the fused path.
         check_status / allreduce as in ``forward``."""
-        return self._forward(*self._boundary_input(x, torch.float32, x_bits, x_exp), torch.float32, False, allreduce, check_status)[0]
+        return self._forward(*self._boundary_input(x, torch.float32, x_bits, x_exp), torch.float32, False, allreduce, check_status, exps)[0]
 
     def forward_batches_float(self, x: torch.Tensor, batch: int, x_bits: Optional[int] = None,
-                              x_exp: Optional[int] = None) -> torch.Tensor:
+                              x_exp: Optional[int] = None, exps=None) -> torch.Tensor:
         """``forward_batches`` float32 in and out: x (G * batch, L, d_in) -> (G * batch, L, d_out), one set of launches."""
-        return self._forward_batches(*self._boundary_input(x, torch.float32, x_bits, x_exp), torch.float32, batch)
+        return self._forward_batches(*self._boundary_input(x, torch.float32, x_bits, x_exp), torch.float32, batch, exps)
 
     def forward_chunk_float(self, x: torch.Tensor, state: Optional[torch.Tensor] = None, x_bits: Optional[int] = None,
-                            x_exp: Optional[int] = None):
+                            x_exp: Optional[int] = None, exps=None):
         """``forward_chunk`` float32 in and out: returns (y float32, new_state); `state` is not modified."""
-        return self._forward_chunk(*self._boundary_input(x, torch.float32, x_bits, x_exp), torch.float32, state)
+        return self._forward_chunk(*self._boundary_input(x, torch.float32, x_bits, x_exp), torch.float32, state, exps)
 
     # -- int16 in, int16 out ----------------------------------------------------------------------
     def forward_int16(self, x, x_bits: Optional[int] = None, x_exp: Optional[int] = None, check_status: bool = True,
-                      allreduce: Optional[Callable] = None) -> torch.Tensor:
+                      allreduce: Optional[Callable] = None, exps=None) -> torch.Tensor:
         """``forward`` with int16 tensors at the model boundary: x int16 (B,L,d_in) or (L,d_in) at (x_bits, x_exp) -- default: the
         encoder's input configuration -- -> int16 (.., d_out) at (out_bits, out_exp), the very integers ``forward`` returns
         for the same values as int32.  On the fused path the encoder reads and the decoder writes int16; a model whose output
         is wider than 16 bits raises NotImplementedError.  check_status / allreduce as in ``forward``."""
-        return self._forward(*self._boundary_input(x, torch.int16, x_bits, x_exp), torch.int16, False, allreduce, check_status)[0]
+        return self._forward(*self._boundary_input(x, torch.int16, x_bits, x_exp), torch.int16, False, allreduce, check_status, exps)[0]
 
-    def forward_batches_int16(self, x, batch: int, x_bits: Optional[int] = None, x_exp: Optional[int] = None) -> torch.Tensor:
+    def forward_batches_int16(self, x, batch: int, x_bits: Optional[int] = None, x_exp: Optional[int] = None, exps=None) -> torch.Tensor:
         """``forward_batches`` int16 in and out: x (G * batch, L, d_in) -> (G * batch, L, d_out), one set of launches."""
-        return self._forward_batches(*self._boundary_input(x, torch.int16, x_bits, x_exp), torch.int16, batch)
+        return self._forward_batches(*self._boundary_input(x, torch.int16, x_bits, x_exp), torch.int16, batch, exps)
 
     def forward_chunk_int16(self, x, state: Optional[torch.Tensor] = None, x_bits: Optional[int] = None,
-                            x_exp: Optional[int] = None):
+                            x_exp: Optional[int] = None, exps=None):
         """``forward_chunk`` int16 in and out: returns (y int16, new_state); `state` is not modified."""
-        return self._forward_chunk(*self._boundary_input(x, torch.int16, x_bits, x_exp), torch.int16, state)
+        return self._forward_chunk(*self._boundary_input(x, torch.int16, x_bits, x_exp), torch.int16, state, exps)
 
     def layer_forward(self, layer: int, x: FxpArray, traces: bool = False):
         """One ``FxpSequenceLayer.forward`` (sparseRNNs/fxpmodel.py:1110-1161) through ``s5fxp_layer_forward``: x is the
@@ -403,23 +421,24 @@ class Engine:
         out = FxpArray(y, lib.s5fxp_model_layer_out_bits(self._h, layer), int(e.item()), True)
         return (out, d) if traces else out
 
-    def forward_batches(self, x: FxpArray, batch: int) -> FxpArray:
+    def forward_batches(self, x: FxpArray, batch: int, exps=None) -> FxpArray:
         """x: (G * batch, L, d_in) -- G independent reference batches of `batch` sequences each (the reference's
         run_validation loop over a loader, sparseRNNs/fxprun.py:53-88, several batches per call).  Returns what G calls of
         ``forward`` would, as one (G * batch, L, d_out) FxpArray, from ONE set of kernel launches."""
-        return self._fxp(self._forward_batches(x.data.contiguous(), x.bits, x.exp, torch.int32, batch))
+        return self._fxp(self._forward_batches(x.data.contiguous(), x.bits, x.exp, torch.int32, batch, exps))
 
     # -- streaming ------------------------------------------------------------------------------
     def zero_state(self, B: int) -> torch.Tensor:
         """The carry a sequence starts with: (n_layers, 2, B, P) int32 zeros (re plane, im plane per layer)."""
         return torch.zeros((self.n_layers, 2, B, self.P), dtype=torch.int32, device=self.device)
 
-    def forward_chunk(self, x: FxpArray, state: Optional[torch.Tensor] = None):
+    def forward_chunk(self, x: FxpArray, state: Optional[torch.Tensor] = None, exps=None):
         """One chunk of a stream: x (B,L,d_in) or (L,d_in); `state` from zero_state() or the previous call (None: zeros).
         Returns (y, new_state).  What comes out is what the reference computes for THIS chunk when its recurrences
         (sparseRNNs/fxpmodel.py:147-172, the carry is an explicit argument of the step function) start from `state`;
-        every chunk is its own compute_best batch.  `state` is not modified."""
-        y, new_state = self._forward_chunk(x.data.contiguous(), x.bits, x.exp, torch.int32, state)
+        every chunk is its own compute_best batch -- or, with `exps`, runs at those stated exponents, and then the chunks of a
+        signal give the rows of one forward of the whole signal however it is cut.  `state` is not modified."""
+        y, new_state = self._forward_chunk(x.data.contiguous(), x.bits, x.exp, torch.int32, state, exps)
         return self._fxp(y), new_state
 
     def stream(self, B: int = 1) -> "StreamingSession":
@@ -1043,8 +1062,8 @@ class InflightRunner:
         self._lane0 = 1
 
     def submit(self, x: torch.Tensor, x_bits: int, x_exp: int, y: torch.Tensor, B: int, L: int, check: bool = True,
-               scan_events: Optional[list] = None, groups: int = 1) -> int:
-        """x and y: both int32, both float32 or both int16, as ``Engine.enqueue`` takes them.  check=False skips the status
+               scan_events: Optional[list] = None, groups: int = 1, exps=None) -> int:
+        """x and y: both int32, both float32 or both int16, as ``Engine.enqueue`` takes them; exps: stated exponents, as there.  check=False skips the status
         check of the lane's previous batch (only sound when every batch of the lane is the same input, as in bench.py: the
         last check then speaks for all)."""
         lane = self._next
@@ -1056,13 +1075,13 @@ class InflightRunner:
         level = self.engine.level
         with torch.cuda.stream(s):
             self.engine.enqueue(x, x_bits, x_exp, y, B, L, flags=Engine.LEVEL_FLAGS[level], lane=self._lane0 + lane,
-                                scan_events=scan_events, groups=groups)
+                                scan_events=scan_events, groups=groups, exps=exps)
         # the tensors were allocated on another stream: tell the caching allocator that this lane's stream uses them, so
         # that dropping the previous job's references below (check=False) cannot hand their memory out while kernels of
         # this stream still read or write it
         x.record_stream(s)
         y.record_stream(s)
-        self._pending[lane] = (x, x_bits, x_exp, y, B, L, level, groups)
+        self._pending[lane] = (x, x_bits, x_exp, y, B, L, level, groups, exps)
         return lane
 
     def _finish(self, lane: int) -> None:
@@ -1072,12 +1091,13 @@ class InflightRunner:
         self._pending[lane] = None
         s = self.streams[lane]
         s.synchronize()
-        x, x_bits, x_exp, y, B, L, level, groups = job
+        x, x_bits, x_exp, y, B, L, level, groups, exps = job
         st = self.engine.check_status(self._lane0 + lane)
         while (st[0] & _lib.ST_REDO) and level < 2:   # climb the ladder: pair -> quad -> exact
             level = self.engine.note_redo(level)
             with torch.cuda.stream(s):
-                self.engine.enqueue(x, x_bits, x_exp, y, B, L, flags=Engine.LEVEL_FLAGS[level], lane=self._lane0 + lane, groups=groups)
+                self.engine.enqueue(x, x_bits, x_exp, y, B, L, flags=Engine.LEVEL_FLAGS[level], lane=self._lane0 + lane, groups=groups,
+                                    exps=exps)
             s.synchronize()
             st = self.engine.check_status(self._lane0 + lane)
 
