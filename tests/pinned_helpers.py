@@ -1,5 +1,6 @@
-"""Helpers of tests/test_pinned_exps.py: the NumPy oracle (oracle/fxp_oracle.py) run at STATED exponents through its
-MAX_EXCHANGE hook, and a host restatement of which exponent sets leave every static shift inside 0..31.
+"""Helpers of tests/test_pinned_exps.py, tests/test_forward_at.py and tests/test_pinned_box.py: the NumPy oracle
+(oracle/fxp_oracle.py) run at STATED exponents through its MAX_EXCHANGE hook, a host restatement of which exponent sets leave
+every static shift inside 0..31, and of which arm of the B projection's row chain a set puts on a layer.
 
 The hook sees every compute_best op's float32 maxima in the order the model runs them: per layer BatchNorm add(-mean),
 mul(invsq_var), [mul(scale)], [add(bias)], then the residual add.  Forcing op k's maximum to a float whose intbits is
@@ -95,6 +96,16 @@ def oracle_run(om, clip, bits, exp, exps=None, chunks=None, state=None):
     return y, carry, (h.natural if exps is None else [np.asarray(exps)] * len(h.natural))
 
 
+def forced_run(om, clip, bits, exp, exps):
+    """oracle_run for one chunk from a zero carry, with what tests/test_pinned_box.py asks of the pool beside it: returns
+    (y, carry out, the (n_layers, 5) exponents every op WOULD have chosen at that point of the forced run)."""
+    st = om.zero_state((1,))
+    with hooked(om, exps) as h:
+        y = om(O.Fx(clip[None], bits, exp, True), state=st).data[0]
+    carry = np.stack([np.stack([s[0][0], s[1][0]]) for s in st]).astype(np.int32)
+    return y, carry, h.natural[0]
+
+
 def shifts_ok(om, exps) -> bool:
     """The host rule of s5fxp_model_exps_check for the static shifts, restated from the ops' definitions: an add's two operand
     shifts and its result shift (fxparray.py:420-448), a mul's right shift (fxparray.py:619-621), the change_cfg to the SSM
@@ -129,6 +140,63 @@ def shifts_ok(om, exps) -> bool:
     if conv and abs(int(he) - d["inp_exp"]) > 31:
         return False
     return 0 <= (d["inp_exp"] if conv else he) + d["w_exp"] - d["out_exp"] <= 31
+
+
+ROW_GENERIC, ROW_PACKED, ROW_SHIFTED = 0, 1, 2
+ARM_NAMES = {ROW_GENERIC: "ROW_GENERIC", ROW_PACKED: "ROW_PACKED", ROW_SHIFTED: "ROW_SHIFTED"}
+
+
+def row_arms(om, exps) -> list:
+    """Per layer the arm of mfma_bn.hpp bn16_row_arm at the stated exponents, None for a layer with a BatchNorm scale or bias
+    (no row chain).  The rule restated: the packed forms need every width at 16 bits, the input shift shx1 <= 14, no left
+    shift of the sum (l1 == 0) and the change_cfg to the SSM input within cl <= 14 / cr <= 15; PACKED is r1 == 0, SHIFTED
+    r1 >= 1, everything else GENERIC.  shx1, l1 and r1 are the first add's shifts (pinned_exps.hpp pinned_add_cb: the layer
+    input's exponent against the mean's, then the stated result exponent against their maximum), cl / cr the distance from the
+    second op's exponent to the SSM input's."""
+    e = np.asarray(exps)
+    xb, xe = om.encoder.qc["out_bits"], om.encoder.qc["out_exp"]
+    arms = []
+    for i, l in enumerate(om.layers):
+        n, u = l.norm, l.mixer.qc["activations"]["u"]
+        if n.scale is not None or n.bias is not None:
+            arms.append(None)
+        else:
+            mb, ib = n.minus_mean.bits, n.invsq_var.bits
+            b1 = max(xb, mb)
+            b2 = max(b1, ib)
+            ea = max(xe, n.minus_mean.exp)
+            shx1, post, de = ea - xe, int(e[i, 0]) - ea, u["exp"] - int(e[i, 1])
+            l1, r1, cl, cr = max(post, 0), max(-post, 0), max(de, 0), max(-de, 0)
+            w16 = ((xb == 16 or (shx1 == 0 and xb < 16)) and mb <= 16 and ib <= 16 and b1 == 16 and b2 == 16 and
+                   min(b2, u["bits"]) == 16 and shx1 <= 14 and l1 == 0 and cl <= 14 and cr <= 15)
+            arms.append(ROW_GENERIC if not w16 else ROW_PACKED if r1 == 0 else ROW_SHIFTED)
+        xb, xe = l.qc["multgate"]["res_bits"], int(e[i, 4])
+    return arms
+
+
+def add_posts(om, exps) -> list:
+    """The result shift (pinned_exps.hpp pinned_add_cb: post = eo - max(xe, ye)) of every add at the stated exponents, in model
+    order: per layer the add of -mean, the add of the bias where the layer has one, the residual add."""
+    e = np.asarray(exps)
+    out, he = [], om.encoder.qc["out_exp"]
+    for i, l in enumerate(om.layers):
+        n = l.norm
+        out.append(int(e[i, 0]) - max(he, n.minus_mean.exp))
+        if n.bias is not None:
+            out.append(int(e[i, 3]) - max(int(e[i, 2 if n.scale is not None else 1]), n.bias.exp))
+        out.append(int(e[i, 4]) - max(l.qc["multgate"]["res_exp"], he))
+        he = int(e[i, 4])
+    return out
+
+
+def corner(om, base, delta: int) -> np.ndarray:
+    """`base` moved by `delta` (+1 / -1) per op, again and again, until no op can move: shifted()'s greedy rule to its end."""
+    e = np.asarray(base, dtype=np.int32)
+    while True:
+        nxt = shifted(om, e, delta)
+        if np.array_equal(nxt, e):
+            return e
+        e = nxt
 
 
 def shifted(om, base, delta: int) -> np.ndarray:
